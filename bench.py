@@ -17,10 +17,15 @@ One JSON line is printed by rank 0 (contract in the task statement), including
                   launch stream inside the timed region (ops.KernelTimer);
   train_step   -- algorithmic FLOP per step (formula + measured reflect-ray count M) and the same per-kernel
                   figures for the backward sweep and the weight-gradient kernels;
+and, with --full only (a plain run sets up, warms up, times --steps steps and prints the line):
   cpu_baseline -- the CPU oracle (oracle/cpu_ref.py, a port of the reference's PyTorch op sequence: get_outputs in
                   training mode + loss + autograd backward) timed on the host cores on a bounded sample;
   eval_level   -- (N = 1) BASELINE configs[1]: 4096 rays x 128 samples fused forward + composite of one level, with
-                  its own roofline and CPU baseline (the round-1 headline, kept for continuity).
+                  its own roofline and CPU baseline (the round-1 headline, kept for continuity);
+  eval_image, train_step_configs2, train_step_bf16_sweeps, train_step_bf16x6_sweeps, train_step_weight_grad_groups2
+               -- (N = 1, f32) the other secondary legs, each timed in runs of its own.
+--dump-outputs DIR writes what the timed path computed in its last step (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 A stalled or failed step exits NON-ZERO (watchdog: rc 3, exception: rc 4 after printing the error to stderr).
 
 Launching: `python bench.py --gpus N` is enough at every N.  With N > 1 and no WORLD_SIZE in the environment the
@@ -123,10 +128,24 @@ def parse():
     ap.add_argument("--wgrad-groups", type=int, default=1, choices=[1, 2],
                     help="2: reduce the reflect branch's weight gradients before the primary levels' backward sweeps and release its "
                          "buffers (opt-in memory bound, model.weight_grad_groups)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (eval_level, configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baselines and, for the training step "
+                         "at N = 1 in f32, the secondary legs (eval level, eval image, configs[2], the bf16 / bf16x6 / "
+                         "weight_grad_groups=2 steps). Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs")
     ap.add_argument("--cpu-rays", type=int, default=0, help="rays of the bounded CPU-baseline sample (0 = auto)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32, float64 where the array is; at most 64 MiB in all, a fixed seeded sample beyond that). "
+                         "train: loss, updated parameters (param.<name>), their gradients (grad.<name>); level: the field's "
+                         "per-sample outputs and the composite; get_outputs: the outputs dict")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in ("train", "level", "get_outputs"):
+        ap.error("--dump-outputs: the %s workload has no timed steps to dump" % args.workload)
+    return args
 
 
 def host_threads():
@@ -244,6 +263,35 @@ def timed_region(dist, share, dev, steps, fn):
     return elapsed
 
 
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as out_dir/<name>.npy, float64 tensors as float64 and everything else
+    as float32.  Over DUMP_BUDGET_BYTES in all, every array is cut to its share of the budget by a sample of flat
+    indices drawn from a generator seeded with its name and size: the same positions in every run of the same
+    arguments.  Returns the list of names written."""
+    import zlib
+
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64) if t.dtype == torch.float64 else t.to(torch.float32)
+        host[name] = t.cpu().numpy().reshape(t.shape)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = int(a.size * DUMP_BUDGET_BYTES / total)
+            if keep < a.size:
+                rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, a.size)).encode()))
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(host)
+
+
 def newest_profile_traffic(kernel_name, rays, samples):
     """HBM bytes per launch of `kernel_name` from the newest profiles/*_summary.json taken on this workload size."""
     traffic = None
@@ -264,8 +312,9 @@ TRAFFIC_NOTE = ("HBM bytes/launch = 2*FETCH_SIZE + WRITE_SIZE (gfx950 correction
                 "tools/profile_round.sh; newest profiles/*_summary.json taken on this kernel and workload size (null if none)")
 
 
-def run_train(pkg, args, dev, rank, world, dist, share, samples, steps, warmup, dog, time_kernels=True):
-    """`steps` timed optimisation steps on this rank's rays; returns the train-step record (rank-0 relevant)."""
+def run_train(pkg, args, dev, rank, world, dist, share, samples, steps, warmup, dog, time_kernels=True, dump_dir=None):
+    """`steps` timed optimisation steps on this rank's rays; returns the train-step record (rank-0 relevant).
+    dump_dir: write the last step's loss, updated parameters and their gradients there (dump_outputs)."""
     from reflect_sampling_nerf_amd import ops
     from reflect_sampling_nerf_amd.parallel import FlatGradAllReduce, train_step
     from reflect_sampling_nerf_amd.synthetic import synthetic_rays
@@ -316,6 +365,13 @@ def run_train(pkg, args, dev, rank, world, dist, share, samples, steps, warmup, 
     finally:
         ops.TIMER = None
     state["M"] = int(m_dev.item())
+    if dump_dir:
+        arrays = {"loss": state["loss"]}
+        for name, p in model.field.named_parameters():
+            arrays["param." + name] = p
+            if p.grad is not None:
+                arrays["grad." + name] = p.grad
+        dump_outputs(dump_dir, arrays)
     macs = algorithmic_macs(args.layers, args.width)
     rec = {"value": world * R * steps / elapsed, "unit": "rays/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps,
            "warmup": warmup, "n_gpus": world, "loss": float(state["loss"]),
@@ -399,8 +455,9 @@ def run_train(pkg, args, dev, rank, world, dist, share, samples, steps, warmup, 
     return rec
 
 
-def run_level(pkg, args, dev, steps, warmup, dog):
-    """BASELINE configs[1] (secondary at N = 1): fused forward + composite of one sampling level, eval mode."""
+def run_level(pkg, args, dev, steps, warmup, dog, dump_dir=None):
+    """BASELINE configs[1] (secondary at N = 1): fused forward + composite of one sampling level, eval mode.
+    dump_dir: write the last step's per-sample field outputs and composite there (dump_outputs)."""
     from reflect_sampling_nerf_amd import ops
     from reflect_sampling_nerf_amd._abi import RSN_SPACING_UNIFORM
     from reflect_sampling_nerf_amd.synthetic import synthetic_rays
@@ -418,11 +475,14 @@ def run_level(pkg, args, dev, steps, warmup, dog):
     nears, fars = torch.full((R,), 2.0, device=dev), torch.full((R,), 6.0, device=dev)
     fld.packed_weights()
     flags = ops.RSN_COMP_EVAL | ops.RSN_COMP_CLIP_RGB
+    last = {}
 
     def step(_i=None):
         sb, eb = ops.sample_spaced(R, None, S, RSN_SPACING_UNIFORM, 1.0, nears, fars, None)
         lv = fld.evaluate_frustums(o, d, pa, eb, full=True)
-        ops.composite(R, None, S, 1, flags, lv["sigma"], eb, lv["color"])
+        comp = ops.composite(R, None, S, 1, flags, lv["sigma"], eb, lv["color"])
+        if dump_dir:
+            last["level"], last["composite"] = lv, comp
         dog.beat()
 
     for _ in range(warmup):
@@ -433,6 +493,9 @@ def run_level(pkg, args, dev, steps, warmup, dog):
         elapsed = timed_region(None, False, dev, steps, step)
     finally:
         ops.TIMER = None
+    if dump_dir:
+        dump_outputs(dump_dir, {**{"level." + k: v for k, v in last["level"].items() if torch.is_tensor(v)},
+                                **{"composite." + k: v for k, v in last["composite"].items()}})
     t = timer.totals()["field_forward_eval"]
     kms = t["ms"] / t["calls"]
     macs = algorithmic_macs(args.layers, args.width)
@@ -462,7 +525,7 @@ def run_level(pkg, args, dev, steps, warmup, dog):
     }
 
 
-def run_get_outputs(pkg, args, dev, steps, warmup, dog):
+def run_get_outputs(pkg, args, dev, steps, warmup, dog, dump_dir=None):
     from reflect_sampling_nerf_amd.synthetic import synthetic_rays
 
     R, S = args.rays, args.samples
@@ -486,6 +549,8 @@ def run_get_outputs(pkg, args, dev, steps, warmup, dog):
     for _ in range(warmup):
         step()
     elapsed = timed_region(None, False, dev, steps, step)
+    if dump_dir:
+        dump_outputs(dump_dir, {k: v for k, v in state["out"].items() if torch.is_tensor(v)})
     return {"workload": "full eval get_outputs: %d rays x (%d coarse + %d fine + reflect 64 + 64), %dx%d field, M/R=%.2f"
                         % (R, S, S, args.layers, args.width, float(state["out"]["mask"].float().mean())),
             "value": R * steps / elapsed, "unit": "rays/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps}
@@ -672,7 +737,8 @@ def main():
     line = None
     try:
         if args.workload == "train":
-            rec = run_train(pkg, args, dev, rank, world, dist, share, samples, args.steps, args.warmup, dog)
+            rec = run_train(pkg, args, dev, rank, world, dist, share, samples, args.steps, args.warmup, dog,
+                            dump_dir=args.dump_outputs if rank == 0 else None)
             if rank == 0:
                 fwd = rec["kernels"]["forward"]
                 line = {
@@ -706,7 +772,7 @@ def main():
                                                        "other_ms_per_step", "loss", "reflect_ray_fraction",
                                                        "host_syncs_in_reducer", "peak_device_memory_gb", "ray_chunk", "launch_kinds")},
                 }
-            if world == 1 and not args.no_secondary and args.mma == "f32":
+            if args.full and world == 1 and not args.no_secondary and args.mma == "f32":
                 # secondary legs (untimed for the headline): configs[1] eval level and the configs[2] training shape
                 lv = run_level(pkg, args, dev, args.steps, args.warmup, dog)
                 c2 = run_train(pkg, args, dev, rank, world, None, share, (64, 128, 64, 64), min(args.steps, 10),
@@ -754,7 +820,7 @@ def main():
                     "workload": "BASELINE configs[2]: %d rays x (64 coarse + 128 fine) + reflect 64 + 64, forward + backward "
                                 "(+ loss + RAdam)" % R,
                     **{k: c2[k] for k in ("value", "unit", "ms_per_step", "steps", "reflect_ray_fraction")}}
-            if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
                 line["cpu_baseline"] = cpu_baseline_train(args, samples)
                 dog.beat()
                 if "eval_level" in line:
@@ -765,8 +831,8 @@ def main():
                 rec = run_eval_image(pkg, args, dev, dog)
                 rec["ms_per_step"] = rec["chunks"]["1024"]["ms_per_image"]
             else:
-                rec = run_level(pkg, args, dev, args.steps, args.warmup, dog) if args.workload == "level" else \
-                    run_get_outputs(pkg, args, dev, args.steps, args.warmup, dog)
+                rec = run_level(pkg, args, dev, args.steps, args.warmup, dog, args.dump_outputs) if args.workload == "level" \
+                    else run_get_outputs(pkg, args, dev, args.steps, args.warmup, dog, args.dump_outputs)
             line = {
                 "metric": "rays/sec (%s) at %d rays x %d samples, 1 MI355X" %
                           ("eval forward + composite of one level" if args.workload == "level" else
@@ -784,7 +850,7 @@ def main():
                 line["roofline"] = rec["roofline"]
             if "chunks" in rec:
                 line["eval_image"] = rec
-            if args.workload == "level" and not args.no_cpu_baseline:
+            if args.full and args.workload == "level" and not args.no_cpu_baseline:
                 line["cpu_baseline"] = cpu_baseline_level(args)
     except BaseException:
         sys.stderr.write(json.dumps({"error": "bench.py failed on rank %d" % rank, "traceback": traceback.format_exc()}) + "\n")

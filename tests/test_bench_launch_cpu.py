@@ -149,3 +149,87 @@ def test_launcher_counts_gpus_without_initialising_hip(monkeypatch):
 
     src = inspect.getsource(bench.main)
     assert "torch.cuda.device_count" not in src.split("self_launch(args.gpus")[0]
+
+
+def test_dump_outputs_dtypes_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 stays float64, everything else is written as float32; over the byte budget every array is
+    cut to its share by a sample whose positions are the same from run to run."""
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    arrays = {"loss": torch.tensor(1.5), "w": torch.arange(12.0).reshape(3, 4), "f64": torch.ones(5, dtype=torch.float64),
+              "mask": torch.tensor([True, False]), "bf": torch.ones(4, dtype=torch.bfloat16)}
+    names = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert names == sorted(arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["f64"].dtype == np.float64 and all(got[n].dtype == np.float32 for n in names if n != "f64")
+    assert got["w"].shape == (3, 4) and np.array_equal(got["w"], np.arange(12.0, dtype=np.float32).reshape(3, 4))
+    assert got["loss"].shape == () and float(got["loss"]) == 1.5 and got["mask"].tolist() == [1.0, 0.0]
+    big = {"x": torch.randn(10000, generator=torch.Generator().manual_seed(0)), "y": torch.arange(3000.0)}
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20000)
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    total = 0
+    for n in big:
+        b, c = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        assert np.array_equal(b, c) and 0 < b.size < big[n].numel()
+        assert np.isin(b, big[n].numpy()).all()
+        total += b.nbytes
+    assert total <= 20000
+
+
+def _fake_train_record(steps):
+    kern = {q: 1.0 for q in ("achieved_tflops", "frac_of_fp32_mfma_peak", "avg_launch_ms", "launches_per_step",
+                             "algorithmic_flop_per_step", "ms_per_step", "frac_of_bf16_mfma_peak",
+                             "algorithmic_hbm_bytes_per_step", "achieved_hbm_tbps", "frac_of_hbm_peak")}
+    kern["kernel"] = "k"
+    return {"value": 1.0, "unit": "rays/s", "ms_per_step": 2.0, "steps": steps, "loss": 0.5, "reflect_ray_fraction": 0.5,
+            "host_syncs_in_reducer": 0, "peak_device_memory_gb": 1.0, "ray_chunk": None, "launch_kinds": {},
+            "kernels": {k: dict(kern) for k in ("forward", "backward", "wgrad")}, "algorithmic_flop_per_step": 1.0,
+            "flop_formula": "", "end_to_end_tflops": 1.0, "end_to_end_frac_of_fp32_mfma_peak": 0.1, "other_ms_per_step": 0.0}
+
+
+def test_plain_run_times_only_the_headline_and_full_adds_the_rest(monkeypatch, capsys):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline training step once, with exactly N timed
+    steps, and prints the line; the CPU baselines and the secondary legs run only under --full (GPU calls mocked)."""
+    import json
+
+    import torch
+
+    import reflect_sampling_nerf_amd as pkg
+
+    bench = _load_bench()
+    for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RSN_BENCH_FORCE_COLLECTIVE", "RSN_BENCH_SHARE_GPU"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda i: None)
+    monkeypatch.setattr(pkg, "load_library", lambda: None)
+    calls = []
+
+    def fake_train(pkg_, args, dev, rank, world, dist, share, samples, steps, warmup, dog, time_kernels=True, dump_dir=None):
+        calls.append(("train", args.mma, steps, warmup, dump_dir))
+        return _fake_train_record(steps)
+
+    monkeypatch.setattr(bench, "run_train", fake_train)
+    monkeypatch.setattr(bench, "run_level", lambda *a, **k: calls.append(("level",)) or {"value": 1.0})
+    monkeypatch.setattr(bench, "run_eval_image", lambda *a, **k: calls.append(("eval_image",)) or {"value": 1.0})
+    monkeypatch.setattr(bench, "cpu_baseline_train", lambda *a, **k: calls.append(("cpu_train",)) or {"value": 1.0})
+    monkeypatch.setattr(bench, "cpu_baseline_level", lambda *a, **k: calls.append(("cpu_level",)) or {"value": 1.0})
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == [("train", "f32", 7, 3, None)]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 7 and line["ms_per_step"] == 2.0 and line["dtype"] == "f32" and "cpu_baseline" not in line
+
+    calls.clear()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3", "--full"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    kinds = [c[0] for c in calls]
+    assert calls[0] == ("train", "f32", 7, 3, None) and kinds.count("train") == 5
+    assert {"level", "eval_image", "cpu_train", "cpu_level"} <= set(kinds)
+    assert {"cpu_baseline", "eval_level", "eval_image", "train_step_configs2"} <= set(line)

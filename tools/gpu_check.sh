@@ -19,7 +19,7 @@ export RSN_BENCH_SHARE_GPU=1
 run 300 ddp_equiv python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 tools/ddp_equiv.py --json $OUT/ddp_equiv.json
 unset RSN_BENCH_SHARE_GPU
 run 900 pytest_gpu python -m pytest tests -m gpu -q -s
-run 300 bench_default python bench.py
+run 300 bench_default python bench.py --full
 export RSN_BENCH_SHARE_GPU=1
 run 300 bench_n2_shared python bench.py --gpus 2 --steps 5 --warmup 2   # self-launching: no torchrun on the command line
 unset RSN_BENCH_SHARE_GPU
