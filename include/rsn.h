@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RSN_ABI_VERSION 16
+#define RSN_ABI_VERSION 17
 #define RSN_MAX_TRUNK_LAYERS 16
 #define RSN_NUM_FREQS 16   /* NeRFEncoding(num_frequencies=16), reflect_sampling_nerf_model.py:98-100 */
 #define RSN_ENC_DIM 99     /* 3*16*2 + 3 */
@@ -571,6 +571,45 @@ int rsn_loss_scale_grads(int32_t n_rays, int32_t s_coarse, int32_t s_fine, const
 int rsn_radam_step(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                    float* const* exp_avg_sq, const int32_t* sizes, int32_t step, float lr, float beta1, float beta2,
                    float eps, void* stream);
+
+
+/* ---- standalone data path (ABI 17): training batches and rendered views from a device-resident posed image set, and the
+ * SSIM metric (reference reflect_sampling_nerf_datamanager.py:49-58 next_train, reflect_sampling_nerf_model.py:468-479).
+ *
+ * Rays: nerfstudio 0.3 Cameras._generate_rays_from_coords, perspective camera.  For pixel (y, x) of a camera with pose
+ * c2w [3,4] (row-major) and intrinsics fx, fy, cx, cy: camera-space direction v = ((x+.5-cx)/fx, -(y+.5-cy)/fy, -1);
+ * directions = normalize(c2w[:, :3] v); origins = c2w[:, 3]; pixel_area = |d - d_x1| * |d - d_y1| with d_x1 / d_y1 the
+ * directions of the x+1 / y+1 neighbours formed the same way (the differences are evaluated in a cancellation-free
+ * rearrangement, so pixel_area is accurate to fp32 rounding rather than to the ~1/f-amplified error of the literal
+ * subtraction).  Both kernels below run the same device function: equal (i, y, x) give bit-identical rays. */
+
+/* rsn_sample_camera_rays: one training batch of n_rays rays, uniform over all N*H*W pixels with replacement (nerfstudio's
+ * PixelSampler).  images: uint8 [N,H,W,4] RGBA (alpha 255 for RGB sources), c2w: fp32 [N,3,4]; N*H*W < 2^32.
+ * Pixel of ray r (bit-exact recipe):
+ *   (u, -, -, -) = Philox4x32-10(counter = (step, r, 0, 0), key = (seed, rank))   (Random123's philox4x32, 10 rounds)
+ *   flat = (uint32)(((uint64)u * (N*H*W)) >> 32);  i = flat / (H*W);  y = (flat % (H*W)) / W;  x = flat % W
+ * Outputs: origins / directions / rgb [R,3], pixel_area [R,1], indices int32 [R,3] = (i, y, x) (nerfstudio's
+ * batch["indices"]); rgb = c/255 * a/255 + (1 - a/255) per channel in fp32 (white background, as get_loss_dict blends). */
+int rsn_sample_camera_rays(int32_t n_images, int32_t height, int32_t width, const uint8_t* images, const float* c2w,
+                           float fx, float fy, float cx, float cy, int32_t n_rays, uint32_t seed, uint32_t rank,
+                           uint32_t step, float* origins, float* directions, float* pixel_area, float* rgb,
+                           int32_t* indices, void* stream);
+
+/* rsn_camera_rays_image: the rays of every pixel of ONE camera (c2w: [3,4]), row-major [H*W]: origins / directions
+ * [H*W,3], pixel_area [H*W,1]. */
+int rsn_camera_rays_image(int32_t height, int32_t width, const float* c2w, float fx, float fy, float cx, float cy,
+                          float* origins, float* directions, float* pixel_area, void* stream);
+
+/* rsn_ssim: torchmetrics structural_similarity_index_measure(pred, target) with the defaults the reference uses
+ * (model.py:131,470) of two fp32 [H,W,3] images (H, W >= 11), written to out[0] (device).  11-tap Gaussian, sigma 1.5
+ * (taps exp(-k^2/(2 sigma^2)), k = -5..5, normalised; 2-D window = their outer product); L = *data_range (device: the
+ * caller's max(max(pred)-min(pred), max(target)-min(target))); C1 = (0.01 L)^2, C2 = (0.03 L)^2; per window the means,
+ * variances E[x^2]-mu^2 and covariance; the SSIM map averaged over the 3 channels and the (H-10) x (W-10) positions whose
+ * window lies inside the image (torchmetrics' reflect-pad-then-crop-by-5 keeps exactly those).  Per-workgroup partial
+ * sums in `workspace` (rsn_ssim_workspace_bytes, 8-byte aligned) are added in a fixed order: bit-reproducible. */
+size_t rsn_ssim_workspace_bytes(int32_t height, int32_t width);
+int rsn_ssim(int32_t height, int32_t width, const float* pred, const float* target, const float* data_range,
+             void* workspace, size_t workspace_bytes, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ import os
 
 from ._build import LIB_PATH
 
-RSN_ABI_VERSION = 16
+RSN_ABI_VERSION = 17
 RSN_ABI_DIAG_FLAG = 0x10000  # rsn_abi_version() of a -DRSN_DIAG_BUILD library (csrc/rsn_common.h)
 RSN_MAX_TRUNK_LAYERS = 16
 RSN_NUM_FREQS = 16
@@ -187,6 +187,13 @@ _SIGNATURES = {
     "rsn_reflect_combine": (C.c_int, [C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]),
     "rsn_train_saved_layout": (C.c_int, [C.POINTER(FieldDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rsn_sample_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, _fp, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _fp,
+                                         C.c_void_p, C.c_void_p]),
+    "rsn_camera_rays_image": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp,
+                                        C.c_void_p]),
+    "rsn_ssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rsn_ssim": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
