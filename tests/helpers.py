@@ -1,4 +1,5 @@
 """Shared helpers for the tests (fixture loading, tolerant comparisons)."""
+import contextlib
 import json
 import os
 
@@ -38,3 +39,79 @@ def model_spec_from_meta(meta):
 
 def max_abs(a, b):
     return float((a.double() - b.double()).abs().max()) if a.numel() else 0.0
+
+
+# ---------------------------------------------------------------------------------------------- persistent-kernel coverage
+@contextlib.contextmanager
+def default_dtype(dt):
+    """Run the oracle at another precision (oracle/cpu_ref.py builds its constants in torch's default dtype)."""
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(dt)
+    try:
+        yield
+    finally:
+        torch.set_default_dtype(old)
+
+
+def multitile_geometry(label, job_points, tile, cus, min_per_wg=3, fixed_size=False):
+    """Tile space of one persistent field launch: every job's points in `tile`-point tiles, grid = min(tiles, cus) (the
+    launchers' rule).  Asserts that every workgroup walks at least `min_per_wg` tiles, that each job ends in a ragged tile,
+    that the tile count is not a multiple of the grid and that job boundaries fall inside a round after the first.
+    fixed_size: a BASELINE workload's size, not chosen by the test -- only the tiles-per-workgroup floor is asserted.
+    -> (tiles, grid, first tile of each job)."""
+    tiles, base = 0, []
+    for p in job_points:
+        base.append(tiles)
+        tiles += -(-p // tile)
+    grid = min(tiles, cus)
+    per = tiles / grid
+    print(f"[{label}] {tiles} tiles of {tile} points on {grid} workgroups: {per:.2f} tiles per workgroup")
+    assert tiles // grid >= min_per_wg, f"{label}: {per:.2f} tiles per workgroup, the test needs >= {min_per_wg}"
+    if fixed_size:
+        return tiles, grid, base
+    assert all(p % tile for p in job_points), f"{label}: every job must end in a ragged tile ({job_points}, tile {tile})"
+    assert tiles % grid, f"{label}: {tiles} tiles are a multiple of the grid ({grid})"
+    for b in base[1:]:
+        assert b > grid and b % grid, f"{label}: job boundary at tile {b} is not inside a later round ({grid} workgroups)"
+    return tiles, grid, base
+
+
+def locate(err, tile, grid, base_tile=0):
+    """err: per-point errors [N] of a job whose first tile is `base_tile` -> (worst, point, tile, loop iteration, worst of
+    iteration 0, worst of iterations >= 1); `tile // grid` is the iteration of the persistent loop that wrote the point."""
+    err = err.double().reshape(-1).cpu()
+    it = (base_tile + torch.arange(err.numel()) // tile) // grid
+    i = int(err.argmax())
+    t = base_tile + i // tile
+    e0 = float(err[it == 0].max()) if bool((it == 0).any()) else 0.0
+    e1 = float(err[it >= 1].max()) if bool((it >= 1).any()) else 0.0
+    return float(err[i]), i, t, t // grid, e0, e1
+
+
+def check_points(label, name, err, bound, tile, grid, base_tile=0):
+    """Assert max(err) <= bound for per-point errors [N]; print and report the worst point's tile and loop iteration."""
+    e, i, t, it, e0, e1 = locate(err, tile, grid, base_tile)
+    print(f"[{label}] {name}: worst {e:.3e} (bound {bound:.1e}) at point {i}, tile {t}, iteration {it}; "
+          f"iteration 0 {e0:.2e}, iterations >= 1 {e1:.2e}")
+    assert e <= bound, (f"{label} {name}: {e:.3e} > {bound:.1e} at point {i} (tile {t}, persistent-loop iteration {it}); "
+                        f"worst in iteration 0 {e0:.3e}, in iterations >= 1 {e1:.3e}")
+    return e
+
+
+def point_err(got, ref, n):
+    """max |got - ref| per point of [n, ...] tensors, in float64 on the host."""
+    return (got.detach().double().cpu().reshape(n, -1) - ref.detach().double().cpu().reshape(n, -1)).abs().amax(dim=1)
+
+
+def tile_rel_err(got, ref, tile):
+    """Relative L2 error of each `tile`-row block of [n, C] rows: one corrupted tile cannot hide in a whole-tensor norm.
+    -> per-point values (every point carries its tile's error) for locate()."""
+    a, b = got.detach().double().cpu(), ref.detach().double().cpu()
+    n = a.shape[0]
+    a, b = a.reshape(n, -1), b.reshape(n, -1)
+    nt = -(-n // tile)
+    pad = nt * tile - n
+    d2 = torch.nn.functional.pad(((a - b) ** 2).sum(1), (0, pad)).reshape(nt, tile).sum(1)
+    r2 = torch.nn.functional.pad((b ** 2).sum(1), (0, pad)).reshape(nt, tile).sum(1)
+    rel = (d2 / (r2 + 1e-12 * float(r2.mean()) + 1e-300)).sqrt()
+    return rel.repeat_interleave(tile)[:n]
