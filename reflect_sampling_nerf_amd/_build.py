@@ -30,7 +30,7 @@ _MFMA_VGPR = ("-mllvm", "-amdgpu-mfma-vgpr-form")
 # for the activations); hipcc prices them above its default 16 K budget, unrolls them late and partially, and the activation /
 # accumulator arrays then live in scratch (832 B per lane).  With the budget raised: no scratch in the backward kernels.
 _UNROLL_BUDGET = ("-mllvm", "-pragma-unroll-threshold=131072")
-SOURCE_FLAGS = {"rsn_field.hip": _MFMA_VGPR, "rsn_field_bwd.hip": _MFMA_VGPR, "rsn_field_x6_train.hip": _UNROLL_BUDGET, "rsn_field_f32_ring.hip": _UNROLL_BUDGET}
+SOURCE_FLAGS = {"rsn_field.hip": _MFMA_VGPR, "rsn_field_bwd.hip": _MFMA_VGPR, "rsn_field_x6_train.hip": _UNROLL_BUDGET}
 
 
 def _headers():
@@ -63,29 +63,24 @@ def _compile_one(hipcc, src, obj, flags, verbose):
     os.replace(obj + ".tmp", obj)
 
 
-def build_library(force: bool = False, verbose: bool = False, extra_flags=(), lib_path: str = LIB_PATH,
-                  extra_sources=(), source_flags=None) -> str:
-    """Compile the HIP sources into librsn_hip.so; returns its path.  `force` recompiles every object.
-    extra_flags / lib_path / extra_sources (absolute paths of further .hip files) / source_flags (per-file flags replacing
-    SOURCE_FLAGS): diagnostic variants (tools/) build a second library beside the product one."""
-    if source_flags is None:
-        source_flags = SOURCE_FLAGS
-    if not force and not extra_flags and lib_path == LIB_PATH and source_flags is SOURCE_FLAGS and not _stale():
+def build_library(force: bool = False, verbose: bool = False) -> str:
+    """Compile the HIP sources into librsn_hip.so; returns its path.  `force` recompiles every object."""
+    if not force and not _stale():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found: cannot build librsn_hip.so")
-    flags = [*FLAGS, *extra_flags]
+    flags = FLAGS
     tag = hashlib.sha256(" ".join(flags).encode()).hexdigest()[:10]
     obj_dir = os.path.join(OBJ_DIR, tag)
     os.makedirs(obj_dir, exist_ok=True)
     hdr = _headers()
     jobs, objs = [], []
-    for s in [*SOURCES, *extra_sources]:
-        src = s if os.path.isabs(s) else os.path.join(CSRC, s)
-        sflags = [*flags, *source_flags.get(os.path.basename(s), ())]
+    for s in SOURCES:
+        src = os.path.join(CSRC, s)
+        sflags = [*flags, *SOURCE_FLAGS.get(s, ())]
         stag = "" if len(sflags) == len(flags) else "." + hashlib.sha256(" ".join(sflags).encode()).hexdigest()[:8]
-        obj = os.path.join(obj_dir, os.path.basename(s).replace(".hip", stag + ".o"))
+        obj = os.path.join(obj_dir, s.replace(".hip", stag + ".o"))
         stamp = obj + ".sha"
         want = _digest([src, *hdr], " ".join(sflags))
         have = open(stamp).read() if os.path.exists(stamp) and os.path.exists(obj) else ""
@@ -99,14 +94,14 @@ def build_library(force: bool = False, verbose: bool = False, extra_flags=(), li
             stamp, want = futs[f]
             with open(stamp, "w") as fh:
                 fh.write(want)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", lib_path + ".tmp"]
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB_PATH + ".tmp"]
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc link failed:\n" + res.stdout + res.stderr)
-    os.replace(lib_path + ".tmp", lib_path)
-    return lib_path
+    os.replace(LIB_PATH + ".tmp", LIB_PATH)
+    return LIB_PATH
 
 
 if __name__ == "__main__":

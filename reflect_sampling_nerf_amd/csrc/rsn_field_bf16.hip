@@ -13,8 +13,6 @@
 // Weights: split 0 of the split-bf16 segments written by rsn_pack_weights ([k16][nb][3][lane][8 bf16]).
 // Slab: X[kk][lane] = 8 bf16 = the lane's features kk*16 + {4h..4h+3} and kk*16 + 8 + {4h..4h+3} (K-iterations 2kk, 2kk+1
 // of the fp32 kernel), so the packed K order is unchanged.
-#include <stdlib.h>
-
 #include "rsn_ring16.h"
 
 // acc -> slab: blocks 0..NBS-1; K=16 step nb*2 + qp holds accumulator registers 8qp..8qp+7 of block nb
@@ -293,382 +291,18 @@ __global__ __launch_bounds__(256, 2) void rsn_field_bf16_kernel(const FieldArgs 
 // The kernel above makes every wave pull its own 1.2 MB of weight fragments per 32-point tile from L1/L2: one 1 KiB
 // fragment per 32-cycle MFMA per SIMD = 128 B/clk/CU, twice what a CU's L1 delivers (round 1: 33 % MFMA-busy, more
 // vector loads than MFMAs).  Here
-//   * the network's fragments form ONE linear stream in consumption order (rsn_pack.hip, L.r_stream), cut into
-//     groups of 8 fragments (8 KiB);
-//   * the four waves of a workgroup walk the network in lockstep and pull the stream through a 5-slot LDS ring by
-//     LDS-DMA (global_load_lds_dwordx4, two 1 KiB pieces per wave and group), 4 groups ahead of the MFMAs; every
-//     fragment is read from L2 once per WORKGROUP and tile (4x less L2 traffic) and feeds the MFMAs by
-//     ds_read_b128 (128 B/clk/CU of the LDS's 256);
+//   * the network's fragments form ONE linear stream in consumption order (rsn_pack.hip, L.q_stream), cut into
+//     groups of 16 fragments (16 KiB);
+//   * the eight waves of a workgroup walk the network in lockstep and pull the stream through a 4-slot LDS ring by
+//     LDS-DMA (global_load_lds_dwordx4, two 1 KiB pieces per wave and group), 3 groups ahead of the MFMAs; every
+//     fragment is read from L2 once per WORKGROUP and tile and feeds the MFMAs by ds_read_b128;
 //   * ONE s_barrier per group: behind it group g+1 has landed for every wave and the slot of group g-1 is free for
-//     the DMA of group g+4 (counted s_waitcnt vmcnt: other vector-memory operations only make it stricter);
-//   * activations never touch LDS: a lane's 256 inputs of the next layer are the bf16 pairs of its own accumulators
-//     (same lane-local hand-off as everywhere), kept in 64 VGPRs and indexed statically by the fully unrolled K loop;
-//     the LDS holds only the ring (40 KiB), the encoded inputs for the skip layer (7 KiB per wave) and the biases;
-//   * two workgroups per CU (78 KiB LDS, <= 256 VGPRs): while one encodes or drains accumulators the other's
-//     MFMAs keep the matrix pipe busy.
-// ================================================================================================
-// acc[nb] += W-fragment(i) * X[kk] over a GEMM of NBO x KS fragments (a whole number of groups); fragment i of the
-// stream sits in FIFO register i % RING_FIFO when its MFMA issues, and fragment i + RING_FIFO is read meanwhile.
-template <int NW, int NBO, int KS, int XN>
-__device__ __forceinline__ void gemm_ring(f32x16 (&acc)[NBO], const bf16x8 (&X)[XN], Ring& r, bf16x8 (&W)[RING_FIFO],
-                                          const char* smem) {
-  static_assert((NBO * KS) % RSN_RING_GROUP_FRAGS == 0 && KS <= XN, "a GEMM is a whole number of ring groups");
-#pragma unroll
-  for (int i = 0; i < NBO * KS; ++i) {
-    if (i % RSN_RING_GROUP_FRAGS == 0) ring_sync<NW>(r);
-    const int kk = i / NBO, nb = i % NBO;
-    const bf16x8 wa = W[i % RING_FIFO];
-    const int pos = (i % RSN_RING_GROUP_FRAGS) + RING_FIFO;
-    W[i % RING_FIFO] = *reinterpret_cast<const bf16x8*>(
-        smem + (pos < RSN_RING_GROUP_FRAGS ? r.rd_cur + pos * 1024 : r.rd_next + (pos - RSN_RING_GROUP_FRAGS) * 1024));
-#ifdef RSN_RING_NO_MFMA
-    acc[nb][i % 16] += (float)wa[0] * (float)X[kk][0];
-#elif defined(RSN_RING_MFMA16)  // timing experiment: the same FLOP as two 16x16x32 MFMAs (wrong results)
-    acc[nb].lo.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, X[kk], acc[nb].lo.lo, 0, 0, 0);
-    acc[nb].hi.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, X[kk], acc[nb].hi.lo, 0, 0, 0);
-#else
-    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, X[kk], acc[nb], 0, 0, 0);
-#endif
-    // keep the source order (read of fragment i + FIFO, then the MFMA of fragment i): hipcc otherwise sinks the reads
-    // to one or two MFMAs ahead of their use and every other MFMA waits out the LDS latency
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// accumulators <- bias (LDS table; all lanes of a half-wave read one address: broadcast)
-template <int NBO>
-__device__ __forceinline__ void init_acc_lds(f32x16 (&acc)[NBO], const float* bias, int h) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 bv = *reinterpret_cast<const float4*>(bias + nb * 32 + 8 * q + 4 * h);
-      acc[nb][4 * q + 0] = bv.x;
-      acc[nb][4 * q + 1] = bv.y;
-      acc[nb][4 * q + 2] = bv.z;
-      acc[nb][4 * q + 3] = bv.w;
-    }
-}
-
-// accumulator blocks 0..NBS-1 -> the next GEMM's B operands: K=16 step nb*2 + qp = registers 8qp..8qp+7 of block nb.
-// With `bias` the block's accumulators restart from the next layer's bias right after they are packed; the
-// sched_barrier keeps hipcc from hoisting all 32 bias loads above the packing (128 extra live registers).
-template <int NBO, int NBS, bool RELU, int XN>
-__device__ __forceinline__ void acc_to_x(f32x16 (&acc)[NBO], bf16x8 (&X)[XN], const float* bias = nullptr, int h = 0) {
-#pragma unroll
-  for (int nb = 0; nb < NBS; ++nb) {
-#pragma unroll
-    for (int qp = 0; qp < 2; ++qp) {
-      uint4v w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) w[e] = pack2<RELU>(acc[nb][8 * qp + 2 * e], acc[nb][8 * qp + 2 * e + 1]);
-      X[nb * 2 + qp] = __builtin_bit_cast(bf16x8, w);
-    }
-    if (bias) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 bv = *reinterpret_cast<const float4*>(bias + nb * 32 + 8 * q + 4 * h);
-        acc[nb][4 * q + 0] = bv.x;
-        acc[nb][4 * q + 1] = bv.y;
-        acc[nb][4 * q + 2] = bv.z;
-        acc[nb][4 * q + 3] = bv.w;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-#ifdef RSN_DIAG_BUILD  // the 32x32x16 form of the ring kernel: A/B reference of tools/ring_ab.sh only, never in librsn_hip.so
-template <int NW>
-__global__ __launch_bounds__(NW * 64, 2) void rsn_field_bf16_ring_kernel(const FieldArgs a) {
-  constexpr int NB = 8, W = 256;
-  constexpr int RING_BYTES = RingCfg<NW>::RING_BYTES;
-  __shared__ __attribute__((aligned(1024))) char smem[RingCfg<NW>::LDS_BYTES];
-  const int lane = threadIdx.x & 63;
-  // wave index as a SCALAR: everything derived from it (this wave's first point of a tile, the running output
-  // addresses hipcc strength-reduces out of the tile loop) then lives in SGPRs instead of 13 spilled VGPR pairs
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  char* stash = smem + RING_BYTES + wid * RING_STASH_BYTES;         // this wave's encoded inputs
-  bf16x8* ST = reinterpret_cast<bf16x8*>(stash) + lane;             // [k16][lane]
-  __bf16* STs = reinterpret_cast<__bf16*>(ST);                      // element (kk, pos) of this lane: STs[kk*512 + pos]
-  float* bias = reinterpret_cast<float*>(smem + RING_BYTES + NW * RING_STASH_BYTES);
-  const float* b_bh = bias + RING_MAX_LAYERS * 256;
-  const float* b_mid = b_bh + 288;
-  const float* b_rgb = b_mid + 128;
-
-  int n_rays = a.n_rays;
-  if (a.n_dev) {
-    const int nd = *a.n_dev;
-    n_rays = nd < n_rays ? nd : n_rays;
-  }
-  // 32-bit point indices (the launcher sends batches of 2^31 points or more to the per-wave-stream kernel): no 64-bit
-  // division per lane, fewer loop-invariant registers
-  const unsigned n_points = (unsigned)n_rays * (unsigned)a.S;
-  const unsigned n_tiles = (n_points + NW * 32 - 1) / (NW * 32);
-  if (blockIdx.x >= n_tiles) return;  // workgroup-uniform: no barrier is skipped by part of a workgroup
-  // Every workgroup streams the SAME 1.2 MB in the same order: started together, the 32 CUs of an XCD ask their L2 for
-  // the same lines at the same moment.  A start delay that grows with the workgroup's index inside its XCD
-  // (blockIdx / 8: workgroups are dealt round-robin over the 8 XCDs) spreads the CUs over the stream.
-  for (int i = 0; i < (int)((blockIdx.x >> 3) & 31) * a.stagger; ++i) __builtin_amdgcn_s_sleep(16);
-  const float* __restrict__ pk = a.packed;
-
-  // ---- biases -> LDS (once per workgroup)
-  for (int i = threadIdx.x; i < a.num_layers * 256; i += NW * 64) bias[i] = pk[a.L.b[i >> 8] + (i & 255)];
-  for (int i = threadIdx.x; i < 288; i += NW * 64) bias[RING_MAX_LAYERS * 256 + i] = pk[a.L.b_bh + i];
-  if (threadIdx.x < 128) bias[RING_MAX_LAYERS * 256 + 288 + threadIdx.x] = pk[a.L.b_mid + threadIdx.x];
-  if (threadIdx.x < 32) bias[RING_MAX_LAYERS * 256 + 288 + 128 + threadIdx.x] = pk[a.L.b_rgb + threadIdx.x];
-
-  // ---- the ring: the first LEAD groups are requested, group 0 is awaited, its first fragments are read
-  Ring r;
-  r.src = reinterpret_cast<const char*>(pk + a.L.r_stream) + wid * (RingCfg<NW>::PPW * 1024);
-  r.lane16 = (unsigned)lane * 16u;
-  r.lds_dst = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem + (unsigned)wid * (RingCfg<NW>::PPW * 1024u);
-  r.n_groups = a.L.r_groups;
-  r.issue_grp = 0;
-  r.issue_slot = 0;
-  r.rd_base = (unsigned)lane * 16u;
-  r.next_slot = 0;
-  r.rd_next = r.rd_base;
-  r.rd_cur = r.rd_base;
-  __syncthreads();  // nothing in flight yet: a plain barrier (also publishes the bias table)
-#pragma unroll
-  for (int g = 0; g < RingCfg<NW>::LEAD; ++g) ring_issue<NW>(r);
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(RingCfg<NW>::PPW * (RingCfg<NW>::LEAD - 1)) : "memory");
-#ifdef RSN_RING_SETPRIO
-  if (wid >= NW / 2) __builtin_amdgcn_s_setprio(1);  // the younger half of the workgroup loses every arbitration otherwise
-#endif
-  bf16x8 Wf[RING_FIFO];
-#pragma unroll
-  for (int j = 0; j < RING_FIFO; ++j) Wf[j] = *reinterpret_cast<const bf16x8*>(smem + r.rd_next + j * 1024);
-
-  for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const unsigned p0 = tile * (NW * 32) + wid * 32;
-    // every wave walks every tile (the barriers and the DMA shares are per wave); a wave past the end recomputes the
-    // last point and stores nothing
-    int ln = lane;
-    asm volatile("" : "+v"(ln));  // opaque per-tile lane id: per-lane addresses are not hoisted out of the tile loop
-    const int m = ln & 31, h = ln >> 5;
-    const unsigned p = p0 + m;
-    const bool valid = p < n_points;
-    const size_t pc = valid ? p : n_points - 1;
-
-    float mc[3] = {0.0f, 0.0f, 0.0f}, vc[3] = {0.0f, 0.0f, 0.0f}, vd[3] = {0.0f, 0.0f, 0.0f};
-    bool has_cov = true, has_dir = true;
-    // ---------------- encode (fp32, as rsn_field.hip) into this wave's stash -----------------
-    if (a.mode == RSN_MODE_FRUSTUM) {
-      const unsigned rayu = (unsigned)pc / (unsigned)a.S;
-      const int s = (int)((unsigned)pc - rayu * (unsigned)a.S);
-      const size_t ray = rayu;
-      float o[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        o[c] = a.origins[ray * 3 + c];
-        vd[c] = a.directions[ray * 3 + c];
-      }
-      const float pa = a.pixel_area[ray];
-      const float t0 = a.bins[ray * (a.S + 1) + s];
-      const float t1 = a.bins[ray * (a.S + 1) + s + 1];
-      frustum_to_contracted(o, vd, pa, t0, t1, mc, vc);
-    } else if (a.mode == RSN_MODE_INF) {
-      const float r2 = a.sqradius[pc];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        vd[c] = a.directions[pc * 3 + c];
-        mc[c] = 2.0f * vd[c];
-        vc[c] = (0.6f * r2) * (1.0f - vd[c] * vd[c]);
-      }
-      has_dir = false;  // SH inputs are zeroed (reflect_sampling_nerf_field.py:199)
-    } else {
-      has_cov = a.cov_diag != nullptr;
-      has_dir = a.view_dirs != nullptr;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        mc[c] = a.means[pc * 3 + c];
-        vc[c] = has_cov ? a.cov_diag[pc * 3 + c] : 0.0f;
-        vd[c] = has_dir ? a.view_dirs[pc * 3 + c] : 0.0f;
-      }
-    }
-#ifdef RSN_RING_NO_ENCODE
-    for (int c = 0; c < 0; ++c) {
-#else
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-#endif
-      const float x = (c == 0) ? mc[0] : (c == 1 ? mc[1] : mc[2]);
-      const float v = (c == 0) ? vc[0] : (c == 1 ? vc[1] : vc[2]);
-      const float sx = 6.283185307179586f * x;
-#pragma unroll 2
-      for (int jj = 0; jj < 8; ++jj) {
-        const float f = h ? a.freqs[8 + jj] : a.freqs[jj];
-        const float ang = sx * f;
-        // exp by v_exp_f32 (2^x): ~1e-6 relative on a feature that is rounded to bf16 (2^-9) next
-        const float e = has_cov ? __builtin_amdgcn_exp2f((-0.5f * (v * (f * f))) * 1.4426950408889634f) : 1.0f;
-#ifndef RSN_RING_EXACT_MATH
-        const float fs = e * sincos_bf16(ang, 0);
-        const float fc = e * sincos_bf16(ang + 1.5707963267948966f, 0);
-#else
-        const float fs = e * sin_big(ang);
-        const float fc = e * sin_big(ang + 1.5707963267948966f);
-#endif
-        const int u = c * 8 + jj, u2 = u + 24;
-        STs[(u >> 3) * 512 + ((u >> 2) & 1) * 4 + (u & 3)] = (__bf16)fs;
-        STs[(u2 >> 3) * 512 + ((u2 >> 2) & 1) * 4 + (u2 & 3)] = (__bf16)fc;
-      }
-    }
-    {
-      const float rw[8] = {h == 0 ? mc[0] : 0.0f, h == 0 ? mc[1] : 0.0f, h == 0 ? mc[2] : 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      ST[6 * 64] = pack8(rw);
-    }
-
-    bf16x8 X[16];
-    // ---------------- trunk -----------------
-    {
-      f32x16 acc[NB];
-      init_acc_lds<NB>(acc, bias, h);
-#pragma unroll
-      for (int kk = 0; kk < RSN_ENC_K16; ++kk) X[kk] = ST[kk * 64];
-#pragma unroll
-      for (int kk = RSN_ENC_K16; kk < RING_ENC_KS; ++kk) X[kk] = bf16x8{};  // padding K-steps (zero weights): finite operands
-      gemm_ring<NW, NB, RING_ENC_KS, 16>(acc, X, r, Wf, smem);
-#pragma unroll 1
-      for (int l = 1; l < a.num_layers; ++l) {
-        acc_to_x<NB, NB, true, 16>(acc, X, bias + l * 256, h);
-        gemm_ring<NW, NB, 16, 16>(acc, X, r, Wf, smem);
-        if (l == a.skip_layer) {
-          bf16x8 XE[RING_ENC_KS];
-#pragma unroll
-          for (int kk = 0; kk < RSN_ENC_K16; ++kk) XE[kk] = ST[kk * 64];
-#pragma unroll
-          for (int kk = RSN_ENC_K16; kk < RING_ENC_KS; ++kk) XE[kk] = bf16x8{};
-          gemm_ring<NW, NB, RING_ENC_KS, RING_ENC_KS>(acc, XE, r, Wf, smem);
-        }
-      }
-      acc_to_x<NB, NB, true, 16>(acc, X);  // out_activation = ReLU: the embedding
-    }
-    if (a.embedding && valid) {  // the embedding as the downstream GEMMs see it (bf16-rounded)
-#pragma unroll
-      for (int kk = 0; kk < NB * 2; ++kk) {
-        const bf16x8 f = X[kk];
-        *reinterpret_cast<float4*>(a.embedding + pc * W + kk * 16 + 4 * h) =
-            make_float4((float)f[0], (float)f[1], (float)f[2], (float)f[3]);
-        *reinterpret_cast<float4*>(a.embedding + pc * W + kk * 16 + 8 + 4 * h) =
-            make_float4((float)f[4], (float)f[5], (float)f[6], (float)f[7]);
-      }
-    }
-
-    // ---------------- heads (one 32-row block), then the bottleneck -----------------
-    float dcol[3], tcol[3], rho;
-    {
-      f32x16 acch[1];
-      init_acc_lds<1>(acch, b_bh + 256, h);
-      gemm_ring<NW, 1, 16, 16>(acch, X, r, Wf, smem);
-      const float r0 = acch[0][0], r1 = acch[0][1], r2 = acch[0][2], r3 = acch[0][3];
-      const float r4 = acch[0][4], r5 = acch[0][5], r6 = acch[0][6];
-      // h == 0: r0 raw density, r1..r3 normals, r4 roughness.   h == 1: r0..r2 diff, r4..r6 tint.
-      const float rough_raw = __shfl(r4, m, 64);
-#ifndef RSN_RING_EXACT_MATH
-      rho = fast_softplus(rough_raw);
-      dcol[0] = fast_sigmoid(r0); dcol[1] = fast_sigmoid(r1); dcol[2] = fast_sigmoid(r2);
-      tcol[0] = fast_sigmoid(r4); tcol[1] = fast_sigmoid(r5); tcol[2] = fast_sigmoid(r6);
-#else
-      rho = softplus_f(rough_raw);
-      dcol[0] = sigmoid_f(r0); dcol[1] = sigmoid_f(r1); dcol[2] = sigmoid_f(r2);
-      tcol[0] = sigmoid_f(r4); tcol[1] = sigmoid_f(r5); tcol[2] = sigmoid_f(r6);
-#endif
-      if (a.mode != RSN_MODE_INF && valid) {
-        if (h == 0) {
-          float nrm = fmaxf(sqrtf(r1 * r1 + r2 * r2 + r3 * r3), 1e-12f);
-          float nx = -(r1 / nrm), ny = -(r2 / nrm), nz = -(r3 / nrm);
-          nrm = fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-12f);
-          nx /= nrm; ny /= nrm; nz /= nrm;
-          if (a.out.sigma) a.out.sigma[pc] = softplus_f(r0 + a.density_bias);
-          if (a.out.raw_density) a.out.raw_density[pc] = r0;
-          if (a.out.pred_normals) {
-            a.out.pred_normals[pc * 3 + 0] = nx;
-            a.out.pred_normals[pc * 3 + 1] = ny;
-            a.out.pred_normals[pc * 3 + 2] = nz;
-          }
-          if (a.out.n_dot_d) a.out.n_dot_d[pc] = vd[0] * nx + vd[1] * ny + vd[2] * nz;
-          if (a.out.roughness) a.out.roughness[pc] = sigmoid_f(r4);
-          if (a.out.raw_roughness) a.out.raw_roughness[pc] = r4;
-        } else {
-          if (a.out.diff) {
-            a.out.diff[pc * 3 + 0] = dcol[0]; a.out.diff[pc * 3 + 1] = dcol[1]; a.out.diff[pc * 3 + 2] = dcol[2];
-          }
-          if (a.out.tint) {
-            a.out.tint[pc * 3 + 0] = tcol[0]; a.out.tint[pc * 3 + 1] = tcol[1]; a.out.tint[pc * 3 + 2] = tcol[2];
-          }
-        }
-      }
-    }
-    // ---------------- SH-34 of the view direction, attenuated by softplus roughness -----------------
-    // computed HERE, while only the embedding (64 VGPRs) is live, and parked in this wave's stash (free since the skip
-    // layer): it costs the bottleneck GEMM below no registers
-    {
-      float sh[34];
-      if (has_dir) {
-        sh34_attenuated(vd[0], vd[1], vd[2], rho, sh);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 34; ++i) sh[i] = 0.0f;
-      }
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {  // slot u = it*4 + s holds component 17h + u (u < 17); K=16 step 3 is padding
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int u = (2 * kk + (e >> 2)) * 4 + (e & 3);
-          v[e] = (u < 17) ? (h ? sh[17 + (u < 17 ? u : 0)] : sh[u < 17 ? u : 0]) : 0.0f;
-        }
-        ST[kk * 64] = pack8(v);
-      }
-    }
-    {
-      f32x16 acc[NB];
-      init_acc_lds<NB>(acc, b_bh, h);
-      gemm_ring<NW, NB, 16, 16>(acc, X, r, Wf, smem);
-      acc_to_x<NB, NB, false, 16>(acc, X);  // bottleneck output (no activation): the x-part of mlp_mid's input
-    }
-
-    // ---------------- mlp_mid + RGB head -----------------
-    {
-      f32x16 accm[4];
-      init_acc_lds<4>(accm, b_mid, h);
-      bf16x8 XS[4];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) XS[kk] = ST[kk * 64];
-      gemm_ring<NW, 4, 4, 4>(accm, XS, r, Wf, smem);
-      gemm_ring<NW, 4, 16, 16>(accm, X, r, Wf, smem);
-      acc_to_x<4, 4, true, 16>(accm, X);  // hidden (128): K=16 steps 0..7
-#pragma unroll
-      for (int kk = 8; kk < RING_RGB_KS; ++kk) X[kk] = bf16x8{};  // padding K-steps of the RGB head
-    }
-    {
-      f32x16 accr[1];
-      init_acc_lds<1>(accr, b_rgb, h);
-      gemm_ring<NW, 1, RING_RGB_KS, 16>(accr, X, r, Wf, smem);
-      if (h == 1 && valid && a.out.color) {
-        const float m0 = sigmoid_f(accr[0][0]);
-        const float m1 = sigmoid_f(accr[0][1]);
-        const float m2 = sigmoid_f(accr[0][2]);
-        if (a.mode == RSN_MODE_INF) {
-          a.out.color[pc * 3 + 0] = m0; a.out.color[pc * 3 + 1] = m1; a.out.color[pc * 3 + 2] = m2;
-        } else {
-          a.out.color[pc * 3 + 0] = dcol[0] + tcol[0] * m0;
-          a.out.color[pc * 3 + 1] = dcol[1] + tcol[1] * m1;
-          a.out.color[pc * 3 + 2] = dcol[2] + tcol[2] * m2;
-        }
-      }
-    }
-  }
-  // no LDS-DMA may outlive the workgroup's LDS allocation
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-#endif  // RSN_DIAG_BUILD
-
-// ================================================================================================
-// The same ring on v_mfma_f32_16x16x32_bf16.  Same FLOP per cycle as 32x32x16, but the chip holds a higher clock on
-// this shape under load (MI355X_MICROARCH.md, DVFS item 7; measured here by swapping the instruction alone: -6.5 %).
+//     the DMA of group g+3 (counted s_waitcnt vmcnt: other vector-memory operations only make it stricter);
+//   * activations never touch LDS: a lane's inputs of the next layer are the bf16 pairs of its own accumulators
+//     (same lane-local hand-off as everywhere), kept in VGPRs and indexed statically by the fully unrolled K loop;
+//     the LDS holds only the ring, the encoded inputs for the skip layer and the biases.
+// The MFMA is v_mfma_f32_16x16x32_bf16: same FLOP per cycle as 32x32x16, but the chip holds a higher clock on this shape
+// under load (MI355X_MICROARCH.md, DVFS item 7; measured here by swapping the instruction alone: -6.5 %).
 // Lane (m = lane & 15, g = lane >> 4): a wave's 32-point tile is two 16-point halves (p = 0, 1: point p0 + 16 p + m),
 // every weight fragment (16 rows x 32 K, 1 KiB) feeds one MFMA per half.  D[row 4g + r][col m]: after a GEMM the lane
 // holds packed rows 16 b + 4 g + r (r = 0..3) of its two points in acc[b][p]; the packed stream permutes the output rows
@@ -968,37 +602,19 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_ring16_kernel(const Fie
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may outlive the workgroup's LDS allocation
 }
 
-// called by launch_field (rsn_field.hip) for RSN_MMA_BF16 eval launches.  The product library takes NO run-time switches from
-// the environment; the A/B switches of tools/ (per-wave stream, start stagger, the 32x32x16 ring) exist in diagnostic
-// builds only (-DRSN_DIAG_BUILD, tools/_variant.py).
+// called by launch_field (rsn_field.hip) for RSN_MMA_BF16 eval launches
 int rsn_launch_field_bf16(int width, long long grid, hipStream_t st, const FieldArgs& a) {
-#ifdef RSN_DIAG_BUILD
-  static const bool per_wave_stream = getenv("RSN_BF16_PER_WAVE_STREAM") != nullptr;
-  static const int stagger = getenv("RSN_RING_STAGGER") ? atoi(getenv("RSN_RING_STAGGER")) : 0;
-  static const bool shape32 = getenv("RSN_RING_SHAPE32") != nullptr;
-#else
-  constexpr bool per_wave_stream = false;
-  constexpr int stagger = 0;
-#endif
   switch (width) {
     case 256:
       // full network evaluations run on the shared LDS weight ring; the granular heads-only mode (a caller-supplied
       // embedding skips the trunk, i.e. most of the stream) keeps the per-wave stream
-      if (a.mode != RSN_MODE_EMB && a.L.q_stream != 0 && a.num_layers <= RING_MAX_LAYERS && !per_wave_stream &&
+      if (a.mode != RSN_MODE_EMB && a.L.q_stream != 0 && a.num_layers <= RING_MAX_LAYERS &&
           (long long)a.n_rays * a.S < (1LL << 31)) {
-        FieldArgs b = a;
-        b.stagger = stagger;  // (diagnostic builds) start skew between the workgroups of an XCD (tools/ring_sweep.sh)
         const long long n_points = (long long)a.n_rays * a.S;
         // one 8-wave workgroup per CU, 256-point tiles
         const long long t8 = (n_points + 255) / 256;
         const long long g8 = t8 < (grid + 1) / 2 ? t8 : (grid + 1) / 2;
-#ifdef RSN_DIAG_BUILD
-        if (shape32 && a.L.r_stream != 0) {
-          hipLaunchKernelGGL(rsn_field_bf16_ring_kernel<8>, dim3((unsigned)g8), dim3(512), 0, st, b);
-          break;
-        }
-#endif
-        hipLaunchKernelGGL(rsn_field_bf16_ring16_kernel, dim3((unsigned)g8), dim3(512), 0, st, b);
+        hipLaunchKernelGGL(rsn_field_bf16_ring16_kernel, dim3((unsigned)g8), dim3(512), 0, st, a);
       } else {
         hipLaunchKernelGGL((rsn_field_bf16_kernel<8>), dim3((unsigned)grid), dim3(256), 0, st, a);
       }

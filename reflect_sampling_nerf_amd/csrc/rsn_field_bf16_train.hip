@@ -69,9 +69,6 @@ __device__ __forceinline__ void gemm_t(f32x4 (&acc)[NBO][2], const bf16x8 (&X)[X
 // (low half > 0) at bit 15 - j and (high half > 0) at bit 31 - j
 template <int XN>
 __device__ __forceinline__ unsigned relu_bits_of(const bf16x8 (&X)[XN][2], int p, int kk0, unsigned one2) {
-#ifdef RSN_RT_NO_BITS
-  return 0xffffffffu;
-#endif
   unsigned b = 0u;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
@@ -83,11 +80,7 @@ __device__ __forceinline__ unsigned relu_bits_of(const bf16x8 (&X)[XN][2], int p
 }
 // packed gradient word (K-step kk, word wi) masked by those bits
 __device__ __forceinline__ unsigned mask_word(unsigned gword, unsigned bits, int j, unsigned one2) {
-#ifdef RSN_RT_NO_BITS
-  return gword;
-#else
   return pk_mul_lo_u16(gword, (bits >> (15 - j)) & one2);
-#endif
 }
 
 // accumulators -> packed bf16 B operand of the next GEMM (no activation), masked by the layer's ReLU bits (2 words per point)
@@ -142,7 +135,7 @@ __device__ __forceinline__ void fold_enc(const f32x4 (&eacc)[8][2], const bf16x8
 template <bool NORMALS>
 __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const FieldJobs J) {
   constexpr int W = 256;
-  constexpr int RB = RT_RING_BYTES(RT_LEAD_FWD, RT_STAG_FWD);
+  constexpr int RB = RT_RING_BYTES(RT_LEAD_FWD);
   __shared__ __attribute__((aligned(1024))) char smem[RB + 8 * R16_STASH_BYTES + RT_TABLE_FLOATS * 4];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
   if (threadIdx.x < 32) bias[RING_MAX_LAYERS * 256 + 288 + 128 + threadIdx.x] = pk[P.L.b_rgb + threadIdx.x];
   if (threadIdx.x < 256) bias[RING_BIAS_FLOATS + threadIdx.x] = pk[P.L.v_density + threadIdx.x];
 
-  RingT<RT_LEAD_FWD, RT_STAG_FWD> r;
+  RingT<RT_LEAD_FWD> r;
   bf16x8 Wf[RING_FIFO];
   // the walk: forward stream [0, q_groups); with the normal sweep then [t_g_trunk, t_g_end) of the transposed stream; again
   ring_start(r, pk, P.L, smem, wid, lane, 0, P.L.q_groups, NORMALS ? P.L.t_g_trunk : 0, NORMALS ? P.L.t_g_end : -1, 0, Wf);
@@ -456,11 +449,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
     }
 
     // ---------------- analytic normals: -normalize(d raw_density / d contracted mean) -----------------
-#ifdef RSN_RT_NO_SWEEP
-    if (false) {
-#else
     if (NORMALS) {
-#endif
       // seed: the density-head row masked by the embedding's ReLU
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
@@ -525,14 +514,14 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
       }
     }
   }
-  ring_finish(r, wid);
+  ring_finish();
 }
 
 // ================================================================================================ backward sweep
 template <bool INPUT>
 __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJobs J) {
   constexpr int W = 256;
-  __shared__ __attribute__((aligned(1024))) char smem[RT_RING_BYTES(RT_LEAD_BWD, RT_STAG_BWD)];
+  __shared__ __attribute__((aligned(1024))) char smem[RT_RING_BYTES(RT_LEAD_BWD)];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const BwdShared& P = J.s;
@@ -541,7 +530,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJob
   const float* __restrict__ pk = P.packed;
   const int L = P.num_layers;
 
-  RingT<RT_LEAD_BWD, RT_STAG_BWD> r;
+  RingT<RT_LEAD_BWD> r;
   bf16x8 Wf[RING_FIFO];
   // the walk: the whole transposed stream; without an input gradient the two encoded-input pieces are jumped over
   {
@@ -797,7 +786,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJob
       }
     }
   }
-  ring_finish(r, wid);
+  ring_finish();
 }
 
 // ------------------------------------------------------------------------------------------------ launchers

@@ -35,9 +35,7 @@ struct FieldJob {
 };
 
 // one evaluation per launch (the plain-bf16 eval kernels of rsn_field_bf16.hip)
-struct FieldArgs : FieldShared, FieldJob {
-  int stagger;                // rsn_field_bf16_ring_kernel: start delay of the second workgroup per CU (x s_sleep 127)
-};
+struct FieldArgs : FieldShared, FieldJob {};
 
 // Several evaluations in ONE launch of rsn_field_kernel: the tiles of job 0, then job 1, ... form one tile space that
 // the persistent workgroups stride through.  The reflect branch of a training step has three evaluations of a few

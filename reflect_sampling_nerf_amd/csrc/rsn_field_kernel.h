@@ -9,24 +9,6 @@
 
 #include "rsn_field_common.h"
 
-// Optional per-phase cycle accounting (debug builds only: tools/phase_report.py compiles a second library with
-// -DRSN_PHASE_TIMERS).  Wave 0 of every workgroup sums shader-clock deltas per phase; never part of librsn_hip.so.
-// Only the kernels of rsn_field.hip (RSN_FIELD_MAIN_TU) carry the counters.
-#if defined(RSN_PHASE_TIMERS) && defined(RSN_FIELD_MAIN_TU)
-#define RSN_FIELD_TIMED 1
-__device__ unsigned long long rsn_phase_cycles[16];
-#define RSN_T(i)                                \
-  do {                                          \
-    __builtin_amdgcn_sched_barrier(0);          \
-    const long long tn_ = clock64();            \
-    tacc[i] += tn_ - tlast;                     \
-    tlast = tn_;                                \
-    __builtin_amdgcn_sched_barrier(0);          \
-  } while (0)
-#else
-#define RSN_T(i)
-#endif
-
 // ------------------------------------------------------------------------------------------------
 template <int NB, bool TRAIN, int MODE>
 __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
@@ -60,10 +42,6 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     if (k == 0) tb1 = n_tiles; else if (k == 1) tb2 = n_tiles;
   }
   const float* __restrict__ pk = P.packed;
-#ifdef RSN_FIELD_TIMED
-  long long tacc[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tlast = clock64();
-#endif
 
   for (long long gtile = blockIdx.x; gtile < n_tiles; gtile += gridDim.x) {
     const int jk = (gtile >= tb1 ? 1 : 0) + (gtile >= tb2 ? 1 : 0);  // workgroup-uniform
@@ -77,7 +55,6 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const int m = ln & 31, h = ln >> 5;
-    RSN_T(11);
     const long long p = p0 + m;
     const bool valid = p < n_points;
     const long long pc = valid ? p : n_points - 1;
@@ -188,26 +165,21 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       for (int it = 0; it < RSN_ENC_ITS; ++it) *reinterpret_cast<float4*>(row + it * 8 + 4 * h) = X[it * 64];
     }
 
-    RSN_T(0);
     // ---------------- trunk -----------------
     {
       f32x16 acc[NB];
       float4 wpre[NB];  // first weight fragment of the next GEMM, fetched ahead of the epilogue in front of it
       pre_mode<MODE, NB>(wpre, pk + P.L.w_enc0, ln);
       init_acc<NB>(acc, pk + P.L.b[0], h);
-      RSN_T(1);
       gemm_mode_run<MODE, NB, NB, TRAIN>(acc, wpre, pk + P.L.w_enc0, pk + P.L.h_enc0, X, RSN_ENC_ITS, ln);
-      RSN_T(2);
 #pragma unroll 1
       for (int l = 1; l < P.num_layers; ++l) {
         pre_mode<MODE, NB>(wpre, pk + P.L.w_x[l], ln);
         // ReLU between layers; the accumulators restart from layer l's bias
         store_act_init<NB, true, SBF>(acc, X, rb_epi(a.saved.act, (l - 1) * a.act_stride + p0 * W, W),
                                  h, pk + P.L.b[l], (TRAIN && a.saved.relu_bits && valid) ? bits_at(l - 1) : nullptr);
-        RSN_T(3);
         gemm_mode_run<MODE, NB, NB, TRAIN>(acc, wpre, pk + P.L.w_x[l], pk + P.L.h_x[l], X, NB * 4, ln,
                                 rb_loop(a.saved.act, (l - 1) * a.act_stride + p0 * W, W));
-        RSN_T(4);
         if (l == P.skip_layer) {
           pre_mode<MODE, NB>(wpre, pk + P.L.w_enc_skip, ln);
 #pragma unroll
@@ -219,14 +191,12 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
           X[12 * 64] = st3;
           if (MODE != 0) X[13 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           gemm_mode_run<MODE, NB, NB, TRAIN>(acc, wpre, pk + P.L.w_enc_skip, pk + P.L.h_enc_skip, X, RSN_ENC_ITS, ln);
-          RSN_T(2);
         }
       }
       // out_activation = ReLU
       pre_mode<MODE, NB + 1>(wbh, pk + P.L.w_bh, ln);
       store_act<NB, NB, true, SBF>(acc, X, rb_epi(a.saved.act, (P.num_layers - 1) * a.act_stride + p0 * W, W), h,
                               (TRAIN && a.saved.relu_bits && valid) ? bits_at(P.num_layers - 1) : nullptr);
-      RSN_T(3);
     }
     }  // mode != RSN_MODE_EMB
     if (a.embedding && valid) {
@@ -241,10 +211,8 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     {
       f32x16 acc[NB + 1];
       init_acc<NB + 1>(acc, pk + P.L.b_bh, h);
-      RSN_T(1);
       gemm_mode_run<MODE, NB + 1, NB + 1, TRAIN>(acc, wbh, pk + P.L.w_bh, pk + P.L.h_bh, X, NB * 4, ln,
                                   rb_loop(a.mode == RSN_MODE_EMB ? nullptr : a.saved.act, (P.num_layers - 1) * a.act_stride + p0 * W, W));
-      RSN_T(5);
       pre_mode<MODE, 4>(wmid, pk + P.L.w_mid_sh, ln);
       const float r0 = acc[NB][0], r1 = acc[NB][1], r2 = acc[NB][2], r3 = acc[NB][3];
       const float r4 = acc[NB][4], r5 = acc[NB][5], r6 = acc[NB][6];
@@ -311,30 +279,23 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       }
     }
 
-    RSN_T(6);
     // ---------------- mlp_mid + RGB head -----------------
     float4 wrgb[1];
     {
       f32x16 accm[4];
       init_acc<4>(accm, pk + P.L.b_mid, h);
-      RSN_T(1);
       float4 wmx[4];
       pre_mode<MODE, 4>(wmx, pk + P.L.w_mid_x, ln);
       gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmid, pk + P.L.w_mid_sh, pk + P.L.h_mid_sh, AUX, RSN_SH_ITS, ln);
-      RSN_T(7);
       gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmx, pk + P.L.w_mid_x, pk + P.L.h_mid_x, X, NB * 4, ln, rb_loop(a.saved.bott, p0 * W, W));
-      RSN_T(8);
       pre_mode<MODE, 1>(wrgb, pk + P.L.w_rgb, ln);
       store_act<4, 4, true, SBF>(accm, X, rb_epi(a.saved.hid, p0 * 128, 128), h,
                             (TRAIN && a.saved.relu_bits && valid) ? bits_at(P.num_layers) : nullptr);
-      RSN_T(3);
     }
     {
       f32x16 accr[1];
       init_acc<1>(accr, pk + P.L.b_rgb, h);
-      RSN_T(1);
       gemm_mode_run<MODE, 1, 1, TRAIN>(accr, wrgb, pk + P.L.w_rgb, pk + P.L.h_rgb, X, 16, ln, rb_loop(a.saved.hid, p0 * 128, 128));
-      RSN_T(9);
       if (h == 1 && valid) {
         const float m0 = sigmoid_f(accr[0][0]);
         const float m1 = sigmoid_f(accr[0][1]);
@@ -352,7 +313,6 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       }
     }
 
-    RSN_T(10);
     // ---------------- training: analytic normals = -normalize(d raw_density / d contracted mean) -----------------
     // (reflect_sampling_nerf_field.py:125-127,146-147 -> nerfstudio Field.get_normals).  A dX-only sweep back
     // through the trunk: seed = density-head row masked by the embedding's ReLU, then W_l^T GEMMs masked by the
@@ -378,7 +338,6 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       }
       f32x16 eacc[4];
       zero_acc<4>(eacc);
-      RSN_T(13);
 #pragma unroll 1
       for (int l = P.num_layers - 1; l >= 1; --l) {
         if (l == P.skip_layer) gemm_mode<MODE, 4, 4, TRAIN>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
@@ -386,14 +345,10 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc[NB];
         zero_acc<NB>(acc);
-        RSN_T(13);
         gemm_mode<MODE, NB, NB, TRAIN>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln);
-        RSN_T(12);
         store_masked_bits<NB>(acc, X, mb, h);
       }
-      RSN_T(13);
       gemm_mode<MODE, 4, 4, TRAIN>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, NB * 4, ln);
-      RSN_T(12);
       store_act<4, 4, false>(eacc, X);  // gradient w.r.t. this lane's encoded inputs, slot order (its 0..12)
       float nrm[3];
 #pragma unroll 1
@@ -423,15 +378,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         a.saved.normals[pc * 3 + 1] = -(nrm[1] / len);
         a.saved.normals[pc * 3 + 2] = -(nrm[2] / len);
       }
-      RSN_T(14);
     }
   }
-#ifdef RSN_FIELD_TIMED
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < 15; ++i) atomicAdd(&rsn_phase_cycles[i], (unsigned long long)tacc[i]);
-    atomicAdd(&rsn_phase_cycles[15], 1ull);
-  }
-#endif
 }
 

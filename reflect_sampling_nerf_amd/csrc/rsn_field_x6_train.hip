@@ -31,12 +31,8 @@
 // 6.94 / 7.10 ms per step (the input-gradient launch 2.12 -> 1.61 ms).  The forward has no LDS for more than 3 beside its stashes; with
 // the stash cut to 6 KiB per wave (raw-coordinate K-step rebuilt from registers) 4 groups ahead measured the same as 3
 // (profiles/r04_x6_ab.txt).
-#ifndef X6_LEAD_FWD
 #define X6_LEAD_FWD 3
-#endif
-#ifndef X6_LEAD_BWD
 #define X6_LEAD_BWD 5
-#endif
 #define X6_STASH_BYTES (8 * 1024)   // per wave: 8 float4 per lane -- the encoded inputs [kk (4)][half (2)], later the SH inputs / the
                                     // derivative factors of the encoding
 
@@ -88,8 +84,6 @@ __device__ __forceinline__ void gemm_j(f32x4 (&acc)[NBO], SRC&& src, NOTE&& note
       const int pos = f + RING_FIFO;
       W[i % RING_FIFO] = *reinterpret_cast<const bf16x8*>(
           smem + (pos < RSN_RING_GROUP_FRAGS ? r.rd_cur + pos * 1024 : r.rd_next + (pos - RSN_RING_GROUP_FRAGS) * 1024));
-#ifndef RSN_RT_NO_PREP  // (timing ablation: every K-step multiplies K-step 0's operand)
-      constexpr int pb = 1;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         if (kk + 1 < KS && j == (q * PK) / 4) {
@@ -97,11 +91,8 @@ __device__ __forceinline__ void gemm_j(f32x4 (&acc)[NBO], SRC&& src, NOTE&& note
           src(kk + 1, q, a, b2);
           note(kk + 1, q, split_pair(a, b2, P[(kk + 1) & 1], q));
         }
-#else
-      constexpr int pb = 0;
-#endif
-      const bf16x8 xh = __builtin_bit_cast(bf16x8, P[kk & pb][XH_]), xm = __builtin_bit_cast(bf16x8, P[kk & pb][XM_]),
-                   xl = __builtin_bit_cast(bf16x8, P[kk & pb][XL_]);
+      const bf16x8 xh = __builtin_bit_cast(bf16x8, P[kk & 1][XH_]), xm = __builtin_bit_cast(bf16x8, P[kk & 1][XM_]),
+                   xl = __builtin_bit_cast(bf16x8, P[kk & 1][XL_]);
       if (s == 0) {
         f32x4 c = acc[b];
         if (INIT != GI_ACC && kk == 0) {
@@ -128,17 +119,13 @@ __device__ __forceinline__ void gemm_j(f32x4 (&acc)[NBO], SRC&& src, NOTE&& note
 // a lane's four fp32 values of a saved row (counted, non-temporal like st16)
 template <class RING>
 __device__ __forceinline__ void st16f(const RowD& d, unsigned voff, unsigned soff, float a, float b, float c, float e, RING& r) {
-#ifndef RSN_RT_NO_STORES
   const u32x4t v = {__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(e)};
   // the constant part goes into the instruction's immediate offset, the scalar offset stays 0: with a REGISTER soffset the
   // compiler's hazard recogniser assumes that a VALU may overwrite the store's data registers in the very next instruction --
   // on gfx950 it may not (measured: the last quarter of every 16 lanes stored the overwriting value); see st16 (rsn_ringt.h)
   __builtin_amdgcn_raw_buffer_store_b128(v, d.r, voff + soff, 0, RT_STORE_AUX);
-#ifndef RSN_RT_UNCOUNTED
   r.c0 += 1;
   r.since += 1;
-#endif
-#endif
 }
 __device__ __forceinline__ void tie1(u32x2t& a) { asm volatile("" : "+v"(a)::"memory"); }
 
@@ -184,12 +171,8 @@ struct SrcMasked {
   __device__ __forceinline__ void operator()(int kk, int i, float& a, float& b) const {
     const f32x4 v = A[2 * kk + (i >> 1)];
     const int j = (kk & 3) * 4 + i;
-#ifdef RSN_RT_NO_BITS
-    const int ma = -1, mb = -1;
-#else
     const int ma = __builtin_amdgcn_sbfe((int)bits[kk >> 2], (unsigned)(15 - j), 1u);  // 0 or -1
     const int mb = __builtin_amdgcn_sbfe((int)bits[kk >> 2], (unsigned)(31 - j), 1u);
-#endif
     a = __uint_as_float(__float_as_uint(v[2 * (i & 1)]) & (unsigned)ma);
     b = __uint_as_float(__float_as_uint(v[2 * (i & 1) + 1]) & (unsigned)mb);
   }
@@ -200,12 +183,8 @@ struct SrcMasked {
 struct BitsNote {
   unsigned (&bw)[2];
   __device__ __forceinline__ void operator()(int kk, int i, unsigned h2) const {
-#ifdef RSN_RT_NO_BITS
-    bw[kk >> 2] = 0xffffffffu;
-#else
     const unsigned t = pk_min_u16(h2, 0x00010001u);
     bw[kk >> 2] = ((kk & 3) == 0 && i == 0) ? t : ((bw[kk >> 2] << 1) | t);
-#endif
   }
 };
 
@@ -241,7 +220,7 @@ __device__ __forceinline__ void copy_acc(f32x4 (&dst)[NB], const f32x4 (&src)[NB
 template <bool NORMALS>
 __global__ __launch_bounds__(512, 2) void rsn_field_x6_train_kernel(const FieldJobs J) {
   constexpr int W = 256;
-  constexpr int RB = RT_RING_BYTES(X6_LEAD_FWD, 0);
+  constexpr int RB = RT_RING_BYTES(X6_LEAD_FWD);
   __shared__ __attribute__((aligned(1024))) char smem[RB + 8 * X6_STASH_BYTES + RT_TABLE_FLOATS * 4];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -264,7 +243,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_x6_train_kernel(const FieldJ
   if (threadIdx.x < 32) bias[RING_MAX_LAYERS * 256 + 288 + 128 + threadIdx.x] = pk[P.L.b_rgb + threadIdx.x];
   if (threadIdx.x < 256) bias[RING_BIAS_FLOATS + threadIdx.x] = pk[P.L.v_density + threadIdx.x];
 
-  RingT<X6_LEAD_FWD, 0> r;
+  RingT<X6_LEAD_FWD> r;
   bf16x8 Wf[RING_FIFO];
   // the walk: forward stream [0, q_groups); with the normal sweep then [t_g_trunk, t_g_end) of the transposed stream; again
   ring_start(r, pk, P.L, smem, wid, lane, 0, P.L.q_groups, NORMALS ? P.L.t_g_trunk : 0, NORMALS ? P.L.t_g_end : -1, 0, Wf);
@@ -489,11 +468,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_x6_train_kernel(const FieldJ
     }
 
     // ---------------- analytic normals: -normalize(d raw_density / d contracted mean) -----------------
-#ifdef RSN_RT_NO_SWEEP
-    if (false) {
-#else
     if (NORMALS) {
-#endif
       // derivative factors of this lane's 24 features w.r.t. their angle, exactly as autograd forms them (the "cosine" features are
       // sines of the ROUNDED angle + pi / 2): parked in the stash (free now) for the two folds of the sweep
       {
@@ -570,14 +545,14 @@ __global__ __launch_bounds__(512, 2) void rsn_field_x6_train_kernel(const FieldJ
       }
     }
   }
-  ring_finish(r, wid);
+  ring_finish();
 }
 
 // ================================================================================================ backward sweep
 template <bool INPUT>
 __global__ __launch_bounds__(512, 2) void rsn_field_x6_bwd_kernel(const BwdJobs J) {
   constexpr int W = 256;
-  __shared__ __attribute__((aligned(1024))) char smem[RT_RING_BYTES(X6_LEAD_BWD, 0)];
+  __shared__ __attribute__((aligned(1024))) char smem[RT_RING_BYTES(X6_LEAD_BWD)];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const BwdShared& P = J.s;
@@ -586,7 +561,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_x6_bwd_kernel(const BwdJobs 
   const float* __restrict__ pk = P.packed;
   const int L = P.num_layers;
 
-  RingT<X6_LEAD_BWD, 0> r;
+  RingT<X6_LEAD_BWD> r;
   bf16x8 Wf[RING_FIFO];
   // the walk: the whole transposed stream; without an input gradient the two encoded-input pieces are jumped over
   {
@@ -812,7 +787,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_x6_bwd_kernel(const BwdJobs 
       for (int kk = 0; kk < 8; ++kk) store_kstep(dd, vrow * 1024 + 32 * g, kk, sm, r);
     }
   }
-  ring_finish(r, wid);
+  ring_finish();
 }
 
 // ------------------------------------------------------------------------------------------------ launchers

@@ -131,11 +131,9 @@ __device__ __forceinline__ void put4(float* save, int off, const float4 v) {
 // [N, row_elems] buffer (base = the tile's first row, wave-uniform), the lane sends one 32-bit offset (its row + 16 h
 // bytes) and the (block, q) position is a scalar offset.  Lanes past the last valid row fall outside the descriptor's
 // range and the hardware drops their stores: no per-lane null pointers, no exec-masked branches around the stores.
-// cache policy of the saved-row buffer stores (aux bits: 2 = nt); A/B switch of tools/ (default policy measured best for the
-// per-wave-stream kernels in round 3; the LDS-ring bf16 training kernels use nt, rsn_field_bf16_train.hip)
-#ifndef RSN_SAVED_ROW_AUX
+// cache policy of the saved-row buffer stores (aux bits: 0 = default, 2 = nt): the default policy measured best for the
+// per-wave-stream kernels in round 3 (the LDS-ring training kernels use nt, rsn_ringt.h)
 #define RSN_SAVED_ROW_AUX 0
-#endif
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 struct RowBuf {
@@ -151,9 +149,6 @@ __device__ __forceinline__ RowBuf rowbuf(float* base, long long elem, int rows, 
   // a literal nullptr (eval instantiations) removes the stores at compile time; a buffer that is absent at run time gets
   // an empty range instead of a branch around every store
   b.on = !(__builtin_constant_p(base == nullptr) && base == nullptr);
-#ifdef RSN_DIAG_NO_SAVED_ROWS  // timing ablation (wrong training results): no saved-row store is issued
-  b.on = false;
-#endif
   b.r = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(base) + elem * BPE, 0,
                                           base != nullptr ? rows * row_elems * BPE : 0, 0x00020000);
   b.voff = (unsigned)((m * row_elems + 4 * h) * BPE);
@@ -231,7 +226,7 @@ __device__ __forceinline__ void mma4(f32x16 (&acc)[NBO], const float4 (&w)[NBO],
 // Software pipeline: the loads of K-iteration it+1 are issued while the 32 MFMAs of iteration it run, one load
 // after each of the first NBO MFMAs (sched_group_barrier pattern), so every load has a full iteration (2048 MFMA
 // cycles) of cover; hipcc on its own sinks the loads to just ahead of their first use.
-// Measured with tools/phase_report.py (BASELINE config 2): with global_load_dwordx4 (64-bit VGPR addresses) the trunk K
+// Measured with per-phase cycle counters (round 3, BASELINE config 2): with global_load_dwordx4 (64-bit VGPR addresses) the trunk K
 // loops ran at 93.5 % of the MFMA issue rate and neither the prefetch distance, the position of the loads nor L1 residency
 // changed that; with buffer loads (load_w above) they run at 98.4 % (profiles/r03_phase_eval.json): the cost was the
 // address path of the load, not its data or its latency.
@@ -402,11 +397,7 @@ __device__ __forceinline__ void load_w16(bf16x8 (&w)[NH][3], const WBuf& wp, int
   for (int t = 0; t < NH; ++t)
 #pragma unroll
     for (int sp = 0; sp < NSPLIT; ++sp) {
-#ifdef RSN_DIAG_X6_SAMEW  // timing ablation (wrong results): every K step re-reads step 0's fragments (L1 / L2 hits)
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wp.r, wp.voff, (unsigned)(((0 * nbo + nb0 + t) * 3 + sp) * 1024), 0);
-#else
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wp.r, wp.voff, (unsigned)(((kk * nbo + nb0 + t) * 3 + sp) * 1024), 0);
-#endif
       w[t][sp] = __builtin_bit_cast(bf16x8, v);
     }
 }
@@ -624,15 +615,10 @@ __device__ __forceinline__ void store_masked_bits(const f32x16 (&acc)[NBO], floa
       const int word = m.w[nb / 2];
       const int base = (nb & 1) * 16 + 4 * q;
       float4 v;
-#ifdef RSN_DIAG_NO_EPI_VALU
-      (void)word; (void)base;
-      v = make_float4(acc[nb][4 * q + 0], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
-#else
       v.x = __uint_as_float(__float_as_uint(acc[nb][4 * q + 0]) & bit_mask(word, base + 0));
       v.y = __uint_as_float(__float_as_uint(acc[nb][4 * q + 1]) & bit_mask(word, base + 1));
       v.z = __uint_as_float(__float_as_uint(acc[nb][4 * q + 2]) & bit_mask(word, base + 2));
       v.w = __uint_as_float(__float_as_uint(acc[nb][4 * q + 3]) & bit_mask(word, base + 3));
-#endif
       xl[(nb * 4 + q) * 64] = v;
       if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
     }
@@ -651,7 +637,6 @@ __device__ __forceinline__ void store_act(const f32x16 (&acc)[NBO], float4* xl, 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float4 v = make_float4(acc[nb][4 * q + 0], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
-#ifndef RSN_DIAG_NO_EPI_VALU  // (timing ablation, wrong results: the upper bound of moving this work under the next layer's MFMAs)
       if (RELU) {
         v.x = relu_f(v.x);
         v.y = relu_f(v.y);
@@ -659,7 +644,6 @@ __device__ __forceinline__ void store_act(const f32x16 (&acc)[NBO], float4* xl, 
         v.w = relu_f(v.w);
         b16 = relu_bits4(b16, v, q);
       }
-#endif
       xl[(nb * 4 + q) * 64] = v;
       if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
     }
@@ -691,7 +675,6 @@ __device__ __forceinline__ void store_act_init(f32x16 (&acc)[NBO], float4* xl, S
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float4 v = make_float4(acc[nb][4 * q + 0], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
-#ifndef RSN_DIAG_NO_EPI_VALU  // (timing ablation, wrong results: the upper bound of moving this work under the next layer's MFMAs)
       if (RELU) {
         v.x = relu_f(v.x);
         v.y = relu_f(v.y);
@@ -699,7 +682,6 @@ __device__ __forceinline__ void store_act_init(f32x16 (&acc)[NBO], float4* xl, S
         v.w = relu_f(v.w);
         b16 = relu_bits4(b16, v, q);
       }
-#endif
       xl[(nb * 4 + q) * 64] = v;
       if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
       const float4 bv = *reinterpret_cast<const float4*>(bias + nb * 32 + 8 * q + 4 * h);

@@ -39,28 +39,7 @@ int rsn_device_cus() {
   return cache[dev];
 }
 
-#ifdef RSN_DIAG_BUILD  // environment A/B switches exist in diagnostic builds only: the product library reads none
-int rsn_env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v != nullptr && v[0] != '\0') ? atoi(v) : dflt;
-}
-
-// A/B switches of the tools (RSN_NO_PAIR=1 ...): read once per process and name.
-bool rsn_env_flag(const char* name) {
-  static thread_local const char* last_name = nullptr;
-  static thread_local bool last_val = false;
-  if (last_name == name) return last_val;  // call sites pass string literals: pointer identity is enough
-  const char* v = getenv(name);
-  last_name = name;
-  last_val = v != nullptr && v[0] != '\0' && v[0] != '0';
-  return last_val;
-}
-#endif
-#ifdef RSN_DIAG_BUILD
-extern "C" int rsn_abi_version(void) { return RSN_ABI_VERSION | RSN_ABI_DIAG_FLAG; }  // never the product library
-#else
 extern "C" int rsn_abi_version(void) { return RSN_ABI_VERSION; }
-#endif
 
 int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
   RSN_REQUIRE(d != nullptr, RSN_ERR_INVALID_ARGUMENT, "desc is NULL");
@@ -166,16 +145,7 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
   L->hT_rgb = off;
   off += (size_t)2 * L->nbm * 3 * blk;
   L->q_pf = 1;
-  if (d->mma_mode == RSN_MMA_BF16 && d->width == 256) {
-    // enc0 7 K-steps x 8 blocks; x layers 16 x 8; enc_skip 7 x 8; heads 16 x 1; bottleneck 16 x 8; mlp_mid SH part
-    // 3 (padded to 4) x 4; mlp_mid x part 16 x 4; rgb 8 x 1 -- every GEMM a whole number of 8-fragment groups
-    const int G = RSN_RING_GROUP_FRAGS;
-    const int enc_ks = (RSN_ENC_K16 * 8 + G - 1) / G * G / 8, rgb_ks = (8 + G - 1) / G * G;
-    L->r_groups = (enc_ks * 8 * (d->skip_layer >= 1 ? 2 : 1) + (d->num_layers - 1) * 128 + 16 + 128 + 16 + 64 + rgb_ks) / G;
-    L->r_stream = off;
-    off += (size_t)L->r_groups * RSN_RING_GROUP_FRAGS * blk;
-  }
-  if ((d->mma_mode == RSN_MMA_BF16 || d->mma_mode == RSN_MMA_BF16X6) && d->width == 256 && RSN_RING_GROUP_FRAGS == 16) {
+  if ((d->mma_mode == RSN_MMA_BF16 || d->mma_mode == RSN_MMA_BF16X6) && d->width == 256) {
     // 16x32 fragments: enc 4 x 16, x 8 x 16, heads 8 x 2, bottleneck 8 x 16, mid SH 2 x 8, mid x 8 x 8, rgb 4 x 4; split-bf16:
     // three pieces per fragment (q_pf), every count below in 16 KiB groups of PIECES
     const int pf = d->mma_mode == RSN_MMA_BF16X6 ? 3 : 1;
@@ -197,13 +167,6 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
     tg += pf * 4;
     L->t_g_end = tg;
     off += (size_t)(tg - L->q_groups) * 16 * blk;
-  }
-  if (rsn_f32_ring_training(d)) {
-    const int enc_g = (RSN_ENC_ITS * 8 + 15) / 16, skip = d->skip_layer >= 1 ? 1 : 0;   // 104 fragments -> 7 groups
-    L->f_groups = enc_g * (1 + skip) + (d->num_layers - 1) * 16 + 18 + 2 + 8 + 1;
-    L->ft_end = L->f_groups + (d->num_layers - 1) * 16 + 8 * (1 + skip);
-    L->f_stream = off;
-    off += (size_t)L->ft_end * 16 * blk;
   }
   L->total = off;
   return RSN_OK;
@@ -390,33 +353,6 @@ __global__ void rsn_pack_split_all_kernel(const SplitJob job) {
   split_elem(job.packed + sg.src, sg.n_it, sg.nbo, job.packed + sg.dst, ((int)blockIdx.x - sg.block0) * 256 + (int)threadIdx.x);
 }
 
-// ---- ring stream (RSN_MMA_BF16, width 256): split-0 fragments of the h_* segments re-ordered into consumption order
-#define RING_MAX_PIECES 48
-struct RingPiece {
-  unsigned src;      // float offset of the source segment: split-bf16 ([k16][nbo_src][3][lane][8 bf16], mul = 3) or fp32 ([it][nbo_src][lane][4], mul = 1)
-  short nbo_src, nb0, nbo, ks_real, ks, mul;
-  int frag0;         // first fragment of this piece in the stream
-};
-struct RingJob {
-  const float* packed;
-  float* dst;
-  int n_pieces, n_frags;
-  RingPiece p[RING_MAX_PIECES];
-};
-
-__global__ void rsn_pack_ring_kernel(const RingJob job) {  // one 64-thread workgroup per 1 KiB fragment
-  const int f = blockIdx.x;
-  int pi = 0;
-  while (pi + 1 < job.n_pieces && job.p[pi + 1].frag0 <= f) ++pi;
-  const RingPiece pc = job.p[pi];
-  const int i = f - pc.frag0;
-  const int kk = i / pc.nbo, nb = pc.nb0 + i % pc.nbo;
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (kk < pc.ks_real)
-    v = reinterpret_cast<const uint4*>(job.packed + pc.src + ((size_t)(kk * pc.nbo_src + nb) * pc.mul) * 256)[threadIdx.x];
-  reinterpret_cast<uint4*>(job.dst + (size_t)f * 256)[threadIdx.x] = v;
-}
-
 namespace {
 
 void rows_natural(PackJob& j, int n_rows, int src = 0) {
@@ -476,10 +412,6 @@ struct PackCollector {
   float* packed;
   std::vector<PackJob> jobs;
   std::vector<SplitSeg> splits;
-  bool have_ring = false;
-  RingJob ring;
-  bool have_fring = false;
-  RingJob fring;   // the fp32 consumption-order stream (f_stream)
 };
 thread_local PackCollector* g_collect = nullptr;
 
@@ -816,47 +748,6 @@ extern "C" int rsn_pack_weights(const rsn_field_desc* d, const rsn_field_params*
                 frag, L.t_g_end);
   }
 
-  // ---------------- fp32 consumption-order stream (rsn_field_f32_train.hip): copies of the fp32 fragments above ----------------
-  if (L.f_stream != 0) {
-    RingJob rj;
-    memset(&rj, 0, sizeof(rj));
-    rj.packed = packed;
-    rj.dst = packed + L.f_stream;
-    int frag = 0;
-    auto piece = [&](size_t src, int nbo, int its_real, int its) {
-      RingPiece& q = rj.p[rj.n_pieces++];
-      q.src = (unsigned)src; q.nbo_src = (short)nbo; q.nb0 = 0; q.nbo = (short)nbo;
-      q.ks_real = (short)its_real; q.ks = (short)its; q.mul = 1; q.frag0 = frag;
-      frag += its * nbo;
-    };
-    const int enc_its = (RSN_ENC_ITS * 8 + 15) / 16 * 16 / 8;  // 13 -> 14: whole groups
-    piece(L.w_enc0, NB, RSN_ENC_ITS, enc_its);
-    for (int l = 1; l < d->num_layers; ++l) {
-      piece(L.w_x[l], NB, NB * 4, NB * 4);
-      if (l == d->skip_layer) piece(L.w_enc_skip, NB, RSN_ENC_ITS, enc_its);
-    }
-    piece(L.w_bh, NB + 1, NB * 4, NB * 4);
-    piece(L.w_mid_sh, NBM, RSN_SH_ITS, 8);
-    piece(L.w_mid_x, NBM, NB * 4, NB * 4);
-    piece(L.w_rgb, 1, NBM * 4, NBM * 4);
-    RSN_REQUIRE(frag == L.f_groups * 16, RSN_ERR_INVALID_ARGUMENT, "fp32 stream: %d fragments, layout says %d groups", frag, L.f_groups);
-    for (int l = d->num_layers - 1; l >= 1; --l) {
-      if (l == d->skip_layer) piece(L.wT_enc_skip, 4, NB * 4, NB * 4);
-      piece(L.wT_x[l], NB, NB * 4, NB * 4);
-    }
-    piece(L.wT_enc0, 4, NB * 4, NB * 4);
-    RSN_REQUIRE(rj.n_pieces <= RING_MAX_PIECES && frag == L.ft_end * 16, RSN_ERR_INVALID_ARGUMENT,
-                "fp32 stream: %d fragments in %d pieces, layout says %d groups", frag, rj.n_pieces, L.ft_end);
-    rj.n_frags = frag;
-    if (g_collect) {
-      g_collect->have_fring = true;
-      g_collect->fring = rj;
-    } else {
-      hipLaunchKernelGGL(rsn_pack_ring_kernel, dim3((unsigned)frag), dim3(64), 0, st, rj);
-      RSN_HIP(hipGetLastError());
-    }
-  }
-
   // ---------------- split-bf16 copies (RSN_MMA_BF16X6 / X3 / BF16) of every GEMM segment ----------------
   if (d->mma_mode == RSN_MMA_F32) return RSN_OK;  // the exact-fp32 kernels never read them
   if ((rc = split_seg(packed + L.w_enc0, RSN_ENC_ITS, NB, packed + L.h_enc0, st)) != RSN_OK) return rc;
@@ -876,45 +767,10 @@ extern "C" int rsn_pack_weights(const rsn_field_desc* d, const rsn_field_params*
   if ((rc = split_seg(packed + L.wT_mid_x, NBM * 4, NB, packed + L.hT_mid_x, st)) != RSN_OK) return rc;
   if ((rc = split_seg(packed + L.w_rgb, NBM * 4, 1, packed + L.h_rgb, st)) != RSN_OK) return rc;
   if ((rc = split_seg(packed + L.wT_rgb, 4, NBM, packed + L.hT_rgb, st)) != RSN_OK) return rc;
-  if (L.r_stream != 0) {
-    RingJob rj;
-    memset(&rj, 0, sizeof(rj));
-    rj.packed = packed;
-    rj.dst = packed + L.r_stream;
-    int frag = 0;
-    auto piece = [&](size_t src, int nbo_src, int nb0, int nbo, int ks_real, int ks) {
-      RingPiece& q = rj.p[rj.n_pieces++];
-      q.src = (unsigned)src; q.nbo_src = (short)nbo_src; q.nb0 = (short)nb0; q.nbo = (short)nbo;
-      q.ks_real = (short)ks_real; q.ks = (short)ks; q.mul = 3; q.frag0 = frag;
-      frag += ks * nbo;
-    };
-    const int G = RSN_RING_GROUP_FRAGS;
-    const int enc_ks = (RSN_ENC_K16 * 8 + G - 1) / G * G / 8, rgb_ks = (8 + G - 1) / G * G;  // padded to whole groups
-    piece(L.h_enc0, NB, 0, NB, RSN_ENC_K16, enc_ks);
-    for (int l = 1; l < d->num_layers; ++l) {
-      piece(L.h_x[l], NB, 0, NB, NB * 2, NB * 2);
-      if (l == d->skip_layer) piece(L.h_enc_skip, NB, 0, NB, RSN_ENC_K16, enc_ks);
-    }
-    piece(L.h_bh, NB + 1, NB, 1, NB * 2, NB * 2);  // heads block first (its epilogue feeds the SH encoding)
-    piece(L.h_bh, NB + 1, 0, NB, NB * 2, NB * 2);  // bottleneck
-    piece(L.h_mid_sh, NBM, 0, NBM, RSN_SH_K16, 4);
-    piece(L.h_mid_x, NBM, 0, NBM, NB * 2, NB * 2);
-    piece(L.h_rgb, 1, 0, 1, NBM * 2, rgb_ks);
-    RSN_REQUIRE(rj.n_pieces <= RING_MAX_PIECES && frag == L.r_groups * RSN_RING_GROUP_FRAGS, RSN_ERR_INVALID_ARGUMENT,
-                "ring stream: %d fragments in %d pieces, layout says %d groups", frag, rj.n_pieces, L.r_groups);
-    rj.n_frags = frag;
-    if (g_collect) {
-      g_collect->have_ring = true;
-      g_collect->ring = rj;
-    } else {
-      hipLaunchKernelGGL(rsn_pack_ring_kernel, dim3((unsigned)frag), dim3(64), 0, st, rj);
-      RSN_HIP(hipGetLastError());
-    }
-  }
   return RSN_OK;
 }
 
-// ---- the same in (at most) three launches: every fp32 segment, every split-bf16 copy, the ring stream ----------------
+// ---- the same in (at most) two launches: every fp32 segment, every split-bf16 copy ----------------
 extern "C" size_t rsn_pack_table_bytes(void) { return sizeof(PackTable); }
 
 extern "C" int rsn_pack_weights_table(const rsn_field_desc* d, const rsn_field_params* p, float* packed,
@@ -929,8 +785,6 @@ extern "C" int rsn_pack_weights_table(const rsn_field_desc* d, const rsn_field_p
   col.packed = packed;
   col.jobs.clear();
   col.splits.clear();
-  col.have_ring = false;
-  col.have_fring = false;
   g_collect = &col;
   const int rc = rsn_pack_weights(d, p, packed, packed_bytes, stream);
   g_collect = nullptr;
@@ -968,14 +822,6 @@ extern "C" int rsn_pack_weights_table(const rsn_field_desc* d, const rsn_field_p
       b += (((sj.s[i].n_it + 1) / 2) * sj.s[i].nbo * 512 + 255) / 256;
     }
     hipLaunchKernelGGL(rsn_pack_split_all_kernel, dim3((unsigned)b), dim3(256), 0, st, sj);
-    RSN_HIP(hipGetLastError());
-  }
-  if (col.have_ring) {
-    hipLaunchKernelGGL(rsn_pack_ring_kernel, dim3((unsigned)col.ring.n_frags), dim3(64), 0, st, col.ring);
-    RSN_HIP(hipGetLastError());
-  }
-  if (col.have_fring) {  // (behind rsn_pack_all_kernel on the same stream: it copies what that kernel wrote)
-    hipLaunchKernelGGL(rsn_pack_ring_kernel, dim3((unsigned)col.fring.n_frags), dim3(64), 0, st, col.fring);
     RSN_HIP(hipGetLastError());
   }
   return RSN_OK;

@@ -54,26 +54,19 @@ __device__ __forceinline__ float sincos_bf16(float a, int quad) {
   return (n & 2) ? -v : v;
 }
 
-
-#define RING_ENC_KS ((RSN_ENC_K16 * 8 + RSN_RING_GROUP_FRAGS - 1) / RSN_RING_GROUP_FRAGS * RSN_RING_GROUP_FRAGS / 8)  // enc K-steps incl. padding
-#define RING_RGB_KS (RSN_RING_GROUP_FRAGS == 16 ? 16 : 8)
-#ifndef RING_FIFO
 #define RING_FIFO 4   // fragments read from the ring ahead of their MFMA (registers: 4 x 4 VGPRs)
-#endif
 #define RING_GROUP_BYTES (RSN_RING_GROUP_FRAGS * 1024)
-#define RING_STASH_BYTES (RSN_ENC_K16 * 1024)          // per wave: encoded inputs as bf16, [k16][lane][8]
 #define RING_MAX_LAYERS RSN_RING_MAX_LAYERS            // trunk depth the LDS bias table is sized for
 #define RING_BIAS_FLOATS (RING_MAX_LAYERS * 256 + 288 + 128 + 32)
 
-// NW = waves per workgroup.  4: two workgroups per CU, 5-slot ring each (78 KiB);  8: one workgroup per CU whose two
-// waves per SIMD share ONE stream (half the LDS-DMA pieces per MFMA, half the L2 traffic), 8-slot ring (130 KiB).
+// NW = waves per workgroup (8: one workgroup per CU whose two waves per SIMD share ONE stream -- half the LDS-DMA pieces per
+// MFMA, half the L2 traffic); a 4-slot ring of 16 KiB groups.
 template <int NW>
 struct RingCfg {
-  static constexpr int SLOTS = RSN_RING_GROUP_FRAGS == 16 ? 4 : (NW == 8 ? 8 : 5);
+  static constexpr int SLOTS = 4;
   static constexpr int LEAD = SLOTS - 1;              // groups in flight ahead of the group being consumed
   static constexpr int PPW = RSN_RING_GROUP_FRAGS / NW;  // LDS-DMA pieces per wave and group
   static constexpr int RING_BYTES = SLOTS * RING_GROUP_BYTES;
-  static constexpr int LDS_BYTES = RING_BYTES + NW * RING_STASH_BYTES + RING_BIAS_FLOATS * 4;
 };
 
 struct Ring {
@@ -110,20 +103,10 @@ __device__ __forceinline__ void ring_issue(Ring& r) {
 // group boundary: the group about to be consumed (and the one after it) are in LDS for every wave; the previous
 // group's slot is refilled.  vmcnt counts in issue order, so "all but the youngest PPW*(LEAD-2)" covers every DMA of
 // the two oldest groups in flight.
-// (RSN_RING_NO_*: timing diagnostics of tools/variant_bench.py -- wrong results by construction; they compile only under
-// -DRSN_DIAG_BUILD, rsn_common.h, and such a library is refused as librsn_hip.so)
 template <int NW>
 __device__ __forceinline__ void ring_sync(Ring& r) {
-#ifdef RSN_RING_NO_BARRIER
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RingCfg<NW>::PPW * (RingCfg<NW>::LEAD - 2)) : "memory");
-#elif defined(RSN_RING_NO_WAIT)
-  asm volatile("s_barrier" ::: "memory");
-#else
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(RingCfg<NW>::PPW * (RingCfg<NW>::LEAD - 2)) : "memory");
-#endif
-#ifndef RSN_RING_NO_DMA
   ring_issue<NW>(r);
-#endif
   r.rd_cur = r.rd_next;
   r.next_slot = (r.next_slot + 1 == RingCfg<NW>::SLOTS) ? 0 : r.next_slot + 1;
   r.rd_next = r.rd_base + (unsigned)r.next_slot * RING_GROUP_BYTES;
@@ -146,20 +129,10 @@ __device__ __forceinline__ void gemm_ring16(f32x4 (&acc)[NBO][2], const bf16x8 (
     const int kk = i / NBO, b = i % NBO;
     const bf16x8 wa = W[i % RING_FIFO];
     const int pos = (i % RSN_RING_GROUP_FRAGS) + RING_FIFO;
-#ifndef RSN_R16_NO_LDS_READ  // timing diagnostics (tools/variant_bench.py --define): wrong results by construction
     W[i % RING_FIFO] = *reinterpret_cast<const bf16x8*>(
         smem + (pos < RSN_RING_GROUP_FRAGS ? r.rd_cur + pos * 1024 : r.rd_next + (pos - RSN_RING_GROUP_FRAGS) * 1024));
-#endif
-#ifndef RSN_R16_NO_MFMA
     acc[b][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, X[kk][0], acc[b][0], 0, 0, 0);
     acc[b][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, X[kk][1], acc[b][1], 0, 0, 0);
-#else
-    acc[b][0][i % 4] += (float)wa[0] * (float)X[kk][0][0];
-#endif
-#ifdef RSN_R16_DOUBLE_MFMA  // the MFMA work of a 64-point tile per fragment read (results wrong)
-    acc[b][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, X[kk][1], acc[b][0], 0, 0, 0);
-    acc[b][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, X[kk][0], acc[b][1], 0, 0, 0);
-#endif
     __builtin_amdgcn_sched_barrier(0);
   }
 }

@@ -21,27 +21,13 @@
 // MFMA-bound: 2 * N * n_out * k_in FLOP; HBM reads N * (n_out + k_in) * 4 B (each operand once per workgroup).
 #include "rsn_mfma.h"
 
-// cache policy of the operand-row loads (buffer-instruction aux bits: 2 = nt); A/B switch of tools/bf16_train_ab.sh
-#ifndef WG_LOAD_AUX
+// cache policy of the operand-row loads (buffer-instruction aux bits: 0 = default, 2 = nt)
 #define WG_LOAD_AUX 0
-#endif
 
 // split-bf16 stage: VALU instructions pinned in front of the first MFMA / behind every MFMA (sched_group_barrier)
-#ifndef WG_X6_HEAD
-#define WG_X6_HEAD 160
-#endif
-#ifndef WG_X6_VALU
 #define WG_X6_VALU 4
-#endif
-#ifndef WG_X6_VALU4
 #define WG_X6_VALU4 5  // 4 column blocks (k_in <= 128): measured 253 us against 275 with 6 (256 x 104 over 524,288 points)
-#endif
-#ifndef WG_X6_VALU2
 #define WG_X6_VALU2 4
-#endif
-#ifndef WG_X6_VMEM
-#define WG_X6_VMEM 4
-#endif
 typedef float f32x2w __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2w __attribute__((ext_vector_type(2)));
@@ -73,9 +59,7 @@ struct WGradJobs {
   WGradArgs j[WG_MAX_JOBS];
 };
 
-#ifndef WG_PAIRS
 #define WG_PAIRS 4  // point pairs (MFMA K-steps) per software-pipeline stage
-#endif
 
 // NKB: input-column blocks of 32 held per wave (8 covers k_in <= 256).
 // XV: lane i owns columns i*NKB.. (vector loads of X);  else column kb*32+i (scalar loads, any k_in / alignment).
@@ -276,15 +260,7 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
     }
   };
   // every variant loads through the buffer form.  (Round 3 kept pointer loads for the split-bf16 variant -- 5 % faster then, when its
-  // splits stood in blocks in front of the MFMAs; with the splits pinned between the MFMAs the 30 address registers are worth more.
-  // -DWG_X6_PTR_LOADS keeps the old form for A/B in diagnostic builds.)
-  auto load_row_m = [&](int buf, int p, long long m0) {
-#ifdef WG_X6_PTR_LOADS
-    if constexpr (BF == 3) load_row(buf, p, m0 + roff(p), true); else load_row_b(buf, p, m0);
-#else
-    load_row_b(buf, p, m0);
-#endif
-  };
+  // splits stood in blocks in front of the MFMAs; with the splits pinned between the MFMAs the 30 address registers are worth more.)
   // Two neighbouring rows / columns c0, c0 + 1 at once: their values of ONE point sit in adjacent registers (one load), so
   // the subtractions are v_pk_add_f32 over the (c0, c0 + 1) pair while v_cvt_pk_bf16_f32 packs the point pair (2q, 2q + 1)
   // of each: 18 VALU per 2 x 2 values.
@@ -317,7 +293,6 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
     cacc = c;
   };
   auto mma_stage = [&](int buf) {
-#ifndef WG_X6_OLD
     if constexpr (BF == 3) {
       // Split-bf16, one stage on its own (the masked tail stage of a segment; the main loop is x6_stage below): each fp32 operand
       // value becomes three bf16 pieces (hi, mid, lo; x = hi + mid + lo to 2^-24).  The 8 points of a lane x (2 rows + NKB columns)
@@ -339,49 +314,6 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
 #pragma unroll
           for (int t = 0; t < 2; ++t)
             if (t == 0 || t1_live) mma6(acc[t][2 * j + c], av[t], bv[j & 1][c]);
-      }
-    } else
-#endif
-    if constexpr (BF == 3) {
-      bf16x8 a1[2], a2[2], a3[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const float x = fa[buf][p][t];
-          bsum[t] += x;
-          const __bf16 s1 = (__bf16)x;
-          const float r1 = x - (float)s1;
-          const __bf16 s2 = (__bf16)r1;
-          a1[t][p] = s1;
-          a2[t][p] = s2;
-          a3[t][p] = (__bf16)(r1 - (float)s2);
-        }
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        bf16x8 b1, b2, b3;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const float x = fb[buf][p][kb];
-          const __bf16 s1 = (__bf16)x;
-          const float r1 = x - (float)s1;
-          const __bf16 s2 = (__bf16)r1;
-          b1[p] = s1;
-          b2[p] = s2;
-          b3[p] = (__bf16)(r1 - (float)s2);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          if (t == 1 && !t1_live) continue;
-          f32x16 c = acc[t][kb];  // smallest terms first
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[t], b1, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[t], b2, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[t], b3, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[t], b1, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[t], b2, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[t], b1, c, 0, 0, 0);
-          acc[t][kb] = c;
-        }
       }
     } else if constexpr (BF != 0) {
       bf16x8 av[2], bv[NKB];
@@ -447,7 +379,6 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
     }
   };
 
-#ifndef WG_X6_OLD
   // The split-bf16 main loop, pipelined ACROSS stages: while stage s multiplies, the splits of its own later column pairs and --
   // under its last pair -- of stage s + 1's rows and first column pair are formed, so that no split stands in front of an MFMA
   // (a wave is alone on its SIMD: what is not slotted between MFMAs is added to them).  xa / xb01: the split rows / first column
@@ -470,17 +401,12 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
         for (int p = 0; p < NP; ++p) bsum[t] += fa[c][p][t];
 #pragma unroll
       for (int k = 0; k < 3; ++k) { bq[0][0][k] = xb01[0][k]; bq[0][1][k] = xb01[1][k]; }
-#ifdef WG_X6_NEAR
-      load_next2(c ^ 1);
-#endif
 #pragma unroll
       for (int j = 0; j < NPR; ++j) {
         if (j + 1 < NPR) {
           split2(bq[j + 1][0], bq[j + 1][1], [&](int p) { return f32x2w{fb[c][p][2 * j + 2], fb[c][p][2 * j + 3]}; });
         } else {
-#ifndef WG_X6_NEAR
           load_next2(c);
-#endif
           split2(an[0], an[1], [&](int p) { return f32x2w{fa[c ^ 1][p][0], fa[c ^ 1][p][1]}; });
           split2(bq[NPR][0], bq[NPR][1], [&](int p) { return f32x2w{fb[c ^ 1][p][0], fb[c ^ 1][p][1]}; });
         }
@@ -495,52 +421,19 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
         xa[0][k] = an[0][k]; xa[1][k] = an[1][k];
         xb01[0][k] = bq[NPR][0][k]; xb01[1][k] = bq[NPR][1][k];
       }
-#ifdef WG_X6_NEAR
-      constexpr int NM = 12 * NKB, NL = 8 * (1 + (NKB >= 4 ? NKB / 4 : 1)), G0 = 0;
-#else
       constexpr int NM = 12 * NKB, NL = 8 * (1 + (NKB >= 4 ? NKB / 4 : 1)), G0 = NM - 12 - NL > 0 ? NM - 12 - NL : 0;
-#endif
 #pragma unroll
       for (int g = 0; g < NM; ++g) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   // 1 MFMA
         __builtin_amdgcn_sched_group_barrier(0x002, NKB == 8 ? WG_X6_VALU : (NKB == 4 ? WG_X6_VALU4 : WG_X6_VALU2), 0);  // splits
-#ifdef WG_X6_EXTRA
-        if (NKB == 8 && g % WG_X6_EXTRA == 0) __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-#endif
         if (g >= G0 && g < G0 + NL) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);       // one load of stage s + 2
       }
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-#endif
   auto interleave_stage = [&]() {
-#ifndef WG_X6_OLD
-    if constexpr (BF == 3) {
-      __builtin_amdgcn_sched_group_barrier(0x002, WG_X6_HEAD, 0);  // the splits of both rows and of column block 0
 #pragma unroll
-      for (int g = 0; g < 12 * NKB; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, WG_X6_VALU, 0);  // VALU of the next column block's splits / addresses
-#if WG_X6_VMEM
-        if (g % WG_X6_VMEM == 0) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // one of the next stage's loads
-#endif
-      }
-      return;
-    }
-#endif
-#ifdef WG_F32_SPREAD
-    if constexpr (BF == 0 && XV && DV) {  // one load behind each of the first MFMAs (hipcc otherwise issues them in blocks of 4-8)
-#pragma unroll
-      for (int g = 0; g < WG_PAIRS * 2 * (1 + NKB / 4); ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x006, WG_F32_SPREAD, 0);
-      }
-      return;
-    }
-#endif
-#pragma unroll
-    for (int g = 0; g < (BF == 3 ? 96 : (BF ? 16 : WG_PAIRS * 4)); ++g) {
+    for (int g = 0; g < (BF ? 16 : WG_PAIRS * 4); ++g) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
       __builtin_amdgcn_sched_group_barrier(0x026, 2, 0);  // up to 2 of VALU / SALU / VMEM read
     }
@@ -569,7 +462,7 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
       const long long tc = t < cnt ? t : cnt - 1;
       const long long m0 = (first + tc * G) * step;
 #pragma unroll
-      for (int p = 0; p < NP; ++p) load_row_m(buf, p, m0);
+      for (int p = 0; p < NP; ++p) load_row_b(buf, p, m0);
     };
     if (cnt > 0) {
       any = true;
@@ -578,24 +471,11 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
         for (int b = 0; b < NBUF - 1; ++b) load_stage(b, b);
       } else {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) load_row_m(0, p, first * step);
+        for (int p = 0; p < NP; ++p) load_row_b(0, p, first * step);
       }
     }
     long long j = 0;
-#if !defined(WG_X6_OLD) && !defined(WG_X6_INSTAGE)
     if constexpr (BF == 3) {
-#ifdef WG_X6_NEAR
-      if (cnt > 0) {
-        x6_head(0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll 1
-      for (; j + 1 < cnt; j += 2) {
-        x6_stage(0, [&](int c) { load_stage(c, j + 1); });
-        x6_stage(1, [&](int c) { load_stage(c, j + 2); });
-      }
-      if (j < cnt) x6_stage(0, [&](int c) { load_stage(c, j + 1); });
-#else
       if (cnt > 0) {
         load_stage(1, 1);
         x6_head(0);
@@ -607,10 +487,7 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
         x6_stage(1, [&](int c) { load_stage(c, j + 3); });
       }
       if (j < cnt) x6_stage(0, [&](int c) { load_stage(c, j + 2); });  // (its look-ahead works on a repeat of the last stage: unused)
-#endif
-    } else
-#endif
-    if constexpr (NBUF == 4) {
+    } else if constexpr (NBUF == 4) {
 #pragma unroll 1
       for (; j + 3 < cnt; j += 4) {
         load_stage(3, j + 3);
@@ -642,13 +519,13 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
         // block between two MFMA bursts they left the matrix pipe idle for ~10 % of the loop.  Straight-line body
         // (the prefetch index is clamped, not branched on) so that the scheduler can interleave.
 #pragma unroll
-        for (int p = 0; p < NP; ++p) load_row_m(1, p, m0 + gs);
+        for (int p = 0; p < NP; ++p) load_row_b(1, p, m0 + gs);
         mma_stage(0);
         interleave_stage();
         __builtin_amdgcn_sched_barrier(0);
         const long long m2 = (j + 2 < cnt) ? m0 + 2 * gs : m0 + gs;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) load_row_m(0, p, m2);
+        for (int p = 0; p < NP; ++p) load_row_b(0, p, m2);
         mma_stage(1);
         interleave_stage();
         __builtin_amdgcn_sched_barrier(0);
@@ -668,9 +545,6 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
     vprefix += n_full + (rem > 0 ? 1 : 0);
   }
   if (!any) return;  // wave-uniform: nothing accumulated, nothing to flush
-#ifdef RSN_DIAG_WG_NO_FLUSH  // timing ablation (wrong results): what the atomic flush costs
-  if (acc[0][0][0] != 12345.678f) return;
-#endif
 
   // flush: C/D layout col = lane&31 (input-column slot), row = (r&3) + 8*(r>>2) + 4*h (output-row slot).  The
   // wave-private LDS tile turns "lane i holds columns i*NKB+kb" back into "lane i holds column kb*32+i" so that one
@@ -717,10 +591,6 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
   }
 }
 
-#if defined(WG_X6_STAGED) || defined(WG_F32_STAGED)
-#include "rsn_wgrad_staged_probe.h"  // LDS-staged probe kernels: diagnostic builds only
-#endif
-
 static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf16 = 0) {
   WGradArgs& a = J.j[0];  // the jobs of a launch share shape, leading dimensions and segment lengths (checked by the caller)
   const bool xb = (operand_bf16 & 1) != 0, db = (operand_bf16 & 2) != 0;  // rows that ARE bf16 in memory
@@ -730,7 +600,7 @@ static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf
   const int cached_cus = rsn_device_cus();
   // grid: every workgroup pays one atomic flush of the output tile (chip-wide ~1.3 TB/s of added bytes) and the
   // waves share the stages; T(G) = stages / (G * nsub) * t_stage + G * t_flush is smallest at G = sqrt(...)
-  const int nkb = a.k_in > 128 ? 8 : (a.k_in > 64 ? 4 : 2), nkb_ = nkb;
+  const int nkb = a.k_in > 128 ? 8 : (a.k_in > 64 ? 4 : 2);
   // vector-load variants need whole NKB-column groups and aligned rows; anything else takes the scalar-load path
   bool xv = a.k_in % nkb == 0 && a.ld_x % (xb ? nkb : (nkb >= 4 ? 4 : 2)) == 0;
   bool dv = a.n_out > 32 && a.ld_dy % 2 == 0 && a.ld_dy >= a.n_out + (a.n_out & 1);
@@ -754,51 +624,14 @@ static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf
     const long long n_s = a.seg_begin[s + 1] - a.seg_begin[s];
     stages += (n_s + stage_pts - 1) / stage_pts;
   }
-  const double t_stage = bf16 ? (a.n_out > 32 ? 2 : 1) * nkb_ * 32 / 1.9e9 * (mode == RSN_MMA_BF16X6 ? 6 : 2.5)  // 1 product: HBM-bound, ~2.5x the MFMA time
-                              : WG_PAIRS * (a.n_out > 32 ? 2 : 1) * nkb_ * 64 / 2.1e9;
+  const double t_stage = bf16 ? (a.n_out > 32 ? 2 : 1) * nkb * 32 / 1.9e9 * (mode == RSN_MMA_BF16X6 ? 6 : 2.5)  // 1 product: HBM-bound, ~2.5x the MFMA time
+                              : WG_PAIRS * (a.n_out > 32 ? 2 : 1) * nkb * 64 / 2.1e9;
   const double t_flush = (double)a.n_out * a.k_in * 4.0 / 1.3e12 + 2e-8;
   long long grid = (long long)(sqrt((double)stages * t_stage / (nsub * t_flush)) + 0.5);  // workgroups per job
   if (grid > cached_cus / J.n_jobs) grid = cached_cus / J.n_jobs;
   if (grid < 1) grid = 1;
   grid *= J.n_jobs;  // workgroup i: job i % n_jobs
   hipStream_t st = (hipStream_t)stream;
-  // split-bf16 over more than 128 output rows: operand rows staged through LDS (rsn_wgrad_x6s_kernel) where the layout allows
-#ifdef WG_X6_STAGED
-  bool staged = xv && dv && bf16 && mode == RSN_MMA_BF16X6 && a.n_out > 128 && nkb >= 4 && a.ld_x % 4 == 0 && a.ld_dy % 4 == 0;
-  for (int jb = 0; jb < J.n_jobs && staged; ++jb)
-    for (int s = 0; s < a.n_seg; ++s) {
-      const long long n_s = a.seg_begin[s + 1] - a.seg_begin[s];
-      staged = staged && (uintptr_t)J.j[jb].x[s] % 16 == 0 && (uintptr_t)J.j[jb].dy[s] % 16 == 0 &&
-               n_s * a.ld_x * 4 < (1ll << 31) - (1ll << 27) && n_s * a.ld_dy * 4 < (1ll << 31) - (1ll << 27);
-    }
-  if (staged) {
-    if (nkb == 8)
-      hipLaunchKernelGGL((rsn_wgrad_x6s_kernel<8>), dim3((unsigned)grid), dim3(256), 0, st, J);
-    else
-      hipLaunchKernelGGL((rsn_wgrad_x6s_kernel<4>), dim3((unsigned)grid), dim3(256), 0, st, J);
-    RSN_HIP(hipGetLastError());
-    return RSN_OK;
-  }
-#endif
-#ifdef WG_F32_STAGED
-  {
-    bool st32 = xv && dv && !bf16 && a.n_out > 128 && nkb >= 4 && a.ld_x % 4 == 0 && a.ld_dy % 4 == 0;
-    for (int jb = 0; jb < J.n_jobs && st32; ++jb)
-      for (int s = 0; s < a.n_seg; ++s) {
-        const long long n_s = a.seg_begin[s + 1] - a.seg_begin[s];
-        st32 = st32 && (uintptr_t)J.j[jb].x[s] % 16 == 0 && (uintptr_t)J.j[jb].dy[s] % 16 == 0 &&
-               n_s * a.ld_x * 4 < (1ll << 31) - (1ll << 27) && n_s * a.ld_dy * 4 < (1ll << 31) - (1ll << 27);
-      }
-    if (st32) {
-      if (nkb == 8)
-        hipLaunchKernelGGL((rsn_wgrad_f32s_kernel<8>), dim3((unsigned)grid), dim3(256), 0, st, J);
-      else
-        hipLaunchKernelGGL((rsn_wgrad_f32s_kernel<4>), dim3((unsigned)grid), dim3(256), 0, st, J);
-      RSN_HIP(hipGetLastError());
-      return RSN_OK;
-    }
-  }
-#endif
 #define RSN_WG(NKBV)                                                                                           \
   do {                                                                                                         \
     if (xv && dv && bf16 && mode == RSN_MMA_BF16X6)                                                            \

@@ -163,32 +163,23 @@ def test_bench_flop_accounting_matches_survey():
     assert bench.algorithmic_macs(4, 128)["forward"] == 100736
 
 
-def test_diagnostic_macros_cannot_enter_the_product_library(tmp_path):
-    """Timing ablations (RSN_RING_NO_*, RSN_R16_*, RSN_DIAG_NO_SAVED_ROWS: wrong results by construction) compile only under
-    -DRSN_DIAG_BUILD, which the product flags never carry, and a diagnostic library reports RSN_ABI_DIAG_FLAG in
-    rsn_abi_version() (the loader refuses it at the product path)."""
-    import shutil
-    import subprocess
-
+def test_kernel_sources_have_one_build():
+    """There is one build of the kernels: no file under csrc/ holds a preprocessor conditional, include/rsn.h only its include
+    guard and the C++ linkage blocks, and no product flag defines a macro.  The LDS-staged weight-gradient kernels of an earlier
+    experiment are not in the library."""
     from reflect_sampling_nerf_amd import _build
 
-    assert not any("RSN_DIAG_BUILD" in f or f.startswith("-DRSN_R") for f in _build.FLAGS)
-    lib = _abi.load_library()
-    assert lib.rsn_abi_version() & _abi.RSN_ABI_DIAG_FLAG == 0
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = tmp_path / "probe.hip"
-    src.write_text('#include "rsn_common.h"\nint main() { return 0; }\n')
-    base = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", os.path.join(REPO, "include"), "-I",
-            _build.CSRC, str(src)]
-    assert subprocess.run(base, capture_output=True).returncode == 0
-    bad = subprocess.run(base + ["-DRSN_R16_NO_MFMA"], capture_output=True, text=True)
-    assert bad.returncode != 0 and "RSN_DIAG_BUILD" in bad.stderr
-    assert subprocess.run(base + ["-DRSN_R16_NO_MFMA", "-DRSN_DIAG_BUILD"], capture_output=True).returncode == 0
-    # the LDS-staged weight-gradient probe kernels (csrc/rsn_wgrad_staged_probe.h) are diagnostic builds only as well
-    for macro in ("-DWG_X6_STAGED", "-DWG_F32_STAGED"):
-        bad = subprocess.run(base + [macro], capture_output=True, text=True)
-        assert bad.returncode != 0 and "RSN_DIAG_BUILD" in bad.stderr, macro
-    blob = open(os.path.join(REPO, "reflect_sampling_nerf_amd", "librsn_hip.so"), "rb").read()
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b")
+    for name in sorted(os.listdir(_build.CSRC)):
+        with open(os.path.join(_build.CSRC, name)) as fh:
+            lines = [i + 1 for i, line in enumerate(fh) if cond.match(line)]
+        assert not lines, f"csrc/{name}: preprocessor conditional at line(s) {lines}"
+    with open(os.path.join(REPO, "include", "rsn.h")) as fh:
+        conds = [" ".join(line.split()) for line in fh if cond.match(line)]
+    assert conds == ["#ifndef RSN_H", "#ifdef __cplusplus", "#ifdef __cplusplus"], conds
+    flags = [*_build.FLAGS, *(f for per_file in _build.SOURCE_FLAGS.values() for f in per_file)]
+    assert not [f for f in flags if f.startswith("-D")], flags
+    blob = open(LIB_PATH, "rb").read()
     assert b"rsn_wgrad_x6s_kernel" not in blob and b"rsn_wgrad_f32s_kernel" not in blob
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Runs one training-mode level on three shapes (37 x 32 with / without normals, 5 x 13) with whatever library RSN_LIBRARY names
-(default: the product) and saves every output and saved buffer; tools/level_dump_cmp.py compares two such files bit for bit.  Used to
-show that the exact-fp32 ring probe (tools/probes/rsn_field_f32_ring.hip) reproduces the slab kernel (profiles/r04_f32_ring.txt).
+(default: the product) and saves every output and saved buffer; tools/level_dump_cmp.py compares two such files bit for bit, e.g. the
+libraries of two checkouts (profiles/r04_f32_ring.txt used it on a build of the exact-fp32 ring form, since removed).
 Usage: [RSN_LIBRARY=<.so>] python tools/level_dump.py out.pt"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

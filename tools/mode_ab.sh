@@ -1,6 +1,7 @@
 #!/bin/bash
-# The training step in one MMA mode with the product library against variant builds, on one box.
-# Usage: tools/mode_ab.sh <tag> <mma mode> <variant .so> [...]
+# The training step in one MMA mode with the product library against other builds of it (e.g. librsn_hip.so of another
+# checkout), on one box.
+# Usage: tools/mode_ab.sh <tag> <mma mode> <other .so> [...]
 TAG=$1; MODE=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 B="python bench.py --mma $MODE --no-secondary --no-cpu-baseline --steps 10 --warmup 3"

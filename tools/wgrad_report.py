@@ -18,7 +18,6 @@ PEAK = 157.3e12
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--define", action="append", default=[], help="extra -D macros: times an experimental build")
     ap.add_argument("--quick", action="store_true", help="only the two large point counts")
     ap.add_argument("--mode", default="f32", choices=["f32", "bf16x6", "bf16"], help="MMA mode of the reduction")
     args = ap.parse_args()
@@ -28,12 +27,7 @@ def main():
 
     train_graph._WGRAD_MODE = {"f32": 0, "bf16x6": 1, "bf16": 3}[args.mode]
 
-    if args.define:
-        from tools._variant import build_variant
-
-        pkg.load_library(build_variant(args.define))
-    else:
-        pkg.load_library()
+    pkg.load_library()
     dev = torch.device("cuda", 0)
     shapes = [(256, 256), (256, 104), (128, 256), (128, 40), (16, 256), (3, 128)]
     rows = []
