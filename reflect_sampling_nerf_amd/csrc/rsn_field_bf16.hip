@@ -108,6 +108,8 @@ __global__ __launch_bounds__(256, 2) void rsn_field_bf16_kernel(const FieldArgs 
       }
     } else {
       // ---------------- encode (fp32, as rsn_field.hip) -----------------
+      // (its own copy of point_gaussian, rsn_field_common.h: with the shared function hipcc spills more at width 256 -- see
+      // profiles/shared_point_maths_static.txt -- although the code is the same)
       if (a.mode == RSN_MODE_FRUSTUM) {
         const long long ray = pc / a.S;
         const int s = (int)(pc - ray * a.S);
@@ -208,30 +210,9 @@ __global__ __launch_bounds__(256, 2) void rsn_field_bf16_kernel(const FieldArgs 
       rho = (a.mode == RSN_MODE_EMB && a.rough_in) ? a.rough_in[pc] : softplus_f(rough_raw);
       dcol[0] = sigmoid_f(r0); dcol[1] = sigmoid_f(r1); dcol[2] = sigmoid_f(r2);
       tcol[0] = sigmoid_f(r4); tcol[1] = sigmoid_f(r5); tcol[2] = sigmoid_f(r6);
-      if (a.mode != RSN_MODE_INF && valid) {
-        if (h == 0) {
-          float nrm = fmaxf(sqrtf(r1 * r1 + r2 * r2 + r3 * r3), 1e-12f);
-          float nx = -(r1 / nrm), ny = -(r2 / nrm), nz = -(r3 / nrm);
-          nrm = fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-12f);
-          nx /= nrm; ny /= nrm; nz /= nrm;
-          if (a.out.sigma) a.out.sigma[pc] = softplus_f(r0 + a.density_bias);
-          if (a.out.raw_density) a.out.raw_density[pc] = r0;
-          if (a.out.pred_normals) {
-            a.out.pred_normals[pc * 3 + 0] = nx;
-            a.out.pred_normals[pc * 3 + 1] = ny;
-            a.out.pred_normals[pc * 3 + 2] = nz;
-          }
-          if (a.out.n_dot_d) a.out.n_dot_d[pc] = vd[0] * nx + vd[1] * ny + vd[2] * nz;
-          if (a.out.roughness) a.out.roughness[pc] = sigmoid_f(r4);
-          if (a.out.raw_roughness) a.out.raw_roughness[pc] = r4;
-        } else {
-          if (a.out.diff) {
-            a.out.diff[pc * 3 + 0] = dcol[0]; a.out.diff[pc * 3 + 1] = dcol[1]; a.out.diff[pc * 3 + 2] = dcol[2];
-          }
-          if (a.out.tint) {
-            a.out.tint[pc * 3 + 0] = tcol[0]; a.out.tint[pc * 3 + 1] = tcol[1]; a.out.tint[pc * 3 + 2] = tcol[2];
-          }
-        }
+      if (valid) {  // rows h and h + 2 of the heads
+        head_outputs_row<false, false>(h == 0 ? 0 : 1, a, a.density_bias, pc, make_float4(r0, r1, r2, r3), dcol, vd);
+        head_outputs_row<false, false>(h == 0 ? 2 : 3, a, a.density_bias, pc, make_float4(r4, r5, r6, 0.0f), tcol, vd);
       }
       store_h<NB + 1, NB, false>(acc, X);  // bottleneck output (no activation): the x-part of mlp_mid's input
     }
@@ -269,18 +250,7 @@ __global__ __launch_bounds__(256, 2) void rsn_field_bf16_kernel(const FieldArgs 
       f32x16 accr[1];
       init_acc<1>(accr, pk + a.L.b_rgb, h);
       gemm_h<1>(accr, pk + a.L.h_rgb, X, 8, ln);
-      if (h == 1 && valid && a.out.color) {
-        const float m0 = sigmoid_f(accr[0][0]);
-        const float m1 = sigmoid_f(accr[0][1]);
-        const float m2 = sigmoid_f(accr[0][2]);
-        if (a.mode == RSN_MODE_INF || (a.mode == RSN_MODE_EMB && !a.out.diff && !a.out.tint)) {
-          a.out.color[pc * 3 + 0] = m0; a.out.color[pc * 3 + 1] = m1; a.out.color[pc * 3 + 2] = m2;
-        } else {
-          a.out.color[pc * 3 + 0] = dcol[0] + tcol[0] * m0;
-          a.out.color[pc * 3 + 1] = dcol[1] + tcol[1] * m1;
-          a.out.color[pc * 3 + 2] = dcol[2] + tcol[2] * m2;
-        }
-      }
+      if (h == 1 && valid) colour_out<false, false>(a, pc, accr[0][0], accr[0][1], accr[0][2], dcol, tcol);
     }
   }
 }
@@ -334,13 +304,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_ring16_kernel(const Fie
   if (blockIdx.x >= n_tiles) return;  // workgroup-uniform
   const float* __restrict__ pk = a.packed;
 
-  // ---- biases -> LDS, in the PACKED row order of the 16x32 stream (rsn_pack.hip, rows_perm16: packed row 16 b + 4 g + r is
-  // feature 32 (b / 2) + 8 g + 4 (b % 2) + r).  Heads: the 32-entry table of the 32x32 layout keeps rows 0..15 = the 16-row
-  // heads block here (not permuted, like the RGB rows).
-  for (int i = threadIdx.x; i < a.num_layers * 256; i += 512) bias[i] = pk[a.L.b[i >> 8] + r16_feature(i & 255)];
-  for (int i = threadIdx.x; i < 288; i += 512) bias[RING_MAX_LAYERS * 256 + i] = pk[a.L.b_bh + (i < 256 ? r16_feature(i) : i)];
-  if (threadIdx.x < 128) bias[RING_MAX_LAYERS * 256 + 288 + threadIdx.x] = pk[a.L.b_mid + r16_feature(threadIdx.x)];
-  if (threadIdx.x < 32) bias[RING_MAX_LAYERS * 256 + 288 + 128 + threadIdx.x] = pk[a.L.b_rgb + threadIdx.x];
+  ring_fill_tables<false>(bias, pk, a.L, a.num_layers);
 
   Ring r;
   r.src = reinterpret_cast<const char*>(pk + a.L.q_stream) + wid * (RingCfg<8>::PPW * 1024);
@@ -381,6 +345,8 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_ring16_kernel(const Fie
       const unsigned pt = p0 + 16 * po + m;
       const size_t pcc = pt < n_points ? pt : n_points - 1;
       float mc[3] = {0.0f, 0.0f, 0.0f}, vc[3] = {0.0f, 0.0f, 0.0f}, dd[3] = {0.0f, 0.0f, 0.0f};
+      // (its own copy of point_gaussian, rsn_field_common.h: with the shared function hipcc spills more in this kernel -- see
+      // profiles/shared_point_maths_static.txt -- although the code is the same)
       if (a.mode == RSN_MODE_FRUSTUM) {
         const unsigned rayu = (unsigned)pcc / (unsigned)a.S;
         const int s = (int)((unsigned)pcc - rayu * (unsigned)a.S);
@@ -523,34 +489,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_ring16_kernel(const Fie
           }
         }
         dcol[p][0] = fast_sigmoid(r0); dcol[p][1] = fast_sigmoid(r1); dcol[p][2] = fast_sigmoid(r2);
-        if (a.mode != RSN_MODE_INF && valid[p]) {
-          const size_t q = pc[p];
-          if (g == 0) {
-            float nrm = fmaxf(sqrtf(r1 * r1 + r2 * r2 + r3 * r3), 1e-12f);
-            float nx = -(r1 / nrm), ny = -(r2 / nrm), nz = -(r3 / nrm);
-            nrm = fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-12f);
-            nx /= nrm; ny /= nrm; nz /= nrm;
-            if (a.out.sigma) a.out.sigma[q] = fast_softplus(r0 + a.density_bias);
-            if (a.out.raw_density) a.out.raw_density[q] = r0;
-            if (a.out.pred_normals) {
-              a.out.pred_normals[q * 3 + 0] = nx;
-              a.out.pred_normals[q * 3 + 1] = ny;
-              a.out.pred_normals[q * 3 + 2] = nz;
-            }
-            if (a.out.n_dot_d) a.out.n_dot_d[q] = vd[p][0] * nx + vd[p][1] * ny + vd[p][2] * nz;
-          } else if (g == 1) {
-            if (a.out.diff) {
-              a.out.diff[q * 3 + 0] = dcol[p][0]; a.out.diff[q * 3 + 1] = dcol[p][1]; a.out.diff[q * 3 + 2] = dcol[p][2];
-            }
-          } else if (g == 2) {
-            if (a.out.roughness) a.out.roughness[q] = fast_sigmoid(r0);
-            if (a.out.raw_roughness) a.out.raw_roughness[q] = r0;
-          } else {
-            if (a.out.tint) {
-              a.out.tint[q * 3 + 0] = dcol[p][0]; a.out.tint[q * 3 + 1] = dcol[p][1]; a.out.tint[q * 3 + 2] = dcol[p][2];
-            }
-          }
-        }
+        if (valid[p]) head_outputs_row<true, false>(g, a, a.density_bias, pc[p], make_float4(r0, r1, r2, r3), dcol[p], vd[p]);
       }
     }
     {
@@ -584,18 +523,8 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_ring16_kernel(const Fie
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         // mid RGB sits on the g == 1 lanes (rows 4..6), like diff; tint comes over from the g == 3 lane of the point
-        const float m0 = fast_sigmoid(accr[0][p][0]), m1 = fast_sigmoid(accr[0][p][1]), m2 = fast_sigmoid(accr[0][p][2]);
-        const float t0 = __shfl(dcol[p][0], 48 + m, 64), t1 = __shfl(dcol[p][1], 48 + m, 64), t2 = __shfl(dcol[p][2], 48 + m, 64);
-        if (g == 1 && valid[p] && a.out.color) {
-          const size_t q = pc[p];
-          if (a.mode == RSN_MODE_INF) {
-            a.out.color[q * 3 + 0] = m0; a.out.color[q * 3 + 1] = m1; a.out.color[q * 3 + 2] = m2;
-          } else {
-            a.out.color[q * 3 + 0] = dcol[p][0] + t0 * m0;
-            a.out.color[q * 3 + 1] = dcol[p][1] + t1 * m1;
-            a.out.color[q * 3 + 2] = dcol[p][2] + t2 * m2;
-          }
-        }
+        const float tcol[3] = {__shfl(dcol[p][0], 48 + m, 64), __shfl(dcol[p][1], 48 + m, 64), __shfl(dcol[p][2], 48 + m, 64)};
+        if (g == 1 && valid[p]) colour_out<true, false>(a, pc[p], accr[0][p][0], accr[0][p][1], accr[0][p][2], dcol[p], tcol);
       }
     }
   }

@@ -153,11 +153,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
   const float* __restrict__ pk = P.packed;
   const int L = P.num_layers;
 
-  for (int i = threadIdx.x; i < L * 256; i += 512) bias[i] = pk[P.L.b[i >> 8] + r16_feature(i & 255)];
-  for (int i = threadIdx.x; i < 288; i += 512) bias[RING_MAX_LAYERS * 256 + i] = pk[P.L.b_bh + (i < 256 ? r16_feature(i) : i)];
-  if (threadIdx.x < 128) bias[RING_MAX_LAYERS * 256 + 288 + threadIdx.x] = pk[P.L.b_mid + r16_feature(threadIdx.x)];
-  if (threadIdx.x < 32) bias[RING_MAX_LAYERS * 256 + 288 + 128 + threadIdx.x] = pk[P.L.b_rgb + threadIdx.x];
-  if (threadIdx.x < 256) bias[RING_BIAS_FLOATS + threadIdx.x] = pk[P.L.v_density + threadIdx.x];
+  ring_fill_tables<true>(bias, pk, P.L, L);
 
   RingT<RT_LEAD_FWD> r;
   bf16x8 Wf[RING_FIFO];
@@ -166,10 +162,9 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
   const unsigned one2 = 0x00010001u;
 
   for (long long gtile = blockIdx.x; gtile < T.n_tiles; gtile += gridDim.x) {
-    const int jk = (gtile >= T.tb1 ? 1 : 0) + (gtile >= T.tb2 ? 1 : 0);  // workgroup-uniform
-    const FieldJob& a = J.j[jk];
-    const unsigned n_points = (unsigned)(jk == 0 ? T.np0 : (jk == 1 ? T.np1 : T.np2));
-    const unsigned tile = (unsigned)(gtile - (jk == 0 ? 0 : (jk == 1 ? T.tb1 : T.tb2)));
+    const TileAt ta = tile_at(T, gtile);  // workgroup-uniform
+    const FieldJob& a = J.j[ta.job];
+    const unsigned n_points = (unsigned)ta.n_points, tile = (unsigned)ta.tile;
     const unsigned p0 = tile * 256 + wid * 32;   // every wave walks every tile (barriers, DMA shares); rows = 0 past the end
     const int rows = p0 >= n_points ? 0 : (int)(n_points - p0 < 32u ? n_points - p0 : 32u);
     const long long n_max = a.act_stride / W;   // points the saved buffers are sized for
@@ -191,6 +186,8 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
       const unsigned pt = p0 + 16 * po + m;
       const size_t pcc = pt < n_points ? pt : (n_points ? n_points - 1 : 0);
       float mc[3] = {0.0f, 0.0f, 0.0f}, vc[3] = {0.0f, 0.0f, 0.0f}, dd[3] = {0.0f, 0.0f, 0.0f};
+      // (its own copy of point_gaussian, rsn_field_common.h: with the shared function hipcc spills more in this kernel -- see
+      // profiles/shared_point_maths_static.txt -- although the code is the same)
       if (a.mode == RSN_MODE_FRUSTUM) {
         const unsigned rayu = (unsigned)pcc / (unsigned)a.S;
         const int s = (int)((unsigned)pcc - rayu * (unsigned)a.S);
@@ -332,40 +329,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
           }
         }
         dcol[p][0] = fast_sigmoid(r0); dcol[p][1] = fast_sigmoid(r1); dcol[p][2] = fast_sigmoid(r2);
-        if (valid[p]) {
-          const size_t q = pc[p];
-          if (g == 0) {
-            if (a.saved.heads) { a.saved.heads[q * 8 + 0] = r1; a.saved.heads[q * 8 + 1] = r2; a.saved.heads[q * 8 + 2] = r3; }
-            if (a.mode != RSN_MODE_INF) {
-              float nrm = fmaxf(sqrtf(r1 * r1 + r2 * r2 + r3 * r3), 1e-12f);
-              float nx = -(r1 / nrm), ny = -(r2 / nrm), nz = -(r3 / nrm);
-              nrm = fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-12f);
-              nx /= nrm; ny /= nrm; nz /= nrm;
-              if (a.out.sigma) a.out.sigma[q] = fast_softplus(r0 + P.density_bias);
-              if (a.out.raw_density) a.out.raw_density[q] = r0;
-              if (a.out.pred_normals) {
-                a.out.pred_normals[q * 3 + 0] = nx;
-                a.out.pred_normals[q * 3 + 1] = ny;
-                a.out.pred_normals[q * 3 + 2] = nz;
-              }
-              if (a.out.n_dot_d) a.out.n_dot_d[q] = vd[p][0] * nx + vd[p][1] * ny + vd[p][2] * nz;
-            }
-          } else if (g == 1) {
-            if (a.mode != RSN_MODE_INF && a.out.diff) {
-              a.out.diff[q * 3 + 0] = dcol[p][0]; a.out.diff[q * 3 + 1] = dcol[p][1]; a.out.diff[q * 3 + 2] = dcol[p][2];
-            }
-          } else if (g == 2) {
-            if (a.saved.heads) a.saved.heads[q * 8 + 3] = r0;
-            if (a.mode != RSN_MODE_INF) {
-              if (a.out.roughness) a.out.roughness[q] = fast_sigmoid(r0);
-              if (a.out.raw_roughness) a.out.raw_roughness[q] = r0;
-            }
-          } else {
-            if (a.mode != RSN_MODE_INF && a.out.tint) {
-              a.out.tint[q * 3 + 0] = dcol[p][0]; a.out.tint[q * 3 + 1] = dcol[p][1]; a.out.tint[q * 3 + 2] = dcol[p][2];
-            }
-          }
-        }
+        if (valid[p]) head_outputs_row<true, true>(g, a, P.density_bias, pc[p], make_float4(r0, r1, r2, r3), dcol[p], vd[p]);
       }
     }
     // ---------------- bottleneck (the embedding's rows and the last layer's bits leave from this GEMM) -----------------
@@ -430,21 +394,8 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_train_kernel(const Fiel
       });
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        const float m0 = fast_sigmoid(accr[0][p][0]), m1 = fast_sigmoid(accr[0][p][1]), m2 = fast_sigmoid(accr[0][p][2]);
-        const float t0 = __shfl(dcol[p][0], 48 + m, 64), t1 = __shfl(dcol[p][1], 48 + m, 64), t2 = __shfl(dcol[p][2], 48 + m, 64);
-        if (g == 1 && valid[p]) {
-          const size_t q = pc[p];
-          if (a.saved.heads) *reinterpret_cast<float4*>(a.saved.heads + q * 8 + 4) = make_float4(m0, m1, m2, 0.0f);
-          if (a.out.color) {
-            if (a.mode == RSN_MODE_INF) {
-              a.out.color[q * 3 + 0] = m0; a.out.color[q * 3 + 1] = m1; a.out.color[q * 3 + 2] = m2;
-            } else {
-              a.out.color[q * 3 + 0] = dcol[p][0] + t0 * m0;
-              a.out.color[q * 3 + 1] = dcol[p][1] + t1 * m1;
-              a.out.color[q * 3 + 2] = dcol[p][2] + t2 * m2;
-            }
-          }
-        }
+        const float tcol[3] = {__shfl(dcol[p][0], 48 + m, 64), __shfl(dcol[p][1], 48 + m, 64), __shfl(dcol[p][2], 48 + m, 64)};
+        if (g == 1 && valid[p]) colour_out<true, true>(a, pc[p], accr[0][p][0], accr[0][p][1], accr[0][p][2], dcol[p], tcol);
       }
     }
 
@@ -532,23 +483,14 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJob
 
   RingT<RT_LEAD_BWD> r;
   bf16x8 Wf[RING_FIFO];
-  // the walk: the whole transposed stream; without an input gradient the two encoded-input pieces are jumped over
-  {
-    const RsnPackedLayout& Y = P.L;
-    int e0, j0, e1, j1;
-    if (INPUT) { e0 = Y.t_g_end; j0 = Y.t_g_begin; e1 = -1; j1 = 0; }
-    else if (Y.t_g_encskip >= 0) { e0 = Y.t_g_encskip; j0 = Y.t_g_encskip + 4; e1 = Y.t_g_enc0; j1 = Y.t_g_begin; }
-    else { e0 = Y.t_g_enc0; j0 = Y.t_g_begin; e1 = -1; j1 = 0; }
-    ring_start(r, pk, Y, smem, wid, lane, Y.t_g_begin, e0, j0, e1, j1, Wf);
-  }
+  ring_start_bwd<INPUT>(r, pk, P.L, smem, wid, lane, Wf);
   const unsigned one2 = 0x00010001u;
   const bf16x8 zero8 = {};
 
   for (long long gtile = blockIdx.x; gtile < T.n_tiles; gtile += gridDim.x) {
-    const int jk = (gtile >= T.tb1 ? 1 : 0) + (gtile >= T.tb2 ? 1 : 0);  // workgroup-uniform
-    const BwdJob& a = J.j[jk];
-    const unsigned n_points = (unsigned)(jk == 0 ? T.np0 : (jk == 1 ? T.np1 : T.np2));
-    const unsigned tile = (unsigned)(gtile - (jk == 0 ? 0 : (jk == 1 ? T.tb1 : T.tb2)));
+    const TileAt ta = tile_at(T, gtile);  // workgroup-uniform
+    const BwdJob& a = J.j[ta.job];
+    const unsigned n_points = (unsigned)ta.n_points, tile = (unsigned)ta.tile;
     const unsigned p0 = tile * 256 + wid * 32;
     const int rows = p0 >= n_points ? 0 : (int)(n_points - p0 < 32u ? n_points - p0 : 32u);
     const long long n_max = a.act_stride / W;
@@ -573,79 +515,14 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJob
       const bool valid = pt < n_points;
       const size_t q = valid ? pt : (n_points ? n_points - 1 : 0);
       const float live = valid ? 1.0f : 0.0f;
-      float gcol[3] = {0.0f, 0.0f, 0.0f};
-      if (a.gin.color) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gcol[c] = a.gin.color[q * 3 + c] * live;
-      }
-      const float4 hd = *reinterpret_cast<const float4*>(a.saved.heads + q * 8);       // n_raw(3), rough_raw
-      const float4 md = *reinterpret_cast<const float4*>(a.saved.heads + q * 8 + 4);   // mid RGB (3)
-      const float mid[3] = {md.x, md.y, md.z};
-      float dif[3] = {0.0f, 0.0f, 0.0f}, tin[3] = {1.0f, 1.0f, 1.0f};
-      if (a.mode != RSN_MODE_INF) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          dif[c] = a.fwd.diff[q * 3 + c];
-          tin[c] = a.fwd.tint[q * 3 + c];
-        }
-      }
-      float dz[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) dz[c] = gcol[c] * tin[c] * (mid[c] * (1.0f - mid[c]));
-      if (g == 1 && valid && a.gout.dz_rgb) *reinterpret_cast<float4*>(a.gout.dz_rgb + q * 4) = make_float4(dz[0], dz[1], dz[2], 0.0f);
+      HeadGradIn hg;
+      head_grad_inputs(a, q, live, g == 1 && valid, hg);
       {
         uint4v w = {0u, 0u, 0u, 0u};
-        if (g == 1) { w[0] = pack2<false>(dz[0], dz[1]); w[1] = pack2<false>(dz[2], 0.0f); }
+        if (g == 1) { w[0] = pack2<false>(hg.dz[0], hg.dz[1]); w[1] = pack2<false>(hg.dz[2], 0.0f); }
         X0[p] = __builtin_bit_cast(bf16x8, w);
       }
-      float4 qh = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // heads rows 4 g + r
-      if (a.mode != RSN_MODE_INF) {
-        if (g == 0) {
-          const long long ray = (long long)(q / (unsigned)a.S);
-          const float rawd = a.fwd.raw_density[q];
-          const float gs = a.gin.sigma ? a.gin.sigma[q] * live : 0.0f;
-          qh.x = gs * fast_sigmoid(rawd + P.density_bias);  // softplus'
-          float dir[3], G[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-          for (int c = 0; c < 3; ++c) dir[c] = a.directions[ray * 3 + c];
-          if (a.gin.pred_normals) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) G[c] = a.gin.pred_normals[q * 3 + c] * live;
-          }
-          float gd = a.gin.n_dot_d ? a.gin.n_dot_d[q] * live : 0.0f;
-          if (a.gin.ray_pn_loss || a.gin.ray_ori_loss) {  // fused normal losses (model.py:403-407)
-            const float w = a.gin.weights[q] * live;
-            if (a.gin.ray_pn_loss) {
-              const float gw = a.gin.ray_pn_loss[ray] * w * -2.0f;
-#pragma unroll
-              for (int c = 0; c < 3; ++c) G[c] += gw * (a.saved.normals[q * 3 + c] - a.fwd.pred_normals[q * 3 + c]);
-            }
-            if (a.gin.ray_ori_loss) gd += a.gin.ray_ori_loss[ray] * w * (2.0f * fmaxf(a.fwd.n_dot_d[q], 0.0f));
-          }
-#pragma unroll
-          for (int c = 0; c < 3; ++c) G[c] += gd * dir[c];
-          const float nraw[3] = {hd.x, hd.y, hd.z};
-          const float len = fmaxf(sqrtf(nraw[0] * nraw[0] + nraw[1] * nraw[1] + nraw[2] * nraw[2]), 1e-12f);
-          const float v[3] = {-(nraw[0] / len), -(nraw[1] / len), -(nraw[2] / len)};
-          float gv[3], gu[3], gn[3];
-          normalize_bwd(v, G, gv);
-          gu[0] = -gv[0]; gu[1] = -gv[1]; gu[2] = -gv[2];
-          normalize_bwd(nraw, gu, gn);
-          qh.y = gn[0]; qh.z = gn[1]; qh.w = gn[2];
-        } else if (g == 1) {
-          qh.x = gcol[0] * (dif[0] * (1.0f - dif[0]));
-          qh.y = gcol[1] * (dif[1] * (1.0f - dif[1]));
-          qh.z = gcol[2] * (dif[2] * (1.0f - dif[2]));
-        } else if (g == 2) {
-          const float sr = fast_sigmoid(hd.w);
-          const float gr = a.gin.roughness ? a.gin.roughness[q] * live : 0.0f;
-          qh.x = gr * sr * (1.0f - sr);
-        } else {
-          qh.x = gcol[0] * mid[0] * (tin[0] * (1.0f - tin[0]));
-          qh.y = gcol[1] * mid[1] * (tin[1] * (1.0f - tin[1]));
-          qh.z = gcol[2] * mid[2] * (tin[2] * (1.0f - tin[2]));
-        }
-      }
+      const float4 qh = head_grad_row<true>(g, a, P.density_bias, q, live, hg);  // heads rows 4 g + r
       if (valid && a.gout.dz_heads) *reinterpret_cast<float4*>(a.gout.dz_heads + q * 16 + 4 * g) = qh;
       {
         uint4v w = {pack2<false>(qh.x, qh.y), pack2<false>(qh.z, qh.w), 0u, 0u};
@@ -756,26 +633,7 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJob
           dvar[c] = tot;
         }
         const unsigned pt = p0 + 16 * p + m;
-        if (g == 0 && pt < n_points && a.gout.d_input) {
-          const size_t q = pt;
-          float gg = 0.0f;
-          if (a.mode == RSN_MODE_FRUSTUM) {
-            const long long ray = (long long)(q / (unsigned)a.S);
-            const int s = (int)(q - (size_t)ray * a.S);
-            float o[3], d[3], dv[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { o[c] = a.origins[ray * 3 + c]; d[c] = a.directions[ray * 3 + c]; }
-            frustum_dvar_dpa(o, d, a.pixel_area[ray], a.bins[ray * (a.S + 1) + s], a.bins[ray * (a.S + 1) + s + 1], dv);
-            gg = dvar[0] * dv[0] + dvar[1] * dv[1] + dvar[2] * dv[2];
-          } else {  // INF: var_c = (0.6 sq)(1 - d_c^2)   (reflect_sampling_nerf_field.py:196)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-              const float dc = a.directions[q * 3 + c];
-              gg += dvar[c] * (0.6f * (1.0f - dc * dc));
-            }
-          }
-          a.gout.d_input[q] = gg;
-        }
+        if (g == 0 && pt < n_points && a.gout.d_input) a.gout.d_input[pt] = input_grad_of_dvar(a, (size_t)pt, dvar);
       }
     } else {  // dy[0] has no GEMM behind it on this path: its rows leave here
       const RowD dd = d_dy(0);
@@ -791,36 +649,9 @@ __global__ __launch_bounds__(512, 2) void rsn_field_bf16_bwd_kernel(const BwdJob
 
 // ------------------------------------------------------------------------------------------------ launchers
 int rsn_launch_field_bf16_train(long long n_tiles256, hipStream_t st, const FieldJobs& J) {
-  bool normals = false, plain = false;
-  for (int k = 0; k < J.n_jobs; ++k) {
-    const FieldJob& a = J.j[k];
-    RSN_REQUIRE(a.mode == RSN_MODE_FRUSTUM || a.mode == RSN_MODE_INF, RSN_ERR_UNSUPPORTED, "job %d: mode %d", k, a.mode);
-    RSN_REQUIRE((long long)a.n_rays * a.S < (1LL << 31), RSN_ERR_UNSUPPORTED, "job %d: 2^31 points or more", k);
-    if (a.saved.normals) normals = true; else plain = true;
-  }
-  RSN_REQUIRE(!(normals && plain), RSN_ERR_UNSUPPORTED,
-              "evaluations with and without analytic normals cannot share a launch (the weight ring walks one program)");
-  const int cus = rsn_device_cus();
-  const long long grid = n_tiles256 < (long long)cus ? n_tiles256 : (long long)cus;
-  if (normals) hipLaunchKernelGGL(rsn_field_bf16_train_kernel<true>, dim3((unsigned)grid), dim3(512), 0, st, J);
-  else hipLaunchKernelGGL(rsn_field_bf16_train_kernel<false>, dim3((unsigned)grid), dim3(512), 0, st, J);
-  RSN_HIP(hipGetLastError());
-  return RSN_OK;
+  return ring_launch_fwd(rsn_field_bf16_train_kernel<true>, rsn_field_bf16_train_kernel<false>, n_tiles256, st, J);
 }
 
 int rsn_launch_field_bf16_bwd(long long n_tiles256, hipStream_t st, const BwdJobs& J) {
-  bool input = false;
-  for (int k = 0; k < J.n_jobs; ++k) {
-    RSN_REQUIRE((long long)J.j[k].n_rays * J.j[k].S < (1LL << 31), RSN_ERR_UNSUPPORTED, "job %d: 2^31 points or more", k);
-    input = input || J.j[k].need_input_grad != 0;
-  }
-  for (int k = 0; k < J.n_jobs; ++k)
-    RSN_REQUIRE((J.j[k].need_input_grad != 0) == input, RSN_ERR_UNSUPPORTED,
-                "evaluations with and without an input gradient cannot share a launch (the weight ring walks one program)");
-  const int cus = rsn_device_cus();
-  const long long grid = n_tiles256 < (long long)cus ? n_tiles256 : (long long)cus;
-  if (input) hipLaunchKernelGGL(rsn_field_bf16_bwd_kernel<true>, dim3((unsigned)grid), dim3(512), 0, st, J);
-  else hipLaunchKernelGGL(rsn_field_bf16_bwd_kernel<false>, dim3((unsigned)grid), dim3(512), 0, st, J);
-  RSN_HIP(hipGetLastError());
-  return RSN_OK;
+  return ring_launch_bwd(rsn_field_bf16_bwd_kernel<true>, rsn_field_bf16_bwd_kernel<false>, n_tiles256, st, J);
 }

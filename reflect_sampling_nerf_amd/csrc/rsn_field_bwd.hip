@@ -37,30 +37,14 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
   float* Xf = reinterpret_cast<float*>(X);
 
   const BwdShared& P = J.s;
-  // the launch's tile space: job k owns tiles [tb_k, tb_k+1) of 128 points (its ray count may live on the device)
-  long long np0 = 0, np1 = 0, np2 = 0, tb1 = 0, tb2 = 0, n_tiles = 0;
-#pragma unroll
-  for (int k = 0; k < RSN_MAX_JOBS; ++k) {
-    if (k < J.n_jobs) {
-      int nr = J.j[k].n_rays;
-      if (J.j[k].n_dev) {
-        const int nd = *J.j[k].n_dev;
-        nr = nd < nr ? nd : nr;
-      }
-      const long long np = (long long)nr * J.j[k].S;
-      if (k == 0) np0 = np; else if (k == 1) np1 = np; else np2 = np;
-      n_tiles += (np + 127) / 128;
-    }
-    if (k == 0) tb1 = n_tiles; else if (k == 1) tb2 = n_tiles;
-  }
+  const TileJobs T = tile_space<128>(J);
   const float* __restrict__ pk = P.packed;
   const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
-  for (long long gtile = blockIdx.x; gtile < n_tiles; gtile += gridDim.x) {
-    const int jk = (gtile >= tb1 ? 1 : 0) + (gtile >= tb2 ? 1 : 0);  // workgroup-uniform
-    const BwdJob& a = J.j[jk];
-    const long long n_points = jk == 0 ? np0 : (jk == 1 ? np1 : np2);
-    const long long tile = gtile - (jk == 0 ? 0 : (jk == 1 ? tb1 : tb2));
+  for (long long gtile = blockIdx.x; gtile < T.n_tiles; gtile += gridDim.x) {
+    const TileAt ta = tile_at(T, gtile);  // workgroup-uniform
+    const BwdJob& a = J.j[ta.job];
+    const long long n_points = ta.n_points, tile = ta.tile;
     const long long p0 = tile * 128 + wid * 32;
     if (p0 >= n_points) continue;
     // opaque per-tile copy of the lane id: keeps hipcc from hoisting (and spilling) per-lane addresses out of the loop
@@ -89,31 +73,11 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
       return a.saved.relu_bits + ((((long long)l * (a.act_stride / W)) + pc) * 2 + h) * (NB / 2 > 2 ? NB / 2 : 2);
     };
     // ---------------- per-sample epilogue gradients -----------------
-    float gcol[3] = {0.0f, 0.0f, 0.0f};
-    if (a.gin.color) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) gcol[c] = a.gin.color[pc * 3 + c] * live;
-    }
-    const float4 hd = *reinterpret_cast<const float4*>(a.saved.heads + pc * 8);       // n_raw(3), rough_raw
-    const float4 md = *reinterpret_cast<const float4*>(a.saved.heads + pc * 8 + 4);   // mid RGB (3)
-    float mid[3] = {md.x, md.y, md.z};
-    float dif[3] = {0.0f, 0.0f, 0.0f}, tin[3] = {1.0f, 1.0f, 1.0f};
-    if (a.mode != RSN_MODE_INF) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        dif[c] = a.fwd.diff[pc * 3 + c];
-        tin[c] = a.fwd.tint[pc * 3 + c];
-      }
-    }
-    // RGB head: colour = diff + tint * mid (INF: colour = mid); mid = sigmoid(z)
-    float dz_rgb[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dz_rgb[c] = gcol[c] * tin[c] * (mid[c] * (1.0f - mid[c]));
-    if (h == 1 && valid && a.gout.dz_rgb)
-      *reinterpret_cast<float4*>(a.gout.dz_rgb + pc * 4) = make_float4(dz_rgb[0], dz_rgb[1], dz_rgb[2], 0.0f);
+    HeadGradIn hg;
+    head_grad_inputs(a, pc, live, h == 1 && valid, hg);
 
     // ---------------- stage 1: d hidden = W_rgb^T dz  (K = 32 with rows 4..6 live), ReLU mask -----------------
-    X[0] = (h == 1) ? make_float4(dz_rgb[0], dz_rgb[1], dz_rgb[2], 0.0f) : zero4;
+    X[0] = (h == 1) ? make_float4(hg.dz[0], hg.dz[1], hg.dz[2], 0.0f) : zero4;
     X[64] = zero4; X[128] = zero4; X[192] = zero4;
     {
       const ReluBits<4> mb = load_relu_bits<4>(bits_at(P.num_layers));
@@ -132,55 +96,9 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
     }
     // ---------------- stage 3: heads pre-activation gradients, then d emb = [W_b; W_heads]^T [d b; dz_heads] ------
     {
-      float4 q0 = zero4, q1 = zero4;  // heads rows 8q + 4h + j for q = 0, 1
-      if (a.mode != RSN_MODE_INF) {
-        if (h == 0) {
-          const float raw = a.fwd.raw_density[pc];
-          const float gs = a.gin.sigma ? a.gin.sigma[pc] * live : 0.0f;
-          q0.x = gs * sigmoid_f(raw + P.density_bias);  // softplus'
-          // predicted normal: pn = normalize(-normalize(n_raw)); G = g_pn + g_ndd * dir
-          float dir[3], G[3] = {0.0f, 0.0f, 0.0f};
-          const long long ray = pc / a.S;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) dir[c] = a.directions[ray * 3 + c];
-          if (a.gin.pred_normals) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) G[c] = a.gin.pred_normals[pc * 3 + c] * live;
-          }
-          float gd = a.gin.n_dot_d ? a.gin.n_dot_d[pc] * live : 0.0f;
-          if (a.gin.ray_pn_loss || a.gin.ray_ori_loss) {
-            // fused normal losses (model.py:403-407): per-ray upstream gradients of sum_s w |n - n_pred|^2 and
-            // sum_s w max(0, n.d)^2; the per-sample gradients are formed here and never stored
-            const float w = a.gin.weights[pc] * live;
-            if (a.gin.ray_pn_loss) {
-              const float gw = a.gin.ray_pn_loss[ray] * w * -2.0f;
-#pragma unroll
-              for (int c = 0; c < 3; ++c) G[c] += gw * (a.saved.normals[pc * 3 + c] - a.fwd.pred_normals[pc * 3 + c]);
-            }
-            if (a.gin.ray_ori_loss) gd += a.gin.ray_ori_loss[ray] * w * (2.0f * fmaxf(a.fwd.n_dot_d[pc], 0.0f));
-          }
-#pragma unroll
-          for (int c = 0; c < 3; ++c) G[c] += gd * dir[c];
-          const float nraw[3] = {hd.x, hd.y, hd.z};
-          const float len = fmaxf(sqrtf(nraw[0] * nraw[0] + nraw[1] * nraw[1] + nraw[2] * nraw[2]), 1e-12f);
-          const float v[3] = {-(nraw[0] / len), -(nraw[1] / len), -(nraw[2] / len)};
-          float gv[3], gu[3], gn[3];
-          normalize_bwd(v, G, gv);
-          gu[0] = -gv[0]; gu[1] = -gv[1]; gu[2] = -gv[2];
-          normalize_bwd(nraw, gu, gn);
-          q0.y = gn[0]; q0.z = gn[1]; q0.w = gn[2];
-          const float sr = sigmoid_f(hd.w);
-          const float gr = a.gin.roughness ? a.gin.roughness[pc] * live : 0.0f;
-          q1.x = gr * sr * (1.0f - sr);
-        } else {
-          q0.x = gcol[0] * (dif[0] * (1.0f - dif[0]));
-          q0.y = gcol[1] * (dif[1] * (1.0f - dif[1]));
-          q0.z = gcol[2] * (dif[2] * (1.0f - dif[2]));
-          q1.x = gcol[0] * mid[0] * (tin[0] * (1.0f - tin[0]));
-          q1.y = gcol[1] * mid[1] * (tin[1] * (1.0f - tin[1]));
-          q1.z = gcol[2] * mid[2] * (tin[2] * (1.0f - tin[2]));
-        }
-      }
+      // heads rows 8q + 4h + j for q = 0, 1: this half's two rows, h and h + 2
+      const float4 q0 = head_grad_row<false>(h == 0 ? 0 : 1, a, P.density_bias, pc, live, hg);
+      const float4 q1 = head_grad_row<false>(h == 0 ? 2 : 3, a, P.density_bias, pc, live, hg);
       X[(NB * 4 + 0) * 64] = q0;
       X[(NB * 4 + 1) * 64] = q1;
       X[(NB * 4 + 2) * 64] = zero4;
@@ -237,25 +155,7 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
         const float tot = part + __shfl_xor(part, 32, 64);
         if (c == 0) dvar[0] = tot; else if (c == 1) dvar[1] = tot; else dvar[2] = tot;
       }
-      if (h == 0 && valid && a.gout.d_input) {
-        float g = 0.0f;
-        if (a.mode == RSN_MODE_FRUSTUM) {
-          const long long ray = pc / a.S;
-          const int s = (int)(pc - ray * a.S);
-          float o[3], d[3], dv[3];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) { o[c] = a.origins[ray * 3 + c]; d[c] = a.directions[ray * 3 + c]; }
-          frustum_dvar_dpa(o, d, a.pixel_area[ray], a.bins[ray * (a.S + 1) + s], a.bins[ray * (a.S + 1) + s + 1], dv);
-          g = dvar[0] * dv[0] + dvar[1] * dv[1] + dvar[2] * dv[2];
-        } else {  // INF: var_c = (0.6 sq)(1 - d_c^2)   (reflect_sampling_nerf_field.py:196)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float dc = a.directions[pc * 3 + c];
-            g += dvar[c] * (0.6f * (1.0f - dc * dc));
-          }
-        }
-        a.gout.d_input[pc] = g;
-      }
+      if (h == 0 && valid && a.gout.d_input) a.gout.d_input[pc] = input_grad_of_dvar(a, pc, dvar);
     }
   }
 }

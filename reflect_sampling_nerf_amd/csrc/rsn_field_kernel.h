@@ -25,29 +25,13 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
   float* Xf = reinterpret_cast<float*>(X);
 
   const FieldShared& P = J.s;
-  // the launch's tile space: job k owns tiles [tb_k, tb_k+1) of 128 points (its ray count may live on the device)
-  long long np0 = 0, np1 = 0, np2 = 0, tb1 = 0, tb2 = 0, n_tiles = 0;
-#pragma unroll
-  for (int k = 0; k < RSN_MAX_JOBS; ++k) {
-    if (k < J.n_jobs) {
-      int nr = J.j[k].n_rays;
-      if (J.j[k].n_dev) {
-        const int nd = *J.j[k].n_dev;
-        nr = nd < nr ? nd : nr;
-      }
-      const long long np = (long long)nr * J.j[k].S;
-      if (k == 0) np0 = np; else if (k == 1) np1 = np; else np2 = np;
-      n_tiles += (np + 127) / 128;
-    }
-    if (k == 0) tb1 = n_tiles; else if (k == 1) tb2 = n_tiles;
-  }
+  const TileJobs T = tile_space<128>(J);
   const float* __restrict__ pk = P.packed;
 
-  for (long long gtile = blockIdx.x; gtile < n_tiles; gtile += gridDim.x) {
-    const int jk = (gtile >= tb1 ? 1 : 0) + (gtile >= tb2 ? 1 : 0);  // workgroup-uniform
-    const FieldJob& a = J.j[jk];
-    const long long n_points = jk == 0 ? np0 : (jk == 1 ? np1 : np2);
-    const long long tile = gtile - (jk == 0 ? 0 : (jk == 1 ? tb1 : tb2));
+  for (long long gtile = blockIdx.x; gtile < T.n_tiles; gtile += gridDim.x) {
+    const TileAt ta = tile_at(T, gtile);  // workgroup-uniform
+    const FieldJob& a = J.j[ta.job];
+    const long long n_points = ta.n_points, tile = ta.tile;
     const long long p0 = tile * 128 + wid * 32;
     if (p0 >= n_points) continue;  // wave-uniform; waves never synchronise with each other
     // an opaque copy of the lane id per tile: per-lane weight / output addresses are then not loop-invariant, so hipcc
@@ -87,28 +71,8 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         X[it * 64] = *reinterpret_cast<const float4*>(a.emb_in + pc * W + it * 8 + 4 * h);
     } else {
     // ---------------- encode -----------------
-    if (a.mode == RSN_MODE_FRUSTUM) {
-      const long long ray = pc / a.S;
-      const int s = (int)(pc - ray * a.S);
-      float o[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        o[c] = a.origins[ray * 3 + c];
-        vd[c] = a.directions[ray * 3 + c];
-      }
-      const float pa = a.pixel_area[ray];
-      const float t0 = a.bins[ray * (a.S + 1) + s];
-      const float t1 = a.bins[ray * (a.S + 1) + s + 1];
-      frustum_to_contracted(o, vd, pa, t0, t1, mc, vc);
-    } else if (a.mode == RSN_MODE_INF) {
-      const float r2 = a.sqradius[pc];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        vd[c] = a.directions[pc * 3 + c];
-        mc[c] = 2.0f * vd[c];
-        vc[c] = (0.6f * r2) * (1.0f - vd[c] * vd[c]);
-      }
-      has_dir = false;  // SH inputs are zeroed (reflect_sampling_nerf_field.py:199)
+    if (a.mode == RSN_MODE_FRUSTUM || a.mode == RSN_MODE_INF) {
+      has_dir = point_gaussian(a, pc, mc, vc, vd);
     } else {
       has_cov = a.cov_diag != nullptr;
       has_dir = a.view_dirs != nullptr;
@@ -221,34 +185,11 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       rho = (a.mode == RSN_MODE_EMB && a.rough_in) ? a.rough_in[pc] : softplus_f(rough_raw);
       dcol[0] = sigmoid_f(r0); dcol[1] = sigmoid_f(r1); dcol[2] = sigmoid_f(r2);
       tcol[0] = sigmoid_f(r4); tcol[1] = sigmoid_f(r5); tcol[2] = sigmoid_f(r6);
-      if (a.mode != RSN_MODE_INF && valid) {
-        if (h == 0) {
-          // get_pred_normals: -normalize(head) then normalize again (field.py:139-144, N6)
-          float nrm = fmaxf(sqrtf(r1 * r1 + r2 * r2 + r3 * r3), 1e-12f);
-          float nx = -(r1 / nrm), ny = -(r2 / nrm), nz = -(r3 / nrm);
-          nrm = fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-12f);
-          nx /= nrm; ny /= nrm; nz /= nrm;
-          if (a.out.sigma) a.out.sigma[pc] = softplus_f(r0 + P.density_bias);
-          if (a.out.raw_density) a.out.raw_density[pc] = r0;
-          if (a.out.pred_normals) {
-            a.out.pred_normals[pc * 3 + 0] = nx;
-            a.out.pred_normals[pc * 3 + 1] = ny;
-            a.out.pred_normals[pc * 3 + 2] = nz;
-          }
-          if (a.out.n_dot_d) a.out.n_dot_d[pc] = vd[0] * nx + vd[1] * ny + vd[2] * nz;
-          if (a.out.roughness) a.out.roughness[pc] = sigmoid_f(r4);
-          if (a.out.raw_roughness) a.out.raw_roughness[pc] = r4;
-        } else {
-          if (a.out.diff) {
-            a.out.diff[pc * 3 + 0] = dcol[0]; a.out.diff[pc * 3 + 1] = dcol[1]; a.out.diff[pc * 3 + 2] = dcol[2];
-          }
-          if (a.out.tint) {
-            a.out.tint[pc * 3 + 0] = tcol[0]; a.out.tint[pc * 3 + 1] = tcol[1]; a.out.tint[pc * 3 + 2] = tcol[2];
-          }
-        }
-      }
-      if (TRAIN && a.saved.heads && valid && h == 0) {  // raw normal head (3) + raw roughness head
-        *reinterpret_cast<float4*>(a.saved.heads + pc * 8) = make_float4(r1, r2, r3, r4);
+      if (valid) {  // rows h and h + 2 of the heads
+        head_outputs_row<false, false>(h == 0 ? 0 : 1, a, P.density_bias, pc, make_float4(r0, r1, r2, r3), dcol, vd);
+        head_outputs_row<false, false>(h == 0 ? 2 : 3, a, P.density_bias, pc, make_float4(r4, r5, r6, 0.0f), tcol, vd);
+        // raw normal head (3) + raw roughness head: both rows sit in this lane, so their saved.heads share leaves as ONE store
+        if (TRAIN && a.saved.heads && h == 0) *reinterpret_cast<float4*>(a.saved.heads + pc * 8) = make_float4(r1, r2, r3, r4);
       }
       // bottleneck output (no activation) becomes the x-part of mlp_mid's input
       store_act<NB + 1, NB, false, SBF>(acc, X, rb_epi(a.saved.bott, p0 * W, W), h);
@@ -296,21 +237,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       f32x16 accr[1];
       init_acc<1>(accr, pk + P.L.b_rgb, h);
       gemm_mode_run<MODE, 1, 1, TRAIN>(accr, wrgb, pk + P.L.w_rgb, pk + P.L.h_rgb, X, 16, ln, rb_loop(a.saved.hid, p0 * 128, 128));
-      if (h == 1 && valid) {
-        const float m0 = sigmoid_f(accr[0][0]);
-        const float m1 = sigmoid_f(accr[0][1]);
-        const float m2 = sigmoid_f(accr[0][2]);
-        if (TRAIN && a.saved.heads) *reinterpret_cast<float4*>(a.saved.heads + pc * 8 + 4) = make_float4(m0, m1, m2, 0.0f);
-        if (a.out.color) {
-          if (a.mode == RSN_MODE_INF || (a.mode == RSN_MODE_EMB && !a.out.diff && !a.out.tint)) {
-            a.out.color[pc * 3 + 0] = m0; a.out.color[pc * 3 + 1] = m1; a.out.color[pc * 3 + 2] = m2;
-          } else {
-            a.out.color[pc * 3 + 0] = dcol[0] + tcol[0] * m0;
-            a.out.color[pc * 3 + 1] = dcol[1] + tcol[1] * m1;
-            a.out.color[pc * 3 + 2] = dcol[2] + tcol[2] * m2;
-          }
-        }
-      }
+      if (h == 1 && valid) colour_out<false, TRAIN>(a, pc, accr[0][0], accr[0][1], accr[0][2], dcol, tcol);
     }
 
     // ---------------- training: analytic normals = -normalize(d raw_density / d contracted mean) -----------------

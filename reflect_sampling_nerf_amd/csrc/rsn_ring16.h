@@ -1,6 +1,7 @@
-// rsn_ring16.h -- what the plain-bf16 kernels share: packed-bf16 helpers, the fast activations of the bf16 mode, the LDS weight
-// ring (LDS-DMA producer / counted-wait consumer) and the 16x16x32 GEMM over it.  Used by rsn_field_bf16.hip (eval) and
-// rsn_field_bf16_train.hip (training forward + backward sweeps).  See rsn_field_bf16.hip for the design notes.
+// rsn_ring16.h -- what the plain-bf16 kernels share: packed-bf16 helpers, the fast trigonometry of the bf16 mode, the LDS weight
+// ring (LDS-DMA producer / counted-wait consumer), its bias-table fill (ring_fill_tables, also used by rsn_field_x6_train.hip) and
+// the 16x16x32 GEMM over it.  Used by rsn_field_bf16.hip (eval) and rsn_field_bf16_train.hip (training forward + backward
+// sweeps).  See rsn_field_bf16.hip for the design notes.  (The fast sigmoid / softplus of the mode: rsn_field_common.h, FieldMath.)
 #pragma once
 #include "rsn_field_common.h"
 
@@ -32,14 +33,6 @@ __device__ __forceinline__ unsigned int pack2(float a, float b) {
 }
 
 
-// bf16-mode activations: sigmoid / softplus on v_exp_f32 / v_log_f32 / v_rcp_f32 (~1e-6 relative) instead of the
-// correctly-rounded library forms -- their results are weighed against bf16 GEMM rounding (2^-9) in this mode
-__device__ __forceinline__ float fast_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
-__device__ __forceinline__ float fast_softplus(float x) {
-  return x > 20.0f ? x : 0.6931471805599453f * __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(1.4426950408889634f * x));
-}
 // sin / cos with the exact fp32 Cody-Waite reduction of sincos_big and degree-5 / degree-6 least-squares polynomials (4e-6 / 2e-7 absolute
 // on |r| <= 0.87): the feature is rounded to bf16 next
 __device__ __forceinline__ float sincos_bf16(float a, int quad) {
@@ -118,6 +111,19 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int r16_feature(int n) { return 32 * (n >> 5) + 8 * ((n >> 2) & 3) + 4 * ((n >> 4) & 1) + (n & 3); }
 #define R16_STASH_BYTES (4 * 2 * 1024)  // per wave: encoded inputs, [k32 (4)][half (2)][lane][8 bf16]
 #define R16_LDS_BYTES (RingCfg<8>::RING_BYTES + 8 * R16_STASH_BYTES + RING_BIAS_FLOATS * 4)
+
+// Kernel prologue: biases -> the LDS table, in the PACKED row order of the 16x32 stream (rsn_pack.hip, rows_perm16: packed row
+// 16 b + 4 g + r is feature 32 (b / 2) + 8 g + 4 (b % 2) + r).  Heads: the 32-entry table of the 32x32 layout keeps rows 0..15 = the
+// 16-row heads block here (not permuted, like the RGB rows).  DENSITY_ROW (training; table of RT_TABLE_FLOATS, rsn_ringt.h): behind
+// them the density-head row in natural feature order, the seed of the analytic-normal sweep.  Published by the caller's barrier.
+template <bool DENSITY_ROW>
+__device__ __forceinline__ void ring_fill_tables(float* bias, const float* pk, const RsnPackedLayout& L, int num_layers) {
+  for (int i = threadIdx.x; i < num_layers * 256; i += 512) bias[i] = pk[L.b[i >> 8] + r16_feature(i & 255)];
+  for (int i = threadIdx.x; i < 288; i += 512) bias[RING_MAX_LAYERS * 256 + i] = pk[L.b_bh + (i < 256 ? r16_feature(i) : i)];
+  if (threadIdx.x < 128) bias[RING_MAX_LAYERS * 256 + 288 + threadIdx.x] = pk[L.b_mid + r16_feature(threadIdx.x)];
+  if (threadIdx.x < 32) bias[RING_MAX_LAYERS * 256 + 288 + 128 + threadIdx.x] = pk[L.b_rgb + threadIdx.x];
+  if (DENSITY_ROW && threadIdx.x < 256) bias[RING_BIAS_FLOATS + threadIdx.x] = pk[L.v_density + threadIdx.x];
+}
 
 template <int NBO, int KS, int XN>
 __device__ __forceinline__ void gemm_ring16(f32x4 (&acc)[NBO][2], const bf16x8 (&X)[XN][2], Ring& r,

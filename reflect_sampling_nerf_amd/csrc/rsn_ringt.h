@@ -1,6 +1,8 @@
 // rsn_ringt.h -- what the TRAINING kernels on the LDS weight ring share (rsn_field_bf16_train.hip: plain bf16;
 // rsn_field_x6_train.hip: split-bf16, fp32-equivalent): the ring with a walk program and a COUNTED consumer wait, saved-row
-// descriptors and counted stores, asynchronous loads behind the ring's own wait arithmetic, the tile space of a multi-job launch.
+// descriptors and counted stores, asynchronous loads behind the ring's own wait arithmetic, the backward walk (ring_start_bwd) and
+// the host launchers of the forward / backward kernel pairs.  (The tile space and the per-sample maths: rsn_field_common.h,
+// rsn_field_bwd_common.h; the LDS table fill: rsn_ring16.h.)
 // Design notes: rsn_field_bf16_train.hip.
 #pragma once
 #include "rsn_field_bwd_common.h"
@@ -172,30 +174,7 @@ __device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned a, unsigned b) {
   return o;
 }
 
-// ------------------------------------------------------------------------------------------------ shared tile prologue
-struct TileJobs {
-  long long np0, np1, np2, tb1, tb2, n_tiles;
-};
-template <int TILE = 256, class JOBS>
-__device__ __forceinline__ TileJobs tile_space(const JOBS& J) {
-  TileJobs t = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int k = 0; k < RSN_MAX_JOBS; ++k) {
-    if (k < J.n_jobs) {
-      int nr = J.j[k].n_rays;
-      if (J.j[k].n_dev) {
-        const int nd = *J.j[k].n_dev;
-        nr = nd < nr ? nd : nr;
-      }
-      const long long np = (long long)nr * J.j[k].S;
-      if (k == 0) t.np0 = np; else if (k == 1) t.np1 = np; else t.np2 = np;
-      t.n_tiles += (np + TILE - 1) / TILE;
-    }
-    if (k == 0) t.tb1 = t.n_tiles; else if (k == 1) t.tb2 = t.n_tiles;
-  }
-  return t;
-}
-
+// ------------------------------------------------------------------------------------------------ shared kernel prologue
 template <class RING>
 __device__ __forceinline__ void ring_start(RING& r, const float* pk, const RsnPackedLayout& L, const char* smem, int wid, int lane,
                                            int first, int e0, int j0, int e1, int j1, bf16x8 (&Wf)[RING_FIFO]) {
@@ -222,6 +201,54 @@ __device__ __forceinline__ void ring_start(RING& r, const float* pk, const RsnPa
 #pragma unroll
   for (int j = 0; j < RING_FIFO; ++j) Wf[j] = *reinterpret_cast<const bf16x8*>(smem + r.rd_next + j * 1024);
 }
+// The backward sweeps' walk: the whole transposed stream; without an input gradient the two encoded-input pieces (4 groups per
+// operand part each: q_pf = 1 plain bf16, 3 split-bf16) are jumped over.
+template <bool INPUT, class RING>
+__device__ __forceinline__ void ring_start_bwd(RING& r, const float* pk, const RsnPackedLayout& Y, const char* smem, int wid, int lane,
+                                               bf16x8 (&Wf)[RING_FIFO]) {
+  int e0, j0, e1, j1;
+  if (INPUT) { e0 = Y.t_g_end; j0 = Y.t_g_begin; e1 = -1; j1 = 0; }
+  else if (Y.t_g_encskip >= 0) { e0 = Y.t_g_encskip; j0 = Y.t_g_encskip + 4 * Y.q_pf; e1 = Y.t_g_enc0; j1 = Y.t_g_begin; }
+  else { e0 = Y.t_g_enc0; j0 = Y.t_g_begin; e1 = -1; j1 = 0; }
+  ring_start(r, pk, Y, smem, wid, lane, Y.t_g_begin, e0, j0, e1, j1, Wf);
+}
 __device__ __forceinline__ void ring_finish() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may outlive the workgroup's LDS allocation
+}
+
+// ------------------------------------------------------------------------------------------------ host launchers
+// One 8-wave workgroup per CU strides through the launch's tiles.  The weight ring walks ONE program per launch, so all jobs must
+// agree on what selects it: analytic normals (forward), an input gradient (backward).
+static inline int ring_launch_fwd(void (*with_normals)(const FieldJobs), void (*plain_k)(const FieldJobs), long long n_tiles,
+                                  hipStream_t st, const FieldJobs& J) {
+  bool normals = false, plain = false;
+  for (int k = 0; k < J.n_jobs; ++k) {
+    const FieldJob& a = J.j[k];
+    RSN_REQUIRE(a.mode == RSN_MODE_FRUSTUM || a.mode == RSN_MODE_INF, RSN_ERR_UNSUPPORTED, "job %d: mode %d", k, a.mode);
+    RSN_REQUIRE((long long)a.n_rays * a.S < (1LL << 31), RSN_ERR_UNSUPPORTED, "job %d: 2^31 points or more", k);
+    if (a.saved.normals) normals = true; else plain = true;
+  }
+  RSN_REQUIRE(!(normals && plain), RSN_ERR_UNSUPPORTED,
+              "evaluations with and without analytic normals cannot share a launch (the weight ring walks one program)");
+  const int cus = rsn_device_cus();
+  const long long grid = n_tiles < (long long)cus ? n_tiles : (long long)cus;
+  hipLaunchKernelGGL(normals ? with_normals : plain_k, dim3((unsigned)grid), dim3(512), 0, st, J);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+static inline int ring_launch_bwd(void (*with_input)(const BwdJobs), void (*without)(const BwdJobs), long long n_tiles,
+                                  hipStream_t st, const BwdJobs& J) {
+  bool input = false;
+  for (int k = 0; k < J.n_jobs; ++k) {
+    RSN_REQUIRE((long long)J.j[k].n_rays * J.j[k].S < (1LL << 31), RSN_ERR_UNSUPPORTED, "job %d: 2^31 points or more", k);
+    input = input || J.j[k].need_input_grad != 0;
+  }
+  for (int k = 0; k < J.n_jobs; ++k)
+    RSN_REQUIRE((J.j[k].need_input_grad != 0) == input, RSN_ERR_UNSUPPORTED,
+                "evaluations with and without an input gradient cannot share a launch (the weight ring walks one program)");
+  const int cus = rsn_device_cus();
+  const long long grid = n_tiles < (long long)cus ? n_tiles : (long long)cus;
+  hipLaunchKernelGGL(input ? with_input : without, dim3((unsigned)grid), dim3(512), 0, st, J);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
 }
