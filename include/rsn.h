@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RSN_ABI_VERSION 17
+#define RSN_ABI_VERSION 18
 #define RSN_MAX_TRUNK_LAYERS 16
 #define RSN_NUM_FREQS 16   /* NeRFEncoding(num_frequencies=16), reflect_sampling_nerf_model.py:98-100 */
 #define RSN_ENC_DIM 99     /* 3*16*2 + 3 */
@@ -469,6 +469,34 @@ typedef struct rsn_wgrad_job {
 int rsn_weight_grad_jobs(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
                          const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy, int32_t n_out,
                          int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16, void* stream);
+
+/* ORDERED weight-gradient reduction (ABI 18): the same sums as rsn_weight_grad_multi_dev / rsn_weight_grad_jobs with a fixed order of
+ * addition, for bit-reproducible training.  The calls above add every wave's partial tile to dW / db with fp32 atomics, whose order of
+ * arrival differs from run to run (the last bits of the gradients differ); here every wave stores its partial tile to a slot of
+ * `workspace`, and a second kernel on the same stream sums the slots of each output element in ascending slot order and adds the sum
+ * to dW / db with one plain read-modify-write.  No atomics.
+ * Guarantee: the same library build, the same device, the same arguments (sizes, leading dimensions, mode, alignment of the pointers)
+ * and the same operand bits -- the device-side counts included -- give the same output bits, in the same process or another one.
+ * It does NOT hold across devices with different CU counts (the grid, and with it the partition of the points, follows the CU count)
+ * or across library builds.  Accumulation into non-zero dW / db, ld_dw, col_map (-1 entries) and rows >= n_out behave as in the
+ * atomic calls; the result differs from theirs by the order of the additions only.
+ * Workspace rule: `workspace` is device memory of at least rsn_weight_grad_workspace_bytes(...) bytes for the same segment upper
+ * bounds, n_jobs (1 for rsn_weight_grad_multi_dev_ordered), shape, mode and operand_bf16, 16-byte aligned; a smaller one is
+ * RSN_ERR_INVALID_ARGUMENT before any launch, with the needed size in rsn_last_error().  Its contents on entry do not matter and are
+ * undefined on return; launches on ONE stream may share it (the library neither allocates nor synchronises).  The size is an upper
+ * bound computed on the host without reading the device counts: 4 slots per workgroup (at most one workgroup per CU) of 192 + 2048 * NKB
+ * floats, NKB = 2 / 4 / 8 for k_in <= 64 / 128 / 256 -- 68 MB for a 256-column output on 256 CUs.  rsn_weight_grad_workspace_bytes returns 0 (and sets rsn_last_error) on bad arguments. */
+size_t rsn_weight_grad_workspace_bytes(int32_t n_segments, const int64_t* n_points_max, int32_t n_jobs, int32_t n_out, int32_t k_in,
+                                       int32_t mma_mode, int32_t operand_bf16);
+int rsn_weight_grad_multi_dev_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                      const int32_t* per_count, const float* const* dy, int32_t ld_dy, int32_t n_out,
+                                      const float* const* x, int32_t ld_x, int32_t k_in, const int32_t* col_map, float* dw,
+                                      int32_t ld_dw, float* db, int32_t mma_mode, int32_t operand_bf16, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int rsn_weight_grad_jobs_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                 const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy, int32_t n_out,
+                                 int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 /* get_loss_dict on per-ray quantities only (training step: the per-sample normal terms arrive reduced per ray from
  * rsn_composite): losses8[k] = the UNSCALED terms (0-3 MSE means of rgb4[k] against image; 4,5 = sum_r pn_loss_ray2[lv][r];

@@ -18,6 +18,13 @@
 // their weights): the per-launch costs -- a 67 MB atomic flush for a 256 x 256 output on 256 workgroups,
 // ~50 us -- are paid once per layer instead of once per layer and level.
 //
+// ORDERED mode (the rsn_weight_grad_*_ordered entry points): the flush uses no atomics.  Every wave stores its accumulators,
+// as they lie in its registers, to a workspace slot of its own -- slot (workgroup b, wave w) = (job b % n_jobs, wave slot g, row-block
+// pair), WG_SLOT_HEAD + 2 * NKB * 1024 floats: [0] live flag, [64 + 64 t + lane] bias partial sums, [192 + ((t NKB + kb) 16 + r) 64 +
+// lane] acc[t][kb][r] -- and rsn_wgrad_reduce_kernel, launched behind it, sums the live slots of every output element in ascending g and
+// adds the sum to dW / db with one plain read-modify-write.  The grid and the deal of stages to wave slots depend on the launch arguments
+// and the CU count alone, so the same call gives the same bits every time.
+//
 // MFMA-bound: 2 * N * n_out * k_in FLOP; HBM reads N * (n_out + k_in) * 4 B (each operand once per workgroup).
 #include "rsn_mfma.h"
 
@@ -57,7 +64,10 @@ struct WGradArgs {
 struct WGradJobs {
   int n_jobs;
   WGradArgs j[WG_MAX_JOBS];
+  float* ws;  // ordered mode: the workspace (4 slots per workgroup); unused by the atomic flush
 };
+
+#define WG_SLOT_HEAD 192  // floats in front of a slot's tile: 64 (word 0 = live flag) + 2 x 64 bias partial sums
 
 #define WG_PAIRS 4  // point pairs (MFMA K-steps) per software-pipeline stage
 
@@ -72,7 +82,8 @@ struct WGradJobs {
 //   XB / DB (BF = 1 only): the X / dY rows ARE bf16 in memory (reduced-precision training saves its wide buffers as
 //          bf16: rsn_field_saved, rsn_field_grads_out): half the bytes of this HBM-bound variant, no conversion; a lane's
 //          8 points x {2 rows | NKB columns} arrive as packed words and are regrouped per row / column by v_perm_b32.
-template <int NKB, bool XV, bool DV, int BF = 0, bool XB = false, bool DB = false>
+// ORD: the ordered flush (plain stores to the wave's workspace slot, summed by rsn_wgrad_reduce_kernel) instead of the atomic one.
+template <int NKB, bool XV, bool DV, int BF = 0, bool XB = false, bool DB = false, bool ORD = false>
 __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
   const int n_jobs = J.n_jobs;
   const WGradArgs& a = J.j[blockIdx.x % n_jobs];  // workgroup-uniform
@@ -544,6 +555,23 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
     }
     vprefix += n_full + (rem > 0 ? 1 : 0);
   }
+  if constexpr (ORD) {
+    // every wave states whether its slot is live, the idle ones too: which slots hold a tile is known on the device only (n_dev),
+    // and the reducer reads no slot that was not written in this launch
+    float* __restrict__ slot = J.ws + ((size_t)blockIdx.x * 4 + wid) * (size_t)(WG_SLOT_HEAD + 2 * NKB * 1024);
+    if (lane == 0) *reinterpret_cast<unsigned*>(slot) = any ? 1u : 0u;
+    if (!any) return;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      if (t == 1 && !t1_live) continue;  // rows >= n_out only: the reducer never asks for them
+      slot[64 + t * 64 + lane] = bsum[t] + __shfl_xor(bsum[t], 32, 64);
+#pragma unroll
+      for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) slot[WG_SLOT_HEAD + ((t * NKB + kb) * 16 + r) * 64 + lane] = acc[t][kb][r];
+    }
+    return;
+  }
   if (!any) return;  // wave-uniform: nothing accumulated, nothing to flush
 
   // flush: C/D layout col = lane&31 (input-column slot), row = (r&3) + 8*(r>>2) + 4*h (output-row slot).  The
@@ -591,15 +619,125 @@ __global__ __launch_bounds__(256) void rsn_wgrad_kernel(const WGradJobs J) {
   }
 }
 
-static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf16 = 0) {
+// The ordered mode's second kernel.  One thread per accumulator element (row-block pair, t, kb, r, lane) of a job -- consecutive
+// threads read consecutive words of a slot -- which undoes the main kernel's lane / register permutation for itself: it owns output
+// element (n, k), or none (clamped duplicates, padded columns, rows >= n_out, col_map -1).  The owner adds the live slots' values in
+// ascending wave slot g = workgroup * nsub + sub and does ONE read-modify-write of dW; the last block of a job does the same for db.
+// The flag of a slot is uniform over the block (a block lies inside one row-block pair).
+__global__ __launch_bounds__(256) void rsn_wgrad_reduce_kernel(const WGradJobs J, int gwg, int nkb, int xv, int dv) {
+  const int n_jobs = J.n_jobs;
+  const int P = J.j[0].n_out <= 64 ? 1 : (J.j[0].n_out <= 128 ? 2 : 4);
+  const int nsub = 4 / P;
+  const int tile_blocks = P * nkb * 8;  // P * 2 * nkb * 1024 elements / 256
+  const int job = blockIdx.x / (tile_blocks + 1), blk = blockIdx.x % (tile_blocks + 1);
+  const WGradArgs& a = J.j[job];
+  const size_t slot_f = (size_t)(WG_SLOT_HEAD + 2 * nkb * 1024);
+  int pair, off;  // the element's row-block pair and its word inside the slot
+  float* dst = nullptr;
+  if (blk < tile_blocks) {
+    const int e = blk * 256 + threadIdx.x;
+    const int lane = e & 63, r = (e >> 6) & 15, tk = e >> 10;
+    const int kb = tk % nkb, t = (tk / nkb) & 1;
+    pair = tk / (2 * nkb);
+    const int i = lane & 31, h = lane >> 5;
+    const int rs = (r & 3) + 8 * (r >> 2) + 4 * h;  // C/D layout: output-row slot of the 32x32 block
+    const int n = dv ? pair * 64 + 2 * rs + t : (pair * 2 + t) * 32 + rs;
+    const int k = xv ? i * nkb + kb : kb * 32 + i;
+    off = WG_SLOT_HEAD + e - pair * 2 * nkb * 1024;
+    if (n < a.n_out && k < a.k_in) {
+      const int c = a.col_map ? a.col_map[k] : k;
+      if (c >= 0) dst = a.dw + (size_t)n * a.ld_dw + c;
+    }
+  } else {
+    if (threadIdx.x >= P * 64) return;
+    const int i = threadIdx.x & 31, t = (threadIdx.x >> 5) & 1;
+    pair = threadIdx.x >> 6;
+    const int n = dv ? pair * 64 + 2 * i + t : (pair * 2 + t) * 32 + i;
+    off = 64 + t * 64 + i;
+    if (a.db && n < a.n_out) dst = a.db + n;
+  }
+  if (!dst) return;
+  const int n_slots = gwg * nsub;
+  float sum = 0.0f;
+  bool live = false;
+  for (int g0 = 0; g0 < n_slots; g0 += 4) {
+    float v[4];
+    bool f[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // four slots' loads in flight, added in order
+      const int g = g0 + u;
+      const size_t sl = ((size_t)(g / nsub) * n_jobs + job) * 4 + (g % nsub) * P + pair;  // (workgroup, wave) of wave slot g
+      f[u] = g < n_slots && *reinterpret_cast<const unsigned*>(J.ws + sl * slot_f) != 0u;
+      v[u] = f[u] ? J.ws[sl * slot_f + off] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (f[u]) {
+        sum += v[u];
+        live = true;
+      }
+  }
+  if (live) *dst += sum;  // no live slot: dW / db stay bit for bit what they were
+}
+
+// workgroups of one launch: a function of the upper-bound segment lengths, the shape, the mode and the CU count
+static long long wgrad_grid(const long long* seg_begin, int n_seg, int n_out, int k_in, int n_jobs, bool bf16, int mode) {
+  const int cached_cus = rsn_device_cus();
+  // grid: every workgroup pays one atomic flush of the output tile (chip-wide ~1.3 TB/s of added bytes) and the
+  // waves share the stages; T(G) = stages / (G * nsub) * t_stage + G * t_flush is smallest at G = sqrt(...)
+  const int nkb = k_in > 128 ? 8 : (k_in > 64 ? 4 : 2);
+  const int P = n_out <= 64 ? 1 : (n_out <= 128 ? 2 : 4);
+  const int nsub = 4 / P;
+  long long stages = 0;
+  const int stage_pts = bf16 ? 16 : 2 * WG_PAIRS;
+  for (int s = 0; s < n_seg; ++s) {
+    const long long n_s = seg_begin[s + 1] - seg_begin[s];
+    stages += (n_s + stage_pts - 1) / stage_pts;
+  }
+  const double t_stage = bf16 ? (n_out > 32 ? 2 : 1) * nkb * 32 / 1.9e9 * (mode == RSN_MMA_BF16X6 ? 6 : 2.5)  // 1 product: HBM-bound, ~2.5x the MFMA time
+                              : WG_PAIRS * (n_out > 32 ? 2 : 1) * nkb * 64 / 2.1e9;
+  const double t_flush = (double)n_out * k_in * 4.0 / 1.3e12 + 2e-8;
+  long long grid = (long long)(sqrt((double)stages * t_stage / (nsub * t_flush)) + 0.5);  // workgroups per job
+  if (grid > cached_cus / n_jobs) grid = cached_cus / n_jobs;
+  if (grid < 1) grid = 1;
+  return grid * n_jobs;  // workgroup i: job i % n_jobs
+}
+
+static size_t wgrad_ws_bytes(long long grid, int k_in) {
+  const int nkb = k_in > 128 ? 8 : (k_in > 64 ? 4 : 2);
+  return (size_t)grid * 4 * (WG_SLOT_HEAD + 2 * nkb * 1024) * sizeof(float);
+}
+
+extern "C" size_t rsn_weight_grad_workspace_bytes(int32_t n_segments, const int64_t* n_points_max, int32_t n_jobs,
+                                                  int32_t n_out, int32_t k_in, int32_t mma_mode, int32_t operand_bf16) {
+  RSN_REQUIRE(n_segments >= 0 && n_segments <= WG_MAX_SEG && (n_segments == 0 || n_points_max), 0, "n_segments=%d (at most %d)",
+              n_segments, WG_MAX_SEG);
+  RSN_REQUIRE(n_jobs >= 1 && n_jobs <= WG_MAX_JOBS, 0, "n_jobs=%d (1..%d)", n_jobs, WG_MAX_JOBS);
+  RSN_REQUIRE(n_out >= 1 && n_out <= 256 && k_in >= 1 && k_in <= 256, 0, "n_out=%d k_in=%d (outputs up to 256 x 256)", n_out, k_in);
+  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, 0, "mma_mode %d", mma_mode);
+  RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, 0, "operand_bf16 %d", operand_bf16);
+  long long seg_begin[WG_MAX_SEG + 1] = {0};
+  for (int s = 0; s < n_segments; ++s) {
+    RSN_REQUIRE(n_points_max[s] >= 0, 0, "n_points_max[%d]=%lld", s, (long long)n_points_max[s]);
+    seg_begin[s + 1] = seg_begin[s] + n_points_max[s];
+  }
+  // a launch in a bf16 mode takes the exact kernel's grid when the rows do not fit the vector-load layout (alignment: known
+  // at the launch only): the larger of the two
+  long long grid = wgrad_grid(seg_begin, n_segments, n_out, k_in, n_jobs, false, mma_mode);
+  if (mma_mode == RSN_MMA_BF16 || mma_mode == RSN_MMA_BF16X6) {
+    const long long gb = wgrad_grid(seg_begin, n_segments, n_out, k_in, n_jobs, true, mma_mode);
+    grid = gb > grid ? gb : grid;
+  }
+  return wgrad_ws_bytes(grid, k_in);
+}
+
+static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf16 = 0, bool ordered = false, void* ws = nullptr,
+                        size_t ws_bytes = 0) {
   WGradArgs& a = J.j[0];  // the jobs of a launch share shape, leading dimensions and segment lengths (checked by the caller)
   const bool xb = (operand_bf16 & 1) != 0, db = (operand_bf16 & 2) != 0;  // rows that ARE bf16 in memory
   bool bf16 = mode == RSN_MMA_BF16 || mode == RSN_MMA_BF16X6;
   const long long total = a.seg_begin[a.n_seg];
   if (total == 0) return RSN_OK;
-  const int cached_cus = rsn_device_cus();
-  // grid: every workgroup pays one atomic flush of the output tile (chip-wide ~1.3 TB/s of added bytes) and the
-  // waves share the stages; T(G) = stages / (G * nsub) * t_stage + G * t_flush is smallest at G = sqrt(...)
   const int nkb = a.k_in > 128 ? 8 : (a.k_in > 64 ? 4 : 2);
   // vector-load variants need whole NKB-column groups and aligned rows; anything else takes the scalar-load path
   bool xv = a.k_in % nkb == 0 && a.ld_x % (xb ? nkb : (nkb >= 4 ? 4 : 2)) == 0;
@@ -616,51 +754,57 @@ static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf
                 a.k_in, a.ld_x, a.n_out, a.ld_dy);
   }
   bf16 = bf16 && xv && (dv || (xb && !db));  // the bf16 variants exist for the vector-load layout only
-  const int P = a.n_out <= 64 ? 1 : (a.n_out <= 128 ? 2 : 4);
-  const int nsub = 4 / P;
-  long long stages = 0;
-  const int stage_pts = bf16 ? 16 : 2 * WG_PAIRS;
-  for (int s = 0; s < a.n_seg; ++s) {
-    const long long n_s = a.seg_begin[s + 1] - a.seg_begin[s];
-    stages += (n_s + stage_pts - 1) / stage_pts;
+  const long long grid = wgrad_grid(a.seg_begin, a.n_seg, a.n_out, a.k_in, J.n_jobs, bf16, mode);
+  if (ordered) {
+    const size_t need = wgrad_ws_bytes(grid, a.k_in);
+    RSN_REQUIRE(ws && (uintptr_t)ws % 16 == 0, RSN_ERR_INVALID_ARGUMENT, "workspace is NULL or not 16-byte aligned");
+    RSN_REQUIRE(ws_bytes >= need, RSN_ERR_INVALID_ARGUMENT, "workspace_bytes=%zu: the ordered reduction needs %zu bytes", ws_bytes,
+                need);
+    J.ws = static_cast<float*>(ws);
   }
-  const double t_stage = bf16 ? (a.n_out > 32 ? 2 : 1) * nkb * 32 / 1.9e9 * (mode == RSN_MMA_BF16X6 ? 6 : 2.5)  // 1 product: HBM-bound, ~2.5x the MFMA time
-                              : WG_PAIRS * (a.n_out > 32 ? 2 : 1) * nkb * 64 / 2.1e9;
-  const double t_flush = (double)a.n_out * a.k_in * 4.0 / 1.3e12 + 2e-8;
-  long long grid = (long long)(sqrt((double)stages * t_stage / (nsub * t_flush)) + 0.5);  // workgroups per job
-  if (grid > cached_cus / J.n_jobs) grid = cached_cus / J.n_jobs;
-  if (grid < 1) grid = 1;
-  grid *= J.n_jobs;  // workgroup i: job i % n_jobs
   hipStream_t st = (hipStream_t)stream;
-#define RSN_WG(NKBV)                                                                                           \
+#define RSN_WG(NKBV, ORDV)                                                                                           \
   do {                                                                                                         \
     if (xv && dv && bf16 && mode == RSN_MMA_BF16X6)                                                            \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 3>), dim3((unsigned)grid), dim3(256), 0, st, J);  \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 3, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);  \
     else if (bf16 && xb && db)                                                                                 \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, true, true>), dim3((unsigned)grid), dim3(256), 0, st, J); \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, true, true, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J); \
     else if (bf16 && db)                                                                                       \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, false, true>), dim3((unsigned)grid), dim3(256), 0, st, J); \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, false, true, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J); \
     else if (bf16 && xb && !dv)                                                                                \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, false, 1, true, false>), dim3((unsigned)grid), dim3(256), 0, st, J); \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, false, 1, true, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J); \
     else if (bf16 && xb)                                                                                       \
       { RSN_REQUIRE(false, RSN_ERR_UNSUPPORTED, "bf16 X rows with fp32 dY rows wider than 32 outputs"); }      \
     else if (xv && dv && bf16)                                                                                 \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1>), dim3((unsigned)grid), dim3(256), 0, st, J);  \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);  \
     else if (xv && dv)                                                                                         \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true>), dim3((unsigned)grid), dim3(256), 0, st, J);     \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 0, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);     \
     else if (xv)                                                                                               \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, false>), dim3((unsigned)grid), dim3(256), 0, st, J);    \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, false, 0, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);    \
     else                                                                                                       \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, false, false>), dim3((unsigned)grid), dim3(256), 0, st, J);   \
+      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, false, false, 0, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);   \
   } while (0)
-  if (nkb == 8)
-    RSN_WG(8);
+  if (ordered) {
+    if (nkb == 8)
+      RSN_WG(8, true);
+    else if (nkb == 4)
+      RSN_WG(4, true);
+    else
+      RSN_WG(2, true);
+  } else if (nkb == 8)
+    RSN_WG(8, false);
   else if (nkb == 4)
-    RSN_WG(4);
+    RSN_WG(4, false);
   else
-    RSN_WG(2);
+    RSN_WG(2, false);
 #undef RSN_WG
   RSN_HIP(hipGetLastError());
+  if (ordered) {
+    const int P = a.n_out <= 64 ? 1 : (a.n_out <= 128 ? 2 : 4);
+    hipLaunchKernelGGL(rsn_wgrad_reduce_kernel, dim3((unsigned)(J.n_jobs * (P * nkb * 8 + 1))), dim3(256), 0, st, J,
+                       (int)(grid / J.n_jobs), nkb, (int)xv, (int)(xv && dv));  // the kernels above: DV only beside XV
+    RSN_HIP(hipGetLastError());
+  }
   return RSN_OK;
 }
 
@@ -668,7 +812,7 @@ static int weight_grad_multi_impl(int32_t n_segments, const int64_t* n_points, c
                                   int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
                                   const int32_t* col_map, float* dw, int32_t ld_dw, float* db, void* stream, int mode,
                                   const int32_t* const* n_dev = nullptr, const int32_t* per_count = nullptr,
-                                  int operand_bf16 = 0);
+                                  int operand_bf16 = 0, bool ordered = false, void* ws = nullptr, size_t ws_bytes = 0);
 
 extern "C" int rsn_weight_grad_multi(int32_t n_segments, const int64_t* n_points, const float* const* dy, int32_t ld_dy,
                                      int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
@@ -679,7 +823,8 @@ extern "C" int rsn_weight_grad_multi(int32_t n_segments, const int64_t* n_points
 static int weight_grad_multi_impl(int32_t n_segments, const int64_t* n_points, const float* const* dy, int32_t ld_dy,
                                   int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
                                   const int32_t* col_map, float* dw, int32_t ld_dw, float* db, void* stream, int mode,
-                                  const int32_t* const* n_dev, const int32_t* per_count, int operand_bf16) {
+                                  const int32_t* const* n_dev, const int32_t* per_count, int operand_bf16, bool ordered, void* ws,
+                                  size_t ws_bytes) {
   RSN_REQUIRE(n_segments >= 0 && n_segments <= WG_MAX_SEG, RSN_ERR_INVALID_ARGUMENT, "n_segments=%d (at most %d)",
               n_segments, WG_MAX_SEG);
   RSN_REQUIRE(n_out >= 1 && n_out <= 256 && k_in >= 1 && k_in <= 256, RSN_ERR_INVALID_ARGUMENT,
@@ -707,7 +852,7 @@ static int weight_grad_multi_impl(int32_t n_segments, const int64_t* n_points, c
   a.n_seg = ns;
   a.ld_dy = ld_dy; a.ld_x = ld_x; a.n_out = n_out; a.k_in = k_in;
   a.ld_dw = ld_dw; a.col_map = col_map; a.dw = dw; a.db = db;
-  return wgrad_launch(J, stream, mode, operand_bf16);
+  return wgrad_launch(J, stream, mode, operand_bf16, ordered, ws, ws_bytes);
 }
 
 extern "C" int rsn_weight_grad_multi_mode(int32_t n_segments, const int64_t* n_points, const float* const* dy,
@@ -731,11 +876,23 @@ extern "C" int rsn_weight_grad_multi_dev(int32_t n_segments, const int64_t* n_po
                                 mma_mode, n_dev, per_count, operand_bf16);
 }
 
+extern "C" int rsn_weight_grad_multi_dev_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                                 const int32_t* per_count, const float* const* dy, int32_t ld_dy,
+                                                 int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
+                                                 const int32_t* col_map, float* dw, int32_t ld_dw, float* db, int32_t mma_mode,
+                                                 int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
+  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode %d", mma_mode);
+  RSN_REQUIRE(n_segments == 0 || (n_dev && per_count), RSN_ERR_INVALID_ARGUMENT, "n_dev / per_count is NULL");
+  RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, RSN_ERR_INVALID_ARGUMENT, "operand_bf16 %d", operand_bf16);
+  return weight_grad_multi_impl(n_segments, n_points_max, dy, ld_dy, n_out, x, ld_x, k_in, col_map, dw, ld_dw, db, stream,
+                                mma_mode, n_dev, per_count, operand_bf16, true, workspace, workspace_bytes);
+}
+
 // rsn_weight_grad_jobs: n_jobs reductions of one shape over the same segments in ONE launch (see WGradJobs).
-extern "C" int rsn_weight_grad_jobs(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
-                                    const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
-                                    int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
-                                    void* stream) {
+static int weight_grad_jobs_impl(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                 const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
+                                 int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
+                                 void* stream, bool ordered, void* ws, size_t ws_bytes) {
   RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode %d", mma_mode);
   RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, RSN_ERR_INVALID_ARGUMENT, "operand_bf16 %d", operand_bf16);
   RSN_REQUIRE(n_jobs >= 1 && n_jobs <= WG_MAX_JOBS && jobs, RSN_ERR_INVALID_ARGUMENT, "n_jobs=%d (1..%d)", n_jobs, WG_MAX_JOBS);
@@ -771,7 +928,23 @@ extern "C" int rsn_weight_grad_jobs(int32_t n_segments, const int64_t* n_points_
     a.ld_dw = q.ld_dw; a.col_map = q.col_map; a.dw = q.dw; a.db = q.db;
   }
   if (J.j[0].n_seg == 0) return RSN_OK;
-  return wgrad_launch(J, stream, mma_mode, operand_bf16);
+  return wgrad_launch(J, stream, mma_mode, operand_bf16, ordered, ws, ws_bytes);
+}
+
+extern "C" int rsn_weight_grad_jobs(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                    const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
+                                    int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
+                                    void* stream) {
+  return weight_grad_jobs_impl(n_segments, n_points_max, n_dev, per_count, n_jobs, jobs, ld_dy, n_out, ld_x, k_in, mma_mode,
+                               operand_bf16, stream, false, nullptr, 0);
+}
+
+extern "C" int rsn_weight_grad_jobs_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                            const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
+                                            int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  return weight_grad_jobs_impl(n_segments, n_points_max, n_dev, per_count, n_jobs, jobs, ld_dy, n_out, ld_x, k_in, mma_mode,
+                               operand_bf16, stream, true, workspace, workspace_bytes);
 }
 
 extern "C" int rsn_weight_grad(int64_t n_points, const float* dy, int32_t ld_dy, int32_t n_out, const float* x,

@@ -10,6 +10,7 @@ The reference's debug prints / six syncs (model.py:230,263-265,342) are not repr
 from __future__ import annotations
 
 import contextlib
+import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Type
 
@@ -97,6 +98,7 @@ class ReflectSamplingNeRFModel(Model):
         # modules (SSIM / LPIPS are out of scope), so their entries are dropped from an incoming state dict before nn.Module's strict
         # key check sees them -- also when the checkpoint is loaded through a parent (nerfstudio's pipeline: prefix `_model.`).
         self._register_load_state_dict_pre_hook(self._drop_reference_metric_state)
+        self._deterministic = os.environ.get("RSN_DETERMINISTIC", "") == "1"
 
     _REFERENCE_METRIC_MODULES = ("lpips", "psnr", "ssim")
 
@@ -105,6 +107,17 @@ class ReflectSamplingNeRFModel(Model):
         drop = tuple(prefix + m + "." for m in ReflectSamplingNeRFModel._REFERENCE_METRIC_MODULES)
         for k in [k for k in state_dict if k.startswith(drop)]:
             del state_dict[k]
+
+    @property
+    def deterministic(self) -> bool:
+        """Bit-reproducible training steps: the weight gradients are reduced in a fixed order (rsn_weight_grad_*_ordered) instead of
+        by fp32 atomics.  Default False, or True when the environment holds RSN_DETERMINISTIC=1 as the model is built."""
+        return self._deterministic
+
+    def set_deterministic(self, flag: bool) -> None:
+        """Same build, device, seed, rays and settings (mma mode, weight_grad_groups, reflect_capacity, ray_chunk) -> the same
+        gradient and parameter bits on every run.  Costs one workspace (68 MB at width 256) and a slower reduction flush."""
+        self._deterministic = bool(flag)
 
     def get_param_groups(self) -> Dict[str, List[Parameter]]:
         if self.field is None:

@@ -145,6 +145,21 @@ def _wgrad(dy: Tensor, n_out: int, x: Tensor, k_in: int, dw: Tensor, dw_col0: in
 
 _WGRAD_MODE = 0  # RSN_MMA_*: set per step by _weight_grads from the Field's MMA mode
 _WGRAD_JOBS_MAX = 8  # WG_MAX_JOBS of rsn_wgrad.hip
+_WGRAD_ORDERED = False  # set per step by _weight_grads (Model.deterministic): the ordered entry points, bit-reproducible sums
+_WGRAD_WS: Dict[torch.device, Tensor] = {}  # the ordered reductions' workspace, one per device, grown on demand
+
+
+def _wgrad_workspace(lib, dev, ns: int, npts, n_jobs: int, n_out: int, k_in: int, operand_bf16: int) -> Tensor:
+    """Workspace of one ordered weight-gradient launch (rsn_weight_grad_workspace_bytes: a host-side upper bound).  One tensor per
+    device serves every launch: they run on one stream, each launch's reducer has read the slots before the next launch writes them."""
+    need = int(lib.rsn_weight_grad_workspace_bytes(ns, npts, n_jobs, n_out, k_in, _WGRAD_MODE, operand_bf16))
+    if need == 0:
+        check(-1)  # bad arguments: the library's message
+    ws = _WGRAD_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        _WGRAD_WS.pop(dev, None)
+        ws = _WGRAD_WS[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
 
 
 def _wgrad_multi(segs, n_out: int, k_in: int, dw: Tensor, dw_col0: int, db: Optional[Tensor],
@@ -174,6 +189,13 @@ def _wgrad_multi(segs, n_out: int, k_in: int, dw: Tensor, dw_col0: int, db: Opti
     dev_work = [(c[0], c[1] * n_out * k_in) for c in cnt if c is not None]
     if dev_work:
         work["point_out_in_dev"] = dev_work
+    if _WGRAD_ORDERED:
+        ws = _wgrad_workspace(lib, dw.device, ns, npts, 1, n_out, k_in, operand_bf16)
+        ops.timed("weight_grad", work,
+                  lambda: check(lib.rsn_weight_grad_multi_dev_ordered(ns, npts, ndev, per, dys, ld_dy, n_out, xs, ld_x, k_in,
+                                                                      ptr(col_map), dwp, dw.stride(0), ptr(db), _WGRAD_MODE,
+                                                                      operand_bf16, ptr(ws), ws.numel(), ops._stream())))
+        return
     ops.timed("weight_grad", work,
               lambda: check(lib.rsn_weight_grad_multi_dev(ns, npts, ndev, per, dys, ld_dy, n_out, xs, ld_x, k_in, ptr(col_map),
                                                           dwp, dw.stride(0), ptr(db), _WGRAD_MODE, operand_bf16, ops._stream())))
@@ -215,17 +237,25 @@ def _wgrad_jobs(jobs, n_out: int, k_in: int):
     dev_work = [(c[0], len(jobs) * c[1] * n_out * k_in) for c in cnt if c is not None]
     if dev_work:
         work["point_out_in_dev"] = dev_work
+    if _WGRAD_ORDERED:
+        ws = _wgrad_workspace(lib, jobs[0][1].device, ns, npts, len(jobs), n_out, k_in, operand_bf16)
+        ops.timed("weight_grad", work,
+                  lambda: check(lib.rsn_weight_grad_jobs_ordered(ns, npts, ndev, per, len(jobs), arr, ld_dy, n_out, ld_x, k_in,
+                                                                 _WGRAD_MODE, operand_bf16, ptr(ws), ws.numel(), ops._stream())))
+        return
     ops.timed("weight_grad", work,
               lambda: check(lib.rsn_weight_grad_jobs(ns, npts, ndev, per, len(jobs), arr, ld_dy, n_out, ld_x, k_in,
                                                      _WGRAD_MODE, operand_bf16, ops._stream())))
 
 
-def _weight_grads(field, levels, acc: _GradAcc):
+def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
     """dW = dY^T X (+ db) for every linear layer, reduced over all field evaluations of the step at once.
     levels: list of (saved activations, backward-sweep outputs, with_heads[, (device count, rows per count)]).  Buffers of an
     evaluation that was launched with a device-side ray count are sized for the upper bound; the weight-gradient kernel
-    reads the count itself and takes the first count * rows-per-count rows."""
-    global _WGRAD_MODE
+    reads the count itself and takes the first count * rows-per-count rows.  ordered: the reductions with a fixed order of addition
+    (Model.deterministic) instead of the atomic flush."""
+    global _WGRAD_MODE, _WGRAD_ORDERED
+    _WGRAD_ORDERED = bool(ordered)
     _WGRAD_MODE = int(field.mma_mode)  # bf16x6: split operands (fp32-equivalent); bf16: rounded operands (reduced precision)
     # W: the PARAMETER width (n_out / k_in of the reductions); the operand rows are [N, field.width] (leading dimension = the
     # kernels' padded width, taken from the tensors' strides)
@@ -584,7 +614,7 @@ class GetOutputsTrain(torch.autograd.Function):
             # Opt-in memory bound: the reflect branch's weight gradients are reduced NOW (six more reduction launches per step, each
             # with its own flush) and its saved rows and sweep outputs -- a third of the step's memory -- are released before the
             # primary levels' sweep outputs are allocated (the caching allocator hands them the same blocks; one stream: no race).
-            _weight_grads(fld, pending, acc)
+            _weight_grads(fld, pending, acc, getattr(model, "deterministic", False))
             pending = []
             for lv in (st["lrf"], st["lrc"]):
                 lv.pop("saved", None)
@@ -615,7 +645,7 @@ class GetOutputsTrain(torch.autograd.Function):
                "ray_ori_loss": ops._f32c(g_orr_c) if g_orr_c is not None else None, "weights": cc["weights"]}
         gout = _field_backward(fld, st["rays"], st["eb_c"], lc, gin, need_input=False)
         pending.append((lc["saved"], gout, True))
-        _weight_grads(fld, pending, acc)
+        _weight_grads(fld, pending, acc, getattr(model, "deterministic", False))
         del pending, gout
 
         final = acc.finish()

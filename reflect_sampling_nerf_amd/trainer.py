@@ -43,6 +43,8 @@ def build_parser() -> argparse.ArgumentParser:
     tr.add_argument("--save-every", type=int, default=1000, help="checkpoint interval in steps")
     tr.add_argument("--log-every", type=int, default=100, help="loss read-back interval in steps (0: never)")
     tr.add_argument("--seed", type=int, default=0, help="model initialisation and ray sampling seed")
+    tr.add_argument("--deterministic", action="store_true",
+                    help="bit-reproducible run: weight gradients reduced in a fixed order (slower flush, one 68 MB workspace)")
     tr.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
     ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json")
@@ -117,10 +119,11 @@ def load_checkpoint(path: str, model_config=None, device="cuda:0"):
 # ------------------------------------------------------------------------------------------------ train
 def train(scene, out_dir: str, steps: int = 100000, rays: int = 1024, mma: str = "f32", save_every: int = 1000,
           log_every: int = 100, seed: int = 0, device="cuda:0", model_config=None,
-          log: Optional[Callable[[str], None]] = print) -> str:
+          log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None) -> str:
     """Train on `scene` (a data.BlenderScene) for `steps` iterations; returns the path of the last checkpoint.  Checkpoints
     at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer does the same).  The loss is
-    read back only every log_every steps: the iterations in between never wait for the GPU."""
+    read back only every log_every steps: the iterations in between never wait for the GPU.  deterministic: Model.set_deterministic
+    (None: the model's default, i.e. the environment's RSN_DETERMINISTIC); the line that starts the run records it."""
     from .data import RayDataManager
     from .parallel import train_step
     from .train_ops import FusedRAdam
@@ -132,6 +135,10 @@ def train(scene, out_dir: str, steps: int = 100000, rays: int = 1024, mma: str =
     dev = torch.device(device)
     model = make_model(model_config, seed).to(dev).train()
     model.field.set_mma_mode(mma)
+    if deterministic is not None:
+        model.set_deterministic(deterministic)
+    if log is not None:
+        log(f"train: steps {steps} rays {rays} mma {mma} seed {seed} deterministic {model.deterministic}")
     dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed)
     params = model.get_param_groups()["fields"]
     optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000)  # config.py:50-53
@@ -208,7 +215,7 @@ def main(argv=None) -> int:
         scene = load_blender_split(args.data, "train", args.scale_factor)
         print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}")
         train(scene, args.out, steps=args.steps, rays=args.rays, mma=args.mma, save_every=args.save_every,
-              log_every=args.log_every, seed=args.seed)
+              log_every=args.log_every, seed=args.seed, deterministic=True if args.deterministic else None)
         return 0
     scene = load_blender_split(args.data, args.split, args.scale_factor)
     res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images)
