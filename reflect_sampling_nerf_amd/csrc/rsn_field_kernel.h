@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     }
 
     // integrated positional encoding (nerfstudio NeRFEncoding, N2): this lane produces the features of
-    // frequencies 8h..8h+7 into its own LDS slots (slot order: rsn_pack.hip cols_encoding).
+    // frequencies 8h..8h+7 into its own LDS slots (slot order: rsn_pack.hip enc_slot_to_column).
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {
       const float x = (c == 0) ? mc[0] : (c == 1 ? mc[1] : mc[2]);

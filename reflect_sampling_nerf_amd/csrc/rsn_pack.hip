@@ -5,6 +5,7 @@
 // The K index is a free permutation (it only changes the summation order); it is chosen so that the
 // accumulator registers a lane holds after one layer are exactly the B-operand values the same
 // lane needs for the next layer (no cross-lane movement between layers, rsn_field.hip).
+// Host side: the slot maps (each once), the fillers of a job's tables, build_jobs (a network's job list) and its two runners.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -172,39 +173,59 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
   return RSN_OK;
 }
 
+// ---- slot maps: where each input of a GEMM sits in the K order of its packed segment, each stated once -----------------
+// Every filler below, rsn_train_saved_layout (the scatter of the weight gradients) and, independently, the host tables
+// of train_graph.py (held against the library by tests/test_abi_cpu.py) are views of these functions.
+namespace {
+// Reference column (NeRFEncoding order: SURVEY §8(a) N2) of the u-th encoded input of a lane that owns the nf
+// frequencies f0 .. f0 + nf - 1 of every coordinate, -1 for padding:
+//   u in [0, 3 nf):        exp*sin of (coord c = u / nf, freq f = f0 + u % nf)  -> column c*16 + f
+//   u in [3 nf, 6 nf):     exp*sin(. + pi/2) of the same                        -> column 48 + c*16 + f
+//   u in [6 nf, 6 nf + 3): raw coordinate c (the lane with f0 == 0 only)        -> column 96 + c
+int enc_column(int u, int f0, int nf) {
+  if (u < 3 * nf) return (u / nf) * 16 + f0 + u % nf;
+  if (u < 6 * nf) return 48 + ((u - 3 * nf) / nf) * 16 + f0 + u % nf;
+  return (u < 6 * nf + 3 && f0 == 0) ? 96 + (u - 6 * nf) : -1;
+}
+// SH component of the u-th SH input of a lane that owns the n components first .. first + n - 1
+int sh_column(int u, int first, int n) { return (u < n && first + u < RSN_SH_DIM) ? first + u : -1; }
+
+// 32x32x2 kernels: slot k = it*8 + 4h + s is input u = 4 it + s of lane half h, which owns frequencies 8h .. 8h+7
+// (104 slots) and SH components 17h .. 17h+16 (40 slots).  Slots past those counts map to -1 like the padding inside.
+int enc_slot_to_column(int k) { return enc_column((k >> 3) * 4 + (k & 3), 8 * ((k >> 2) & 1), 8); }
+int sh_slot_to_column(int k) { return sh_column((k >> 3) * 4 + (k & 3), 17 * ((k >> 2) & 1), 17); }
+// ring kernels (16x32 fragments): slot k = 32 kk + 8 g + e is input u = 8 kk + e of lane group g, which owns frequencies
+// 4g .. 4g+3 (128 slots) and SH components 9g .. 9g+8, 7 of them for g == 3 (64 slots)
+int enc16_slot_to_column(int k) { return enc_column((k >> 5) * 8 + (k & 7), 4 * ((k >> 3) & 3), 4); }
+int sh16_slot_to_column(int k) { return sh_column((k >> 5) * 8 + (k & 7), 9 * ((k >> 3) & 3), 9); }
+
+// 16x32 fragments: output rows of every GEMM whose result feeds another GEMM are PERMUTED.  Packed row n = 16 b + 4 g + r
+// (what lane group g holds in accumulator register r of block b after the MFMA) carries feature 32 (b / 2) + 8 g +
+// 4 (b % 2) + r.  The eight values lane (m, g) holds of blocks 2kk, 2kk+1 are then the CONTIGUOUS features 32 kk + 8 g .. + 7:
+// the K order of the next layer is the natural one (slot (kk, g, e) <- feature 32 kk + 8 g + e, lane-local hand-off as
+// before), and a training kernel stores a lane's share of an activation row as ONE 16-byte piece per K-step (the four
+// lanes of a point cover 64 contiguous bytes) instead of two 8-byte pieces 32 bytes apart.
+int perm16_row_to_feature(int n) {
+  const int b = n >> 4, g = (n >> 2) & 3, r = n & 3;
+  return 32 * (b >> 1) + 8 * g + 4 * (b & 1) + r;
+}
+
+// The heads block: rows where the epilogue wants the MFMA C rows.  head: 0 density, 1 normals, 2 diff, 3 roughness, 4 tint
+struct HeadRows { int head, row0, n_rows; };
+constexpr HeadRows kHeads[5] = {{0, 0, 1}, {1, 1, 3}, {2, 4, 3}, {3, 8, 1}, {4, 12, 3}};
+}  // namespace
+
 extern "C" int rsn_train_saved_layout(const rsn_field_desc* d, int32_t* enc_cols, int32_t* sh_cols, int32_t* narrow_bf16,
                                       int32_t* enc_map, int32_t* sh_map) {
   RSN_REQUIRE(d && enc_cols && sh_cols && narrow_bf16 && enc_map && sh_map, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
   RsnPackedLayout L;
   const int rc = rsn_compute_layout(d, &L);
   if (rc != RSN_OK) return rc;
-  for (int s = 0; s < 128; ++s) enc_map[s] = -1;
-  for (int s = 0; s < 64; ++s) sh_map[s] = -1;
-  if (rsn_ring_training(d)) {  // slot s = 32 kk + 8 g + e of lane group g (rsn_field_bf16_train.hip; cols_enc16 / cols_sh16 below)
-    *enc_cols = 128; *sh_cols = 64; *narrow_bf16 = d->mma_mode == RSN_MMA_BF16 ? 1 : 0;  // split-bf16: fp32 rows
-    for (int s = 0; s < 128; ++s) {
-      const int kk = s >> 5, g = (s >> 3) & 3, e = s & 7, u = kk * 8 + e;
-      if (u < 12) enc_map[s] = (u / 4) * 16 + 4 * g + (u % 4);
-      else if (u < 24) enc_map[s] = 48 + ((u - 12) / 4) * 16 + 4 * g + ((u - 12) % 4);
-      else if (u < 27 && g == 0) enc_map[s] = 96 + (u - 24);
-    }
-    for (int s = 0; s < 64; ++s) {
-      const int kk = s >> 5, g = (s >> 3) & 3, e = s & 7, u = kk * 8 + e;
-      if (u < 9 && 9 * g + u < RSN_SH_DIM) sh_map[s] = 9 * g + u;
-    }
-    return RSN_OK;
-  }
-  *enc_cols = RSN_K_ENC_PAD; *sh_cols = RSN_K_SH_PAD; *narrow_bf16 = 0;
-  for (int k = 0; k < RSN_K_ENC_PAD; ++k) {  // slot k = it * 8 + 4 h + s of lane half h (cols_encoding / cols_sh below)
-    const int it = k >> 3, h = (k >> 2) & 1, s = k & 3, u = it * 4 + s;
-    if (u < 24) enc_map[k] = (u / 8) * 16 + 8 * h + (u % 8);
-    else if (u < 48) enc_map[k] = 48 + ((u - 24) / 8) * 16 + 8 * h + ((u - 24) % 8);
-    else if (u < 51 && h == 0) enc_map[k] = 96 + (u - 48);
-  }
-  for (int k = 0; k < RSN_K_SH_PAD; ++k) {
-    const int it = k >> 3, h = (k >> 2) & 1, s = k & 3, u = it * 4 + s;
-    if (u < 17) sh_map[k] = 17 * h + u;
-  }
+  const bool ring = rsn_ring_training(d);  // rsn_field_bf16_train.hip / rsn_field_x6_train.hip: rows in the ring's slot order
+  *enc_cols = ring ? 128 : RSN_K_ENC_PAD; *sh_cols = ring ? 64 : RSN_K_SH_PAD;
+  *narrow_bf16 = (ring && d->mma_mode == RSN_MMA_BF16) ? 1 : 0;  // split-bf16: fp32 rows
+  for (int s = 0; s < 128; ++s) enc_map[s] = ring ? enc16_slot_to_column(s) : enc_slot_to_column(s);
+  for (int s = 0; s < 64; ++s) sh_map[s] = ring ? sh16_slot_to_column(s) : sh_slot_to_column(s);
   return RSN_OK;
 }
 
@@ -355,418 +376,261 @@ __global__ void rsn_pack_split_all_kernel(const SplitJob job) {
 
 namespace {
 
-void rows_natural(PackJob& j, int n_rows, int src = 0) {
+// ---- fillers of a job's row / column tables ----------------------------------------------------------------------------
+// packed row n <- source row (transposed: column) index(n); a zero row where that is negative
+template <class F>
+void rows_from(PackJob& j, int n_rows, F index) {
   for (int n = 0; n < n_rows; ++n) {
-    j.row_src[n] = (int16_t)src;
-    j.row_idx[n] = (int16_t)n;
+    const int c = index(n);
+    j.row_src[n] = (int16_t)(c >= 0 ? 0 : -1);
+    j.row_idx[n] = (int16_t)(c >= 0 ? c : 0);
   }
 }
-
+void rows_natural(PackJob& j, int n_rows, int offset = 0) { rows_from(j, n_rows, [=](int n) { return offset + n; }); }
 void cols_natural(PackJob& j, int n_cols, int offset) {
   for (int k = 0; k < n_cols; ++k) j.col[k] = (int16_t)(offset + k);
 }
-
-// Encoded-input order: lane half h owns frequencies 8h..8h+7.  Slot u of a lane:
-//   u in [0,24):  exp*sin  of (coord c = u/8, freq 8h + u%8)   -> reference column c*16 + f
-//   u in [24,48): exp*sin(.+pi/2) of the same                 -> reference column 48 + c*16 + f
-//   u in [48,51): raw coordinate c (h == 0 only)              -> reference column 96 + c
-// packed k = (u/4)*8 + 4h + u%4.            (NeRFEncoding column order: SURVEY §8(a) N2)
-void cols_encoding(PackJob& j) {
-  for (int k = 0; k < RSN_K_ENC_PAD; ++k) {
-    const int it = k >> 3, h = (k >> 2) & 1, s = k & 3;
-    const int u = it * 4 + s;
-    int c = -1;
-    if (u < 24) {
-      c = (u / 8) * 16 + 8 * h + (u % 8);
-    } else if (u < 48) {
-      c = 48 + ((u - 24) / 8) * 16 + 8 * h + ((u - 24) % 8);
-    } else if (u < 51 && h == 0) {
-      c = 96 + (u - 48);
+// packed k <- the source column a slot map gives (encoded / SH inputs)
+void cols_slots(PackJob& j, int n_slots, int (*slot_to_column)(int)) {
+  for (int k = 0; k < n_slots; ++k) j.col[k] = (int16_t)slot_to_column(k);
+}
+// 16x32 fragments: packed row n <- offset + the feature it carries; features >= n_valid (zero-padded units) are zero rows
+void rows_perm16(PackJob& j, int n_rows, int n_valid, int offset = 0) {
+  rows_from(j, n_rows, [=](int n) { const int f = perm16_row_to_feature(n); return f < n_valid ? offset + f : -1; });
+}
+// the five heads tensors (kHeads order) as sources first .. first + 4
+void heads_src(PackJob& j, int first, const float* const heads[5], int ld) {
+  for (int t = 0; t < 5; ++t) { j.src[first + t] = heads[t]; j.ld[first + t] = ld; }
+}
+// the heads block at packed rows base .. base + 15, its tensors being sources 1 .. 5 (source 0: the bottleneck)
+void heads_rows(PackJob& j, int base) {
+  for (const HeadRows& h : kHeads)
+    for (int c = 0; c < h.n_rows; ++c) {
+      j.row_src[base + h.row0 + c] = (int16_t)(1 + h.head);
+      j.row_idx[base + h.row0 + c] = (int16_t)c;
     }
-    j.col[k] = (int16_t)c;
-  }
+}
+// [heads]^T (transpose = 3: k selects the source tensor, sources 0 .. 4).  Heads row hr sits at k = hr of the fp32 layout
+// and, in a 16x32 fragment, at slot (g, e < 4) = k 8 g + e with hr = 4 g + e
+void cols_headsT(PackJob& j, bool frag16) {
+  for (const HeadRows& h : kHeads)
+    for (int c = 0; c < h.n_rows; ++c) {
+      const int hr = h.row0 + c, k = frag16 ? 8 * (hr >> 2) + (hr & 3) : hr;
+      j.col[k] = (int16_t)c;
+      j.col_src[k] = (int16_t)h.head;
+    }
+}
+void rows_rgb(PackJob& j) {  // RGB head: rows 4..6 of its block
+  for (int c = 0; c < 3; ++c) { j.row_src[4 + c] = 0; j.row_idx[4 + c] = (int16_t)c; }
 }
 
-// the same slot order used as packed ROWS (transposed segments): packed row r <- reference column enc(r)
-int enc_slot_to_column(int k) {
-  const int it = k >> 3, h = (k >> 2) & 1, s = k & 3;
-  const int u = it * 4 + s;
-  if (k >= RSN_K_ENC_PAD) return -1;
-  if (u < 24) return (u / 8) * 16 + 8 * h + (u % 8);
-  if (u < 48) return 48 + ((u - 24) / 8) * 16 + 8 * h + ((u - 24) % 8);
-  if (u < 51 && h == 0) return 96 + (u - 48);
-  return -1;
+// appends a cleared job (every row and column zero) and hands it back; the pointer holds until the next call
+PackJob* add_job(std::vector<PackJob>& jobs) {
+  jobs.emplace_back();
+  PackJob* j = &jobs.back();
+  memset(j, 0, sizeof(*j));
+  for (int i = 0; i < PACK_MAX_ROWS; ++i) j->row_src[i] = -1;
+  for (int i = 0; i < PACK_MAX_COLS; ++i) j->col[i] = j->col_src[i] = -1;
+  return j;
 }
 
-// SH order: lane half h owns components 17h .. 17h+16 in slots 0..16 (slots 17..19 zero).
-void cols_sh(PackJob& j) {
-  for (int k = 0; k < RSN_K_SH_PAD; ++k) {
-    const int it = k >> 3, h = (k >> 2) & 1, s = k & 3;
-    const int u = it * 4 + s;
-    j.col[k] = (int16_t)(u < 17 ? 17 * h + u : -1);
-  }
+int job_blocks(const PackJob& j) {  // workgroups of 256 threads, one element each
+  return ((j.is_bias ? j.n_rows : j.n_it * j.nbo * (j.layout >= 1 ? 512 : 256)) + 255) / 256;
 }
+int split_blocks(const SplitSeg& s) { return (((s.n_it + 1) / 2) * s.nbo * 512 + 255) / 256; }
 
-// rsn_pack_weights_table collects the jobs instead of launching them one by one
-struct PackCollector {
-  float* packed;
-  std::vector<PackJob> jobs;
-  std::vector<SplitSeg> splits;
-};
-thread_local PackCollector* g_collect = nullptr;
-
-int split_seg(const float* src, int n_it, int nbo, float* dst, hipStream_t st) {
-  if (g_collect) {
-    SplitSeg sg;
-    sg.src = (unsigned)(src - g_collect->packed); sg.dst = (unsigned)(dst - g_collect->packed);
-    sg.n_it = (short)n_it; sg.nbo = (short)nbo; sg.block0 = 0;
-    g_collect->splits.push_back(sg);
-    return RSN_OK;
-  }
-  const int total = ((n_it + 1) / 2) * nbo * 512;
-  const int threads = 256;
-  hipLaunchKernelGGL(rsn_pack_split_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, st, src, n_it, nbo,
-                     dst);
-  RSN_HIP(hipGetLastError());
-  return RSN_OK;
-}
-
-int launch(const PackJob& j, hipStream_t st) {
-  if (g_collect) {
-    g_collect->jobs.push_back(j);
-    return RSN_OK;
-  }
-  const int total = j.is_bias ? j.n_rows : j.n_it * j.nbo * (j.layout >= 1 ? 512 : 256);
-  const int threads = 256;
-  hipLaunchKernelGGL(rsn_pack_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, st, j);
-  RSN_HIP(hipGetLastError());
-  return RSN_OK;
-}
-
-void clear_job(PackJob& j) {
-  memset(&j, 0, sizeof(j));
-  for (int i = 0; i < PACK_MAX_ROWS; ++i) j.row_src[i] = -1;
-  for (int i = 0; i < PACK_MAX_COLS; ++i) j.col[i] = -1;
-  for (int i = 0; i < PACK_MAX_COLS; ++i) j.col_src[i] = -1;
-}
-
-}  // namespace
-
-extern "C" int rsn_pack_weights(const rsn_field_desc* d, const rsn_field_params* p, float* packed,
-                                size_t packed_bytes, void* stream) {
-  RsnPackedLayout L;
-  int rc = rsn_compute_layout(d, &L);
-  if (rc != RSN_OK) return rc;
-  RSN_REQUIRE(p != nullptr && packed != nullptr, RSN_ERR_INVALID_ARGUMENT, "params/packed is NULL");
-  RSN_REQUIRE(packed_bytes >= L.total * sizeof(float), RSN_ERR_WORKSPACE,
-              "packed buffer too small: %zu < %zu bytes", packed_bytes, L.total * sizeof(float));
-  hipStream_t st = (hipStream_t)stream;
+// Every pack job and every split-bf16 copy of one network, in launch order.  The descriptors depend on the shape and on
+// the parameter / packed POINTERS only; no HIP call, no state outside the arguments.
+int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed, const RsnPackedLayout& L,
+               std::vector<PackJob>& jobs, std::vector<SplitSeg>& splits) {
   // WP: the width the kernels run at (64 / 128 / 256); W: the width of the PARAMETER tensors (rsn_field_desc.param_width): units
   // W .. WP - 1 get zero weights and zero biases (their activations and gradients are exact zeros)
-  const int WP = d->width, W = (d->param_width > 0 ? d->param_width : d->width), NB = L.nb, NBM = L.nbm;
-  PackJob j;
-
-  for (int l = 0; l < d->num_layers; ++l) {
+  const int WP = d->width, W = (d->param_width > 0 ? d->param_width : d->width), MW = d->mid_width, NB = L.nb, NBM = L.nbm;
+  const int n_layers = d->num_layers, skip = d->skip_layer, mid_in = RSN_SH_DIM + W;  // mlp_mid: input cat([SH(34), bottleneck(W)])
+  auto in_f = [&](int l) { return l == 0 ? RSN_ENC_DIM : (l == skip ? RSN_ENC_DIM + W : W); };
+  auto x_off = [&](int l) { return l == skip ? RSN_ENC_DIM : 0; };  // cat([encoding, x]): x columns come second
+  auto gemm = [&](const float* w, int ld, size_t dst, int n_it, int nbo, int transpose = 0) {
+    PackJob* j = add_job(jobs);
+    j->src[0] = w; j->ld[0] = ld; j->dst = packed + dst; j->n_it = n_it; j->nbo = nbo; j->transpose = transpose;
+    return j;
+  };
+  auto bias = [&](const float* b, size_t dst, int n_rows) {
+    PackJob* j = add_job(jobs);
+    j->is_bias = 1; j->src[0] = b; j->dst = packed + dst; j->n_rows = n_rows;
+    return j;
+  };
+  PackJob* j;  // the job being described
+  for (int l = 0; l < n_layers; ++l) {
     RSN_REQUIRE(p->trunk_w[l] && p->trunk_b[l], RSN_ERR_INVALID_ARGUMENT, "trunk layer %d has NULL parameters", l);
-    const int in_f = (l == 0) ? RSN_ENC_DIM : (l == d->skip_layer ? RSN_ENC_DIM + W : W);
-    if (l == 0) {
-      clear_job(j);
-      j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; j.dst = packed + L.w_enc0; j.n_it = RSN_ENC_ITS; j.nbo = NB;
-      rows_natural(j, W); cols_encoding(j);
-      if ((rc = launch(j, st)) != RSN_OK) return rc;
-    } else {
-      clear_job(j);
-      j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; j.dst = packed + L.w_x[l]; j.n_it = NB * 4; j.nbo = NB;
-      rows_natural(j, W);
-      cols_natural(j, W, l == d->skip_layer ? RSN_ENC_DIM : 0);  // cat([encoding, x]): x columns come second
-      if ((rc = launch(j, st)) != RSN_OK) return rc;
-      if (l == d->skip_layer) {
-        clear_job(j);
-        j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; j.dst = packed + L.w_enc_skip; j.n_it = RSN_ENC_ITS; j.nbo = NB;
-        rows_natural(j, W); cols_encoding(j);
-        if ((rc = launch(j, st)) != RSN_OK) return rc;
-      }
+    if (l >= 1) {
+      j = gemm(p->trunk_w[l], in_f(l), L.w_x[l], NB * 4, NB);
+      rows_natural(*j, W); cols_natural(*j, W, x_off(l));
     }
-    clear_job(j);
-    j.is_bias = 1; j.src[0] = p->trunk_b[l]; j.dst = packed + L.b[l]; j.n_rows = WP;
-    rows_natural(j, W);
-    if ((rc = launch(j, st)) != RSN_OK) return rc;
+    if (l == 0 || l == skip) {
+      j = gemm(p->trunk_w[l], in_f(l), l == 0 ? L.w_enc0 : L.w_enc_skip, RSN_ENC_ITS, NB);
+      rows_natural(*j, W); cols_slots(*j, RSN_K_ENC_PAD, enc_slot_to_column);
+    }
+    rows_natural(*bias(p->trunk_b[l], L.b[l], WP), W);
   }
 
   RSN_REQUIRE(p->density_w && p->normals_w && p->roughness_w && p->diff_w && p->tint_w && p->bottleneck_w &&
                   p->mid_w && p->rgb_w && p->density_b && p->normals_b && p->roughness_b && p->diff_b &&
                   p->tint_b && p->bottleneck_b && p->mid_b && p->rgb_b,
               RSN_ERR_INVALID_ARGUMENT, "a head parameter pointer is NULL");
+  const float* const heads_w[5] = {p->density_w, p->normals_w, p->diff_w, p->roughness_w, p->tint_w};
+  const float* const heads_b[5] = {p->density_b, p->normals_b, p->diff_b, p->roughness_b, p->tint_b};
 
-  // bottleneck (blocks 0..NB-1) + heads block NB.  Heads rows (so that MFMA C rows land where the
-  // epilogue wants them): 0 density, 1-3 normals, 4-6 diff, 8 roughness, 12-14 tint.
-  auto heads_rows = [&](PackJob& jj, int base) {
-    jj.row_src[base + 0] = 1; jj.row_idx[base + 0] = 0;
-    for (int c = 0; c < 3; ++c) {
-      jj.row_src[base + 1 + c] = 2;  jj.row_idx[base + 1 + c] = (int16_t)c;
-      jj.row_src[base + 4 + c] = 3;  jj.row_idx[base + 4 + c] = (int16_t)c;
-      jj.row_src[base + 12 + c] = 5; jj.row_idx[base + 12 + c] = (int16_t)c;
-    }
-    jj.row_src[base + 8] = 4; jj.row_idx[base + 8] = 0;
-  };
-  clear_job(j);
-  j.src[0] = p->bottleneck_w; j.src[1] = p->density_w; j.src[2] = p->normals_w; j.src[3] = p->diff_w;
-  j.src[4] = p->roughness_w; j.src[5] = p->tint_w;
-  for (int i = 0; i < PACK_MAX_SRC; ++i) j.ld[i] = W;
-  j.dst = packed + L.w_bh; j.n_it = NB * 4; j.nbo = NB + 1;
-  rows_natural(j, W); heads_rows(j, WP); cols_natural(j, W, 0);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-  clear_job(j);
-  j.is_bias = 1; j.n_rows = WP + 32; j.dst = packed + L.b_bh;
-  j.src[0] = p->bottleneck_b; j.src[1] = p->density_b; j.src[2] = p->normals_b; j.src[3] = p->diff_b;
-  j.src[4] = p->roughness_b; j.src[5] = p->tint_b;
-  rows_natural(j, W); heads_rows(j, WP);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-
-  // mlp_mid: input cat([SH(34), bottleneck(W)])
-  clear_job(j);
-  j.src[0] = p->mid_w; j.ld[0] = RSN_SH_DIM + W; j.dst = packed + L.w_mid_sh; j.n_it = RSN_SH_ITS; j.nbo = NBM;
-  rows_natural(j, d->mid_width); cols_sh(j);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-  clear_job(j);
-  j.src[0] = p->mid_w; j.ld[0] = RSN_SH_DIM + W; j.dst = packed + L.w_mid_x; j.n_it = NB * 4; j.nbo = NBM;
-  rows_natural(j, d->mid_width); cols_natural(j, W, RSN_SH_DIM);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-  clear_job(j);
-  j.is_bias = 1; j.n_rows = d->mid_width; j.src[0] = p->mid_b; j.dst = packed + L.b_mid;
-  rows_natural(j, d->mid_width);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-
-  // field_output_mid (RGB head): rows 4..6 of one 32-row block
-  clear_job(j);
-  j.src[0] = p->rgb_w; j.ld[0] = d->mid_width; j.dst = packed + L.w_rgb; j.n_it = NBM * 4; j.nbo = 1;
-  for (int c = 0; c < 3; ++c) { j.row_src[4 + c] = 0; j.row_idx[4 + c] = (int16_t)c; }
-  cols_natural(j, d->mid_width, 0);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-  clear_job(j);
-  j.is_bias = 1; j.n_rows = 32; j.src[0] = p->rgb_b; j.dst = packed + L.b_rgb;
-  for (int c = 0; c < 3; ++c) { j.row_src[4 + c] = 0; j.row_idx[4 + c] = (int16_t)c; }
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
+  j = gemm(p->bottleneck_w, W, L.w_bh, NB * 4, NB + 1);  // bottleneck (blocks 0..NB-1) + heads block NB
+  heads_src(*j, 1, heads_w, W); rows_natural(*j, W); heads_rows(*j, WP); cols_natural(*j, W, 0);
+  j = bias(p->bottleneck_b, L.b_bh, WP + 32);
+  heads_src(*j, 1, heads_b, 0); rows_natural(*j, W); heads_rows(*j, WP);
+  j = gemm(p->mid_w, mid_in, L.w_mid_sh, RSN_SH_ITS, NBM);
+  rows_natural(*j, MW); cols_slots(*j, RSN_K_SH_PAD, sh_slot_to_column);
+  j = gemm(p->mid_w, mid_in, L.w_mid_x, NB * 4, NBM);
+  rows_natural(*j, MW); cols_natural(*j, W, RSN_SH_DIM);
+  rows_natural(*bias(p->mid_b, L.b_mid, MW), MW);
+  j = gemm(p->rgb_w, MW, L.w_rgb, NBM * 4, 1);  // field_output_mid (RGB head): rows 4..6 of one 32-row block
+  rows_rgb(*j); cols_natural(*j, MW, 0);
+  rows_rgb(*bias(p->rgb_b, L.b_rgb, 32));
 
   // ---------------- transposed segments (dX sweeps of the training path) ----------------
   // With transpose=1 a packed ROW selects a source COLUMN (row_idx) and a packed k selects a source ROW (col).
-  for (int l = 1; l < d->num_layers; ++l) {
-    const int in_f = (l == d->skip_layer) ? RSN_ENC_DIM + W : W;
-    clear_job(j);
-    j.transpose = 1; j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; j.dst = packed + L.wT_x[l]; j.n_it = NB * 4; j.nbo = NB;
-    for (int n = 0; n < W; ++n) { j.row_src[n] = 0; j.row_idx[n] = (int16_t)((l == d->skip_layer ? RSN_ENC_DIM : 0) + n); }
-    cols_natural(j, W, 0);
-    if ((rc = launch(j, st)) != RSN_OK) return rc;
+  for (int l = 1; l < n_layers; ++l) {
+    j = gemm(p->trunk_w[l], in_f(l), L.wT_x[l], NB * 4, NB, 1);
+    rows_natural(*j, W, x_off(l)); cols_natural(*j, W, 0);
   }
-  for (int which = 0; which < 2; ++which) {
-    const int l = which == 0 ? 0 : d->skip_layer;
+  for (int l : {0, skip}) {  // (encoded-input part)^T: rows = the 104 slots padded to 128
     if (l < 0) continue;
-    const int in_f = (l == 0) ? RSN_ENC_DIM : RSN_ENC_DIM + W;
-    clear_job(j);
-    j.transpose = 1; j.src[0] = p->trunk_w[l]; j.ld[0] = in_f;
-    j.dst = packed + (which == 0 ? L.wT_enc0 : L.wT_enc_skip); j.n_it = NB * 4; j.nbo = 4;
-    for (int n = 0; n < 128; ++n) {
-      const int c = enc_slot_to_column(n);
-      j.row_src[n] = (int16_t)(c >= 0 ? 0 : -1); j.row_idx[n] = (int16_t)(c >= 0 ? c : 0);
-    }
-    cols_natural(j, W, 0);
-    if ((rc = launch(j, st)) != RSN_OK) return rc;
+    j = gemm(p->trunk_w[l], in_f(l), l == 0 ? L.wT_enc0 : L.wT_enc_skip, NB * 4, 4, 1);
+    rows_from(*j, 128, enc_slot_to_column); cols_natural(*j, W, 0);
   }
-  {  // [bottleneck; heads]^T : rows = W input features; k < W -> bottleneck row k; k >= W -> heads row k - W
-    // one source per job row is not enough here (k selects the source), so pack the two K ranges separately
-    clear_job(j);
-    j.transpose = 1; j.src[0] = p->bottleneck_w; j.ld[0] = W; j.dst = packed + L.wT_bh; j.n_it = NB * 4; j.nbo = NB;
-    rows_natural(j, W); cols_natural(j, W, 0);
-    if ((rc = launch(j, st)) != RSN_OK) return rc;
-    // heads part: 4 K-iterations (k = 0..31 -> heads rows); the source tensor depends on k (one small tensor per head)
-    const float* hw[5] = {p->density_w, p->normals_w, p->diff_w, p->roughness_w, p->tint_w};
-    const int hbase[5] = {0, 1, 4, 8, 12};
-    const int hrows[5] = {1, 3, 3, 1, 3};
-    clear_job(j);
-    j.transpose = 3;
-    for (int t = 0; t < 5; ++t) { j.src[t] = hw[t]; j.ld[t] = W; }
-    j.dst = packed + L.wT_bh + (size_t)(NB * 4) * NB * 256; j.n_it = 4; j.nbo = NB;
-    rows_natural(j, W);
-    for (int t = 0; t < 5; ++t)
-      for (int c = 0; c < hrows[t]; ++c) { j.col[hbase[t] + c] = (int16_t)c; j.col_src[hbase[t] + c] = (int16_t)t; }
-    if ((rc = launch(j, st)) != RSN_OK) return rc;
-  }
-  clear_job(j);  // (mlp_mid bottleneck part)^T: rows = W (source columns 34..34+W), K = mid rows
-  j.transpose = 1; j.src[0] = p->mid_w; j.ld[0] = RSN_SH_DIM + W; j.dst = packed + L.wT_mid_x; j.n_it = NBM * 4; j.nbo = NB;
-  for (int n = 0; n < W; ++n) { j.row_src[n] = 0; j.row_idx[n] = (int16_t)(RSN_SH_DIM + n); }
-  cols_natural(j, d->mid_width, 0);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-  clear_job(j);  // (RGB head)^T: rows = mid features, K = 32 with k = 4..6 -> rgb rows 0..2
-  j.transpose = 1; j.src[0] = p->rgb_w; j.ld[0] = d->mid_width; j.dst = packed + L.wT_rgb; j.n_it = 4; j.nbo = NBM;
-  rows_natural(j, d->mid_width);
-  for (int c = 0; c < 3; ++c) j.col[4 + c] = (int16_t)c;
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
-  clear_job(j);
-  j.is_bias = 1; j.n_rows = WP; j.src[0] = p->density_w; j.dst = packed + L.v_density;
-  rows_natural(j, W);
-  if ((rc = launch(j, st)) != RSN_OK) return rc;
+  // [bottleneck; heads]^T : rows = W input features; k < W -> bottleneck row k; k >= W -> heads row k - W.  One source per
+  // job row is not enough here (k selects the source), so the two K ranges are packed separately
+  j = gemm(p->bottleneck_w, W, L.wT_bh, NB * 4, NB, 1);
+  rows_natural(*j, W); cols_natural(*j, W, 0);
+  j = gemm(nullptr, 0, L.wT_bh + (size_t)(NB * 4) * NB * 256, 4, NB, 3);  // heads part: 4 K-iterations (k = 0..31 -> heads rows)
+  heads_src(*j, 0, heads_w, W); rows_natural(*j, W); cols_headsT(*j, false);
+  j = gemm(p->mid_w, mid_in, L.wT_mid_x, NBM * 4, NB, 1);  // (mlp_mid bottleneck part)^T: rows = W (source columns 34..34+W), K = mid rows
+  rows_natural(*j, W, RSN_SH_DIM); cols_natural(*j, MW, 0);
+  j = gemm(p->rgb_w, MW, L.wT_rgb, 4, NBM, 1);  // (RGB head)^T: rows = mid features, K = 32 with k = 4..6 -> rgb rows 0..2
+  rows_natural(*j, MW);
+  for (int c = 0; c < 3; ++c) j->col[4 + c] = (int16_t)c;
+  rows_natural(*bias(p->density_w, L.v_density, WP), W);  // the density head's weight row, packed like a bias
 
   // ---------------- 16x32 bf16 fragment stream (rsn_field_bf16_ring16_kernel), straight from the nn.Linear tensors ------
   if (L.q_stream != 0) {
     int frag = 0;
-    // Output rows of every GEMM whose result feeds another GEMM are PERMUTED: packed row 16 b + 4 g + r (what lane group g
-    // holds in accumulator register r of block b after the MFMA) <- source row 32 (b / 2) + 8 g + 4 (b % 2) + r.  The eight
-    // values lane (m, g) holds of blocks 2kk, 2kk+1 are then the CONTIGUOUS features 32 kk + 8 g .. + 7: the K order of
-    // the next layer is the natural one (slot (kk, g, e) <- feature 32 kk + 8 g + e, lane-local hand-off as before), and a
-    // training kernel stores a lane's share of an activation row as ONE 16-byte piece per K-step (the four lanes of a
-    // point cover 64 contiguous bytes) instead of two 8-byte pieces 32 bytes apart.
-    auto rows_perm16 = [&](PackJob& jj, int n_rows, int n_valid) {  // features >= n_valid (zero-padded units): zero rows
-      for (int n = 0; n < n_rows; ++n) {
-        const int b = n >> 4, i = n & 15, feat = 32 * (b >> 1) + 8 * (i >> 2) + 4 * (b & 1) + (i & 3);
-        jj.row_src[n] = (int16_t)(feat < n_valid ? 0 : -1);
-        jj.row_idx[n] = (int16_t)(feat < n_valid ? feat : 0);
-      }
-    };
-    auto cols_x16 = [&](PackJob& jj, int K, int offset) { cols_natural(jj, K, offset); };
-    // encoded inputs: lane group g owns frequencies 4g..4g+3; its 32 slots u = 8 kk + e: 12 sin, 12 cos, 3 raw (g == 0)
-    auto cols_enc16 = [&](PackJob& jj) {
-      for (int k = 0; k < 128; ++k) {
-        const int kk = k >> 5, g = (k >> 3) & 3, e = k & 7, u = kk * 8 + e;
-        int c = -1;
-        if (u < 12) c = (u / 4) * 16 + 4 * g + (u % 4);
-        else if (u < 24) c = 48 + ((u - 12) / 4) * 16 + 4 * g + ((u - 12) % 4);
-        else if (u < 27 && g == 0) c = 96 + (u - 24);
-        jj.col[k] = (int16_t)c;
-      }
-    };
-    // SH inputs: lane group g owns components 9g .. 9g+8 (7 for g == 3) in its slots u = 8 kk + e < 9
-    auto cols_sh16 = [&](PackJob& jj) {
-      for (int k = 0; k < 64; ++k) {
-        const int kk = k >> 5, g = (k >> 3) & 3, e = k & 7, u = kk * 8 + e;
-        jj.col[k] = (int16_t)((u < 9 && 9 * g + u < RSN_SH_DIM) ? 9 * g + u : -1);
-      }
-    };
-    auto qpiece = [&](PackJob& jj, int ks, int nbo16) -> int {
-      jj.layout = L.q_pf == 3 ? 2 : 1; jj.n_it = ks; jj.nbo = nbo16;
-      jj.dst = packed + L.q_stream + (size_t)frag * 256 * L.q_pf;
+    auto ring = [&](const float* w, int ld, int ks, int nbo16, int transpose = 0) {  // the stream's next ks x nbo16 fragments
+      PackJob* q = gemm(w, ld, L.q_stream + (size_t)frag * 256 * L.q_pf, ks, nbo16, transpose);
+      q->layout = L.q_pf == 3 ? 2 : 1;
       frag += ks * nbo16;
-      return launch(jj, st);
+      return q;
     };
-    clear_job(j);
-    j.src[0] = p->trunk_w[0]; j.ld[0] = RSN_ENC_DIM; rows_perm16(j, WP, W); cols_enc16(j);
-    if ((rc = qpiece(j, 4, 16)) != RSN_OK) return rc;
-    for (int l = 1; l < d->num_layers; ++l) {
-      const int in_f = (l == d->skip_layer) ? RSN_ENC_DIM + W : W;
-      clear_job(j);
-      j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; rows_perm16(j, WP, W); cols_x16(j, W, l == d->skip_layer ? RSN_ENC_DIM : 0);
-      if ((rc = qpiece(j, 8, 16)) != RSN_OK) return rc;
-      if (l == d->skip_layer) {
-        clear_job(j);
-        j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; rows_perm16(j, WP, W); cols_enc16(j);
-        if ((rc = qpiece(j, 4, 16)) != RSN_OK) return rc;
+    for (int l = 0; l < n_layers; ++l) {
+      if (l >= 1) {
+        j = ring(p->trunk_w[l], in_f(l), 8, 16);
+        rows_perm16(*j, WP, W); cols_natural(*j, W, x_off(l));
+      }
+      if (l == 0 || l == skip) {
+        j = ring(p->trunk_w[l], in_f(l), 4, 16);
+        rows_perm16(*j, WP, W); cols_slots(*j, 128, enc16_slot_to_column);
       }
     }
-    clear_job(j);  // heads: ONE 16-row block (0 density, 1-3 normals, 4-6 diff, 8 roughness, 12-14 tint) + a zero block
-    j.src[1] = p->density_w; j.src[2] = p->normals_w; j.src[3] = p->diff_w; j.src[4] = p->roughness_w; j.src[5] = p->tint_w;
-    for (int i = 0; i < PACK_MAX_SRC; ++i) j.ld[i] = W;
-    heads_rows(j, 0); cols_x16(j, W, 0);
-    if ((rc = qpiece(j, 8, 2)) != RSN_OK) return rc;
-    clear_job(j);
-    j.src[0] = p->bottleneck_w; j.ld[0] = W; rows_perm16(j, WP, W); cols_x16(j, W, 0);
-    if ((rc = qpiece(j, 8, 16)) != RSN_OK) return rc;
-    clear_job(j);
-    j.src[0] = p->mid_w; j.ld[0] = RSN_SH_DIM + W; rows_perm16(j, d->mid_width, d->mid_width); cols_sh16(j);
-    if ((rc = qpiece(j, 2, 8)) != RSN_OK) return rc;
-    clear_job(j);
-    j.src[0] = p->mid_w; j.ld[0] = RSN_SH_DIM + W; rows_perm16(j, d->mid_width, d->mid_width); cols_x16(j, W, RSN_SH_DIM);
-    if ((rc = qpiece(j, 8, 8)) != RSN_OK) return rc;
-    clear_job(j);  // RGB head: rows 4..6 of the first of four 16-row blocks (three of them zero: whole-group padding)
-    j.src[0] = p->rgb_w; j.ld[0] = d->mid_width;
-    for (int c = 0; c < 3; ++c) { j.row_src[4 + c] = 0; j.row_idx[4 + c] = (int16_t)c; }
-    cols_x16(j, d->mid_width, 0);
-    if ((rc = qpiece(j, 4, 4)) != RSN_OK) return rc;
+    j = ring(nullptr, W, 8, 2);  // heads: ONE 16-row block + a zero block
+    heads_src(*j, 1, heads_w, W); heads_rows(*j, 0); cols_natural(*j, W, 0);
+    j = ring(p->bottleneck_w, W, 8, 16);
+    rows_perm16(*j, WP, W); cols_natural(*j, W, 0);
+    j = ring(p->mid_w, mid_in, 2, 8);
+    rows_perm16(*j, MW, MW); cols_slots(*j, 64, sh16_slot_to_column);
+    j = ring(p->mid_w, mid_in, 8, 8);
+    rows_perm16(*j, MW, MW); cols_natural(*j, W, RSN_SH_DIM);
+    j = ring(p->rgb_w, MW, 4, 4);  // RGB head: rows 4..6 of the first of four 16-row blocks (three of them zero: whole-group padding)
+    rows_rgb(*j); cols_natural(*j, MW, 0);
     RSN_REQUIRE(frag * L.q_pf == L.q_groups * 16, RSN_ERR_INVALID_ARGUMENT, "16x32 stream: %d fragments, layout says %d groups",
                 frag, L.q_groups);
-    // ---- transposed pieces (training sweeps): packed ROW 16 b + 4 g + r <- input feature r16_feature (source COLUMN), packed
-    //      K natural <- output feature (source ROW); transpose = 1 (see above: row_idx selects the source column)
-    auto rowsT_perm16 = [&](PackJob& jj, int n_rows, int n_valid, int col_offset) {
-      for (int n = 0; n < n_rows; ++n) {
-        const int b = n >> 4, i = n & 15, feat = 32 * (b >> 1) + 8 * (i >> 2) + 4 * (b & 1) + (i & 3);
-        jj.row_src[n] = (int16_t)(feat < n_valid ? 0 : -1);
-        jj.row_idx[n] = (int16_t)(feat < n_valid ? col_offset + feat : 0);
+    // ---- transposed pieces (training sweeps): packed ROW <- the input feature it carries (source COLUMN), packed K natural
+    //      <- output feature (source ROW); transpose = 1 as above
+    j = ring(p->rgb_w, MW, 2, 8, 1);  // (RGB head)^T: rows = 128 hidden features; K-step 0 slot (g = 1, e = 0..2) = k 8..10 <- rgb rows; K-step 1 zero
+    rows_perm16(*j, MW, MW);
+    for (int c = 0; c < 3; ++c) j->col[8 + c] = (int16_t)c;
+    j = ring(p->mid_w, mid_in, 4, 16, 1);  // (mlp_mid x part)^T: rows = W bottleneck features (source columns 34..), K = 128 hidden rows
+    rows_perm16(*j, WP, W, RSN_SH_DIM); cols_natural(*j, MW, 0);
+    j = ring(p->bottleneck_w, W, 8, 16, 1);  // [bottleneck]^T: rows = W embedding features, K = W bottleneck rows ...
+    rows_perm16(*j, WP, W); cols_natural(*j, W, 0);
+    j = ring(nullptr, 0, 1, 16, 3);  // ... + [heads]^T as a ninth K-step
+    heads_src(*j, 0, heads_w, W); rows_perm16(*j, WP, W); cols_headsT(*j, true);
+    for (int l = n_layers - 1; l >= 0; --l) {  // last: (layer 0)^T, encoded inputs only
+      if (l == 0 || l == skip) {  // encoded-input slots as packed rows: row 16 b + 4 g + r is slot (kk = b / 2, g, e = 4 (b % 2) + r)
+        j = ring(p->trunk_w[l], in_f(l), 8, 8, 1);
+        rows_from(*j, 128, [](int n) { return enc16_slot_to_column(perm16_row_to_feature(n)); }); cols_natural(*j, W, 0);
       }
-    };
-    // encoded-input slots as packed rows: row 16 b + 4 g + r = slot (kk = b / 2, g, e = 4 (b % 2) + r) of cols_enc16
-    auto rowsT_enc16 = [&](PackJob& jj) {
-      for (int n = 0; n < 128; ++n) {
-        const int b = n >> 4, g = (n >> 2) & 3, r = n & 3, kk = b >> 1, e = 4 * (b & 1) + r, u = kk * 8 + e;
-        int c = -1;
-        if (u < 12) c = (u / 4) * 16 + 4 * g + (u % 4);
-        else if (u < 24) c = 48 + ((u - 12) / 4) * 16 + 4 * g + ((u - 12) % 4);
-        else if (u < 27 && g == 0) c = 96 + (u - 24);
-        jj.row_src[n] = (int16_t)(c >= 0 ? 0 : -1);
-        jj.row_idx[n] = (int16_t)(c >= 0 ? c : 0);
+      if (l >= 1) {
+        j = ring(p->trunk_w[l], in_f(l), 8, 16, 1);
+        rows_perm16(*j, WP, W, x_off(l)); cols_natural(*j, W, 0);
       }
-    };
-    clear_job(j);  // (RGB head)^T: rows = 128 hidden features; K-step 0 slot (g = 1, e = 0..2) = k 8..10 <- rgb row 0..2; K-step 1 zero
-    j.transpose = 1; j.src[0] = p->rgb_w; j.ld[0] = d->mid_width; rowsT_perm16(j, d->mid_width, d->mid_width, 0);
-    for (int c = 0; c < 3; ++c) j.col[8 + c] = (int16_t)c;
-    if ((rc = qpiece(j, 2, 8)) != RSN_OK) return rc;
-    clear_job(j);  // (mlp_mid x part)^T: rows = W bottleneck features (source columns 34..), K = 128 hidden rows
-    j.transpose = 1; j.src[0] = p->mid_w; j.ld[0] = RSN_SH_DIM + W; rowsT_perm16(j, WP, W, RSN_SH_DIM); cols_natural(j, d->mid_width, 0);
-    if ((rc = qpiece(j, 4, 16)) != RSN_OK) return rc;
-    clear_job(j);  // [bottleneck]^T: rows = W embedding features, K = W bottleneck rows ...
-    j.transpose = 1; j.src[0] = p->bottleneck_w; j.ld[0] = W; rowsT_perm16(j, WP, W, 0); cols_natural(j, W, 0);
-    if ((rc = qpiece(j, 8, 16)) != RSN_OK) return rc;
-    {  // ... + [heads]^T as a ninth K-step: slot (g, e < 4) = k 8 g + e <- heads row 4 g + e (0 density, 1-3 normals, 4-6 diff, 8 roughness, 12-14 tint)
-      const float* hw[5] = {p->density_w, p->normals_w, p->diff_w, p->roughness_w, p->tint_w};
-      const int hbase[5] = {0, 1, 4, 8, 12};
-      const int hrows[5] = {1, 3, 3, 1, 3};
-      clear_job(j);
-      j.transpose = 3;
-      for (int t = 0; t < 5; ++t) { j.src[t] = hw[t]; j.ld[t] = W; }
-      rowsT_perm16(j, WP, W, 0);
-      for (int t = 0; t < 5; ++t)
-        for (int c = 0; c < hrows[t]; ++c) {
-          const int hr = hbase[t] + c;  // heads row 4 g + e
-          j.col[8 * (hr >> 2) + (hr & 3)] = (int16_t)c;
-          j.col_src[8 * (hr >> 2) + (hr & 3)] = (int16_t)t;
-        }
-      if ((rc = qpiece(j, 1, 16)) != RSN_OK) return rc;
     }
-    for (int l = d->num_layers - 1; l >= 1; --l) {
-      const int in_f = (l == d->skip_layer) ? RSN_ENC_DIM + W : W;
-      if (l == d->skip_layer) {
-        clear_job(j);
-        j.transpose = 1; j.src[0] = p->trunk_w[l]; j.ld[0] = in_f; rowsT_enc16(j); cols_natural(j, W, 0);
-        if ((rc = qpiece(j, 8, 8)) != RSN_OK) return rc;
-      }
-      clear_job(j);
-      j.transpose = 1; j.src[0] = p->trunk_w[l]; j.ld[0] = in_f;
-      rowsT_perm16(j, WP, W, l == d->skip_layer ? RSN_ENC_DIM : 0); cols_natural(j, W, 0);
-      if ((rc = qpiece(j, 8, 16)) != RSN_OK) return rc;
-    }
-    clear_job(j);
-    j.transpose = 1; j.src[0] = p->trunk_w[0]; j.ld[0] = RSN_ENC_DIM; rowsT_enc16(j); cols_natural(j, W, 0);
-    if ((rc = qpiece(j, 8, 8)) != RSN_OK) return rc;
     RSN_REQUIRE(frag * L.q_pf == L.t_g_end * 16, RSN_ERR_INVALID_ARGUMENT, "transposed 16x32 stream: %d fragments, layout says %d groups",
                 frag, L.t_g_end);
   }
 
   // ---------------- split-bf16 copies (RSN_MMA_BF16X6 / X3 / BF16) of every GEMM segment ----------------
   if (d->mma_mode == RSN_MMA_F32) return RSN_OK;  // the exact-fp32 kernels never read them
-  if ((rc = split_seg(packed + L.w_enc0, RSN_ENC_ITS, NB, packed + L.h_enc0, st)) != RSN_OK) return rc;
-  for (int l = 1; l < d->num_layers; ++l) {
-    if ((rc = split_seg(packed + L.w_x[l], NB * 4, NB, packed + L.h_x[l], st)) != RSN_OK) return rc;
-    if ((rc = split_seg(packed + L.wT_x[l], NB * 4, NB, packed + L.hT_x[l], st)) != RSN_OK) return rc;
+  auto split = [&](size_t src, int n_it, int nbo, size_t dst) {  // block0: numbered by the single-launch path
+    splits.push_back(SplitSeg{(unsigned)src, (unsigned)dst, (short)n_it, (short)nbo, 0});
+  };
+  split(L.w_enc0, RSN_ENC_ITS, NB, L.h_enc0);
+  for (int l = 1; l < n_layers; ++l) {
+    split(L.w_x[l], NB * 4, NB, L.h_x[l]);
+    split(L.wT_x[l], NB * 4, NB, L.hT_x[l]);
   }
-  if (d->skip_layer >= 1) {
-    if ((rc = split_seg(packed + L.w_enc_skip, RSN_ENC_ITS, NB, packed + L.h_enc_skip, st)) != RSN_OK) return rc;
-    if ((rc = split_seg(packed + L.wT_enc_skip, NB * 4, 4, packed + L.hT_enc_skip, st)) != RSN_OK) return rc;
+  if (skip >= 1) {
+    split(L.w_enc_skip, RSN_ENC_ITS, NB, L.h_enc_skip);
+    split(L.wT_enc_skip, NB * 4, 4, L.hT_enc_skip);
   }
-  if ((rc = split_seg(packed + L.wT_enc0, NB * 4, 4, packed + L.hT_enc0, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.w_bh, NB * 4, NB + 1, packed + L.h_bh, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.wT_bh, NB * 4 + 4, NB, packed + L.hT_bh, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.w_mid_sh, RSN_SH_ITS, NBM, packed + L.h_mid_sh, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.w_mid_x, NB * 4, NBM, packed + L.h_mid_x, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.wT_mid_x, NBM * 4, NB, packed + L.hT_mid_x, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.w_rgb, NBM * 4, 1, packed + L.h_rgb, st)) != RSN_OK) return rc;
-  if ((rc = split_seg(packed + L.wT_rgb, 4, NBM, packed + L.hT_rgb, st)) != RSN_OK) return rc;
+  split(L.wT_enc0, NB * 4, 4, L.hT_enc0);
+  split(L.w_bh, NB * 4, NB + 1, L.h_bh);
+  split(L.wT_bh, NB * 4 + 4, NB, L.hT_bh);
+  split(L.w_mid_sh, RSN_SH_ITS, NBM, L.h_mid_sh);
+  split(L.w_mid_x, NB * 4, NBM, L.h_mid_x);
+  split(L.wT_mid_x, NBM * 4, NB, L.hT_mid_x);
+  split(L.w_rgb, NBM * 4, 1, L.h_rgb);
+  split(L.wT_rgb, 4, NBM, L.hT_rgb);
+  return RSN_OK;
+}
+
+// the job lists of the calling thread, reused across calls: packing is on the host path of every training step
+thread_local std::vector<PackJob> t_jobs;
+thread_local std::vector<SplitSeg> t_splits;
+
+// what both entry points check, then the build into t_jobs / t_splits
+int validate_and_build(const rsn_field_desc* d, const rsn_field_params* p, float* packed, size_t packed_bytes) {
+  RsnPackedLayout L;
+  const int rc = rsn_compute_layout(d, &L);
+  if (rc != RSN_OK) return rc;
+  RSN_REQUIRE(p != nullptr && packed != nullptr, RSN_ERR_INVALID_ARGUMENT, "params/packed is NULL");
+  RSN_REQUIRE(packed_bytes >= L.total * sizeof(float), RSN_ERR_WORKSPACE,
+              "packed buffer too small: %zu < %zu bytes", packed_bytes, L.total * sizeof(float));
+  t_jobs.clear(); t_splits.clear();
+  return build_jobs(d, p, packed, L, t_jobs, t_splits);
+}
+
+}  // namespace
+
+// one launch per segment, then one per split-bf16 copy
+extern "C" int rsn_pack_weights(const rsn_field_desc* d, const rsn_field_params* p, float* packed,
+                                size_t packed_bytes, void* stream) {
+  const int rc = validate_and_build(d, p, packed, packed_bytes);
+  if (rc != RSN_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  for (const PackJob& j : t_jobs) {
+    hipLaunchKernelGGL(rsn_pack_kernel, dim3((unsigned)job_blocks(j)), dim3(256), 0, st, j);
+    RSN_HIP(hipGetLastError());
+  }
+  for (const SplitSeg& s : t_splits) {
+    hipLaunchKernelGGL(rsn_pack_split_kernel, dim3((unsigned)split_blocks(s)), dim3(256), 0, st, packed + s.src, (int)s.n_it,
+                       (int)s.nbo, packed + s.dst);
+    RSN_HIP(hipGetLastError());
+  }
   return RSN_OK;
 }
 
@@ -778,48 +642,34 @@ extern "C" int rsn_pack_weights_table(const rsn_field_desc* d, const rsn_field_p
                                       void* stream) {
   RSN_REQUIRE(table != nullptr && table_bytes >= sizeof(PackTable), RSN_ERR_WORKSPACE,
               "job table buffer too small: %zu < %zu bytes", table_bytes, sizeof(PackTable));
-  hipStream_t st = (hipStream_t)stream;
-  // the descriptors depend on the shape and on the parameter / packed POINTERS only: collected on the host, laid out
-  // as one table and (when the caller says the pointers changed, or on first use) uploaded once
-  static thread_local PackCollector col;
-  col.packed = packed;
-  col.jobs.clear();
-  col.splits.clear();
-  g_collect = &col;
-  const int rc = rsn_pack_weights(d, p, packed, packed_bytes, stream);
-  g_collect = nullptr;
+  const int rc = validate_and_build(d, p, packed, packed_bytes);
   if (rc != RSN_OK) return rc;
-  RSN_REQUIRE((int)col.jobs.size() <= PACK_MAX_JOBS && (int)col.splits.size() <= SPLIT_MAX_SEGS, RSN_ERR_UNSUPPORTED,
-              "%zu pack jobs / %zu split segments exceed the table", col.jobs.size(), col.splits.size());
-  int blocks = 0;
+  RSN_REQUIRE((int)t_jobs.size() <= PACK_MAX_JOBS && (int)t_splits.size() <= SPLIT_MAX_SEGS, RSN_ERR_UNSUPPORTED,
+              "%zu pack jobs / %zu split segments exceed the table", t_jobs.size(), t_splits.size());
+  hipStream_t st = (hipStream_t)stream;
   static thread_local PackTable host_table;  // stays alive behind the asynchronous upload
-  if (rebuild_table) {
-    host_table.n_jobs = (int)col.jobs.size();
-    for (int i = 0; i < host_table.n_jobs; ++i) {
-      const PackJob& j = col.jobs[i];
-      host_table.block_start[i] = blocks;
-      host_table.jobs[i] = j;
-      blocks += ((j.is_bias ? j.n_rows : j.n_it * j.nbo * (j.layout >= 1 ? 512 : 256)) + 255) / 256;
-    }
-    host_table.block_start[host_table.n_jobs] = blocks;
-    host_table.n_blocks = blocks;
+  const int n_jobs = (int)t_jobs.size();
+  int blocks = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    if (rebuild_table) { host_table.block_start[i] = blocks; host_table.jobs[i] = t_jobs[i]; }
+    blocks += job_blocks(t_jobs[i]);
+  }
+  if (rebuild_table) {  // the caller says a pointer or the shape changed (or this is the first use): upload the table
+    host_table.n_jobs = n_jobs;
+    host_table.n_blocks = host_table.block_start[n_jobs] = blocks;
     RSN_HIP(hipMemcpyAsync(table, &host_table, sizeof(PackTable), hipMemcpyHostToDevice, st));
-  } else {
-    for (const PackJob& j : col.jobs)
-      blocks += ((j.is_bias ? j.n_rows : j.n_it * j.nbo * (j.layout >= 1 ? 512 : 256)) + 255) / 256;
   }
   hipLaunchKernelGGL(rsn_pack_all_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const PackTable*)table);
   RSN_HIP(hipGetLastError());
-  if (!col.splits.empty()) {
+  if (!t_splits.empty()) {
     SplitJob sj;
     memset(&sj, 0, sizeof(sj));
-    sj.packed = packed;
-    sj.n_segs = (int)col.splits.size();
+    sj.packed = packed; sj.n_segs = (int)t_splits.size();
     int b = 0;
     for (int i = 0; i < sj.n_segs; ++i) {
-      sj.s[i] = col.splits[i];
+      sj.s[i] = t_splits[i];
       sj.s[i].block0 = b;
-      b += (((sj.s[i].n_it + 1) / 2) * sj.s[i].nbo * 512 + 255) / 256;
+      b += split_blocks(sj.s[i]);
     }
     hipLaunchKernelGGL(rsn_pack_split_all_kernel, dim3((unsigned)b), dim3(256), 0, st, sj);
     RSN_HIP(hipGetLastError());

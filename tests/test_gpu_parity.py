@@ -931,6 +931,51 @@ def test_single_launch_packing_equals_per_segment_packing(dev, layers, width, mo
     assert torch.equal(fast2.view(torch.int32), slow.view(torch.int32)) and not torch.equal(fast2, fast)
 
 
+# (trunk layers, base_mlp_layer_width, skip_connections): the smallest shapes that reach every segment kind, the zero-padded
+# units (48 -> 64, 100 -> 128, 200 -> 256), both ring streams (width 256) and the one-layer-after-skip corner (3 layers, skip 1)
+PACKED_PIN_SHAPES = [(2, 48, ()), (4, 100, (2,)), (3, 256, (1,)), (8, 200, (4,))]
+PACKED_PIN_MODES = ["f32", "bf16x6", "bf16x3", "bf16"]
+
+
+def packed_pin_key(layers, param_width, skips, mode):
+    return f"{layers}x{param_width}_skip{skips[0] if skips else -1}_{mode}"
+
+
+def packed_sha256(dev, layers, param_width, skips, mode):
+    """SHA-256 of the whole packed buffer of a field whose parameters are seeded on the CPU.  The buffer is zero-filled
+    first: the f32 mode leaves the split-bf16 regions unwritten.  tools/record_packed_sha256.py records with this function."""
+    import hashlib
+
+    fld = pkg.ReflectSamplingNeRFNerfField(base_mlp_num_layers=layers, base_mlp_layer_width=param_width,
+                                           skip_connections=skips)
+    g = torch.Generator().manual_seed(1000 * layers + param_width)
+    with torch.no_grad():
+        for p in fld.parameters():
+            p.copy_(torch.rand(p.shape, generator=g) - 0.5)
+    fld = fld.to(dev).eval()
+    fld.set_mma_mode(mode)
+    fld.packed_weights()  # allocates the buffer
+    fld._packed.zero_()
+    fld._packed_key = None
+    packed = fld.packed_weights()
+    torch.cuda.synchronize()
+    return hashlib.sha256(packed.cpu().numpy().tobytes()).hexdigest()
+
+
+@pytest.mark.parametrize("mode", PACKED_PIN_MODES)
+@pytest.mark.parametrize("layers,param_width,skips", PACKED_PIN_SHAPES)
+def test_packed_bytes_are_pinned(dev, layers, param_width, skips, mode):
+    """Every byte of the packed buffer (rsn_pack_weights_table through Field.packed_weights) against hashes recorded from
+    the library as it was before the pack jobs got their one builder (tests/golden/packed_sha256.json)."""
+    import json
+
+    from tests.helpers import GOLDEN
+
+    with open(os.path.join(GOLDEN, "packed_sha256.json")) as fh:
+        pinned = json.load(fh)
+    assert packed_sha256(dev, layers, param_width, skips, mode) == pinned[packed_pin_key(layers, param_width, skips, mode)]
+
+
 # ---------------------------------------------------------------------------------------------- edge shapes
 @pytest.mark.parametrize("R,samples", [(1, (1, 1, 1, 1)), (3, (2, 5, 1, 3)), (130, (33, 7, 9, 2))])
 def test_edge_shapes_single_ray_single_sample(dev, R, samples):
