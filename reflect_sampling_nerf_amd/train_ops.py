@@ -184,6 +184,11 @@ class FusedRAdam:
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd: dict) -> None:
+        """Everything is checked before anything is changed: a rejected state dict leaves the optimiser as it was.
+        The learning rate: without a schedule (lr_final None) `lr` of the first group, as torch.  With one, self.lr is the BASE rate
+        that current_lr() decays from step_count, and a torch optimiser under a scheduler (the reference: LambdaLR) keeps its
+        already-decayed rate in `lr` and the base rate in `initial_lr`: that one is taken when present, else self.lr stays as
+        constructed (this class's own state dicts carry the base rate in `lr` and no `initial_lr`)."""
         groups = sd["param_groups"]
         ids = [i for g in groups for i in g["params"]]
         if len(ids) != len(self.params):
@@ -191,22 +196,33 @@ class FusedRAdam:
         g0 = groups[0]
         if any(g.get("weight_decay", 0) != 0 for g in groups):
             raise ValueError("FusedRAdam has no weight decay (the reference trains without: config.py:50-53)")
-        self.lr, self.betas, self.eps = float(g0["lr"]), tuple(g0["betas"]), float(g0["eps"])
-        steps = set()
+        if self.lr_final is None:
+            lr = float(g0["lr"])
+        else:
+            lr = float(g0["initial_lr"]) if g0.get("initial_lr") is not None else self.lr
+        betas, eps = tuple(g0["betas"]), float(g0["eps"])
+        steps, moments = set(), []
         for k, pid in enumerate(ids):  # k-th parameter of this optimizer <- state entry `pid` (torch numbers them in group order)
             st = sd["state"].get(pid)
             p = self.params[k]
             if st is None:  # torch creates a parameter's state at its first gradient: none yet = zeros
-                self.exp_avg[k].zero_()
-                self.exp_avg_sq[k].zero_()
+                moments.append(None)
                 continue
-            if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                raise ValueError(f"parameter {k}: state of shape {tuple(st['exp_avg'].shape)}, parameter {tuple(p.shape)}")
-            self.exp_avg[k] = st["exp_avg"].detach().to(device=p.device, dtype=p.dtype).clone()
-            self.exp_avg_sq[k] = st["exp_avg_sq"].detach().to(device=p.device, dtype=p.dtype).clone()
+            for name in ("exp_avg", "exp_avg_sq"):
+                if tuple(st[name].shape) != tuple(p.shape):
+                    raise ValueError(f"parameter {k}: {name} of shape {tuple(st[name].shape)}, parameter {tuple(p.shape)}")
+            moments.append((st["exp_avg"], st["exp_avg_sq"]))
             steps.add(int(float(st["step"])))
         if len(steps) > 1:
             raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the fused kernel keeps one step count")
+        self.lr, self.betas, self.eps = lr, betas, eps
+        for k, (mv, p) in enumerate(zip(moments, self.params)):
+            if mv is None:
+                self.exp_avg[k].zero_()
+                self.exp_avg_sq[k].zero_()
+            else:
+                self.exp_avg[k] = mv[0].detach().to(device=p.device, dtype=p.dtype).clone()
+                self.exp_avg_sq[k] = mv[1].detach().to(device=p.device, dtype=p.dtype).clone()
         self.step_count = steps.pop() if steps else 0
 
     def current_lr(self) -> float:

@@ -1,7 +1,7 @@
 """Standalone training and evaluation on Blender-format scenes, without nerfstudio.
 
-    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16]
-    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE [--split test] [--out metrics.json]
+    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR]
+    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
 
 `train` is the reference's `ns-train reflect-sampling-nerf --data DIR` loop on this package's own pieces: the reference
 Model config (ReflectSamplingNeRFModelConfig defaults), RayDataManager batches (1024 rays, reflect_sampling_nerf_config.py:36-41),
@@ -10,7 +10,14 @@ use nerfstudio's layout (step-{step:09d}.ckpt holding step / pipeline / optimize
 views in the reference's 1024-ray chunks and writes an ns-eval-shaped JSON: psnr, coarse_psnr, fine_psnr
 (get_image_metrics_and_images) and fine_ssim (metrics.ssim of the clipped mid_reflect_fine render, model.py:468-479).
 fine_lpips is not computed: it needs pretrained network weights that are not part of this package.
-Resuming from a checkpoint and multi-GPU training are not offered here.
+
+`train --resume PATH` continues a run from a step-*.ckpt (or from the newest one of a run directory): model, FusedRAdam moments and
+step count, and -- from the trainer's own checkpoints, which carry a fifth key `rsn_run` -- the run's settings and both torch
+generators.  `--steps` stays the total: a checkpoint of step k continues at k + 1 and writes the file names the uninterrupted run
+would.  With --deterministic the continuation has the uninterrupted run's bits; in the default mode the first resumed step's forward
+pass and loss do, and later steps differ as two uninterrupted default runs differ (the order of the weight-gradient atomics).  A
+checkpoint without `rsn_run` (the reference's ns-train, or an older trainer) continues with the arguments given and a fresh jitter
+stream.  Multi-GPU training is not offered here.
 """
 from __future__ import annotations
 
@@ -18,6 +25,7 @@ import argparse
 import json
 import math
 import os
+import re
 import sys
 import time
 from typing import Callable, Dict, Optional
@@ -28,27 +36,37 @@ import torch
 METHOD_NAME = "reflect-sampling-nerf"
 MMA_CHOICES = ("f32", "bf16x6", "bf16")
 EVAL_CHUNK = 1024  # reflect_sampling_nerf_config.py:41 eval_num_rays_per_chunk
+RUN_STATE_KEY = "rsn_run"  # the trainer's own fifth checkpoint key; nerfstudio's loader ignores it
+RUN_STATE_VERSION = 1
+RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
 LPIPS_NOTE = "fine_lpips not computed: LPIPS needs pretrained network weights that are not shipped with this package"
 
 
-def build_parser() -> argparse.ArgumentParser:
+def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
+    """run_defaults=False: --rays / --mma / --seed parse to None when absent, so that `main` can tell "not given" (a resumed run then
+    takes the checkpoint's value) from a value typed by the user."""
+    dflt = RUN_DEFAULTS if run_defaults else dict.fromkeys(RUN_DEFAULTS)
     ap = argparse.ArgumentParser(prog="python -m reflect_sampling_nerf_amd.trainer", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="command", required=True)
     tr = sub.add_parser("train", help="train on the train split of a Blender-format scene")
     tr.add_argument("--data", required=True, help="scene directory with transforms_train.json")
     tr.add_argument("--out", required=True, help="directory for step-*.ckpt")
     tr.add_argument("--steps", type=int, default=100000, help="training iterations (reference max_num_iterations)")
-    tr.add_argument("--rays", type=int, default=1024, help="rays per batch")
-    tr.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels")
+    tr.add_argument("--rays", type=int, default=dflt["rays"], help="rays per batch (default 1024)")
+    tr.add_argument("--mma", choices=MMA_CHOICES, default=dflt["mma"],
+                    help="matrix-core arithmetic of the field kernels (default f32)")
     tr.add_argument("--save-every", type=int, default=1000, help="checkpoint interval in steps")
     tr.add_argument("--log-every", type=int, default=100, help="loss read-back interval in steps (0: never)")
-    tr.add_argument("--seed", type=int, default=0, help="model initialisation and ray sampling seed")
+    tr.add_argument("--seed", type=int, default=dflt["seed"], help="model initialisation and ray sampling seed (default 0)")
     tr.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible run: weight gradients reduced in a fixed order (slower flush, one 68 MB workspace)")
     tr.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    tr.add_argument("--resume", default=None, metavar="PATH",
+                    help="continue from this step-*.ckpt, or from the newest one in this run directory; --steps stays the total, and "
+                         "--rays / --mma / --seed / --deterministic come from the checkpoint unless given")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
     ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json")
-    ev.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train)")
+    ev.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
     ev.add_argument("--split", default="test")
     ev.add_argument("--max-images", type=int, default=None, help="score only the first N views")
     ev.add_argument("--out", default="metrics.json", help="output JSON")
@@ -71,14 +89,48 @@ def checkpoint_path(out_dir: str, step: int) -> str:
     return os.path.join(out_dir, f"step-{step:09d}.ckpt")
 
 
-def save_checkpoint(path: str, model, optimizer, step: int) -> str:
-    """nerfstudio's trainer layout: the pipeline's state dict is the model's under the `_model.` prefix."""
+_STEP_CKPT = re.compile(r"^step-(\d+)\.ckpt$")
+
+
+def latest_checkpoint(run_dir: str) -> str:
+    """The step-*.ckpt of the highest step in `run_dir` (nerfstudio's --load-dir rule); FileNotFoundError when there is none."""
+    best = None
+    for name in os.listdir(run_dir):
+        m = _STEP_CKPT.match(name)  # a step-*.ckpt.tmp is a save that never finished
+        if m and (best is None or int(m.group(1)) > best[0]):
+            best = (int(m.group(1)), name)
+    if best is None:
+        raise FileNotFoundError(f"no step-*.ckpt in {run_dir}")
+    return os.path.join(run_dir, best[1])
+
+
+def resolve_checkpoint(path: str) -> str:
+    """`path` itself, or the latest checkpoint of the run directory `path`."""
+    return latest_checkpoint(path) if os.path.isdir(path) else path
+
+
+def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device) -> dict:
+    """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
+    bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
+    seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one."""
+    dev = torch.device(device)
+    return {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
+            "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+            "cpu_rng_state": torch.get_rng_state()}
+
+
+def save_checkpoint(path: str, model, optimizer, step: int, run_state: Optional[dict] = None) -> str:
+    """nerfstudio's trainer layout: the pipeline's state dict is the model's under the `_model.` prefix.  run_state
+    (make_run_state) goes under a fifth key, `rsn_run`, only when given."""
     pipeline = {"_model." + k: v.detach().cpu() for k, v in model.state_dict().items()}
     opt = optimizer.state_dict()
     opt = {"state": {i: {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
                      for i, st in opt["state"].items()}, "param_groups": opt["param_groups"]}
+    ckpt = {"step": int(step), "pipeline": pipeline, "optimizers": {"fields": opt}, "scalers": {}}
+    if run_state is not None:
+        ckpt[RUN_STATE_KEY] = run_state
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    torch.save({"step": int(step), "pipeline": pipeline, "optimizers": {"fields": opt}, "scalers": {}}, path + ".tmp")
+    torch.save(ckpt, path + ".tmp")
     os.replace(path + ".tmp", path)
     return path
 
@@ -106,51 +158,126 @@ class _Pipeline(torch.nn.Module):
         self._model = model
 
 
-def load_checkpoint(path: str, model_config=None, device="cuda:0"):
-    """-> (model in eval mode on `device`, checkpoint step).  Strict key check: the reference's own pipeline checkpoints
-    load too (their torchmetrics entries, `_model.lpips.*`, are dropped by the Model's load pre-hook)."""
+def _load_pipeline(path: str, model_config=None):
+    """-> (model on the CPU with the checkpoint's `pipeline` loaded under strict key checking, the checkpoint dict)."""
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     state = ckpt["pipeline"]
     model = make_model(config_for_checkpoint(state, model_config))
     _Pipeline(model).load_state_dict(state, strict=True)
+    return model, ckpt
+
+
+def load_checkpoint(path: str, model_config=None, device="cuda:0"):
+    """-> (model in eval mode on `device`, checkpoint step).  Strict key check: the reference's own pipeline checkpoints
+    load too (their torchmetrics entries, `_model.lpips.*`, are dropped by the Model's load pre-hook)."""
+    model, ckpt = _load_pipeline(path, model_config)
     return model.to(device).eval(), int(ckpt.get("step", -1))
 
 
 # ------------------------------------------------------------------------------------------------ train
-def train(scene, out_dir: str, steps: int = 100000, rays: int = 1024, mma: str = "f32", save_every: int = 1000,
-          log_every: int = 100, seed: int = 0, device="cuda:0", model_config=None,
-          log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None) -> str:
-    """Train on `scene` (a data.BlenderScene) for `steps` iterations; returns the path of the last checkpoint.  Checkpoints
-    at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer does the same).  The loss is
-    read back only every log_every steps: the iterations in between never wait for the GPU.  deterministic: Model.set_deterministic
-    (None: the model's default, i.e. the environment's RSN_DETERMINISTIC); the line that starts the run records it."""
+def _resolve_run_settings(given: dict, recorded: Optional[dict]):
+    """Each of rays / mma / seed / deterministic: the caller's value if given, else the checkpoint's, else the fresh-run default
+    (deterministic: None = the model's own default).  -> (settings, one line per given value that departs from the checkpoint's)."""
+    out, notes = {}, []
+    for k, v in given.items():
+        rec = None if recorded is None else recorded.get(k)
+        if v is None:
+            v = rec if rec is not None else RUN_DEFAULTS.get(k)
+        elif rec is not None and v != rec:
+            notes.append(f"train: {k} {v!r} given, the checkpoint's run had {rec!r}: using {v!r}; the continuation is not bit-exact")
+        out[k] = v
+    return out, notes
+
+
+def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, mma: Optional[str] = None, save_every: int = 1000,
+          log_every: int = 100, seed: Optional[int] = None, device="cuda:0", model_config=None,
+          log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None, resume: Optional[str] = None,
+          on_step: Optional[Callable[[int, torch.Tensor], None]] = None) -> str:
+    """Train on `scene` (a data.BlenderScene) up to iteration `steps` (the total, nerfstudio's max_num_iterations); returns the path
+    of the last checkpoint.  Checkpoints at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer
+    does the same).  The loss is read back only every log_every steps: the iterations in between never wait for the GPU.
+    rays / mma / seed: None = 1024 / "f32" / 0 (a resumed run: the checkpoint's).  deterministic: Model.set_deterministic (None: the
+    checkpoint's when resuming, else the model's default, i.e. the environment's RSN_DETERMINISTIC); the line that starts the run
+    records all four.  on_step(step, loss) is called after every step with the 0-d device tensor of train_step, which nothing here
+    reads back for it.
+
+    resume: a step-*.ckpt or a run directory (its latest).  A checkpoint of step k continues at k + 1 with the same checkpoint names
+    and save_every rule; k >= steps - 1 is a ValueError.  Model (strict, as load_checkpoint) and FusedRAdam state come from the file.
+    From a checkpoint with `rsn_run` (every checkpoint this function writes) also both torch generators and, where not given here,
+    rays / mma / seed / deterministic; a given value that differs is logged and used.  Without `rsn_run` the run continues with the
+    arguments given and a fresh jitter stream, and says once that this is not bit-exact.
+
+    Why the restored state is all of it (default settings: reflect_capacity None, weight_grad_groups 1, no ray_chunk).  A step reads:
+    its batch, a pure function of (seed, rank, step) (RayDataManager.next_train); the loss coefficients and the learning rate,
+    functions of the step and of FusedRAdam.step_count; the parameters and the moments; and the samplers' jitter from the device's
+    torch generator (train_graph: torch.rand).  Everything else a step leaves behind is written before it is read in the next one:
+    model._last_n_masked_dev / _step_n_masked_dev are this step's reflected-ray count, for diagnostics; the Field's packed weights
+    are rebuilt whenever a parameter's version moved; the ordered reduction's workspace is never read before it is written
+    (test_deterministic_gpu).  One value does travel between steps, only under the opt-in reflect_capacity = "auto": the reflected
+    count that sizes the next step's reflect buffers.  It is not saved.  A resumed run starts with full-size buffers, which is
+    the exact computation; it can differ from the uninterrupted run only on a step which that run truncated (and warned about)."""
     from .data import RayDataManager
     from .parallel import train_step
     from .train_ops import FusedRAdam
 
-    if mma not in MMA_CHOICES:
-        raise ValueError(f"mma must be one of {MMA_CHOICES}, got {mma!r}")
     if steps < 1:
         raise ValueError(f"steps must be >= 1, got {steps}")
+    given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic}
+    first, model, ckpt, recorded = 0, None, None, None
+    if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
+        resume = resolve_checkpoint(resume)
+        model, ckpt = _load_pipeline(resume, model_config)
+        first = int(ckpt["step"]) + 1
+        if first >= steps:
+            raise ValueError(f"{resume} is at step {first - 1} and steps is {steps}: the run ends with step {steps - 1}, nothing is "
+                             "left to train (steps is the total, not the number of further steps)")
+        recorded = ckpt.get(RUN_STATE_KEY)
+        if recorded is not None and recorded.get("version") != RUN_STATE_VERSION:
+            raise ValueError(f"{resume}: {RUN_STATE_KEY} version {recorded.get('version')!r}, this trainer reads {RUN_STATE_VERSION}")
+    cfg, notes = _resolve_run_settings(given, recorded)
+    rays, mma, seed, deterministic = cfg["rays"], cfg["mma"], cfg["seed"], cfg["deterministic"]
+    if mma not in MMA_CHOICES:
+        raise ValueError(f"mma must be one of {MMA_CHOICES}, got {mma!r}")
     dev = torch.device(device)
-    model = make_model(model_config, seed).to(dev).train()
+    if model is None:
+        model = make_model(model_config, seed)
+    model = model.to(dev).train()
     model.field.set_mma_mode(mma)
     if deterministic is not None:
         model.set_deterministic(deterministic)
-    if log is not None:
-        log(f"train: steps {steps} rays {rays} mma {mma} seed {seed} deterministic {model.deterministic}")
     dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed)
     params = model.get_param_groups()["fields"]
     optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000)  # config.py:50-53
+    settings = f"steps {steps} rays {rays} mma {mma} seed {seed} deterministic {model.deterministic}"
+    if resume is None:
+        if log is not None:
+            log(f"train: {settings}")
+    else:
+        optimizer.load_state_dict(ckpt["optimizers"]["fields"])
+        if log is not None:
+            log(f"train: resumed from {resume} at step {first - 1}: {settings}")
+            for note in notes:
+                log(note)
+        if recorded is not None:
+            torch.set_rng_state(recorded["cpu_rng_state"])
+            if dev.type == "cuda" and recorded.get("cuda_rng_state") is not None:
+                torch.cuda.set_rng_state(recorded["cuda_rng_state"], dev)
+        elif log is not None:
+            log(f"train: {resume} has no {RUN_STATE_KEY} entry (not written by this trainer): the sampling jitter starts a fresh "
+                "stream, the continuation is not bit-exact")
+        ckpt = None  # the host copy of the checkpoint is not needed past this point
     last = None
     t0 = time.time()
-    for step in range(steps):
+    for step in range(first, steps):
         ray_bundle, batch = dm.next_train(step)
         loss = train_step(model, ray_bundle, batch, optimizer, None, step)
+        if on_step is not None:
+            on_step(step, loss)
         if log is not None and log_every and (step % log_every == 0 or step == steps - 1):
             log(f"step {step:7d}  loss {float(loss):.6f}  lr {optimizer.current_lr():.3e}  {time.time() - t0:8.1f} s")
         if (save_every and step > 0 and step % save_every == 0) or step == steps - 1:
-            last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step)
+            last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
+                                   make_run_state(seed, rays, mma, model.deterministic, dev))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -163,11 +290,13 @@ def _white(image: torch.Tensor) -> torch.Tensor:
 
 def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Optional[str] = None, device="cuda:0",
              model_config=None) -> dict:
-    """Score the checkpoint on every view of `scene` (a data.BlenderScene); -> ns-eval-shaped dict."""
+    """Score the checkpoint (a file, or the latest of a run directory) on every view of `scene` (a data.BlenderScene); -> ns-eval-
+    shaped dict."""
     from . import metrics
     from .data import RayDataManager
 
     dev = torch.device(device)
+    ckpt = resolve_checkpoint(ckpt)
     model, step = load_checkpoint(ckpt, model_config, dev)
     model.config.eval_num_rays_per_chunk = EVAL_CHUNK
     dm = RayDataManager(scene, dev)
@@ -208,14 +337,15 @@ def main(argv=None) -> int:
     from .data import load_blender_split
 
     args = build_parser().parse_args(argv)
+    given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
     if not torch.cuda.is_available():
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
     if args.command == "train":
         scene = load_blender_split(args.data, "train", args.scale_factor)
         print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}")
-        train(scene, args.out, steps=args.steps, rays=args.rays, mma=args.mma, save_every=args.save_every,
-              log_every=args.log_every, seed=args.seed, deterministic=True if args.deterministic else None)
+        train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
+              log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume)
         return 0
     scene = load_blender_split(args.data, args.split, args.scale_factor)
     res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images)
