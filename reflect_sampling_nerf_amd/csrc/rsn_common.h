@@ -25,6 +25,12 @@ int rsn_device_cus();                   // CU count of the current device (cache
     }                                       \
   } while (0)
 
+#define RSN_TRY(call)                       \
+  do {                                      \
+    const int rc_ = (call);                 \
+    if (rc_ != RSN_OK) return rc_;          \
+  } while (0)
+
 #define RSN_HIP(call)                                                                   \
   do {                                                                                  \
     hipError_t e_ = (call);                                                             \

@@ -20,32 +20,23 @@
 #include "rsn_field_bwd_common.h"
 
 // ------------------------------------------------------------------------------------------------
-// One launch over n evaluations (all training or all eval; the plain-bf16 eval kernels take one).
-static int launch_field_jobs(const rsn_field_desc* d, FieldArgs* js, int n, void* stream) {
+// One launch over n evaluations of one field (all training or all eval; the plain-bf16 eval kernels take one).
+static int launch_field_jobs(const rsn_field_desc* d, const float* packed, FieldJob* js, int n, void* stream) {
   RSN_REQUIRE(n >= 1 && n <= RSN_MAX_JOBS, RSN_ERR_INVALID_ARGUMENT, "n_jobs=%d (1..%d)", n, RSN_MAX_JOBS);
   FieldJobs J = {};
-  int rc = rsn_compute_layout(d, &J.s.L);
-  if (rc != RSN_OK) return rc;
-  RSN_REQUIRE(js[0].packed != nullptr, RSN_ERR_INVALID_ARGUMENT, "packed weights pointer is NULL");
-  J.s.packed = js[0].packed;
-  J.s.num_layers = d->num_layers;
-  J.s.skip_layer = d->skip_layer;
+  RSN_TRY(rsn_fill_shared(J.s, d, packed));
   J.s.width = d->width;
-  J.s.density_bias = d->density_bias;
-  for (int i = 0; i < RSN_NUM_FREQS; ++i) J.s.freqs[i] = d->freqs[i];
-  const bool train = js[0].saved.act != nullptr || js[0].saved.enc != nullptr || js[0].saved.heads != nullptr;
-  long long n_tiles = 0;
+  auto training = [](const FieldJob& a) { return a.saved.act != nullptr || a.saved.enc != nullptr || a.saved.heads != nullptr; };
+  const bool train = training(js[0]);
   for (int k = 0; k < n; ++k) {
-    FieldArgs& a = js[k];
+    FieldJob& a = js[k];
     if (a.n_rays <= 0) continue;
-    const bool tk = a.saved.act != nullptr || a.saved.enc != nullptr || a.saved.heads != nullptr;
-    RSN_REQUIRE(tk == train, RSN_ERR_INVALID_ARGUMENT, "job %d: training and eval evaluations cannot share a launch", k);
-    const long long n_points = (long long)a.n_rays * a.S;
-    a.act_stride = n_points * (long long)d->width;
-    n_tiles += (n_points + 127) / 128;
-    J.j[J.n_jobs++] = static_cast<const FieldJob&>(a);
+    RSN_REQUIRE(training(a) == train, RSN_ERR_INVALID_ARGUMENT, "job %d: training and eval evaluations cannot share a launch", k);
+    a.act_stride = (long long)a.n_rays * a.S * (long long)d->width;
+    J.j[J.n_jobs++] = a;
   }
   if (J.n_jobs == 0) return RSN_OK;
+  const long long n_tiles = rsn_job_tiles(J, 128);
   const int cus = rsn_device_cus();
   // one 4-wave workgroup per CU (one wave per SIMD, LDS slab 148 KiB at W=256): persistent tiles
   const long long grid = n_tiles < (long long)cus ? n_tiles : (long long)cus;
@@ -59,15 +50,10 @@ static int launch_field_jobs(const rsn_field_desc* d, FieldArgs* js, int n, void
     const long long g2 = n_tiles < 2LL * cus ? n_tiles : 2LL * cus;
     return rsn_launch_field_bf16(d->width, g2, st, one);
   }
-  if (train && rsn_ring_training(d)) {  // plain / split bf16 training at width 256: the LDS-ring kernels (256- / 128-point tiles)
-    const int tp = mode == RSN_MMA_BF16X6 ? 128 : 256;
-    long long tn = 0;
-    for (int k = 0; k < J.n_jobs; ++k) tn += ((long long)J.j[k].n_rays * J.j[k].S + tp - 1) / tp;
-    return mode == RSN_MMA_BF16X6 ? rsn_launch_field_x6_train(tn, st, J) : rsn_launch_field_bf16_train(tn, st, J);
-  }
+  if (train && rsn_ring_training(d))  // plain / split bf16 training at width 256: the LDS-ring kernels (256- / 128-point tiles)
+    return mode == RSN_MMA_BF16X6 ? rsn_launch_field_x6_train(n_tiles, st, J) : rsn_launch_field_bf16_train(rsn_job_tiles(J, 256), st, J);
   if (mode == RSN_MMA_BF16X6 || (!train && mode == RSN_MMA_BF16X3)) {  // split-bf16 instantiations: rsn_field_split.hip
-    rc = rsn_launch_field_split(d->width, train, mode == RSN_MMA_BF16X6 ? 1 : 2, grid, st, J);
-    if (rc != RSN_OK) return rc;
+    RSN_TRY(rsn_launch_field_split(d->width, train, mode == RSN_MMA_BF16X6 ? 1 : 2, grid, st, J));
     RSN_HIP(hipGetLastError());
     return RSN_OK;
   }
@@ -91,42 +77,54 @@ static int launch_field_jobs(const rsn_field_desc* d, FieldArgs* js, int n, void
   return RSN_OK;
 }
 
-static int launch_field(const rsn_field_desc* d, FieldArgs& a, void* stream) { return launch_field_jobs(d, &a, 1, stream); }
+static int launch_field(const rsn_field_desc* d, const float* pk, FieldJob& a, void* st) { return launch_field_jobs(d, pk, &a, 1, st); }
+
+// The entry points: NULL-check the struct pointers, fill a zeroed FieldJob with the kind's filler (frustum and inf, which the
+// backward has too: rsn_field_common.h), launch.  A training evaluation adds `saved` and this requirement (get_inf_color
+// has no analytic normals, so its wording leaves them out).
+static int require_saved(const char* pfx, const rsn_field_saved* s, bool inf) {
+  RSN_REQUIRE(s->act && s->enc && s->bott && s->sh && s->hid && s->heads && s->relu_bits, RSN_ERR_INVALID_ARGUMENT,
+              "%straining needs every saved-activation buffer%s", pfx, inf ? "" : " (normals may be NULL)");
+  return RSN_OK;
+}
+
+static int fill_gaussians(FieldJob& a, int n_points, const float* means, const float* cov_diag, const float* view_dirs,
+                          const rsn_field_outputs* out, float* embedding) {
+  RSN_REQUIRE(n_points >= 0, RSN_ERR_INVALID_ARGUMENT, "n_points=%d", n_points);
+  RSN_REQUIRE(n_points == 0 || means, RSN_ERR_INVALID_ARGUMENT, "means is NULL");
+  a.mode = RSN_MODE_GAUSS;
+  a.n_rays = n_points; a.S = 1;
+  a.means = means; a.cov_diag = cov_diag; a.view_dirs = view_dirs;
+  a.out = *out;
+  a.embedding = embedding;
+  return RSN_OK;
+}
 
 // rsn_field_forward_train_jobs: several training-mode evaluations of the SAME field in one launch.
 extern "C" int rsn_field_forward_train_jobs(const rsn_field_desc* desc, const float* packed, int32_t n_jobs,
                                             const rsn_field_job* jobs, void* stream) {
   RSN_REQUIRE(desc && jobs, RSN_ERR_INVALID_ARGUMENT, "desc/jobs is NULL");
   RSN_REQUIRE(n_jobs >= 1 && n_jobs <= RSN_MAX_JOBS, RSN_ERR_INVALID_ARGUMENT, "n_jobs=%d (1..%d)", n_jobs, RSN_MAX_JOBS);
-  FieldArgs js[RSN_MAX_JOBS] = {};
+  FieldJob js[RSN_MAX_JOBS] = {};
   for (int k = 0; k < n_jobs; ++k) {
     const rsn_field_job& q = jobs[k];
-    FieldArgs& a = js[k];
+    FieldJob& a = js[k];
+    const JobPrefix pfx(k);
     RSN_REQUIRE(q.kind == 0 || q.kind == 1, RSN_ERR_INVALID_ARGUMENT, "job %d: kind=%d", k, q.kind);
     RSN_REQUIRE(q.n_rays >= 0 && q.saved, RSN_ERR_INVALID_ARGUMENT, "job %d: n_rays=%d / saved is NULL", k, q.n_rays);
-    RSN_REQUIRE(q.saved->act && q.saved->enc && q.saved->bott && q.saved->sh && q.saved->hid && q.saved->heads &&
-                    q.saved->relu_bits,
-                RSN_ERR_INVALID_ARGUMENT, "job %d: training needs every saved-activation buffer (normals may be NULL)", k);
-    a.packed = packed;
-    a.n_rays = q.n_rays; a.n_dev = q.n_dev;
+    RSN_TRY(require_saved(pfx.s, q.saved, false));
     a.saved = *q.saved;
     if (q.kind == 0) {
       RSN_REQUIRE(q.n_samples >= 1 && q.out, RSN_ERR_INVALID_ARGUMENT, "job %d: n_samples=%d / out is NULL", k, q.n_samples);
-      RSN_REQUIRE(q.n_rays == 0 || (q.origins && q.directions && q.pixel_area && q.euclid_bins), RSN_ERR_INVALID_ARGUMENT,
-                  "job %d: a ray input pointer is NULL", k);
-      a.mode = RSN_MODE_FRUSTUM; a.S = q.n_samples;
-      a.origins = q.origins; a.directions = q.directions; a.pixel_area = q.pixel_area; a.bins = q.euclid_bins;
+      RSN_TRY(rsn_fill_frustum(a, pfx.s, q.n_rays, q.n_dev, q.n_samples, q.origins, q.directions, q.pixel_area, q.euclid_bins));
       a.out = *q.out;
     } else {
-      RSN_REQUIRE(q.n_rays == 0 || (q.directions && q.sqradius && q.out_rgb), RSN_ERR_INVALID_ARGUMENT,
-                  "job %d: an input pointer is NULL", k);
-      a.mode = RSN_MODE_INF; a.S = 1;
-      a.directions = q.directions; a.sqradius = q.sqradius;
+      RSN_TRY(rsn_fill_inf(a, pfx.s, q.n_rays, q.n_dev, q.directions, q.sqradius, q.out_rgb));
       a.out.color = q.out_rgb;
       a.saved.normals = nullptr;
     }
   }
-  return launch_field_jobs(desc, js, n_jobs, stream);
+  return launch_field_jobs(desc, packed, js, n_jobs, stream);
 }
 
 extern "C" int rsn_field_forward_gaussians_train(const rsn_field_desc* desc, const float* packed, int32_t n_points,
@@ -134,21 +132,13 @@ extern "C" int rsn_field_forward_gaussians_train(const rsn_field_desc* desc, con
                                                  const rsn_field_outputs* out, float* embedding,
                                                  const rsn_field_saved* saved, void* stream) {
   RSN_REQUIRE(desc && out && saved, RSN_ERR_INVALID_ARGUMENT, "desc/out/saved is NULL");
-  RSN_REQUIRE(n_points >= 0, RSN_ERR_INVALID_ARGUMENT, "n_points=%d", n_points);
-  RSN_REQUIRE(n_points == 0 || means, RSN_ERR_INVALID_ARGUMENT, "means is NULL");
+  FieldJob a = {};
+  RSN_TRY(fill_gaussians(a, n_points, means, cov_diag, view_dirs, out, embedding));
   RSN_REQUIRE(desc->mma_mode == RSN_MMA_F32, RSN_ERR_UNSUPPORTED,
               "training-mode evaluation of explicit Gaussians runs on the exact-fp32 kernels only (mma_mode %d)", desc->mma_mode);
-  RSN_REQUIRE(saved->act && saved->enc && saved->bott && saved->sh && saved->hid && saved->heads && saved->relu_bits,
-              RSN_ERR_INVALID_ARGUMENT, "training needs every saved-activation buffer (normals may be NULL)");
-  FieldArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_GAUSS;
-  a.n_rays = n_points; a.n_dev = nullptr; a.S = 1;
-  a.means = means; a.cov_diag = cov_diag; a.view_dirs = view_dirs;
-  a.out = *out;
-  a.embedding = embedding;
+  RSN_TRY(require_saved("", saved, false));
   a.saved = *saved;
-  return launch_field(desc, a, stream);
+  return launch_field(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_forward_frustum(const rsn_field_desc* desc, const float* packed, int32_t n_rays,
@@ -157,15 +147,10 @@ extern "C" int rsn_field_forward_frustum(const rsn_field_desc* desc, const float
                                          const rsn_field_outputs* out, void* stream) {
   RSN_REQUIRE(desc && out, RSN_ERR_INVALID_ARGUMENT, "desc/out is NULL");
   RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
-  RSN_REQUIRE(n_rays == 0 || (origins && directions && pixel_area && euclid_bins), RSN_ERR_INVALID_ARGUMENT,
-              "a ray input pointer is NULL");
-  FieldArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_FRUSTUM;
-  a.n_rays = n_rays; a.n_dev = n_dev; a.S = n_samples;
-  a.origins = origins; a.directions = directions; a.pixel_area = pixel_area; a.bins = euclid_bins;
+  FieldJob a = {};
+  RSN_TRY(rsn_fill_frustum(a, "", n_rays, n_dev, n_samples, origins, directions, pixel_area, euclid_bins));
   a.out = *out;
-  return launch_field(desc, a, stream);
+  return launch_field(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_forward_frustum_train(const rsn_field_desc* desc, const float* packed, int32_t n_rays,
@@ -175,18 +160,12 @@ extern "C" int rsn_field_forward_frustum_train(const rsn_field_desc* desc, const
                                                const rsn_field_saved* saved, void* stream) {
   RSN_REQUIRE(desc && out && saved, RSN_ERR_INVALID_ARGUMENT, "desc/out/saved is NULL");
   RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
-  RSN_REQUIRE(n_rays == 0 || (origins && directions && pixel_area && euclid_bins), RSN_ERR_INVALID_ARGUMENT,
-              "a ray input pointer is NULL");
-  RSN_REQUIRE(saved->act && saved->enc && saved->bott && saved->sh && saved->hid && saved->heads && saved->relu_bits,
-              RSN_ERR_INVALID_ARGUMENT, "training needs every saved-activation buffer (normals may be NULL)");
-  FieldArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_FRUSTUM;
-  a.n_rays = n_rays; a.n_dev = n_dev; a.S = n_samples;
-  a.origins = origins; a.directions = directions; a.pixel_area = pixel_area; a.bins = euclid_bins;
+  FieldJob a = {};
+  RSN_TRY(rsn_fill_frustum(a, "", n_rays, n_dev, n_samples, origins, directions, pixel_area, euclid_bins));
+  RSN_TRY(require_saved("", saved, false));
   a.out = *out;
   a.saved = *saved;
-  return launch_field(desc, a, stream);
+  return launch_field(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_forward_inf(const rsn_field_desc* desc, const float* packed, int32_t n_rays,
@@ -194,14 +173,10 @@ extern "C" int rsn_field_forward_inf(const rsn_field_desc* desc, const float* pa
                                      float* out_rgb, void* stream) {
   RSN_REQUIRE(desc, RSN_ERR_INVALID_ARGUMENT, "desc is NULL");
   RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
-  RSN_REQUIRE(n_rays == 0 || (directions && sqradius && out_rgb), RSN_ERR_INVALID_ARGUMENT, "an input pointer is NULL");
-  FieldArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_INF;
-  a.n_rays = n_rays; a.n_dev = n_dev; a.S = 1;
-  a.directions = directions; a.sqradius = sqradius;
+  FieldJob a = {};
+  RSN_TRY(rsn_fill_inf(a, "", n_rays, n_dev, directions, sqradius, out_rgb));
   a.out.color = out_rgb;
-  return launch_field(desc, a, stream);
+  return launch_field(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_forward_inf_train(const rsn_field_desc* desc, const float* packed, int32_t n_rays,
@@ -209,18 +184,13 @@ extern "C" int rsn_field_forward_inf_train(const rsn_field_desc* desc, const flo
                                            float* out_rgb, const rsn_field_saved* saved, void* stream) {
   RSN_REQUIRE(desc && saved, RSN_ERR_INVALID_ARGUMENT, "desc/saved is NULL");
   RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
-  RSN_REQUIRE(n_rays == 0 || (directions && sqradius && out_rgb), RSN_ERR_INVALID_ARGUMENT, "an input pointer is NULL");
-  RSN_REQUIRE(saved->act && saved->enc && saved->bott && saved->sh && saved->hid && saved->heads && saved->relu_bits,
-              RSN_ERR_INVALID_ARGUMENT, "training needs every saved-activation buffer");
-  FieldArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_INF;
-  a.n_rays = n_rays; a.n_dev = n_dev; a.S = 1;
-  a.directions = directions; a.sqradius = sqradius;
+  FieldJob a = {};
+  RSN_TRY(rsn_fill_inf(a, "", n_rays, n_dev, directions, sqradius, out_rgb));
+  RSN_TRY(require_saved("", saved, true));
   a.out.color = out_rgb;
   a.saved = *saved;
   a.saved.normals = nullptr;
-  return launch_field(desc, a, stream);
+  return launch_field(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_forward_embedding(const rsn_field_desc* desc, const float* packed, int32_t n_points,
@@ -229,27 +199,19 @@ extern "C" int rsn_field_forward_embedding(const rsn_field_desc* desc, const flo
   RSN_REQUIRE(desc && out, RSN_ERR_INVALID_ARGUMENT, "desc/out is NULL");
   RSN_REQUIRE(n_points >= 0, RSN_ERR_INVALID_ARGUMENT, "n_points=%d", n_points);
   RSN_REQUIRE(n_points == 0 || embedding, RSN_ERR_INVALID_ARGUMENT, "embedding is NULL");
-  FieldArgs a = {};
-  a.packed = packed;
+  FieldJob a = {};  // the one entry point of its kind: filled here
   a.mode = RSN_MODE_EMB;
-  a.n_rays = n_points; a.n_dev = nullptr; a.S = 1;
+  a.n_rays = n_points; a.S = 1;
   a.emb_in = embedding; a.view_dirs = view_dirs; a.rough_in = roughness;
   a.out = *out;
-  return launch_field(desc, a, stream);
+  return launch_field(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_forward_gaussians(const rsn_field_desc* desc, const float* packed, int32_t n_points,
                                            const float* means, const float* cov_diag, const float* view_dirs,
                                            const rsn_field_outputs* out, float* embedding, void* stream) {
   RSN_REQUIRE(desc && out, RSN_ERR_INVALID_ARGUMENT, "desc/out is NULL");
-  RSN_REQUIRE(n_points >= 0, RSN_ERR_INVALID_ARGUMENT, "n_points=%d", n_points);
-  RSN_REQUIRE(n_points == 0 || means, RSN_ERR_INVALID_ARGUMENT, "means is NULL");
-  FieldArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_GAUSS;
-  a.n_rays = n_points; a.n_dev = nullptr; a.S = 1;
-  a.means = means; a.cov_diag = cov_diag; a.view_dirs = view_dirs;
-  a.out = *out;
-  a.embedding = embedding;
-  return launch_field(desc, a, stream);
+  FieldJob a = {};
+  RSN_TRY(fill_gaussians(a, n_points, means, cov_diag, view_dirs, out, embedding));
+  return launch_field(desc, packed, a, stream);
 }

@@ -160,20 +160,13 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
   }
 }
 
-static int launch_bwd_jobs(const rsn_field_desc* d, BwdArgs* js, int n, void* stream) {
+// One launch over the backward sweeps of n evaluations of one field.
+static int launch_bwd_jobs(const rsn_field_desc* d, const float* packed, BwdJob* js, int n, void* stream) {
   RSN_REQUIRE(n >= 1 && n <= RSN_MAX_JOBS, RSN_ERR_INVALID_ARGUMENT, "n_jobs=%d (1..%d)", n, RSN_MAX_JOBS);
   BwdJobs J = {};
-  int rc = rsn_compute_layout(d, &J.s.L);
-  if (rc != RSN_OK) return rc;
-  RSN_REQUIRE(js[0].packed != nullptr, RSN_ERR_INVALID_ARGUMENT, "packed weights pointer is NULL");
-  J.s.packed = js[0].packed;
-  J.s.num_layers = d->num_layers;
-  J.s.skip_layer = d->skip_layer;
-  J.s.density_bias = d->density_bias;
-  for (int i = 0; i < RSN_NUM_FREQS; ++i) J.s.freqs[i] = d->freqs[i];
-  long long n_tiles = 0;
+  RSN_TRY(rsn_fill_shared(J.s, d, packed));
   for (int k = 0; k < n; ++k) {
-    BwdArgs& a = js[k];
+    BwdJob& a = js[k];
     RSN_REQUIRE(a.saved.relu_bits && a.saved.heads && a.gout.dy, RSN_ERR_INVALID_ARGUMENT,
                 "job %d: saved relu_bits / heads and gout.dy are required", k);
     RSN_REQUIRE(!a.need_input_grad || (a.saved.enc && a.gout.d_input), RSN_ERR_INVALID_ARGUMENT,
@@ -186,22 +179,17 @@ static int launch_bwd_jobs(const rsn_field_desc* d, BwdArgs* js, int n, void* st
                 "job %d: ray_pn_loss needs saved.normals and the forward pred_normals", k);
     RSN_REQUIRE(!a.gin.ray_ori_loss || a.fwd.n_dot_d, RSN_ERR_INVALID_ARGUMENT, "job %d: ray_ori_loss needs the forward n_dot_d", k);
     if (a.n_rays <= 0) continue;
-    const long long n_points = (long long)a.n_rays * a.S;
-    a.act_stride = n_points * (long long)d->width;
-    n_tiles += (n_points + 127) / 128;
-    J.j[J.n_jobs++] = static_cast<const BwdJob&>(a);
+    a.act_stride = (long long)a.n_rays * a.S * (long long)d->width;
+    J.j[J.n_jobs++] = a;
   }
   if (J.n_jobs == 0) return RSN_OK;
+  const long long n_tiles = rsn_job_tiles(J, 128);
   const int cached_cus = rsn_device_cus();
   const long long grid = n_tiles < (long long)cached_cus ? n_tiles : (long long)cached_cus;
   hipStream_t st = (hipStream_t)stream;
-  if (rsn_ring_training(d)) {  // plain / split bf16 training at width 256: the LDS-ring kernels (256- / 128-point tiles)
-    const int tp = d->mma_mode == RSN_MMA_BF16X6 ? 128 : 256;
-    long long tn = 0;
-    for (int k = 0; k < J.n_jobs; ++k) tn += ((long long)J.j[k].n_rays * J.j[k].S + tp - 1) / tp;
-    return d->mma_mode == RSN_MMA_BF16X6 ? rsn_launch_field_x6_bwd(tn, st, J) : rsn_launch_field_bf16_bwd(tn, st, J);
-  }
   const bool x6 = d->mma_mode == RSN_MMA_BF16X6;  // fp32-emulating split-bf16 sweeps (opt-in); else exact fp32
+  if (rsn_ring_training(d))  // plain / split bf16 training at width 256: the LDS-ring kernels (256- / 128-point tiles)
+    return x6 ? rsn_launch_field_x6_bwd(n_tiles, st, J) : rsn_launch_field_bf16_bwd(rsn_job_tiles(J, 256), st, J);
 #define RSN_LAUNCH_BWD(NBV)                                                                                  \
   do {                                                                                                       \
     if (x6) hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 1>), dim3((unsigned)grid), dim3(256), 0, st, J);    \
@@ -220,38 +208,33 @@ static int launch_bwd_jobs(const rsn_field_desc* d, BwdArgs* js, int n, void* st
   return RSN_OK;
 }
 
-static int launch_bwd(const rsn_field_desc* d, BwdArgs& a, void* stream) { return launch_bwd_jobs(d, &a, 1, stream); }
+static int launch_bwd(const rsn_field_desc* d, const float* pk, BwdJob& a, void* st) { return launch_bwd_jobs(d, pk, &a, 1, st); }
 
-// rsn_field_backward_jobs: the backward sweeps of several evaluations of the same field in one launch.
+// The entry points: NULL-check the struct pointers, fill a zeroed BwdJob with the kind's filler (rsn_field_common.h, shared with
+// the forward) and the gradient blocks, launch; what the sweeps require of those blocks is checked once, in launch_bwd_jobs.
 extern "C" int rsn_field_backward_jobs(const rsn_field_desc* desc, const float* packed, int32_t n_jobs,
                                        const rsn_field_bwd_job* jobs, void* stream) {
   RSN_REQUIRE(desc && jobs, RSN_ERR_INVALID_ARGUMENT, "desc/jobs is NULL");
   RSN_REQUIRE(n_jobs >= 1 && n_jobs <= RSN_MAX_JOBS, RSN_ERR_INVALID_ARGUMENT, "n_jobs=%d (1..%d)", n_jobs, RSN_MAX_JOBS);
-  BwdArgs js[RSN_MAX_JOBS] = {};
+  BwdJob js[RSN_MAX_JOBS] = {};
   for (int k = 0; k < n_jobs; ++k) {
     const rsn_field_bwd_job& q = jobs[k];
-    BwdArgs& a = js[k];
+    BwdJob& a = js[k];
+    const JobPrefix pfx(k);
     RSN_REQUIRE(q.kind == 0 || q.kind == 1, RSN_ERR_INVALID_ARGUMENT, "job %d: kind=%d", k, q.kind);
     RSN_REQUIRE(q.n_rays >= 0 && q.saved && q.gout, RSN_ERR_INVALID_ARGUMENT, "job %d: n_rays / saved / gout", k);
-    a.packed = packed;
-    a.n_rays = q.n_rays; a.n_dev = q.n_dev; a.need_input_grad = q.need_input_grad;
-    a.saved = *q.saved; a.gout = *q.gout;
     if (q.kind == 0) {
       RSN_REQUIRE(q.n_samples >= 1 && q.fwd && q.gin, RSN_ERR_INVALID_ARGUMENT, "job %d: n_samples / fwd / gin", k);
-      RSN_REQUIRE(q.n_rays == 0 || (q.origins && q.directions && q.pixel_area && q.euclid_bins), RSN_ERR_INVALID_ARGUMENT,
-                  "job %d: a ray input pointer is NULL", k);
-      a.mode = RSN_MODE_FRUSTUM; a.S = q.n_samples;
-      a.origins = q.origins; a.directions = q.directions; a.pixel_area = q.pixel_area; a.bins = q.euclid_bins;
+      RSN_TRY(rsn_fill_frustum(a, pfx.s, q.n_rays, q.n_dev, q.n_samples, q.origins, q.directions, q.pixel_area, q.euclid_bins));
       a.gin = *q.gin; a.fwd = *q.fwd;
     } else {
-      RSN_REQUIRE(q.n_rays == 0 || (q.directions && q.sqradius && q.g_rgb), RSN_ERR_INVALID_ARGUMENT,
-                  "job %d: an input pointer is NULL", k);
-      a.mode = RSN_MODE_INF; a.S = 1;
-      a.directions = q.directions; a.sqradius = q.sqradius;
+      RSN_TRY(rsn_fill_inf(a, pfx.s, q.n_rays, q.n_dev, q.directions, q.sqradius, q.g_rgb));
       a.gin.color = q.g_rgb;
     }
+    a.need_input_grad = q.need_input_grad;
+    a.saved = *q.saved; a.gout = *q.gout;
   }
-  return launch_bwd_jobs(desc, js, n_jobs, stream);
+  return launch_bwd_jobs(desc, packed, js, n_jobs, stream);
 }
 
 extern "C" int rsn_field_backward_frustum(const rsn_field_desc* desc, const float* packed, int32_t n_rays,
@@ -262,15 +245,11 @@ extern "C" int rsn_field_backward_frustum(const rsn_field_desc* desc, const floa
                                           int32_t need_input_grad, void* stream) {
   RSN_REQUIRE(desc && fwd && saved && gin && gout, RSN_ERR_INVALID_ARGUMENT, "a struct pointer is NULL");
   RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
-  RSN_REQUIRE(n_rays == 0 || (origins && directions && pixel_area && euclid_bins), RSN_ERR_INVALID_ARGUMENT,
-              "a ray input pointer is NULL");
-  BwdArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_FRUSTUM;
-  a.n_rays = n_rays; a.n_dev = n_dev; a.S = n_samples; a.need_input_grad = need_input_grad;
-  a.origins = origins; a.directions = directions; a.pixel_area = pixel_area; a.bins = euclid_bins;
+  BwdJob a = {};
+  RSN_TRY(rsn_fill_frustum(a, "", n_rays, n_dev, n_samples, origins, directions, pixel_area, euclid_bins));
+  a.need_input_grad = need_input_grad;
   a.gin = *gin; a.fwd = *fwd; a.saved = *saved; a.gout = *gout;
-  return launch_bwd(desc, a, stream);
+  return launch_bwd(desc, packed, a, stream);
 }
 
 extern "C" int rsn_field_backward_inf(const rsn_field_desc* desc, const float* packed, int32_t n_rays,
@@ -279,13 +258,10 @@ extern "C" int rsn_field_backward_inf(const rsn_field_desc* desc, const float* p
                                       const rsn_field_grads_out* gout, int32_t need_input_grad, void* stream) {
   RSN_REQUIRE(desc && saved && gout, RSN_ERR_INVALID_ARGUMENT, "a struct pointer is NULL");
   RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
-  RSN_REQUIRE(n_rays == 0 || (directions && sqradius && g_rgb), RSN_ERR_INVALID_ARGUMENT, "an input pointer is NULL");
-  BwdArgs a = {};
-  a.packed = packed;
-  a.mode = RSN_MODE_INF;
-  a.n_rays = n_rays; a.n_dev = n_dev; a.S = 1; a.need_input_grad = need_input_grad;
-  a.directions = directions; a.sqradius = sqradius;
+  BwdJob a = {};
+  RSN_TRY(rsn_fill_inf(a, "", n_rays, n_dev, directions, sqradius, g_rgb));
+  a.need_input_grad = need_input_grad;
   a.gin.color = g_rgb;
   a.saved = *saved; a.gout = *gout;
-  return launch_bwd(desc, a, stream);
+  return launch_bwd(desc, packed, a, stream);
 }

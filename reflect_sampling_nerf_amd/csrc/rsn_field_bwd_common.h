@@ -29,8 +29,6 @@ struct BwdJob {
   long long act_stride;
 };
 
-struct BwdArgs : BwdShared, BwdJob {};
-
 // Several evaluations in one launch (see FieldJobs, rsn_field_common.h): the backward sweeps of the two reflect levels and
 // of get_inf_color are independent of each other once the compositing backward of both levels has run.
 struct BwdJobs {

@@ -255,6 +255,57 @@ __device__ __forceinline__ void colour_out(const FieldJob& a, IDX q, float z0, f
 }
 
 
+// ------------------------------------------------------------------------------------------------ host side: filling a launch
+// Shared by the forward (rsn_field.hip) and backward (rsn_field_bwd.hip) entry points, whose blocks name what they have in common
+// alike.  A single call is a one-job launch: `pfx` is "" there and JobPrefix(k).s = "job k: " for evaluation k of a *_jobs call.
+struct JobPrefix {
+  char s[16];
+  explicit JobPrefix(int k) { snprintf(s, sizeof(s), "job %d: ", k); }
+};
+
+// The network of a launch (FieldShared / BwdShared): its packed layout and the descriptor's constants.
+template <class SHARED>
+inline int rsn_fill_shared(SHARED& s, const rsn_field_desc* d, const float* packed) {
+  RSN_TRY(rsn_compute_layout(d, &s.L));
+  RSN_REQUIRE(packed != nullptr, RSN_ERR_INVALID_ARGUMENT, "packed weights pointer is NULL");
+  s.packed = packed;
+  s.num_layers = d->num_layers;
+  s.skip_layer = d->skip_layer;
+  s.density_bias = d->density_bias;
+  for (int i = 0; i < RSN_NUM_FREQS; ++i) s.freqs[i] = d->freqs[i];
+  return RSN_OK;
+}
+
+// Tiles of `tile` points over the jobs of a launch, by the host-side ray counts (an upper bound of what the device counts give).
+template <class JOBS>
+inline long long rsn_job_tiles(const JOBS& J, int tile) {
+  long long n = 0;
+  for (int k = 0; k < J.n_jobs; ++k) n += ((long long)J.j[k].n_rays * J.j[k].S + tile - 1) / tile;
+  return n;
+}
+
+// The fillers of the two kinds both directions have (FieldJob / BwdJob): check the kind's input pointers, set its fields.  The
+// counts are checked by the entry points, whose wording differs.  INF's rgb: its colour (forward) / that colour's gradient.
+template <class JOB>
+inline int rsn_fill_frustum(JOB& a, const char* pfx, int n_rays, const int* n_dev, int n_samples, const float* origins,
+                            const float* directions, const float* pixel_area, const float* euclid_bins) {
+  RSN_REQUIRE(n_rays == 0 || (origins && directions && pixel_area && euclid_bins), RSN_ERR_INVALID_ARGUMENT,
+              "%sa ray input pointer is NULL", pfx);
+  a.mode = RSN_MODE_FRUSTUM;
+  a.n_rays = n_rays; a.n_dev = n_dev; a.S = n_samples;
+  a.origins = origins; a.directions = directions; a.pixel_area = pixel_area; a.bins = euclid_bins;
+  return RSN_OK;
+}
+template <class JOB>
+inline int rsn_fill_inf(JOB& a, const char* pfx, int n_rays, const int* n_dev, const float* directions, const float* sqradius,
+                        const float* rgb) {
+  RSN_REQUIRE(n_rays == 0 || (directions && sqradius && rgb), RSN_ERR_INVALID_ARGUMENT, "%san input pointer is NULL", pfx);
+  a.mode = RSN_MODE_INF;
+  a.n_rays = n_rays; a.n_dev = n_dev; a.S = 1;
+  a.directions = directions; a.sqradius = sqradius;
+  return RSN_OK;
+}
+
 // rsn_field_bf16.hip: the dedicated RSN_MMA_BF16 eval kernel (two workgroups per CU)
 int rsn_launch_field_bf16(int width, long long grid, hipStream_t st, const FieldArgs& a);
 // split-bf16 instantiations of rsn_field_kernel (rsn_field_split.hip); mode 1 = BF16X6, 2 = BF16X3 (eval only)

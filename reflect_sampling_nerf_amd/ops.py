@@ -9,7 +9,7 @@ import torch
 from torch import Tensor
 
 from . import _abi
-from ._abi import CompositeIO, FieldOutputs, ReflectIO, check, ptr
+from ._abi import CompositeIO, FieldOutputs, FieldSaved, ReflectIO, check, ptr
 
 RSN_COMP_EVAL = 1
 RSN_COMP_CLIP_RGB = 2
@@ -167,6 +167,21 @@ def field_outputs_struct(level: Dict[str, Tensor]) -> FieldOutputs:
                  "raw_roughness"):
         setattr(fo, name, ptr(level.get(name)))
     return fo
+
+
+def saved_struct(saved: Dict[str, Tensor]) -> FieldSaved:
+    fs = FieldSaved()
+    for name in ("enc", "act", "bott", "sh", "hid", "heads", "normals", "relu_bits"):
+        setattr(fs, name, ptr(saved.get(name)))
+    return fs
+
+
+def set_frustum_job(job, n_rays: int, n_dev: Tensor, n_samples: int, origins: Tensor, directions: Tensor, pixel_area: Tensor,
+                    euclid_bins: Tensor) -> None:
+    """The conical-frustum (kind 0) fields of a FieldJob / FieldBwdJob."""
+    job.kind, job.n_rays, job.n_dev, job.n_samples = 0, n_rays, n_dev.data_ptr(), n_samples
+    job.origins, job.directions = origins.data_ptr(), directions.data_ptr()
+    job.pixel_area, job.euclid_bins = pixel_area.data_ptr(), euclid_bins.data_ptr()
 
 
 def sh34_encode(directions: Tensor, roughness: Optional[Tensor] = None) -> Tensor:

@@ -17,7 +17,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _abi, ops
-from ._abi import FieldDesc, FieldParams, FieldSaved, check, ptr
+from ._abi import FieldDesc, FieldParams, check, ptr
 from .nerfstudio_compat import Field
 from .reflect_sampling_nerf_components import IntegratedSHEncoding, NeRFEncoding
 
@@ -235,18 +235,12 @@ class ReflectSamplingNeRFNerfField(Field):
         self._no_distortion()
         lib = _abi.load_library()
         R, S = euclid_bins.shape[0], euclid_bins.shape[1] - 1
-        N, W, L = R * S, self.width, self.mlp_base.num_layers
-        dev = origins.device
-        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
-        level = {"sigma": f(R, S), "color": f(R, S, 3), "pred_normals": f(R, S, 3), "n_dot_d": f(R, S),
-                 "diff": f(R, S, 3), "tint": f(R, S, 3), "roughness": f(R, S), "raw_density": f(R, S)}
+        N, dev = R * S, origins.device
+        level = self.alloc_train_level(dev, R, S)
         saved = self.alloc_saved(N, dev)
         if want_normals:
-            saved["normals"] = f(R, S, 3)
-        fo = ops.field_outputs_struct(level)
-        fs = FieldSaved()
-        for k, v in saved.items():
-            setattr(fs, k, ptr(v))
+            saved["normals"] = torch.empty(R, S, 3, device=dev, dtype=torch.float32)
+        fo, fs = ops.field_outputs_struct(level), ops.saved_struct(saved)
         desc = self.field_desc()
         pk = self.packed_weights()
         if work is None:  # (a caller launching with a device-side ray count fills in the evaluated points later)
@@ -276,21 +270,12 @@ class ReflectSamplingNeRFNerfField(Field):
         d_inf = directions if inf_directions is None else inf_directions
         R_inf = d_inf.shape[0]
         dev = origins.device
-        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
-        level = {"sigma": f(R, S), "color": f(R, S, 3), "pred_normals": f(R, S, 3), "n_dot_d": f(R, S),
-                 "diff": f(R, S, 3), "tint": f(R, S, 3), "roughness": f(R, S), "raw_density": f(R, S)}
+        level = self.alloc_train_level(dev, R, S)
         saved, inf_saved = self.alloc_saved(R * S, dev), self.alloc_saved(R_inf, dev)
-        bg = f(R_inf, 3)
-        fo = ops.field_outputs_struct(level)
-        fs, fs_inf = FieldSaved(), FieldSaved()
-        for k, v in saved.items():
-            setattr(fs, k, ptr(v))
-        for k, v in inf_saved.items():
-            setattr(fs_inf, k, ptr(v))
+        bg = torch.empty(R_inf, 3, device=dev, dtype=torch.float32)
+        fo, fs, fs_inf = ops.field_outputs_struct(level), ops.saved_struct(saved), ops.saved_struct(inf_saved)
         jobs = (_abi.FieldJob * 2)()
-        jobs[0].kind, jobs[0].n_rays, jobs[0].n_dev, jobs[0].n_samples = 0, R, n_dev.data_ptr(), S
-        jobs[0].origins, jobs[0].directions = origins.data_ptr(), directions.data_ptr()
-        jobs[0].pixel_area, jobs[0].euclid_bins = pixel_area.data_ptr(), euclid_bins.data_ptr()
+        ops.set_frustum_job(jobs[0], R, n_dev, S, origins, directions, pixel_area, euclid_bins)
         jobs[0].out, jobs[0].saved = C.pointer(fo), C.pointer(fs)
         jobs[1].kind, jobs[1].n_rays, jobs[1].n_dev, jobs[1].n_samples = 1, R_inf, n_dev.data_ptr(), 1
         jobs[1].directions, jobs[1].sqradius, jobs[1].out_rgb = d_inf.data_ptr(), sqradius.data_ptr(), bg.data_ptr()
@@ -334,6 +319,12 @@ class ReflectSamplingNeRFNerfField(Field):
                                torch.tensor(lay["sh_map"], dtype=torch.int32, device=dev))
         return lay["dev"][dev]
 
+    def alloc_train_level(self, dev, *lead: int) -> Dict[str, Tensor]:
+        """The per-sample outputs of one training level (rsn_field_outputs) for samples of shape `lead`."""
+        f = lambda *s: torch.empty(*lead, *s, device=dev, dtype=torch.float32)  # noqa: E731
+        return {"sigma": f(), "color": f(3), "pred_normals": f(3), "n_dot_d": f(), "diff": f(3), "tint": f(3),
+                "roughness": f(), "raw_density": f()}
+
     def alloc_saved(self, N: int, dev) -> Dict[str, Tensor]:
         """The buffers a training-mode forward over N points fills (rsn_field_saved)."""
         W, L = self.width, self.mlp_base.num_layers
@@ -363,17 +354,14 @@ class ReflectSamplingNeRFNerfField(Field):
         lib = _abi.load_library()
         N, dev = means.shape[0], means.device
         f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
-        level = {"sigma": f(N), "color": f(N, 3), "pred_normals": f(N, 3), "n_dot_d": f(N), "diff": f(N, 3),
-                 "tint": f(N, 3), "roughness": f(N), "raw_density": f(N)}
+        level = self.alloc_train_level(dev, N)
         emb = f(N, self.width) if want_embedding else None
         fo = ops.field_outputs_struct(level)
         desc = self.field_desc()
         if want_normals:
             saved = self.alloc_saved(N, dev)
             saved["normals"] = f(N, 3)
-            fs = _abi.FieldSaved()
-            for k in ("enc", "act", "bott", "sh", "hid", "heads", "normals", "relu_bits"):
-                setattr(fs, k, ptr(saved[k]))
+            fs = ops.saved_struct(saved)
             check(lib.rsn_field_forward_gaussians_train(C.byref(desc), ptr(self.packed_weights()), N, ptr(means), ptr(cov_diag),
                                                         ptr(view_dirs), C.byref(fo), ptr(emb), C.byref(fs), ops._stream()))
             level["normals"] = saved["normals"]

@@ -22,7 +22,7 @@ import torch
 from torch import Tensor
 
 from . import _abi, ops
-from ._abi import CompositeBwdIO, FieldGradsIn, FieldGradsOut, FieldSaved, check, ptr
+from ._abi import CompositeBwdIO, FieldGradsIn, FieldGradsOut, check, ptr
 
 ENC_SLOTS = 104
 SH_SLOTS = 40
@@ -85,13 +85,6 @@ def _composite_backward(n, S, background, flags, detach_w, level, eb, weights, g
     io.g_roughness_sample, io.g_bg = ptr(out.get("g_rough")), ptr(out.get("g_bg"))
     check(lib.rsn_composite_backward(n, ptr(n_dev), S, background, flags, detach_w, io, ops._stream()))
     return out
-
-
-def _saved_struct(saved: Dict[str, Tensor]) -> FieldSaved:
-    fs = FieldSaved()
-    for k in ("enc", "act", "bott", "sh", "hid", "heads", "normals", "relu_bits"):
-        setattr(fs, k, ptr(saved.get(k)))
-    return fs
 
 
 def _alloc_gout(field, N: int, dev, need_input: bool):
@@ -304,7 +297,7 @@ def _field_backward(field, rays, eb, level, gin: Dict[str, Optional[Tensor]], ne
     if gin.get("ray_pn_loss") is not None or gin.get("ray_ori_loss") is not None:
         gi.weights = ptr(gin["weights"])
     fo = ops.field_outputs_struct(level)
-    fs = _saved_struct(level["saved"])
+    fs = ops.saved_struct(level["saved"])
     desc = field.field_desc()
     pk = field.packed_weights()
     ops.timed("field_backward_input" if need_input else "field_backward", work or {"points": n * S}, lambda: check(
@@ -329,16 +322,16 @@ def _reflect_field_backward(field, rays2, sq, levels, inf_saved, g_bg, n_dev, R:
         gout, gst = _alloc_gout(field, Rb * S, dev, True)
         gi = FieldGradsIn()
         gi.color = ptr(g_color)
-        fo, fs = ops.field_outputs_struct(lv), _saved_struct(lv["saved"])
+        fo, fs = ops.field_outputs_struct(lv), ops.saved_struct(lv["saved"])
         keep += [gst, gi, fo, fs]
         j = jobs[k]
-        j.kind, j.n_rays, j.n_dev, j.n_samples, j.need_input_grad = 0, Rb, n_dev.data_ptr(), S, 1
-        j.origins, j.directions, j.pixel_area, j.euclid_bins = o.data_ptr(), d.data_ptr(), pa.data_ptr(), eb.data_ptr()
+        ops.set_frustum_job(j, Rb, n_dev, S, o, d, pa, eb)
+        j.need_input_grad = 1
         j.fwd, j.saved, j.gin, j.gout = C.pointer(fo), C.pointer(fs), C.pointer(gi), C.pointer(gst)
         gouts.append(gout)
         dev_work.append((n_dev, S))
     gout_inf, gst_inf = _alloc_gout(field, R, dev, True)
-    fs_inf = _saved_struct(inf_saved)
+    fs_inf = ops.saved_struct(inf_saved)
     keep += [gst_inf, fs_inf]
     j = jobs[len(levels)]
     j.kind, j.n_rays, j.n_dev, j.n_samples, j.need_input_grad = 1, R, n_dev.data_ptr(), 1, 1
@@ -361,6 +354,7 @@ def _ray_sum(x: Tensor, n: int, S: int, n_dev=None) -> Tensor:
 
 
 from .ops import LazyOutputs  # noqa: E402,F401  (kept importable from here)
+from .ops import saved_struct as _saved_struct  # noqa: E402,F401  (its earlier name here, which tests/test_multitile_gpu.py binds)
 
 _LazyAux = LazyOutputs
 

@@ -271,3 +271,25 @@ def test_reference_pipeline_checkpoint_keys_load_strictly():
     direct = dict(src._model.state_dict())
     direct["lpips.net.lin0.model.1.weight"] = torch.zeros(1, 64, 1, 1)
     assert not dst._model.load_state_dict(direct, strict=True).unexpected_keys
+
+
+def test_field_argument_errors_are_pinned(lib):
+    """Every field entry point's answer to invalid arguments -- (return code, rsn_last_error()) for each NULL pointer, missing buffer and
+    count out of range, singly and in pairs (which check comes first), and RSN_OK for calls without rays -- equals
+    tests/golden/field_errors.json, recorded with tools/record_field_errors.py on the library of the commit before the argument
+    fillers were shared: 2,903 calls, none of which reaches the device.  The matrix runs in a child process that hides the GPUs from
+    itself, so a library that let one of the calls through could not launch on the made-up pointers."""
+    import json
+    import subprocess
+    import sys
+
+    res = subprocess.run([sys.executable, os.path.join(REPO, "tools", "record_field_errors.py"), "-"], capture_output=True,
+                         text=True, env={**os.environ, "RSN_LIBRARY": LIB_PATH})
+    assert res.returncode == 0, res.stderr[-2000:]
+    got = json.loads(res.stdout)
+    with open(os.path.join(REPO, "tests", "golden", "field_errors.json")) as fh:
+        want = json.load(fh)
+    assert len(want["cases"]) == 2903 and set(got["cases"]) == set(want["cases"])
+    diff = {k: (want["answers"][want["cases"][k]], got["answers"][got["cases"][k]]) for k in want["cases"]
+            if want["answers"][want["cases"][k]] != got["answers"][got["cases"][k]]}
+    assert not diff, "%d of %d differ, e.g. %s" % (len(diff), len(want["cases"]), sorted(diff.items())[:5])

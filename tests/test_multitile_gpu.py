@@ -521,6 +521,141 @@ def test_inf_entry_points_against_fp64(dev, cus, mode):
             check_param_grads(label, f, grads, gref)
 
 
+# ------------------------------------------------------------------------- 3b. a single call is a one-job launch
+# The single entry points and the *_jobs entry points fill the same job block through the same fillers: the same evaluation through
+# either must give the same bits in every output, saved buffer and gradient buffer (plain stores only).  Shapes: 5 rays x 29 samples
+# = 145 points (two ragged 128-point tiles: exact and bf16x6; one ragged 256-point tile: bf16) with a device-side count of 4 rays in
+# buffers for 5, and 37 get_inf_color rays with a device-side count of 33 -- a dropped n_dev shows as rows written by one path only.
+ONE_JOB_FIELDS = [("f32", 2, 64), ("bf16", 8, 256), ("bf16x6", 8, 256)]  # the ring kernels serve 8 x 256 only
+_POISON = {torch.float32: (torch.int32, 0x7FC0DEAD), torch.bfloat16: (torch.int16, 0x7FC1), torch.int32: (torch.int32, -1)}
+
+
+def _poisoned(bufs):
+    """Every buffer filled with a NaN bit pattern (int32 mask words: all ones), so that what no path wrote does not pass as equal."""
+    for t in bufs.values():
+        it, pattern = _POISON[t.dtype]
+        t.view(it).fill_(pattern)
+    return bufs
+
+
+def _one_job_field(dev, mode, layers, width):
+    torch.manual_seed(51)
+    f = pkg.ReflectSamplingNeRFNerfField(base_mlp_num_layers=layers, base_mlp_layer_width=width).to(dev).train()
+    f.set_mma_mode(mode)
+    return f
+
+
+def _one_job_inputs(kind, dev):
+    """-> (job as _fwd_alone / _bwd_alone take it, rows per ray count, device-side count tensor, points the count leaves live)."""
+    if kind == 0:
+        R, S, live = 5, 29, 4
+        o, d, pa, eb = _rays(R, S, 52)
+        gin = {k: v.reshape((R, S) + v.shape[1:]).to(dev) for k, v in _gin(R * S, 53).items()}
+        job = {"kind": 0, "rays": (o.to(dev), d.to(dev), pa.reshape(R).to(dev), eb.to(dev)), "gin": gin, "n": R * S}
+        return job, torch.tensor([live], dtype=torch.int32, device=dev), live * S
+    dirs, sq, g_rgb = _inf_inputs(37, 54, dev)
+    job = {"kind": 1, "inf": (dirs.to(dev), sq.to(dev)), "g_rgb": g_rgb.to(dev), "n": 37}
+    return job, torch.tensor([33], dtype=torch.int32, device=dev), 33
+
+
+def _one_job_forward(f, job, n_dev, dev, as_job):
+    """The training forward of `job` through its single entry point, or as a one-job rsn_field_forward_train_jobs launch."""
+    lib = _abi.load_library()
+    desc, pk = f.field_desc(), f.packed_weights()
+    saved = f.alloc_saved(job["n"], dev)
+    if job["kind"] == 0:
+        o, d, pa, eb = job["rays"]
+        R, S = eb.shape[0], eb.shape[1] - 1
+        saved["normals"] = torch.empty(R, S, 3, device=dev)
+        out = f.alloc_train_level(dev, R, S)
+    else:
+        dirs, sq = job["inf"]
+        out = {"rgb": torch.empty(job["n"], 3, device=dev)}
+    _poisoned(out)
+    _poisoned(saved)
+    fo, fs = ops.field_outputs_struct(out), ops.saved_struct(saved)
+    q = _abi.FieldJob()
+    q.saved = C.pointer(fs)
+    if job["kind"] == 0:
+        ops.set_frustum_job(q, R, n_dev, S, o, d, pa, eb)
+        q.out = C.pointer(fo)
+        single = lambda: lib.rsn_field_forward_frustum_train(  # noqa: E731
+            C.byref(desc), ptr(pk), R, ptr(n_dev), S, ptr(o), ptr(d), ptr(pa), ptr(eb), C.byref(fo), C.byref(fs), ops._stream())
+    else:
+        q.kind, q.n_rays, q.n_dev, q.n_samples = 1, job["n"], n_dev.data_ptr(), 1
+        q.directions, q.sqradius, q.out_rgb = dirs.data_ptr(), sq.data_ptr(), out["rgb"].data_ptr()
+        single = lambda: lib.rsn_field_forward_inf_train(  # noqa: E731
+            C.byref(desc), ptr(pk), job["n"], ptr(n_dev), ptr(dirs), ptr(sq), ptr(out["rgb"]), C.byref(fs), ops._stream())
+    check(lib.rsn_field_forward_train_jobs(C.byref(desc), ptr(pk), 1, C.byref(q), ops._stream()) if as_job else single())
+    torch.cuda.synchronize()
+    return {**out, "saved": saved}
+
+
+def _one_job_backward(f, job, n_dev, fwd, dev, as_job):
+    lib = _abi.load_library()
+    desc, pk = f.field_desc(), f.packed_weights()
+    g, st = train_graph._alloc_gout(f, job["n"], dev, True)
+    _poisoned(g)
+    fs = ops.saved_struct(fwd["saved"])
+    q = _abi.FieldBwdJob()
+    q.need_input_grad, q.saved, q.gout = 1, C.pointer(fs), C.pointer(st)
+    if job["kind"] == 0:
+        o, d, pa, eb = job["rays"]
+        R, S = eb.shape[0], eb.shape[1] - 1
+        gi, fo = _gin_struct(job["gin"]), ops.field_outputs_struct(fwd)
+        ops.set_frustum_job(q, R, n_dev, S, o, d, pa, eb)
+        q.fwd, q.gin = C.pointer(fo), C.pointer(gi)
+        single = lambda: lib.rsn_field_backward_frustum(  # noqa: E731
+            C.byref(desc), ptr(pk), R, ptr(n_dev), S, ptr(o), ptr(d), ptr(pa), ptr(eb), C.byref(fo), C.byref(fs), C.byref(gi),
+            C.byref(st), 1, ops._stream())
+    else:
+        dirs, sq = job["inf"]
+        q.kind, q.n_rays, q.n_dev, q.n_samples = 1, job["n"], n_dev.data_ptr(), 1
+        q.directions, q.sqradius, q.g_rgb = dirs.data_ptr(), sq.data_ptr(), job["g_rgb"].data_ptr()
+        single = lambda: lib.rsn_field_backward_inf(  # noqa: E731
+            C.byref(desc), ptr(pk), job["n"], ptr(n_dev), ptr(dirs), ptr(sq), C.byref(fs), ptr(job["g_rgb"]), C.byref(st), 1,
+            ops._stream())
+    check(lib.rsn_field_backward_jobs(C.byref(desc), ptr(pk), 1, C.byref(q), ops._stream()) if as_job else single())
+    torch.cuda.synchronize()
+    return g
+
+
+def _assert_same_bits(label, a, b, n, live):
+    """Buffers of the two paths: equal bit for bit over all n rows, and written (not the fill pattern) in each of the `live` rows."""
+    for key in a:
+        x, y = a[key], b[key]
+        it, pattern = _POISON[x.dtype]
+        xb, yb = _flat(x.view(it), n), _flat(y.view(it), n)
+        rows = (xb != yb).any(dim=1).nonzero().flatten().tolist()
+        assert not rows, f"{label} {key}: the one-job launch differs from the single call in rows {rows[:8]} ({len(rows)} of {n})"
+        blank = (xb[:live] == pattern).all(dim=1).nonzero().flatten().tolist()
+        assert not blank, f"{label} {key}: rows {blank[:8]} ({len(blank)} of the {live} live rows) were written by neither path"
+
+
+@pytest.mark.parametrize("mode,layers,width", ONE_JOB_FIELDS)
+@pytest.mark.parametrize("kind", [0, 1], ids=["frustum", "inf"])
+def test_single_forward_equals_one_job_launch(dev, kind, mode, layers, width):
+    """rsn_field_forward_frustum_train / rsn_field_forward_inf_train against rsn_field_forward_train_jobs with that one job (kind 0 / 1)."""
+    f = _one_job_field(dev, mode, layers, width)
+    job, n_dev, live = _one_job_inputs(kind, dev)
+    a, b = (_one_job_forward(f, job, n_dev, dev, as_job) for as_job in (False, True))
+    label = f"forward {'inf' if kind else 'frustum'} {mode}"
+    _assert_same_bits(label, {k: v for k, v in a.items() if k != "saved"}, b, job["n"], live)
+    _assert_same_bits(label + " saved", a["saved"], b["saved"], job["n"], live)
+
+
+@pytest.mark.parametrize("mode,layers,width", ONE_JOB_FIELDS)
+@pytest.mark.parametrize("kind", [0, 1], ids=["frustum", "inf"])
+def test_single_backward_equals_one_job_launch(dev, kind, mode, layers, width):
+    """rsn_field_backward_frustum / rsn_field_backward_inf against rsn_field_backward_jobs with that one job (kind 0 / 1), both on
+    the saved buffers of one training forward, with the input gradient."""
+    f = _one_job_field(dev, mode, layers, width)
+    job, n_dev, live = _one_job_inputs(kind, dev)
+    fwd = _one_job_forward(f, job, n_dev, dev, as_job=False)
+    a, b = (_one_job_backward(f, job, n_dev, fwd, dev, as_job) for as_job in (False, True))
+    _assert_same_bits(f"backward {'inf' if kind else 'frustum'} {mode} gout", a, b, job["n"], live)
+
+
 # ---------------------------------------------------------------------------------------------- 4. whole steps
 def _weighted_loss(out, tgt, wr):
     """_loss_from_outputs of test_gpu_parity with a weight per ray instead of the mean over rays."""
