@@ -115,3 +115,17 @@ def tile_rel_err(got, ref, tile):
     r2 = torch.nn.functional.pad((b ** 2).sum(1), (0, pad)).reshape(nt, tile).sum(1)
     rel = (d2 / (r2 + 1e-12 * float(r2.mean()) + 1e-300)).sqrt()
     return rel.repeat_interleave(tile)[:n]
+
+
+# ---------------------------------------------------------------------------------------------- buffers no kernel has written
+# NaN bit patterns per dtype (int32 words: all ones; uint8 masks: a value that is neither 0 nor 1)
+_POISON = {torch.float32: (torch.int32, 0x7FC0DEAD), torch.bfloat16: (torch.int16, 0x7FC1), torch.int32: (torch.int32, -1),
+           torch.uint8: (torch.uint8, 0xA5)}
+
+
+def _poisoned(bufs):
+    """Every buffer filled with a NaN bit pattern (int32 mask words: all ones), so that what no path wrote does not pass as equal."""
+    for t in bufs.values():
+        it, pattern = _POISON[t.dtype]
+        t.view(it).fill_(pattern)
+    return bufs

@@ -16,7 +16,7 @@ import reflect_sampling_nerf_amd as pkg
 from oracle import cpu_ref
 from reflect_sampling_nerf_amd import _abi, ops, train_graph
 from reflect_sampling_nerf_amd._abi import FieldGradsIn, check, ptr
-from tests.helpers import check_points, default_dtype, locate, multitile_geometry, point_err, tile_rel_err
+from tests.helpers import _POISON, _poisoned, check_points, default_dtype, locate, multitile_geometry, point_err, tile_rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -527,16 +527,6 @@ def test_inf_entry_points_against_fp64(dev, cus, mode):
 # = 145 points (two ragged 128-point tiles: exact and bf16x6; one ragged 256-point tile: bf16) with a device-side count of 4 rays in
 # buffers for 5, and 37 get_inf_color rays with a device-side count of 33 -- a dropped n_dev shows as rows written by one path only.
 ONE_JOB_FIELDS = [("f32", 2, 64), ("bf16", 8, 256), ("bf16x6", 8, 256)]  # the ring kernels serve 8 x 256 only
-_POISON = {torch.float32: (torch.int32, 0x7FC0DEAD), torch.bfloat16: (torch.int16, 0x7FC1), torch.int32: (torch.int32, -1)}
-
-
-def _poisoned(bufs):
-    """Every buffer filled with a NaN bit pattern (int32 mask words: all ones), so that what no path wrote does not pass as equal."""
-    for t in bufs.values():
-        it, pattern = _POISON[t.dtype]
-        t.view(it).fill_(pattern)
-    return bufs
-
 
 def _one_job_field(dev, mode, layers, width):
     torch.manual_seed(51)
