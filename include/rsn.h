@@ -639,6 +639,43 @@ size_t rsn_ssim_workspace_bytes(int32_t height, int32_t width);
 int rsn_ssim(int32_t height, int32_t width, const float* pred, const float* target, const float* data_range,
              void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+
+/* ---- mesh export: the iso-surface of a scalar volume as an indexed triangle mesh (additive to ABI 18: no existing call
+ * changes).  Marching tetrahedra on the Kuhn (Freudenthal) split of every grid cell: no case table, consistent across
+ * shared cell faces by construction (a surface away from the grid boundary is closed), and every surface vertex lies on
+ * exactly one grid edge, so vertices are welded by arithmetic.  No atomics: two runs give the same bits in the same order.
+ *
+ * Grid: vol is fp32 [nz, ny, nx], x fastest; vertex (i, j, k) has flat index v = (k*ny + j)*nx + i and position
+ * origin + spacing * (i, j, k) (per axis: one fp32 multiply, one fp32 add).  Vertex v owns 7 outgoing edges dir = 0..6
+ * towards the offsets (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1); an edge exists if its far end is in
+ * the grid.  The cell with lowest corner c splits into 6 tetrahedra, one per permutation (a, b, c') of the axes, with
+ * vertices c, c + e_a, c + e_a + e_b, c + (1,1,1).
+ *
+ * Classification: a vertex is inside when vol >= iso (NaN: outside).
+ * Surface vertices: one per existing edge whose ends differ, numbered in ascending (v, dir).  With lo = v the owning
+ *   (lower-index) end and hi the far end: t = (iso - f_lo) / (f_hi - f_lo), a NaN t becomes 0.5, then t is clamped to
+ *   [0, 1]; p = p_lo + t * (p_hi - p_lo) per axis, clamped to [p_lo, p_hi]: finite and on the edge for any input bits.
+ * Triangles: a tetrahedron with 1 or 3 inside vertices gives one, with 2 inside two; the right-hand normal points to
+ *   the outside (towards lower values).  Order: ascending cell (flat index of its lowest corner), then the permutations
+ *   in lexicographic order xyz, xzy, yxz, yzx, zxy, zyx, then within a tetrahedron with vertices q = 0..3 in the order
+ *   above: one vertex i alone on its side, the others j < k < l: (e_ij, e_ik, e_il); inside a < b, outside c < d:
+ *   (e_ac, e_ad, e_bd) then (e_ac, e_bd, e_bc); in both cases the last two entries swap when the orientation asks for it.
+ *
+ * The workspace-size call returns the bytes the other two need (5 per grid point + 8 per 1024 points), or 0 with a
+ * message for dimensions outside the limits: every dimension >= 2 (else RSN_ERR_INVALID_ARGUMENT from the other two)
+ * and nx*ny*nz <= 2^27 (else RSN_ERR_UNSUPPORTED), so that 8*v + dir and 12 triangles per cell fit an int32.
+ * The count call classifies, scans and leaves in `workspace` (4-byte aligned) what the emit call needs for the same
+ * vol and iso; counts (device, [2]) receives the numbers of vertices and triangles.
+ * The emit call writes positions [V,3], vert_key [V] = 8*v + dir (or NULL) and triangles [T,3] (vertex ids), but only
+ * vertices < max_vertices and triangles < max_triangles: never a byte past either capacity; an output with capacity 0
+ * may be NULL, and with both capacities 0 nothing is launched.  origin3 / spacing3 are HOST arrays (spacing > 0). */
+size_t rsn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int rsn_mesh_count(int32_t nx, int32_t ny, int32_t nz, const float* vol, float iso, void* workspace, size_t workspace_bytes,
+                   int32_t* counts, void* stream);
+int rsn_mesh_emit(int32_t nx, int32_t ny, int32_t nz, const float* vol, float iso, const float* origin3,
+                  const float* spacing3, const void* workspace, size_t workspace_bytes, int32_t max_vertices,
+                  int32_t max_triangles, float* positions, int32_t* vert_key, int32_t* triangles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,10 @@ _SIGNATURES = {
                                         C.c_void_p]),
     "rsn_ssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rsn_ssim": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "rsn_mesh_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rsn_mesh_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rsn_mesh_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

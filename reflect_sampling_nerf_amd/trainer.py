@@ -2,6 +2,7 @@
 
     python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR]
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
+    python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
 
 `train` is the reference's `ns-train reflect-sampling-nerf --data DIR` loop on this package's own pieces: the reference
 Model config (ReflectSamplingNeRFModelConfig defaults), RayDataManager batches (1024 rays, reflect_sampling_nerf_config.py:36-41),
@@ -18,6 +19,10 @@ would.  With --deterministic the continuation has the uninterrupted run's bits; 
 pass and loss do, and later steps differ as two uninterrupted default runs differ (the order of the weight-gradient atomics).  A
 checkpoint without `rsn_run` (the reference's ns-train, or an older trainer) continues with the arguments given and a fresh jitter
 stream.  Multi-GPU training is not offered here.
+
+`export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
+the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
+(mesh.py).  The default level, sigma = 10, is a starting point that has not been measured against a scene.
 """
 from __future__ import annotations
 
@@ -72,6 +77,16 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ev.add_argument("--out", default="metrics.json", help="output JSON")
     ev.add_argument("--save-images", default=None, help="directory for rendered ground truth | coarse | fine panels")
     ev.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    ex = sub.add_parser("export-mesh", help="write the iso-surface of a checkpoint's density as a coloured triangle mesh (PLY)")
+    ex.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
+    ex.add_argument("--out", required=True, help="output file (binary little-endian PLY)")
+    ex.add_argument("--resolution", type=int, default=256, help="grid vertices per axis (default 256)")
+    ex.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="box the grid spans (default -1.5 -1.5 -1.5 1.5 1.5 1.5, nerfstudio's Blender scene box)")
+    ex.add_argument("--iso", type=float, default=None, metavar="S",
+                    help="density level of the surface (default 10: a starting point, not measured against any scene; pick it per scene)")
+    ex.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels (default f32)")
+    ex.add_argument("--chunk", type=int, default=None, help="points per field launch (default 262144)")
     return ap
 
 
@@ -346,6 +361,18 @@ def main(argv=None) -> int:
         print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}")
         train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
               log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume)
+        return 0
+    if args.command == "export-mesh":
+        from . import mesh
+
+        res = mesh.export_mesh(args.ckpt, args.out, resolution=args.resolution,
+                               bounds=mesh.DEFAULT_BOUNDS if args.bounds is None else tuple(args.bounds),
+                               iso=mesh.DEFAULT_ISO if args.iso is None else args.iso, mma=args.mma,
+                               chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
+        sec = res["seconds"]
+        print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles at sigma = "
+              f"{res['iso']:g} on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
+              " ".join(f"{k} {sec[k]:.3f} s" for k in ("grid", "count", "emit", "attributes", "write")) + f" -> {res['out']}")
         return 0
     scene = load_blender_split(args.data, args.split, args.scale_factor)
     res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images)
