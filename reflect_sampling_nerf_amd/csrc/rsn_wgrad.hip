@@ -680,14 +680,17 @@ __global__ __launch_bounds__(256) void rsn_wgrad_reduce_kernel(const WGradJobs J
   if (live) *dst += sum;  // no live slot: dW / db stay bit for bit what they were
 }
 
+// ---------------------------------------------------------------------------------------------------------------- host side
+static int wgrad_nkb(int k_in) { return k_in > 128 ? 8 : (k_in > 64 ? 4 : 2); }  // NKB of the kernel that serves k_in columns
+static int wgrad_pairs(int n_out) { return n_out <= 64 ? 1 : (n_out <= 128 ? 2 : 4); }  // P of the kernels: pairs of 32-row output blocks
+
 // workgroups of one launch: a function of the upper-bound segment lengths, the shape, the mode and the CU count
 static long long wgrad_grid(const long long* seg_begin, int n_seg, int n_out, int k_in, int n_jobs, bool bf16, int mode) {
   const int cached_cus = rsn_device_cus();
   // grid: every workgroup pays one atomic flush of the output tile (chip-wide ~1.3 TB/s of added bytes) and the
   // waves share the stages; T(G) = stages / (G * nsub) * t_stage + G * t_flush is smallest at G = sqrt(...)
-  const int nkb = k_in > 128 ? 8 : (k_in > 64 ? 4 : 2);
-  const int P = n_out <= 64 ? 1 : (n_out <= 128 ? 2 : 4);
-  const int nsub = 4 / P;
+  const int nkb = wgrad_nkb(k_in);
+  const int nsub = 4 / wgrad_pairs(n_out);
   long long stages = 0;
   const int stage_pts = bf16 ? 16 : 2 * WG_PAIRS;
   for (int s = 0; s < n_seg; ++s) {
@@ -704,41 +707,125 @@ static long long wgrad_grid(const long long* seg_begin, int n_seg, int n_out, in
 }
 
 static size_t wgrad_ws_bytes(long long grid, int k_in) {
-  const int nkb = k_in > 128 ? 8 : (k_in > 64 ? 4 : 2);
-  return (size_t)grid * 4 * (WG_SLOT_HEAD + 2 * nkb * 1024) * sizeof(float);
+  return (size_t)grid * 4 * (WG_SLOT_HEAD + 2 * wgrad_nkb(k_in) * 1024) * sizeof(float);
+}
+
+// The argument checks, each stated once: false with rsn_last_error() set.  An entry point calls them in its own order and returns
+// its own failure value (WG_CHECK: the error code; rsn_weight_grad_workspace_bytes: 0).  `also`: what the caller requires besides
+// the range (a pointer that goes with the count), reported with the same message.
+#define WG_OK(cond, ...) ((cond) || (rsn_set_error(__VA_ARGS__), false))
+static bool wgrad_mode_ok(int mode) { return WG_OK(mode >= RSN_MMA_F32 && mode <= RSN_MMA_BF16, "mma_mode %d", mode); }
+static bool wgrad_operand_bf16_ok(int op) { return WG_OK(op >= 0 && op <= 3, "operand_bf16 %d", op); }
+static bool wgrad_n_jobs_ok(int n_jobs, bool also = true) {
+  return WG_OK(n_jobs >= 1 && n_jobs <= WG_MAX_JOBS && also, "n_jobs=%d (1..%d)", n_jobs, WG_MAX_JOBS);
+}
+static bool wgrad_n_segments_ok(int n_segments, bool also = true) {
+  return WG_OK(n_segments >= 0 && n_segments <= WG_MAX_SEG && also, "n_segments=%d (at most %d)", n_segments, WG_MAX_SEG);
+}
+static bool wgrad_shape_ok(int n_out, int k_in) {
+  return WG_OK(n_out >= 1 && n_out <= 256 && k_in >= 1 && k_in <= 256, "n_out=%d k_in=%d (outputs up to 256 x 256)", n_out, k_in);
+}
+#undef WG_OK
+#define WG_CHECK(ok)                            \
+  do {                                          \
+    if (!(ok)) return RSN_ERR_INVALID_ARGUMENT; \
+  } while (0)
+
+// The one segment-table builder: a's segments = the non-empty ones of (n_points_max, n_dev, per_count) with the rows of job q.
+// q == nullptr: the lengths alone (the workspace bound).  job < 0: the message texts of the flat entry points, else the job's index.
+static int wgrad_fill_segments(WGradArgs& a, int n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                               const int32_t* per_count, const rsn_wgrad_job* q, int job) {
+  a.seg_begin[0] = 0;
+  int ns = 0;
+  for (int s = 0; s < n_segments; ++s) {
+    RSN_REQUIRE(n_points_max[s] >= 0, RSN_ERR_INVALID_ARGUMENT, job < 0 ? "n_points[%d]=%lld" : "n_points_max[%d]=%lld", s,
+                (long long)n_points_max[s]);
+    if (n_points_max[s] == 0) continue;
+    a.seg_begin[ns + 1] = a.seg_begin[ns] + n_points_max[s];
+    if (q) {
+      if (job < 0)
+        RSN_REQUIRE(q->dy[s] && q->x[s], RSN_ERR_INVALID_ARGUMENT, "segment %d: a pointer is NULL", s);
+      else
+        RSN_REQUIRE(q->dy[s] && q->x[s], RSN_ERR_INVALID_ARGUMENT, "job %d segment %d: a pointer is NULL", job, s);
+      a.dy[ns] = q->dy[s];
+      a.x[ns] = q->x[s];
+      a.n_dev[ns] = n_dev ? n_dev[s] : nullptr;
+      a.per_count[ns] = (n_dev && n_dev[s] && per_count) ? per_count[s] : 1;
+      RSN_REQUIRE(a.per_count[ns] >= 1, RSN_ERR_INVALID_ARGUMENT, "segment %d: per_count=%d", s, a.per_count[ns]);
+    }
+    ++ns;
+  }
+  a.n_seg = ns;
+  if (q) {
+    a.ld_dw = q->ld_dw; a.col_map = q->col_map; a.dw = q->dw; a.db = q->db;
+  }
+  return RSN_OK;
 }
 
 extern "C" size_t rsn_weight_grad_workspace_bytes(int32_t n_segments, const int64_t* n_points_max, int32_t n_jobs,
                                                   int32_t n_out, int32_t k_in, int32_t mma_mode, int32_t operand_bf16) {
-  RSN_REQUIRE(n_segments >= 0 && n_segments <= WG_MAX_SEG && (n_segments == 0 || n_points_max), 0, "n_segments=%d (at most %d)",
-              n_segments, WG_MAX_SEG);
-  RSN_REQUIRE(n_jobs >= 1 && n_jobs <= WG_MAX_JOBS, 0, "n_jobs=%d (1..%d)", n_jobs, WG_MAX_JOBS);
-  RSN_REQUIRE(n_out >= 1 && n_out <= 256 && k_in >= 1 && k_in <= 256, 0, "n_out=%d k_in=%d (outputs up to 256 x 256)", n_out, k_in);
-  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, 0, "mma_mode %d", mma_mode);
-  RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, 0, "operand_bf16 %d", operand_bf16);
-  long long seg_begin[WG_MAX_SEG + 1] = {0};
-  for (int s = 0; s < n_segments; ++s) {
-    RSN_REQUIRE(n_points_max[s] >= 0, 0, "n_points_max[%d]=%lld", s, (long long)n_points_max[s]);
-    seg_begin[s + 1] = seg_begin[s] + n_points_max[s];
-  }
+  if (!wgrad_n_segments_ok(n_segments, n_segments == 0 || n_points_max) || !wgrad_n_jobs_ok(n_jobs) || !wgrad_shape_ok(n_out, k_in) ||
+      !wgrad_mode_ok(mma_mode) || !wgrad_operand_bf16_ok(operand_bf16))
+    return 0;
+  WGradArgs a = {};
+  if (wgrad_fill_segments(a, n_segments, n_points_max, nullptr, nullptr, nullptr, 0) != RSN_OK) return 0;
   // a launch in a bf16 mode takes the exact kernel's grid when the rows do not fit the vector-load layout (alignment: known
   // at the launch only): the larger of the two
-  long long grid = wgrad_grid(seg_begin, n_segments, n_out, k_in, n_jobs, false, mma_mode);
+  long long grid = wgrad_grid(a.seg_begin, a.n_seg, n_out, k_in, n_jobs, false, mma_mode);
   if (mma_mode == RSN_MMA_BF16 || mma_mode == RSN_MMA_BF16X6) {
-    const long long gb = wgrad_grid(seg_begin, n_segments, n_out, k_in, n_jobs, true, mma_mode);
+    const long long gb = wgrad_grid(a.seg_begin, a.n_seg, n_out, k_in, n_jobs, true, mma_mode);
     grid = gb > grid ? gb : grid;
   }
   return wgrad_ws_bytes(grid, k_in);
 }
 
-static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf16 = 0, bool ordered = false, void* ws = nullptr,
-                        size_t ws_bytes = 0) {
+// How a call wants its reduction done: what the entry points differ in behind the segments and the jobs.
+struct WGradCall {
+  int mode;          // RSN_MMA_*
+  int operand_bf16;  // bit 0: the X rows, bit 1: the dY rows ARE bf16 in memory
+  bool ordered;      // the ordered flush into `ws` and the reducer behind it, instead of the atomic flush
+  void* ws;
+  size_t ws_bytes;
+};
+
+// The kernel variant as a value: rsn_wgrad_kernel's template arguments behind NKB (and in front of ORD).
+struct WGradVariant {
+  bool xv, dv;
+  int bf;
+  bool xb, db;
+};
+typedef void (*wgrad_kernel_t)(const WGradJobs);
+
+template <int NKB, bool ORD, bool XV, bool DV, int BF, bool XB, bool DB>
+static bool wgrad_is(const WGradVariant& v, wgrad_kernel_t* k) {
+  if (v.xv != XV || v.dv != DV || v.bf != BF || v.xb != XB || v.db != DB) return false;
+  *k = rsn_wgrad_kernel<NKB, XV, DV, BF, XB, DB, ORD>;
+  return true;
+}
+// the variants that exist (every one named here is compiled, for three NKB and both flushes); nullptr for any other value
+template <int NKB, bool ORD>
+static wgrad_kernel_t wgrad_kernel_of(const WGradVariant& v) {
+  wgrad_kernel_t k = nullptr;
+  (void)(wgrad_is<NKB, ORD, true, true, 3, false, false>(v, &k) ||     // split bf16
+         wgrad_is<NKB, ORD, true, true, 1, true, true>(v, &k) ||       // plain bf16: bf16 X and dY rows
+         wgrad_is<NKB, ORD, true, true, 1, false, true>(v, &k) ||      //             bf16 dY rows
+         wgrad_is<NKB, ORD, true, false, 1, true, false>(v, &k) ||     //             bf16 X rows, <= 32 outputs
+         wgrad_is<NKB, ORD, true, true, 1, false, false>(v, &k) ||     //             fp32 rows
+         wgrad_is<NKB, ORD, true, true, 0, false, false>(v, &k) ||     // exact fp32: vector loads of X and dY
+         wgrad_is<NKB, ORD, true, false, 0, false, false>(v, &k) ||    //             vector loads of X
+         wgrad_is<NKB, ORD, false, false, 0, false, false>(v, &k));    //             scalar loads
+  return k;
+}
+template <bool ORD>
+static wgrad_kernel_t wgrad_kernel_of(int nkb, const WGradVariant& v) {
+  return nkb == 8 ? wgrad_kernel_of<8, ORD>(v) : (nkb == 4 ? wgrad_kernel_of<4, ORD>(v) : wgrad_kernel_of<2, ORD>(v));
+}
+
+static int wgrad_launch(WGradJobs& J, const WGradCall& c, void* stream) {
   WGradArgs& a = J.j[0];  // the jobs of a launch share shape, leading dimensions and segment lengths (checked by the caller)
-  const bool xb = (operand_bf16 & 1) != 0, db = (operand_bf16 & 2) != 0;  // rows that ARE bf16 in memory
-  bool bf16 = mode == RSN_MMA_BF16 || mode == RSN_MMA_BF16X6;
-  const long long total = a.seg_begin[a.n_seg];
-  if (total == 0) return RSN_OK;
-  const int nkb = a.k_in > 128 ? 8 : (a.k_in > 64 ? 4 : 2);
+  const bool xb = (c.operand_bf16 & 1) != 0, db = (c.operand_bf16 & 2) != 0;  // rows that ARE bf16 in memory
+  if (a.seg_begin[a.n_seg] == 0) return RSN_OK;  // no points
+  const int nkb = wgrad_nkb(a.k_in);
   // vector-load variants need whole NKB-column groups and aligned rows; anything else takes the scalar-load path
   bool xv = a.k_in % nkb == 0 && a.ld_x % (xb ? nkb : (nkb >= 4 ? 4 : 2)) == 0;
   bool dv = a.n_out > 32 && a.ld_dy % 2 == 0 && a.ld_dy >= a.n_out + (a.n_out & 1);
@@ -748,158 +835,63 @@ static int wgrad_launch(WGradJobs& J, void* stream, int mode = 0, int operand_bf
       dv = dv && ((uintptr_t)J.j[jb].dy[s] % (db ? 4 : 8) == 0);
     }
   if (xb || db) {  // no other kernel can read bf16 rows: the layout must fit, loudly
-    RSN_REQUIRE(mode == RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "bf16 operand rows need mma_mode RSN_MMA_BF16");
+    RSN_REQUIRE(c.mode == RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "bf16 operand rows need mma_mode RSN_MMA_BF16");
     RSN_REQUIRE(xv && (!db || dv), RSN_ERR_UNSUPPORTED,
                 "bf16 operand rows: k_in=%d ld_x=%d n_out=%d ld_dy=%d / alignment do not fit the vector-load layout",
                 a.k_in, a.ld_x, a.n_out, a.ld_dy);
   }
-  bf16 = bf16 && xv && (dv || (xb && !db));  // the bf16 variants exist for the vector-load layout only
-  const long long grid = wgrad_grid(a.seg_begin, a.n_seg, a.n_out, a.k_in, J.n_jobs, bf16, mode);
-  if (ordered) {
+  // the bf16 variants exist for the vector-load layout only
+  const bool bf16 = (c.mode == RSN_MMA_BF16 || c.mode == RSN_MMA_BF16X6) && xv && (dv || (xb && !db));
+  const long long grid = wgrad_grid(a.seg_begin, a.n_seg, a.n_out, a.k_in, J.n_jobs, bf16, c.mode);
+  if (c.ordered) {
     const size_t need = wgrad_ws_bytes(grid, a.k_in);
-    RSN_REQUIRE(ws && (uintptr_t)ws % 16 == 0, RSN_ERR_INVALID_ARGUMENT, "workspace is NULL or not 16-byte aligned");
-    RSN_REQUIRE(ws_bytes >= need, RSN_ERR_INVALID_ARGUMENT, "workspace_bytes=%zu: the ordered reduction needs %zu bytes", ws_bytes,
+    RSN_REQUIRE(c.ws && (uintptr_t)c.ws % 16 == 0, RSN_ERR_INVALID_ARGUMENT, "workspace is NULL or not 16-byte aligned");
+    RSN_REQUIRE(c.ws_bytes >= need, RSN_ERR_INVALID_ARGUMENT, "workspace_bytes=%zu: the ordered reduction needs %zu bytes", c.ws_bytes,
                 need);
-    J.ws = static_cast<float*>(ws);
+    J.ws = static_cast<float*>(c.ws);
   }
+  // exact fp32 (bf16 rows were refused above unless a bf16 variant serves them): DV only beside XV
+  WGradVariant v = {xv, xv && dv, 0, false, false};
+  if (bf16) v = {true, dv, c.mode == RSN_MMA_BF16X6 ? 3 : 1, xb, db};
+  RSN_REQUIRE(!(v.xb && !v.db && v.dv), RSN_ERR_UNSUPPORTED, "bf16 X rows with fp32 dY rows wider than 32 outputs");
+  const wgrad_kernel_t kernel = c.ordered ? wgrad_kernel_of<true>(nkb, v) : wgrad_kernel_of<false>(nkb, v);
+  RSN_REQUIRE(kernel, RSN_ERR_UNSUPPORTED, "no weight-gradient kernel for xv=%d dv=%d bf=%d xb=%d db=%d", v.xv, v.dv, v.bf, v.xb, v.db);
   hipStream_t st = (hipStream_t)stream;
-#define RSN_WG(NKBV, ORDV)                                                                                           \
-  do {                                                                                                         \
-    if (xv && dv && bf16 && mode == RSN_MMA_BF16X6)                                                            \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 3, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);  \
-    else if (bf16 && xb && db)                                                                                 \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, true, true, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J); \
-    else if (bf16 && db)                                                                                       \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, false, true, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J); \
-    else if (bf16 && xb && !dv)                                                                                \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, false, 1, true, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J); \
-    else if (bf16 && xb)                                                                                       \
-      { RSN_REQUIRE(false, RSN_ERR_UNSUPPORTED, "bf16 X rows with fp32 dY rows wider than 32 outputs"); }      \
-    else if (xv && dv && bf16)                                                                                 \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 1, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);  \
-    else if (xv && dv)                                                                                         \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, true, 0, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);     \
-    else if (xv)                                                                                               \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, true, false, 0, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);    \
-    else                                                                                                       \
-      hipLaunchKernelGGL((rsn_wgrad_kernel<NKBV, false, false, 0, false, false, ORDV>), dim3((unsigned)grid), dim3(256), 0, st, J);   \
-  } while (0)
-  if (ordered) {
-    if (nkb == 8)
-      RSN_WG(8, true);
-    else if (nkb == 4)
-      RSN_WG(4, true);
-    else
-      RSN_WG(2, true);
-  } else if (nkb == 8)
-    RSN_WG(8, false);
-  else if (nkb == 4)
-    RSN_WG(4, false);
-  else
-    RSN_WG(2, false);
-#undef RSN_WG
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, J);
   RSN_HIP(hipGetLastError());
-  if (ordered) {
-    const int P = a.n_out <= 64 ? 1 : (a.n_out <= 128 ? 2 : 4);
-    hipLaunchKernelGGL(rsn_wgrad_reduce_kernel, dim3((unsigned)(J.n_jobs * (P * nkb * 8 + 1))), dim3(256), 0, st, J,
-                       (int)(grid / J.n_jobs), nkb, (int)xv, (int)(xv && dv));  // the kernels above: DV only beside XV
+  if (c.ordered) {
+    hipLaunchKernelGGL(rsn_wgrad_reduce_kernel, dim3((unsigned)(J.n_jobs * (wgrad_pairs(a.n_out) * nkb * 8 + 1))), dim3(256), 0, st, J,
+                       (int)(grid / J.n_jobs), nkb, (int)v.xv, (int)v.dv);
     RSN_HIP(hipGetLastError());
   }
   return RSN_OK;
 }
 
-static int weight_grad_multi_impl(int32_t n_segments, const int64_t* n_points, const float* const* dy, int32_t ld_dy,
-                                  int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
-                                  const int32_t* col_map, float* dw, int32_t ld_dw, float* db, void* stream, int mode,
-                                  const int32_t* const* n_dev = nullptr, const int32_t* per_count = nullptr,
-                                  int operand_bf16 = 0, bool ordered = false, void* ws = nullptr, size_t ws_bytes = 0);
-
-extern "C" int rsn_weight_grad_multi(int32_t n_segments, const int64_t* n_points, const float* const* dy, int32_t ld_dy,
-                                     int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
-                                     const int32_t* col_map, float* dw, int32_t ld_dw, float* db, void* stream) {
-  return weight_grad_multi_impl(n_segments, n_points, dy, ld_dy, n_out, x, ld_x, k_in, col_map, dw, ld_dw, db, stream, RSN_MMA_F32);
-}
-
-static int weight_grad_multi_impl(int32_t n_segments, const int64_t* n_points, const float* const* dy, int32_t ld_dy,
-                                  int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
-                                  const int32_t* col_map, float* dw, int32_t ld_dw, float* db, void* stream, int mode,
-                                  const int32_t* const* n_dev, const int32_t* per_count, int operand_bf16, bool ordered, void* ws,
-                                  size_t ws_bytes) {
-  RSN_REQUIRE(n_segments >= 0 && n_segments <= WG_MAX_SEG, RSN_ERR_INVALID_ARGUMENT, "n_segments=%d (at most %d)",
-              n_segments, WG_MAX_SEG);
-  RSN_REQUIRE(n_out >= 1 && n_out <= 256 && k_in >= 1 && k_in <= 256, RSN_ERR_INVALID_ARGUMENT,
-              "n_out=%d k_in=%d (outputs up to 256 x 256)", n_out, k_in);
-  RSN_REQUIRE(ld_dy >= n_out && ld_x >= k_in && ld_dw >= 1, RSN_ERR_INVALID_ARGUMENT, "leading dimensions too small");
+// the flat entry points: one job
+static int wgrad_one(int32_t n_segments, const int64_t* n_points, const int32_t* const* n_dev, const int32_t* per_count, int32_t ld_dy,
+                     int32_t n_out, int32_t ld_x, int32_t k_in, const rsn_wgrad_job& q, const WGradCall& c, void* stream) {
+  WG_CHECK(wgrad_n_segments_ok(n_segments));
+  WG_CHECK(wgrad_shape_ok(n_out, k_in));
+  RSN_REQUIRE(ld_dy >= n_out && ld_x >= k_in && q.ld_dw >= 1, RSN_ERR_INVALID_ARGUMENT, "leading dimensions too small");
   if (n_segments == 0) return RSN_OK;
-  RSN_REQUIRE(n_points && dy && x && dw, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
+  RSN_REQUIRE(n_points && q.dy && q.x && q.dw, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
   WGradJobs J = {};
   J.n_jobs = 1;
   WGradArgs& a = J.j[0];
-  a.seg_begin[0] = 0;
-  int ns = 0;
-  for (int s = 0; s < n_segments; ++s) {
-    RSN_REQUIRE(n_points[s] >= 0, RSN_ERR_INVALID_ARGUMENT, "n_points[%d]=%lld", s, (long long)n_points[s]);
-    if (n_points[s] == 0) continue;
-    RSN_REQUIRE(dy[s] && x[s], RSN_ERR_INVALID_ARGUMENT, "segment %d: a pointer is NULL", s);
-    a.dy[ns] = dy[s];
-    a.x[ns] = x[s];
-    a.seg_begin[ns + 1] = a.seg_begin[ns] + n_points[s];
-    a.n_dev[ns] = n_dev ? n_dev[s] : nullptr;
-    a.per_count[ns] = (n_dev && n_dev[s] && per_count) ? per_count[s] : 1;
-    RSN_REQUIRE(a.per_count[ns] >= 1, RSN_ERR_INVALID_ARGUMENT, "segment %d: per_count=%d", s, a.per_count[ns]);
-    ++ns;
-  }
-  a.n_seg = ns;
   a.ld_dy = ld_dy; a.ld_x = ld_x; a.n_out = n_out; a.k_in = k_in;
-  a.ld_dw = ld_dw; a.col_map = col_map; a.dw = dw; a.db = db;
-  return wgrad_launch(J, stream, mode, operand_bf16, ordered, ws, ws_bytes);
-}
-
-extern "C" int rsn_weight_grad_multi_mode(int32_t n_segments, const int64_t* n_points, const float* const* dy,
-                                          int32_t ld_dy, int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
-                                          const int32_t* col_map, float* dw, int32_t ld_dw, float* db, int32_t mma_mode,
-                                          void* stream) {
-  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode %d", mma_mode);
-  return weight_grad_multi_impl(n_segments, n_points, dy, ld_dy, n_out, x, ld_x, k_in, col_map, dw, ld_dw, db, stream,
-                                mma_mode);
-}
-
-extern "C" int rsn_weight_grad_multi_dev(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
-                                         const int32_t* per_count, const float* const* dy, int32_t ld_dy, int32_t n_out,
-                                         const float* const* x, int32_t ld_x, int32_t k_in, const int32_t* col_map,
-                                         float* dw, int32_t ld_dw, float* db, int32_t mma_mode, int32_t operand_bf16,
-                                         void* stream) {
-  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode %d", mma_mode);
-  RSN_REQUIRE(n_segments == 0 || (n_dev && per_count), RSN_ERR_INVALID_ARGUMENT, "n_dev / per_count is NULL");
-  RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, RSN_ERR_INVALID_ARGUMENT, "operand_bf16 %d", operand_bf16);
-  return weight_grad_multi_impl(n_segments, n_points_max, dy, ld_dy, n_out, x, ld_x, k_in, col_map, dw, ld_dw, db, stream,
-                                mma_mode, n_dev, per_count, operand_bf16);
-}
-
-extern "C" int rsn_weight_grad_multi_dev_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
-                                                 const int32_t* per_count, const float* const* dy, int32_t ld_dy,
-                                                 int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
-                                                 const int32_t* col_map, float* dw, int32_t ld_dw, float* db, int32_t mma_mode,
-                                                 int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
-  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode %d", mma_mode);
-  RSN_REQUIRE(n_segments == 0 || (n_dev && per_count), RSN_ERR_INVALID_ARGUMENT, "n_dev / per_count is NULL");
-  RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, RSN_ERR_INVALID_ARGUMENT, "operand_bf16 %d", operand_bf16);
-  return weight_grad_multi_impl(n_segments, n_points_max, dy, ld_dy, n_out, x, ld_x, k_in, col_map, dw, ld_dw, db, stream,
-                                mma_mode, n_dev, per_count, operand_bf16, true, workspace, workspace_bytes);
+  RSN_TRY(wgrad_fill_segments(a, n_segments, n_points, n_dev, per_count, &q, -1));
+  return wgrad_launch(J, c, stream);
 }
 
 // rsn_weight_grad_jobs: n_jobs reductions of one shape over the same segments in ONE launch (see WGradJobs).
-static int weight_grad_jobs_impl(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
-                                 const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
-                                 int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
-                                 void* stream, bool ordered, void* ws, size_t ws_bytes) {
-  RSN_REQUIRE(mma_mode >= RSN_MMA_F32 && mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode %d", mma_mode);
-  RSN_REQUIRE(operand_bf16 >= 0 && operand_bf16 <= 3, RSN_ERR_INVALID_ARGUMENT, "operand_bf16 %d", operand_bf16);
-  RSN_REQUIRE(n_jobs >= 1 && n_jobs <= WG_MAX_JOBS && jobs, RSN_ERR_INVALID_ARGUMENT, "n_jobs=%d (1..%d)", n_jobs, WG_MAX_JOBS);
-  RSN_REQUIRE(n_segments >= 0 && n_segments <= WG_MAX_SEG, RSN_ERR_INVALID_ARGUMENT, "n_segments=%d (at most %d)",
-              n_segments, WG_MAX_SEG);
-  RSN_REQUIRE(n_out >= 1 && n_out <= 256 && k_in >= 1 && k_in <= 256, RSN_ERR_INVALID_ARGUMENT,
-              "n_out=%d k_in=%d (outputs up to 256 x 256)", n_out, k_in);
+static int wgrad_jobs(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev, const int32_t* per_count,
+                      int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy, int32_t n_out, int32_t ld_x, int32_t k_in,
+                      const WGradCall& c, void* stream) {
+  WG_CHECK(wgrad_mode_ok(c.mode));
+  WG_CHECK(wgrad_operand_bf16_ok(c.operand_bf16));
+  WG_CHECK(wgrad_n_jobs_ok(n_jobs, jobs != nullptr));
+  WG_CHECK(wgrad_n_segments_ok(n_segments));
+  WG_CHECK(wgrad_shape_ok(n_out, k_in));
   RSN_REQUIRE(ld_dy >= n_out && ld_x >= k_in, RSN_ERR_INVALID_ARGUMENT, "leading dimensions too small");
   if (n_segments == 0) return RSN_OK;
   RSN_REQUIRE(n_points_max, RSN_ERR_INVALID_ARGUMENT, "n_points_max is NULL");
@@ -909,42 +901,72 @@ static int weight_grad_jobs_impl(int32_t n_segments, const int64_t* n_points_max
     const rsn_wgrad_job& q = jobs[jb];
     WGradArgs& a = J.j[jb];
     RSN_REQUIRE(q.dy && q.x && q.dw && q.ld_dw >= 1, RSN_ERR_INVALID_ARGUMENT, "job %d: a pointer is NULL / ld_dw=%d", jb, q.ld_dw);
-    a.seg_begin[0] = 0;
-    int ns = 0;
-    for (int s = 0; s < n_segments; ++s) {
-      RSN_REQUIRE(n_points_max[s] >= 0, RSN_ERR_INVALID_ARGUMENT, "n_points_max[%d]=%lld", s, (long long)n_points_max[s]);
-      if (n_points_max[s] == 0) continue;
-      RSN_REQUIRE(q.dy[s] && q.x[s], RSN_ERR_INVALID_ARGUMENT, "job %d segment %d: a pointer is NULL", jb, s);
-      a.dy[ns] = q.dy[s];
-      a.x[ns] = q.x[s];
-      a.seg_begin[ns + 1] = a.seg_begin[ns] + n_points_max[s];
-      a.n_dev[ns] = n_dev ? n_dev[s] : nullptr;
-      a.per_count[ns] = (n_dev && n_dev[s] && per_count) ? per_count[s] : 1;
-      RSN_REQUIRE(a.per_count[ns] >= 1, RSN_ERR_INVALID_ARGUMENT, "segment %d: per_count=%d", s, a.per_count[ns]);
-      ++ns;
-    }
-    a.n_seg = ns;
     a.ld_dy = ld_dy; a.ld_x = ld_x; a.n_out = n_out; a.k_in = k_in;
-    a.ld_dw = q.ld_dw; a.col_map = q.col_map; a.dw = q.dw; a.db = q.db;
+    RSN_TRY(wgrad_fill_segments(a, n_segments, n_points_max, n_dev, per_count, &q, jb));
   }
-  if (J.j[0].n_seg == 0) return RSN_OK;
-  return wgrad_launch(J, stream, mma_mode, operand_bf16, ordered, ws, ws_bytes);
+  return wgrad_launch(J, c, stream);
+}
+
+extern "C" int rsn_weight_grad_multi(int32_t n_segments, const int64_t* n_points, const float* const* dy, int32_t ld_dy,
+                                     int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
+                                     const int32_t* col_map, float* dw, int32_t ld_dw, float* db, void* stream) {
+  const rsn_wgrad_job q = {dy, x, col_map, dw, ld_dw, db};
+  return wgrad_one(n_segments, n_points, nullptr, nullptr, ld_dy, n_out, ld_x, k_in, q, {RSN_MMA_F32, 0, false, nullptr, 0}, stream);
+}
+
+extern "C" int rsn_weight_grad_multi_mode(int32_t n_segments, const int64_t* n_points, const float* const* dy,
+                                          int32_t ld_dy, int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
+                                          const int32_t* col_map, float* dw, int32_t ld_dw, float* db, int32_t mma_mode,
+                                          void* stream) {
+  WG_CHECK(wgrad_mode_ok(mma_mode));
+  const rsn_wgrad_job q = {dy, x, col_map, dw, ld_dw, db};
+  return wgrad_one(n_segments, n_points, nullptr, nullptr, ld_dy, n_out, ld_x, k_in, q, {mma_mode, 0, false, nullptr, 0}, stream);
+}
+
+// rsn_weight_grad_multi_dev and its ordered twin
+static int wgrad_one_dev(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev, const int32_t* per_count,
+                         int32_t ld_dy, int32_t n_out, int32_t ld_x, int32_t k_in, const rsn_wgrad_job& q, const WGradCall& c,
+                         void* stream) {
+  WG_CHECK(wgrad_mode_ok(c.mode));
+  RSN_REQUIRE(n_segments == 0 || (n_dev && per_count), RSN_ERR_INVALID_ARGUMENT, "n_dev / per_count is NULL");
+  WG_CHECK(wgrad_operand_bf16_ok(c.operand_bf16));
+  return wgrad_one(n_segments, n_points_max, n_dev, per_count, ld_dy, n_out, ld_x, k_in, q, c, stream);
+}
+
+extern "C" int rsn_weight_grad_multi_dev(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                         const int32_t* per_count, const float* const* dy, int32_t ld_dy, int32_t n_out,
+                                         const float* const* x, int32_t ld_x, int32_t k_in, const int32_t* col_map,
+                                         float* dw, int32_t ld_dw, float* db, int32_t mma_mode, int32_t operand_bf16,
+                                         void* stream) {
+  const rsn_wgrad_job q = {dy, x, col_map, dw, ld_dw, db};
+  return wgrad_one_dev(n_segments, n_points_max, n_dev, per_count, ld_dy, n_out, ld_x, k_in, q,
+                       {mma_mode, operand_bf16, false, nullptr, 0}, stream);
+}
+
+extern "C" int rsn_weight_grad_multi_dev_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
+                                                 const int32_t* per_count, const float* const* dy, int32_t ld_dy,
+                                                 int32_t n_out, const float* const* x, int32_t ld_x, int32_t k_in,
+                                                 const int32_t* col_map, float* dw, int32_t ld_dw, float* db, int32_t mma_mode,
+                                                 int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
+  const rsn_wgrad_job q = {dy, x, col_map, dw, ld_dw, db};
+  return wgrad_one_dev(n_segments, n_points_max, n_dev, per_count, ld_dy, n_out, ld_x, k_in, q,
+                       {mma_mode, operand_bf16, true, workspace, workspace_bytes}, stream);
 }
 
 extern "C" int rsn_weight_grad_jobs(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
                                     const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
                                     int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
                                     void* stream) {
-  return weight_grad_jobs_impl(n_segments, n_points_max, n_dev, per_count, n_jobs, jobs, ld_dy, n_out, ld_x, k_in, mma_mode,
-                               operand_bf16, stream, false, nullptr, 0);
+  return wgrad_jobs(n_segments, n_points_max, n_dev, per_count, n_jobs, jobs, ld_dy, n_out, ld_x, k_in,
+                    {mma_mode, operand_bf16, false, nullptr, 0}, stream);
 }
 
 extern "C" int rsn_weight_grad_jobs_ordered(int32_t n_segments, const int64_t* n_points_max, const int32_t* const* n_dev,
                                             const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy,
                                             int32_t n_out, int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16,
                                             void* workspace, size_t workspace_bytes, void* stream) {
-  return weight_grad_jobs_impl(n_segments, n_points_max, n_dev, per_count, n_jobs, jobs, ld_dy, n_out, ld_x, k_in, mma_mode,
-                               operand_bf16, stream, true, workspace, workspace_bytes);
+  return wgrad_jobs(n_segments, n_points_max, n_dev, per_count, n_jobs, jobs, ld_dy, n_out, ld_x, k_in,
+                    {mma_mode, operand_bf16, true, workspace, workspace_bytes}, stream);
 }
 
 extern "C" int rsn_weight_grad(int64_t n_points, const float* dy, int32_t ld_dy, int32_t n_out, const float* x,

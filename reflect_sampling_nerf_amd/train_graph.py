@@ -136,16 +136,16 @@ def _wgrad(dy: Tensor, n_out: int, x: Tensor, k_in: int, dw: Tensor, dw_col0: in
     _wgrad_multi([(dy, x)], n_out, k_in, dw, dw_col0, db, col_map)
 
 
-_WGRAD_MODE = 0  # RSN_MMA_*: set per step by _weight_grads from the Field's MMA mode
+_WGRAD_MODE = 0  # RSN_MMA_*: the mode of a _wgrad_multi / _wgrad_jobs call that names none (tests and tools set it)
 _WGRAD_JOBS_MAX = 8  # WG_MAX_JOBS of rsn_wgrad.hip
-_WGRAD_ORDERED = False  # set per step by _weight_grads (Model.deterministic): the ordered entry points, bit-reproducible sums
+_WGRAD_ORDERED = False  # likewise: the ordered entry points (bit-reproducible sums) for a call that does not say
 _WGRAD_WS: Dict[torch.device, Tensor] = {}  # the ordered reductions' workspace, one per device, grown on demand
 
 
-def _wgrad_workspace(lib, dev, ns: int, npts, n_jobs: int, n_out: int, k_in: int, operand_bf16: int) -> Tensor:
+def _wgrad_workspace(lib, dev, ns: int, npts, n_jobs: int, n_out: int, k_in: int, operand_bf16: int, mode: int) -> Tensor:
     """Workspace of one ordered weight-gradient launch (rsn_weight_grad_workspace_bytes: a host-side upper bound).  One tensor per
     device serves every launch: they run on one stream, each launch's reducer has read the slots before the next launch writes them."""
-    need = int(lib.rsn_weight_grad_workspace_bytes(ns, npts, n_jobs, n_out, k_in, _WGRAD_MODE, operand_bf16))
+    need = int(lib.rsn_weight_grad_workspace_bytes(ns, npts, n_jobs, n_out, k_in, mode, operand_bf16))
     if need == 0:
         check(-1)  # bad arguments: the library's message
     ws = _WGRAD_WS.get(dev)
@@ -155,90 +155,84 @@ def _wgrad_workspace(lib, dev, ns: int, npts, n_jobs: int, n_out: int, k_in: int
     return ws
 
 
+class _WGradSegs:
+    """What a weight-gradient call says about its segments = [(dy, x[, (device count, rows per count)])], the same for every job
+    of the call: the segments with rows (`keep`: their indices), the ctypes arrays of their lengths and device counts, the leading
+    dimensions, which rows are bf16 in memory (reduced-precision training: all segments alike) and the timer's work record."""
+
+    def __init__(self, segs, n_jobs: int, n_out: int, k_in: int):
+        self.keep = [i for i, sg in enumerate(segs) if sg[0].shape[0] > 0]
+        if not self.keep:
+            return
+        self.ref = ref = [segs[i] for i in self.keep]
+        self.ns = ns = len(ref)
+        self.ld_dy, self.ld_x = ref[0][0].stride(0), ref[0][1].stride(0)
+        bf = torch.bfloat16
+        assert all((sg[0].dtype == bf) == (ref[0][0].dtype == bf) and (sg[1].dtype == bf) == (ref[0][1].dtype == bf) for sg in ref)
+        self.operand_bf16 = (1 if ref[0][1].dtype == bf else 0) | (2 if ref[0][0].dtype == bf else 0)
+        self.npts = (C.c_int64 * ns)(*[sg[0].shape[0] for sg in ref])
+        cnt = [sg[2] if len(sg) > 2 else None for sg in ref]
+        self.ndev = (C.c_void_p * ns)(*[None if c is None else c[0].data_ptr() for c in cnt])
+        self.per = (C.c_int32 * ns)(*[1 if c is None else int(c[1]) for c in cnt])
+        self.work = {"point_out_in": n_jobs * sum(sg[0].shape[0] for sg, c in zip(ref, cnt) if c is None) * n_out * k_in}
+        dev_work = [(c[0], n_jobs * c[1] * n_out * k_in) for c in cnt if c is not None]
+        if dev_work:
+            self.work["point_out_in_dev"] = dev_work
+
+    def rows(self, segs):
+        """The (dy, x) pointer arrays of one job's kept segments, which must have the shape of the call's."""
+        sel = [segs[i] for i in self.keep]
+        assert all(a[0].shape[0] == a[1].shape[0] == b[0].shape[0] and a[0].stride(0) == self.ld_dy and a[1].stride(0) == self.ld_x and
+                   a[0].dtype == b[0].dtype and a[1].dtype == b[1].dtype for a, b in zip(sel, self.ref))
+        return ((C.c_void_p * self.ns)(*[sg[0].data_ptr() for sg in sel]), (C.c_void_p * self.ns)(*[sg[1].data_ptr() for sg in sel]))
+
+
+def _wgrad_launch(entry: str, head, sg: _WGradSegs, dev, n_jobs: int, n_out: int, k_in: int, mode, ordered):
+    """The call itself: lib.<entry>(*head, mode, operand_bf16, stream), or <entry>_ordered with the workspace in front of the stream.
+    mode / ordered None: the module's _WGRAD_MODE / _WGRAD_ORDERED.  `head` (its ctypes arrays) lives until the call has returned."""
+    lib = _abi.load_library()
+    tail = (int(_WGRAD_MODE if mode is None else mode), sg.operand_bf16)
+    if _WGRAD_ORDERED if ordered is None else ordered:
+        ws = _wgrad_workspace(lib, dev, sg.ns, sg.npts, n_jobs, n_out, k_in, sg.operand_bf16, tail[0])
+        entry, tail = entry + "_ordered", tail + (ptr(ws), ws.numel())
+    fn = getattr(lib, entry)
+    ops.timed("weight_grad", sg.work, lambda: check(fn(*head, *tail, ops._stream())))
+
+
 def _wgrad_multi(segs, n_out: int, k_in: int, dw: Tensor, dw_col0: int, db: Optional[Tensor],
-                 col_map: Optional[Tensor] = None):
+                 col_map: Optional[Tensor] = None, *, mode=None, ordered=None):
     """One weight-gradient launch: the reduction runs over the points of every (dy, x[, (count, rows per count)]) segment
     (the field evaluations of one step share their weights), so the per-launch flush is paid once per layer.  A segment
     with a device-side count holds min(rows of dy, count * rows per count) rows (rsn_weight_grad_multi_dev): the
-    reflected-ray count never comes to the host."""
-    lib = _abi.load_library()
-    segs = [sg for sg in segs if sg[0].shape[0] > 0]
-    if not segs:
+    reflected-ray count never comes to the host.  mode (RSN_MMA_*) / ordered: None = the module's _WGRAD_MODE / _WGRAD_ORDERED."""
+    sg = _WGradSegs(segs, 1, n_out, k_in)
+    if not sg.keep:
         return
-    ns = len(segs)
-    ld_dy, ld_x = segs[0][0].stride(0), segs[0][1].stride(0)
-    assert all(sg[0].stride(0) == ld_dy and sg[1].stride(0) == ld_x and sg[0].shape[0] == sg[1].shape[0] for sg in segs)
-    npts = (C.c_int64 * ns)(*[sg[0].shape[0] for sg in segs])
-    dys = (C.c_void_p * ns)(*[sg[0].data_ptr() for sg in segs])
-    xs = (C.c_void_p * ns)(*[sg[1].data_ptr() for sg in segs])
-    cnt = [sg[2] if len(sg) > 2 else None for sg in segs]
-    ndev = (C.c_void_p * ns)(*[None if c is None else c[0].data_ptr() for c in cnt])
-    per = (C.c_int32 * ns)(*[1 if c is None else int(c[1]) for c in cnt])
-    dwp = C.c_void_p(dw.data_ptr() + 4 * dw_col0)
-    bf = torch.bfloat16  # rows that are bf16 in memory (reduced-precision training): all segments alike
-    assert all((sg[0].dtype == bf) == (segs[0][0].dtype == bf) and (sg[1].dtype == bf) == (segs[0][1].dtype == bf) for sg in segs)
-    operand_bf16 = (1 if segs[0][1].dtype == bf else 0) | (2 if segs[0][0].dtype == bf else 0)
-    work = {"point_out_in": sum(sg[0].shape[0] for sg in segs if len(sg) < 3 or sg[2] is None) * n_out * k_in}
-    dev_work = [(c[0], c[1] * n_out * k_in) for c in cnt if c is not None]
-    if dev_work:
-        work["point_out_in_dev"] = dev_work
-    if _WGRAD_ORDERED:
-        ws = _wgrad_workspace(lib, dw.device, ns, npts, 1, n_out, k_in, operand_bf16)
-        ops.timed("weight_grad", work,
-                  lambda: check(lib.rsn_weight_grad_multi_dev_ordered(ns, npts, ndev, per, dys, ld_dy, n_out, xs, ld_x, k_in,
-                                                                      ptr(col_map), dwp, dw.stride(0), ptr(db), _WGRAD_MODE,
-                                                                      operand_bf16, ptr(ws), ws.numel(), ops._stream())))
-        return
-    ops.timed("weight_grad", work,
-              lambda: check(lib.rsn_weight_grad_multi_dev(ns, npts, ndev, per, dys, ld_dy, n_out, xs, ld_x, k_in, ptr(col_map),
-                                                          dwp, dw.stride(0), ptr(db), _WGRAD_MODE, operand_bf16, ops._stream())))
+    dys, xs = sg.rows(segs)
+    head = (sg.ns, sg.npts, sg.ndev, sg.per, dys, sg.ld_dy, n_out, xs, sg.ld_x, k_in, ptr(col_map),
+            C.c_void_p(dw.data_ptr() + 4 * dw_col0), dw.stride(0), ptr(db))
+    _wgrad_launch("rsn_weight_grad_multi_dev", head, sg, dw.device, 1, n_out, k_in, mode, ordered)
 
 
-def _wgrad_jobs(jobs, n_out: int, k_in: int):
+def _wgrad_jobs(jobs, n_out: int, k_in: int, *, mode=None, ordered=None):
     """Several weight-gradient reductions of ONE shape in one launch (rsn_weight_grad_jobs): jobs = [(segs, dw, dw_col0, db[, col_map])]
     with segs as _wgrad_multi takes them, the same segment lengths / counts / leading dimensions / dtypes in every job.
     The workgroups are dealt to the jobs; the launch pays one atomic-flush phase and one ramp for all of them."""
-    lib = _abi.load_library()
-    jobs = [(jb[0], jb[1], jb[2], jb[3], jb[4] if len(jb) > 4 else None) for jb in jobs]
-    keep = [i for i, sg in enumerate(jobs[0][0]) if sg[0].shape[0] > 0]
-    if not keep:
+    sg = _WGradSegs(jobs[0][0], len(jobs), n_out, k_in)
+    if not sg.keep:
         return
-    ns = len(keep)
-    ref = [jobs[0][0][i] for i in keep]
-    ld_dy, ld_x = ref[0][0].stride(0), ref[0][1].stride(0)
-    bf = torch.bfloat16
-    operand_bf16 = (1 if ref[0][1].dtype == bf else 0) | (2 if ref[0][0].dtype == bf else 0)
-    npts = (C.c_int64 * ns)(*[sg[0].shape[0] for sg in ref])
-    cnt = [sg[2] if len(sg) > 2 else None for sg in ref]
-    ndev = (C.c_void_p * ns)(*[None if c is None else c[0].data_ptr() for c in cnt])
-    per = (C.c_int32 * ns)(*[1 if c is None else int(c[1]) for c in cnt])
     arr = (_abi.WGradJob * len(jobs))()
     hold = []  # the pointer arrays must outlive the call
-    for q, (segs_, dw, c0, db, cmap) in zip(arr, jobs):
-        sel = [segs_[i] for i in keep]
-        assert all(a[0].shape[0] == b[0].shape[0] and a[0].stride(0) == ld_dy and a[1].stride(0) == ld_x and
-                   a[0].dtype == b[0].dtype and a[1].dtype == b[1].dtype for a, b in zip(sel, ref))
-        dys = (C.c_void_p * ns)(*[sg[0].data_ptr() for sg in sel])
-        xs = (C.c_void_p * ns)(*[sg[1].data_ptr() for sg in sel])
+    for q, (segs_, dw, c0, db, *cmap) in zip(arr, jobs):
+        dys, xs = sg.rows(segs_)
         hold += [dys, xs]
         q.dy, q.x = dys, xs
-        q.col_map = None if cmap is None else cmap.data_ptr()
+        q.col_map = None if not cmap or cmap[0] is None else cmap[0].data_ptr()
         q.dw = dw.data_ptr() + 4 * c0
         q.ld_dw = dw.stride(0)
         q.db = None if db is None else db.data_ptr()
-    work = {"point_out_in": len(jobs) * sum(sg[0].shape[0] for sg in ref if len(sg) < 3 or sg[2] is None) * n_out * k_in}
-    dev_work = [(c[0], len(jobs) * c[1] * n_out * k_in) for c in cnt if c is not None]
-    if dev_work:
-        work["point_out_in_dev"] = dev_work
-    if _WGRAD_ORDERED:
-        ws = _wgrad_workspace(lib, jobs[0][1].device, ns, npts, len(jobs), n_out, k_in, operand_bf16)
-        ops.timed("weight_grad", work,
-                  lambda: check(lib.rsn_weight_grad_jobs_ordered(ns, npts, ndev, per, len(jobs), arr, ld_dy, n_out, ld_x, k_in,
-                                                                 _WGRAD_MODE, operand_bf16, ptr(ws), ws.numel(), ops._stream())))
-        return
-    ops.timed("weight_grad", work,
-              lambda: check(lib.rsn_weight_grad_jobs(ns, npts, ndev, per, len(jobs), arr, ld_dy, n_out, ld_x, k_in,
-                                                     _WGRAD_MODE, operand_bf16, ops._stream())))
+    head = (sg.ns, sg.npts, sg.ndev, sg.per, len(jobs), arr, sg.ld_dy, n_out, sg.ld_x, k_in)
+    _wgrad_launch("rsn_weight_grad_jobs", head, sg, jobs[0][1].device, len(jobs), n_out, k_in, mode, ordered)
 
 
 def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
@@ -247,9 +241,8 @@ def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
     evaluation that was launched with a device-side ray count are sized for the upper bound; the weight-gradient kernel
     reads the count itself and takes the first count * rows-per-count rows.  ordered: the reductions with a fixed order of addition
     (Model.deterministic) instead of the atomic flush."""
-    global _WGRAD_MODE, _WGRAD_ORDERED
-    _WGRAD_ORDERED = bool(ordered)
-    _WGRAD_MODE = int(field.mma_mode)  # bf16x6: split operands (fp32-equivalent); bf16: rounded operands (reduced precision)
+    # passed to every call below; bf16x6: split operands (fp32-equivalent); bf16: rounded operands (reduced precision)
+    how = {"mode": int(field.mma_mode), "ordered": bool(ordered)}
     # W: the PARAMETER width (n_out / k_in of the reductions); the operand rows are [N, field.width] (leading dimension = the
     # kernels' padded width, taken from the tensors' strides)
     L, W = field.mlp_base.num_layers, field.param_width
@@ -274,15 +267,16 @@ def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
             ww.append((segs(lambda sv, go: (go["dy"][l], sv["act"][l - 1])), gw, 0, gb))
     ww.append((segs(lambda sv, go: (go["d_bott"], sv["act"][L - 1])), g["field_output_bottleneck.net.weight"], 0,
                g["field_output_bottleneck.net.bias"]))
-    _wgrad_jobs(we, W, int(enc_map.numel()))
+    _wgrad_jobs(we, W, int(enc_map.numel()), **how)
     for i in range(0, len(ww), _WGRAD_JOBS_MAX):
-        _wgrad_jobs(ww[i:i + _WGRAD_JOBS_MAX], W, W)
+        _wgrad_jobs(ww[i:i + _WGRAD_JOBS_MAX], W, W, **how)
     _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["sh"])), 128, int(sh_map.numel()), g["mlp_mid.layers.0.weight"], 0,
-                 g["mlp_mid.layers.0.bias"], sh_map)
-    _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["bott"])), 128, W, g["mlp_mid.layers.0.weight"], 34, None)
+                 g["mlp_mid.layers.0.bias"], sh_map, **how)
+    _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["bott"])), 128, W, g["mlp_mid.layers.0.weight"], 34, None, **how)
     _wgrad_multi(segs(lambda sv, go: (go["dz_rgb"], sv["hid"])), 3, 128, g["field_output_mid.net.weight"], 0,
-                 g["field_output_mid.net.bias"])
-    _wgrad_multi(segs(lambda sv, go: (go["dz_heads"], sv["act"][L - 1]), only_heads=True), 16, W, acc.heads_w, 0, acc.heads_b)
+                 g["field_output_mid.net.bias"], **how)
+    _wgrad_multi(segs(lambda sv, go: (go["dz_heads"], sv["act"][L - 1]), only_heads=True), 16, W, acc.heads_w, 0, acc.heads_b,
+                 **how)
 
 
 def _field_backward(field, rays, eb, level, gin: Dict[str, Optional[Tensor]], need_input: bool, n_dev=None,

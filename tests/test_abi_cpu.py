@@ -293,3 +293,59 @@ def test_field_argument_errors_are_pinned(lib):
     diff = {k: (want["answers"][want["cases"][k]], got["answers"][got["cases"][k]]) for k in want["cases"]
             if want["answers"][want["cases"][k]] != got["answers"][got["cases"][k]]}
     assert not diff, "%d of %d differ, e.g. %s" % (len(diff), len(want["cases"]), sorted(diff.items())[:5])
+
+
+_wgrad_child = {}
+
+
+def _wgrad_matrix():
+    """tools/record_wgrad_errors.py on the tree's own build, once for the two tests below: a child process that hides the GPUs from
+    itself, so that a library that let a call through could not launch on the made-up pointers."""
+    if not _wgrad_child:
+        import json
+        import subprocess
+        import sys
+
+        from tests.test_deterministic_gpu import SHAPES
+
+        shapes = [list(s) for s in SHAPES] + [[64, 64, 64, 64]]
+        res = subprocess.run([sys.executable, os.path.join(REPO, "tools", "record_wgrad_errors.py"), "-", "--bound", json.dumps(shapes)],
+                             capture_output=True, text=True, env={**os.environ, "RSN_LIBRARY": LIB_PATH})
+        assert res.returncode == 0, res.stderr[-2000:]
+        _wgrad_child.update(json.loads(res.stdout), shapes=shapes)
+    return _wgrad_child
+
+
+def test_weight_grad_argument_errors_are_pinned(lib):
+    """Every weight-gradient entry point's answer to invalid arguments -- (return code, rsn_last_error()) for each NULL pointer, count,
+    shape, mode or leading dimension out of range, NULL row pointer and bad job, singly and in pairs (which check comes first) --,
+    RSN_OK for the calls without points, and the refusals that come before a launch (bf16 rows no kernel reads, an ordered call
+    without its workspace; "needs N bytes" pins the grid) equal tests/golden/wgrad_errors.json, recorded with
+    tools/record_wgrad_errors.py on the library of the commit before the launch path was restated: 4,860 calls, none of which
+    reaches the device."""
+    import hashlib
+    import json
+
+    got = _wgrad_matrix()
+    with open(os.path.join(REPO, "tests", "golden", "wgrad_errors.json")) as fh:
+        want = json.load(fh)
+    # the record holds the answers in the order of the sorted case names, and the names' digest instead of the names
+    names = sorted(got["cases"])
+    assert want["n_cases"] == len(want["answer_of_case"]) == len(names) == 4860
+    assert hashlib.sha256("\n".join(names).encode()).hexdigest() == want["cases_sha256"], "the matrix has other cases than the record"
+    diff = {k: (want["answers"][i], got["answers"][got["cases"][k]]) for k, i in zip(names, want["answer_of_case"])
+            if want["answers"][i] != got["answers"][got["cases"][k]]}
+    assert not diff, "%d of %d differ, e.g. %s" % (len(diff), len(names), sorted(diff.items())[:5])
+
+
+def test_weight_grad_workspace_bytes_bounds_the_ordered_launch(lib):
+    """rsn_weight_grad_workspace_bytes is computed without the row pointers; the ordered launch sizes its workspace with them (rows
+    off the vector-load layout take the scalar-load kernel's grid).  For every shape of test_deterministic_gpu.SHAPES and 64 x 64,
+    modes 0..3, four lists of segment lengths and X rows aligned / 4 bytes off, the "needs N bytes" of an ordered call with
+    workspace_bytes = 0 must not exceed it."""
+    got = _wgrad_matrix()
+    rows = got["workspace_bound"]
+    assert len(rows) == len(got["shapes"]) * 4 * 4 * 2 == 256
+    over = [r for r in rows if not 0 < r[1] <= r[2]]
+    print("largest needed / bound: %.3f" % max(r[1] / r[2] for r in rows))
+    assert not over, "%d of %d launches need more than the bound, e.g. %s" % (len(over), len(rows), over[:3])

@@ -1114,7 +1114,8 @@ def test_fused_radam_matches_torch_optim(dev):
     (37, 130, 38, 132),    # X vector path impossible (130 % 8): scalar loads, odd row count
 ])
 def test_weight_grad_segments_and_shapes(dev, n_out, k_in, ld_dy, ld_x):
-    """rsn_weight_grad_multi: dW = sum over all segments of dY^T X, db = column sums; against fp64 matmul.
+    """rsn_weight_grad_multi_dev (through train_graph._wgrad_multi, in its default mode: exact fp32, atomic flush): dW = sum over all
+    segments of dY^T X, db = column sums; against fp64 matmul.
     Segment lengths cover empty segments, lengths below one pipeline stage and non-multiples of the stage."""
     from reflect_sampling_nerf_amd.train_graph import _wgrad_multi
 
@@ -1137,11 +1138,69 @@ def test_weight_grad_segments_and_shapes(dev, n_out, k_in, ld_dy, ld_x):
     assert float(dw[:, :5].abs().max()) == 0.0
     assert float((db.double().cpu() - ref_b).abs().max()) <= 2e-5 * float(ref_b.abs().max())
 
+_FLAT_LENS = [300, 0, 37, 3]
+_flat_cases = {}
+
+
+def _flat_case(n_out, k_in, ld_dy, ld_x):
+    """Host operands of one shape and the fp64 products (exact / of the bf16-rounded operands; all segments / the first): once."""
+    key = (n_out, k_in, ld_dy, ld_x)
+    if key not in _flat_cases:
+        g = torch.Generator().manual_seed(n_out * 1000 + k_in + 1)
+        segs = [(torch.randn(n, ld_dy, generator=g), torch.randn(n, ld_x, generator=g)) for n in _FLAT_LENS]
+        w = [dy[:, :n_out].double().t() @ x[:, :k_in].double() for dy, x in segs]
+        w_bf = [dy[:, :n_out].bfloat16().double().t() @ x[:, :k_in].bfloat16().double() for dy, x in segs]
+        b = [dy[:, :n_out].double().sum(0) for dy, _ in segs]
+        _flat_cases[key] = (segs, {"all": (sum(w), sum(w_bf), sum(b)), "first": (w[0], w_bf[0], b[0])})
+    return _flat_cases[key]
+
+
+@pytest.mark.parametrize("n_out,k_in,ld_dy,ld_x", [
+    (64, 64, 64, 64),      # vector loads, NKB 2, one row-block pair
+    (37, 130, 38, 132),    # scalar loads, NKB 8
+])
+@pytest.mark.parametrize("entry,mode", [("rsn_weight_grad", 0), ("rsn_weight_grad_multi", 0), ("rsn_weight_grad_multi_mode", 0),
+                                        ("rsn_weight_grad_multi_mode", 1), ("rsn_weight_grad_multi_mode", 3)])
+def test_weight_grad_flat_entry_points(dev, entry, mode, n_out, k_in, ld_dy, ld_x):
+    """rsn_weight_grad, rsn_weight_grad_multi and rsn_weight_grad_multi_mode called directly (the training graph goes through
+    rsn_weight_grad_multi_dev / _jobs): segments of 300, 0, 37 and 3 points (rsn_weight_grad: the first), into a k_in + 5 wide dW at
+    column 5, with a bias; against the fp64 product under the bound of the tests above -- in plain bf16 on its vector path, the
+    product of the bf16-rounded operands (test_weight_grad_mma_modes)."""
+    import ctypes as C
+
+    from reflect_sampling_nerf_amd._abi import check, ptr
+
+    lib = pkg.load_library()
+    host, refs = _flat_case(n_out, k_in, ld_dy, ld_x)
+    segs = [(dy.to(dev), x.to(dev)) for dy, x in host]
+    dw, db = torch.zeros(n_out, k_in + 5, device=dev), torch.zeros(n_out, device=dev)
+    dwp, stream = C.c_void_p(dw.data_ptr() + 4 * 5), ops._stream()
+    if entry == "rsn_weight_grad":
+        check(lib.rsn_weight_grad(_FLAT_LENS[0], ptr(segs[0][0]), ld_dy, n_out, ptr(segs[0][1]), ld_x, k_in, None, dwp, dw.stride(0),
+                                  ptr(db), stream))
+    else:
+        ns = len(segs)
+        head = (ns, (C.c_int64 * ns)(*_FLAT_LENS), (C.c_void_p * ns)(*[sg[0].data_ptr() for sg in segs]), ld_dy, n_out,
+                (C.c_void_p * ns)(*[sg[1].data_ptr() for sg in segs]), ld_x, k_in, None, dwp, dw.stride(0), ptr(db))
+        check(lib.rsn_weight_grad_multi(*head, stream) if entry == "rsn_weight_grad_multi" else
+              lib.rsn_weight_grad_multi_mode(*head, mode, stream))
+    torch.cuda.synchronize()
+    exact_w, bf_w, ref_b = refs["first" if entry == "rsn_weight_grad" else "all"]
+    vector_path = n_out > 32 and k_in % (8 if k_in > 128 else 4 if k_in > 64 else 2) == 0 and ld_x % 4 == 0 and ld_dy % 2 == 0
+    ref_w = bf_w if mode == 3 and vector_path else exact_w
+    e_w, e_b = float((dw[:, 5:].double().cpu() - ref_w).abs().max()), float((db.double().cpu() - ref_b).abs().max())
+    print(f"{entry} mode {mode} {n_out}x{k_in}: dW err {e_w:.3e} / bound {2e-5 * float(ref_w.abs().max()):.3e}, "
+          f"db err {e_b:.3e} / bound {2e-5 * float(ref_b.abs().max()):.3e}")
+    assert e_w <= 2e-5 * float(ref_w.abs().max())
+    assert e_b <= 2e-5 * float(ref_b.abs().max())
+    assert float(dw[:, :5].abs().max()) == 0.0
+
 
 @pytest.mark.parametrize("mode", ["bf16", "bf16x6"])
 @pytest.mark.parametrize("n_out,k_in", [(256, 256), (256, 104), (128, 40), (16, 256), (250, 99)])
 def test_weight_grad_mma_modes(dev, monkeypatch, n_out, k_in, mode):
-    """rsn_weight_grad_multi_mode.  bf16 (the opt-in reduced-precision training mode): operands rounded to bf16 inside the
+    """rsn_weight_grad_multi_dev in the bf16 modes (through train_graph._wgrad_multi; rsn_weight_grad_multi_mode itself:
+    test_weight_grad_flat_entry_points).  bf16 (the opt-in reduced-precision training mode): operands rounded to bf16 inside the
     kernel, fp32 accumulation -> equals the fp64 product of the bf16-ROUNDED operands to fp32 accumulation accuracy.
     bf16x6: operands split into bf16 triples, 6 products -> meets the exact kernel's bound against the fp64 product.
     The bias sums stay exact fp32, and shapes the vector loads cannot take fall back to the exact kernel."""

@@ -646,6 +646,31 @@ def test_single_backward_equals_one_job_launch(dev, kind, mode, layers, width):
     _assert_same_bits(f"backward {'inf' if kind else 'frustum'} {mode} gout", a, b, job["n"], live)
 
 
+def test_weight_grads_leave_no_mode_behind(dev):
+    """train_graph._weight_grads passes its mode and its order of addition to every call it makes and leaves the module's defaults
+    alone: after the weight gradients of a plain-bf16 field with the ordered reduction, _WGRAD_MODE / _WGRAD_ORDERED are still 0 /
+    False, and a bare _wgrad_multi call is the exact-fp32 reduction -- within 2e-5 x max|ref| of the fp64 product of the unrounded
+    operands (test_gpu_parity.test_weight_grad_segments_and_shapes' bound), which bf16 operands (2^-9 each) miss by far."""
+    f = _one_job_field(dev, "bf16", 8, 256)
+    job, _, _ = _one_job_inputs(0, dev)
+    o, d, pa, eb = job["rays"]
+    lv = f.evaluate_frustums_train(o, d, pa, eb, want_normals=True)
+    go = train_graph._field_backward(f, (o, d, pa), eb, lv, job["gin"], True)
+    acc = train_graph._GradAcc(f)
+    train_graph._weight_grads(f, [(lv["saved"], go, True)], acc, ordered=True)
+    grads = acc.finish()
+    assert all(bool(torch.isfinite(g).all()) for g in grads.values()) and float(grads["mlp_base.layers.3.weight"].abs().max()) > 0.0
+    assert train_graph._WGRAD_MODE == 0 and train_graph._WGRAD_ORDERED is False
+    g = torch.Generator().manual_seed(64)
+    dy, x = torch.randn(300, 64, generator=g), torch.randn(300, 64, generator=g)
+    ref = dy.double().t() @ x.double()
+    dw = torch.zeros(64, 64, device=dev)
+    train_graph._wgrad_multi([(dy.to(dev), x.to(dev))], 64, 64, dw, 0, None)
+    err, bound = float((dw.double().cpu() - ref).abs().max()), 2e-5 * float(ref.abs().max())
+    print(f"bare _wgrad_multi after a bf16 ordered step: dW err {err:.3e} / bound {bound:.3e}")
+    assert err <= bound
+
+
 # ---------------------------------------------------------------------------------------------- 4. whole steps
 def _weighted_loss(out, tgt, wr):
     """_loss_from_outputs of test_gpu_parity with a weight per ray instead of the mean over rays."""
