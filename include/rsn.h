@@ -676,6 +676,35 @@ int rsn_mesh_emit(int32_t nx, int32_t ny, int32_t nz, const float* vol, float is
                   const float* spacing3, const void* workspace, size_t workspace_bytes, int32_t max_vertices,
                   int32_t max_triangles, float* positions, int32_t* vert_key, int32_t* triangles, void* stream);
 
+
+/* ---- visualisation: per-pixel floats as one 8-bit RGB tile of a panel (additive to ABI 18: no existing call changes).
+ * One call draws one channel of a rendered view into one tile, so a frame is a handful of launches on the caller's stream.
+ *
+ * out is uint8 [height, pitch, 3] with pitch in pixels; input pixel p = y*width + x goes to out[(y*pitch + x0 + x)*3 + c],
+ * c = 0..2, and no byte outside the tile [x0, x0 + width) of any row is written.  Every step below is one fp32 operation:
+ *   sat(v)  = 0 if v is NaN or v <= 0, 1 if v > 1, else v   (-inf -> 0, +inf -> 1, -0.0 -> +0)
+ *   a       = sat(alpha[p]), or 1 when alpha is NULL
+ *   over(c) = c*a + (1 - a)            white beneath: what RGBRenderer does with the model's white background and
+ *                                      nerfstudio's apply_depth_colormap with its accumulation; a multiply, a subtract, an add
+ *   q(v)    = (uint8)(int)(v*255.0f + 0.5f) for v in [0, 1]      (the quantisation of the trainer's eval panels)
+ * RSN_VIS_RGB : x [N,3]; out_c = q(over(sat(x_c)))
+ * RSN_VIS_UNIT: x [N,3]; out_c = q(over(sat(x_c*0.5f + 0.5f)))   (the usual colouring of a unit normal)
+ * RSN_VIS_GRAY: x [N];   t = sat((x - lo) / (hi - lo)), all three channels q(over(t))
+ * RSN_VIS_LUT : x [N];   t as above, k = (int)(t*255.0f), in [0, 255] since t <= 1; out_c = q(over(lut[k][c])) with lut an
+ *               fp32 [256,3] table on the device, values in [0, 1].  With the turbo table, lo / hi = near / far and alpha =
+ *               the accumulation this is nerfstudio 0.3 colormaps.apply_depth_colormap, except that nerfstudio divides by
+ *               (far - near + 1e-10) and this call by (hi - lo).
+ * lo / hi / lut are not read by the kinds that do not name them.
+ * RSN_ERR_INVALID_ARGUMENT before any launch, with the reason in rsn_last_error(): height < 1, width < 1 or height*width >
+ * 2^31 - 1; x0 < 0 or x0 + width > pitch; an unknown kind; x or out NULL; lut NULL with RSN_VIS_LUT; for GRAY and LUT lo or
+ * hi not finite, or hi <= lo.  No allocation and no synchronisation. */
+#define RSN_VIS_RGB 0
+#define RSN_VIS_UNIT 1
+#define RSN_VIS_GRAY 2
+#define RSN_VIS_LUT 3
+int rsn_visualize(int32_t height, int32_t width, int32_t kind, const float* x, const float* alpha, float lo, float hi,
+                  const float* lut, uint8_t* out, int32_t pitch, int32_t x0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

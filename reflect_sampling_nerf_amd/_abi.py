@@ -15,6 +15,7 @@ RSN_NUM_FREQS = 16
 RSN_SPACING_UNIFORM = 0
 RSN_SPACING_RECIPROCAL = 1
 RSN_MMA_F32, RSN_MMA_BF16X6, RSN_MMA_BF16X3, RSN_MMA_BF16 = 0, 1, 2, 3
+RSN_VIS_RGB, RSN_VIS_UNIT, RSN_VIS_GRAY, RSN_VIS_LUT = 0, 1, 2, 3
 
 _fp = C.c_void_p  # device float*
 
@@ -206,6 +207,8 @@ _SIGNATURES = {
     "rsn_mesh_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rsn_mesh_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rsn_visualize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_float, C.c_float, _fp, C.c_void_p, C.c_int32,
+                                C.c_int32, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

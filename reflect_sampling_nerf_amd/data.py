@@ -140,13 +140,11 @@ class RayDataManager:
         s = self.scene
         if not 0 <= i < s.num_images:
             raise IndexError(f"camera {i} of {s.num_images}")
-        H, W = s.height, s.width
-        flat = torch.empty(H * W * 7, device=self.device, dtype=torch.float32)
-        o, d, pa = flat[0:3 * H * W].view(H, W, 3), flat[3 * H * W:6 * H * W].view(H, W, 3), flat[6 * H * W:].view(H, W, 1)
-        _abi.check(self._lib.rsn_camera_rays_image(H, W, _abi.ptr(self.c2w[i]), s.fx, s.fy, s.cx, s.cy, _abi.ptr(o),
-                                                   _abi.ptr(d), _abi.ptr(pa), self._stream()))
-        cam = torch.full((H, W, 1), i, device=self.device, dtype=torch.int32)
-        return RayBundle(origins=o, directions=d, pixel_area=pa, camera_indices=cam)
+        from .render import camera_rays
+
+        rb = camera_rays(self.c2w[i], s.height, s.width, s.fx, s.fy, s.cx, s.cy, self.device)
+        rb.camera_indices = torch.full((s.height, s.width, 1), i, device=self.device, dtype=torch.int32)
+        return rb
 
     def image(self, i: int) -> torch.Tensor:
         """Ground truth of camera i: [H,W,4] float32 RGBA in [0, 1] on the device, uint8 / 255 as nerfstudio's

@@ -3,6 +3,7 @@
     python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR]
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
+    python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
 
 `train` is the reference's `ns-train reflect-sampling-nerf --data DIR` loop on this package's own pieces: the reference
 Model config (ReflectSamplingNeRFModelConfig defaults), RayDataManager batches (1024 rays, reflect_sampling_nerf_config.py:36-41),
@@ -23,6 +24,12 @@ stream.  Multi-GPU training is not offered here.
 `export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
 the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
 (mesh.py).  The default level, sigma = 10, is a starting point that has not been measured against a scene.
+
+`render` draws a checkpoint from viewpoints of the user's choosing (render.py): an orbit around a centre, or the poses of a
+transforms-format file, optionally with poses interpolated in between.  Every frame is a PNG panel of the chosen channels side by
+side -- the final colour, the direct pass, diffuse colour, tint, roughness, predicted normals, turbo-coloured depth, accumulation,
+the reflection mask -- or, with --tiles, one PNG per channel; frames.json records the cameras.  There is no video encoder here:
+the frames are the product.
 """
 from __future__ import annotations
 
@@ -87,7 +94,95 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                     help="density level of the surface (default 10: a starting point, not measured against any scene; pick it per scene)")
     ex.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels (default f32)")
     ex.add_argument("--chunk", type=int, default=None, help="points per field launch (default 262144)")
+    from .render import CHANNELS, DEFAULT_CHANNELS, DEFAULT_CHUNK
+
+    rn = sub.add_parser("render", help="render a camera path from a checkpoint as PNG panels of colour and material maps")
+    rn.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
+    rn.add_argument("--out", required=True, help="output directory: panel/0000.png ... (or <channel>/0000.png ... with --tiles), frames.json")
+    rn.add_argument("--path", choices=("orbit", "poses"), default=None,
+                    help="orbit around --center, or the poses of --poses / of --data's split (default: poses when --poses is given, else orbit)")
+    rn.add_argument("--frames", type=int, default=120, help="frames of an orbit (default 120)")
+    rn.add_argument("--center", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"), help="orbit centre (default 0 0 0)")
+    rn.add_argument("--radius", type=float, default=None,
+                    help="orbit radius (default with --data: the mean distance of the split's cameras from --center)")
+    rn.add_argument("--elevation", type=float, default=None, metavar="DEG",
+                    help="orbit elevation above the xy-plane (default with --data: the mean elevation of the split's cameras; else 30)")
+    rn.add_argument("--azimuth", type=float, default=0.0, metavar="DEG", help="azimuth of the orbit's first frame (default 0)")
+    rn.add_argument("--poses", default=None, metavar="FILE.json", help="transforms-format file: frames[].transform_matrix, camera_angle_x, w / h")
+    rn.add_argument("--data", default=None, metavar="DIR", help="scene directory: poses, field of view and image size of transforms_{split}.json")
+    rn.add_argument("--split", default="test")
+    rn.add_argument("--scale-factor", type=float, default=1.0, help="scale of the translations read from --poses / --data")
+    rn.add_argument("--interpolate", type=int, default=0, metavar="K", help="poses inserted between consecutive ones of a poses path (default 0)")
+    rn.add_argument("--width", type=int, default=None)
+    rn.add_argument("--height", type=int, default=None)
+    rn.add_argument("--fov-x", type=float, default=None, metavar="DEG", help="horizontal field of view in degrees")
+    rn.add_argument("--channels", nargs="+", choices=tuple(CHANNELS), default=list(DEFAULT_CHANNELS), metavar="CHANNEL",
+                    help="tiles of the panel, left to right: " + " ".join(CHANNELS) + " (default: " + " ".join(DEFAULT_CHANNELS) + ")")
+    rn.add_argument("--depth-range", type=float, nargs=2, default=None, metavar=("NEAR", "FAR"),
+                    help="range of the depth colour map (default: the model's collider planes)")
+    rn.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels (default f32)")
+    rn.add_argument("--chunk", type=int, default=DEFAULT_CHUNK, help=f"rays per eval chunk (default {DEFAULT_CHUNK})")
+    rn.add_argument("--tiles", action="store_true", help="one PNG per channel and frame instead of the tiled panel")
     return ap
+
+
+def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
+    """The cameras of a `render` command line: {"c2w" [F,3,4], "width", "height", "fx", "fy", "cx", "cy"}.  Host work only (JSON and
+    one image header).  What the command line leaves open and no file settles is an argparse error that names the option."""
+    from . import render
+
+    if args.poses is not None and args.data is not None:
+        ap.error("render: give --poses or --data, not both")
+    src = None
+    if args.poses is not None:
+        src = render.load_poses(args.poses, args.scale_factor)
+    elif args.data is not None:
+        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), args.scale_factor)
+        if src["width"] is None or src["height"] is None:  # Blender-format files carry no size: the first image's header has it
+            rel = src["file_paths"][0]
+            path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
+            if os.path.isfile(path):
+                from PIL import Image
+
+                with Image.open(path) as img:
+                    src["width"], src["height"] = (int(v) for v in img.size)
+    width = args.width if args.width is not None else (src or {}).get("width")
+    height = args.height if args.height is not None else (src or {}).get("height")
+    fov = math.radians(args.fov_x) if args.fov_x is not None else (src or {}).get("camera_angle_x")
+    where = "" if src is None else " (the file gives none)"
+    for name, v in (("--width", width), ("--height", height), ("--fov-x", fov)):
+        if v is None:
+            ap.error(f"render: {name} is required{where}: without --data / --poses all of --width --height --fov-x are")
+    if width < 1 or height < 1 or not 0.0 < fov < math.pi:
+        ap.error(f"render: --width {width} --height {height} --fov-x {math.degrees(fov):g}: need a positive size and 0 < fov < 180")
+    path = args.path or ("poses" if args.poses is not None else "orbit")
+    if path == "poses":
+        if src is None:
+            ap.error("render: --path poses needs --poses or --data")
+        c2w = render.interpolate_path(src["c2w"], args.interpolate)
+    else:
+        radius, elevation = args.radius, args.elevation
+        if args.data is not None:  # the split's own cameras say where a camera of this scene sits
+            rel = src["c2w"][:, :, 3].astype(np.float64) - np.asarray(args.center, dtype=np.float64)
+            dist = np.linalg.norm(rel, axis=1)
+            if radius is None:
+                radius = float(dist.mean())
+            if elevation is None:
+                elevation = float(np.degrees(np.arcsin(np.clip(rel[:, 2] / np.maximum(dist, 1e-30), -1.0, 1.0))).mean())
+        if radius is None:
+            ap.error("render: --radius is required for an orbit without --data")
+        if elevation is None:
+            elevation = 30.0
+        try:
+            c2w = render.orbit_path(args.frames, args.center, radius, elevation, args.azimuth)
+        except ValueError as e:
+            ap.error(f"render: {e}")
+    if args.depth_range is not None and not args.depth_range[1] > args.depth_range[0]:
+        ap.error("render: --depth-range needs NEAR < FAR")
+    if args.chunk < 1:
+        ap.error("render: --chunk must be >= 1")
+    fx, fy, cx, cy = render.pinhole(width, height, fov)
+    return {"c2w": c2w, "width": int(width), "height": int(height), "fx": fx, "fy": fy, "cx": cx, "cy": cy}
 
 
 # ------------------------------------------------------------------------------------------------ model and checkpoints
@@ -351,8 +446,10 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
 def main(argv=None) -> int:
     from .data import load_blender_split
 
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
     given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
+    cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
     if not torch.cuda.is_available():
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
@@ -373,6 +470,17 @@ def main(argv=None) -> int:
         print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles at sigma = "
               f"{res['iso']:g} on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
               " ".join(f"{k} {sec[k]:.3f} s" for k in ("grid", "count", "emit", "attributes", "write")) + f" -> {res['out']}")
+        return 0
+    if args.command == "render":
+        from . import render
+
+        res = render.render_checkpoint(args.ckpt, args.out, cameras["c2w"], cameras["height"], cameras["width"], cameras["fx"],
+                                       cameras["fy"], cameras["cx"], cameras["cy"], channels=args.channels,
+                                       depth_range=None if args.depth_range is None else tuple(args.depth_range), mma=args.mma,
+                                       chunk=args.chunk, tiles=args.tiles)
+        n, sec = len(res["frames"]), res["seconds"]
+        print(f"{res['checkpoint']} (step {res['step']}): {n} frames {res['width']} x {res['height']} of {' '.join(res['channels'])}; "
+              f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
         return 0
     scene = load_blender_split(args.data, args.split, args.scale_factor)
     res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images)
