@@ -705,6 +705,45 @@ int rsn_mesh_emit(int32_t nx, int32_t ny, int32_t nz, const float* vol, float is
 int rsn_visualize(int32_t height, int32_t width, int32_t kind, const float* x, const float* alpha, float lo, float hi,
                   const float* lut, uint8_t* out, int32_t pitch, int32_t x0, void* stream);
 
+
+/* ---- occupancy: skip the rays of an eval render that see nothing (additive to ABI 18: no existing call changes).
+ *
+ * Grid: nx * ny * nz vertices in the layout of the mesh calls (x fastest, vertex (i, j, k) at origin + spacing * (i, j, k)) and
+ * (nx-1)(ny-1)(nz-1) cells; cell (i, j, k) spans the vertices (i..i+1, j..j+1, k..k+1), has flat index
+ * c = (k*(ny-1) + j)*(nx-1) + i and is bit c % 32 of uint32 word c / 32.  rsn_occupancy_bytes: the size of that bit array, the word
+ * count rounded up times 4; 0 with a message when a dimension is below 2 or nx*ny*nz > 2^27.
+ *
+ * rsn_occupancy_build: bits from a density volume vol (fp32 [nz, ny, nx]).  Cell (i, j, k) is occupied if and only if some vertex
+ * (i', j', k') inside the grid has !(vol < threshold) -- so a NaN vertex counts as occupied -- with i - dilate <= i' <= i + 1 + dilate
+ * and likewise for j and k; dilate = 0, 1 or 2.  That is "any of the cell's eight corners, then grown by `dilate` cells in the
+ * Chebyshev sense", stated over vertices so that no temporary bit array is needed.  The unused high bits of the last word are written
+ * as 0; `bytes` is the capacity of bits (at least rsn_occupancy_bytes, else RSN_ERR_INVALID_ARGUMENT) and no byte past the bit array
+ * is written.  Bit-exact and deterministic.
+ *
+ * rsn_occupancy_cull: which of n_rays segments o + t d, t in [near, far] (origins / directions [R,3], nears / fars [R]; d as given,
+ * not normalised) can be skipped.  origin3 / spacing3 are HOST arrays (finite, spacing > 0).  hit[r] (uint8) = 1 when the segment
+ * crosses an occupied cell; with outside_occupied != 0 also when any part of it lies outside the grid's box; and always when an
+ * origin, direction, near or far is not finite or far < near: a ray that cannot be reasoned about is never culled.  The decision is
+ * exact up to a band of 1e-3 of a cell around the cell faces (and the box's), inside which either answer may come; it is
+ * deterministic.  n_hit (device int32) = the number of hit rays; ray_index (int32 [R]) is a permutation of 0..R-1: first the hit
+ * rays in ascending order, then the culled rays in ascending order (a stable compaction without atomics; `workspace`: device memory
+ * of rsn_occupancy_cull_workspace_bytes(n_rays) bytes, contents irrelevant).  n_rays == 0 launches nothing and sets *n_hit = 0.
+ *
+ * rsn_scatter_rows: results of the compacted rays back to their rows: out[ray_index[i]*row_floats + c] = src[i*row_floats + c] when
+ * i < *n_dev (n_dev NULL: n_rows), `fill` otherwise, for i < n_rows, c < row_floats.  With ray_index a permutation of 0..n_rows-1
+ * every row of out is written exactly once; rows of src at and past the count are never read, and an entry of ray_index outside
+ * 0..n_rows-1 writes nothing. */
+size_t rsn_occupancy_bytes(int32_t nx, int32_t ny, int32_t nz);
+int rsn_occupancy_build(int32_t nx, int32_t ny, int32_t nz, const float* vol, float threshold, int32_t dilate, uint32_t* bits,
+                        size_t bytes, void* stream);
+size_t rsn_occupancy_cull_workspace_bytes(int32_t n_rays);
+int rsn_occupancy_cull(int32_t n_rays, const float* origins, const float* directions, const float* nears, const float* fars,
+                       int32_t nx, int32_t ny, int32_t nz, const float* origin3, const float* spacing3, const uint32_t* bits,
+                       int32_t outside_occupied, uint8_t* hit, int32_t* n_hit, int32_t* ray_index, int32_t* workspace,
+                       void* stream);
+int rsn_scatter_rows(int32_t n_rows, const int32_t* n_dev, const int32_t* ray_index, const float* src, int32_t row_floats,
+                     float fill, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

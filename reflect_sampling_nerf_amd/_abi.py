@@ -209,6 +209,13 @@ _SIGNATURES = {
                                 C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsn_visualize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_float, C.c_float, _fp, C.c_void_p, C.c_int32,
                                 C.c_int32, C.c_void_p]),
+    "rsn_occupancy_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rsn_occupancy_build": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rsn_occupancy_cull_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "rsn_occupancy_cull": (C.c_int, [C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "rsn_scatter_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, _fp, C.c_int32, C.c_float, _fp, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

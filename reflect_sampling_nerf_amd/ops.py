@@ -94,16 +94,18 @@ def sample_pdf(n_rays: int, n_dev: Optional[Tensor], s_in: int, s_out: int, spac
 
 def composite(n_rays: int, n_dev: Optional[Tensor], n_samples: int, background: int, flags: int, sigma: Tensor,
               euclid_bins: Tensor, color: Tensor, bg_rgb: Optional[Tensor] = None, level: Optional[Dict] = None,
-              surface: bool = False, want_depth: bool = True, ray_losses: bool = False) -> Dict[str, Tensor]:
+              surface: bool = False, want_depth: bool = True, ray_losses: bool = False,
+              zero_accumulation: bool = False) -> Dict[str, Tensor]:
     """-> weights [R,S], rgb [R,3], accumulation [R], depth [R] (+ diff/tint/normals/roughness if surface;
     + pn_loss_ray / ori_loss_ray [R] if ray_losses: the per-sample normal losses of get_loss_dict (model.py:403-407)
-    reduced per ray where the weights are in registers; needs level["normals"], ["pred_normals"], ["n_dot_d"])."""
+    reduced per ray where the weights are in registers; needs level["normals"], ["pred_normals"], ["n_dot_d"]).
+    zero_accumulation: the accumulation starts as zeros, so that the rows at and past *n_dev, which the kernel leaves alone, hold 0."""
     lib = _abi.load_library()
     dev = sigma.device
     out = {
         "weights": torch.empty(n_rays, n_samples, device=dev, dtype=torch.float32),
         "rgb": torch.empty(n_rays, 3, device=dev, dtype=torch.float32),
-        "accumulation": torch.empty(n_rays, device=dev, dtype=torch.float32),
+        "accumulation": (torch.zeros if zero_accumulation else torch.empty)(n_rays, device=dev, dtype=torch.float32),
     }
     if want_depth:
         out["depth"] = torch.empty(n_rays, device=dev, dtype=torch.float32)

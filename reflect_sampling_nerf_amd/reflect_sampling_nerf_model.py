@@ -99,6 +99,7 @@ class ReflectSamplingNeRFModel(Model):
         # key check sees them -- also when the checkpoint is loaded through a parent (nerfstudio's pipeline: prefix `_model.`).
         self._register_load_state_dict_pre_hook(self._drop_reference_metric_state)
         self._deterministic = os.environ.get("RSN_DETERMINISTIC", "") == "1"
+        self.occupancy = None  # an occupancy.OccupancyGrid: eval renders skip the rays that cross no occupied cell (_cull)
 
     _REFERENCE_METRIC_MODULES = ("lpips", "psnr", "ssim")
 
@@ -130,6 +131,8 @@ class ReflectSamplingNeRFModel(Model):
             raise ValueError("populate_fields() must be called before get_outputs")
         if self.training:
             return self._get_outputs_train(ray_bundle)
+        if getattr(self, "occupancy", None) is not None:
+            return self._get_outputs_eval_culled(ray_bundle)
         return self._get_outputs_eval(ray_bundle)
 
     def _get_outputs_train(self, ray_bundle, jitter: Optional[Dict[str, Tensor]] = None,
@@ -164,7 +167,10 @@ class ReflectSamplingNeRFModel(Model):
         return 0 if nm is None else int(nm.item())
 
     @torch.no_grad()
-    def _get_outputs_eval(self, ray_bundle) -> Dict[str, Tensor]:
+    def _get_outputs_eval(self, ray_bundle, n_dev0: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """n_dev0 (culled renders only): device int32 count of the bundle's leading rays that are live.  The primary-level launches
+        take it as their n_dev; the rows behind it are never computed, and their accumulation is 0 so that rsn_reflect_setup --
+        which takes only a host count -- masks none of them."""
         cfg, fld = self.config, self.field
         R = ray_bundle.origins.shape[0]
         o = ops._f32c(ray_bundle.origins.reshape(R, 3))
@@ -178,14 +184,15 @@ class ReflectSamplingNeRFModel(Model):
         uni, rec = self.sampler_uniform.spec, self.sampler_reciprocal.spec
 
         # A. coarse primary (model.py:148-177)
-        sb_c, eb_c = ops.sample_spaced(R, None, Sc, uni.spacing, uni.tan, nears, fars, None)
-        lc = fld.evaluate_frustums(o, d, pa, eb_c)
-        cc = ops.composite(R, None, Sc, 1, EVAL | CLIP, lc["sigma"], eb_c, lc["color"])
+        sb_c, eb_c = ops.sample_spaced(R, n_dev0, Sc, uni.spacing, uni.tan, nears, fars, None)
+        lc = fld.evaluate_frustums(o, d, pa, eb_c, n_dev0)
+        cc = ops.composite(R, n_dev0, Sc, 1, EVAL | CLIP, lc["sigma"], eb_c, lc["color"])
         # B. fine primary (model.py:182-211) + C. per-ray surface attributes (model.py:215-227)
-        sb_f, eb_f = ops.sample_pdf(R, None, Sc, Sf, uni.spacing, uni.tan, self.sampler_pdf.histogram_padding, nears,
+        sb_f, eb_f = ops.sample_pdf(R, n_dev0, Sc, Sf, uni.spacing, uni.tan, self.sampler_pdf.histogram_padding, nears,
                                     fars, cc["weights"], sb_c, None)
-        lf = fld.evaluate_frustums(o, d, pa, eb_f)
-        cf = ops.composite(R, None, Sf, 1, EVAL | CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True)
+        lf = fld.evaluate_frustums(o, d, pa, eb_f, n_dev0)
+        cf = ops.composite(R, n_dev0, Sf, 1, EVAL | CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True,
+                           zero_accumulation=n_dev0 is not None)
         # mask, stable compaction, secondary rays, default reflect colours (model.py:222-229,240-241,267-289)
         rs = ops.reflect_setup(o, d, cf["accumulation"], cf["depth"], cf["normals"], cf["roughness"], float(self.far))
         n_dev = rs["n_masked"]
@@ -233,6 +240,58 @@ class ReflectSamplingNeRFModel(Model):
         outputs.lazy["depth_reflect_fine"] = (n_dev, crf["depth"])
         return outputs
 
+    # ------------------------------------------------------------------ empty-space skipping (occupancy.py)
+    def _cull(self, ray_bundle, marks: Optional[list] = None):
+        """Cull a flat ray bundle [R] (nears / fars set) against self.occupancy: one rsn_occupancy_cull launch over all R rays and a
+        gather of the rays through ray_index -> (the bundle with the hit rays first, the cull's outputs).  The count of hit rays
+        stays on the device.
+
+        The eval pipeline then runs on the leading rays only, and rsn_scatter_rows writes every output key back to the rays' own
+        rows.  A culled ray holds, per key:
+
+            mid_rgb_coarse, mid_rgb_fine, mid_reflect_coarse, mid_reflect_fine, diff      1 (what compositing zero weights on the
+                                                                                           white background gives)
+            accumulation_*, tint, roughness, weights_*, pred_normals_*, normals_*, n_dot_d_*   0
+            depth_*                                                                        the ray's far
+            mask                                                                           false
+
+        A hit ray holds the bits the unculled render gives it: the kernels treat rays independently.  depth_reflect_fine ([M, 1],
+        lazy) lists the reflected rays in ascending ray order as before; a culled ray is never among them.
+
+        marks: a list that receives timing events recorded at the start, after the cull and after the gather."""
+        from . import occupancy
+
+        R = ray_bundle.origins.shape[0]
+        o = ops._f32c(ray_bundle.origins.reshape(R, 3))
+        d = ops._f32c(ray_bundle.directions.reshape(R, 3))
+        nears = ops._f32c(ray_bundle.nears.reshape(R))
+        fars = ops._f32c(ray_bundle.fars.reshape(R))
+        self._mark(marks)
+        culled = occupancy.cull(self.occupancy, o, d, nears, fars)
+        culled["fars"] = fars
+        self._mark(marks)
+        compact = ray_bundle[culled["ray_index"].long()]
+        self._mark(marks)
+        return compact, culled
+
+    @staticmethod
+    def _mark(marks: Optional[list]) -> None:
+        if marks is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append(e)
+
+    @torch.no_grad()
+    def _get_outputs_eval_culled(self, ray_bundle) -> Dict[str, Tensor]:
+        """Eval-mode get_outputs with self.occupancy set: cull, one pass over the compacted rays with the device-side count, scatter."""
+        from . import occupancy
+
+        compact_rays, culled = self._cull(ray_bundle)
+        compact = self._get_outputs_eval(compact_rays, culled["n_hit"])
+        outputs = ops.LazyOutputs(occupancy.scatter_outputs(dict(compact.present()), culled, culled["fars"]))
+        outputs.lazy = compact.lazy
+        return outputs
+
     # ------------------------------------------------------------------ eval image, chunked (config.py:41; "next" row §8(f).4)
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle) -> Dict[str, Tensor]:
@@ -241,7 +300,13 @@ class ReflectSamplingNeRFModel(Model):
         (for nerfstudio's own base class too) so that EVERY CHUNK IS ENQUEUED BEFORE ANYTHING IS READ BACK: get_outputs
         issues no device-to-host read (the one output whose shape needs the reflected-ray count, depth_reflect_fine
         [M, 1], is lazy and is no image anyway; the base class's `.items()` would materialise it once per chunk), so the
-        GPU runs chunk after chunk while the host is already launching the following ones."""
+        GPU runs chunk after chunk while the host is already launching the following ones.
+
+        With self.occupancy set (occupancy.py) the whole image is culled in one launch, the chunks are cut from the compacted rays,
+        chunk i carries the device-side count clamp(n_hit - i * chunk, 0, chunk) into its primary-level launches (the trailing
+        chunks run with count 0), and every key is written back with one rsn_scatter_rows; still no device-to-host read.
+        While self.occupancy_stage_events is a list, every culled image appends its five timing events to it: start, cull done,
+        gather done, chunks done, scatter done (tools/occupancy_report.py)."""
         chunk = self.config.eval_num_rays_per_chunk
         image_shape = camera_ray_bundle.origins.shape[:-1]
         n = 1
@@ -249,6 +314,17 @@ class ReflectSamplingNeRFModel(Model):
             n *= int(s_)
         lists: Dict[str, list] = {}
         n_chunks = 0
+        culled = counts = marks = None
+        if getattr(self, "occupancy", None) is not None:
+            if isinstance(getattr(self, "occupancy_stage_events", None), list):
+                marks = []
+                self.occupancy_stage_events.append(marks)
+            flat = camera_ray_bundle.get_row_major_sliced_ray_bundle(0, n)
+            if self.collider is not None:
+                flat = self.collider(flat)
+            camera_ray_bundle, culled = self._cull(flat, marks)
+            starts = torch.arange(0, max(n, 1), chunk, device=culled["n_hit"].device, dtype=torch.int32)
+            counts = (culled["n_hit"] - starts).clamp_(0, chunk).to(torch.int32)
         # Small chunks (the reference's 1024 rays) leave the GPU with ramps, tails and a dozen 10-us launches per 3 ms of field
         # kernels: consecutive chunks are independent, so they alternate between two side streams and one chunk's small
         # launches / last partial round of tiles run beside the other's field kernels.
@@ -268,7 +344,7 @@ class ReflectSamplingNeRFModel(Model):
             ctx = torch.cuda.stream(side[n_chunks % len(side)]) if side is not None else contextlib.nullcontext()
             n_chunks += 1
             with ctx:
-                out = self.forward(rb)
+                out = self.forward(rb) if counts is None else self._get_outputs_eval(rb, counts[n_chunks - 1:n_chunks])
             present = out.present() if hasattr(out, "present") else out.items()
             for k, v in present:
                 if isinstance(v, Tensor) and v.shape[:1] == (len(rb),):
@@ -280,6 +356,20 @@ class ReflectSamplingNeRFModel(Model):
                 for v in vs:
                     v.record_stream(main)
         # per-ray outputs only: a key that is not [rays, ...] in every chunk (depth_reflect_fine is [M,1]) is no image
+        if culled is not None:
+            from . import occupancy
+
+            self._mark(marks)
+            joined: Dict[int, Tensor] = {}  # normals_* are the pred_normals_* tensors: joined and written back once
+            compact = {}
+            for k, v in lists.items():
+                if len(v) == n_chunks and k != "depth_reflect_fine":
+                    if id(v[0]) not in joined:
+                        joined[id(v[0])] = torch.cat(v)
+                    compact[k] = joined[id(v[0])]
+            full = occupancy.scatter_outputs(compact, culled, culled["fars"])
+            self._mark(marks)
+            return {k: v.view(*image_shape, *v.shape[1:]) for k, v in full.items()}
         return {k: torch.cat(v).view(*image_shape, *v[0].shape[1:]) for k, v in lists.items()
                 if len(v) == n_chunks and k != "depth_reflect_fine"}
 

@@ -407,11 +407,15 @@ DEFAULT_CHUNK = 4096  # rays per eval chunk: the kernels are at their best from 
 
 def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx: float, fy: float, cx: float, cy: float,
                       channels: Sequence[str] = DEFAULT_CHANNELS, depth_range: Optional[Tuple[float, float]] = None,
-                      mma: str = "f32", chunk: int = DEFAULT_CHUNK, tiles: bool = False, device="cuda:0", model_config=None) -> dict:
+                      mma: str = "f32", chunk: int = DEFAULT_CHUNK, tiles: bool = False, device="cuda:0", model_config=None,
+                      occupancy: Optional[dict] = None) -> dict:
     """Render the poses c2w [F,3,4] from a checkpoint (a step-*.ckpt, or the newest of a run directory) into out_dir: the tiled
     panel of every frame as out_dir/panel/0000.png ..., or with `tiles` one image per channel as out_dir/<channel>/0000.png ...,
     and out_dir/frames.json (checkpoint, step, size, intrinsics, channels in tile order, depth range, mma, chunk, and per frame
     its file name(s) and c2w).  Existing files of these names are replaced; nothing else in out_dir is touched.
+    occupancy: None, or {"resolution", "sigma", "dilate", "bounds" (None: occupancy.segment_bounds of the path)}: the frames are
+    rendered with empty-space skipping and frames.json gains an "occupancy" entry (settings, box, occupied share of cells, culled
+    share of rays; the latter read from the device once, after the last frame).
     -> the dict written to frames.json plus {"seconds": wall time of the frames, "out": out_dir}."""
     from PIL import Image
 
@@ -428,6 +432,10 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
     if depth_range is None:
         depth_range = (model.config.collider_params["near_plane"], model.config.collider_params["far_plane"])
     poses = np.asarray(c2w, dtype=np.float32)[:, :3, :4]
+    if occupancy is not None:
+        from .occupancy import attach_occupancy
+
+        attach_occupancy(model, occupancy, poses, height, width, fx, fy, cx, cy)
     folders = list(channels) if tiles else ["panel"]
     for f in folders:
         os.makedirs(os.path.join(out_dir, f), exist_ok=True)
@@ -450,6 +458,8 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
             "cx": float(cx), "cy": float(cy), "channels": list(channels), "tiles": bool(tiles),
             "depth_range": [float(depth_range[0]), float(depth_range[1])], "mma": mma, "chunk": int(chunk),
             "frames": [{"files": f, "c2w": poses[i].astype(np.float64).tolist()} for i, f in enumerate(files)]}
+    if occupancy is not None:
+        meta["occupancy"] = model.occupancy.describe()
     tmp = os.path.join(out_dir, "frames.json.tmp")
     with open(tmp, "w") as fh:
         json.dump(meta, fh, indent=1)

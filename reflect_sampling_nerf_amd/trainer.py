@@ -4,6 +4,7 @@
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
+    (eval and render: [--skip-empty [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
 
 `train` is the reference's `ns-train reflect-sampling-nerf --data DIR` loop on this package's own pieces: the reference
 Model config (ReflectSamplingNeRFModelConfig defaults), RayDataManager batches (1024 rays, reflect_sampling_nerf_config.py:36-41),
@@ -30,6 +31,11 @@ transforms-format file, optionally with poses interpolated in between.  Every fr
 side -- the final colour, the direct pass, diffuse colour, tint, roughness, predicted normals, turbo-coloured depth, accumulation,
 the reflection mask -- or, with --tiles, one PNG per channel; frames.json records the cameras.  There is no video encoder here:
 the frames are the product.
+
+`eval` and `render` take `--skip-empty`: an occupancy grid of the field's density is built once (occupancy.py), and the rays whose
+[near, far] segment crosses no occupied cell are not evaluated; they get the white background.  The grid's defaults (sigma 0.01,
+one cell of dilation) are starting points from one experiment on a briefly trained field, not measured against a scene.  The
+output JSON then carries an "occupancy" entry: the settings, the box, the occupied share of cells and the culled share of rays.
 """
 from __future__ import annotations
 
@@ -52,6 +58,47 @@ RUN_STATE_KEY = "rsn_run"  # the trainer's own fifth checkpoint key; nerfstudio'
 RUN_STATE_VERSION = 1
 RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
 LPIPS_NOTE = "fine_lpips not computed: LPIPS needs pretrained network weights that are not shipped with this package"
+
+
+OCCUPANCY_SUBFLAGS = ("occupancy_resolution", "occupancy_sigma", "occupancy_dilate", "occupancy_bounds")
+
+
+def _add_occupancy_flags(p: argparse.ArgumentParser) -> None:
+    from .occupancy import DEFAULT_DILATE, DEFAULT_RESOLUTION, DEFAULT_SIGMA
+
+    p.add_argument("--skip-empty", action="store_true",
+                   help="cull the rays that cross no occupied cell of an occupancy grid built from the field (they get the white background)")
+    p.add_argument("--occupancy-resolution", type=int, default=None, metavar="N", help=f"grid vertices per axis (default {DEFAULT_RESOLUTION})")
+    p.add_argument("--occupancy-sigma", type=float, default=None, metavar="S",
+                   help=f"a cell is occupied when a corner has density >= S (default {DEFAULT_SIGMA:g}: a starting point from one experiment "
+                        "on a field trained for 2000 steps, not measured against any scene; pick it per scene)")
+    p.add_argument("--occupancy-dilate", type=int, choices=(0, 1, 2), default=None, metavar="D",
+                   help=f"grow the occupied cells by D cells, 0..2 (default {DEFAULT_DILATE}: a starting point from the same experiment)")
+    p.add_argument("--occupancy-bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                   help="box of the grid (default: a box around the [near, far] segments of the cameras' rays); what it does not cover counts as occupied")
+
+
+def resolve_occupancy_args(ap: argparse.ArgumentParser, args) -> Optional[dict]:
+    """The occupancy settings of an `eval` / `render` command line: None without --skip-empty (the sub-flags are an error then), else
+    {"resolution", "sigma", "dilate", "bounds" (None: from the cameras)}."""
+    from .occupancy import DEFAULT_DILATE, DEFAULT_RESOLUTION, DEFAULT_SIGMA
+
+    if not getattr(args, "skip_empty", False):
+        given = ["--" + f.replace("_", "-") for f in OCCUPANCY_SUBFLAGS if getattr(args, f, None) is not None]
+        if given:
+            ap.error(f"{args.command}: {' '.join(given)} need(s) --skip-empty")
+        return None
+    res = DEFAULT_RESOLUTION if args.occupancy_resolution is None else args.occupancy_resolution
+    sigma = DEFAULT_SIGMA if args.occupancy_sigma is None else args.occupancy_sigma
+    if res < 2 or res ** 3 > 2 ** 27:
+        ap.error(f"{args.command}: --occupancy-resolution {res}: need 2 <= N <= 512")
+    if not math.isfinite(sigma):
+        ap.error(f"{args.command}: --occupancy-sigma {sigma}: need a finite value")
+    b = args.occupancy_bounds
+    if b is not None and not (all(math.isfinite(x) for x in b) and all(b[3 + a] > b[a] for a in range(3))):
+        ap.error(f"{args.command}: --occupancy-bounds needs X0 Y0 Z0 X1 Y1 Z1 with every upper bound above its lower one")
+    return {"resolution": int(res), "sigma": float(sigma), "dilate": DEFAULT_DILATE if args.occupancy_dilate is None else args.occupancy_dilate,
+            "bounds": None if b is None else tuple(float(x) for x in b)}
 
 
 def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
@@ -84,6 +131,7 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ev.add_argument("--out", default="metrics.json", help="output JSON")
     ev.add_argument("--save-images", default=None, help="directory for rendered ground truth | coarse | fine panels")
     ev.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    _add_occupancy_flags(ev)
     ex = sub.add_parser("export-mesh", help="write the iso-surface of a checkpoint's density as a coloured triangle mesh (PLY)")
     ex.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
     ex.add_argument("--out", required=True, help="output file (binary little-endian PLY)")
@@ -123,6 +171,7 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     rn.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels (default f32)")
     rn.add_argument("--chunk", type=int, default=DEFAULT_CHUNK, help=f"rays per eval chunk (default {DEFAULT_CHUNK})")
     rn.add_argument("--tiles", action="store_true", help="one PNG per channel and frame instead of the tiled panel")
+    _add_occupancy_flags(rn)
     return ap
 
 
@@ -399,9 +448,10 @@ def _white(image: torch.Tensor) -> torch.Tensor:
 
 
 def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Optional[str] = None, device="cuda:0",
-             model_config=None) -> dict:
+             model_config=None, occupancy: Optional[dict] = None) -> dict:
     """Score the checkpoint (a file, or the latest of a run directory) on every view of `scene` (a data.BlenderScene); -> ns-eval-
-    shaped dict."""
+    shaped dict.  occupancy: None, or the settings of resolve_occupancy_args: the views are rendered with empty-space skipping and
+    the dict gains an "occupancy" entry."""
     from . import metrics
     from .data import RayDataManager
 
@@ -411,6 +461,10 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     model.config.eval_num_rays_per_chunk = EVAL_CHUNK
     dm = RayDataManager(scene, dev)
     n = scene.num_images if max_images is None else min(int(max_images), scene.num_images)
+    if occupancy is not None:
+        from .occupancy import attach_occupancy
+
+        attach_occupancy(model, occupancy, scene.c2w[:n], scene.height, scene.width, scene.fx, scene.fy, scene.cx, scene.cy)
     if save_images:
         os.makedirs(save_images, exist_ok=True)
     per_image = []
@@ -437,9 +491,12 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         v = np.array([p[k] for p in per_image], dtype=np.float64)
         results[k] = float(v.mean())
         results[k + "_std"] = float(v.std(ddof=1)) if len(v) > 1 else 0.0  # torch.std_mean (ns-eval): unbiased
-    return {"experiment_name": os.path.basename(os.path.dirname(os.path.abspath(ckpt))), "method_name": METHOD_NAME,
-            "checkpoint": ckpt, "step": step, "results": results, "not_computed": {"fine_lpips": LPIPS_NOTE},
-            "per_image": per_image}
+    res = {"experiment_name": os.path.basename(os.path.dirname(os.path.abspath(ckpt))), "method_name": METHOD_NAME,
+           "checkpoint": ckpt, "step": step, "results": results, "not_computed": {"fine_lpips": LPIPS_NOTE},
+           "per_image": per_image}
+    if occupancy is not None:
+        res["occupancy"] = model.occupancy.describe()
+    return res
 
 
 # ------------------------------------------------------------------------------------------------ CLI
@@ -450,6 +507,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
     cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
+    occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
     if not torch.cuda.is_available():
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
@@ -477,13 +535,13 @@ def main(argv=None) -> int:
         res = render.render_checkpoint(args.ckpt, args.out, cameras["c2w"], cameras["height"], cameras["width"], cameras["fx"],
                                        cameras["fy"], cameras["cx"], cameras["cy"], channels=args.channels,
                                        depth_range=None if args.depth_range is None else tuple(args.depth_range), mma=args.mma,
-                                       chunk=args.chunk, tiles=args.tiles)
+                                       chunk=args.chunk, tiles=args.tiles, occupancy=occupancy)
         n, sec = len(res["frames"]), res["seconds"]
         print(f"{res['checkpoint']} (step {res['step']}): {n} frames {res['width']} x {res['height']} of {' '.join(res['channels'])}; "
               f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
         return 0
     scene = load_blender_split(args.data, args.split, args.scale_factor)
-    res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images)
+    res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images, occupancy=occupancy)
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=2)
     r = res["results"]
