@@ -744,6 +744,51 @@ int rsn_occupancy_cull(int32_t n_rays, const float* origins, const float* direct
 int rsn_scatter_rows(int32_t n_rows, const int32_t* n_dev, const int32_t* ray_index, const float* src, int32_t row_floats,
                      float fill, float* out, void* stream);
 
+/* ---- occupancy, per sample: evaluate the field only on the samples of a level that lie in occupied cells (additive to ABI 18).
+ *
+ * A level has n_rays rays of n_samples intervals, euclid_bins [R,S+1]; sample i of ray r is point p = r*S + i, as in
+ * rsn_field_forward_frustum.  rsn_occupancy_compact_samples decides which samples are live and lists them as "rays" of one sample
+ * each, which rsn_field_forward_frustum evaluates with n_samples = 1, euclid_bins = bins_c and n_dev = n_live; rsn_scatter_level
+ * writes the results back to their [R,S] slots.  The grid arguments (nx .. outside_occupied) are those of rsn_occupancy_cull.
+ *
+ * rsn_occupancy_samples_workspace_bytes: HOST only; 0 with a message when n_rays < 0, n_samples < 1 or n_rays * n_samples * 3 does
+ * not fit in int32 (rsn_occupancy_compact_samples refuses the same shapes with RSN_ERR_INVALID_ARGUMENT).
+ *
+ * rsn_occupancy_compact_samples, the rules:
+ *  - live[p] (uint8 [R*S]) = 0 for r >= *n_dev (n_dev NULL: n_rays; clamped to 0 .. n_rays); the inputs of those rays are never read.
+ *  - Otherwise live[p] = 1 when at least one of these holds, else 0:
+ *      (a) the sub-segment o + t d, t in [bins[r,i], bins[r,i+1]], is a hit by exactly the predicate of rsn_occupancy_cull: the same
+ *          1e-3-cell band, the same outside_occupied, and the same "never skip what cannot be reasoned about" clauses, which cover a
+ *          non-finite origin, direction or bin and bins[r,i+1] < bins[r,i];
+ *      (b) the cone is wider than the grid's margin: bins[r,i+1] * |d| * sqrt(pixel_area[r] / pi) > max_radius, evaluated in fp64
+ *          (sqrt(pixel_area) / sqrt(pi) is the cone's radius at unit distance; a pixel_area below 0 never satisfies it);
+ *      (c) pixel_area[r] is not finite.
+ *    max_radius = +inf switches (b) off; NaN is RSN_ERR_INVALID_ARGUMENT.
+ *  - n_live (device int32) = the number of live samples.
+ *  - sample_index (int32 [R*S]) is a permutation of 0 .. R*S-1: the live samples in ascending order, then the others in ascending
+ *    order -- the contract of ray_index: stable, no atomics, deterministic.
+ *  - For j < *n_live, row j of origins_c [R*S,3], directions_c [R*S,3], pixel_area_c [R*S] and bins_c [R*S,2] (8-byte aligned)
+ *    holds the origin, direction and pixel area of the ray of sample sample_index[j] and its (t_i, t_i+1), bit for bit.  Rows at and
+ *    past *n_live are left unwritten.
+ *  - n_rays == 0 launches nothing and sets *n_live = 0.  workspace: device memory of rsn_occupancy_samples_workspace_bytes bytes,
+ *    contents irrelevant.  No allocation, no synchronisation, no host read.
+ *
+ * rsn_scatter_level: one launch for every non-NULL member of src (rows of 1 or 3 floats, n_points rows each): row j of a member of
+ * src goes to row sample_index[j] of the same member of dst for j < *n_live (clamped to 0 .. n_points), and every row of dst that
+ * belongs to no live sample is written as zeros -- a zero sigma gives a zero weight, so no other member of a skipped sample reaches
+ * a ray's result.  With sample_index a permutation every row of dst is written exactly once; an entry outside 0 .. n_points-1
+ * writes nothing; rows of src at and past *n_live are never read.  A member set in one struct and NULL in the other is
+ * RSN_ERR_INVALID_ARGUMENT. */
+size_t rsn_occupancy_samples_workspace_bytes(int32_t n_rays, int32_t n_samples);
+int rsn_occupancy_compact_samples(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* origins,
+                                  const float* directions, const float* pixel_area, const float* euclid_bins, int32_t nx, int32_t ny,
+                                  int32_t nz, const float* origin3, const float* spacing3, const uint32_t* bits,
+                                  int32_t outside_occupied, float max_radius, uint8_t* live, int32_t* n_live, int32_t* sample_index,
+                                  float* origins_c, float* directions_c, float* pixel_area_c, float* bins_c, int32_t* workspace,
+                                  void* stream);
+int rsn_scatter_level(int32_t n_points, const int32_t* n_live, const int32_t* sample_index, const rsn_field_outputs* src,
+                      const rsn_field_outputs* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,11 @@ _SIGNATURES = {
                                      C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "rsn_scatter_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, _fp, C.c_int32, C.c_float, _fp, C.c_void_p]),
+    "rsn_occupancy_samples_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rsn_occupancy_compact_samples": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_float,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]),
+    "rsn_scatter_level": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(FieldOutputs), C.POINTER(FieldOutputs), C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

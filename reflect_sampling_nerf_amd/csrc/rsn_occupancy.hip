@@ -10,6 +10,11 @@
 //           accumulated.  The compaction is the two-pass one of rsn_reflect_setup: per-block counts, then every block sums the
 //           counts in front of it (and all of them, for the culled rays' base) and places its rays by wave ballots.  No atomics.
 //   scatter one lane per float of the compacted rows.
+//   samples the same decision per SAMPLE of a level (rsn_occupancy_compact_samples): one lane per sub-segment [t_i, t_i+1] through
+//           occ_ray_hits -- the DDA then spans one to three cells, and R*S lanes fill the machine -- plus the footprint rule; block
+//           counts, one workgroup that turns them into offsets (and the total), then every block places its samples by wave
+//           ballots and copies a live sample's ray and interval to its compact row.  rsn_scatter_level writes every member of a
+//           level back in one launch, zeros in the rows of the skipped samples.  No atomics.
 #include "rsn_common.h"
 
 #include <math.h>
@@ -273,6 +278,240 @@ extern "C" int rsn_scatter_rows(int32_t n_rows, const int32_t* n_dev, const int3
   const unsigned blocks = (unsigned)(want < RSN_SCATTER_MAX_BLOCKS ? want : RSN_SCATTER_MAX_BLOCKS);
   hipLaunchKernelGGL(rsn_scatter_rows_kernel, dim3(blocks), dim3(RSN_OCC_BLOCK), 0, (hipStream_t)stream, n_rows, n_dev, ray_index,
                      src, row_floats, fill, out);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+// -------------------------------------------------------------------------------------------------------------------- samples
+#define RSN_OCC_PI 3.141592653589793
+
+__device__ __forceinline__ int occ_count(const int* __restrict__ n_dev, int n) {
+  if (!n_dev) return n;
+  const int nd = *n_dev;
+  return nd < 0 ? 0 : (nd < n ? nd : n);
+}
+
+// live[p] of sample p = r*S + i, and the number of live samples of every block
+__global__ __launch_bounds__(RSN_OCC_BLOCK) void rsn_occupancy_mark_kernel(
+    int R, const int* __restrict__ n_dev, int S, const float* __restrict__ origins, const float* __restrict__ directions,
+    const float* __restrict__ pixel_area, const float* __restrict__ bins, const OccGrid g, const uint32_t* __restrict__ bits,
+    int outside_occupied, float max_radius, uint8_t* __restrict__ live, int* __restrict__ block_counts) {
+  __shared__ int s_wave_tot[RSN_OCC_BLOCK / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int N = R * S;  // the launcher bounds it
+  const int count = occ_count(n_dev, R);
+  const int p = blockIdx.x * RSN_OCC_BLOCK + tid;
+  bool l = false;
+  if (p < N) {
+    const int r = p / S, i = p - r * S;
+    if (r < count) {  // the rays behind the count are never read
+      float o3[3], d3[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) { o3[a] = origins[(size_t)r * 3 + a]; d3[a] = directions[(size_t)r * 3 + a]; }
+      const float t0 = bins[(size_t)r * (S + 1) + i], t1 = bins[(size_t)r * (S + 1) + i + 1];
+      const float pa = pixel_area[r];
+      const double len = sqrt((double)d3[0] * d3[0] + (double)d3[1] * d3[1] + (double)d3[2] * d3[2]);
+      // the cone's radius at the far end of the interval against the grid's margin; a NaN on the left compares false, and
+      // whatever made it (a non-finite t or d) is flagged by occ_ray_hits
+      l = !occ_finite(pa) || (double)t1 * len * sqrt((double)pa / RSN_OCC_PI) > (double)max_radius;
+      l = l || occ_ray_hits(g, o3, d3, t0, t1, bits, outside_occupied != 0);
+    }
+    live[p] = l ? 1 : 0;
+  }
+  const unsigned long long bal = __ballot(l);
+  if (lane == 0) s_wave_tot[wid] = __builtin_popcountll(bal);
+  __syncthreads();
+  if (tid == 0) {
+    int t = 0;
+#pragma unroll
+    for (int wv = 0; wv < RSN_OCC_BLOCK / 64; ++wv) t += s_wave_tot[wv];
+    block_counts[blockIdx.x] = t;
+  }
+}
+
+// One workgroup: counts[b] -> the number of live samples in the blocks in front of b (in place), their total -> *n_live.
+__global__ __launch_bounds__(RSN_OCC_BLOCK) void rsn_occupancy_scan_kernel(int n_blocks, int* __restrict__ counts, int* __restrict__ n_live) {
+  __shared__ int s_wave_tot[RSN_OCC_BLOCK / 64];
+  __shared__ int s_carry;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (tid == 0) s_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n_blocks; base += RSN_OCC_BLOCK) {  // the bound is the same in every lane
+    const int j = base + tid;
+    const int v = j < n_blocks ? counts[j] : 0;
+    int x = v;  // inclusive scan of the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int y = __shfl_up(x, off, 64);
+      if (lane >= off) x += y;
+    }
+    if (lane == 63) s_wave_tot[wid] = x;
+    __syncthreads();
+    int wave_off = 0, tot = 0;
+#pragma unroll
+    for (int wv = 0; wv < RSN_OCC_BLOCK / 64; ++wv) {
+      const int t = s_wave_tot[wv];
+      if (wv < wid) wave_off += t;
+      tot += t;
+    }
+    const int carry = s_carry;
+    if (j < n_blocks) counts[j] = carry + wave_off + x - v;
+    __syncthreads();  // every lane has read s_carry and s_wave_tot
+    if (tid == 0) s_carry = carry + tot;
+    __syncthreads();
+  }
+  if (tid == 0) *n_live = s_carry;
+}
+
+__global__ __launch_bounds__(RSN_OCC_BLOCK) void rsn_occupancy_compact_kernel(
+    int R, int S, const float* __restrict__ origins, const float* __restrict__ directions, const float* __restrict__ pixel_area,
+    const float* __restrict__ bins, const uint8_t* __restrict__ live, const int* __restrict__ block_offsets,
+    const int* __restrict__ n_live, int* __restrict__ sample_index, float* __restrict__ origins_c, float* __restrict__ directions_c,
+    float* __restrict__ pixel_area_c, float2* __restrict__ bins_c) {
+  __shared__ int s_wave_tot[RSN_OCC_BLOCK / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int N = R * S;
+  const int p = blockIdx.x * RSN_OCC_BLOCK + tid;
+  const bool l = p < N && live[p] != 0;
+  const unsigned long long bal = __ballot(l);
+  const int in_wave = __builtin_popcountll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) s_wave_tot[wid] = __builtin_popcountll(bal);
+  __syncthreads();
+  int wave_off = 0;
+#pragma unroll
+  for (int wv = 0; wv < RSN_OCC_BLOCK / 64; ++wv)
+    if (wv < wid) wave_off += s_wave_tot[wv];
+  if (p >= N) return;
+  const int before = block_offsets[blockIdx.x] + wave_off + in_wave;  // live samples with a smaller index than p: 0 .. p
+  if (!l) {
+    sample_index[*n_live + (p - before)] = p;  // total + the skipped samples in front of p: below N
+    return;
+  }
+  sample_index[before] = p;
+  const int r = p / S, i = p - r * S;
+  const size_t j = (size_t)before;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {  // consecutive live lanes write consecutive rows
+    origins_c[j * 3 + a] = origins[(size_t)r * 3 + a];
+    directions_c[j * 3 + a] = directions[(size_t)r * 3 + a];
+  }
+  pixel_area_c[j] = pixel_area[r];
+  bins_c[j] = make_float2(bins[(size_t)r * (S + 1) + i], bins[(size_t)r * (S + 1) + i + 1]);
+}
+
+static bool occ_samples_ok(int64_t n_rays, int64_t n_samples) {  // n_rays * n_samples * 3 <= INT32_MAX, without forming the product
+  const int64_t most = (int64_t)INT32_MAX / 3;
+  return n_rays >= 0 && n_samples >= 1 && n_samples <= most && n_rays <= most / n_samples;
+}
+
+extern "C" size_t rsn_occupancy_samples_workspace_bytes(int32_t n_rays, int32_t n_samples) {
+  if (!occ_samples_ok(n_rays, n_samples)) {
+    rsn_set_error("occupancy_samples: n_rays=%d n_samples=%d: need n_rays >= 0, n_samples >= 1 and n_rays*n_samples*3 < 2^31", n_rays,
+                  n_samples);
+    return 0;
+  }
+  const int64_t n = (int64_t)n_rays * n_samples;
+  return (size_t)((n + RSN_OCC_BLOCK - 1) / RSN_OCC_BLOCK + 1) * sizeof(int32_t);
+}
+
+extern "C" int rsn_occupancy_compact_samples(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* origins,
+                                             const float* directions, const float* pixel_area, const float* euclid_bins, int32_t nx,
+                                             int32_t ny, int32_t nz, const float* origin3, const float* spacing3, const uint32_t* bits,
+                                             int32_t outside_occupied, float max_radius, uint8_t* live, int32_t* n_live,
+                                             int32_t* sample_index, float* origins_c, float* directions_c, float* pixel_area_c,
+                                             float* bins_c, int32_t* workspace, void* stream) {
+  RSN_REQUIRE(occ_samples_ok(n_rays, n_samples), RSN_ERR_INVALID_ARGUMENT,
+              "occupancy_compact_samples: n_rays=%d n_samples=%d: need n_rays >= 0, n_samples >= 1 and n_rays*n_samples*3 < 2^31", n_rays,
+              n_samples);
+  RSN_REQUIRE(occ_dims_ok(nx, ny, nz), RSN_ERR_INVALID_ARGUMENT,
+              "occupancy_compact_samples: grid %d x %d x %d: need every dimension >= 2 and nx*ny*nz <= 2^27", nx, ny, nz);
+  RSN_REQUIRE(origin3 && spacing3, RSN_ERR_INVALID_ARGUMENT, "occupancy_compact_samples: origin3 or spacing3 is NULL");
+  OccGrid g;
+  g.cx = nx - 1; g.cy = ny - 1; g.cz = nz - 1;
+  for (int a = 0; a < 3; ++a) {
+    RSN_REQUIRE(isfinite(origin3[a]) && isfinite(spacing3[a]) && spacing3[a] > 0.0f, RSN_ERR_INVALID_ARGUMENT,
+                "occupancy_compact_samples: axis %d: origin %g spacing %g: need finite values and spacing > 0", a, (double)origin3[a],
+                (double)spacing3[a]);
+    g.org[a] = (double)origin3[a];
+    g.inv[a] = 1.0 / (double)spacing3[a];
+  }
+  RSN_REQUIRE(!isnan(max_radius), RSN_ERR_INVALID_ARGUMENT, "occupancy_compact_samples: max_radius is NaN (+inf switches the rule off)");
+  RSN_REQUIRE(n_live, RSN_ERR_INVALID_ARGUMENT, "occupancy_compact_samples: n_live is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_rays == 0) {
+    RSN_HIP(hipMemsetAsync(n_live, 0, sizeof(int32_t), st));
+    return RSN_OK;
+  }
+  RSN_REQUIRE(origins && directions && pixel_area && euclid_bins && bits && live && sample_index && origins_c && directions_c &&
+                  pixel_area_c && bins_c && workspace,
+              RSN_ERR_INVALID_ARGUMENT, "occupancy_compact_samples: a pointer is NULL");
+  RSN_REQUIRE(((uintptr_t)bins_c & 7u) == 0, RSN_ERR_INVALID_ARGUMENT, "occupancy_compact_samples: bins_c must be 8-byte aligned");
+  const int64_t n = (int64_t)n_rays * n_samples;
+  const unsigned blocks = (unsigned)((n + RSN_OCC_BLOCK - 1) / RSN_OCC_BLOCK);
+  hipLaunchKernelGGL(rsn_occupancy_mark_kernel, dim3(blocks), dim3(RSN_OCC_BLOCK), 0, st, n_rays, n_dev, n_samples, origins, directions,
+                     pixel_area, euclid_bins, g, bits, outside_occupied, max_radius, live, workspace);
+  hipLaunchKernelGGL(rsn_occupancy_scan_kernel, dim3(1), dim3(RSN_OCC_BLOCK), 0, st, (int)blocks, workspace, n_live);
+  hipLaunchKernelGGL(rsn_occupancy_compact_kernel, dim3(blocks), dim3(RSN_OCC_BLOCK), 0, st, n_rays, n_samples, origins, directions,
+                     pixel_area, euclid_bins, live, workspace, n_live, sample_index, origins_c, directions_c, pixel_area_c,
+                     (float2*)bins_c);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+// One launch for every member of a level: compact row j -> row sample_index[j], zeros in the rows of the skipped samples.
+#define RSN_LEVEL_MEMBERS 9
+struct OccLevel {
+  const float* src[RSN_LEVEL_MEMBERS];
+  float* dst[RSN_LEVEL_MEMBERS];
+  int wide[RSN_LEVEL_MEMBERS];  // rows of three floats (else of one)
+};
+
+__global__ __launch_bounds__(RSN_OCC_BLOCK) void rsn_scatter_level_kernel(int n, const int* __restrict__ n_live,
+                                                                          const int* __restrict__ sample_index, const OccLevel L) {
+  const int nl = occ_count(n_live, n);
+  for (int64_t j = (int64_t)blockIdx.x * RSN_OCC_BLOCK + threadIdx.x; j < n; j += (int64_t)gridDim.x * RSN_OCC_BLOCK) {
+    const int p = sample_index[j];
+    if ((unsigned)p >= (unsigned)n) continue;  // not a row of dst: skipped rather than written through
+    const bool l = j < nl;                     // rows of src at and past the count are never read
+#pragma unroll
+    for (int m = 0; m < RSN_LEVEL_MEMBERS; ++m) {
+      if (!L.dst[m]) continue;  // the same in every lane
+      if (L.wide[m]) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) L.dst[m][(size_t)p * 3 + c] = l ? L.src[m][(size_t)j * 3 + c] : 0.0f;
+      } else {
+        L.dst[m][p] = l ? L.src[m][j] : 0.0f;
+      }
+    }
+  }
+}
+
+extern "C" int rsn_scatter_level(int32_t n_points, const int32_t* n_live, const int32_t* sample_index, const rsn_field_outputs* src,
+                                 const rsn_field_outputs* dst, void* stream) {
+  RSN_REQUIRE(n_points >= 0 && (int64_t)n_points * 3 <= (int64_t)INT32_MAX, RSN_ERR_INVALID_ARGUMENT,
+              "scatter_level: n_points=%d: need 0 <= n_points and n_points*3 < 2^31", n_points);
+  RSN_REQUIRE(src && dst, RSN_ERR_INVALID_ARGUMENT, "scatter_level: src or dst is NULL");
+  float* const s[RSN_LEVEL_MEMBERS] = {src->sigma, src->color, src->pred_normals, src->n_dot_d, src->diff, src->tint, src->roughness,
+                                       src->raw_density, src->raw_roughness};
+  float* const d[RSN_LEVEL_MEMBERS] = {dst->sigma, dst->color, dst->pred_normals, dst->n_dot_d, dst->diff, dst->tint, dst->roughness,
+                                       dst->raw_density, dst->raw_roughness};
+  static const int wide[RSN_LEVEL_MEMBERS] = {0, 1, 1, 0, 1, 1, 0, 0, 0};
+  OccLevel L;
+  int members = 0;
+  for (int m = 0; m < RSN_LEVEL_MEMBERS; ++m) {
+    RSN_REQUIRE((s[m] != nullptr) == (d[m] != nullptr), RSN_ERR_INVALID_ARGUMENT,
+                "scatter_level: member %d is set in one of src / dst and NULL in the other", m);
+    L.src[m] = s[m];
+    L.dst[m] = d[m];
+    L.wide[m] = wide[m];
+    members += s[m] != nullptr;
+  }
+  if (n_points == 0 || members == 0) return RSN_OK;
+  RSN_REQUIRE(n_live && sample_index, RSN_ERR_INVALID_ARGUMENT, "scatter_level: n_live or sample_index is NULL");
+  const int64_t want = ((int64_t)n_points + RSN_OCC_BLOCK - 1) / RSN_OCC_BLOCK;
+  const unsigned blocks = (unsigned)(want < RSN_SCATTER_MAX_BLOCKS ? want : RSN_SCATTER_MAX_BLOCKS);
+  hipLaunchKernelGGL(rsn_scatter_level_kernel, dim3(blocks), dim3(RSN_OCC_BLOCK), 0, (hipStream_t)stream, n_points, n_live,
+                     sample_index, L);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

@@ -5,6 +5,8 @@ cell (rsn_occupancy_build / rsn_occupancy_cull / rsn_scatter_rows of include/rsn
                        `dilate` cells)
     segment_bounds     a box that holds the [near, far] segments of every ray of a set of pinhole cameras
     cull / scatter_rows   the two launches around the model's eval pipeline
+    mark_and_compact / scatter_level   the same per SAMPLE of a level (rsn_occupancy_compact_samples / rsn_scatter_level): the
+                       field is evaluated only on the samples whose interval crosses an occupied cell
 
 `model.occupancy = grid` turns it on for the eval-mode get_outputs and get_outputs_for_camera_ray_bundle of
 ReflectSamplingNeRFModel (None, the default, leaves that path exactly as it is; training never uses the grid).  Nothing here reads
@@ -13,6 +15,12 @@ the device: the number of hit rays stays in device memory and the later launches
 The defaults (sigma 0.01, one cell of dilation) are starting points from ONE experiment on a field trained for 2000 steps; they
 have not been measured against a scene.  What the grid's box does not cover counts as occupied by default, so a box that is too
 small costs speed, never correctness.
+
+`model.occupancy_samples = True` (off by default; needs the grid) adds the per-sample decision: every level of the eval pipeline
+goes through Field.evaluate_frustums_skipping.  A skipped sample gets sigma 0, hence weight 0.  A sample is kept, whatever cells it
+crosses, when its cone is wider than sample_max_radius(grid) = max(dilate, 1) * min(spacing): dilation grew the occupied region by
+that many cells, so a Gaussian narrower than the margin that sits in an unmarked cell has its bulk outside every above-threshold
+cell.  That margin is a DESIGN RULE, reasoned and not measured: like sigma and the dilation it has not been tuned against a scene.
 """
 from __future__ import annotations
 
@@ -30,6 +38,13 @@ DEFAULT_RESOLUTION = 128
 DEFAULT_SIGMA = 0.01   # a starting point, not measured against any scene
 DEFAULT_DILATE = 1     # likewise
 BOUNDS_LATTICE = 33    # image-plane points per axis that segment_bounds shoots rays through
+LEVELS = ("coarse", "fine", "reflect_coarse", "reflect_fine")  # level_id of the per-sample counters
+
+
+def sample_max_radius(grid) -> float:
+    """The widest cone radius a sample may have and still be skipped: the grid's dilation margin, max(dilate, 1) cells of the
+    smallest spacing.  A design rule, not a measured value (see the module's docstring)."""
+    return float(max(grid.dilate, 1)) * float(np.min(grid.spacing))
 
 
 class OccupancyGrid:
@@ -54,6 +69,11 @@ class OccupancyGrid:
         self._spacing3 = (C.c_float * 3)(*[float(x) for x in self.spacing])
         self.rays_seen = 0
         self.hits_dev = torch.zeros(1, device=bits.device, dtype=torch.int64)
+        # per-sample skipping, one entry per level (LEVELS): the sample slots its launches covered -- rows behind a device-side
+        # count included, which are never live -- and, per stream that ran them, the live samples among them
+        self.samples_seen = [0, 0, 0, 0]
+        self._samples_live: Dict[int, Tensor] = {}
+        self.sample_stage_events = None  # a list: every evaluate_frustums_skipping appends (level, [4 events]) (tools/occupancy_report.py)
 
     @property
     def n_cells(self) -> int:
@@ -74,11 +94,36 @@ class OccupancyGrid:
         """Culled rays / rays seen since the grid was made (one device-to-host read)."""
         return 1.0 - int(self.hits_dev.item()) / self.rays_seen if self.rays_seen else 0.0
 
+    @property
+    def samples_live_dev(self) -> Tensor:
+        """Live samples per level since the grid was made, device int64 [4].  The chunks of an image run on side streams, and every
+        stream adds to a counter of its own (no atomics); this sums them on the current stream, which the model's calls have
+        joined with the side streams by the time they return."""
+        total = torch.zeros(len(LEVELS), device=self.bits.device, dtype=torch.int64)
+        for acc in self._samples_live.values():
+            total += acc
+        return total
+
+    def count_samples(self, level_id: int, seen: int, n_live: Tensor) -> None:
+        """Book one rsn_occupancy_compact_samples: `seen` sample slots (host) and its device-side live count."""
+        self.samples_seen[level_id] += int(seen)
+        key = torch.cuda.current_stream(self.bits.device).cuda_stream
+        acc = self._samples_live.get(key)
+        if acc is None:
+            acc = self._samples_live[key] = torch.zeros(len(LEVELS), device=self.bits.device, dtype=torch.int64)
+        acc[level_id:level_id + 1] += n_live
+
     def describe(self) -> dict:
-        """What `render` / `eval` record under "occupancy"."""
-        return {"resolution": list(self.dims), "sigma": self.threshold, "dilate": self.dilate, "outside_occupied": self.outside_occupied,
-                "bounds": list(self.bounds), "occupied_share": self.occupied_share(), "culled_share": self.culled_share(),
-                "rays": int(self.rays_seen)}
+        """What `render` / `eval` record under "occupancy"; with per-sample skipping also "samples": per level the sample slots
+        seen and the live ones (this and culled_share are the only host reads)."""
+        d = {"resolution": list(self.dims), "sigma": self.threshold, "dilate": self.dilate, "outside_occupied": self.outside_occupied,
+             "bounds": list(self.bounds), "occupied_share": self.occupied_share(), "culled_share": self.culled_share(),
+             "rays": int(self.rays_seen)}
+        if any(self.samples_seen):
+            live = [int(x) for x in self.samples_live_dev.tolist()]
+            d["samples"] = {"max_radius": sample_max_radius(self),
+                            "levels": {name: {"seen": int(self.samples_seen[i]), "live": live[i]} for i, name in enumerate(LEVELS)}}
+        return d
 
 
 def occupancy_from_volume(vol: Tensor, origin, spacing, threshold: float = DEFAULT_SIGMA, dilate: int = DEFAULT_DILATE,
@@ -161,6 +206,7 @@ def attach_occupancy(model, settings: dict, c2w, height: int, width: int, fx: fl
         grid = build_occupancy(model.field, bounds, res, float(settings.get("sigma", DEFAULT_SIGMA)),
                                int(settings.get("dilate", DEFAULT_DILATE)))
     model.occupancy = grid
+    model.occupancy_samples = bool(settings.get("samples", False))
     return grid
 
 
@@ -192,6 +238,45 @@ def scatter_rows(src: Tensor, ray_index: Tensor, n_dev: Optional[Tensor], fill: 
     row = src.numel() // n if n else 1
     check(lib.rsn_scatter_rows(n, ptr(n_dev), ptr(ray_index), ptr(src), max(row, 1), float(fill), ptr(out), ops._stream()))
     return out
+
+
+def mark_and_compact(grid: OccupancyGrid, origins: Tensor, directions: Tensor, pixel_area: Tensor, euclid_bins: Tensor,
+                     n_dev: Optional[Tensor] = None, max_radius: Optional[float] = None) -> Dict[str, Tensor]:
+    """rsn_occupancy_compact_samples over a level (origins / directions fp32 [R,3], pixel_area [R], euclid_bins [R,S+1], contiguous,
+    on the grid's device; n_dev: device int32 count of leading rays, or None) -> live uint8 [R,S], n_live int32 [1] (device),
+    sample_index int32 [R*S] (the live samples in ascending order, then the others) and the compact "rays" of one sample each:
+    origins_c / directions_c [R*S,3], pixel_area_c [R*S], bins_c [R*S,2], of which the first n_live rows are written.
+    max_radius: None = sample_max_radius(grid)."""
+    lib = _abi.load_library()
+    R, S = int(euclid_bins.shape[0]), int(euclid_bins.shape[1]) - 1
+    dev = origins.device
+    nbytes = int(lib.rsn_occupancy_samples_workspace_bytes(R, S))
+    if nbytes == 0:
+        check(-1)
+    N = R * S
+    f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+    out = {"live": torch.empty(R, S, device=dev, dtype=torch.uint8), "n_live": torch.empty(1, device=dev, dtype=torch.int32),
+           "sample_index": torch.empty(N, device=dev, dtype=torch.int32), "origins_c": f(N, 3), "directions_c": f(N, 3),
+           "pixel_area_c": f(N), "bins_c": f(N, 2)}
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    nx, ny, nz = grid.dims
+    radius = sample_max_radius(grid) if max_radius is None else float(max_radius)
+    check(lib.rsn_occupancy_compact_samples(R, ptr(n_dev), S, ptr(origins), ptr(directions), ptr(pixel_area), ptr(euclid_bins), nx, ny, nz,
+                                            grid._origin3, grid._spacing3, ptr(grid.bits), int(grid.outside_occupied), radius,
+                                            ptr(out["live"]), ptr(out["n_live"]), ptr(out["sample_index"]), ptr(out["origins_c"]),
+                                            ptr(out["directions_c"]), ptr(out["pixel_area_c"]), ptr(out["bins_c"]), ptr(ws), ops._stream()))
+    return out
+
+
+def scatter_level(compact: Dict[str, Tensor], n_live: Tensor, sample_index: Tensor, lead: Sequence[int]) -> Dict[str, Tensor]:
+    """rsn_scatter_level: the members of a level evaluated on the compact samples ([N] or [N,3] each) -> the same keys shaped
+    [*lead] / [*lead, 3]: compact row j in slot sample_index[j] for j < *n_live, zeros in the slots of the skipped samples."""
+    lib = _abi.load_library()
+    N = int(sample_index.shape[0])
+    level = {k: torch.empty(*lead, *v.shape[1:], device=v.device, dtype=torch.float32) for k, v in compact.items()}
+    src, dst = ops.field_outputs_struct(compact), ops.field_outputs_struct(level)
+    check(lib.rsn_scatter_level(N, ptr(n_live), ptr(sample_index), C.byref(src), C.byref(dst), ops._stream()))
+    return level
 
 
 # what a culled ray holds, per output key of the model (everything else: 0)

@@ -227,6 +227,53 @@ class ReflectSamplingNeRFNerfField(Field):
                                           ptr(pixel_area), ptr(euclid_bins), C.byref(fo), ops._stream())))
         return level
 
+    def evaluate_frustums_skipping(self, grid, level_id: int, origins: Tensor, directions: Tensor, pixel_area: Tensor,
+                                   euclid_bins: Tensor, n_dev: Optional[Tensor] = None, full: bool = True) -> Dict[str, Tensor]:
+        """evaluate_frustums on the samples of the level that an occupancy.OccupancyGrid leaves live, without a host read:
+        rsn_occupancy_compact_samples lists the live samples as R*S "rays" of one sample each, ONE rsn_field_forward_frustum
+        evaluates that list with the device-side count n_live (a sample's Gaussian depends on its ray and its two bin edges only,
+        and the kernels treat the rows of a tile independently, so a live sample has the bits evaluate_frustums gives it), and
+        rsn_scatter_level writes the results to their [R,S] slots -- zeros in the slots of the skipped samples, and of the rays
+        behind n_dev.  -> the dict of evaluate_frustums plus "live" (uint8 [R,S]).  level_id: which counter of the grid books the
+        launch (occupancy.LEVELS)."""
+        from . import occupancy
+
+        self._no_distortion()
+        lib = _abi.load_library()
+        R, S = euclid_bins.shape[0], euclid_bins.shape[1] - 1
+        N = R * S
+        dev = origins.device
+        events = grid.sample_stage_events if isinstance(grid.sample_stage_events, list) else None
+        marks = []
+
+        def mark():
+            if events is not None:
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                marks.append(e)
+
+        mark()
+        c = occupancy.mark_and_compact(grid, origins, directions, pixel_area, euclid_bins, n_dev)
+        grid.count_samples(level_id, N, c["n_live"])
+        mark()
+        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        compact = {"sigma": f(N), "color": f(N, 3)}
+        if full:
+            compact.update({"pred_normals": f(N, 3), "n_dot_d": f(N), "diff": f(N, 3), "tint": f(N, 3), "roughness": f(N)})
+        fo = ops.field_outputs_struct(compact)
+        desc = self.field_desc()
+        pk = self.packed_weights()
+        ops.timed("field_forward_eval_live" if full else "field_forward_eval_color_live", {"points": N}, lambda: check(
+            lib.rsn_field_forward_frustum(C.byref(desc), ptr(pk), N, ptr(c["n_live"]), 1, ptr(c["origins_c"]), ptr(c["directions_c"]),
+                                          ptr(c["pixel_area_c"]), ptr(c["bins_c"]), C.byref(fo), ops._stream())))
+        mark()
+        level = occupancy.scatter_level(compact, c["n_live"], c["sample_index"], (R, S))
+        mark()
+        if events is not None:
+            events.append((level_id, marks))
+        level["live"] = c["live"]
+        return level
+
     def evaluate_frustums_train(self, origins: Tensor, directions: Tensor, pixel_area: Tensor, euclid_bins: Tensor,
                                 n_dev: Optional[Tensor] = None, want_normals: bool = True,
                                 work: Optional[Dict] = None) -> Dict[str, Tensor]:

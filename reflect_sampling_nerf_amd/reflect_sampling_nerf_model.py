@@ -100,6 +100,7 @@ class ReflectSamplingNeRFModel(Model):
         self._register_load_state_dict_pre_hook(self._drop_reference_metric_state)
         self._deterministic = os.environ.get("RSN_DETERMINISTIC", "") == "1"
         self.occupancy = None  # an occupancy.OccupancyGrid: eval renders skip the rays that cross no occupied cell (_cull)
+        self.occupancy_samples = False  # with the grid: also evaluate the field only on the samples in occupied cells (_get_outputs_eval)
 
     _REFERENCE_METRIC_MODULES = ("lpips", "psnr", "ssim")
 
@@ -182,15 +183,21 @@ class ReflectSamplingNeRFModel(Model):
         Src, Srf = cfg.num_reflect_coarse_samples, cfg.num_reflect_importance_samples
         EVAL, CLIP = ops.RSN_COMP_EVAL, ops.RSN_COMP_CLIP_RGB
         uni, rec = self.sampler_uniform.spec, self.sampler_reciprocal.spec
+        grid = getattr(self, "occupancy", None) if getattr(self, "occupancy_samples", False) else None
+
+        def evaluate(level_id, *args, **kw):  # the four levels: all samples, or (occupancy_samples) the ones in occupied cells
+            if grid is None:
+                return fld.evaluate_frustums(*args, **kw)
+            return fld.evaluate_frustums_skipping(grid, level_id, *args, **kw)
 
         # A. coarse primary (model.py:148-177)
         sb_c, eb_c = ops.sample_spaced(R, n_dev0, Sc, uni.spacing, uni.tan, nears, fars, None)
-        lc = fld.evaluate_frustums(o, d, pa, eb_c, n_dev0)
+        lc = evaluate(0, o, d, pa, eb_c, n_dev0)
         cc = ops.composite(R, n_dev0, Sc, 1, EVAL | CLIP, lc["sigma"], eb_c, lc["color"])
         # B. fine primary (model.py:182-211) + C. per-ray surface attributes (model.py:215-227)
         sb_f, eb_f = ops.sample_pdf(R, n_dev0, Sc, Sf, uni.spacing, uni.tan, self.sampler_pdf.histogram_padding, nears,
                                     fars, cc["weights"], sb_c, None)
-        lf = fld.evaluate_frustums(o, d, pa, eb_f, n_dev0)
+        lf = evaluate(1, o, d, pa, eb_f, n_dev0)
         cf = ops.composite(R, n_dev0, Sf, 1, EVAL | CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True,
                            zero_accumulation=n_dev0 is not None)
         # mask, stable compaction, secondary rays, default reflect colours (model.py:222-229,240-241,267-289)
@@ -224,13 +231,13 @@ class ReflectSamplingNeRFModel(Model):
         o2, d2, pa2, near2, far2 = rs["origins2"], rs["directions2"], rs["pixel_area2"], rs["nears2"], rs["fars2"]
         bg = fld.evaluate_inf(d2, rs["sqradius"], n_dev)
         sb_rc, eb_rc = ops.sample_spaced(R, n_dev, Src, rec.spacing, rec.tan, near2, far2, None)
-        lrc = fld.evaluate_frustums(o2, d2, pa2, eb_rc, n_dev, full=False)
+        lrc = evaluate(2, o2, d2, pa2, eb_rc, n_dev, full=False)
         crc = ops.composite(R, n_dev, Src, 2, EVAL, lrc["sigma"], eb_rc, lrc["color"], bg_rgb=bg, want_depth=False)
         ops.reflect_combine(R, n_dev, rs["ray_index"], cf["diff"], cf["tint"], crc["rgb"], rs["reflect_coarse"])
         sb_rf, eb_rf = ops.sample_pdf(R, n_dev, Src, Srf, rec.spacing, rec.tan,
                                       self.sampler_reflect_pdf.histogram_padding, near2, far2, crc["weights"], sb_rc,
                                       None)
-        lrf = fld.evaluate_frustums(o2, d2, pa2, eb_rf, n_dev, full=False)
+        lrf = evaluate(3, o2, d2, pa2, eb_rf, n_dev, full=False)
         crf = ops.composite(R, n_dev, Srf, 2, EVAL, lrf["sigma"], eb_rf, lrf["color"], bg_rgb=bg)
         ops.reflect_combine(R, n_dev, rs["ray_index"], cf["diff"], cf["tint"], crf["rgb"], rs["reflect_fine"])
 

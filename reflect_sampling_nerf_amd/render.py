@@ -415,7 +415,8 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
     its file name(s) and c2w).  Existing files of these names are replaced; nothing else in out_dir is touched.
     occupancy: None, or {"resolution", "sigma", "dilate", "bounds" (None: occupancy.segment_bounds of the path)}: the frames are
     rendered with empty-space skipping and frames.json gains an "occupancy" entry (settings, box, occupied share of cells, culled
-    share of rays; the latter read from the device once, after the last frame).
+    share of rays; the latter read from the device once, after the last frame).  With "samples": True in it the field is also
+    evaluated only on the samples in occupied cells, and the entry holds "samples": per level the sample slots seen and the live ones.
     -> the dict written to frames.json plus {"seconds": wall time of the frames, "out": out_dir}."""
     from PIL import Image
 

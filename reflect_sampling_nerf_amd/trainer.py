@@ -4,7 +4,7 @@
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
-    (eval and render: [--skip-empty [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
+    (eval and render: [--skip-empty | --skip-empty-samples [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
 
 `train` is the reference's `ns-train reflect-sampling-nerf --data DIR` loop on this package's own pieces: the reference
 Model config (ReflectSamplingNeRFModelConfig defaults), RayDataManager batches (1024 rays, reflect_sampling_nerf_config.py:36-41),
@@ -36,6 +36,10 @@ the frames are the product.
 [near, far] segment crosses no occupied cell are not evaluated; they get the white background.  The grid's defaults (sigma 0.01,
 one cell of dilation) are starting points from one experiment on a briefly trained field, not measured against a scene.  The
 output JSON then carries an "occupancy" entry: the settings, the box, the occupied share of cells and the culled share of rays.
+`--skip-empty-samples` implies it and goes one step further: on the rays that remain, the field is evaluated only on the samples
+whose interval crosses an occupied cell (or whose cone is wider than the grid's dilation margin -- a design rule, not a measured
+one); the others get zero density.  The "occupancy" entry then also holds "samples": per level, the sample slots seen and the live
+ones.
 """
 from __future__ import annotations
 
@@ -68,6 +72,9 @@ def _add_occupancy_flags(p: argparse.ArgumentParser) -> None:
 
     p.add_argument("--skip-empty", action="store_true",
                    help="cull the rays that cross no occupied cell of an occupancy grid built from the field (they get the white background)")
+    p.add_argument("--skip-empty-samples", action="store_true",
+                   help="implies --skip-empty; on the remaining rays, evaluate the field only on the samples whose interval crosses an "
+                        "occupied cell or whose cone is wider than the grid's dilation margin (a design rule, not measured against any scene)")
     p.add_argument("--occupancy-resolution", type=int, default=None, metavar="N", help=f"grid vertices per axis (default {DEFAULT_RESOLUTION})")
     p.add_argument("--occupancy-sigma", type=float, default=None, metavar="S",
                    help=f"a cell is occupied when a corner has density >= S (default {DEFAULT_SIGMA:g}: a starting point from one experiment "
@@ -79,11 +86,13 @@ def _add_occupancy_flags(p: argparse.ArgumentParser) -> None:
 
 
 def resolve_occupancy_args(ap: argparse.ArgumentParser, args) -> Optional[dict]:
-    """The occupancy settings of an `eval` / `render` command line: None without --skip-empty (the sub-flags are an error then), else
-    {"resolution", "sigma", "dilate", "bounds" (None: from the cameras)}."""
+    """The occupancy settings of an `eval` / `render` command line: None without --skip-empty and --skip-empty-samples (the sub-flags
+    are an error then), else {"resolution", "sigma", "dilate", "bounds" (None: from the cameras)}, with "samples": True added by
+    --skip-empty-samples (absent means False: --skip-empty alone resolves to what it always did)."""
     from .occupancy import DEFAULT_DILATE, DEFAULT_RESOLUTION, DEFAULT_SIGMA
 
-    if not getattr(args, "skip_empty", False):
+    samples = bool(getattr(args, "skip_empty_samples", False))
+    if not (getattr(args, "skip_empty", False) or samples):
         given = ["--" + f.replace("_", "-") for f in OCCUPANCY_SUBFLAGS if getattr(args, f, None) is not None]
         if given:
             ap.error(f"{args.command}: {' '.join(given)} need(s) --skip-empty")
@@ -97,8 +106,11 @@ def resolve_occupancy_args(ap: argparse.ArgumentParser, args) -> Optional[dict]:
     b = args.occupancy_bounds
     if b is not None and not (all(math.isfinite(x) for x in b) and all(b[3 + a] > b[a] for a in range(3))):
         ap.error(f"{args.command}: --occupancy-bounds needs X0 Y0 Z0 X1 Y1 Z1 with every upper bound above its lower one")
-    return {"resolution": int(res), "sigma": float(sigma), "dilate": DEFAULT_DILATE if args.occupancy_dilate is None else args.occupancy_dilate,
-            "bounds": None if b is None else tuple(float(x) for x in b)}
+    settings = {"resolution": int(res), "sigma": float(sigma), "dilate": DEFAULT_DILATE if args.occupancy_dilate is None else args.occupancy_dilate,
+                "bounds": None if b is None else tuple(float(x) for x in b)}
+    if samples:
+        settings["samples"] = True
+    return settings
 
 
 def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
