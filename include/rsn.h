@@ -677,6 +677,43 @@ int rsn_mesh_emit(int32_t nx, int32_t ny, int32_t nz, const float* vol, float is
                   int32_t max_triangles, float* positions, int32_t* vert_key, int32_t* triangles, void* stream);
 
 
+/* ---- TSDF fusion: depth maps of posed pinhole cameras into a truncated signed distance volume (additive to ABI 18: no existing
+ * call changes).  The volume is what the mesh calls extract from: a mesh of the surface the model's own depth maps describe.
+ *
+ * Grid: tsdf and weight are fp32 [nz, ny, nx] in the layout of the mesh calls (x fastest, vertex (i, j, k) at
+ * origin + spacing * (i, j, k)); origin3 / spacing3 are HOST arrays.  Cameras: c2w fp32 [n_views,3,4] (row-major, device) and one
+ * set of intrinsics, in the ray convention written above rsn_sample_camera_rays; depth fp32 [n_views, height*width] (device),
+ * row-major, the EUCLIDEAN distance along the ray of pixel (y, x) -- the model's median depth depth_fine, from which it starts its
+ * own reflected rays.  There is no accumulation input: the median depth of a ray that does not reach 0.5 opacity is its last
+ * sample, so such a ray carves free space up to its far end.
+ *
+ * Views are applied in ascending view order at every grid vertex, so a call with n views equals n calls of one view, bit for bit;
+ * the caller batches views only to bound the memory its depth maps hold.  Per vertex (T = tsdf, W = weight) and view, every step
+ * one correctly rounded fp32 operation in exactly this order:
+ *   p_a   = o_a + s_a * idx_a                                            a = 0, 1, 2
+ *   q_a   = p_a - c2w[a][3]
+ *   cam_c = (c2w[0][c]*q_0 + c2w[1][c]*q_1) + c2w[2][c]*q_2              c = 0, 1, 2
+ *   z     = -cam_2; the view is skipped unless z > 0
+ *   u     = (fx*cam_0)/z + cx,  v = cy - (fy*cam_1)/z                    the inverse of the ray convention: the pixel whose square
+ *                                                                        holds the projection is x = floor(u), y = floor(v)
+ *   skipped unless 0 <= u < width and 0 <= v < height, compared as floats (a NaN skips)
+ *   r     = sqrt((q_0*q_0 + q_1*q_1) + q_2*q_2); skipped if r < near
+ *   D     = depth[view][y*width + x]; skipped if D is not finite
+ *   s     = D - r; skipped if s < -trunc: the vertex is hidden behind the surface this view saw
+ *   d     = min(1, s / trunc)
+ *   Wn    = W + 1;  T = (T*W + d) / Wn;  W = Wn
+ * A skipped view leaves both words of that vertex untouched.  T is positive in front of the surface, up to 1 in free space, and
+ * negative down to -1 behind it; W counts the views that reached the vertex.
+ *
+ * RSN_ERR_INVALID_ARGUMENT before any launch, with the reason in rsn_last_error(): a dimension below 2; height < 1, width < 1 or
+ * height*width > 2^31 - 1; n_views < 0; a NULL pointer when n_views > 0; trunc not finite or <= 0; near not finite; fx or fy not
+ * finite or zero.  RSN_ERR_UNSUPPORTED for nx*ny*nz > 2^27.  n_views == 0 launches nothing.  No allocation and no synchronisation;
+ * depth is indexed in 64 bits.  No atomics: every word has one owner, so the result is deterministic. */
+int rsn_tsdf_integrate(int32_t nx, int32_t ny, int32_t nz, const float* origin3, const float* spacing3, int32_t n_views,
+                       const float* c2w, int32_t height, int32_t width, float fx, float fy, float cx, float cy, const float* depth,
+                       float trunc, float near, float* tsdf, float* weight, void* stream);
+
+
 /* ---- visualisation: per-pixel floats as one 8-bit RGB tile of a panel (additive to ABI 18: no existing call changes).
  * One call draws one channel of a rendered view into one tile, so a frame is a handful of launches on the caller's stream.
  *

@@ -207,6 +207,9 @@ _SIGNATURES = {
     "rsn_mesh_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rsn_mesh_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rsn_tsdf_integrate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, _fp,
+                                     C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, C.c_float, C.c_float,
+                                     _fp, _fp, C.c_void_p]),
     "rsn_visualize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_float, C.c_float, _fp, C.c_void_p, C.c_int32,
                                 C.c_int32, C.c_void_p]),
     "rsn_occupancy_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -13,6 +13,14 @@ query lets the 2^16 frequency through and the density turns to noise.
 
 The default iso level (sigma = 10) is a starting point that has not been measured against a scene; so is the default box,
 nerfstudio's Blender scene box.  Pick the level per scene.
+
+    ... export-mesh --method tsdf --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T] [--min-weight 1]
+
+The second route needs no level: fuse_depth renders the model's own median depth (depth_fine, where it starts its reflected rays:
+Model.get_surface_outputs) from the given cameras and fuses the maps into a truncated signed distance volume (rsn_tsdf_integrate
+of include/rsn.h) -> tsdf_volume -> the same extractor at level 0 -> drop_unobserved (without it a second shell appears inside
+the object, where the observed band ends) -> vertex_attributes -> write_ply.  Its defaults, a truncation of 4 grid spacings and
+min_weight 1, are starting points from an experiment on analytic depth maps of a sphere; they have not been measured on a scene.
 """
 from __future__ import annotations
 
@@ -135,6 +143,106 @@ def vertex_attributes(field, positions: Tensor, spacing: Sequence[float], chunk:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ TSDF fusion
+DEFAULT_TRUNC_SPACINGS = 4.0  # truncation in units of the largest spacing: a starting point from the sphere experiment, not measured on a scene
+DEFAULT_MIN_WEIGHT = 1.0      # likewise
+DEFAULT_RAY_CHUNK = 4096      # rays per chunk of the depth pass (render.DEFAULT_CHUNK)
+EDGE_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))  # dir 0..6 of vert_key (include/rsn.h)
+
+
+def integrate_depth(tsdf: Tensor, weight: Tensor, origin, spacing, c2w: Tensor, depth: Tensor, height: int, width: int, fx: float,
+                    fy: float, cx: float, cy: float, trunc: float, near: float) -> None:
+    """One rsn_tsdf_integrate launch: the views c2w [n,3,4] with depth maps depth [n, H*W] (fp32, on the volumes' device) into
+    tsdf / weight (fp32 [nz, ny, nx], contiguous), in place."""
+    for name, t in (("tsdf", tsdf), ("weight", weight), ("c2w", c2w), ("depth", depth)):
+        if t.dtype != torch.float32 or t.device.type != "cuda" or not t.is_contiguous():
+            raise _abi.RsnError(f"integrate_depth: {name} must be a contiguous fp32 tensor on a cuda (ROCm) device")
+    if tsdf.dim() != 3 or weight.shape != tsdf.shape:
+        raise _abi.RsnError("integrate_depth: tsdf and weight must be [nz, ny, nx] tensors of one shape")
+    n = int(c2w.shape[0])
+    if tuple(c2w.shape) != (n, 3, 4) or depth.numel() != n * int(height) * int(width):
+        raise _abi.RsnError(f"integrate_depth: c2w {tuple(c2w.shape)} / depth {tuple(depth.shape)}: need [n,3,4] and [n, {height}*{width}]")
+    nz, ny, nx = tsdf.shape
+    o3 = (C.c_float * 3)(*[float(x) for x in origin])
+    s3 = (C.c_float * 3)(*[float(x) for x in spacing])
+    check(_abi.load_library().rsn_tsdf_integrate(nx, ny, nz, o3, s3, n, ptr(c2w), int(height), int(width), float(fx), float(fy),
+                                                 float(cx), float(cy), ptr(depth), float(trunc), float(near), ptr(tsdf),
+                                                 ptr(weight), ops._stream()))
+
+
+def fuse_depth(model, poses, H: int, W: int, fx: float, fy: float, cx: float, cy: float, bounds: Sequence[float],
+               resolution: Union[int, Sequence[int]], trunc: float, views_per_launch: int = 8, chunk: int = DEFAULT_RAY_CHUNK,
+               events: Optional[list] = None) -> Tuple[Tensor, Tensor]:
+    """Render the model's median depth (Model.get_surface_outputs: depth_fine) from the cameras poses [F,3,4] (or [F,4,4]) with
+    one pinhole H x W, fx, fy, cx, cy, and fuse the maps into the grid of grid_frame(bounds, resolution) -> (tsdf, weight), fp32
+    [nz, ny, nx] on the model's device, both starting at zero.  `near` of the fusion is the model's collider near plane.
+    views_per_launch depth maps are held at a time and go into one rsn_tsdf_integrate launch (the result does not depend on it);
+    chunk: rays per chunk of the depth pass.  No device-to-host read.
+    events: a list that receives, per launch, three timing events: start, depth maps rendered, integrated."""
+    from .render import _upload, camera_rays
+
+    (nx, ny, nz), origin, spacing = grid_frame(bounds, resolution)
+    H, W = int(H), int(W)
+    views_per_launch = max(1, int(views_per_launch))
+    dev = model.device
+    c2w = np.ascontiguousarray(np.asarray(poses.cpu() if isinstance(poses, torch.Tensor) else poses, dtype=np.float32)[:, :3, :4])
+    near = float(model.config.collider_params["near_plane"])
+    tsdf = torch.zeros(nz, ny, nx, device=dev, dtype=torch.float32)
+    weight = torch.zeros(nz, ny, nx, device=dev, dtype=torch.float32)
+    poses_dev = _upload(torch.from_numpy(c2w), dev) if len(c2w) else None
+    depth = torch.empty(min(views_per_launch, max(len(c2w), 1)), H * W, device=dev, dtype=torch.float32)
+    with torch.no_grad():
+        for start in range(0, len(c2w), views_per_launch):
+            n = min(views_per_launch, len(c2w) - start)
+            _mark(events, new=True)
+            for i in range(n):
+                rays = camera_rays(poses_dev[start + i], H, W, fx, fy, cx, cy, dev)
+                depth[i] = model.get_surface_outputs_for_camera_ray_bundle(rays, chunk)["depth_fine"].reshape(H * W)
+            _mark(events)
+            integrate_depth(tsdf, weight, origin, spacing, poses_dev[start:start + n], depth[:n], H, W, fx, fy, cx, cy, trunc, near)
+            _mark(events)
+    return tsdf, weight
+
+
+def _mark(events: Optional[list], new: bool = False) -> None:
+    if events is None:
+        return
+    if new:
+        events.append([])
+    e = torch.cuda.Event(enable_timing=True)
+    e.record()
+    events[-1].append(e)
+
+
+def tsdf_volume(tsdf: Tensor, weight: Tensor, min_weight: float = DEFAULT_MIN_WEIGHT) -> Tensor:
+    """The volume the extractor takes at level 0: -tsdf where weight >= min_weight, else -1.  The extractor's "inside = vol >= 0"
+    then means "behind the surface", and a vertex no view reached counts as outside."""
+    return torch.where(weight >= min_weight, -tsdf, torch.full_like(tsdf, -1.0))
+
+
+def drop_unobserved(mesh: Dict[str, Tensor], weight: Tensor, dims: Sequence[int], min_weight: float = DEFAULT_MIN_WEIGHT) -> Dict[str, Tensor]:
+    """Keep the part of an extracted mesh that lies between observed grid vertices.  A surface vertex sits on the grid edge its
+    vert_key = 8 v + dir names; it is valid if and only if both ends of that edge have weight >= min_weight.  The triangles whose
+    three vertices are valid stay, in their order; the vertices no remaining triangle names are dropped and the others renumbered
+    in their order.  dims = (nx, ny, nz) of weight [nz, ny, nx].  Plain torch operations: CPU tensors work as well.
+    -> {"positions", "triangles", "vert_key"} (and every other per-vertex entry of `mesh`, filtered alike)."""
+    nx, ny, _ = (int(d) for d in dims)
+    key = mesh["vert_key"].to(torch.int64)
+    tri = mesh["triangles"].to(torch.int64).reshape(-1, 3)
+    V = key.shape[0]
+    off = torch.tensor([dx + dy * nx + dz * nx * ny for dx, dy, dz in EDGE_OFFSETS] + [0], device=key.device, dtype=torch.int64)
+    lo = torch.div(key, 8, rounding_mode="floor")
+    seen = weight.reshape(-1) >= min_weight
+    valid = seen[lo] & seen[lo + off[key % 8]]
+    tri = tri[valid[tri].all(dim=1)]
+    used = torch.zeros(V, device=key.device, dtype=torch.bool)
+    used[tri.reshape(-1)] = True
+    new_id = torch.cumsum(used.to(torch.int64), dim=0) - 1
+    out = {k: v[used] for k, v in mesh.items() if k != "triangles" and isinstance(v, Tensor) and v.shape[:1] == (V,)}
+    out["triangles"] = new_id[tri].to(mesh["triangles"].dtype)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ PLY
 PLY_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                              ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("roughness", "<f4"), ("tint_r", "<f4"),
@@ -204,29 +312,65 @@ class _Stages:
 
 def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256, bounds: Sequence[float] = DEFAULT_BOUNDS,
                 iso: float = DEFAULT_ISO, mma: str = "f32", chunk: int = DEFAULT_CHUNK, device="cuda:0",
-                model_config=None) -> dict:
-    """Checkpoint (a step-*.ckpt, or a run directory: its newest) -> PLY at `out`.  -> dict with the counts, the grid, iso and
-    the seconds per stage (grid evaluation, count, emit, attributes on the device; write on the host)."""
+                model_config=None, method: str = "density", cameras: Optional[dict] = None, trunc: Optional[float] = None,
+                min_weight: float = DEFAULT_MIN_WEIGHT, views_per_launch: int = 8, ray_chunk: int = DEFAULT_RAY_CHUNK) -> dict:
+    """Checkpoint (a step-*.ckpt, or a run directory: its newest) -> PLY at `out`.  -> dict with the counts, the grid, the method
+    and the seconds per stage.
+    method "density": the iso-surface of the field's density at `iso`; stages: grid evaluation, count, emit, attributes on the
+    device; write on the host.
+    method "tsdf": the surface of the model's own depth maps (see the module text); `iso` plays no part.  cameras: {"c2w" [F,3,4],
+    "width", "height", "fx", "fy", "cx", "cy"} (what trainer.resolve_export_cameras returns); trunc: the truncation distance in
+    world units (None: DEFAULT_TRUNC_SPACINGS x the largest spacing); min_weight: the views a grid vertex needs to count as
+    observed.  Stages: depth (the depth passes), integrate, count, emit, filter, attributes; write.  The dict also holds the view
+    count, trunc, min_weight and the counts before the filter."""
     from .trainer import load_checkpoint, resolve_checkpoint
 
+    if method not in ("density", "tsdf"):
+        raise ValueError(f"method {method!r}: density or tsdf")
+    if method == "tsdf" and cameras is None:
+        raise ValueError("method tsdf needs cameras")
     ckpt = resolve_checkpoint(ckpt)
     model, step = load_checkpoint(ckpt, model_config, device)
     field = model.field
     field.set_mma_mode(mma)
     (nx, ny, nz), origin, spacing = grid_frame(bounds, resolution)
+    extra = {}
     with torch.cuda.device(torch.device(device)):
         field.packed_weights()  # the one-off weight packing is not part of the grid stage
         stages = _Stages()
-        vol = density_grid(field, bounds, resolution, chunk)
-        stages("grid")
-        mesh = _extract(vol, iso, origin, spacing, mark=stages)
+        if method == "density":
+            vol = density_grid(field, bounds, resolution, chunk)
+            stages("grid")
+            mesh = _extract(vol, iso, origin, spacing, mark=stages)
+        else:
+            trunc = float(DEFAULT_TRUNC_SPACINGS * float(spacing.max()) if trunc is None else trunc)
+            events: list = []
+            tsdf, weight = fuse_depth(model, cameras["c2w"], cameras["height"], cameras["width"], cameras["fx"], cameras["fy"],
+                                      cameras["cx"], cameras["cy"], bounds, resolution, trunc, views_per_launch, ray_chunk, events)
+            vol = tsdf_volume(tsdf, weight, min_weight)
+            stages("fuse")
+            mesh = _extract(vol, 0.0, origin, spacing, mark=stages)
+            extra = {"views": int(len(cameras["c2w"])), "trunc": trunc, "min_weight": float(min_weight),
+                     "vertices_extracted": int(mesh["positions"].shape[0]), "triangles_extracted": int(mesh["triangles"].shape[0]),
+                     "image": [int(cameras["width"]), int(cameras["height"])]}
+            mesh = drop_unobserved(mesh, weight, (nx, ny, nz), min_weight)
+            stages("filter")
         mesh.update(vertex_attributes(field, mesh["positions"], spacing, chunk))
         stages("attributes")
         seconds = stages.seconds()
+        if method == "tsdf":  # the fuse stage, split into its two kinds of work by the per-launch events
+            del seconds["fuse"]
+            seconds = {"depth": sum(e[0].elapsed_time(e[1]) for e in events) / 1000.0,
+                       "integrate": sum(e[1].elapsed_time(e[2]) for e in events) / 1000.0, **seconds}
+            extra["integrate_launches"] = len(events)
     t0 = time.time()
     write_ply(out, mesh)
     seconds["write"] = time.time() - t0
-    return {"checkpoint": ckpt, "step": step, "out": out, "vertices": int(mesh["positions"].shape[0]),
-            "triangles": int(mesh["triangles"].shape[0]), "resolution": [nx, ny, nz], "bounds": [float(b) for b in bounds],
-            "origin": [float(x) for x in origin], "spacing": [float(x) for x in spacing], "iso": float(iso), "mma": mma,
-            "seconds": seconds}
+    res = {"checkpoint": ckpt, "step": step, "out": out, "vertices": int(mesh["positions"].shape[0]),
+           "triangles": int(mesh["triangles"].shape[0]), "resolution": [nx, ny, nz], "bounds": [float(b) for b in bounds],
+           "origin": [float(x) for x in origin], "spacing": [float(x) for x in spacing], "method": method, "mma": mma,
+           "seconds": seconds}
+    if method == "density":
+        res["iso"] = float(iso)
+    res.update(extra)
+    return res

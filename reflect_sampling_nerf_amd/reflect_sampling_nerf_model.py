@@ -168,10 +168,11 @@ class ReflectSamplingNeRFModel(Model):
         return 0 if nm is None else int(nm.item())
 
     @torch.no_grad()
-    def _get_outputs_eval(self, ray_bundle, n_dev0: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    def _get_outputs_eval(self, ray_bundle, n_dev0: Optional[Tensor] = None, primary_only: bool = False) -> Dict[str, Tensor]:
         """n_dev0 (culled renders only): device int32 count of the bundle's leading rays that are live.  The primary-level launches
         take it as their n_dev; the rows behind it are never computed, and their accumulation is 0 so that rsn_reflect_setup --
-        which takes only a host count -- masks none of them."""
+        which takes only a host count -- masks none of them.
+        primary_only: stop after the two primary levels (steps A and B) and return only what they give (get_surface_outputs)."""
         cfg, fld = self.config, self.field
         R = ray_bundle.origins.shape[0]
         o = ops._f32c(ray_bundle.origins.reshape(R, 3))
@@ -200,6 +201,9 @@ class ReflectSamplingNeRFModel(Model):
         lf = evaluate(1, o, d, pa, eb_f, n_dev0)
         cf = ops.composite(R, n_dev0, Sf, 1, EVAL | CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True,
                            zero_accumulation=n_dev0 is not None)
+        if primary_only:  # the same launches, so the same bits, as the full pass up to here; no reflected ray is set up
+            return {"accumulation_coarse": cc["accumulation"].unsqueeze(-1), "accumulation_fine": cf["accumulation"].unsqueeze(-1),
+                    "depth_coarse": cc["depth"].unsqueeze(-1), "depth_fine": cf["depth"].unsqueeze(-1)}
         # mask, stable compaction, secondary rays, default reflect colours (model.py:222-229,240-241,267-289)
         rs = ops.reflect_setup(o, d, cf["accumulation"], cf["depth"], cf["normals"], cf["roughness"], float(self.far))
         n_dev = rs["n_masked"]
@@ -246,6 +250,40 @@ class ReflectSamplingNeRFModel(Model):
         # image render enqueues every chunk before anything waits
         outputs.lazy["depth_reflect_fine"] = (n_dev, crf["depth"])
         return outputs
+
+    # ------------------------------------------------------------------ depth-only eval pass (mesh.fuse_depth)
+    @torch.no_grad()
+    def get_surface_outputs(self, ray_bundle) -> Dict[str, Tensor]:
+        """Where the model puts its surface, without the reflections: the coarse and fine primary levels of the eval-mode
+        get_outputs and nothing after them -- no reflected rays, no background evaluation, no reflect levels: two of the
+        four levels (at the default sample counts 256 of a reflected ray's 384 samples).  -> depth_fine (the median depth the model starts its reflected rays from),
+        accumulation_fine, depth_coarse, accumulation_coarse, each [R, 1], with the bits the full pass gives for the same rays.
+        The collider fills nears / fars as in forward().  No device-to-host read.  self.occupancy is not consulted: no ray is
+        culled here."""
+        if self.field is None:
+            raise ValueError("populate_fields() must be called before get_surface_outputs")
+        if self.collider is not None:
+            ray_bundle = self.collider(ray_bundle)
+        return self._get_outputs_eval(ray_bundle, primary_only=True)
+
+    @torch.no_grad()
+    def get_surface_outputs_for_camera_ray_bundle(self, camera_ray_bundle, chunk: Optional[int] = None) -> Dict[str, Tensor]:
+        """get_surface_outputs over a whole image in chunks of `chunk` rays (default: config.eval_num_rays_per_chunk), each key
+        reshaped to the image: [H, W, 1].  Every chunk is enqueued on the current stream before anything is read back: no
+        device-to-host read per chunk, or at all."""
+        chunk = int(self.config.eval_num_rays_per_chunk if chunk is None else chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        image_shape = camera_ray_bundle.origins.shape[:-1]
+        n = 1
+        for s_ in image_shape:
+            n *= int(s_)
+        lists: Dict[str, list] = {}
+        for i in range(0, n, chunk):
+            out = self.get_surface_outputs(camera_ray_bundle.get_row_major_sliced_ray_bundle(i, min(i + chunk, n)))
+            for k, v in out.items():
+                lists.setdefault(k, []).append(v)
+        return {k: torch.cat(v).view(*image_shape, *v[0].shape[1:]) for k, v in lists.items()}
 
     # ------------------------------------------------------------------ empty-space skipping (occupancy.py)
     def _cull(self, ray_bundle, marks: Optional[list] = None):

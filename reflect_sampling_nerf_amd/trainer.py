@@ -3,6 +3,7 @@
     python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR]
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
+    python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
     (eval and render: [--skip-empty | --skip-empty-samples [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
 
@@ -25,6 +26,11 @@ stream.  Multi-GPU training is not offered here.
 `export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
 the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
 (mesh.py).  The default level, sigma = 10, is a starting point that has not been measured against a scene.
+With `--method tsdf` the surface is instead the one the model itself renders: its median depth is rendered from the cameras of
+--data's split or of --poses (every one, or --max-views evenly spaced ones, at 1/--downscale of their size), the depth maps are
+fused into a truncated signed distance volume on the same grid, and its zero level is extracted, the part between observed grid
+vertices kept, and coloured as before.  No density level is involved.  The defaults, a truncation of 4 grid spacings and
+--min-weight 1, are starting points from an experiment on analytic depth maps of a sphere, not measured on a scene.
 
 `render` draws a checkpoint from viewpoints of the user's choosing (render.py): an orbit around a centre, or the poses of a
 transforms-format file, optionally with poses interpolated in between.  Every frame is a PNG panel of the chosen channels side by
@@ -154,6 +160,24 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                     help="density level of the surface (default 10: a starting point, not measured against any scene; pick it per scene)")
     ex.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels (default f32)")
     ex.add_argument("--chunk", type=int, default=None, help="points per field launch (default 262144)")
+    ex.add_argument("--method", choices=("density", "tsdf"), default="density",
+                    help="density: the iso-surface of the field's density at --iso (default); tsdf: the surface of the model's own depth "
+                         "maps, rendered from the cameras of --data / --poses and fused into a truncated signed distance volume")
+    ex.add_argument("--data", default=None, metavar="DIR", help="tsdf: scene directory; the cameras of transforms_{split}.json")
+    ex.add_argument("--split", default="train", help="tsdf: the split of --data (default train)")
+    ex.add_argument("--poses", default=None, metavar="FILE.json",
+                    help="tsdf: transforms-format file with frames[].transform_matrix, camera_angle_x and w / h")
+    ex.add_argument("--scale-factor", type=float, default=1.0, help="tsdf: scale of the translations read from --data / --poses")
+    ex.add_argument("--max-views", type=int, default=None, metavar="N", help="tsdf: use N evenly spaced views of the file (default: all)")
+    ex.add_argument("--downscale", type=int, default=1, metavar="K",
+                    help="tsdf: render every depth map at 1/K of the cameras' size, intrinsics scaled alike (default 1)")
+    ex.add_argument("--trunc", type=float, default=None, metavar="T",
+                    help="tsdf: truncation distance in world units (default 4 x the largest grid spacing: a starting point from an "
+                         "experiment on analytic depth maps of a sphere, not measured on a scene)")
+    ex.add_argument("--min-weight", type=float, default=None, metavar="W",
+                    help="tsdf: views a grid vertex needs to count as observed; surface between unobserved vertices is dropped "
+                         "(default 1: a starting point from the same experiment, not measured on a scene)")
+    ex.add_argument("--ray-chunk", type=int, default=None, metavar="R", help="tsdf: rays per chunk of the depth pass (default 4096)")
     from .render import CHANNELS, DEFAULT_CHANNELS, DEFAULT_CHUNK
 
     rn = sub.add_parser("render", help="render a camera path from a checkpoint as PNG panels of colour and material maps")
@@ -244,6 +268,59 @@ def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
         ap.error("render: --chunk must be >= 1")
     fx, fy, cx, cy = render.pinhole(width, height, fov)
     return {"c2w": c2w, "width": int(width), "height": int(height), "fx": fx, "fy": fy, "cx": cx, "cy": cy}
+
+
+TSDF_ONLY_FLAGS = ("data", "poses", "max_views", "trunc", "min_weight", "ray_chunk")
+
+
+def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
+    """The cameras of an `export-mesh` command line: None for --method density (the tsdf flags are an error then), else {"c2w"
+    [F,3,4], "width", "height", "fx", "fy", "cx", "cy"} after --max-views and --downscale.  Host work only (JSON and one image
+    header).  What the command line leaves open and no file settles is an argparse error that names the option."""
+    from . import render
+
+    if args.method != "tsdf":
+        given = ["--" + f.replace("_", "-") for f in TSDF_ONLY_FLAGS if getattr(args, f, None) is not None]
+        if args.downscale != 1:
+            given.append("--downscale")
+        if given:
+            ap.error(f"export-mesh: {' '.join(given)} need(s) --method tsdf")
+        return None
+    if args.iso is not None:
+        ap.error("export-mesh: --iso is the density route's level; --method tsdf has none")
+    if (args.poses is None) == (args.data is None):
+        ap.error("export-mesh: --method tsdf needs cameras: give --data DIR or --poses FILE.json (one of them)")
+    if args.poses is not None:
+        src = render.load_poses(args.poses, args.scale_factor)
+    else:
+        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), args.scale_factor)
+        if src["width"] is None or src["height"] is None:  # Blender-format files carry no size: the first image's header has it
+            rel = src["file_paths"][0] or ""
+            path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
+            if os.path.isfile(path):
+                from PIL import Image
+
+                with Image.open(path) as img:
+                    src["width"], src["height"] = (int(v) for v in img.size)
+    for name in ("width", "height", "camera_angle_x"):
+        if src[name] is None:
+            ap.error(f"export-mesh: the cameras' {name} is unknown: the file needs camera_angle_x and w / h (or, with --data, a first image)")
+    if args.downscale < 1 or (args.max_views is not None and args.max_views < 1):
+        ap.error("export-mesh: --downscale and --max-views must be >= 1")
+    if args.trunc is not None and not (math.isfinite(args.trunc) and args.trunc > 0.0):
+        ap.error(f"export-mesh: --trunc {args.trunc}: need a finite value above 0")
+    if args.min_weight is not None and not math.isfinite(args.min_weight):
+        ap.error(f"export-mesh: --min-weight {args.min_weight}: need a finite value")
+    if args.ray_chunk is not None and args.ray_chunk < 1:
+        ap.error("export-mesh: --ray-chunk must be >= 1")
+    c2w = src["c2w"]
+    if args.max_views is not None and args.max_views < len(c2w):  # N evenly spaced views, the first one among them
+        c2w = c2w[(np.arange(args.max_views, dtype=np.int64) * len(c2w)) // args.max_views]
+    fx, fy, cx, cy = render.pinhole(src["width"], src["height"], src["camera_angle_x"])
+    width, height = max(1, src["width"] // args.downscale), max(1, src["height"] // args.downscale)
+    sx, sy = width / src["width"], height / src["height"]
+    return {"c2w": np.ascontiguousarray(c2w), "width": int(width), "height": int(height), "fx": fx * sx, "fy": fy * sy,
+            "cx": cx * sx, "cy": cy * sy}
 
 
 # ------------------------------------------------------------------------------------------------ model and checkpoints
@@ -520,6 +597,7 @@ def main(argv=None) -> int:
     given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
     cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
     occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
+    export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
     if not torch.cuda.is_available():
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
@@ -532,14 +610,23 @@ def main(argv=None) -> int:
     if args.command == "export-mesh":
         from . import mesh
 
-        res = mesh.export_mesh(args.ckpt, args.out, resolution=args.resolution,
-                               bounds=mesh.DEFAULT_BOUNDS if args.bounds is None else tuple(args.bounds),
-                               iso=mesh.DEFAULT_ISO if args.iso is None else args.iso, mma=args.mma,
-                               chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
+        common = dict(resolution=args.resolution, bounds=mesh.DEFAULT_BOUNDS if args.bounds is None else tuple(args.bounds),
+                      mma=args.mma, chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
+        if args.method == "tsdf":
+            res = mesh.export_mesh(args.ckpt, args.out, method="tsdf", cameras=export_cameras, trunc=args.trunc,
+                                   min_weight=mesh.DEFAULT_MIN_WEIGHT if args.min_weight is None else args.min_weight,
+                                   ray_chunk=mesh.DEFAULT_RAY_CHUNK if args.ray_chunk is None else args.ray_chunk, **common)
+            what = (f"of {res['views']} depth maps {res['image'][0]} x {res['image'][1]} fused at truncation {res['trunc']:g} "
+                    f"({res['triangles_extracted']} triangles before the filter)")
+            stages = ("depth", "integrate", "count", "emit", "filter", "attributes", "write")
+        else:
+            res = mesh.export_mesh(args.ckpt, args.out, iso=mesh.DEFAULT_ISO if args.iso is None else args.iso, **common)
+            what = f"at sigma = {res['iso']:g}"
+            stages = ("grid", "count", "emit", "attributes", "write")
         sec = res["seconds"]
-        print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles at sigma = "
-              f"{res['iso']:g} on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
-              " ".join(f"{k} {sec[k]:.3f} s" for k in ("grid", "count", "emit", "attributes", "write")) + f" -> {res['out']}")
+        print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles {what} "
+              f"on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
+              " ".join(f"{k} {sec[k]:.3f} s" for k in stages) + f" -> {res['out']}")
         return 0
     if args.command == "render":
         from . import render
