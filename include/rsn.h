@@ -600,6 +600,56 @@ int rsn_radam_step(int32_t n_tensors, float* const* params, const float* const* 
                    float* const* exp_avg_sq, const int32_t* sizes, int32_t step, float lr, float beta1, float beta2,
                    float eps, void* stream);
 
+/* ---- guarded optimiser step (additive to ABI 18; opt-in, rsn_radam_step itself is unchanged): clipping of the global
+ * gradient norm (nerfstudio OptimizerConfig.max_norm -> torch.nn.utils.clip_grad_norm_) and the skip of an iteration whose
+ * gradients hold an inf or a NaN (what torch's GradScaler.step does under the reference's mixed_precision=True).  Two
+ * launches, no atomics, no hand-off between workgroups inside a launch, no host read.
+ *
+ * rsn_grad_sumsq: for every tensor t with grads[t] != NULL, fp64 partial sums of squares at fixed positions of `workspace`
+ * (rsn_grad_sumsq_workspace_bytes; 8-byte aligned; it needs no zeroing: every position the next call reads is written by
+ * every call).  Each fp32 element is converted to fp64 and squared there, which is exact.  Tensor t is cut into quads of 4
+ * consecutive elements; with B <= 8 blocks of 256 threads per tensor (B = ceil(max size / 1024), a function of `sizes`
+ * alone), thread k of the 256 B threads adds the squares of quads k, k + 256 B, ... element by element, threads
+ * 0 .. size % 4 - 1 then one element of the tail each; a block sums its threads by a wave butterfly and its four wave sums
+ * in index order and stores the result in slot (t, block).  16-byte aligned tensors are read as 16-byte vectors, any other
+ * element by element: the same sums in the same order.  At most 48 tensors, sizes >= 0. */
+size_t rsn_grad_sumsq_workspace_bytes(int32_t n_tensors, const int32_t* sizes);  /* 0 + rsn_last_error on bad arguments */
+int rsn_grad_sumsq(int32_t n_tensors, const float* const* grads, const int32_t* sizes, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
+#define RSN_GUARD_MAX_TENSORS 48
+/* Written by rsn_radam_step_guarded on every call, in DEVICE memory (8-byte aligned), zero-filled by the caller before the
+ * first call.  Entries of tensors beyond n_tensors or without a gradient are 0. */
+typedef struct rsn_guard_stats {
+  float last_norm;            /* (float)sqrt(total_sq) of this call */
+  float last_coef;            /* the factor the gradients were read with (1 without clipping) */
+  int32_t last_skipped;       /* 1: this call changed no parameter and no moment */
+  int32_t skipped_total;      /* its own previous value, plus one on a skip */
+  int32_t last_skipped_step;  /* `step` of the last skipped call; 0: none so far */
+  int32_t reserved;
+  double per_tensor_sq[RSN_GUARD_MAX_TENSORS];               /* sum of squares per tensor, this call */
+  double per_tensor_sq_at_last_skip[RSN_GUARD_MAX_TENSORS];  /* the same of the last skipped call: which one blew up */
+} rsn_guard_stats;
+
+/* rsn_radam_step_guarded: rsn_radam_step's arguments and update, preceded in every workgroup by the sum of the partials
+ * that rsn_grad_sumsq left in `workspace` for the same (n_tensors, grads, sizes), in a fixed order and in fp64: per tensor
+ * over its slots, then over the tensors in index order (total_sq).  With norm = (float)sqrt(total_sq):
+ *   - skip_nonfinite != 0 and total_sq not finite: no parameter and no moment is written;
+ *   - else coef = min(1.0f, max_norm / (norm + 1e-6f)) in fp32, torch.nn.utils.clip_grad_norm_'s formula (a NaN stays a
+ *     NaN, as torch's clamp keeps it); max_norm <= 0 or +inf: no clipping, coef = 1.  The update is rsn_radam_step's on
+ *     grads[t][i] * coef; with coef = 1 it has rsn_radam_step's bits.  Without skip_nonfinite a non-finite norm simply
+ *     goes through this arithmetic (torch: error_if_nonfinite=False).
+ * grads themselves are NOT rewritten (torch scales .grad in place; nothing in this library reads it after the step).
+ * One workgroup writes *stats.
+ * A skipped call leaves the step counting to the caller, who passes `step` and the learning rate: the Python optimiser
+ * advances both on every call, skipped or not, so a skip costs one step of bias correction against torch's GradScaler,
+ * which does not advance a skipped step -- and in exchange there is no device-side counter, no host read and no optimiser
+ * state beyond RAdam's. */
+int rsn_radam_step_guarded(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, const int32_t* sizes, int32_t step, float lr, float beta1,
+                           float beta2, float eps, float max_norm, int32_t skip_nonfinite, const void* workspace,
+                           size_t workspace_bytes, rsn_guard_stats* stats, void* stream);
+
 
 /* ---- standalone data path (ABI 17): training batches and rendered views from a device-resident posed image set, and the
  * SSIM metric (reference reflect_sampling_nerf_datamanager.py:49-58 next_train, reflect_sampling_nerf_model.py:468-479).

@@ -108,6 +108,17 @@ class ReflectIO(C.Structure):
                  "reflect_coarse", "reflect_fine", "workspace")]
 
 
+RSN_GUARD_MAX_TENSORS = 48
+
+
+class GuardStats(C.Structure):
+    """rsn_guard_stats: what rsn_radam_step_guarded records on the device (train_ops.FusedRAdam.guard_stats reads it)."""
+    _fields_ = [("last_norm", C.c_float), ("last_coef", C.c_float), ("last_skipped", C.c_int32), ("skipped_total", C.c_int32),
+                ("last_skipped_step", C.c_int32), ("reserved", C.c_int32),
+                ("per_tensor_sq", C.c_double * RSN_GUARD_MAX_TENSORS),
+                ("per_tensor_sq_at_last_skip", C.c_double * RSN_GUARD_MAX_TENSORS)]
+
+
 _SIGNATURES = {
     "rsn_abi_version": (C.c_int, []),
     "rsn_last_error": (C.c_char_p, []),
@@ -174,6 +185,11 @@ _SIGNATURES = {
     "rsn_radam_step": (C.c_int, [C.c_int32, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                  C.POINTER(C.c_int32), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                  C.c_void_p]),
+    "rsn_grad_sumsq_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(C.c_int32)]),
+    "rsn_grad_sumsq": (C.c_int, [C.c_int32, C.POINTER(_fp), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rsn_radam_step_guarded": (C.c_int, [C.c_int32, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
+                                         C.POINTER(C.c_int32), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rsn_colsum": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_void_p]),
     "rsn_ray_sum": (C.c_int, [C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_void_p]),
     "rsn_reflect_backward": (C.c_int, [C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]),

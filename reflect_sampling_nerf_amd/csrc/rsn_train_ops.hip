@@ -363,3 +363,227 @@ extern "C" int rsn_radam_step(int32_t n_tensors, float* const* params, const flo
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Guarded RAdam step (opt-in): global gradient-norm clipping and the skip of a step whose gradients hold an inf or a NaN.
+// Two launches.  rsn_grad_sumsq_kernel leaves fp64 partial sums of squares at fixed positions, one per (tensor, block);
+// rsn_radam_guarded_kernel sums them in a fixed order in every block's prologue (a few KB from L2: the launch boundary is the
+// only hand-off between workgroups), derives the clip coefficient or the skip from the total, and applies rsn_radam_kernel's
+// update to g * coef.  No atomics, no flag, no host read; the order of every sum is a function of (sizes, grid) alone.
+// ---------------------------------------------------------------------------------------------------
+#define GUARD_THREADS 256   // threads per block of both kernels
+#define GUARD_VEC 4         // fp32 elements per vector load (16 bytes)
+#define GUARD_SLOTS 8       // most blocks (= partial sums) per tensor: 48 x 8 doubles = 3 KB read per prologue
+
+struct GradSumsqArgs {
+  const float* g[RADAM_MAX_TENSORS];
+  int n[RADAM_MAX_TENSORS];
+  double* partials;  // [n_tensors][GUARD_SLOTS]; block (s, t) writes slot t * GUARD_SLOTS + s
+};
+
+// Block (s, t) of a (slots, n_tensors) grid.  Tensor t is cut into quads of GUARD_VEC consecutive elements; thread k of the
+// slots * GUARD_THREADS threads of the row takes quads k, k + slots * GUARD_THREADS, ... and adds their squares element by
+// element, in fp64 (the square of an fp32 value is exact there); threads 0 .. n % GUARD_VEC - 1 then take one element of the
+// tail each.  A 16-byte aligned tensor reads its quads as float4, any other one element by element: the same sums either way.
+__global__ __launch_bounds__(GUARD_THREADS) void rsn_grad_sumsq_kernel(const GradSumsqArgs a) {
+  __shared__ double sh[GUARD_THREADS / 64];
+  const int t = blockIdx.y;
+  const float* __restrict__ g = a.g[t];
+  if (g == nullptr) return;  // no slot of this tensor is read
+  const int n = a.n[t];
+  const int nq = n / GUARD_VEC;
+  const int k = blockIdx.x * GUARD_THREADS + threadIdx.x;
+  const int stride = gridDim.x * GUARD_THREADS;
+  double acc = 0.0;
+  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    for (int q = k; q < nq; q += stride) {
+      const float4 x = g4[q];
+      acc += (double)x.x * (double)x.x;
+      acc += (double)x.y * (double)x.y;
+      acc += (double)x.z * (double)x.z;
+      acc += (double)x.w * (double)x.w;
+    }
+  } else {
+    for (int q = k; q < nq; q += stride) {
+#pragma unroll
+      for (int e = 0; e < GUARD_VEC; ++e) {
+        const double x = (double)g[(size_t)q * GUARD_VEC + e];
+        acc += x * x;
+      }
+    }
+  }
+  if (k < n - nq * GUARD_VEC) {
+    const double x = (double)g[(size_t)nq * GUARD_VEC + k];
+    acc += x * x;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) a.partials[t * GUARD_SLOTS + blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// blocks along x that rsn_grad_sumsq launches (and rsn_radam_step_guarded reads) for these sizes
+static int guard_slots(int32_t n_tensors, const int32_t* sizes) {
+  int max_n = 0;
+  for (int t = 0; t < n_tensors; ++t)
+    if (sizes[t] > max_n) max_n = sizes[t];
+  const int per_block = GUARD_THREADS * GUARD_VEC;
+  int slots = max_n / per_block + (max_n % per_block != 0);
+  if (slots > GUARD_SLOTS) slots = GUARD_SLOTS;
+  return slots < 1 ? 1 : slots;
+}
+
+extern "C" size_t rsn_grad_sumsq_workspace_bytes(int32_t n_tensors, const int32_t* sizes) {
+  if (n_tensors < 1 || n_tensors > RADAM_MAX_TENSORS || !sizes) {
+    rsn_set_error("n_tensors=%d (max %d) or sizes NULL", n_tensors, RADAM_MAX_TENSORS);
+    return 0;
+  }
+  return (size_t)n_tensors * GUARD_SLOTS * sizeof(double);
+}
+
+extern "C" int rsn_grad_sumsq(int32_t n_tensors, const float* const* grads, const int32_t* sizes, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  RSN_REQUIRE(n_tensors >= 1 && n_tensors <= RADAM_MAX_TENSORS, RSN_ERR_INVALID_ARGUMENT, "n_tensors=%d (max %d)",
+              n_tensors, RADAM_MAX_TENSORS);
+  RSN_REQUIRE(grads && sizes && workspace, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
+  RSN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RSN_ERR_INVALID_ARGUMENT, "workspace is not 8-byte aligned");
+  const size_t need = (size_t)n_tensors * GUARD_SLOTS * sizeof(double);
+  RSN_REQUIRE(workspace_bytes >= need, RSN_ERR_WORKSPACE, "workspace of %zu bytes, needs %zu", workspace_bytes, need);
+  GradSumsqArgs a;
+  for (int t = 0; t < n_tensors; ++t) {
+    RSN_REQUIRE(sizes[t] >= 0, RSN_ERR_INVALID_ARGUMENT, "tensor %d has size %d", t, sizes[t]);
+    a.g[t] = grads[t]; a.n[t] = sizes[t];
+  }
+  a.partials = (double*)workspace;
+  hipLaunchKernelGGL(rsn_grad_sumsq_kernel, dim3(guard_slots(n_tensors, sizes), n_tensors), dim3(GUARD_THREADS), 0,
+                     (hipStream_t)stream, a);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+struct RAdamGuardArgs {
+  RAdamArgs r;
+  const double* partials;  // what rsn_grad_sumsq left: [n_tensors][GUARD_SLOTS], `slots` of each row written
+  int slots;
+  int step;
+  float max_norm;          // <= 0: no clipping
+  int skip_nonfinite;
+  rsn_guard_stats* stats;
+};
+
+__global__ __launch_bounds__(256) void rsn_radam_guarded_kernel(const RAdamGuardArgs a) {
+  __shared__ double sh_sq[RADAM_MAX_TENSORS];
+  __shared__ double sh_total;
+  const int t = blockIdx.y;
+  const bool first = blockIdx.x == 0 && blockIdx.y == 0;  // the block that records the statistics, update or not
+  const bool idle = a.r.g[t] == nullptr || (int)(blockIdx.x * blockDim.x) >= a.r.n[t];
+  if (idle && !first) return;
+  // every block forms the same total from the same partial sums in the same order: per tensor over its slots, then over the
+  // tensors in index order
+  if (threadIdx.x < RADAM_MAX_TENSORS) {
+    double s = 0.0;
+    if ((int)threadIdx.x < a.r.n_tensors && a.r.g[threadIdx.x] != nullptr)
+      for (int k = 0; k < a.slots; ++k) s += a.partials[threadIdx.x * GUARD_SLOTS + k];
+    sh_sq[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < a.r.n_tensors; ++k) s += sh_sq[k];
+    sh_total = s;
+  }
+  __syncthreads();
+  const double total_sq = sh_total;
+  const float norm = (float)sqrt(total_sq);
+  const bool skip = a.skip_nonfinite != 0 && !isfinite(total_sq);
+  float coef = 1.0f;
+  if (a.max_norm > 0.0f) {  // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1), a NaN stays a NaN
+    const float c = a.max_norm / (norm + 1e-6f);
+    coef = c > 1.0f ? 1.0f : c;
+  }
+  if (first) {
+    rsn_guard_stats* st = a.stats;
+    if (threadIdx.x < RADAM_MAX_TENSORS) {
+      st->per_tensor_sq[threadIdx.x] = sh_sq[threadIdx.x];
+      if (skip) st->per_tensor_sq_at_last_skip[threadIdx.x] = sh_sq[threadIdx.x];
+    }
+    if (threadIdx.x == 0) {
+      st->last_norm = norm;
+      st->last_coef = coef;
+      st->last_skipped = skip ? 1 : 0;
+      if (skip) {
+        st->skipped_total = st->skipped_total + 1;
+        st->last_skipped_step = a.step;
+      }
+    }
+  }
+  if (skip || idle) return;
+  float* __restrict__ p = a.r.p[t];
+  const float* __restrict__ g = a.r.g[t];
+  float* __restrict__ m = a.r.m[t];
+  float* __restrict__ v = a.r.v[t];
+  // rsn_radam_kernel's loop on g[i] * coef (coef = 1: the same bits, x * 1.0f is exact)
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.r.n[t]; i += gridDim.x * blockDim.x) {
+    const float gi = g[i] * coef;
+    const float mi = a.r.beta1 * m[i] + (1.0f - a.r.beta1) * gi;
+    const float vi = a.r.beta2 * v[i] + (1.0f - a.r.beta2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const float mhat = mi / a.r.bias_c1;
+    if (a.r.rect >= 0.0f) {
+      const float adaptive = a.r.bias_c2_sqrt / (sqrtf(vi) + a.r.eps);
+      p[i] = p[i] + mhat * a.r.lr * adaptive * a.r.rect * -1.0f;
+    } else {
+      p[i] = p[i] + mhat * a.r.lr * -1.0f;
+    }
+  }
+}
+
+extern "C" int rsn_radam_step_guarded(int32_t n_tensors, float* const* params, const float* const* grads,
+                                      float* const* exp_avg, float* const* exp_avg_sq, const int32_t* sizes, int32_t step,
+                                      float lr, float beta1, float beta2, float eps, float max_norm, int32_t skip_nonfinite,
+                                      const void* workspace, size_t workspace_bytes, rsn_guard_stats* stats, void* stream) {
+  RSN_REQUIRE(n_tensors >= 1 && n_tensors <= RADAM_MAX_TENSORS, RSN_ERR_INVALID_ARGUMENT, "n_tensors=%d (max %d)",
+              n_tensors, RADAM_MAX_TENSORS);
+  RSN_REQUIRE(params && grads && exp_avg && exp_avg_sq && sizes && step >= 1, RSN_ERR_INVALID_ARGUMENT,
+              "a pointer is NULL or step < 1");
+  RSN_REQUIRE(workspace && stats, RSN_ERR_INVALID_ARGUMENT, "workspace or stats is NULL");
+  RSN_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(stats)) & 7) == 0,
+              RSN_ERR_INVALID_ARGUMENT, "workspace or stats is not 8-byte aligned");
+  RSN_REQUIRE(max_norm == max_norm, RSN_ERR_INVALID_ARGUMENT, "max_norm is NaN");
+  const size_t need = (size_t)n_tensors * GUARD_SLOTS * sizeof(double);
+  RSN_REQUIRE(workspace_bytes >= need, RSN_ERR_WORKSPACE, "workspace of %zu bytes, needs %zu", workspace_bytes, need);
+  RAdamGuardArgs a;
+  int max_n = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    a.r.p[t] = params[t]; a.r.g[t] = grads[t]; a.r.m[t] = exp_avg[t]; a.r.v[t] = exp_avg_sq[t]; a.r.n[t] = sizes[t];
+    RSN_REQUIRE(a.r.p[t] && a.r.m[t] && a.r.v[t] && a.r.n[t] >= 0, RSN_ERR_INVALID_ARGUMENT, "tensor %d has NULL state", t);
+    if (a.r.n[t] > max_n) max_n = a.r.n[t];
+  }
+  a.r.n_tensors = n_tensors;
+  a.r.lr = lr; a.r.beta1 = beta1; a.r.beta2 = beta2; a.r.eps = eps;
+  // the step-dependent factors exactly as rsn_radam_step forms them
+  const double b1t = pow((double)beta1, (double)step), b2t = pow((double)beta2, (double)step);
+  const double bias1 = 1.0 - b1t, bias2 = 1.0 - b2t;
+  const double rho_inf = 2.0 / (1.0 - (double)beta2) - 1.0;
+  const double rho_t = rho_inf - 2.0 * step * b2t / bias2;
+  a.r.bias_c1 = (float)bias1;
+  a.r.bias_c2_sqrt = (float)sqrt(bias2);
+  a.r.rect = rho_t > 5.0
+                 ? (float)sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t))
+                 : -1.0f;
+  a.partials = (const double*)workspace;
+  a.slots = guard_slots(n_tensors, sizes);
+  a.step = step;
+  a.max_norm = (max_norm > 0.0f && max_norm <= 3.402823466e+38f) ? max_norm : 0.0f;  // <= 0 or +inf: no clipping
+  a.skip_nonfinite = skip_nonfinite != 0;
+  a.stats = stats;
+  int bx = (max_n + 255) / 256;
+  if (bx > 256) bx = 256;
+  if (bx < 1) bx = 1;
+  hipLaunchKernelGGL(rsn_radam_guarded_kernel, dim3(bx, n_tensors), dim3(256), 0, (hipStream_t)stream, a);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}

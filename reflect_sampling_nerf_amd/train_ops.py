@@ -5,12 +5,15 @@ FusedLoss   -- get_loss_dict (reference model.py:346-430) on ANY outputs dict: r
 FusedRayLoss-- the same for outputs of this package's training graph: the per-sample normal terms were already reduced
                per ray in the compositing epilogue, the loss is two launches over R rays.
 FusedRAdam  -- torch.optim.RAdam semantics (reference config.py:50-53) as one multi-tensor launch (rsn_radam_step),
-               with the reference's exponential learning-rate decay (lr 1e-3 -> 1e-4 over 50 000 steps).
+               with the reference's exponential learning-rate decay (lr 1e-3 -> 1e-4 over 50 000 steps).  Opt-in guard:
+               global gradient-norm clipping and the skip of a step with non-finite gradients, two launches
+               (rsn_grad_sumsq, rsn_radam_step_guarded), still without a host read.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, List, Optional
+import math
+from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -151,11 +154,44 @@ def exponential_decay_lr(step: int, lr_init: float = 1e-3, lr_final: float = 1e-
     return float(lr_init * (lr_final / lr_init) ** t)
 
 
+# rsn_grad_sumsq's grid (csrc/rsn_train_ops.hip: GUARD_THREADS, GUARD_VEC, GUARD_SLOTS; test_guard_cpu compares): a tensor of more
+# than GUARD_SLOTS * GUARD_THREADS * GUARD_VEC elements is walked by a grid-stride loop
+GUARD_THREADS, GUARD_VEC, GUARD_SLOTS = 256, 4, 8
+
+
 class FusedRAdam:
-    """RAdam (torch.optim.RAdam semantics, weight_decay 0) over a fixed parameter list, one kernel launch per step."""
+    """RAdam (torch.optim.RAdam semantics, weight_decay 0) over a fixed parameter list, one kernel launch per step.
+
+    The guard (both parts off by default; with both off step() is the one launch above):
+      max_grad_norm   -- clip the global L2 norm of all gradients to this value before the update, as
+                         torch.nn.utils.clip_grad_norm_ does (nerfstudio's OptimizerConfig.max_norm); None or inf: no clipping.
+                         The update reads g * coef; .grad itself is not rewritten (torch rewrites it).
+      skip_nonfinite  -- a step whose gradients hold an inf or a NaN changes no parameter and no moment (what torch's
+                         GradScaler.step does for the reference under mixed_precision=True).
+    With either on, step() is two launches, rsn_grad_sumsq and rsn_radam_step_guarded, and still reads nothing back: the
+    decision is taken on the device.  guard_stats() is the explicit read.
+
+    A skipped step still advances step_count, hence the learning-rate schedule and the bias-correction `t`: both count
+    iterations.  torch's scaler does not advance `t` on a skipped step; the difference is one step of bias correction per
+    skip.  In exchange there is no device-side counter, no host read, and no optimiser state beyond torch.optim.RAdam's:
+    state_dict() is the same with and without the guard, and so is a bit-exact resume.
+
+    names: optional parameter names, in the order of `params` (all of them, before the requires_grad filter); guard_stats()
+    keys its per-parameter entries by them."""
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-15,
-                 lr_final: Optional[float] = None, max_steps: int = 50000):
+                 lr_final: Optional[float] = None, max_steps: int = 50000, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False, names: Optional[Sequence[str]] = None):
+        params = list(params)
+        if names is not None and len(names) != len(params):
+            raise ValueError(f"{len(names)} names for {len(params)} parameters")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:  # a NaN fails this too
+            raise ValueError(f"max_grad_norm must be above 0 (None: no clipping), got {max_grad_norm!r}")
+        self.names: Optional[List[str]] = None if names is None else [str(n) for n, p in zip(names, params) if p.requires_grad]
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard_ws: Optional[Tensor] = None     # rsn_grad_sumsq's partial sums; allocated by the first guarded step
+        self._guard_stats: Optional[Tensor] = None  # one rsn_guard_stats, as int32 words
         self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
         self.lr, self.betas, self.eps = lr, betas, eps
         self.lr_final, self.max_steps = lr_final, max_steps
@@ -230,6 +266,46 @@ class FusedRAdam:
             return self.lr
         return exponential_decay_lr(self.step_count, self.lr, self.lr_final, self.max_steps)
 
+    @property
+    def guarded(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _guarded_launches(self, lib, grads, lr: float) -> None:
+        n, dev = len(self.params), self.params[0].device
+        if self._guard_ws is None or self._guard_ws.device != dev:
+            nbytes = lib.rsn_grad_sumsq_workspace_bytes(n, self._sizes)
+            if nbytes == 0:
+                check(-1)  # raises with the message rsn_last_error() holds
+            self._guard_ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)  # written before it is read, every call
+            self._guard_stats = torch.zeros(C.sizeof(_abi.GuardStats) // 4, dtype=torch.int32, device=dev)
+        ws, ws_bytes = ptr(self._guard_ws), self._guard_ws.numel() * 8
+        g = _ptr_array(grads)
+        check(lib.rsn_grad_sumsq(n, g, self._sizes, ws, ws_bytes, ops._stream()))
+        max_norm = 0.0 if self.max_grad_norm is None or math.isinf(self.max_grad_norm) else self.max_grad_norm
+        check(lib.rsn_radam_step_guarded(n, _ptr_array([p.data for p in self.params]), g, _ptr_array(self.exp_avg),
+                                         _ptr_array(self.exp_avg_sq), self._sizes, self.step_count, lr, self.betas[0],
+                                         self.betas[1], self.eps, max_norm, int(self.skip_nonfinite), ws, ws_bytes,
+                                         ptr(self._guard_stats), ops._stream()))
+
+    def guard_stats(self) -> Optional[dict]:
+        """What the last guarded step recorded on the device, by ONE explicit device-to-host read (step() never calls this):
+        last_norm (the global gradient norm), last_coef (the factor the gradients were read with), last_skipped (that step),
+        skipped_total, last_skipped_step (the step_count of the last skipped step, None: none so far), per_tensor_sq and
+        per_tensor_sq_at_last_skip (sum of squares per parameter of the last step / of the last skipped step, keyed by
+        `names`, else by index) and nonfinite_at_last_skip (the keys whose sum was not finite then).  None before the
+        first guarded step."""
+        if self._guard_stats is None:
+            return None
+        st = _abi.GuardStats.from_buffer_copy(self._guard_stats.cpu().numpy().tobytes())
+        keys = self.names if self.names is not None else list(range(len(self.params)))
+        at_skip = {k: float(st.per_tensor_sq_at_last_skip[i]) for i, k in enumerate(keys)}
+        return {"last_norm": float(st.last_norm), "last_coef": float(st.last_coef), "last_skipped": bool(st.last_skipped),
+                "skipped_total": int(st.skipped_total),
+                "last_skipped_step": int(st.last_skipped_step) if st.last_skipped_step > 0 else None,
+                "per_tensor_sq": {k: float(st.per_tensor_sq[i]) for i, k in enumerate(keys)},
+                "per_tensor_sq_at_last_skip": at_skip,
+                "nonfinite_at_last_skip": [k for k, v in at_skip.items() if not math.isfinite(v)] if st.skipped_total > 0 else []}
+
     @torch.no_grad()
     def step(self) -> None:
         lib = _abi.load_library()
@@ -239,9 +315,12 @@ class FusedRAdam:
             self.exp_avg = [m.to(p.device) for m, p in zip(self.exp_avg, self.params)]
             self.exp_avg_sq = [v.to(p.device) for v, p in zip(self.exp_avg_sq, self.params)]
         grads = [None if p.grad is None else ops._f32c(p.grad) for p in self.params]
-        check(lib.rsn_radam_step(len(self.params), _ptr_array([p.data for p in self.params]), _ptr_array(grads),
-                                 _ptr_array(self.exp_avg), _ptr_array(self.exp_avg_sq), self._sizes, self.step_count,
-                                 lr, self.betas[0], self.betas[1], self.eps, ops._stream()))
+        if not self.guarded:
+            check(lib.rsn_radam_step(len(self.params), _ptr_array([p.data for p in self.params]), _ptr_array(grads),
+                                     _ptr_array(self.exp_avg), _ptr_array(self.exp_avg_sq), self._sizes, self.step_count,
+                                     lr, self.betas[0], self.betas[1], self.eps, ops._stream()))
+        else:
+            self._guarded_launches(lib, grads, lr)
         # The kernel updated the parameters behind torch's back: bump their version counters so that consumers keyed on
         # Tensor._version (the Field's packed-weights cache) see the change.
         touched = [p for p in self.params if p.grad is not None]

@@ -1,6 +1,6 @@
 """Standalone training and evaluation on Blender-format scenes, without nerfstudio.
 
-    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR]
+    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite]
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
@@ -22,6 +22,12 @@ would.  With --deterministic the continuation has the uninterrupted run's bits; 
 pass and loss do, and later steps differ as two uninterrupted default runs differ (the order of the weight-gradient atomics).  A
 checkpoint without `rsn_run` (the reference's ns-train, or an older trainer) continues with the arguments given and a fresh jitter
 stream.  Multi-GPU training is not offered here.
+
+`train --max-grad-norm X` clips the global gradient norm to X before every optimiser step (nerfstudio's OptimizerConfig.max_norm),
+and `--skip-nonfinite` leaves parameters and moments untouched on a step whose gradients hold an inf or a NaN (what torch's
+GradScaler does for `ns-train` under mixed precision); both are off by default and decided on the device (FusedRAdam).  A guarded
+run's log lines carry the gradient norm, the clip factor and the number of skipped steps, and the first line after a skip names the
+parameters whose gradients were not finite.  Both settings are recorded in the checkpoint and come back with --resume.
 
 `export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
 the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
@@ -138,9 +144,14 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     tr.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible run: weight gradients reduced in a fixed order (slower flush, one 68 MB workspace)")
     tr.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    tr.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global gradient norm to X before every optimiser step (default: no clipping)")
+    tr.add_argument("--skip-nonfinite", action="store_true",
+                    help="a step whose gradients hold an inf or a NaN changes no parameter and no optimiser moment")
     tr.add_argument("--resume", default=None, metavar="PATH",
                     help="continue from this step-*.ckpt, or from the newest one in this run directory; --steps stays the total, and "
-                         "--rays / --mma / --seed / --deterministic come from the checkpoint unless given")
+                         "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite come from the checkpoint "
+                         "unless given")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
     ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json")
     ev.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
@@ -357,14 +368,22 @@ def resolve_checkpoint(path: str) -> str:
     return latest_checkpoint(path) if os.path.isdir(path) else path
 
 
-def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device) -> dict:
+def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, max_grad_norm: Optional[float] = None,
+                   skip_nonfinite: Optional[bool] = None) -> dict:
     """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
     bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
-    seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one."""
+    seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one.
+    max_grad_norm / skip_nonfinite (the optimiser's guard) are recorded only when set: an unguarded run's entry has the keys it
+    always had."""
     dev = torch.device(device)
-    return {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
-            "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
-            "cpu_rng_state": torch.get_rng_state()}
+    state = {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
+             "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+             "cpu_rng_state": torch.get_rng_state()}
+    if max_grad_norm is not None:
+        state["max_grad_norm"] = float(max_grad_norm)
+    if skip_nonfinite:
+        state["skip_nonfinite"] = True
+    return state
 
 
 def save_checkpoint(path: str, model, optimizer, step: int, run_state: Optional[dict] = None) -> str:
@@ -424,8 +443,9 @@ def load_checkpoint(path: str, model_config=None, device="cuda:0"):
 
 # ------------------------------------------------------------------------------------------------ train
 def _resolve_run_settings(given: dict, recorded: Optional[dict]):
-    """Each of rays / mma / seed / deterministic: the caller's value if given, else the checkpoint's, else the fresh-run default
-    (deterministic: None = the model's own default).  -> (settings, one line per given value that departs from the checkpoint's)."""
+    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite: the caller's value if given, else the checkpoint's,
+    else the fresh-run default (deterministic: None = the model's own default; the two guard settings: None = off).
+    -> (settings, one line per given value that departs from the checkpoint's)."""
     out, notes = {}, []
     for k, v in given.items():
         rec = None if recorded is None else recorded.get(k)
@@ -437,10 +457,22 @@ def _resolve_run_settings(given: dict, recorded: Optional[dict]):
     return out, notes
 
 
+def _guard_log(stats: dict, skips_logged: int) -> str:
+    """The guard's part of a log line from FusedRAdam.guard_stats(); names the non-finite parameters of the last skipped step when
+    steps were skipped since the line that reported `skips_logged` of them.  The optimiser's step_count of a step is its
+    iteration number + 1."""
+    text = f"  gnorm {stats['last_norm']:.4e} clip {stats['last_coef']:.4g} skipped {stats['skipped_total']}"
+    if stats["skipped_total"] > skips_logged:
+        bad = ", ".join(str(k) for k in stats["nonfinite_at_last_skip"])
+        text += f" (step {stats['last_skipped_step'] - 1}: non-finite gradients in {bad})"
+    return text
+
+
 def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, mma: Optional[str] = None, save_every: int = 1000,
           log_every: int = 100, seed: Optional[int] = None, device="cuda:0", model_config=None,
           log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None, resume: Optional[str] = None,
-          on_step: Optional[Callable[[int, torch.Tensor], None]] = None) -> str:
+          on_step: Optional[Callable[[int, torch.Tensor], None]] = None, max_grad_norm: Optional[float] = None,
+          skip_nonfinite: Optional[bool] = None) -> str:
     """Train on `scene` (a data.BlenderScene) up to iteration `steps` (the total, nerfstudio's max_num_iterations); returns the path
     of the last checkpoint.  Checkpoints at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer
     does the same).  The loss is read back only every log_every steps: the iterations in between never wait for the GPU.
@@ -448,6 +480,11 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     checkpoint's when resuming, else the model's default, i.e. the environment's RSN_DETERMINISTIC); the line that starts the run
     records all four.  on_step(step, loss) is called after every step with the 0-d device tensor of train_step, which nothing here
     reads back for it.
+
+    max_grad_norm / skip_nonfinite: FusedRAdam's guard (None: the checkpoint's when resuming, else off).  With either set, the
+    log_every lines -- where the loss is read back anyway -- also read the optimiser's guard_stats(): the last step's gradient
+    norm and clip factor and the number of steps skipped so far; the first such line after a skip names the parameters whose
+    gradients were not finite on the last skipped step.  The steps in between read nothing.
 
     resume: a step-*.ckpt or a run directory (its latest).  A checkpoint of step k continues at k + 1 with the same checkpoint names
     and save_every rule; k >= steps - 1 is a ValueError.  Model (strict, as load_checkpoint) and FusedRAdam state come from the file.
@@ -470,7 +507,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
 
     if steps < 1:
         raise ValueError(f"steps must be >= 1, got {steps}")
-    given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic}
+    given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic, "max_grad_norm": max_grad_norm,
+             "skip_nonfinite": skip_nonfinite}
     first, model, ckpt, recorded = 0, None, None, None
     if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
         resume = resolve_checkpoint(resume)
@@ -484,6 +522,7 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
             raise ValueError(f"{resume}: {RUN_STATE_KEY} version {recorded.get('version')!r}, this trainer reads {RUN_STATE_VERSION}")
     cfg, notes = _resolve_run_settings(given, recorded)
     rays, mma, seed, deterministic = cfg["rays"], cfg["mma"], cfg["seed"], cfg["deterministic"]
+    max_grad_norm, skip_nonfinite = cfg["max_grad_norm"], bool(cfg["skip_nonfinite"])
     if mma not in MMA_CHOICES:
         raise ValueError(f"mma must be one of {MMA_CHOICES}, got {mma!r}")
     dev = torch.device(device)
@@ -495,8 +534,14 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         model.set_deterministic(deterministic)
     dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed)
     params = model.get_param_groups()["fields"]
-    optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000)  # config.py:50-53
+    name_of = {id(p): n for n, p in model.named_parameters()}
+    optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000,  # config.py:50-53
+                           max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, names=[name_of[id(p)] for p in params])
     settings = f"steps {steps} rays {rays} mma {mma} seed {seed} deterministic {model.deterministic}"
+    if max_grad_norm is not None:
+        settings += f" max_grad_norm {max_grad_norm:g}"
+    if skip_nonfinite:
+        settings += " skip_nonfinite True"
     if resume is None:
         if log is not None:
             log(f"train: {settings}")
@@ -515,6 +560,7 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
                 "stream, the continuation is not bit-exact")
         ckpt = None  # the host copy of the checkpoint is not needed past this point
     last = None
+    skips_logged = 0
     t0 = time.time()
     for step in range(first, steps):
         ray_bundle, batch = dm.next_train(step)
@@ -522,10 +568,15 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         if on_step is not None:
             on_step(step, loss)
         if log is not None and log_every and (step % log_every == 0 or step == steps - 1):
-            log(f"step {step:7d}  loss {float(loss):.6f}  lr {optimizer.current_lr():.3e}  {time.time() - t0:8.1f} s")
+            line = f"step {step:7d}  loss {float(loss):.6f}  lr {optimizer.current_lr():.3e}  {time.time() - t0:8.1f} s"
+            if optimizer.guarded:
+                stats = optimizer.guard_stats()  # one more read where the loss is read anyway
+                line += _guard_log(stats, skips_logged)
+                skips_logged = stats["skipped_total"]
+            log(line)
         if (save_every and step > 0 and step % save_every == 0) or step == steps - 1:
             last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
-                                   make_run_state(seed, rays, mma, model.deterministic, dev))
+                                   make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -598,6 +649,8 @@ def main(argv=None) -> int:
     cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
     occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
     export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
+    if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
+        ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
     if not torch.cuda.is_available():
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
@@ -605,7 +658,8 @@ def main(argv=None) -> int:
         scene = load_blender_split(args.data, "train", args.scale_factor)
         print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}")
         train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
-              log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume)
+              log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume,
+              max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None)
         return 0
     if args.command == "export-mesh":
         from . import mesh
