@@ -33,8 +33,8 @@ __device__ __forceinline__ unsigned int pack2(float a, float b) {
 }
 
 
-// sin / cos with the exact fp32 Cody-Waite reduction of sincos_big and degree-5 / degree-6 least-squares polynomials (4e-6 / 2e-7 absolute
-// on |r| <= 0.87): the feature is rounded to bf16 next
+// sin / cos with the exact fp32 Cody-Waite reduction of sincos_big and degree-5 / degree-6 least-squares polynomials (3.9e-6 / 1.8e-6
+// absolute on |r| <= 0.87, float32 emulation over 4e6 arguments up to 8.3e5): the feature is rounded to bf16 next
 __device__ __forceinline__ float sincos_bf16(float a, int quad) {
   const float q = rintf(a * 0.63661977236758134308f);
   float r = __builtin_fmaf(-q, 1.5707963705062866f, a);
