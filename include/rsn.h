@@ -876,6 +876,73 @@ int rsn_occupancy_compact_samples(int32_t n_rays, const int32_t* n_dev, int32_t 
 int rsn_scatter_level(int32_t n_points, const int32_t* n_live, const int32_t* sample_index, const rsn_field_outputs* src,
                       const rsn_field_outputs* dst, void* stream);
 
+
+/* ---- point cloud: depth maps of posed pinhole cameras into one deduplicated, deterministically ordered set of points (additive to
+ * ABI 18: no existing call changes).  A point is where the model starts a reflected ray: origin + depth * direction of a pixel.
+ *
+ * Inputs, in the layouts of rsn_tsdf_integrate: c2w fp32 [n_views,3,4] (row-major, device) and one set of intrinsics height, width,
+ * fx, fy, cx, cy; depth fp32 [n_views, height*width] (device), row-major, the EUCLIDEAN distance along the ray; accumulation fp32
+ * [n_views, height*width] (device) or NULL; view0 >= 0, the number of views that earlier calls have already processed.  A grid of
+ * nx * ny * nz CELLS, every dimension >= 1, with origin3 / spacing3 as HOST arrays: cell (i, j, k) spans
+ * origin + spacing * (i..i+1, j..j+1, k..k+1) and has flat index (k*ny + j)*nx + i.
+ *
+ * Global pixel index: pixel (y, x) of view v of a call has g = ((view0 + v)*height + y)*width + x; (view0 + n_views)*height*width
+ * must not exceed 2^31 - 1.
+ *
+ * The ray (o, d) of a pixel is the one written above rsn_sample_camera_rays, from the same device function that call and
+ * rsn_camera_rays_image run: equal (pose, intrinsics, y, x) give bit-identical rays.
+ *
+ * Candidate rule.  Pixel p = y*width + x of view v is a candidate if and only if all of the following hold; every arithmetic step
+ * is one correctly rounded fp32 operation, none contracted into a fused multiply-add:
+ *   1. D = depth[v][p] is finite and D > 0.
+ *   2. accumulation is NULL, or accumulation[v][p] >= min_accumulation (a NaN fails).
+ *   3. For each of the up to four neighbours (y-1, x), (y+1, x), (y, x-1), (y, x+1) inside the image of the same view whose depth
+ *      Dn is finite: NOT fabsf(D - Dn) > edge * fminf(D, Dn) -- one subtract, one multiply, one compare.  edge = +inf switches the
+ *      test off (a NaN product compares false).  The neighbour's accumulation plays no part, so a silhouette pixel next to a ray
+ *      that ran to its far end is rejected: that is the point of the test.
+ *   4. The point lies inside the grid:  t_a = D * d_a,  p_a = o_a + t_a,  q_a = (p_a - origin_a) / spacing_a  for a = 0, 1, 2, and
+ *      0 <= q_a < n_a on all three axes, compared as floats with n_a converted to float (a NaN fails).  cell_a = (int)floorf(q_a).
+ *
+ * rsn_pointcloud_workspace_bytes: HOST only; the bytes rsn_pointcloud_select needs for a call of this shape (8 per 256 pixels + 1
+ * per pixel, rounded up), never 0 for a valid shape; 0 with a message when n_views < 0, height < 1, width < 1 or
+ * n_views*height*width > 2^31 - 1.
+ *
+ * rsn_pointcloud_mark: owner is int32 [nz, ny, nx] on the device, filled by the caller with 0x7fffffff before the first call.  For
+ * every candidate, owner[cell] = min(owner[cell], g) by an integer atomic minimum -- the only atomic of these calls; an integer
+ * minimum does not depend on the order, so owner is deterministic.  owner == NULL means no thinning: evaluating the rule would
+ * leave no trace, so the call checks its arguments and launches nothing.
+ *
+ * rsn_pointcloud_select: a candidate is KEPT if and only if owner == NULL or owner[cell] == g.  *n_points (device int32) = the
+ * number of kept pixels of this call; rows 0 .. *n_points-1 of pixel_index (int32 [n_views*height*width]) hold the kept pixels' g
+ * in ascending order and the same rows of positions (fp32 [n_views*height*width, 3]) their (p_0, p_1, p_2), bit for bit.  Rows at
+ * and past the count are left unwritten.  The compaction is stable and uses no atomics, as in rsn_occupancy_cull.  workspace:
+ * device memory of at least rsn_pointcloud_workspace_bytes bytes, 4-byte aligned, contents irrelevant (RSN_ERR_WORKSPACE when
+ * workspace_bytes is less).  n_candidates (device int32, or NULL) receives the number of candidates of this call, before the owner
+ * test; without an owner it equals *n_points.  n_views == 0 launches nothing and sets both counts to 0; n_points must never be NULL.
+ * Cost: two passes over the pixels and, between them, one workgroup that scans the counts of the tiles of 256 pixels, 256 tiles per
+ * step -- a serial term of n_views*height*width / 65536 steps, 78 for eight 800 x 800 views and 32768 at the largest shape.
+ *
+ * Two properties follow.  A later call has higher g, so it never takes a cell from an earlier one: views 0..n-1 in one mark + select
+ * pair keep exactly the pixels, in exactly the order, of any split into consecutive pairs that share owner and advance view0 (the
+ * rows of the pairs concatenated).  And with thinning every cell that holds a candidate gets exactly one point, its candidate with
+ * the lowest g.
+ *
+ * Both calls: RSN_ERR_INVALID_ARGUMENT before any launch, with the reason in rsn_last_error(): a grid dimension below 1; height or
+ * width below 1; n_views < 0 or view0 < 0; the index bound above exceeded; fx or fy not finite or zero; min_accumulation NaN; edge
+ * NaN or negative; a NULL c2w, depth, origin3 or spacing3 when n_views > 0 (and for select a NULL workspace, pixel_index or
+ * positions); a spacing that is not finite or not positive, or an origin that is not finite.  RSN_ERR_UNSUPPORTED for
+ * nx*ny*nz > 2^27.  No allocation, no synchronisation and no host read. */
+size_t rsn_pointcloud_workspace_bytes(int32_t n_views, int32_t height, int32_t width);
+int rsn_pointcloud_mark(int32_t n_views, const float* c2w, int32_t height, int32_t width, float fx, float fy, float cx, float cy,
+                        const float* depth, const float* accumulation, int32_t view0, int32_t nx, int32_t ny, int32_t nz,
+                        const float* origin3, const float* spacing3, float min_accumulation, float edge, int32_t* owner,
+                        void* stream);
+int rsn_pointcloud_select(int32_t n_views, const float* c2w, int32_t height, int32_t width, float fx, float fy, float cx, float cy,
+                          const float* depth, const float* accumulation, int32_t view0, int32_t nx, int32_t ny, int32_t nz,
+                          const float* origin3, const float* spacing3, float min_accumulation, float edge, const int32_t* owner,
+                          void* workspace, size_t workspace_bytes, int32_t* n_points, int32_t* n_candidates, int32_t* pixel_index,
+                          float* positions, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

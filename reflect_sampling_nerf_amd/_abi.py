@@ -240,6 +240,14 @@ _SIGNATURES = {
                                                 C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_float,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p]),
     "rsn_scatter_level": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(FieldOutputs), C.POINTER(FieldOutputs), C.c_void_p]),
+    "rsn_pointcloud_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rsn_pointcloud_mark": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "rsn_pointcloud_select": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        _fp, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -4,6 +4,7 @@
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
+    python -m reflect_sampling_nerf_amd.trainer export-pointcloud --ckpt FILE|DIR --out cloud.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--resolution 512] [--min-accumulation 0.5] [--edge 0.05 | --no-edge] [--no-thin]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
     (eval and render: [--skip-empty | --skip-empty-samples [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
 
@@ -37,6 +38,13 @@ With `--method tsdf` the surface is instead the one the model itself renders: it
 fused into a truncated signed distance volume on the same grid, and its zero level is extracted, the part between observed grid
 vertices kept, and coloured as before.  No density level is involved.  The defaults, a truncation of 4 grid spacings and
 --min-weight 1, are starting points from an experiment on analytic depth maps of a sphere, not measured on a scene.
+
+`export-pointcloud` writes the surface the model renders as points (pointcloud.py): one point per pixel of the depth maps rendered
+from the cameras of --data's split or of --poses, origin + depth_fine * direction -- where the model starts its reflected rays --, for
+the pixels whose accumulation reaches --min-accumulation, whose depth is no silhouette edge (--edge) and whose point lies in --bounds;
+a grid of --resolution cells per axis keeps one point per cell (--no-thin: all).  The file is a PLY with the vertex layout of
+export-mesh and no face element; a point's colour is the field's diffuse colour there, not a rendered pixel.  The defaults (512 cells
+per axis, accumulation 0.5, edge 0.05) are starting points, not measured on a scene.
 
 `render` draws a checkpoint from viewpoints of the user's choosing (render.py): an orbit around a centre, or the poses of a
 transforms-format file, optionally with poses interpolated in between.  Every frame is a PNG panel of the chosen channels side by
@@ -189,6 +197,32 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                     help="tsdf: views a grid vertex needs to count as observed; surface between unobserved vertices is dropped "
                          "(default 1: a starting point from the same experiment, not measured on a scene)")
     ex.add_argument("--ray-chunk", type=int, default=None, metavar="R", help="tsdf: rays per chunk of the depth pass (default 4096)")
+    pc = sub.add_parser("export-pointcloud", help="write the surface a checkpoint's model renders as a coloured point cloud (PLY without faces)")
+    pc.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
+    pc.add_argument("--out", required=True, help="output file (binary little-endian PLY, vertex element only)")
+    pc.add_argument("--data", default=None, metavar="DIR", help="scene directory; the cameras of transforms_{split}.json")
+    pc.add_argument("--split", default="train", help="the split of --data (default train)")
+    pc.add_argument("--poses", default=None, metavar="FILE.json",
+                    help="transforms-format file with frames[].transform_matrix, camera_angle_x and w / h")
+    pc.add_argument("--scale-factor", type=float, default=1.0, help="scale of the translations read from --data / --poses")
+    pc.add_argument("--max-views", type=int, default=None, metavar="N", help="use N evenly spaced views of the file (default: all)")
+    pc.add_argument("--downscale", type=int, default=1, metavar="K",
+                    help="render every depth map at 1/K of the cameras' size, intrinsics scaled alike (default 1)")
+    pc.add_argument("--resolution", type=int, default=512, metavar="N",
+                    help="cells per axis of the grid that keeps one point per cell (default 512: a starting point, not measured on a scene)")
+    pc.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="box the points must lie in (default -1.5 -1.5 -1.5 1.5 1.5 1.5, nerfstudio's Blender scene box)")
+    pc.add_argument("--min-accumulation", type=float, default=0.5, metavar="A",
+                    help="a pixel needs this accumulation (default 0.5: a starting point, not measured on a scene)")
+    edge = pc.add_mutually_exclusive_group()
+    edge.add_argument("--edge", type=float, default=0.05, metavar="E",
+                      help="drop a pixel whose depth differs from a neighbour's by more than E times the smaller of the two "
+                           "(default 0.05: a starting point, not measured on a scene)")
+    edge.add_argument("--no-edge", action="store_true", help="keep the pixels on depth edges")
+    pc.add_argument("--no-thin", action="store_true", help="keep every candidate pixel instead of one per grid cell")
+    pc.add_argument("--mma", choices=MMA_CHOICES, default="f32", help="matrix-core arithmetic of the field kernels (default f32)")
+    pc.add_argument("--ray-chunk", type=int, default=None, metavar="R", help="rays per chunk of the depth pass (default 4096)")
+    pc.add_argument("--chunk", type=int, default=None, help="points per field launch of the attribute pass (default 262144)")
     from .render import CHANNELS, DEFAULT_CHANNELS, DEFAULT_CHUNK
 
     rn = sub.add_parser("render", help="render a camera path from a checkpoint as PNG panels of colour and material maps")
@@ -288,8 +322,6 @@ def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
     """The cameras of an `export-mesh` command line: None for --method density (the tsdf flags are an error then), else {"c2w"
     [F,3,4], "width", "height", "fx", "fy", "cx", "cy"} after --max-views and --downscale.  Host work only (JSON and one image
     header).  What the command line leaves open and no file settles is an argparse error that names the option."""
-    from . import render
-
     if args.method != "tsdf":
         given = ["--" + f.replace("_", "-") for f in TSDF_ONLY_FLAGS if getattr(args, f, None) is not None]
         if args.downscale != 1:
@@ -299,8 +331,24 @@ def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
         return None
     if args.iso is not None:
         ap.error("export-mesh: --iso is the density route's level; --method tsdf has none")
+    cameras = export_cameras_from_args(ap, args, "export-mesh", "--method tsdf needs")
+    if args.trunc is not None and not (math.isfinite(args.trunc) and args.trunc > 0.0):
+        ap.error(f"export-mesh: --trunc {args.trunc}: need a finite value above 0")
+    if args.min_weight is not None and not math.isfinite(args.min_weight):
+        ap.error(f"export-mesh: --min-weight {args.min_weight}: need a finite value")
+    if args.ray_chunk is not None and args.ray_chunk < 1:
+        ap.error("export-mesh: --ray-chunk must be >= 1")
+    return cameras
+
+
+def export_cameras_from_args(ap: argparse.ArgumentParser, args, command: str, needs: str) -> dict:
+    """The cameras --data [--split] / --poses [--scale-factor] [--max-views] [--downscale] name, for the export commands: {"c2w"
+    [F,3,4], "width", "height", "fx", "fy", "cx", "cy"}.  Errors are argparse errors of `command`; `needs` words the one about
+    missing cameras."""
+    from . import render
+
     if (args.poses is None) == (args.data is None):
-        ap.error("export-mesh: --method tsdf needs cameras: give --data DIR or --poses FILE.json (one of them)")
+        ap.error(f"{command}: {needs} cameras: give --data DIR or --poses FILE.json (one of them)")
     if args.poses is not None:
         src = render.load_poses(args.poses, args.scale_factor)
     else:
@@ -315,15 +363,9 @@ def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
                     src["width"], src["height"] = (int(v) for v in img.size)
     for name in ("width", "height", "camera_angle_x"):
         if src[name] is None:
-            ap.error(f"export-mesh: the cameras' {name} is unknown: the file needs camera_angle_x and w / h (or, with --data, a first image)")
+            ap.error(f"{command}: the cameras' {name} is unknown: the file needs camera_angle_x and w / h (or, with --data, a first image)")
     if args.downscale < 1 or (args.max_views is not None and args.max_views < 1):
-        ap.error("export-mesh: --downscale and --max-views must be >= 1")
-    if args.trunc is not None and not (math.isfinite(args.trunc) and args.trunc > 0.0):
-        ap.error(f"export-mesh: --trunc {args.trunc}: need a finite value above 0")
-    if args.min_weight is not None and not math.isfinite(args.min_weight):
-        ap.error(f"export-mesh: --min-weight {args.min_weight}: need a finite value")
-    if args.ray_chunk is not None and args.ray_chunk < 1:
-        ap.error("export-mesh: --ray-chunk must be >= 1")
+        ap.error(f"{command}: --downscale and --max-views must be >= 1")
     c2w = src["c2w"]
     if args.max_views is not None and args.max_views < len(c2w):  # N evenly spaced views, the first one among them
         c2w = c2w[(np.arange(args.max_views, dtype=np.int64) * len(c2w)) // args.max_views]
@@ -332,6 +374,32 @@ def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
     sx, sy = width / src["width"], height / src["height"]
     return {"c2w": np.ascontiguousarray(c2w), "width": int(width), "height": int(height), "fx": fx * sx, "fy": fy * sy,
             "cx": cx * sx, "cy": cy * sy}
+
+
+def resolve_pointcloud_args(ap: argparse.ArgumentParser, args) -> dict:
+    """The settings of an `export-pointcloud` command line: {"cameras" (as resolve_export_cameras returns them), "resolution",
+    "bounds", "min_accumulation", "edge" (math.inf with --no-edge), "thin", "ray_chunk", "chunk"}.  What the command line alone
+    settles is checked before any file is opened; every error is an argparse error that names the option."""
+    from . import mesh
+
+    if args.resolution < 1 or args.resolution ** 3 > 2 ** 27:
+        ap.error(f"export-pointcloud: --resolution {args.resolution}: need 1 <= N <= 512")
+    if not (math.isfinite(args.edge) and args.edge >= 0.0):
+        ap.error(f"export-pointcloud: --edge {args.edge}: need a finite value >= 0 (--no-edge switches the test off)")
+    if math.isnan(args.min_accumulation):
+        ap.error(f"export-pointcloud: --min-accumulation {args.min_accumulation}: need a number")
+    b = args.bounds
+    if b is not None and not (all(math.isfinite(x) for x in b) and all(b[3 + a] > b[a] for a in range(3))):
+        ap.error("export-pointcloud: --bounds needs X0 Y0 Z0 X1 Y1 Z1 with every upper bound above its lower one")
+    if args.ray_chunk is not None and args.ray_chunk < 1:
+        ap.error("export-pointcloud: --ray-chunk must be >= 1")
+    if args.chunk is not None and args.chunk < 1:
+        ap.error("export-pointcloud: --chunk must be >= 1")
+    cameras = export_cameras_from_args(ap, args, "export-pointcloud", "needs")
+    return {"cameras": cameras, "resolution": int(args.resolution), "bounds": mesh.DEFAULT_BOUNDS if b is None else tuple(float(x) for x in b),
+            "min_accumulation": float(args.min_accumulation), "edge": math.inf if args.no_edge else float(args.edge),
+            "thin": not args.no_thin, "ray_chunk": mesh.DEFAULT_RAY_CHUNK if args.ray_chunk is None else args.ray_chunk,
+            "chunk": mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk}
 
 
 # ------------------------------------------------------------------------------------------------ model and checkpoints
@@ -649,6 +717,7 @@ def main(argv=None) -> int:
     cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
     occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
     export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
+    cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
         ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
     if not torch.cuda.is_available():
@@ -681,6 +750,17 @@ def main(argv=None) -> int:
         print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles {what} "
               f"on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
               " ".join(f"{k} {sec[k]:.3f} s" for k in stages) + f" -> {res['out']}")
+        return 0
+    if args.command == "export-pointcloud":
+        from . import pointcloud
+
+        res = pointcloud.export_pointcloud(args.ckpt, args.out, cloud_args.pop("cameras"), mma=args.mma, **cloud_args)
+        sec = res["seconds"]
+        print(f"{res['checkpoint']} (step {res['step']}): a grid of {' x '.join(str(n) for n in res['resolution'])} cells, "
+              f"accumulation >= {res['min_accumulation']:g}, edge {res['edge']:g}, {'one point per cell' if res['thin'] else 'every candidate'}; " +
+              " ".join(f"{k} {sec[k]:.3f} s" for k in ("depth", "mark", "select", "attributes", "write")))
+        print(f"{res['points']} points from {res['views']} depth maps {res['image'][0]} x {res['image'][1]} "
+              f"({res['candidates']} candidates) -> {res['out']}")
         return 0
     if args.command == "render":
         from . import render
