@@ -943,6 +943,43 @@ int rsn_pointcloud_select(int32_t n_views, const float* c2w, int32_t height, int
                           void* workspace, size_t workspace_bytes, int32_t* n_points, int32_t* n_candidates, int32_t* pixel_index,
                           float* positions, void* stream);
 
+
+/* ---- texture atlas: where on an indexed triangle mesh every texel of a per-triangle atlas samples the field (additive to ABI 18:
+ * no existing call changes).  The field's material maps are then baked at those points, finer than the mesh's vertices.
+ *
+ * Layout.  One pair of triangles gets one square of P x P texels, P = texels >= 4 -- nerfstudio's "custom" per-triangle unwrap with
+ * a gutter, so that bilinear filtering never mixes two triangles.  T triangles need S = ceil(T / 2) squares; with Q =
+ * squares_per_row squares in a row (the caller's choice, 2*Q*Q >= T; the package takes Q = max(1, ceil(sqrt(S))) in integers) the
+ * texture is N x N texels, N = Q*P, row-major with image row 0 at the top.  Texel (row, col) has flat index row*N + col and
+ *   sx = col / P, a = col % P, sy = row / P, b = row % P;  square q = sy*Q + sx holds triangle 2q (lower) and 2q + 1 (upper).
+ * Texel centres sit at integer (a, b).
+ *                            lower triangle 2q                        upper triangle 2q + 1
+ *   corners 0, 1, 2 at       (0,0), (P-3,0), (0,P-3)                  (P-1,P-1), (2,P-1), (P-1,2)
+ *   owns the texels with     a + b <= P-2                             a + b >= P-1
+ *   live if additionally     a <= P-3 and b <= P-3                    a >= 2 and b >= 2
+ *   u                        (float)a / (float)(P-3)                  (float)(P-1-a) / (float)(P-3)
+ *   v                        (float)b / (float)(P-3)                  (float)(P-1-b) / (float)(P-3)
+ * A texel is UNUSED when it is owned but not live, when its triangle's index is >= T, or when any vertex index of its triangle lies
+ * outside [0, V) -- then positions is not read for it.  An unused texel gets face = -1 and zeros in point and footprint.
+ * A live texel of triangle t with vertices p0, p1, p2 = positions[triangles[t][0..2]] gets face = t and, per axis,
+ *   w0 = (1 - u) - v,   p = (w0*p0 + u*p1) + v*p2
+ *   h  = max(|p1 - p0|, |p2 - p0|) / (float)(P-3),   each length sqrt((dx*dx + dy*dy) + dz*dz)
+ * in point and footprint; every difference, product, sum, quotient and square root is one correctly rounded fp32 operation, none
+ * contracted into a fused multiply-add.  The live texels with u + v > 1 are the gutter: real samples slightly beyond the
+ * hypotenuse, in the triangle's plane.  Two properties (tests/test_texture_cpu.py checks both): (a) every texel that bilinear
+ * filtering reads with a weight above zero from a point inside a triangle's corner triangle is a live texel of that triangle;
+ * (b) no texel is live for two triangles.  Corner k of a triangle at texel centre (col_k, row_k) has the OBJ coordinate
+ * vt = ((col_k + 0.5) / N, 1 - (row_k + 0.5) / N).
+ *
+ * positions fp32 [n_vertices,3] and triangles int32 [n_triangles,3] on the device; face int32 [N*N], point fp32 [N*N,3], footprint
+ * fp32 [N*N].  One lane per texel; every output word has one owner: no atomics, so two runs give the same bits; no allocation and
+ * no synchronisation; no word outside the three outputs' N*N rows is written.  Degenerate triangles give finite outputs.
+ * RSN_ERR_INVALID_ARGUMENT before any launch, with the reason in rsn_last_error(): texels < 4; squares_per_row < 1; n_vertices < 0
+ * or n_triangles < 0; 2*squares_per_row^2 < n_triangles; with n_triangles > 0 a NULL triangles, face, point or footprint, or a NULL
+ * positions when n_vertices > 0.  RSN_ERR_UNSUPPORTED for N > 16384.  n_triangles == 0 launches nothing. */
+int rsn_texture_points(int32_t n_vertices, const float* positions, int32_t n_triangles, const int32_t* triangles, int32_t texels,
+                       int32_t squares_per_row, int32_t* face, float* point, float* footprint, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

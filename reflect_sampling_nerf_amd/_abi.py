@@ -248,6 +248,7 @@ _SIGNATURES = {
                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                         _fp, C.c_void_p]),
+    "rsn_texture_points": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _fp, _fp, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

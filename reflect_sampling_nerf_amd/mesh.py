@@ -21,6 +21,11 @@ Model.get_surface_outputs) from the given cameras and fuses the maps into a trun
 of include/rsn.h) -> tsdf_volume -> the same extractor at level 0 -> drop_unobserved (without it a second shell appears inside
 the object, where the observed band ends) -> vertex_attributes -> write_ply.  Its defaults, a truncation of 4 grid spacings and
 min_weight 1, are starting points from an experiment on analytic depth maps of a sphere; they have not been measured on a scene.
+
+    ... export-mesh --out mesh.obj --texture [--texels 8] [--min-footprint F]
+
+With --texture either route ends in write_obj of texture.py instead of write_ply: the same four quantities, sampled per texel of a
+per-triangle atlas instead of per vertex (texture_atlas -> bake_textures).  Its defaults have not been measured on a scene either.
 """
 from __future__ import annotations
 
@@ -313,8 +318,9 @@ class _Stages:
 def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256, bounds: Sequence[float] = DEFAULT_BOUNDS,
                 iso: float = DEFAULT_ISO, mma: str = "f32", chunk: int = DEFAULT_CHUNK, device="cuda:0",
                 model_config=None, method: str = "density", cameras: Optional[dict] = None, trunc: Optional[float] = None,
-                min_weight: float = DEFAULT_MIN_WEIGHT, views_per_launch: int = 8, ray_chunk: int = DEFAULT_RAY_CHUNK) -> dict:
-    """Checkpoint (a step-*.ckpt, or a run directory: its newest) -> PLY at `out`.  -> dict with the counts, the grid, the method
+                min_weight: float = DEFAULT_MIN_WEIGHT, views_per_launch: int = 8, ray_chunk: int = DEFAULT_RAY_CHUNK,
+                texture: bool = False, texels: int = 8, min_footprint: Optional[float] = None) -> dict:
+    """Checkpoint (a step-*.ckpt, or a run directory: its newest) -> PLY at `out` (texture=True: a textured OBJ, see below).  -> dict with the counts, the grid, the method
     and the seconds per stage.
     method "density": the iso-surface of the field's density at `iso`; stages: grid evaluation, count, emit, attributes on the
     device; write on the host.
@@ -322,8 +328,19 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
     "width", "height", "fx", "fy", "cx", "cy"} (what trainer.resolve_export_cameras returns); trunc: the truncation distance in
     world units (None: DEFAULT_TRUNC_SPACINGS x the largest spacing); min_weight: the views a grid vertex needs to count as
     observed.  Stages: depth (the depth passes), integrate, count, emit, filter, attributes; write.  The dict also holds the view
-    count, trunc, min_weight and the counts before the filter."""
+    count, trunc, min_weight and the counts before the filter.
+    texture=True (either method): `out` must end in .obj and becomes a textured OBJ with its MTL and four PNG maps beside it
+    (texture.py) instead of a PLY; texels: the side of the square of texels a pair of triangles gets; min_footprint: the smallest
+    footprint a texel is queried with (None: the largest spacing / 8) -- both defaults are starting points, not measured on a
+    scene.  The stages atlas and bake join the seconds, texture_size, texels, live_texels, min_footprint and files the dict."""
     from .trainer import load_checkpoint, resolve_checkpoint
+
+    if texture:
+        from . import texture as tex
+
+        tex.obj_file_set(out)    # the argument errors come before the checkpoint is read
+        tex.atlas_shape(0, texels)
+        footprint_lo, _ = tex.footprint_bounds(grid_frame(bounds, resolution)[2], min_footprint)
 
     if method not in ("density", "tsdf"):
         raise ValueError(f"method {method!r}: density or tsdf")
@@ -357,6 +374,14 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
             stages("filter")
         mesh.update(vertex_attributes(field, mesh["positions"], spacing, chunk))
         stages("attributes")
+        if texture:
+            attributes = tex.field_attributes(field, spacing, footprint_lo, chunk)
+            atlas = tex.texture_atlas(mesh["positions"], mesh["triangles"], texels)
+            stages("atlas")
+            maps = tex.bake_textures(attributes, atlas, chunk)
+            stages("bake")
+            extra.update(texture_size=int(atlas["size"]), texels=int(texels), live_texels=int(atlas["live"].numel()),
+                         min_footprint=footprint_lo)
         seconds = stages.seconds()
         if method == "tsdf":  # the fuse stage, split into its two kinds of work by the per-launch events
             del seconds["fuse"]
@@ -364,7 +389,10 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
                        "integrate": sum(e[1].elapsed_time(e[2]) for e in events) / 1000.0, **seconds}
             extra["integrate_launches"] = len(events)
     t0 = time.time()
-    write_ply(out, mesh)
+    if texture:
+        extra["files"] = tex.write_obj(out, mesh, atlas["uv"], maps)
+    else:
+        write_ply(out, mesh)
     seconds["write"] = time.time() - t0
     res = {"checkpoint": ckpt, "step": step, "out": out, "vertices": int(mesh["positions"].shape[0]),
            "triangles": int(mesh["triangles"].shape[0]), "resolution": [nx, ny, nz], "bounds": [float(b) for b in bounds],

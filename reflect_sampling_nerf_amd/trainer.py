@@ -4,6 +4,7 @@
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
+    python -m reflect_sampling_nerf_amd.trainer export-mesh ... --out mesh.obj --texture [--texels 8] [--min-footprint F]
     python -m reflect_sampling_nerf_amd.trainer export-pointcloud --ckpt FILE|DIR --out cloud.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--resolution 512] [--min-accumulation 0.5] [--edge 0.05 | --no-edge] [--no-thin]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
     (eval and render: [--skip-empty | --skip-empty-samples [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
@@ -38,6 +39,11 @@ With `--method tsdf` the surface is instead the one the model itself renders: it
 fused into a truncated signed distance volume on the same grid, and its zero level is extracted, the part between observed grid
 vertices kept, and coloured as before.  No density level is involved.  The defaults, a truncation of 4 grid spacings and
 --min-weight 1, are starting points from an experiment on analytic depth maps of a sphere, not measured on a scene.
+With `--texture` either method writes a textured OBJ instead of the PLY (texture.py): NAME.obj, NAME.mtl and four PNG maps -- diffuse
+colour, tint, roughness and the object-space predicted normal -- in which every pair of triangles owns a square of --texels x --texels
+texels and the field is queried once per texel, with a footprint no smaller than --min-footprint.  The maps are the field's material
+decomposition, not a rendered colour.  The defaults, 8 texels and the largest grid spacing / 8, are starting points, not measured on
+a scene.
 
 `export-pointcloud` writes the surface the model renders as points (pointcloud.py): one point per pixel of the depth maps rendered
 from the cameras of --data's split or of --poses, origin + depth_fine * direction -- where the model starts its reflected rays --, for
@@ -197,6 +203,15 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                     help="tsdf: views a grid vertex needs to count as observed; surface between unobserved vertices is dropped "
                          "(default 1: a starting point from the same experiment, not measured on a scene)")
     ex.add_argument("--ray-chunk", type=int, default=None, metavar="R", help="tsdf: rays per chunk of the depth pass (default 4096)")
+    ex.add_argument("--texture", action="store_true",
+                    help="write a textured OBJ (--out NAME.obj, with NAME.mtl and four PNG maps: diffuse colour, tint, roughness, "
+                         "object-space normal) instead of a PLY: the field sampled per texel of a per-triangle atlas")
+    ex.add_argument("--texels", type=int, default=None, metavar="P",
+                    help="texture: side of the square of texels a pair of triangles gets, at least 4 (default 8: a starting point, "
+                         "not measured on a scene)")
+    ex.add_argument("--min-footprint", type=float, default=None, metavar="F",
+                    help="texture: the smallest footprint, in world units, a texel is queried with (default the largest grid spacing "
+                         "/ 8: a starting point, not measured on a scene)")
     pc = sub.add_parser("export-pointcloud", help="write the surface a checkpoint's model renders as a coloured point cloud (PLY without faces)")
     pc.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
     pc.add_argument("--out", required=True, help="output file (binary little-endian PLY, vertex element only)")
@@ -316,6 +331,33 @@ def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
 
 
 TSDF_ONLY_FLAGS = ("data", "poses", "max_views", "trunc", "min_weight", "ray_chunk")
+TEXTURE_ONLY_FLAGS = ("texels", "min_footprint")
+
+
+def resolve_texture_args(ap: argparse.ArgumentParser, args) -> None:
+    """The texture flags of an `export-mesh` command line: --texels and --min-footprint need --texture; with it --out must end in
+    .obj, --texels be at least 4 and --min-footprint lie above 0 and not above the largest spacing of the grid --bounds and
+    --resolution make.  Host work only; what cannot work is an argparse error that names the option."""
+    from . import mesh, texture
+
+    if not args.texture:
+        given = ["--" + f.replace("_", "-") for f in TEXTURE_ONLY_FLAGS if getattr(args, f, None) is not None]
+        if given:
+            ap.error(f"export-mesh: {' '.join(given)} need(s) --texture")
+        return
+    if not args.out.lower().endswith(".obj"):
+        ap.error(f"export-mesh: --texture writes an OBJ with its MTL and PNG maps: --out {args.out} must end in .obj")
+    if args.texels is not None and not 4 <= args.texels <= texture.MAX_SIZE:
+        ap.error(f"export-mesh: --texels {args.texels}: need a value from 4 to {texture.MAX_SIZE}")
+    if args.min_footprint is not None:
+        try:
+            spacing = mesh.grid_frame(mesh.DEFAULT_BOUNDS if args.bounds is None else args.bounds, args.resolution)[2]
+        except ValueError:
+            return  # a grid that cannot be: the export says so
+        try:
+            texture.footprint_bounds(spacing, args.min_footprint)
+        except ValueError as e:
+            ap.error(f"export-mesh: --min-footprint {args.min_footprint}: {e}")
 
 
 def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
@@ -716,6 +758,8 @@ def main(argv=None) -> int:
     given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
     cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
     occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
+    if args.command == "export-mesh":
+        resolve_texture_args(ap, args)
     export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
     cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
@@ -735,6 +779,8 @@ def main(argv=None) -> int:
 
         common = dict(resolution=args.resolution, bounds=mesh.DEFAULT_BOUNDS if args.bounds is None else tuple(args.bounds),
                       mma=args.mma, chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
+        if args.texture:
+            common.update(texture=True, texels=8 if args.texels is None else args.texels, min_footprint=args.min_footprint)
         if args.method == "tsdf":
             res = mesh.export_mesh(args.ckpt, args.out, method="tsdf", cameras=export_cameras, trunc=args.trunc,
                                    min_weight=mesh.DEFAULT_MIN_WEIGHT if args.min_weight is None else args.min_weight,
@@ -747,6 +793,10 @@ def main(argv=None) -> int:
             what = f"at sigma = {res['iso']:g}"
             stages = ("grid", "count", "emit", "attributes", "write")
         sec = res["seconds"]
+        if args.texture:
+            stages = stages[:-1] + ("atlas", "bake", "write")
+            what += (f", textured with {res['texture_size']} x {res['texture_size']} texels ({res['live_texels']} live, "
+                     f"{res['texels']} per square side, footprint >= {res['min_footprint']:g})")
         print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles {what} "
               f"on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
               " ".join(f"{k} {sec[k]:.3f} s" for k in stages) + f" -> {res['out']}")
