@@ -72,8 +72,16 @@ typedef struct rsn_field_desc {
  *                   relative): fp32-equivalent results at 6/16 of the fp32-MFMA cost;
  *   RSN_MMA_BF16X3  2-way split, 3 products (~2^-16 relative): reduced precision, opt-in only;
  *   RSN_MMA_BF16    plain bf16 operands (1 product, 8 mantissa bits), fp32 accumulate: BASELINE configs[3]
- *                   ("bf16 MFMA hidden GEMMs"); encode, heads' activations and compositing stay fp32. */
-typedef enum rsn_mma_mode { RSN_MMA_F32 = 0, RSN_MMA_BF16X6 = 1, RSN_MMA_BF16X3 = 2, RSN_MMA_BF16 = 3 } rsn_mma_mode;
+ *                   ("bf16 MFMA hidden GEMMs"); encode, heads' activations and compositing stay fp32;
+ *   RSN_MMA_F32_FOLDED  RSN_MMA_F32 with field_output_bottleneck folded into the x part of mlp_mid.layers.0 in the
+ *                   TRAINING kernels (two affine maps with nothing between them are one): W_c = W_mid[:, 34:] W_b,
+ *                   b_c = b_mid + W_mid[:, 34:] b_b, formed with fp64 accumulation when the weights are packed.  The packed
+ *                   buffer is the RSN_MMA_F32 one with the folded segments appended; rsn_field_saved.bott and
+ *                   rsn_field_grads_out.d_bott are neither written nor read (NULL is fine); the parameter gradients of the
+ *                   two layers come from rsn_unfold_bottleneck_grads.  Eval launches run the RSN_MMA_F32 kernels. */
+typedef enum rsn_mma_mode {
+  RSN_MMA_F32 = 0, RSN_MMA_BF16X6 = 1, RSN_MMA_BF16X3 = 2, RSN_MMA_BF16 = 3, RSN_MMA_F32_FOLDED = 4
+} rsn_mma_mode;
 
 /* Parameters in torch.nn.Linear layout: weight [out,in] row-major, bias [out]; names follow the
  * reference Field's state_dict (reflect_sampling_nerf_field.py:54-86).  field_output_low (:67) is
@@ -112,7 +120,7 @@ typedef struct rsn_field_outputs {
 typedef struct rsn_field_saved {
   float* enc;     /* [N,104]  encoded inputs (input of trunk layer 0), kernel slot order                   */
   float* act;     /* [L,N,W]  post-ReLU output of trunk layer l (act[L-1] = embedding)                       */
-  float* bott;    /* [N,W]    bottleneck output                                                              */
+  float* bott;    /* [N,W]    bottleneck output (RSN_MMA_F32_FOLDED: not touched, may be NULL)                */
   float* sh;      /* [N,40]   attenuated SH-34 inputs of mlp_mid, kernel slot order                          */
   float* hid;     /* [N,128]  mlp_mid hidden (post-ReLU)                                                     */
   float* heads;   /* [N,8]    raw normal head (3), raw roughness head (1), mid RGB (3), pad                  */
@@ -239,7 +247,8 @@ typedef struct rsn_field_grads_in {
 typedef struct rsn_field_grads_out {
   float* dz_rgb;    /* [N,4]   field_output_mid pre-sigmoid (3 live columns)                          */
   float* da_mid;    /* [N,128] mlp_mid pre-activation                      (bf16 under RSN_MMA_BF16)   */
-  float* d_bott;    /* [N,W]   bottleneck output                           (bf16 under RSN_MMA_BF16)   */
+  float* d_bott;    /* [N,W]   bottleneck output                           (bf16 under RSN_MMA_BF16;   *
+                     *          RSN_MMA_F32_FOLDED: not touched, may be NULL)                           */
   float* dz_heads;  /* [N,16]  columns: 0 density, 1-3 normals, 4-6 diff, 8 roughness, 12-14 tint      */
   float* dy;        /* [L,N,W] pre-activation of trunk layer l             (bf16 under RSN_MMA_BF16)   */
   float* d_input;   /* [N]     d loss / d pixel_area (frustum) or d sqradius (inf); need_input_grad only */
@@ -497,6 +506,17 @@ int rsn_weight_grad_jobs_ordered(int32_t n_segments, const int64_t* n_points_max
                                  const int32_t* per_count, int32_t n_jobs, const rsn_wgrad_job* jobs, int32_t ld_dy, int32_t n_out,
                                  int32_t ld_x, int32_t k_in, int32_t mma_mode, int32_t operand_bf16, void* workspace,
                                  size_t workspace_bytes, void* stream);
+
+/* Parameter gradients of field_output_bottleneck and of the x part of mlp_mid.layers.0 from the reductions of the FOLDED training
+ * step (RSN_MMA_F32_FOLDED), with W_mx = mid_w[:, 34:34+width] (row stride ld_mid) and n_mid = the rows of mlp_mid.layers.0:
+ *   c [n_mid, width] (row stride ld_c) = sum over points of d a_mid (x) act[L-1]      s [n_mid] = sum over points of d a_mid
+ *   d_bott_w [width, width] += W_mx^T c         d_bott_b [width] += W_mx^T s         d_mid_w[:, 34:34+width] += c W_b^T + s (x) b_b
+ * (d_mid_w: the gradient tensor of mlp_mid.layers.0.weight, row stride ld_mid; bott_w [width, width], bott_b [width]).  `width` is the
+ * width of the PARAMETER tensors.  fp64 accumulation in ascending index order, one thread per output element, one fp32 rounding of
+ * the sum and one fp32 add into the gradient: the same inputs give the same bits.  Linear in (c, s): one call per reduction. */
+int rsn_unfold_bottleneck_grads(int32_t width, int32_t n_mid, const float* c, int32_t ld_c, const float* s, const float* mid_w,
+                                int32_t ld_mid, const float* bott_w, const float* bott_b, float* d_bott_w, float* d_bott_b,
+                                float* d_mid_w, void* stream);
 
 /* get_loss_dict on per-ray quantities only (training step: the per-sample normal terms arrive reduced per ray from
  * rsn_composite): losses8[k] = the UNSCALED terms (0-3 MSE means of rgb4[k] against image; 4,5 = sum_r pn_loss_ray2[lv][r];

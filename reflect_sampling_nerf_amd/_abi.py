@@ -15,6 +15,7 @@ RSN_NUM_FREQS = 16
 RSN_SPACING_UNIFORM = 0
 RSN_SPACING_RECIPROCAL = 1
 RSN_MMA_F32, RSN_MMA_BF16X6, RSN_MMA_BF16X3, RSN_MMA_BF16 = 0, 1, 2, 3
+RSN_MMA_F32_FOLDED = 4  # exact fp32 training with field_output_bottleneck folded into mlp_mid (a descriptor value, not a Field mode)
 RSN_VIS_RGB, RSN_VIS_UNIT, RSN_VIS_GRAY, RSN_VIS_LUT = 0, 1, 2, 3
 
 _fp = C.c_void_p  # device float*
@@ -173,6 +174,8 @@ _SIGNATURES = {
     "rsn_weight_grad_jobs_ordered": (C.c_int, [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                                C.c_int32, C.POINTER(WGradJob), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rsn_unfold_bottleneck_grads": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp,
+                                              C.c_void_p]),
     "rsn_loss_forward_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, C.POINTER(_fp), C.POINTER(_fp),
                                             C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(C.c_float), _fp,
                                             C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_void_p]),

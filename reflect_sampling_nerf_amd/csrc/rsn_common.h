@@ -82,6 +82,12 @@ struct RsnPackedLayout {
   // RSN_MMA_BF16X6 at width 256 (rsn_field_x6_train.hip): the same stream with every fragment as THREE 1 KiB pieces -- the lo, mid
   // and hi bf16 parts of the fp32 weights, in that order (small products first); q_pf = 3 and every group count above is x 3
   int q_pf;                           // 1 KiB pieces per fragment of q_stream: 1 (plain bf16) or 3 (split-bf16)
+  // RSN_MMA_F32_FOLDED only (0 = absent), appended behind everything above: the bottleneck folded into mlp_mid's x part.
+  //   fold_wc / fold_bc  W_c = W_mid[:, 34:] W_b as a dense [mid_width, param_width] tensor and b_c [mid_width] (rsn_fold_kernel
+  //                      writes them, the pack jobs of the three segments below read them like parameters)
+  //   w_fold / b_fold    [W_c ; heads]: K = W, nbm + 1 row blocks (the heads block last), and its bias
+  //   wT_fold            [W_c ; heads]^T: rows W, K = mid_width + 32 (the K-concatenation of wT_bh)
+  size_t fold_wc, fold_bc, w_fold, b_fold, wT_fold;
   size_t total;                       // floats
 };
 #define RSN_RING_GROUP_FRAGS 16   // 1 KiB weight fragments per ring group

@@ -61,6 +61,8 @@ static int launch_field_jobs(const rsn_field_desc* d, const float* packed, Field
   do {                                                                                                           \
     if (train && mode == RSN_MMA_BF16)  /* reduced-precision training: plain bf16 operands, fp32 accumulate */  \
       hipLaunchKernelGGL((rsn_field_kernel<NBV, true, 3>), dim3((unsigned)grid), dim3(256), 0, st, J);            \
+    else if (train && mode == RSN_MMA_F32_FOLDED)  /* exact fp32, the bottleneck folded into mlp_mid */         \
+      hipLaunchKernelGGL((rsn_field_kernel<NBV, true, 4>), dim3((unsigned)grid), dim3(256), 0, st, J);      \
     else if (train)  /* BF16X3 is an eval-only opt-in: training falls back to exact fp32 */                      \
       hipLaunchKernelGGL((rsn_field_kernel<NBV, true, 0>), dim3((unsigned)grid), dim3(256), 0, st, J);            \
     else                                                                                                         \
@@ -82,8 +84,9 @@ static int launch_field(const rsn_field_desc* d, const float* pk, FieldJob& a, v
 // The entry points: NULL-check the struct pointers, fill a zeroed FieldJob with the kind's filler (frustum and inf, which the
 // backward has too: rsn_field_common.h), launch.  A training evaluation adds `saved` and this requirement (get_inf_color
 // has no analytic normals, so its wording leaves them out).
-static int require_saved(const char* pfx, const rsn_field_saved* s, bool inf) {
-  RSN_REQUIRE(s->act && s->enc && s->bott && s->sh && s->hid && s->heads && s->relu_bits, RSN_ERR_INVALID_ARGUMENT,
+static int require_saved(const rsn_field_desc* d, const char* pfx, const rsn_field_saved* s, bool inf) {
+  const bool bott = s->bott || d->mma_mode == RSN_MMA_F32_FOLDED;  // the folded kernels have no bottleneck row
+  RSN_REQUIRE(s->act && s->enc && bott && s->sh && s->hid && s->heads && s->relu_bits, RSN_ERR_INVALID_ARGUMENT,
               "%straining needs every saved-activation buffer%s", pfx, inf ? "" : " (normals may be NULL)");
   return RSN_OK;
 }
@@ -112,7 +115,7 @@ extern "C" int rsn_field_forward_train_jobs(const rsn_field_desc* desc, const fl
     const JobPrefix pfx(k);
     RSN_REQUIRE(q.kind == 0 || q.kind == 1, RSN_ERR_INVALID_ARGUMENT, "job %d: kind=%d", k, q.kind);
     RSN_REQUIRE(q.n_rays >= 0 && q.saved, RSN_ERR_INVALID_ARGUMENT, "job %d: n_rays=%d / saved is NULL", k, q.n_rays);
-    RSN_TRY(require_saved(pfx.s, q.saved, false));
+    RSN_TRY(require_saved(desc, pfx.s, q.saved, false));
     a.saved = *q.saved;
     if (q.kind == 0) {
       RSN_REQUIRE(q.n_samples >= 1 && q.out, RSN_ERR_INVALID_ARGUMENT, "job %d: n_samples=%d / out is NULL", k, q.n_samples);
@@ -134,9 +137,9 @@ extern "C" int rsn_field_forward_gaussians_train(const rsn_field_desc* desc, con
   RSN_REQUIRE(desc && out && saved, RSN_ERR_INVALID_ARGUMENT, "desc/out/saved is NULL");
   FieldJob a = {};
   RSN_TRY(fill_gaussians(a, n_points, means, cov_diag, view_dirs, out, embedding));
-  RSN_REQUIRE(desc->mma_mode == RSN_MMA_F32, RSN_ERR_UNSUPPORTED,
+  RSN_REQUIRE(desc->mma_mode == RSN_MMA_F32 || desc->mma_mode == RSN_MMA_F32_FOLDED, RSN_ERR_UNSUPPORTED,
               "training-mode evaluation of explicit Gaussians runs on the exact-fp32 kernels only (mma_mode %d)", desc->mma_mode);
-  RSN_TRY(require_saved("", saved, false));
+  RSN_TRY(require_saved(desc, "", saved, false));
   a.saved = *saved;
   return launch_field(desc, packed, a, stream);
 }
@@ -162,7 +165,7 @@ extern "C" int rsn_field_forward_frustum_train(const rsn_field_desc* desc, const
   RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
   FieldJob a = {};
   RSN_TRY(rsn_fill_frustum(a, "", n_rays, n_dev, n_samples, origins, directions, pixel_area, euclid_bins));
-  RSN_TRY(require_saved("", saved, false));
+  RSN_TRY(require_saved(desc, "", saved, false));
   a.out = *out;
   a.saved = *saved;
   return launch_field(desc, packed, a, stream);
@@ -186,7 +189,7 @@ extern "C" int rsn_field_forward_inf_train(const rsn_field_desc* desc, const flo
   RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
   FieldJob a = {};
   RSN_TRY(rsn_fill_inf(a, "", n_rays, n_dev, directions, sqradius, out_rgb));
-  RSN_TRY(require_saved("", saved, true));
+  RSN_TRY(require_saved(desc, "", saved, true));
   a.out.color = out_rgb;
   a.saved = *saved;
   a.saved.normals = nullptr;

@@ -23,8 +23,14 @@
 #include "rsn_field_common.h"
 #include "rsn_field_bwd_common.h"
 
-template <int NB, int MODE>
+// FOLD (RSN_MMA_F32_FOLDED, see rsn_field_kernel.h): stages 2 and 3 are ONE GEMM d emb = [W_c ; W_heads]^T [d a_mid ; dz_heads] over
+// K = 128 + 32; no bottleneck gradient row exists (gout.d_bott is neither written nor read).
+// MMA: the rsn_mma_mode the kernel serves -- 0 exact fp32, 1 split-bf16, 3 plain bf16, 4 = 0 with FOLD.
+template <int NB, int MMA>
 __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
+  constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;
+  constexpr int MODE = FOLD ? 0 : MMA;  // the arithmetic of the GEMM loops
+  constexpr int HIT = FOLD ? 16 : NB * 4;  // first K-iteration of the heads gradients in the slab (FOLD: behind d a_mid's 16)
   constexpr int XITS = (NB * 4 > 16) ? NB * 4 : 16;
   constexpr int WAVE_F4 = (XITS + RSN_AUX_ITS) * 64;
   constexpr int W = NB * 32;
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
       store_masked_bits<4, SBF>(acc, X, mb, h, rb_epi(a.gout.da_mid, p0 * 128, 128));
     }
     // ---------------- stage 2: d bottleneck = W_mid[:, 34:]^T d a_mid -----------------
-    {
+    if constexpr (!FOLD) {
       f32x16 acc[NB];
       zero_acc<NB>(acc);
       gemm_mode<MODE, NB, NB, true>(acc, pk + P.L.wT_mid_x, pk + P.L.hT_mid_x, X, 16, ln, rb_loop(a.gout.da_mid, p0 * 128, 128));
@@ -99,10 +105,10 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
       // heads rows 8q + 4h + j for q = 0, 1: this half's two rows, h and h + 2
       const float4 q0 = head_grad_row<false>(h == 0 ? 0 : 1, a, P.density_bias, pc, live, hg);
       const float4 q1 = head_grad_row<false>(h == 0 ? 2 : 3, a, P.density_bias, pc, live, hg);
-      X[(NB * 4 + 0) * 64] = q0;
-      X[(NB * 4 + 1) * 64] = q1;
-      X[(NB * 4 + 2) * 64] = zero4;
-      X[(NB * 4 + 3) * 64] = zero4;
+      X[(HIT + 0) * 64] = q0;
+      X[(HIT + 1) * 64] = q1;
+      X[(HIT + 2) * 64] = zero4;
+      X[(HIT + 3) * 64] = zero4;
       if (valid && a.gout.dz_heads) {
         *reinterpret_cast<float4*>(a.gout.dz_heads + pc * 16 + 4 * h) = q0;
         *reinterpret_cast<float4*>(a.gout.dz_heads + pc * 16 + 8 + 4 * h) = q1;
@@ -112,7 +118,10 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
       __builtin_amdgcn_sched_barrier(0);
       f32x16 acc[NB];
       zero_acc<NB>(acc);
-      gemm_mode<MODE, NB, NB, true>(acc, pk + P.L.wT_bh, pk + P.L.hT_bh, X, NB * 4 + 4, ln, rb_loop(a.gout.d_bott, p0 * W, W));
+      if constexpr (FOLD)  // reads (and keeps) d a_mid: its rows end at K-iteration 16, the heads gradients behind them are not stored
+        gemm_mode<MODE, NB, NB, true>(acc, pk + P.L.wT_fold, pk + P.L.hT_bh, X, 16 + 4, ln, rb_loop(a.gout.da_mid, p0 * 128, 128));
+      else
+        gemm_mode<MODE, NB, NB, true>(acc, pk + P.L.wT_bh, pk + P.L.hT_bh, X, NB * 4 + 4, ln, rb_loop(a.gout.d_bott, p0 * W, W));
       store_masked_bits<NB, SBF>(acc, X, mb, h, rb_epi(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));
     }
     // ---------------- stage 4: trunk, layers L-1 .. 1 -----------------
@@ -195,6 +204,8 @@ static int launch_bwd_jobs(const rsn_field_desc* d, const float* packed, BwdJob*
     if (x6) hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 1>), dim3((unsigned)grid), dim3(256), 0, st, J);    \
     else if (d->mma_mode == RSN_MMA_BF16)  /* reduced-precision training sweeps (bf16 operands, fp32 accumulate) */ \
       hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 3>), dim3((unsigned)grid), dim3(256), 0, st, J);              \
+    else if (d->mma_mode == RSN_MMA_F32_FOLDED)  /* exact fp32, the bottleneck folded into mlp_mid */           \
+      hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 4>), dim3((unsigned)grid), dim3(256), 0, st, J);        \
     else hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 0>), dim3((unsigned)grid), dim3(256), 0, st, J);       \
   } while (0)
   switch (d->width) {

@@ -10,8 +10,18 @@
 #include "rsn_field_common.h"
 
 // ------------------------------------------------------------------------------------------------
-template <int NB, bool TRAIN, int MODE>
+// FOLD (exact-fp32 training, RSN_MMA_F32_FOLDED): field_output_bottleneck has no activation and feeds only the x part of
+// mlp_mid.layers.0, so the two are ONE affine map W_c = W_mx W_b, b_c = b_mid + W_mx b_b (rsn_fold_kernel, rsn_pack.hip).  The
+// N = W + 32 GEMM over the trunk output becomes N = 128 + 32 (the four mlp_mid blocks, started from b_c, and the heads block), the
+// SH part then accumulates into the same four blocks, and the K = W GEMM over the bottleneck row is gone with the row itself
+// (saved.bott is neither written nor read).  Heads, sigma and normals keep their bits: same K order, same bias start.
+// MMA: the rsn_mma_mode the kernel serves -- 0 exact fp32, 1 / 2 split-bf16, 3 plain-bf16 training, 4 = 0 with FOLD.
+template <int NB, bool TRAIN, int MMA>
 __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
+  constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;
+  constexpr int MODE = FOLD ? 0 : MMA;  // the arithmetic of the GEMM loops
+  static_assert(!FOLD || TRAIN, "the folded bottleneck serves the exact-fp32 training kernels");
+  constexpr int NBH = FOLD ? 5 : NB + 1;  // row blocks of the GEMM that carries the heads block (its last)
   constexpr int XITS = (NB * 4 > 16) ? NB * 4 : 16;  // >= 14 (encoding, K=16 steps) and >= 16 (mid hidden)
   constexpr int WAVE_F4 = (XITS + RSN_AUX_ITS) * 64;
   constexpr int W = NB * 32;
@@ -59,9 +69,10 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
 
     float mc[3] = {0.0f, 0.0f, 0.0f}, vc[3] = {0.0f, 0.0f, 0.0f}, vd[3] = {0.0f, 0.0f, 0.0f};
     bool has_cov = true, has_dir = true;
-    float4 wbh[NB + 1];  // first weight fragment of the bottleneck+heads GEMM
+    float4 wbh[NBH];  // first weight fragment of the bottleneck+heads GEMM
+    const float* __restrict__ w_bh = pk + (FOLD ? P.L.w_fold : P.L.w_bh);
     if (a.mode == RSN_MODE_EMB) {
-      pre_mode<MODE, NB + 1>(wbh, pk + P.L.w_bh, ln);
+      pre_mode<MODE, NBH>(wbh, w_bh, ln);
       // granular Field API: heads / mid MLP on a caller-supplied embedding (field.py:139-186)
       has_dir = a.view_dirs != nullptr;
 #pragma unroll
@@ -158,7 +169,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         }
       }
       // out_activation = ReLU
-      pre_mode<MODE, NB + 1>(wbh, pk + P.L.w_bh, ln);
+      pre_mode<MODE, NBH>(wbh, w_bh, ln);
       store_act<NB, NB, true, SBF>(acc, X, rb_epi(a.saved.act, (P.num_layers - 1) * a.act_stride + p0 * W, W), h,
                               (TRAIN && a.saved.relu_bits && valid) ? bits_at(P.num_layers - 1) : nullptr);
     }
@@ -172,14 +183,15 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // ---------------- bottleneck + heads (one GEMM, N = W + 32) -----------------
     float dcol[3], tcol[3], rho;
     float4 wmid[4];  // first weight fragment of mlp_mid's SH part
+    f32x16 accm[4];  // mlp_mid's pre-activation (FOLD: its x part comes out of the GEMM below, started from b_c)
     {
-      f32x16 acc[NB + 1];
-      init_acc<NB + 1>(acc, pk + P.L.b_bh, h);
-      gemm_mode_run<MODE, NB + 1, NB + 1, TRAIN>(acc, wbh, pk + P.L.w_bh, pk + P.L.h_bh, X, NB * 4, ln,
+      f32x16 acc[NBH];
+      init_acc<NBH>(acc, pk + (FOLD ? P.L.b_fold : P.L.b_bh), h);
+      gemm_mode_run<MODE, NBH, NBH, TRAIN>(acc, wbh, w_bh, pk + P.L.h_bh, X, NB * 4, ln,
                                   rb_loop(a.mode == RSN_MODE_EMB ? nullptr : a.saved.act, (P.num_layers - 1) * a.act_stride + p0 * W, W));
       pre_mode<MODE, 4>(wmid, pk + P.L.w_mid_sh, ln);
-      const float r0 = acc[NB][0], r1 = acc[NB][1], r2 = acc[NB][2], r3 = acc[NB][3];
-      const float r4 = acc[NB][4], r5 = acc[NB][5], r6 = acc[NB][6];
+      const float r0 = acc[NBH - 1][0], r1 = acc[NBH - 1][1], r2 = acc[NBH - 1][2], r3 = acc[NBH - 1][3];
+      const float r4 = acc[NBH - 1][4], r5 = acc[NBH - 1][5], r6 = acc[NBH - 1][6];
       // h == 0: r0 raw density, r1..r3 normals, r4 roughness.   h == 1: r0..r2 diff, r4..r6 tint.
       const float rough_raw = __shfl(r4, m, 64);
       rho = (a.mode == RSN_MODE_EMB && a.rough_in) ? a.rough_in[pc] : softplus_f(rough_raw);
@@ -191,8 +203,13 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         // raw normal head (3) + raw roughness head: both rows sit in this lane, so their saved.heads share leaves as ONE store
         if (TRAIN && a.saved.heads && h == 0) *reinterpret_cast<float4*>(a.saved.heads + pc * 8) = make_float4(r1, r2, r3, r4);
       }
-      // bottleneck output (no activation) becomes the x-part of mlp_mid's input
-      store_act<NB + 1, NB, false, SBF>(acc, X, rb_epi(a.saved.bott, p0 * W, W), h);
+      if constexpr (FOLD) {
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) accm[nb] = acc[nb];
+      } else {
+        // bottleneck output (no activation) becomes the x-part of mlp_mid's input
+        store_act<NBH, NB, false, SBF>(acc, X, rb_epi(a.saved.bott, p0 * W, W), h);
+      }
     }
 
     // ---------------- SH-34 of the view direction, attenuated by softplus roughness -----------------
@@ -223,12 +240,15 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // ---------------- mlp_mid + RGB head -----------------
     float4 wrgb[1];
     {
-      f32x16 accm[4];
-      init_acc<4>(accm, pk + P.L.b_mid, h);
-      float4 wmx[4];
-      pre_mode<MODE, 4>(wmx, pk + P.L.w_mid_x, ln);
-      gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmid, pk + P.L.w_mid_sh, pk + P.L.h_mid_sh, AUX, RSN_SH_ITS, ln);
-      gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmx, pk + P.L.w_mid_x, pk + P.L.h_mid_x, X, NB * 4, ln, rb_loop(a.saved.bott, p0 * W, W));
+      if constexpr (FOLD) {  // the SH part on top of W_c a + b_c
+        gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmid, pk + P.L.w_mid_sh, pk + P.L.h_mid_sh, AUX, RSN_SH_ITS, ln);
+      } else {
+        init_acc<4>(accm, pk + P.L.b_mid, h);
+        float4 wmx[4];
+        pre_mode<MODE, 4>(wmx, pk + P.L.w_mid_x, ln);
+        gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmid, pk + P.L.w_mid_sh, pk + P.L.h_mid_sh, AUX, RSN_SH_ITS, ln);
+        gemm_mode_run<MODE, 4, 4, TRAIN>(accm, wmx, pk + P.L.w_mid_x, pk + P.L.h_mid_x, X, NB * 4, ln, rb_loop(a.saved.bott, p0 * W, W));
+      }
       pre_mode<MODE, 1>(wrgb, pk + P.L.w_rgb, ln);
       store_act<4, 4, true, SBF>(accm, X, rb_epi(a.saved.hid, p0 * 128, 128), h,
                             (TRAIN && a.saved.relu_bits && valid) ? bits_at(P.num_layers) : nullptr);
@@ -308,4 +328,3 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     }
   }
 }
-

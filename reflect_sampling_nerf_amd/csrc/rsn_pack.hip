@@ -51,7 +51,7 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
   RSN_REQUIRE(d->mid_width == 128, RSN_ERR_UNSUPPORTED, "mid_width=%d unsupported (128)", d->mid_width);
   RSN_REQUIRE(d->param_width >= 0 && d->param_width <= d->width, RSN_ERR_INVALID_ARGUMENT,
               "param_width=%d must be 0 (= width) or 1..width=%d", d->param_width, d->width);
-  RSN_REQUIRE(d->mma_mode >= RSN_MMA_F32 && d->mma_mode <= RSN_MMA_BF16, RSN_ERR_INVALID_ARGUMENT, "mma_mode=%d",
+  RSN_REQUIRE(d->mma_mode >= RSN_MMA_F32 && d->mma_mode <= RSN_MMA_F32_FOLDED, RSN_ERR_INVALID_ARGUMENT, "mma_mode=%d",
               d->mma_mode);
   RSN_REQUIRE(d->skip_layer == -1 || (d->skip_layer >= 1 && d->skip_layer <= d->num_layers - 2),
               RSN_ERR_INVALID_ARGUMENT,
@@ -168,6 +168,19 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
     tg += pf * 4;
     L->t_g_end = tg;
     off += (size_t)(tg - L->q_groups) * 16 * blk;
+  }
+  if (d->mma_mode == RSN_MMA_F32_FOLDED) {  // appended: every offset above is the RSN_MMA_F32 one
+    const size_t pw = (size_t)(d->param_width > 0 ? d->param_width : d->width);
+    L->fold_wc = off;
+    off += ((size_t)d->mid_width * pw + 3) / 4 * 4;
+    L->fold_bc = off;
+    off += (size_t)d->mid_width;
+    L->w_fold = off;
+    off += (size_t)(L->nb * 4) * (L->nbm + 1) * blk;
+    L->b_fold = off;
+    off += (size_t)(L->nbm + 1) * 32;
+    L->wT_fold = off;
+    off += (size_t)(L->nbm * 4 + 4) * L->nb * blk;
   }
   L->total = off;
   return RSN_OK;
@@ -329,6 +342,29 @@ __global__ void rsn_pack_all_kernel(const PackTable* __restrict__ t) {
     if (t->block_start[mid] <= b) lo = mid; else hi = mid - 1;
   }
   pack_elem(t->jobs[lo], (b - t->block_start[lo]) * 256 + (int)threadIdx.x);
+}
+
+// RSN_MMA_F32_FOLDED: field_output_bottleneck folded into the x part of mlp_mid.layers.0.  Thread e < n_mid * w forms one element
+// of W_c = W_mx W_b (W_mx = mid_w[:, 34:], row stride 34 + w), the next n_mid threads one element of b_c = b_mid + W_mx b_b:
+// fp64 products and sums in ascending k, ONE rounding to fp32.  The results are dense tensors inside the packed buffer; the
+// pack jobs of the folded segments read them as they read a parameter, so this launch goes first on the stream.
+__global__ void rsn_fold_kernel(const float* __restrict__ mid_w, const float* __restrict__ mid_b, const float* __restrict__ bott_w,
+                                const float* __restrict__ bott_b, int w, int n_mid, float* __restrict__ wc, float* __restrict__ bc) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ld = RSN_SH_DIM + w;
+  if (e < n_mid * w) {
+    const int i = e / w, j = e - i * w;
+    const float* row = mid_w + (size_t)i * ld + RSN_SH_DIM;
+    double acc = 0.0;
+    for (int k = 0; k < w; ++k) acc += (double)row[k] * (double)bott_w[(size_t)k * w + j];
+    wc[e] = (float)acc;
+  } else if (e < n_mid * w + n_mid) {
+    const int i = e - n_mid * w;
+    const float* row = mid_w + (size_t)i * ld + RSN_SH_DIM;
+    double acc = (double)mid_b[i];
+    for (int k = 0; k < w; ++k) acc += (double)row[k] * (double)bott_b[k];
+    bc[i] = (float)acc;
+  }
 }
 
 // all split-bf16 copies in one launch
@@ -573,6 +609,20 @@ int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed
                 frag, L.t_g_end);
   }
 
+  // ---------------- RSN_MMA_F32_FOLDED: [W_c ; heads] forward and transposed, from the dense W_c / b_c of rsn_fold_kernel ------
+  if (d->mma_mode == RSN_MMA_F32_FOLDED) {
+    const float* wc = packed + L.fold_wc;
+    j = gemm(wc, W, L.w_fold, NB * 4, NBM + 1);  // W_c (blocks 0..NBM-1) + heads block NBM: the heads rows as in w_bh
+    heads_src(*j, 1, heads_w, W); rows_natural(*j, MW); heads_rows(*j, MW); cols_natural(*j, W, 0);
+    j = bias(packed + L.fold_bc, L.b_fold, MW + 32);
+    heads_src(*j, 1, heads_b, 0); rows_natural(*j, MW); heads_rows(*j, MW);
+    j = gemm(wc, W, L.wT_fold, NBM * 4, NB, 1);  // [W_c]^T: rows = W embedding features, K = the mid rows ...
+    rows_natural(*j, W); cols_natural(*j, MW, 0);
+    j = gemm(nullptr, 0, L.wT_fold + (size_t)(NBM * 4) * NB * 256, 4, NB, 3);  // ... + [heads]^T as four more K-iterations (wT_bh)
+    heads_src(*j, 0, heads_w, W); rows_natural(*j, W); cols_headsT(*j, false);
+    return RSN_OK;  // exact fp32: no split-bf16 copies
+  }
+
   // ---------------- split-bf16 copies (RSN_MMA_BF16X6 / X3 / BF16) of every GEMM segment ----------------
   if (d->mma_mode == RSN_MMA_F32) return RSN_OK;  // the exact-fp32 kernels never read them
   auto split = [&](size_t src, int n_it, int nbo, size_t dst) {  // block0: numbered by the single-launch path
@@ -616,12 +666,25 @@ int validate_and_build(const rsn_field_desc* d, const rsn_field_params* p, float
 
 }  // namespace
 
+// RSN_MMA_F32_FOLDED: W_c / b_c into the packed buffer, ahead of the pack jobs that read them (validate_and_build has checked p)
+static int launch_fold(const rsn_field_desc* d, const rsn_field_params* p, float* packed, hipStream_t st) {
+  if (d->mma_mode != RSN_MMA_F32_FOLDED) return RSN_OK;
+  RsnPackedLayout L;
+  RSN_TRY(rsn_compute_layout(d, &L));
+  const int w = d->param_width > 0 ? d->param_width : d->width, n = d->mid_width * w + d->mid_width;
+  hipLaunchKernelGGL(rsn_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p->mid_w, p->mid_b, p->bottleneck_w,
+                     p->bottleneck_b, w, d->mid_width, packed + L.fold_wc, packed + L.fold_bc);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
 // one launch per segment, then one per split-bf16 copy
 extern "C" int rsn_pack_weights(const rsn_field_desc* d, const rsn_field_params* p, float* packed,
                                 size_t packed_bytes, void* stream) {
   const int rc = validate_and_build(d, p, packed, packed_bytes);
   if (rc != RSN_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
+  RSN_TRY(launch_fold(d, p, packed, st));
   for (const PackJob& j : t_jobs) {
     hipLaunchKernelGGL(rsn_pack_kernel, dim3((unsigned)job_blocks(j)), dim3(256), 0, st, j);
     RSN_HIP(hipGetLastError());
@@ -659,6 +722,7 @@ extern "C" int rsn_pack_weights_table(const rsn_field_desc* d, const rsn_field_p
     host_table.n_blocks = host_table.block_start[n_jobs] = blocks;
     RSN_HIP(hipMemcpyAsync(table, &host_table, sizeof(PackTable), hipMemcpyHostToDevice, st));
   }
+  RSN_TRY(launch_fold(d, p, packed, st));
   hipLaunchKernelGGL(rsn_pack_all_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const PackTable*)table);
   RSN_HIP(hipGetLastError());
   if (!t_splits.empty()) {

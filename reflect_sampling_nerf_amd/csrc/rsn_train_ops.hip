@@ -587,3 +587,58 @@ extern "C" int rsn_radam_step_guarded(int32_t n_tensors, float* const* params, c
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// rsn_unfold_bottleneck_grads: the folded training step (RSN_MMA_F32_FOLDED) reduces C = sum d a_mid (x) act[L-1] and s = sum d a_mid
+// over the points; the parameter gradients of field_output_bottleneck and of the x part of mlp_mid.layers.0 follow from them exactly:
+//   dW_b = W_mx^T C      db_b = W_mx^T s      dW_mx = C W_b^T + s (x) b_b          (W_mx = mid_w[:, 34:])
+// One thread per output element, fp64 products summed in ascending index order, one fp32 rounding, one fp32 add: bit-reproducible.
+// ------------------------------------------------------------------------------------------------
+struct UnfoldArgs {
+  int w, n_mid, ld_c, ld_mid;
+  const float* c; const float* s; const float* mid_w; const float* bott_w; const float* bott_b;
+  float* d_bott_w; float* d_bott_b; float* d_mid_w;
+};
+
+__global__ __launch_bounds__(256) void rsn_unfold_kernel(const UnfoldArgs a) {
+  const int w = a.w, n_mid = a.n_mid;
+  int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const float* __restrict__ wmx = a.mid_w + RSN_SH_DIM;
+  if (e < w * w) {  // dW_b[k][j] += sum_i W_mx[i][k] C[i][j]
+    const int k = e / w, j = e - k * w;
+    double acc = 0.0;
+    for (int i = 0; i < n_mid; ++i) acc += (double)wmx[(size_t)i * a.ld_mid + k] * (double)a.c[(size_t)i * a.ld_c + j];
+    a.d_bott_w[e] += (float)acc;
+    return;
+  }
+  e -= w * w;
+  if (e < w) {  // db_b[k] += sum_i W_mx[i][k] s[i]
+    double acc = 0.0;
+    for (int i = 0; i < n_mid; ++i) acc += (double)wmx[(size_t)i * a.ld_mid + e] * (double)a.s[i];
+    a.d_bott_b[e] += (float)acc;
+    return;
+  }
+  e -= w;
+  if (e < n_mid * w) {  // dW_mx[i][k] += sum_j C[i][j] W_b[k][j] + s[i] b_b[k]
+    const int i = e / w, k = e - i * w;
+    double acc = 0.0;
+    for (int j = 0; j < w; ++j) acc += (double)a.c[(size_t)i * a.ld_c + j] * (double)a.bott_w[(size_t)k * w + j];
+    acc += (double)a.s[i] * (double)a.bott_b[k];
+    a.d_mid_w[(size_t)i * a.ld_mid + RSN_SH_DIM + k] += (float)acc;
+  }
+}
+
+extern "C" int rsn_unfold_bottleneck_grads(int32_t width, int32_t n_mid, const float* c, int32_t ld_c, const float* s,
+                                           const float* mid_w, int32_t ld_mid, const float* bott_w, const float* bott_b,
+                                           float* d_bott_w, float* d_bott_b, float* d_mid_w, void* stream) {
+  RSN_REQUIRE(width >= 1 && width <= 256 && n_mid >= 1 && n_mid <= 1024, RSN_ERR_INVALID_ARGUMENT, "width=%d (1..256) n_mid=%d (1..1024)",
+              width, n_mid);
+  RSN_REQUIRE(ld_c >= width && ld_mid >= RSN_SH_DIM + width, RSN_ERR_INVALID_ARGUMENT, "ld_c=%d < width=%d or ld_mid=%d < %d + width",
+              ld_c, width, ld_mid, RSN_SH_DIM);
+  RSN_REQUIRE(c && s && mid_w && bott_w && bott_b && d_bott_w && d_bott_b && d_mid_w, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
+  UnfoldArgs a = {width, n_mid, ld_c, ld_mid, c, s, mid_w, bott_w, bott_b, d_bott_w, d_bott_b, d_mid_w};
+  const int n = width * width + width + n_mid * width;
+  hipLaunchKernelGGL(rsn_unfold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}

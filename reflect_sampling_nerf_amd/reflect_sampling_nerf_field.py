@@ -110,6 +110,12 @@ class ReflectSamplingNeRFNerfField(Field):
         self._pack_table: Optional[Tensor] = None
         self._pack_table_key = None
         self._desc: Optional[FieldDesc] = None
+        # the same four for the folded training kernels (fold=True below): their own descriptor and packed buffer
+        self._packed_fold: Optional[Tensor] = None
+        self._packed_fold_key = None
+        self._pack_table_fold: Optional[Tensor] = None
+        self._pack_table_fold_key = None
+        self._desc_fold: Optional[FieldDesc] = None
         self.mma_mode = _abi.RSN_MMA_F32
 
     MMA_MODES = {"f32": _abi.RSN_MMA_F32, "bf16x6": _abi.RSN_MMA_BF16X6, "bf16x3": _abi.RSN_MMA_BF16X3,
@@ -120,7 +126,7 @@ class ReflectSamplingNeRFNerfField(Field):
         emulation by 3-way bf16 splits, fp32-equivalent), "bf16x3" (2-way split, reduced precision, opt-in) or "bf16"
         (plain bf16 operands, fp32 accumulate: BASELINE configs[3])."""
         self.mma_mode = self.MMA_MODES[mode]
-        self._desc = None
+        self._desc = self._desc_fold = None
         self._packed_key = None  # rsn_pack_weights writes the split-bf16 segments only for the modes that read them
 
     # ------------------------------------------------------------------ C-ABI plumbing
@@ -140,7 +146,21 @@ class ReflectSamplingNeRFNerfField(Field):
                 return w
         raise NotImplementedError(f"base_mlp_layer_width={pw}: the fused kernels hold at most 256 units per layer")
 
-    def field_desc(self) -> FieldDesc:
+    def folds(self) -> bool:
+        """Whether this Field's training kernels have a folded form (fold=True of the training calls): exact fp32 only."""
+        return int(self.mma_mode) == _abi.RSN_MMA_F32
+
+    def field_desc(self, fold: bool = False) -> FieldDesc:
+        """fold: the descriptor of the exact-fp32 training kernels with field_output_bottleneck folded into mlp_mid
+        (RSN_MMA_F32_FOLDED, include/rsn.h); it goes with packed_weights(fold=True)."""
+        if fold:
+            if not self.folds():
+                raise _abi.RsnError("the folded training kernels are exact fp32: set_mma_mode('f32')")
+            if self._desc_fold is None:
+                d = FieldDesc.from_buffer_copy(self.field_desc())
+                d.mma_mode = _abi.RSN_MMA_F32_FOLDED
+                self._desc_fold = d
+            return self._desc_fold
         if self._desc is None:
             L = self.mlp_base.num_layers
             live = [s for s in self.skip_connections if 0 < s <= L - 1]
@@ -172,9 +192,10 @@ class ReflectSamplingNeRFNerfField(Field):
             setattr(p, name + "_b", mod.bias.data_ptr())
         return p
 
-    def packed_weights(self) -> Tensor:
+    def packed_weights(self, fold: bool = False) -> Tensor:
         """Parameters re-laid into MFMA fragment order (rsn_pack_weights); re-packed only when a parameter
-        changed (torch bumps Tensor._version on every in-place optimiser update)."""
+        changed (torch bumps Tensor._version on every in-place optimiser update).  fold: the buffer of field_desc(fold=True)
+        -- the same segments plus the folded ones -- kept beside the plain one and re-packed under the same rule."""
         params = [p for p in self.parameters()]
         dev = params[0].device
         if dev.type != "cuda":
@@ -183,27 +204,32 @@ class ReflectSamplingNeRFNerfField(Field):
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise _abi.RsnError("Field parameters must be contiguous fp32")
         key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed is None or self._packed_key != key or self._packed.device != dev:
+        a_pk, a_key, a_tab, a_tkey = (n + ("_fold" if fold else "") + k for n, k in
+                                      (("_packed", ""), ("_packed", "_key"), ("_pack_table", ""), ("_pack_table", "_key")))
+        packed, table = getattr(self, a_pk), getattr(self, a_tab)
+        if packed is None or getattr(self, a_key) != key or packed.device != dev:
             lib = _abi.load_library()
-            desc = self.field_desc()
+            desc = self.field_desc(fold)
             nbytes = lib.rsn_packed_weights_bytes(C.byref(desc))
             if nbytes == 0:
                 check(-1)
-            if self._packed is None or self._packed.numel() * 4 != nbytes or self._packed.device != dev:
-                self._packed = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+            if packed is None or packed.numel() * 4 != nbytes or packed.device != dev:
+                packed = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+                setattr(self, a_pk, packed)
             ps = self._param_struct()
             # one launch for all segments; the job table is re-uploaded only when a pointer or the shape changed
             tbytes = lib.rsn_pack_table_bytes()
-            if self._pack_table is None or self._pack_table.device != dev:
-                self._pack_table = torch.empty(tbytes, device=dev, dtype=torch.uint8)
-                self._pack_table_key = None
-            tkey = (tuple(p.data_ptr() for p in params), self._packed.data_ptr(), int(self.mma_mode))
-            rebuild = 1 if tkey != self._pack_table_key else 0
-            check(lib.rsn_pack_weights_table(C.byref(desc), C.byref(ps), ptr(self._packed), nbytes,
-                                             ptr(self._pack_table), tbytes, rebuild, ops._stream()))
-            self._pack_table_key = tkey
-            self._packed_key = key
-        return self._packed
+            if table is None or table.device != dev:
+                table = torch.empty(tbytes, device=dev, dtype=torch.uint8)
+                setattr(self, a_tab, table)
+                setattr(self, a_tkey, None)
+            tkey = (tuple(p.data_ptr() for p in params), packed.data_ptr(), int(desc.mma_mode))
+            rebuild = 1 if tkey != getattr(self, a_tkey) else 0
+            check(lib.rsn_pack_weights_table(C.byref(desc), C.byref(ps), ptr(packed), nbytes,
+                                             ptr(table), tbytes, rebuild, ops._stream()))
+            setattr(self, a_tkey, tkey)
+            setattr(self, a_key, key)
+        return packed
 
     # ------------------------------------------------------------------ fused evaluation (what the Model calls)
     def evaluate_frustums(self, origins: Tensor, directions: Tensor, pixel_area: Tensor, euclid_bins: Tensor,
@@ -276,20 +302,21 @@ class ReflectSamplingNeRFNerfField(Field):
 
     def evaluate_frustums_train(self, origins: Tensor, directions: Tensor, pixel_area: Tensor, euclid_bins: Tensor,
                                 n_dev: Optional[Tensor] = None, want_normals: bool = True,
-                                work: Optional[Dict] = None) -> Dict[str, Tensor]:
+                                work: Optional[Dict] = None, fold: bool = False) -> Dict[str, Tensor]:
         """Training-mode level: same per-sample outputs as evaluate_frustums plus `raw_density`, the analytic
-        `normals` (Field.get_normals, when want_normals) and `saved` = the activations the backward pass needs."""
+        `normals` (Field.get_normals, when want_normals) and `saved` = the activations the backward pass needs.
+        fold (exact fp32): the kernels with the bottleneck folded into mlp_mid; `saved` then has no "bott"."""
         self._no_distortion()
         lib = _abi.load_library()
         R, S = euclid_bins.shape[0], euclid_bins.shape[1] - 1
         N, dev = R * S, origins.device
         level = self.alloc_train_level(dev, R, S)
-        saved = self.alloc_saved(N, dev)
+        saved = self.alloc_saved_folded(N, dev) if fold else self.alloc_saved(N, dev)
         if want_normals:
             saved["normals"] = torch.empty(R, S, 3, device=dev, dtype=torch.float32)
         fo, fs = ops.field_outputs_struct(level), ops.saved_struct(saved)
-        desc = self.field_desc()
-        pk = self.packed_weights()
+        desc = self.field_desc(fold)
+        pk = self.packed_weights(fold)
         if work is None:  # (a caller launching with a device-side ray count fills in the evaluated points later)
             work = {"points": N}
         ops.timed("field_forward_train_normals" if want_normals else "field_forward_train", work, lambda: check(
@@ -303,7 +330,7 @@ class ReflectSamplingNeRFNerfField(Field):
 
     def evaluate_reflect_train(self, origins: Tensor, directions: Tensor, pixel_area: Tensor, euclid_bins: Tensor,
                                n_dev: Tensor, sqradius: Tensor, work: Optional[Dict] = None,
-                               inf_directions: Optional[Tensor] = None):
+                               inf_directions: Optional[Tensor] = None, fold: bool = False):
         """The first two field evaluations of the reflect branch in ONE launch (rsn_field_forward_train_jobs): the
         reflect-coarse level on the reflected rays (model.py:292-296) and get_inf_color of the same rays (model.py:290,
         field.py:190-201).  Both depend only on the secondary rays; as jobs of one launch get_inf_color's few tiles fill
@@ -318,7 +345,8 @@ class ReflectSamplingNeRFNerfField(Field):
         R_inf = d_inf.shape[0]
         dev = origins.device
         level = self.alloc_train_level(dev, R, S)
-        saved, inf_saved = self.alloc_saved(R * S, dev), self.alloc_saved(R_inf, dev)
+        alloc = self.alloc_saved_folded if fold else self.alloc_saved
+        saved, inf_saved = alloc(R * S, dev), alloc(R_inf, dev)
         bg = torch.empty(R_inf, 3, device=dev, dtype=torch.float32)
         fo, fs, fs_inf = ops.field_outputs_struct(level), ops.saved_struct(saved), ops.saved_struct(inf_saved)
         jobs = (_abi.FieldJob * 2)()
@@ -327,8 +355,8 @@ class ReflectSamplingNeRFNerfField(Field):
         jobs[1].kind, jobs[1].n_rays, jobs[1].n_dev, jobs[1].n_samples = 1, R_inf, n_dev.data_ptr(), 1
         jobs[1].directions, jobs[1].sqradius, jobs[1].out_rgb = d_inf.data_ptr(), sqradius.data_ptr(), bg.data_ptr()
         jobs[1].saved = C.pointer(fs_inf)
-        desc = self.field_desc()
-        pk = self.packed_weights()
+        desc = self.field_desc(fold)
+        pk = self.packed_weights(fold)
         ops.timed("field_forward_train", work if work is not None else {"points": R * (S + 1)}, lambda: check(
             lib.rsn_field_forward_train_jobs(C.byref(desc), ptr(pk), 2, jobs, ops._stream())))
         level["saved"] = saved
@@ -374,15 +402,25 @@ class ReflectSamplingNeRFNerfField(Field):
 
     def alloc_saved(self, N: int, dev) -> Dict[str, Tensor]:
         """The buffers a training-mode forward over N points fills (rsn_field_saved)."""
+        return self._alloc_saved(N, dev, False)
+
+    def alloc_saved_folded(self, N: int, dev) -> Dict[str, Tensor]:
+        """alloc_saved for the folded kernels (fold=True): no bottleneck rows."""
+        return self._alloc_saved(N, dev, True)
+
+    def _alloc_saved(self, N: int, dev, fold: bool) -> Dict[str, Tensor]:
         W, L = self.width, self.mlp_base.num_layers
         f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
         wd = self.wide_dtype()
         lay = self.train_layout()
         nd = lay["narrow_dtype"]
-        return {"enc": torch.empty(N, lay["enc_cols"], device=dev, dtype=nd), "act": torch.empty(L, N, W, device=dev, dtype=wd),
-                "bott": torch.empty(N, W, device=dev, dtype=wd), "sh": torch.empty(N, lay["sh_cols"], device=dev, dtype=nd),
-                "hid": torch.empty(N, 128, device=dev, dtype=wd), "heads": f(N, 8),
-                "relu_bits": torch.empty(L + 1, N, 2, max(W // 64, 2), device=dev, dtype=torch.int32)}
+        saved = {"enc": torch.empty(N, lay["enc_cols"], device=dev, dtype=nd), "act": torch.empty(L, N, W, device=dev, dtype=wd),
+                 "sh": torch.empty(N, lay["sh_cols"], device=dev, dtype=nd),
+                 "hid": torch.empty(N, 128, device=dev, dtype=wd), "heads": f(N, 8),
+                 "relu_bits": torch.empty(L + 1, N, 2, max(W // 64, 2), device=dev, dtype=torch.int32)}
+        if not fold:
+            saved["bott"] = torch.empty(N, W, device=dev, dtype=wd)
+        return saved
 
     def evaluate_inf(self, directions: Tensor, sqradius: Tensor, n_dev: Optional[Tensor] = None) -> Tensor:
         """get_inf_color on M (<= len) rays: directions [R,3], sqradius [R] -> rgb [R,3]."""

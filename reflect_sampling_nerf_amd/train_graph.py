@@ -87,12 +87,31 @@ def _composite_backward(n, S, background, flags, detach_w, level, eb, weights, g
     return out
 
 
+FOLD_BOTTLENECK = True  # the model's exact-fp32 training graph runs the folded kernels (fold_enabled); False: the two-GEMM form
+
+
+def fold_enabled(model) -> bool:
+    """Whether GetOutputsTrain folds field_output_bottleneck into mlp_mid for `model`: exact-fp32 fields, unless this module's
+    FOLD_BOTTLENECK or the model's `fold_bottleneck` attribute says no."""
+    return bool(FOLD_BOTTLENECK and getattr(model, "fold_bottleneck", True) and model.field.folds())
+
+
 def _alloc_gout(field, N: int, dev, need_input: bool):
+    return _alloc_gout_rows(field, N, dev, need_input, False)
+
+
+def _alloc_gout_folded(field, N: int, dev, need_input: bool):
+    """_alloc_gout for the folded sweep: no bottleneck gradient rows."""
+    return _alloc_gout_rows(field, N, dev, need_input, True)
+
+
+def _alloc_gout_rows(field, N: int, dev, need_input: bool, fold: bool):
     W, L = field.width, field.mlp_base.num_layers
     wd = field.wide_dtype()  # bf16 in the reduced-precision training mode (rsn_field_grads_out)
     g = {"dz_rgb": torch.empty(N, 4, device=dev), "da_mid": torch.empty(N, 128, device=dev, dtype=wd),
-         "d_bott": torch.empty(N, W, device=dev, dtype=wd), "dz_heads": torch.empty(N, 16, device=dev),
-         "dy": torch.empty(L, N, W, device=dev, dtype=wd)}
+         "dz_heads": torch.empty(N, 16, device=dev), "dy": torch.empty(L, N, W, device=dev, dtype=wd)}
+    if not fold:
+        g["d_bott"] = torch.empty(N, W, device=dev, dtype=wd)
     if need_input:
         g["d_input"] = torch.empty(N, device=dev)
     st = FieldGradsOut()
@@ -235,12 +254,15 @@ def _wgrad_jobs(jobs, n_out: int, k_in: int, *, mode=None, ordered=None):
     _wgrad_launch("rsn_weight_grad_jobs", head, sg, jobs[0][1].device, len(jobs), n_out, k_in, mode, ordered)
 
 
-def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
+def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False, fold: bool = False):
     """dW = dY^T X (+ db) for every linear layer, reduced over all field evaluations of the step at once.
     levels: list of (saved activations, backward-sweep outputs, with_heads[, (device count, rows per count)]).  Buffers of an
     evaluation that was launched with a device-side ray count are sized for the upper bound; the weight-gradient kernel
     reads the count itself and takes the first count * rows-per-count rows.  ordered: the reductions with a fixed order of addition
-    (Model.deterministic) instead of the atomic flush."""
+    (Model.deterministic) instead of the atomic flush.
+    fold: the levels come from the folded kernels (no bottleneck rows).  The bottleneck leaves the W x W launch; d a_mid is reduced
+    against the trunk output into a zeroed scratch C (and its column sums s), and rsn_unfold_bottleneck_grads adds the gradients of
+    field_output_bottleneck and of mlp_mid's x part that follow from C and s (linear in both: one call per _weight_grads call)."""
     # passed to every call below; bf16x6: split operands (fp32-equivalent); bf16: rounded operands (reduced precision)
     how = {"mode": int(field.mma_mode), "ordered": bool(ordered)}
     # W: the PARAMETER width (n_out / k_in of the reductions); the operand rows are [N, field.width] (leading dimension = the
@@ -265,14 +287,25 @@ def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
             ww.append((segs(lambda sv, go: (go["dy"][l], sv["act"][l - 1])), gw, 99, None))
         else:
             ww.append((segs(lambda sv, go: (go["dy"][l], sv["act"][l - 1])), gw, 0, gb))
-    ww.append((segs(lambda sv, go: (go["d_bott"], sv["act"][L - 1])), g["field_output_bottleneck.net.weight"], 0,
-               g["field_output_bottleneck.net.bias"]))
+    if not fold:
+        ww.append((segs(lambda sv, go: (go["d_bott"], sv["act"][L - 1])), g["field_output_bottleneck.net.weight"], 0,
+                   g["field_output_bottleneck.net.bias"]))
     _wgrad_jobs(we, W, int(enc_map.numel()), **how)
     for i in range(0, len(ww), _WGRAD_JOBS_MAX):
         _wgrad_jobs(ww[i:i + _WGRAD_JOBS_MAX], W, W, **how)
     _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["sh"])), 128, int(sh_map.numel()), g["mlp_mid.layers.0.weight"], 0,
                  g["mlp_mid.layers.0.bias"], sh_map, **how)
-    _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["bott"])), 128, W, g["mlp_mid.layers.0.weight"], 34, None, **how)
+    if fold:
+        gmw = g["mlp_mid.layers.0.weight"]
+        cs = torch.zeros(128 * W + 128, device=gmw.device)  # C [128, W] and s [128] of THIS call's levels
+        c, s = cs[: 128 * W].view(128, W), cs[128 * W:]
+        _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["act"][L - 1])), 128, W, c, 0, s, **how)
+        fb, fm = field.field_output_bottleneck.net, field.mlp_mid.layers[0]
+        check(_abi.load_library().rsn_unfold_bottleneck_grads(
+            W, 128, ptr(c), c.stride(0), ptr(s), ptr(fm.weight), fm.weight.stride(0), ptr(fb.weight), ptr(fb.bias),
+            ptr(g["field_output_bottleneck.net.weight"]), ptr(g["field_output_bottleneck.net.bias"]), ptr(gmw), ops._stream()))
+    else:
+        _wgrad_multi(segs(lambda sv, go: (go["da_mid"], sv["bott"])), 128, W, g["mlp_mid.layers.0.weight"], 34, None, **how)
     _wgrad_multi(segs(lambda sv, go: (go["dz_rgb"], sv["hid"])), 3, 128, g["field_output_mid.net.weight"], 0,
                  g["field_output_mid.net.bias"], **how)
     _wgrad_multi(segs(lambda sv, go: (go["dz_heads"], sv["act"][L - 1]), only_heads=True), 16, W, acc.heads_w, 0, acc.heads_b,
@@ -280,11 +313,12 @@ def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False):
 
 
 def _field_backward(field, rays, eb, level, gin: Dict[str, Optional[Tensor]], need_input: bool, n_dev=None,
-                    work: Optional[Dict] = None):
+                    work: Optional[Dict] = None, fold: bool = False):
+    """fold: `level` comes from a folded forward (evaluate_frustums_train(fold=True)); the sweep writes no "d_bott"."""
     lib = _abi.load_library()
     o, d, pa = rays
     n, S = eb.shape[0], eb.shape[1] - 1
-    gout, gst = _alloc_gout(field, n * S, o.device, need_input)
+    gout, gst = (_alloc_gout_folded if fold else _alloc_gout)(field, n * S, o.device, need_input)
     gi = FieldGradsIn()
     for k in ("sigma", "color", "pred_normals", "n_dot_d", "roughness", "ray_pn_loss", "ray_ori_loss"):
         setattr(gi, k, ptr(gin.get(k)))
@@ -292,8 +326,8 @@ def _field_backward(field, rays, eb, level, gin: Dict[str, Optional[Tensor]], ne
         gi.weights = ptr(gin["weights"])
     fo = ops.field_outputs_struct(level)
     fs = ops.saved_struct(level["saved"])
-    desc = field.field_desc()
-    pk = field.packed_weights()
+    desc = field.field_desc(fold)
+    pk = field.packed_weights(fold)
     ops.timed("field_backward_input" if need_input else "field_backward", work or {"points": n * S}, lambda: check(
         lib.rsn_field_backward_frustum(C.byref(desc), ptr(pk), n, ptr(n_dev), S, ptr(o), ptr(d), ptr(pa), ptr(eb),
                                        C.byref(fo), C.byref(fs), C.byref(gi), C.byref(gst), 1 if need_input else 0,
@@ -301,7 +335,8 @@ def _field_backward(field, rays, eb, level, gin: Dict[str, Optional[Tensor]], ne
     return gout
 
 
-def _reflect_field_backward(field, rays2, sq, levels, inf_saved, g_bg, n_dev, R: int, Rb: Optional[int] = None):
+def _reflect_field_backward(field, rays2, sq, levels, inf_saved, g_bg, n_dev, R: int, Rb: Optional[int] = None,
+                            fold: bool = False):
     """The three backward sweeps of the reflect branch in ONE launch (rsn_field_backward_jobs): the two reflect levels
     (`levels`: [(euclid bins, level dict, upstream colour gradient, S)]) and get_inf_color (upstream: g_bg, the background
     gradient both levels' compositing backward accumulated).  -> ([gout per level], gout of get_inf_color)."""
@@ -313,7 +348,7 @@ def _reflect_field_backward(field, rays2, sq, levels, inf_saved, g_bg, n_dev, R:
     jobs = (_abi.FieldBwdJob * (len(levels) + 1))()
     gouts, dev_work = [], []
     for k, (eb, lv, g_color, S) in enumerate(levels):
-        gout, gst = _alloc_gout(field, Rb * S, dev, True)
+        gout, gst = (_alloc_gout_folded if fold else _alloc_gout)(field, Rb * S, dev, True)
         gi = FieldGradsIn()
         gi.color = ptr(g_color)
         fo, fs = ops.field_outputs_struct(lv), ops.saved_struct(lv["saved"])
@@ -324,7 +359,7 @@ def _reflect_field_backward(field, rays2, sq, levels, inf_saved, g_bg, n_dev, R:
         j.fwd, j.saved, j.gin, j.gout = C.pointer(fo), C.pointer(fs), C.pointer(gi), C.pointer(gst)
         gouts.append(gout)
         dev_work.append((n_dev, S))
-    gout_inf, gst_inf = _alloc_gout(field, R, dev, True)
+    gout_inf, gst_inf = (_alloc_gout_folded if fold else _alloc_gout)(field, R, dev, True)
     fs_inf = ops.saved_struct(inf_saved)
     keep += [gst_inf, fs_inf]
     j = jobs[len(levels)]
@@ -332,8 +367,8 @@ def _reflect_field_backward(field, rays2, sq, levels, inf_saved, g_bg, n_dev, R:
     j.directions, j.sqradius, j.g_rgb = d.data_ptr(), sq.data_ptr(), g_bg.data_ptr()
     j.saved, j.gout = C.pointer(fs_inf), C.pointer(gst_inf)
     dev_work.append((n_dev, 1))
-    desc = field.field_desc()
-    pk = field.packed_weights()
+    desc = field.field_desc(fold)
+    pk = field.packed_weights(fold)
     ops.timed("field_backward_input", {"points": 0, "points_dev": dev_work}, lambda: check(
         lib.rsn_field_backward_jobs(C.byref(desc), ptr(pk), len(levels) + 1, jobs, ops._stream())))
     del keep
@@ -429,6 +464,7 @@ class GetOutputsTrain(torch.autograd.Function):
         uni, rec = model.sampler_uniform.spec, model.sampler_reciprocal.spec
         jitter = jitter or {}
         bins = bins or {}
+        fold = fold_enabled(model)  # exact fp32: the kernels with the bottleneck folded into mlp_mid (no bottleneck rows)
 
         def pad_rows(t, n):
             """[m, ...] -> [n, ...] (m <= n), zero rows behind: device-counted launches ignore them"""
@@ -469,12 +505,12 @@ class GetOutputsTrain(torch.autograd.Function):
         # A. coarse, B. fine (+ per-ray surface attributes)
         sb_c, eb_c = level_bins("coarse", R, Sc, lambda: ops.sample_spaced(R, None, Sc, uni.spacing, uni.tan, nears, fars,
                                                                            jit("coarse", R, Sc)))
-        lc = fld.evaluate_frustums_train(o, d, pa, eb_c, want_normals=True)
+        lc = fld.evaluate_frustums_train(o, d, pa, eb_c, want_normals=True, fold=fold)
         cc = ops.composite(R, None, Sc, 1, CLIP, lc["sigma"], eb_c, lc["color"], level=lc, ray_losses=True)
         sb_f, eb_f = level_bins("fine", R, Sf, lambda: ops.sample_pdf(
             R, None, Sc, Sf, uni.spacing, uni.tan, model.sampler_pdf.histogram_padding, nears, fars, cc["weights"], sb_c,
             jit("fine", R, Sf)))
-        lf = fld.evaluate_frustums_train(o, d, pa, eb_f, want_normals=True)
+        lf = fld.evaluate_frustums_train(o, d, pa, eb_f, want_normals=True, fold=fold)
         cf = ops.composite(R, None, Sf, 1, CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True, ray_losses=True)
         rs = ops.reflect_setup(o, d, cf["accumulation"], cf["depth"], cf["normals"], cf["roughness"], float(model.far))
         # C.-F. the reflect branch runs on the M <= R rays behind the mask.  Like the eval path (model.get_outputs) every
@@ -501,13 +537,13 @@ class GetOutputsTrain(torch.autograd.Function):
         work_rc, work_rf = ({"points": 0, "points_dev": [(nm, k)]} for k in (Src + 1, Srf))
         sb_rc, eb_rc = level_bins("reflect_coarse", Rb, Src, lambda: ops.sample_spaced(
             Rb, nm, Src, rec.spacing, rec.tan, near2b, far2b, jit("reflect_coarse", Rb, Src, rs["ray_index"], M)), M)
-        lrc, bg, inf_saved = fld.evaluate_reflect_train(o2b, d2b, pa2b, eb_rc, nm, sq, work=work_rc, inf_directions=d2)
+        lrc, bg, inf_saved = fld.evaluate_reflect_train(o2b, d2b, pa2b, eb_rc, nm, sq, work=work_rc, inf_directions=d2, fold=fold)
         crc = ops.composite(Rb, nm, Src, 2, 0, lrc["sigma"], eb_rc, lrc["color"], bg_rgb=bg, want_depth=False)
         ops.reflect_combine(Rb, nm, rs["ray_index"], cf["diff"], cf["tint"], crc["rgb"], rs["reflect_coarse"])
         sb_rf, eb_rf = level_bins("reflect_fine", Rb, Srf, lambda: ops.sample_pdf(
             Rb, nm, Src, Srf, rec.spacing, rec.tan, model.sampler_reflect_pdf.histogram_padding, near2b, far2b,
             crc["weights"], sb_rc, jit("reflect_fine", Rb, Srf, rs["ray_index"], M)), M)
-        lrf = fld.evaluate_frustums_train(o2b, d2b, pa2b, eb_rf, n_dev=nm, want_normals=False, work=work_rf)
+        lrf = fld.evaluate_frustums_train(o2b, d2b, pa2b, eb_rf, n_dev=nm, want_normals=False, work=work_rf, fold=fold)
         crf = ops.composite(Rb, nm, Srf, 2, 0, lrf["sigma"], eb_rf, lrf["color"], bg_rgb=bg)
         ops.reflect_combine(Rb, nm, rs["ray_index"], cf["diff"], cf["tint"], crf["rgb"], rs["reflect_fine"])
         mask_bool = rs["mask"].bool()
@@ -526,7 +562,7 @@ class GetOutputsTrain(torch.autograd.Function):
             aux.lazy["depth_reflect_fine"] = (nm, crf["depth"])
         elif M > 0:  # the count is on the host already (injected draws / bins)
             aux["depth_reflect_fine"] = crf["depth"][:M].unsqueeze(-1)
-        st = dict(R=R, Rb=Rb, eb_c=eb_c, eb_f=eb_f, lc=lc, lf=lf, cc=cc, cf=cf, rs=rs, rays=(o, d, pa),
+        st = dict(R=R, Rb=Rb, fold=fold, eb_c=eb_c, eb_f=eb_f, lc=lc, lf=lf, cc=cc, cf=cf, rs=rs, rays=(o, d, pa),
                   rays2=(o2, d2, pa2), sq=sq, bg=bg, inf_saved=inf_saved, eb_rc=eb_rc, eb_rf=eb_rf, lrc=lrc, lrf=lrf,
                   crc=crc, crf=crf)
         if getattr(model, "_keep_train_state", False):  # test hook: the sample positions this pass evaluated
@@ -575,6 +611,7 @@ class GetOutputsTrain(torch.autograd.Function):
         # M = 0 every launch below is a no-op on the device: no host-side early-out, no host read.
         nm = rs["n_masked"]
         Rb = st["Rb"]  # rays the two reflect levels were sized for (R by default; forward)
+        fold = st["fold"]
         g_bg = torch.zeros(R, 3, device=dev)
         g_pa2 = torch.zeros(R, device=dev)
         jobs = []
@@ -589,7 +626,7 @@ class GetOutputsTrain(torch.autograd.Function):
             jobs.append((eb, lv, cb["g_color"], S))
         # the sweeps of both levels and of get_inf_color (whose upstream gradient g_bg is complete now) in ONE launch:
         # their tiles share the persistent workgroups' rounds (rsn_field_backward_jobs)
-        gouts, gout = _reflect_field_backward(fld, st["rays2"], st["sq"], jobs, st["inf_saved"], g_bg, nm, R, Rb)
+        gouts, gout = _reflect_field_backward(fld, st["rays2"], st["sq"], jobs, st["inf_saved"], g_bg, nm, R, Rb, fold)
         for (eb, lv, _g, S), go in zip(jobs, gouts):
             g_pa2[:Rb] += _ray_sum(go["d_input"], Rb, S, nm)
             pending.append((lv["saved"], go, True, (nm, S)))
@@ -602,7 +639,7 @@ class GetOutputsTrain(torch.autograd.Function):
             # Opt-in memory bound: the reflect branch's weight gradients are reduced NOW (six more reduction launches per step, each
             # with its own flush) and its saved rows and sweep outputs -- a third of the step's memory -- are released before the
             # primary levels' sweep outputs are allocated (the caching allocator hands them the same blocks; one stream: no race).
-            _weight_grads(fld, pending, acc, getattr(model, "deterministic", False))
+            _weight_grads(fld, pending, acc, getattr(model, "deterministic", False), fold)
             pending = []
             for lv in (st["lrf"], st["lrc"]):
                 lv.pop("saved", None)
@@ -621,7 +658,7 @@ class GetOutputsTrain(torch.autograd.Function):
                "n_dot_d": ops._f32c(g_ndd_f.reshape(R, Sf)) if g_ndd_f is not None else None,
                "ray_pn_loss": ops._f32c(g_pnr_f) if g_pnr_f is not None else None,
                "ray_ori_loss": ops._f32c(g_orr_f) if g_orr_f is not None else None, "weights": cf["weights"]}
-        gout = _field_backward(fld, st["rays"], st["eb_f"], lf, gin, need_input=False)
+        gout = _field_backward(fld, st["rays"], st["eb_f"], lf, gin, need_input=False, fold=fold)
         pending.append((lf["saved"], gout, True))
         # coarse primary level
         lc, cc = st["lc"], st["cc"]
@@ -631,9 +668,9 @@ class GetOutputsTrain(torch.autograd.Function):
                "n_dot_d": ops._f32c(g_ndd_c.reshape(R, Sc)) if g_ndd_c is not None else None,
                "ray_pn_loss": ops._f32c(g_pnr_c) if g_pnr_c is not None else None,
                "ray_ori_loss": ops._f32c(g_orr_c) if g_orr_c is not None else None, "weights": cc["weights"]}
-        gout = _field_backward(fld, st["rays"], st["eb_c"], lc, gin, need_input=False)
+        gout = _field_backward(fld, st["rays"], st["eb_c"], lc, gin, need_input=False, fold=fold)
         pending.append((lc["saved"], gout, True))
-        _weight_grads(fld, pending, acc, getattr(model, "deterministic", False))
+        _weight_grads(fld, pending, acc, getattr(model, "deterministic", False), fold)
         del pending, gout
 
         final = acc.finish()
