@@ -150,7 +150,12 @@ int rsn_train_saved_layout(const rsn_field_desc* desc, int32_t* enc_cols, int32_
 /* ---- weights: nn.Linear layout -> MFMA fragment order ---------------------------------------
  * The field kernels stream weights in the exact order the 32x32x2 f32 MFMA consumes them; this
  * re-lays the Field's parameters into one flat buffer (done once per optimiser step).  The split-bf16
- * copies of the segments are written only when desc->mma_mode != RSN_MMA_F32: re-pack after changing it. */
+ * copies of the segments are written only when desc->mma_mode != RSN_MMA_F32: re-pack after changing it.
+ * With RSN_MMA_F32_FOLDED (num_layers >= 2) the region of ONE of those copies -- the transposed x part of the last trunk layer,
+ * which the exact-fp32 kernels never read -- holds the seed segment of the analytic-normal sweep instead: V[k][n] =
+ * fl32(W_{L-1}[n][k] * w_density[n]) (one rounding), transposed like that copy, as three bf16 pieces hi + mid + lo = V (exact for
+ * |V| >= 2^-110).  The folded training forward multiplies it by the ReLU bits of layer L-1; the RSN_MMA_F32
+ * training forward forms the same pieces in registers, and its buffer is byte for byte what it was.  All sizes are unchanged. */
 size_t rsn_packed_weights_bytes(const rsn_field_desc* desc);
 int rsn_pack_weights(const rsn_field_desc* desc, const rsn_field_params* params, float* packed,
                      size_t packed_bytes, void* stream);

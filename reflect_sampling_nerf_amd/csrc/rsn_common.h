@@ -68,6 +68,12 @@ struct RsnPackedLayout {
   size_t h_enc0, h_enc_skip, h_bh, h_mid_sh, h_mid_x, h_rgb;
   size_t hT_x[RSN_MAX_TRUNK_LAYERS];  // split-bf16 copies of the transposed segments (training sweeps)
   size_t hT_enc0, hT_enc_skip, hT_bh, hT_mid_x, hT_rgb;
+  // RSN_MMA_F32_FOLDED with num_layers >= 2 only (0 = absent): V = (x part of layer L-1)^T diag(w_density), one rounding per
+  // element (rsn_seed_product), as three bf16 pieces in the layout and K order of hT_x[L-1] -- the first GEMM of the
+  // analytic-normal sweep reads it against the ReLU bits of layer L-1 (gemm_bf16_bits).  It takes the PLACE of hT_x[L-1]: the
+  // exact-fp32 modes neither write nor read their split-bf16 copies, so the folded buffer keeps its size.  The RSN_MMA_F32
+  // buffer keeps every byte: its training kernel forms the same pieces from wT_x[L-1] and v_density in registers
+  size_t hT_seed;
   // RSN_MMA_BF16 / BF16X6 at width 256 only: the whole network as 16x32 fragments for v_mfma_f32_16x16x32_bf16, ONE linear
   // stream in the exact order rsn_field_bf16_ring16_kernel consumes them (its workgroups pull it through an LDS ring): lane
   // (i = lane & 15, g = lane >> 4) holds W[16 b + i][feature(kk, g, e)], e = 0..7, of fragment (K-step kk, row block b)
@@ -100,3 +106,7 @@ inline bool rsn_ring_training(const rsn_field_desc* d) {
 }
 
 int rsn_compute_layout(const rsn_field_desc* desc, RsnPackedLayout* L);
+
+// One element of V = W_{L-1}^T diag(w_density): the fp32 product, rounded once (-ffp-contract=off).  The pack kernel (hT_seed)
+// and the RSN_MMA_F32 training kernel (in registers) both form V with this function, then split it the same way: same bits.
+__device__ __forceinline__ float rsn_seed_product(float w, float wd) { return w * wd; }

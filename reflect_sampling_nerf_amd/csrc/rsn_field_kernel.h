@@ -266,9 +266,28 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // saved activations; the encoded-input gradient accumulates in 4 extra blocks (slot order), and the chain
     // through sin(2 pi x f [+ pi/2]) * exp(-var f^2 / 2) is closed per lane (the covariance is a constant here,
     // exactly like the reference, which sets requires_grad on the mean after contraction).
+    // Exact fp32 (MMA 0 and 4): the first GEMM of the sweep, W_{L-1}^T (w_density masked by the bits of layer L-1), runs on the
+    // bf16 MFMAs straight from those bits against V = W_{L-1}^T diag(w_density) in three bf16 pieces: the peeled iteration
+    // l = L-1.  FOLD reads the pieces packed (hT_seed, gemm_bf16_bits); MMA 0, whose packed buffer has no such segment, forms them
+    // in registers (gemm_f32_bits): the same bits.  The skip layer is never the last one (rsn_compute_layout), so that iteration
+    // has no encoded-input GEMM.
+    constexpr bool SEED_BITS = TRAIN && MODE == 0;
     if (TRAIN && a.saved.normals && a.saved.relu_bits) {
       const float* __restrict__ wd = pk + P.L.v_density;
-      {
+      const bool peel = SEED_BITS && P.num_layers >= 2;  // workgroup-uniform
+      if (peel) {
+        const ReluBits<NB> m7 = load_relu_bits<NB>(bits_at(P.num_layers - 1));
+        const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(P.num_layers - 2));
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc[NB];
+        zero_acc<NB>(acc);
+        if constexpr (FOLD) {
+          gemm_bf16_bits<NB>(acc, pk + P.L.hT_seed, m7, ln);
+        } else {  // RSN_MMA_F32: no packed seed, the same pieces formed in registers (same bits)
+          gemm_f32_bits<NB>(acc, pk + P.L.wT_x[P.num_layers - 1], wd, m7, ln);
+        }
+        store_masked_bits<NB>(acc, X, mb, h);
+      } else {
         // seed: the density-head row masked by the embedding's ReLU (bits of the last trunk layer)
         const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(P.num_layers - 1));
 #pragma unroll
@@ -286,7 +305,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       f32x16 eacc[4];
       zero_acc<4>(eacc);
 #pragma unroll 1
-      for (int l = P.num_layers - 1; l >= 1; --l) {
+      for (int l = P.num_layers - (peel ? 2 : 1); l >= 1; --l) {
         if (l == P.skip_layer) gemm_mode<MODE, 4, 4, TRAIN>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
         const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));
         __builtin_amdgcn_sched_barrier(0);

@@ -595,6 +595,146 @@ __device__ __forceinline__ ReluBits<NBO> load_relu_bits(const unsigned* __restri
   return m;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Bits K loop (exact-fp32 training, first GEMM of the analytic-normal sweep): acc += V m with m in {0, 1} given as the
+// lane's ReLU bits and V = W^T diag(w_density) pre-split into three bf16 pieces (hT_seed, rsn_pack.hip).  A 0 / 1 operand is
+// exact in bf16, the three pieces add up to the fp32 value exactly, every product is exact and the accumulation is fp32:
+// three v_mfma_f32_32x32x16_bf16 per block and K = 16 step in place of sixteen v_mfma_f32_32x32x2_f32 on the masked seed.
+// ------------------------------------------------------------------------------------------------
+// B operand of K = 16 step kk: element e is K-iteration 2kk + (e >> 2), component e & 3 -- bit (kk & 3) * 8 + e of word kk / 4
+// (store_act: bit nb * 16 + 4 q + j of a lane is K-iteration 4 nb + q, component j).  The word is picked by selects over
+// static register indices (an indexed read would put the words in scratch).
+struct SeedWords {
+  unsigned w0, w1, w2, w3;
+};
+template <int NBO>
+__device__ __forceinline__ SeedWords seed_words(const ReluBits<NBO>& m) {
+  static_assert(NBO == 2 || NBO == 4 || NBO == 8, "one, two or four mask words");
+  SeedWords s = {m.w[0], 0u, 0u, 0u};
+  if constexpr (NBO >= 4) s.w1 = m.w[1];
+  if constexpr (NBO >= 8) { s.w2 = m.w[2]; s.w3 = m.w[3]; }
+  return s;
+}
+__device__ __forceinline__ bf16x8 bits_bf16x8(const SeedWords m, int kk) {
+  const int wi = kk >> 2;
+  const unsigned word = wi == 0 ? m.w0 : (wi == 1 ? m.w1 : (wi == 2 ? m.w2 : m.w3));
+  const unsigned by = word >> ((kk & 3) * 8);
+  u32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)  // bf16 1.0 = 0x3f80; element 2j in the low half of dword j
+    v[j] = (((by >> (2 * j)) & 1u) * 0x3f80u) | (((by >> (2 * j + 1)) & 1u) * 0x3f800000u);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// the three pieces of NH blocks against one B operand: small pieces first, the blocks interleaved
+template <int NBO, int NH>
+__device__ __forceinline__ void mma16_bits(f32x16 (&acc)[NBO], const bf16x8 (&w)[NH][3], const bf16x8 b, int nb0) {
+#pragma unroll
+  for (int sp = 2; sp >= 0; --sp)
+#pragma unroll
+    for (int t = 0; t < NH; ++t) acc[nb0 + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[t][sp], b, acc[nb0 + t], 0, 0, 0);
+}
+
+// K = 32 NBO (the layer's output features), NBO row blocks; fragment buffers of half a K step like gemm_bf16 (a full step
+// ahead is 48 fragments = 192 registers beside the 128 accumulator registers: tools/probes/seed_bits_probe.hip measures both)
+template <int NBO>
+__device__ __forceinline__ void gemm_bf16_bits(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const ReluBits<NBO>& m, int lane) {
+  static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
+  constexpr int NH = NBO / 2, NK = 2 * NBO;
+  const WBuf wp = wbuf_make(wseg, lane);
+  bf16x8 wa[NH][3], wb[NH][3];
+  load_w16<NH, 3>(wa, wp, 0, NBO, 0);
+  const SeedWords mw = seed_words<NBO>(m);
+  bf16x8 bc = bits_bf16x8(mw, 0);
+#pragma unroll 1
+  for (int kk = 0; kk < NK; ++kk) {
+    load_w16<NH, 3>(wb, wp, kk, NBO, NH);
+    __builtin_amdgcn_sched_barrier(0);
+    const int kn = (kk + 1 < NK) ? kk + 1 : kk;  // clamped: one control path keeps the s_waitcnt counts exact
+    const bf16x8 bn = bits_bf16x8(mw, kn);   // rides in the issue gaps of the MFMAs below
+    mma16_bits<NBO, NH>(acc, wa, bc, 0);
+#pragma unroll
+    for (int g = 0; g < NH * 3; ++g) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // 2 VALU
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_w16<NH, 3>(wa, wp, kn, NBO, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    mma16_bits<NBO, NH>(acc, wb, bc, NH);
+    __builtin_amdgcn_sched_barrier(0);
+    bc = bn;
+  }
+}
+
+// The same GEMM without a packed V (RSN_MMA_F32, whose packed buffer carries no seed segment): the three pieces are formed in
+// registers from the fp32 fragments of wT_x[L-1] (K-iterations 2kk, 2kk + 1: the eight values of K = 16 step kk) and the density
+// row, by the expressions of split_elem (rsn_pack.hip), and meet the accumulators in the order of mma16_bits (lo, mid, hi per
+// block): bit for bit the result of gemm_bf16_bits.  About 50 VALU instructions per block and K step against three MFMAs: the
+// loop is VALU-bound, but still well under the fp32-MFMA form it replaces (tools/probes/seed_bits_probe.hip).
+template <int NBO, int NH>
+__device__ __forceinline__ void load_w32_pair(float4 (&f)[NH][2], const WBuf& b, int kk, int nb0) {
+#pragma unroll
+  for (int t = 0; t < NH; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(b.r, b.voff + (unsigned)(nb0 + t) * 1024u, (unsigned)(2 * kk + j) * (NBO * 1024u), 0);
+      f[t][j] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+    }
+}
+
+template <int NBO, int NH>
+__device__ __forceinline__ void mma16_bits_f32(f32x16 (&acc)[NBO], const float4 (&f)[NH][2], const float4 dlo, const float4 dhi,
+                                               const bf16x8 b, int nb0) {
+#pragma unroll
+  for (int t = 0; t < NH; ++t) {
+    const float v[8] = {rsn_seed_product(f[t][0].x, dlo.x), rsn_seed_product(f[t][0].y, dlo.y), rsn_seed_product(f[t][0].z, dlo.z),
+                        rsn_seed_product(f[t][0].w, dlo.w), rsn_seed_product(f[t][1].x, dhi.x), rsn_seed_product(f[t][1].y, dhi.y),
+                        rsn_seed_product(f[t][1].z, dhi.z), rsn_seed_product(f[t][1].w, dhi.w)};
+    bf16x8 s1, s2, s3;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const __bf16 b1 = (__bf16)v[e];
+      const float r1 = v[e] - (float)b1;
+      const __bf16 b2 = (__bf16)r1;
+      const float r2 = r1 - (float)b2;
+      s1[e] = b1; s2[e] = b2; s3[e] = (__bf16)r2;
+    }
+    f32x16 c = acc[nb0 + t];
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s3, b, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s2, b, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s1, b, c, 0, 0, 0);
+    acc[nb0 + t] = c;
+  }
+}
+
+// w32seg: wT_x[L-1] ([it][NBO][lane][4]); wd: the packed density row (v_density)
+template <int NBO>
+__device__ __forceinline__ void gemm_f32_bits(f32x16 (&acc)[NBO], const float* __restrict__ w32seg, const float* __restrict__ wd,
+                                              const ReluBits<NBO>& m, int lane) {
+  static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
+  constexpr int NH = NBO / 2, NK = 2 * NBO;
+  const WBuf wp = wbuf_make(w32seg, lane);
+  const float* __restrict__ wdl = wd + 4 * (lane >> 5);
+  float4 fa[NH][2], fb[NH][2];
+  load_w32_pair<NBO, NH>(fa, wp, 0, 0);
+  const SeedWords mw = seed_words<NBO>(m);
+  float4 dlo = *reinterpret_cast<const float4*>(wdl), dhi = *reinterpret_cast<const float4*>(wdl + 8);
+#pragma unroll 1
+  for (int kk = 0; kk < NK; ++kk) {
+    load_w32_pair<NBO, NH>(fb, wp, kk, NH);
+    const int kn = (kk + 1 < NK) ? kk + 1 : kk;
+    const float4 nlo = *reinterpret_cast<const float4*>(wdl + 16 * kn), nhi = *reinterpret_cast<const float4*>(wdl + 16 * kn + 8);
+    const bf16x8 bc = bits_bf16x8(mw, kk);
+    mma16_bits_f32<NBO, NH>(acc, fa, dlo, dhi, bc, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    load_w32_pair<NBO, NH>(fa, wp, kn, 0);
+    mma16_bits_f32<NBO, NH>(acc, fb, dlo, dhi, bc, NH);
+    __builtin_amdgcn_sched_barrier(0);
+    dlo = nlo; dhi = nhi;
+  }
+}
+
 // bit `pos` of `word` as 0 / 0xffffffff: one v_bfe_i32.  Written as (non-volatile) asm because hipcc rewrites
 // `x & sext(bit)` into v_and (test) + v_cmp_ne + v_cndmask: three VALU per value and a VCC hazard nop, where bfe + and is two.
 __device__ __forceinline__ unsigned bit_mask(int word, int pos) {

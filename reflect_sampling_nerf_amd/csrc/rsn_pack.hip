@@ -145,6 +145,8 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
   off += (size_t)(L->nbm * 2) * L->nb * 3 * blk;
   L->hT_rgb = off;
   off += (size_t)2 * L->nbm * 3 * blk;
+  // the seed of the analytic-normal sweep in a slot RSN_MMA_F32_FOLDED leaves unused (see RsnPackedLayout)
+  L->hT_seed = (d->mma_mode == RSN_MMA_F32_FOLDED && d->num_layers >= 2) ? L->hT_x[d->num_layers - 1] : 0;
   L->q_pf = 1;
   if ((d->mma_mode == RSN_MMA_BF16 || d->mma_mode == RSN_MMA_BF16X6) && d->width == 256) {
     // 16x32 fragments: enc 4 x 16, x 8 x 16, heads 8 x 2, bottleneck 8 x 16, mid SH 2 x 8, mid x 8 x 8, rgb 4 x 4; split-bf16:
@@ -369,14 +371,17 @@ __global__ void rsn_fold_kernel(const float* __restrict__ mid_w, const float* __
 
 // all split-bf16 copies in one launch
 #define SPLIT_MAX_SEGS 48
-struct SplitSeg { unsigned src, dst; short n_it, nbo; int block0; };
+struct SplitSeg { unsigned src, dst; short n_it, nbo; int block0; unsigned kscale; };  // kscale: see split_elem (0 = none)
 struct SplitJob { float* packed; int n_segs; SplitSeg s[SPLIT_MAX_SEGS]; };
 
 // split-bf16 copy of an already packed fp32 segment [it][nb][lane][4] -> [k16][nb][split(3)][lane][8 bf16]:
 // element e of K=16 step kk is the fp32 value of K-iteration 2kk + (e>>2), component e&3 (zero beyond n_it), split
 // EXACTLY into three bf16 (v = b1 + b2 + b3 up to 2^-24): the K=16 MFMA step consumes the same lane-local
 // activations as the two fp32 K-iterations it replaces.  Works for forward and transposed segments alike.
-__device__ __forceinline__ void split_elem(const float* __restrict__ src, int n_it, int nbo, float* dstf, int e) {
+// kscale (optional): one fp32 factor per K slot, it * 8 + 4 h + s -- the value split is rsn_seed_product(v, kscale[k]), the fp32
+// product with ONE rounding.  hT_seed: wT_x[L-1] times the density row.
+__device__ __forceinline__ void split_elem(const float* __restrict__ src, int n_it, int nbo, float* dstf, int e,
+                                           const float* __restrict__ kscale = nullptr) {
   const int n_k16 = (n_it + 1) / 2;
   if (e >= n_k16 * nbo * 512) return;
   const int ee = e & 7;
@@ -387,6 +392,7 @@ __device__ __forceinline__ void split_elem(const float* __restrict__ src, int n_
   const int it = 2 * kk + (ee >> 2);
   float v = 0.0f;
   if (it < n_it) v = src[((size_t)(it * nbo + nb) * 64 + lane) * 4 + (ee & 3)];
+  if (kscale != nullptr && it < n_it) v = rsn_seed_product(v, kscale[it * 8 + 4 * (lane >> 5) + (ee & 3)]);
   const __bf16 b1 = (__bf16)v;
   const float r1 = v - (float)b1;
   const __bf16 b2 = (__bf16)r1;
@@ -399,15 +405,16 @@ __device__ __forceinline__ void split_elem(const float* __restrict__ src, int n_
   dst[((base + 2) * 64 + lane) * 8 + ee] = b3;
 }
 
-__global__ void rsn_pack_split_kernel(const float* __restrict__ src, int n_it, int nbo, float* dstf) {
-  split_elem(src, n_it, nbo, dstf, blockIdx.x * blockDim.x + threadIdx.x);
+__global__ void rsn_pack_split_kernel(const float* __restrict__ src, int n_it, int nbo, float* dstf, const float* __restrict__ kscale) {
+  split_elem(src, n_it, nbo, dstf, blockIdx.x * blockDim.x + threadIdx.x, kscale);
 }
 
 __global__ void rsn_pack_split_all_kernel(const SplitJob job) {
   int si = 0;
   while (si + 1 < job.n_segs && job.s[si + 1].block0 <= (int)blockIdx.x) ++si;
   const SplitSeg sg = job.s[si];
-  split_elem(job.packed + sg.src, sg.n_it, sg.nbo, job.packed + sg.dst, ((int)blockIdx.x - sg.block0) * 256 + (int)threadIdx.x);
+  split_elem(job.packed + sg.src, sg.n_it, sg.nbo, job.packed + sg.dst, ((int)blockIdx.x - sg.block0) * 256 + (int)threadIdx.x,
+             sg.kscale ? job.packed + sg.kscale : nullptr);
 }
 
 namespace {
@@ -620,14 +627,18 @@ int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed
     rows_natural(*j, W); cols_natural(*j, MW, 0);
     j = gemm(nullptr, 0, L.wT_fold + (size_t)(NBM * 4) * NB * 256, 4, NB, 3);  // ... + [heads]^T as four more K-iterations (wT_bh)
     heads_src(*j, 0, heads_w, W); rows_natural(*j, W); cols_headsT(*j, false);
-    return RSN_OK;  // exact fp32: no split-bf16 copies
   }
 
   // ---------------- split-bf16 copies (RSN_MMA_BF16X6 / X3 / BF16) of every GEMM segment ----------------
-  if (d->mma_mode == RSN_MMA_F32) return RSN_OK;  // the exact-fp32 kernels never read them
-  auto split = [&](size_t src, int n_it, int nbo, size_t dst) {  // block0: numbered by the single-launch path
-    splits.push_back(SplitSeg{(unsigned)src, (unsigned)dst, (short)n_it, (short)nbo, 0});
+  auto split = [&](size_t src, int n_it, int nbo, size_t dst, size_t kscale = 0) {  // block0: numbered by the single-launch path
+    splits.push_back(SplitSeg{(unsigned)src, (unsigned)dst, (short)n_it, (short)nbo, 0, (unsigned)kscale});
   };
+  if (d->mma_mode == RSN_MMA_F32 || d->mma_mode == RSN_MMA_F32_FOLDED) {
+    // exact fp32: the kernels read none of the copies below; the folded mode's one split segment is the seed of the
+    // analytic-normal sweep (RSN_MMA_F32 packs nothing more: its training kernel forms the same pieces in registers)
+    if (L.hT_seed != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_seed, L.v_density);
+    return RSN_OK;
+  }
   split(L.w_enc0, RSN_ENC_ITS, NB, L.h_enc0);
   for (int l = 1; l < n_layers; ++l) {
     split(L.w_x[l], NB * 4, NB, L.h_x[l]);
@@ -691,7 +702,7 @@ extern "C" int rsn_pack_weights(const rsn_field_desc* d, const rsn_field_params*
   }
   for (const SplitSeg& s : t_splits) {
     hipLaunchKernelGGL(rsn_pack_split_kernel, dim3((unsigned)split_blocks(s)), dim3(256), 0, st, packed + s.src, (int)s.n_it,
-                       (int)s.nbo, packed + s.dst);
+                       (int)s.nbo, packed + s.dst, s.kscale ? packed + s.kscale : nullptr);
     RSN_HIP(hipGetLastError());
   }
   return RSN_OK;
