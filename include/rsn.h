@@ -155,7 +155,11 @@ int rsn_train_saved_layout(const rsn_field_desc* desc, int32_t* enc_cols, int32_
  * which the exact-fp32 kernels never read -- holds the seed segment of the analytic-normal sweep instead: V[k][n] =
  * fl32(W_{L-1}[n][k] * w_density[n]) (one rounding), transposed like that copy, as three bf16 pieces hi + mid + lo = V (exact for
  * |V| >= 2^-110).  The folded training forward multiplies it by the ReLU bits of layer L-1; the RSN_MMA_F32
- * training forward forms the same pieces in registers, and its buffer is byte for byte what it was.  All sizes are unchanged. */
+ * training forward forms the same pieces in registers, and its buffer is byte for byte what it was.  All sizes are unchanged.
+ * RSN_MMA_F32_FOLDED also fills the split-bf16 copies of the OTHER segments the analytic-normal sweep reads -- the transposed x
+ * parts of trunk layers 1 .. L-2 and the transposed encoded-input parts of layer 0 and of the skip layer -- in their own regions,
+ * as the split-bf16 modes write them: the folded training forward runs those GEMMs on all nine products of the three pieces of the
+ * weights and of the activations.  The remaining split-bf16 regions of the two exact-fp32 modes stay unwritten. */
 size_t rsn_packed_weights_bytes(const rsn_field_desc* desc);
 int rsn_pack_weights(const rsn_field_desc* desc, const rsn_field_params* params, float* packed,
                      size_t packed_bytes, void* stream);

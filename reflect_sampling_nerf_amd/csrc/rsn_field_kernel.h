@@ -16,6 +16,19 @@
 // SH part then accumulates into the same four blocks, and the K = W GEMM over the bottleneck row is gone with the row itself
 // (saved.bott is neither written nor read).  Heads, sigma and normals keep their bits: same K order, same bias start.
 // MMA: the rsn_mma_mode the kernel serves -- 0 exact fp32, 1 / 2 split-bf16, 3 plain-bf16 training, 4 = 0 with FOLD.
+// A loop GEMM of the analytic-normal sweep.  X9 (the exact-fp32 training instantiations): the nine-product loop on the bf16 MFMAs,
+// PACKED (FOLD) over the pre-split hT_* segment, else with the same pieces formed in registers from the fp32 wT_* segment (the
+// RSN_MMA_F32 buffer has no split copies): the same bits either way.  Otherwise the mode's own loop.
+template <bool X9, bool PACKED, int MODE, int NBO>
+__device__ __forceinline__ void sweep_gemm(f32x16 (&acc)[NBO], const float* __restrict__ w32, const float* __restrict__ w16,
+                                           const float4* xl, int n_it, int lane) {
+  if constexpr (X9) {
+    if constexpr (PACKED) gemm_bf16<NBO, 3, true>(acc, w16, xl, n_it / 2, lane); else gemm_f32_x9<NBO>(acc, w32, xl, n_it / 2, lane);
+  } else {
+    gemm_mode<MODE, NBO, NBO, true>(acc, w32, w16, xl, n_it, lane);
+  }
+}
+
 template <int NB, bool TRAIN, int MMA>
 __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
   constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;
@@ -271,6 +284,8 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // l = L-1.  FOLD reads the pieces packed (hT_seed, gemm_bf16_bits); MMA 0, whose packed buffer has no such segment, forms them
     // in registers (gemm_f32_bits): the same bits.  The skip layer is never the last one (rsn_compute_layout), so that iteration
     // has no encoded-input GEMM.
+    // The GEMMs behind it (W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs) run on the bf16 MFMAs too, as all NINE products of
+    // three bf16 pieces a side (sweep_gemm): no term of the fp32 product is dropped, only the order of the fp32 accumulation differs.
     constexpr bool SEED_BITS = TRAIN && MODE == 0;
     if (TRAIN && a.saved.normals && a.saved.relu_bits) {
       const float* __restrict__ wd = pk + P.L.v_density;
@@ -306,15 +321,15 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       zero_acc<4>(eacc);
 #pragma unroll 1
       for (int l = P.num_layers - (peel ? 2 : 1); l >= 1; --l) {
-        if (l == P.skip_layer) gemm_mode<MODE, 4, 4, TRAIN>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
+        if (l == P.skip_layer) sweep_gemm<SEED_BITS, FOLD, MODE, 4>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
         const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc[NB];
         zero_acc<NB>(acc);
-        gemm_mode<MODE, NB, NB, TRAIN>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln);
+        sweep_gemm<SEED_BITS, FOLD, MODE, NB>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln);
         store_masked_bits<NB>(acc, X, mb, h);
       }
-      gemm_mode<MODE, 4, 4, TRAIN>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, NB * 4, ln);
+      sweep_gemm<SEED_BITS, FOLD, MODE, 4>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, NB * 4, ln);
       store_act<4, 4, false>(eacc, X);  // gradient w.r.t. this lane's encoded inputs, slot order (its 0..12)
       float nrm[3];
 #pragma unroll 1

@@ -402,11 +402,20 @@ __device__ __forceinline__ void load_w16(bf16x8 (&w)[NH][3], const WBuf& wp, int
     }
 }
 
-template <int NBO, int NH, int NB0, int NSPLIT>
+// FULL (NSPLIT = 3 only): all NINE piece products -- w3x3, w3x2, w2x3 ahead of the six, so that the smallest terms meet the
+// accumulator first.  Every piece product is exact in fp32 and the pieces add up to the fp32 operands, so no term of the fp32
+// product is dropped: the result differs from the fp32 MFMA's only by the order of the fp32 accumulation.
+template <int NBO, int NH, int NB0, int NSPLIT, bool FULL = false>
 __device__ __forceinline__ void mma16(f32x16 (&acc)[NBO], const bf16x8 (&w)[NH][3], const BSplit& b) {
+  static_assert(!FULL || NSPLIT == 3, "the full product is over three pieces a side");
 #pragma unroll
   for (int t = 0; t < NH; ++t) {
     f32x16 c = acc[NB0 + t];
+    if (FULL) {
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[t][2], b.s3, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[t][2], b.s2, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[t][1], b.s3, c, 0, 0, 0);
+    }
     if (NSPLIT == 3) {
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[t][2], b.s1, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[t][1], b.s2, c, 0, 0, 0);
@@ -421,11 +430,11 @@ __device__ __forceinline__ void mma16(f32x16 (&acc)[NBO], const bf16x8 (&w)[NH][
   }
 }
 
-template <int NBO, int NSPLIT>
+template <int NBO, int NSPLIT, bool FULL = false>
 __device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const float4* xl,
                                           int n_k16, int lane) {
   constexpr int H0 = (NBO + 1) / 2, H1 = NBO - H0;
-  constexpr int PER = (NSPLIT == 3 ? 6 : (NSPLIT == 2 ? 3 : 1));  // MFMAs per output block and K step
+  constexpr int PER = FULL ? 9 : (NSPLIT == 3 ? 6 : (NSPLIT == 2 ? 3 : 1));  // MFMAs per output block and K step
   const WBuf wp = wbuf_make(wseg, lane);
   bf16x8 wa[H0][3], wb[H1 > 0 ? H1 : 1][3];
   load_w16<H0, NSPLIT>(wa, wp, 0, NBO, 0);
@@ -439,7 +448,7 @@ __device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NBO], const float* __res
     if (H1 > 0) load_w16<(H1 > 0 ? H1 : 1), NSPLIT>(wb, wp, kk, NBO, H0);
     __builtin_amdgcn_sched_barrier(0);
     const BSplit bn = split8<NSPLIT>(xlo, xhi);
-    mma16<NBO, H0, 0, NSPLIT>(acc, wa, bc);
+    mma16<NBO, H0, 0, NSPLIT, FULL>(acc, wa, bc);
 #pragma unroll
     for (int g = 0; g < H0 * PER; ++g) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
@@ -454,7 +463,7 @@ __device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NBO], const float* __res
     xlo = xl[(2 * k2) * 64];
     xhi = xl[(2 * k2 + 1) * 64];
     __builtin_amdgcn_sched_barrier(0);
-    if (H1 > 0) mma16<NBO, (H1 > 0 ? H1 : 1), (H1 > 0 ? H0 : 0), NSPLIT>(acc, wb, bc);
+    if (H1 > 0) mma16<NBO, (H1 > 0 ? H1 : 1), (H1 > 0 ? H0 : 0), NSPLIT, FULL>(acc, wb, bc);
     __builtin_amdgcn_sched_barrier(0);
     bc = bn;
   }
@@ -732,6 +741,80 @@ __device__ __forceinline__ void gemm_f32_bits(f32x16 (&acc)[NBO], const float* _
     mma16_bits_f32<NBO, NH>(acc, fb, dlo, dhi, bc, NH);
     __builtin_amdgcn_sched_barrier(0);
     dlo = nlo; dhi = nhi;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Nine-product K loop without packed pieces (RSN_MMA_F32, whose packed buffer has no hT_* copies): gemm_bf16<NBO, 3, true> with the
+// weight pieces formed in registers from the fp32 fragments of a wT_* segment ([it][NBO][lane][4]; K-iterations 2kk, 2kk + 1 are
+// the eight values of K = 16 step kk).  split8<3> is split_elem's expression (rsn_pack.hip), and the nine products meet each
+// accumulator in mma16<.., true>'s order: bit for bit the result of the packed form.  K a multiple of 16.
+// ------------------------------------------------------------------------------------------------
+// the nine products of one block and K step, in mma16<.., true>'s order
+__device__ __forceinline__ f32x16 x9_block(f32x16 c, const BSplit& w, const BSplit& b) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s1, c, 0, 0, 0);
+  return c;
+}
+
+// A software pipeline over the blocks: while the nine MFMAs of block b run (288 cycles), the VALU forms the pieces of block b + 1
+// (about 50 instructions, five or six behind each MFMA; the last block of a K step also splits the next step's activations).  A
+// fragment buffer is dead once its last block is split, and is reloaded for the next K step at the start of the block after that.
+// Written block by block (split, then nine MFMAs) hipcc issues the ~50 VALU instructions of a block in one run ahead of its MFMAs:
+// that loop took 0.98 of the fp32 form's time alone and made the unfolded training forward 7 % slower; this one 0.87-0.90
+// (tools/probes/sweep_x9_probe.hip), the forward 2 % faster.
+template <int NBO>
+__device__ __forceinline__ void gemm_f32_x9(f32x16 (&acc)[NBO], const float* __restrict__ w32seg, const float4* xl, int n_k16,
+                                            int lane) {
+  static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
+  constexpr int NH = NBO / 2;
+  const WBuf wp = wbuf_make(w32seg, lane);
+  float4 fa[NH][2], fb[NH][2];
+  load_w32_pair<NBO, NH>(fa, wp, 0, 0);
+  load_w32_pair<NBO, NH>(fb, wp, 0, NH);
+  BSplit bc = split8<3>(xl[0], xl[64]);
+  const int k1 = n_k16 > 1 ? 1 : 0;
+  float4 xlo = xl[(2 * k1) * 64], xhi = xl[(2 * k1 + 1) * 64];  // fp32 activations of the NEXT K step
+  BSplit w = split8<3>(fa[0][0], fa[0][1]);
+  BSplit bn = bc;
+#pragma unroll 1
+  for (int kk = 0; kk < n_k16; ++kk) {
+    const int kn = (kk + 1 < n_k16) ? kk + 1 : kk;  // clamped: one control path keeps the s_waitcnt counts exact
+    const int k2 = (kk + 2 < n_k16) ? kk + 2 : kn;
+#pragma unroll
+    for (int b = 0; b < NBO; ++b) {
+      BSplit wn;
+      if (b + 1 < NH) wn = split8<3>(fa[b + 1][0], fa[b + 1][1]);
+      else if (b + 1 < NBO) wn = split8<3>(fb[b + 1 - NH][0], fb[b + 1 - NH][1]);
+      else wn = split8<3>(fa[0][0], fa[0][1]);  // block 0 of step kn: fa was reloaded at block NH - 1
+      if (b == NH - 1) load_w32_pair<NBO, NH>(fa, wp, kn, 0);
+      if (b == NBO - 1) {
+        load_w32_pair<NBO, NH>(fb, wp, kn, NH);
+        bn = split8<3>(xlo, xhi);
+        xlo = xl[(2 * k2) * 64];
+        xhi = xl[(2 * k2 + 1) * 64];
+      }
+      acc[b] = x9_block(acc[b], w, bc);
+      const bool loads = b == NH - 1 || b == NBO - 1;
+#pragma unroll
+      for (int g = 0; g < 9; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+        if (loads && g < 2 * NH) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
+        if (b == NBO - 1) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);  // the next block's pieces + the next step's activations
+        else __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);  // the next block's pieces
+      }
+      if (b == NBO - 1) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // the LDS reads of the activations
+      __builtin_amdgcn_sched_barrier(0);
+      w = wn;
+    }
+    bc = bn;
   }
 }
 

@@ -634,9 +634,15 @@ int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed
     splits.push_back(SplitSeg{(unsigned)src, (unsigned)dst, (short)n_it, (short)nbo, 0, (unsigned)kscale});
   };
   if (d->mma_mode == RSN_MMA_F32 || d->mma_mode == RSN_MMA_F32_FOLDED) {
-    // exact fp32: the kernels read none of the copies below; the folded mode's one split segment is the seed of the
-    // analytic-normal sweep (RSN_MMA_F32 packs nothing more: its training kernel forms the same pieces in registers)
+    // exact fp32: the forward and backward kernels read none of the copies below.  The folded mode splits what the analytic-normal
+    // sweep of its training forward reads (nine-product loop, rsn_mfma.h): the seed, then the transposed trunk and encoded-input
+    // segments behind it (RSN_MMA_F32 packs nothing more: its training kernel forms the same pieces in registers)
     if (L.hT_seed != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_seed, L.v_density);
+    if (d->mma_mode == RSN_MMA_F32_FOLDED) {
+      for (int l = 1; l + 1 < n_layers; ++l) split(L.wT_x[l], NB * 4, NB, L.hT_x[l]);
+      if (skip >= 1) split(L.wT_enc_skip, NB * 4, 4, L.hT_enc_skip);
+      split(L.wT_enc0, NB * 4, 4, L.hT_enc0);
+    }
     return RSN_OK;
   }
   split(L.w_enc0, RSN_ENC_ITS, NB, L.h_enc0);
