@@ -719,6 +719,48 @@ int rsn_ssim(int32_t height, int32_t width, const float* pred, const float* targ
              void* workspace, size_t workspace_bytes, float* out, void* stream);
 
 
+/* ---- image pyramids (additive to ABI 18: no existing call changes): every image of the set at 1, 1/2, 1/4, ... of its size, and
+ * training batches drawn across the scales (mip-NeRF's multi-scale protocol, Barron et al. 2021).
+ *
+ * Level l = 0 .. L-1 of an H x W image has (H >> l) x (W >> l) pixels; 1 <= L <= RSN_PYRAMID_MAX_LEVELS, and H and W must be
+ * divisible by 2^(L-1).  Level 0 is the uint8 RGBA image set itself (images [N,H,W,4]); it is never copied.  The levels l >= 1 are
+ * white-blended fp32 [*, 3] in ONE allocation `pyramid`, level after level and within a level image after image, row-major.
+ * Offsets count pixels: level l starts at off_l = sum over 1 <= k < l of N (H >> k) (W >> k), image i of it at
+ * off_l + i (H >> l) (W >> l); the allocation holds off_L pixels, 3 floats each.
+ *
+ * Value of pixel (Y, X), channel c of level l >= 1, with s = 2^l (bit-exact recipe):
+ *   S     = sum over the s x s pixels (Y s + dy, X s + dx) of level 0 of  c8 * a8 + 255 * (255 - a8)     (integers; a8 = alpha)
+ *   value = (float)S / (float)(65025 * s * s)                                                         (one fp32 division)
+ * S <= 65025 * 256 = 16,646,400 < 2^24 for s <= 16, so both operands are exact in fp32 and value is the correctly rounded box
+ * average of the white-blended colours c/255 * a/255 + (1 - a/255): that is where the limit of 5 levels comes from.  Every level
+ * is computed from level 0, never from the level above: no rounding compounds.  No atomics; one lane per output pixel.
+ * Level 0 keeps the fp32 blend written above the single-scale sampler (three roundings); it can differ from S / 65025 by an ulp.
+ *
+ * Camera of level l: the pose of the image and the intrinsics (fx, fy, cx, cy) / 2^l, exact in fp32.  Pixel (y, x) of level l
+ * then covers the pixels (y s .. y s + s - 1, x s .. x s + s - 1) of level 0, and its pixel_area, from the same device function
+ * as every other ray of this library, is 4^l times a level-0 pixel's to first order in the pixel's angular size. */
+#define RSN_PYRAMID_MAX_LEVELS 5
+
+/* The levels 1 .. levels-1 of all images into `pyramid` (capacity pyramid_pixels >= off_L pixels, else an argument error); one
+ * launch.  levels == 1 launches nothing and reads no pointer. */
+int rsn_build_pyramid(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images, float* pyramid,
+                      size_t pyramid_pixels, void* stream);
+
+/* One training batch drawn across the levels, each level with probability 1/L (mip-NeRF draws uniformly over the pixels of all
+ * scales and weights a ray's loss by 4^l; equal level probability is that objective by importance sampling, with unit weights).
+ * Ray r (bit-exact recipe), with the Philox keying of the single-scale sampler:
+ *   (u, v, -, -) = Philox4x32-10(counter = (step, r, 0, 0), key = (seed, rank))
+ *   l = (uint32)(((uint64)v * L) >> 32);  H_l = H >> l, W_l = W >> l
+ *   flat = (uint32)(((uint64)u * (N*H_l*W_l)) >> 32);  i = flat / (H_l*W_l);  y = (flat % (H_l*W_l)) / W_l;  x = flat % W_l
+ * The ray is that of pixel (y, x) of the level's camera; rgb is the single-scale sampler's blend of images for l = 0 and the
+ * pyramid's value for l >= 1.  Outputs as the single-scale sampler's, indices = (i, y, x) in the level's own pixel coordinates,
+ * plus level int32 [R].  With levels == 1 (pyramid may be NULL) every output byte equals the single-scale sampler's. */
+int rsn_sample_pyramid_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images,
+                            const float* pyramid, size_t pyramid_pixels, const float* c2w, float fx, float fy, float cx,
+                            float cy, int32_t n_rays, uint32_t seed, uint32_t rank, uint32_t step, float* origins,
+                            float* directions, float* pixel_area, float* rgb, int32_t* indices, int32_t* level, void* stream);
+
+
 /* ---- mesh export: the iso-surface of a scalar volume as an indexed triangle mesh (additive to ABI 18: no existing call
  * changes).  Marching tetrahedra on the Kuhn (Freudenthal) split of every grid cell: no case table, consistent across
  * shared cell faces by construction (a surface away from the grid boundary is closed), and every surface vertex lies on

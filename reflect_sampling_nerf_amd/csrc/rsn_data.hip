@@ -5,31 +5,12 @@
 // Recipes (Philox keying, ray arithmetic, SSIM definition): include/rsn.h.
 #include "rsn_camera.h"
 #include "rsn_common.h"
+#include "rsn_philox.h"
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------ Philox4x32-10
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r > 0) {
-      k0 += W0;
-      k1 += W1;
-    }
-    const uint64_t p0 = (uint64_t)M0 * c.x, p1 = (uint64_t)M1 * c.z;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-  }
-  return c;
-}
-
 // ------------------------------------------------------------------------------------------------ camera rays
-// Intrinsics and camera_ray: rsn_camera.h (shared with rsn_pointcloud.hip)
+// Intrinsics and camera_ray: rsn_camera.h (shared with rsn_pointcloud.hip and rsn_pyramid.hip); Philox4x32-10: rsn_philox.h
 struct SampleArgs {
   int32_t n_images, height, width, n_rays;
   const uint8_t* images;  // [N, H, W, 4]

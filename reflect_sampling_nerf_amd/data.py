@@ -4,6 +4,10 @@
 `RayDataManager.next_train` is the reference datamanager's next_train (reflect_sampling_nerf_datamanager.py:49-58: pixel sampler ->
 pixel gather -> ray generator) as ONE launch of rsn_sample_camera_rays on the images uploaded once: no host work beyond the launch,
 no device-to-host read.  The exact sampling and ray recipes are in include/rsn.h.
+
+`RayDataManager(..., levels=L)` with L > 1 is mip-NeRF's multi-scale protocol: rsn_build_pyramid forms every image at 1/2 .. 1/2^(L-1)
+of its size once, next_train draws each ray's level with probability 1/L (rsn_sample_pyramid_rays, still one launch), and
+camera_ray_bundle / image take a level.
 """
 from __future__ import annotations
 
@@ -100,14 +104,41 @@ def load_blender_split(root: str, split: str, scale_factor: float = 1.0) -> Blen
     return BlenderScene(images=im, c2w=c2w, fx=focal, fy=focal, cx=W / 2.0, cy=H / 2.0)
 
 
+MAX_LEVELS = 5  # include/rsn.h RSN_PYRAMID_MAX_LEVELS: a 16 x 16 box keeps the integer sums of the blend below 2^24
+
+
+def pyramid_layout(n_images: int, height: int, width: int, levels: int) -> Tuple[Tuple[Tuple[int, int], ...], Tuple[int, ...]]:
+    """The pyramid of include/rsn.h ("image pyramids") for N images of height x width: -> (sizes, offsets) with sizes[l] = (H >> l,
+    W >> l) for l = 0 .. levels-1 and offsets[l] = the first pixel of level l >= 1 in the one allocation (offsets[0] = 0 is unused:
+    level 0 is the image set itself), offsets[levels] = its size in pixels.  ValueError for levels outside 1 .. 5 and for a size that
+    2^(levels-1) does not divide; host arithmetic only."""
+    levels = int(levels)
+    if not 1 <= levels <= MAX_LEVELS:
+        raise ValueError(f"levels = {levels}: need 1 to {MAX_LEVELS}")
+    s = 1 << (levels - 1)
+    if height % s or width % s:
+        raise ValueError(f"images of {width} x {height} pixels: {levels} levels need a width and a height divisible by {s}")
+    sizes = tuple((height >> l, width >> l) for l in range(levels))
+    offsets = [0, 0]
+    for l in range(1, levels):
+        offsets.append(offsets[-1] + n_images * sizes[l][0] * sizes[l][1])
+    return sizes, tuple(offsets[:levels + 1])
+
+
 class RayDataManager:
     """Training batches and full-image ray bundles of a BlenderScene, on `device`.
 
     The images and poses are uploaded once.  next_train(step) draws num_rays_per_batch pixels uniformly with replacement
     over all images (Philox4x32-10 keyed by (seed, rank), counter (step, ray)), so a batch is a pure function of
-    (seed, rank, step): a later rank of a data-parallel run gets its own stream by its rank alone."""
+    (seed, rank, step): a later rank of a data-parallel run gets its own stream by its rank alone.
 
-    def __init__(self, scene: BlenderScene, device, num_rays_per_batch: int = 1024, seed: int = 0, rank: int = 0):
+    levels > 1: the images also exist at 1/2 .. 1/2^(levels-1) of their size (self.pyramid, built once on the device); a ray's level
+    is drawn first, with probability 1 / levels, then its pixel within the level, from the same Philox words.  levels = 1 is the
+    single-scale path: the same launches and bytes as without the argument."""
+
+    def __init__(self, scene: BlenderScene, device, num_rays_per_batch: int = 1024, seed: int = 0, rank: int = 0, levels: int = 1):
+        self.levels = int(levels)
+        self.level_sizes, self.level_offsets = pyramid_layout(scene.num_images, scene.height, scene.width, self.levels)  # raises first
         self.scene = scene
         self.device = torch.device(device)
         self.num_rays_per_batch = int(num_rays_per_batch)
@@ -116,37 +147,72 @@ class RayDataManager:
         self.images = torch.from_numpy(np.ascontiguousarray(scene.images)).to(self.device)
         self.c2w = torch.from_numpy(np.ascontiguousarray(scene.c2w, dtype=np.float32)).to(self.device)
         self._lib = _abi.load_library()
+        self.pyramid = None  # fp32 [pixels of the levels >= 1, 3]
+        if self.levels > 1:
+            self.pyramid = torch.empty(self.level_offsets[-1], 3, device=self.device, dtype=torch.float32)
+            _abi.check(self._lib.rsn_build_pyramid(scene.num_images, scene.height, scene.width, self.levels, _abi.ptr(self.images),
+                                                   _abi.ptr(self.pyramid), self.pyramid.shape[0], self._stream()))
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def next_train(self, step: int) -> Tuple[RayBundle, Dict[str, torch.Tensor]]:
         """-> (RayBundle [R] with nears / fars None (the model's collider fills them), {"image": [R,3] white-blended
-        rgb, "indices": int32 [R,3] = (image, y, x)}).  One kernel launch."""
+        rgb, "indices": int32 [R,3] = (image, y, x)}).  One kernel launch.  With levels > 1 the batch also holds "levels": int32
+        [R], and (y, x) are pixel coordinates of the ray's own level."""
         s, R = self.scene, self.num_rays_per_batch
         flat = torch.empty(R * 10, device=self.device, dtype=torch.float32)  # one allocation, four views
-        idx = torch.empty(R, 3, device=self.device, dtype=torch.int32)
+        multi = self.levels > 1
+        idx = torch.empty(R, 4 if multi else 3, device=self.device, dtype=torch.int32)  # multi: the levels ride behind the indices
         o, d, pa, rgb = (flat[0:3 * R].view(R, 3), flat[3 * R:6 * R].view(R, 3), flat[6 * R:7 * R].view(R, 1),
                          flat[7 * R:10 * R].view(R, 3))
-        _abi.check(self._lib.rsn_sample_camera_rays(
-            s.num_images, s.height, s.width, _abi.ptr(self.images), _abi.ptr(self.c2w), s.fx, s.fy, s.cx, s.cy, R,
-            self.seed, self.rank, int(step) & 0xFFFFFFFF, _abi.ptr(o), _abi.ptr(d), _abi.ptr(pa), _abi.ptr(rgb),
-            _abi.ptr(idx), self._stream()))
+        if not multi:
+            _abi.check(self._lib.rsn_sample_camera_rays(
+                s.num_images, s.height, s.width, _abi.ptr(self.images), _abi.ptr(self.c2w), s.fx, s.fy, s.cx, s.cy, R,
+                self.seed, self.rank, int(step) & 0xFFFFFFFF, _abi.ptr(o), _abi.ptr(d), _abi.ptr(pa), _abi.ptr(rgb),
+                _abi.ptr(idx), self._stream()))
+            rb = RayBundle(origins=o, directions=d, pixel_area=pa, camera_indices=idx[:, 0:1])
+            return rb, {"image": rgb, "indices": idx}
+        both = idx.view(-1)
+        idx, lvl = both[:3 * R].view(R, 3), both[3 * R:]
+        _abi.check(self._lib.rsn_sample_pyramid_rays(
+            s.num_images, s.height, s.width, self.levels, _abi.ptr(self.images), _abi.ptr(self.pyramid), self.pyramid.shape[0],
+            _abi.ptr(self.c2w), s.fx, s.fy, s.cx, s.cy, R, self.seed, self.rank, int(step) & 0xFFFFFFFF, _abi.ptr(o), _abi.ptr(d),
+            _abi.ptr(pa), _abi.ptr(rgb), _abi.ptr(idx), _abi.ptr(lvl), self._stream()))
         rb = RayBundle(origins=o, directions=d, pixel_area=pa, camera_indices=idx[:, 0:1])
-        return rb, {"image": rgb, "indices": idx}
+        return rb, {"image": rgb, "indices": idx, "levels": lvl}
 
-    def camera_ray_bundle(self, i: int) -> RayBundle:
-        """The [H,W] RayBundle of camera i (row-major), for Model.get_outputs_for_camera_ray_bundle."""
+    def _level(self, level: int) -> int:
+        if not 0 <= level < self.levels:
+            raise IndexError(f"level {level} of {self.levels}")
+        return int(level)
+
+    def level_intrinsics(self, level: int = 0) -> Tuple[float, float, float, float]:
+        """(fx, fy, cx, cy) of the level's camera: the scene's over 2^level (exact: a power of two)."""
+        s, k = self.scene, float(1 << self._level(level))
+        return s.fx / k, s.fy / k, s.cx / k, s.cy / k
+
+    def camera_ray_bundle(self, i: int, level: int = 0) -> RayBundle:
+        """The [H,W] RayBundle of camera i (row-major), for Model.get_outputs_for_camera_ray_bundle; level l: the [H >> l, W >> l]
+        bundle of the level's camera (the same pose, the intrinsics over 2^l)."""
         s = self.scene
         if not 0 <= i < s.num_images:
             raise IndexError(f"camera {i} of {s.num_images}")
         from .render import camera_rays
 
-        rb = camera_rays(self.c2w[i], s.height, s.width, s.fx, s.fy, s.cx, s.cy, self.device)
-        rb.camera_indices = torch.full((s.height, s.width, 1), i, device=self.device, dtype=torch.int32)
+        (h, w), (fx, fy, cx, cy) = self.level_sizes[self._level(level)], self.level_intrinsics(level)
+        rb = camera_rays(self.c2w[i], h, w, fx, fy, cx, cy, self.device)
+        rb.camera_indices = torch.full((h, w, 1), i, device=self.device, dtype=torch.int32)
         return rb
 
-    def image(self, i: int) -> torch.Tensor:
+    def image(self, i: int, level: int = 0) -> torch.Tensor:
         """Ground truth of camera i: [H,W,4] float32 RGBA in [0, 1] on the device, uint8 / 255 as nerfstudio's
-        InputDataset forms it (get_image_metrics_and_images and get_loss_dict blend the alpha onto white)."""
-        return torch.from_numpy(self.scene.images[i].astype(np.float32) / np.float32(255.0)).to(self.device)
+        InputDataset forms it (get_image_metrics_and_images and get_loss_dict blend the alpha onto white).  level l >= 1: the
+        pyramid's [H >> l, W >> l, 3] image, already blended onto white; a view, not a copy."""
+        if self._level(level) == 0:
+            return torch.from_numpy(self.scene.images[i].astype(np.float32) / np.float32(255.0)).to(self.device)
+        if not 0 <= i < self.scene.num_images:
+            raise IndexError(f"camera {i} of {self.scene.num_images}")
+        h, w = self.level_sizes[level]
+        first = self.level_offsets[level] + i * h * w
+        return self.pyramid[first:first + h * w].view(h, w, 3)

@@ -1,7 +1,7 @@
 """Standalone training and evaluation on Blender-format scenes, without nerfstudio.
 
-    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite]
-    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json]
+    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L]
+    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
     python -m reflect_sampling_nerf_amd.trainer export-mesh ... --out mesh.obj --texture [--texels 8] [--min-footprint F]
@@ -30,6 +30,16 @@ and `--skip-nonfinite` leaves parameters and moments untouched on a step whose g
 GradScaler does for `ns-train` under mixed precision); both are off by default and decided on the device (FusedRAdam).  A guarded
 run's log lines carry the gradient norm, the clip factor and the number of skipped steps, and the first line after a skip names the
 parameters whose gradients were not finite.  Both settings are recorded in the checkpoint and come back with --resume.
+
+`train --multiscale L` and `eval --multiscale L` are mip-NeRF's multi-scale protocol (Barron et al. 2021) for L = 2 .. 5: every view
+also exists at 1/2 .. 1/2^(L-1) of its size, as box averages of the white-blended pixels built once on the device (data.py).  Training
+draws each ray's scale with probability 1/L -- in expectation mip-NeRF's objective, which draws uniformly over the pixels of all
+scales and weights a ray's loss by its pixel's area: the same objective by importance sampling, with the losses untouched.  `eval`
+renders and scores every view at every scale against the pyramid's ground truth: the JSON's psnr_x1, psnr_x2, psnr_x4, ... (and so on
+for every metric) are the means over the views at one scale, the plain keys the mean of those per-scale means.  The image size must
+be divisible by 2^(L-1), and `eval` needs the smallest scale to be at least 11 x 11 (the SSIM window).  The setting is recorded in the
+checkpoint when it is above 1 and comes back with --resume; the default, 1, is the single-scale run with the launches, bytes and
+checkpoint keys it always had.
 
 `export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
 the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
@@ -86,7 +96,7 @@ MMA_CHOICES = ("f32", "bf16x6", "bf16")
 EVAL_CHUNK = 1024  # reflect_sampling_nerf_config.py:41 eval_num_rays_per_chunk
 RUN_STATE_KEY = "rsn_run"  # the trainer's own fifth checkpoint key; nerfstudio's loader ignores it
 RUN_STATE_VERSION = 1
-RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
+RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0, "multiscale": 1}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
 LPIPS_NOTE = "fine_lpips not computed: LPIPS needs pretrained network weights that are not shipped with this package"
 
 
@@ -162,10 +172,13 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                     help="clip the global gradient norm to X before every optimiser step (default: no clipping)")
     tr.add_argument("--skip-nonfinite", action="store_true",
                     help="a step whose gradients hold an inf or a NaN changes no parameter and no optimiser moment")
+    tr.add_argument("--multiscale", type=int, default=dflt["multiscale"], metavar="L",
+                    help="draw the training rays from L scales of every image, 1, 1/2, ... 1/2^(L-1), each with probability 1/L "
+                         "(1 to 5; default 1: full resolution only); the image size must be divisible by 2^(L-1)")
     tr.add_argument("--resume", default=None, metavar="PATH",
                     help="continue from this step-*.ckpt, or from the newest one in this run directory; --steps stays the total, and "
-                         "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite come from the checkpoint "
-                         "unless given")
+                         "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite / --multiscale come from the "
+                         "checkpoint unless given")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
     ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json")
     ev.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
@@ -174,6 +187,9 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ev.add_argument("--out", default="metrics.json", help="output JSON")
     ev.add_argument("--save-images", default=None, help="directory for rendered ground truth | coarse | fine panels")
     ev.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    ev.add_argument("--multiscale", type=int, default=1, metavar="L",
+                    help="score every view at L scales, 1, 1/2, ... 1/2^(L-1), against box-averaged ground truth (1 to 5; default 1); "
+                         "the results gain KEY_x1, KEY_x2, ... per scale and the plain KEY becomes the mean of those")
     _add_occupancy_flags(ev)
     ex = sub.add_parser("export-mesh", help="write the iso-surface of a checkpoint's density as a coloured triangle mesh (PLY)")
     ex.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
@@ -479,12 +495,12 @@ def resolve_checkpoint(path: str) -> str:
 
 
 def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, max_grad_norm: Optional[float] = None,
-                   skip_nonfinite: Optional[bool] = None) -> dict:
+                   skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None) -> dict:
     """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
     bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
     seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one.
     max_grad_norm / skip_nonfinite (the optimiser's guard) are recorded only when set: an unguarded run's entry has the keys it
-    always had."""
+    always had.  Likewise multiscale (the number of pyramid levels the rays are drawn from): only when above 1."""
     dev = torch.device(device)
     state = {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
              "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
@@ -493,6 +509,8 @@ def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, 
         state["max_grad_norm"] = float(max_grad_norm)
     if skip_nonfinite:
         state["skip_nonfinite"] = True
+    if multiscale is not None and int(multiscale) > 1:
+        state["multiscale"] = int(multiscale)
     return state
 
 
@@ -553,8 +571,9 @@ def load_checkpoint(path: str, model_config=None, device="cuda:0"):
 
 # ------------------------------------------------------------------------------------------------ train
 def _resolve_run_settings(given: dict, recorded: Optional[dict]):
-    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite: the caller's value if given, else the checkpoint's,
-    else the fresh-run default (deterministic: None = the model's own default; the two guard settings: None = off).
+    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale: the caller's value if given, else the
+    checkpoint's, else the fresh-run default (deterministic: None = the model's own default; the two guard settings: None = off;
+    multiscale: 1, which a checkpoint does not record).
     -> (settings, one line per given value that departs from the checkpoint's)."""
     out, notes = {}, []
     for k, v in given.items():
@@ -582,7 +601,7 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
           log_every: int = 100, seed: Optional[int] = None, device="cuda:0", model_config=None,
           log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None, resume: Optional[str] = None,
           on_step: Optional[Callable[[int, torch.Tensor], None]] = None, max_grad_norm: Optional[float] = None,
-          skip_nonfinite: Optional[bool] = None) -> str:
+          skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None) -> str:
     """Train on `scene` (a data.BlenderScene) up to iteration `steps` (the total, nerfstudio's max_num_iterations); returns the path
     of the last checkpoint.  Checkpoints at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer
     does the same).  The loss is read back only every log_every steps: the iterations in between never wait for the GPU.
@@ -595,6 +614,10 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     log_every lines -- where the loss is read back anyway -- also read the optimiser's guard_stats(): the last step's gradient
     norm and clip factor and the number of steps skipped so far; the first such line after a skip names the parameters whose
     gradients were not finite on the last skipped step.  The steps in between read nothing.
+
+    multiscale: the number of pyramid levels the rays are drawn from (RayDataManager's levels; None: the checkpoint's when resuming,
+    else 1).  A batch stays a pure function of (seed, rank, step) and the pyramid one of the images, so the paragraph on the restored
+    state below holds for a multi-scale run as it stands.
 
     resume: a step-*.ckpt or a run directory (its latest).  A checkpoint of step k continues at k + 1 with the same checkpoint names
     and save_every rule; k >= steps - 1 is a ValueError.  Model (strict, as load_checkpoint) and FusedRAdam state come from the file.
@@ -611,14 +634,14 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     (test_deterministic_gpu).  One value does travel between steps, only under the opt-in reflect_capacity = "auto": the reflected
     count that sizes the next step's reflect buffers.  It is not saved.  A resumed run starts with full-size buffers, which is
     the exact computation; it can differ from the uninterrupted run only on a step which that run truncated (and warned about)."""
-    from .data import RayDataManager
+    from .data import RayDataManager, pyramid_layout
     from .parallel import train_step
     from .train_ops import FusedRAdam
 
     if steps < 1:
         raise ValueError(f"steps must be >= 1, got {steps}")
     given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic, "max_grad_norm": max_grad_norm,
-             "skip_nonfinite": skip_nonfinite}
+             "skip_nonfinite": skip_nonfinite, "multiscale": multiscale}
     first, model, ckpt, recorded = 0, None, None, None
     if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
         resume = resolve_checkpoint(resume)
@@ -632,9 +655,10 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
             raise ValueError(f"{resume}: {RUN_STATE_KEY} version {recorded.get('version')!r}, this trainer reads {RUN_STATE_VERSION}")
     cfg, notes = _resolve_run_settings(given, recorded)
     rays, mma, seed, deterministic = cfg["rays"], cfg["mma"], cfg["seed"], cfg["deterministic"]
-    max_grad_norm, skip_nonfinite = cfg["max_grad_norm"], bool(cfg["skip_nonfinite"])
+    max_grad_norm, skip_nonfinite, multiscale = cfg["max_grad_norm"], bool(cfg["skip_nonfinite"]), int(cfg["multiscale"])
     if mma not in MMA_CHOICES:
         raise ValueError(f"mma must be one of {MMA_CHOICES}, got {mma!r}")
+    pyramid_layout(scene.num_images, scene.height, scene.width, multiscale)  # a size the levels do not divide ends here, on the host
     dev = torch.device(device)
     if model is None:
         model = make_model(model_config, seed)
@@ -642,7 +666,7 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     model.field.set_mma_mode(mma)
     if deterministic is not None:
         model.set_deterministic(deterministic)
-    dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed)
+    dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed, levels=multiscale)
     params = model.get_param_groups()["fields"]
     name_of = {id(p): n for n, p in model.named_parameters()}
     optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000,  # config.py:50-53
@@ -652,6 +676,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         settings += f" max_grad_norm {max_grad_norm:g}"
     if skip_nonfinite:
         settings += " skip_nonfinite True"
+    if multiscale > 1:
+        settings += f" multiscale {multiscale}"
     if resume is None:
         if log is not None:
             log(f"train: {settings}")
@@ -686,7 +712,7 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
             log(line)
         if (save_every and step > 0 and step % save_every == 0) or step == steps - 1:
             last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
-                                   make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite))
+                                   make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite, multiscale))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -697,19 +723,45 @@ def _white(image: torch.Tensor) -> torch.Tensor:
     return image[..., :3] * image[..., 3:] + (1.0 - image[..., 3:]) if image.shape[-1] == 4 else image
 
 
+MULTISCALE_NOTE = ("every view is scored at every scale 1/s, s = 1, 2, 4, ..., against the box average of the white-blended ground truth; "
+                   "KEY_x<s> / KEY_x<s>_std are the mean and the unbiased standard deviation over the views at scale 1/s; the plain KEY "
+                   "is the mean of the per-scale means and KEY_std the unbiased standard deviation of those means")
+SSIM_WINDOW = 11  # include/rsn.h rsn_ssim
+
+
+def eval_level_sizes(scene, multiscale: int):
+    """((H, W) of level 0 .. multiscale-1) of the scene's views; ValueError for a level count outside 1 .. 5, a size 2^(multiscale-1)
+    does not divide, and a smallest level below the 11 x 11 pixels SSIM needs.  Host arithmetic only."""
+    from .data import pyramid_layout
+
+    sizes, _ = pyramid_layout(scene.num_images, scene.height, scene.width, multiscale)
+    if multiscale > 1 and min(sizes[-1]) < SSIM_WINDOW:
+        raise ValueError(f"multiscale {multiscale}: the views of level {multiscale - 1} are {sizes[-1][1]} x {sizes[-1][0]} pixels, "
+                         f"SSIM needs at least {SSIM_WINDOW} x {SSIM_WINDOW}")
+    return sizes
+
+
 def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Optional[str] = None, device="cuda:0",
-             model_config=None, occupancy: Optional[dict] = None) -> dict:
+             model_config=None, occupancy: Optional[dict] = None, multiscale: int = 1) -> dict:
     """Score the checkpoint (a file, or the latest of a run directory) on every view of `scene` (a data.BlenderScene); -> ns-eval-
     shaped dict.  occupancy: None, or the settings of resolve_occupancy_args: the views are rendered with empty-space skipping and
-    the dict gains an "occupancy" entry."""
+    the dict gains an "occupancy" entry.
+
+    multiscale = L > 1: every view is rendered and scored at the L levels of RayDataManager's pyramid.  per_image then holds one entry
+    per (view, level) with a "level" key, view after view; results gains k_x1, k_x2, k_x4, ... (+ _std) for every metric k, the mean
+    over the views at that level; the plain k is the mean of the per-level means, and a "multiscale" entry says so.  The occupancy grid
+    is built once, from the full-resolution cameras (whose frusta are those of every level), and culls the rays of every level.
+    ValueError, before the checkpoint is read, when the smallest level is below the 11 x 11 pixels SSIM needs."""
     from . import metrics
     from .data import RayDataManager
 
+    multiscale = int(multiscale)
+    sizes = eval_level_sizes(scene, multiscale)
     dev = torch.device(device)
     ckpt = resolve_checkpoint(ckpt)
     model, step = load_checkpoint(ckpt, model_config, dev)
     model.config.eval_num_rays_per_chunk = EVAL_CHUNK
-    dm = RayDataManager(scene, dev)
+    dm = RayDataManager(scene, dev, levels=multiscale)
     n = scene.num_images if max_images is None else min(int(max_images), scene.num_images)
     if occupancy is not None:
         from .occupancy import attach_occupancy
@@ -718,32 +770,44 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     if save_images:
         os.makedirs(save_images, exist_ok=True)
     per_image = []
-    for i in range(n):
+    for i, level in ((i, level) for i in range(n) for level in range(multiscale)):
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        outputs = model.get_outputs_for_camera_ray_bundle(dm.camera_ray_bundle(i))
-        gt = dm.image(i)
+        outputs = model.get_outputs_for_camera_ray_bundle(dm.camera_ray_bundle(i, level))
+        gt = dm.image(i, level)
         m, images = model.get_image_metrics_and_images(outputs, {"image": gt})
         m = dict(m)
         m["fine_ssim"] = float(metrics.ssim(torch.clip(outputs["mid_reflect_fine"], 0.0, 1.0), _white(gt)))
         dt = time.time() - t0
-        m["num_rays_per_sec"] = scene.height * scene.width / dt
+        m["num_rays_per_sec"] = sizes[level][0] * sizes[level][1] / dt
         m["fps"] = 1.0 / dt
-        per_image.append({"image": i, **m})
+        per_image.append({"image": i, **({"level": level} if multiscale > 1 else {}), **m})
         if save_images:
             from PIL import Image
 
             panel = (images["img"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
-            Image.fromarray(panel).save(os.path.join(save_images, f"{i:04d}_img.png"))
-    keys = [k for k in per_image[0] if k != "image"] if per_image else []
+            name = f"{i:04d}_img.png" if level == 0 else f"{i:04d}_x{1 << level}_img.png"
+            Image.fromarray(panel).save(os.path.join(save_images, name))
+    keys = [k for k in per_image[0] if k not in ("image", "level")] if per_image else []
+
+    def mean_std(v):
+        v = np.asarray(v, dtype=np.float64)
+        return float(v.mean()), float(v.std(ddof=1)) if len(v) > 1 else 0.0  # torch.std_mean (ns-eval): unbiased
+
     results = {}
     for k in keys:
-        v = np.array([p[k] for p in per_image], dtype=np.float64)
-        results[k] = float(v.mean())
-        results[k + "_std"] = float(v.std(ddof=1)) if len(v) > 1 else 0.0  # torch.std_mean (ns-eval): unbiased
+        if multiscale == 1:
+            results[k], results[k + "_std"] = mean_std([p[k] for p in per_image])
+            continue
+        per_level = [mean_std([p[k] for p in per_image if p["level"] == level]) for level in range(multiscale)]
+        results[k], results[k + "_std"] = mean_std([m for m, _ in per_level])
+        for level, (m, sd) in enumerate(per_level):
+            results[f"{k}_x{1 << level}"], results[f"{k}_x{1 << level}_std"] = m, sd
     res = {"experiment_name": os.path.basename(os.path.dirname(os.path.abspath(ckpt))), "method_name": METHOD_NAME,
            "checkpoint": ckpt, "step": step, "results": results, "not_computed": {"fine_lpips": LPIPS_NOTE},
            "per_image": per_image}
+    if multiscale > 1:
+        res["multiscale"] = {"levels": multiscale, "scales": [1 << level for level in range(multiscale)], "note": MULTISCALE_NOTE}
     if occupancy is not None:
         res["occupancy"] = model.occupancy.describe()
     return res
@@ -764,15 +828,24 @@ def main(argv=None) -> int:
     cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
         ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
+    if args.command in ("train", "eval") and not 1 <= args.multiscale <= 5:
+        ap.error(f"{args.command}: --multiscale {args.multiscale}: need 1 to 5")
     if not torch.cuda.is_available():
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
     if args.command == "train":
         scene = load_blender_split(args.data, "train", args.scale_factor)
         print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}")
+        if args.multiscale > 1:  # a resumed run's own level count is checked by train()
+            from .data import pyramid_layout
+
+            try:
+                pyramid_layout(scene.num_images, scene.height, scene.width, args.multiscale)
+            except ValueError as e:
+                ap.error(f"train: --multiscale {args.multiscale}: {e}")
         train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
               log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume,
-              max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None)
+              max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None, multiscale=given.multiscale)
         return 0
     if args.command == "export-mesh":
         from . import mesh
@@ -824,10 +897,18 @@ def main(argv=None) -> int:
               f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
         return 0
     scene = load_blender_split(args.data, args.split, args.scale_factor)
-    res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images, occupancy=occupancy)
+    try:
+        eval_level_sizes(scene, args.multiscale)
+    except ValueError as e:
+        ap.error(f"eval: {e}")
+    res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images, occupancy=occupancy,
+                   multiscale=args.multiscale)
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=2)
     r = res["results"]
+    for level in range(args.multiscale if args.multiscale > 1 else 0):
+        print(f"  1/{1 << level}: " + " ".join(f"{k} {r[f'{k}_x{1 << level}']:.4f}" for k in ("psnr", "coarse_psnr", "fine_psnr", "fine_ssim")
+                                        if f"{k}_x{1 << level}" in r and not math.isnan(r[f"{k}_x{1 << level}"])))
     print(" ".join(f"{k} {r[k]:.4f}" for k in ("psnr", "coarse_psnr", "fine_psnr", "fine_ssim") if k in r
                    and not math.isnan(r[k])) + f"  ({len(res['per_image'])} images) -> {args.out}")
     return 0
