@@ -422,6 +422,38 @@ typedef struct rsn_composite_bwd_io {
 int rsn_composite_backward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, int32_t background, int32_t flags,
                            int32_t detach_weights, const rsn_composite_bwd_io* io, void* stream);
 
+/* Distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15; nerfstudio's lossfun_distortion) of one level's compositing
+ * weights, an opt-in regulariser of the training step.  Per ray, with the S intervals of the samplers' normalised spacing bins
+ * s_0 <= ... <= s_S (spacing_bins [R,S+1], ascending), midpoints m_i = (s_i + s_{i+1}) / 2, widths d_i = s_{i+1} - s_i and the
+ * weights w_i of rsn_composite (weights [R,S]):
+ *   L_ray        = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+ *   dL_ray/dw_k  = 2 sum_j w_j |m_k - m_j| + (2/3) w_k d_k
+ * The double sum is evaluated in O(S) from prefix sums of w and w m along the sorted ray,
+ *   sum_j w_j |m_k - m_j| = m_k (W_<k - W_>k) - (WM_<k - WM_>k),
+ * which subtracts numbers of order 1 for a result that is tiny on a compact ray: midpoints, widths, prefixes and the per-ray sum are
+ * fp64 (exact from the fp32 bits up to the scans' roundings) and the result is rounded to fp32 once.
+ * One wave per ray, 64-sample chunks with carried scans, no atomics, a fixed order of addition: the same inputs give the same bits.
+ * n_dev (or NULL): device-side ray count, min(n_rays, *n_dev) rows are processed and the rows behind are not touched.
+ *
+ * rsn_distortion_forward: loss_ray [R] = L_ray, unscaled.
+ * rsn_distortion_backward: g_w[k] = g_loss_ray[r] dL_ray/dw_k is recomputed (nothing [R,S]-sized is kept from the forward) and
+ *   carried to sigma through the transmittance by rsn_composite_backward's rule,
+ *     g_sigma[k] = delta_k (g_w[k] T_{k+1} - sum_{i>k} g_w[i] w_i),  delta_k from euclid_bins [R,S+1], T_{k+1} = exp(-sum_{j<=k} delta_j sigma_j),
+ *   sigma [R,S] and euclid_bins being the inputs of the rsn_composite call whose weights the forward read.  It takes no weights: it
+ *   re-derives them in fp64, w_k = (1 - exp(-delta_k sigma_k)) T_k.  rsn_composite's fp32 weights are good to 2^-24 of T_k, not of
+ *   w_k, and both g_w and the suffix sum are proportional to single weights; from them a thin sample's gradient is off by thousands
+ *   of fp32 roundings.  The suffix sum is added up from the far end of the ray, not taken as total - prefix.
+ *   accumulate != 0: the value, rounded to fp32, is ADDED to g_sigma [R,S] (the training step adds it to what
+ *   rsn_composite_backward wrote); 0: it overwrites.  n_samples <= 4096 (RSN_ERR_UNSUPPORTED above).
+ *
+ * RSN_ERR_INVALID_ARGUMENT before any launch: n_rays < 0, n_samples < 1, or, with n_rays > 0, a NULL pointer other than n_dev.
+ * n_rays == 0 launches nothing. */
+int rsn_distortion_forward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* spacing_bins, const float* weights,
+                           float* loss_ray, void* stream);
+int rsn_distortion_backward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* spacing_bins,
+                            const float* euclid_bins, const float* sigma, const float* g_loss_ray, float* g_sigma,
+                            int32_t accumulate, void* stream);
+
 /* Standalone encoders: what calling the Field's encoding modules directly computes.
  * rsn_sh34_encode: IntegratedSHEncoding.forward (components.py:52-140): 34 real-SH terms of bands l = 1, 2, 4, 8 of
  *   `directions` [n,3], band l attenuated by exp(-l(l+1)/2 * roughness) (roughness [n] or NULL = 0); out [n,34].

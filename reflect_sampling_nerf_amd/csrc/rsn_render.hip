@@ -441,6 +441,183 @@ extern "C" int rsn_composite_backward(int32_t n_rays, const int32_t* n_dev, int3
   return RSN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// distortion loss (mip-NeRF 360 eq. 15) of one level's weights on the samplers' normalised spacing bins (include/rsn.h):
+//   L = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i,   dL/dw_k = 2 sum_j w_j |m_k - m_j| + (2/3) w_k d_k.
+// The bins ascend along the ray, so sum_{j<k} w_j (m_k - m_j) = m_k W_<k - WM_<k with exclusive prefix sums of w and w m.  That
+// difference of order-1 numbers is tiny on a compact ray: midpoints, widths, products and prefixes are fp64 (m, d and w m are exact
+// there), rounded to fp32 once at the end.  One wave per ray, 64-sample chunks with carried scans, like compositing.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// sample i of a ray: weight, midpoint and width of its spacing interval (zeros past the ray's end)
+__device__ __forceinline__ void dist_sample(const float* sb, const float* w, int i, bool in, double& wd, double& m, double& d) {
+  wd = m = d = 0.0;
+  if (in) {
+    const double a = (double)sb[i], b = (double)sb[i + 1];
+    wd = (double)w[i];
+    m = 0.5 * (a + b);
+    d = b - a;
+  }
+}
+
+// exclusive prefix (carried across the chunks) of v along the ray; advances the carry
+__device__ __forceinline__ double dist_excl(double v, int lane, double& carry) {
+  const double incl = wave_scan_incl(v, lane);
+  const double prev = __shfl_up(incl, 1, 64);
+  const double excl = (lane > 0 ? prev : 0.0) + carry;
+  carry += __shfl(incl, 63, 64);
+  return excl;
+}
+
+__global__ __launch_bounds__(256) void rsn_distortion_fwd_kernel(int n_rays, const int* n_dev, int S, const float* spacing_bins,
+                                                                 const float* weights, float* loss_ray) {
+  const int R = dyn_count(n_rays, n_dev);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int ray = blockIdx.x * 4 + wid; ray < R; ray += gridDim.x * 4) {
+    const float* sb = spacing_bins + (long long)ray * (S + 1);
+    const float* w = weights + (long long)ray * S;
+    double carry_w = 0.0, carry_wm = 0.0, part = 0.0;
+    for (int base = 0; base < S; base += 64) {
+      const int i = base + lane;
+      double wd, m, d;
+      dist_sample(sb, w, i, i < S, wd, m, d);
+      const double ew = dist_excl(wd, lane, carry_w);
+      const double ewm = dist_excl(wd * m, lane, carry_wm);
+      // both orders of the pair (i, j < i), and the sample's own interval
+      part += 2.0 * wd * (m * ew - ewm) + wd * wd * d * (1.0 / 3.0);
+    }
+    part = wave_sum_f64(part);
+    if (lane == 0) loss_ray[ray] = (float)part;
+  }
+}
+
+extern "C" int rsn_distortion_forward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* spacing_bins,
+                                      const float* weights, float* loss_ray, void* stream) {
+  RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
+  if (n_rays == 0) return RSN_OK;
+  RSN_REQUIRE(spacing_bins && weights && loss_ray, RSN_ERR_INVALID_ARGUMENT, "spacing_bins/weights/loss_ray is NULL");
+  int blocks = (n_rays + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(rsn_distortion_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_rays, n_dev, n_samples,
+                     spacing_bins, weights, loss_ray);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+// Backward: g_w[k] = g dL/dw_k from the same prefixes (W_>k = W - W_<k - w_k), then rsn_composite_bwd_kernel's rule
+//   g_sigma[k] = delta_k (g_w[k] T_{k+1} - sum_{i>k} g_w[i] w_i).
+// The weights are re-derived here in fp64 from sigma and the euclidean bins, w_k = -expm1(-x_k) exp(-X_k): rsn_composite's fp32
+// weights are good to 2^-24 of the transmittance T_k, not of w_k (1 - expf(-x) for a small x), and dL/dw and the suffix sum are
+// proportional to single weights.  The suffix sum is added up from the far end (the lanes above within the chunk, plus the totals of
+// the later chunks, one per lane: S <= 64 x 64), never total - prefix: behind an opaque sample it is exactly what is left.
+#define DIST_MAX_S 4096
+
+struct dist_sample64 {
+  double w, m, d, delta, t_next;  // weight, spacing midpoint and width, euclidean width, T_{k+1}
+};
+
+__device__ __forceinline__ dist_sample64 dist_derive(const float* sb, const float* eb, const float* sigma, int i, bool in, int lane,
+                                                     double& carry_x) {
+  dist_sample64 c = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double x = 0.0;
+  if (in) {
+    const double a = (double)sb[i], b = (double)sb[i + 1];
+    c.m = 0.5 * (a + b);
+    c.d = b - a;
+    c.delta = (double)eb[i + 1] - (double)eb[i];
+    x = c.delta * (double)sigma[i];
+  }
+  const double incl = wave_scan_incl(x, lane);
+  const double prev = __shfl_up(incl, 1, 64);
+  const double excl = (lane > 0 ? prev : 0.0) + carry_x;  // X_k (not incl - x: an infinite x must not poison its own T)
+  const double xin = incl + carry_x;                       // X_{k+1}
+  carry_x = __shfl(xin, 63, 64);
+  c.w = in ? -expm1(-x) * exp(-excl) : 0.0;
+  c.t_next = exp(-xin);
+  return c;
+}
+
+// g_w[k] of the chunk's samples from the ray's totals (tw, twm) and the carried exclusive prefixes of w and w m
+__device__ __forceinline__ double dist_g_w(const dist_sample64& c, double g, double tw, double twm, int lane, double& carry_w,
+                                           double& carry_wm) {
+  const double wm = c.w * c.m;
+  const double ew = dist_excl(c.w, lane, carry_w);
+  const double ewm = dist_excl(wm, lane, carry_wm);
+  return g * (2.0 * (c.m * (ew - (tw - ew - c.w)) - (ewm - (twm - ewm - wm))) + (2.0 / 3.0) * c.w * c.d);
+}
+
+// sum of v over the lanes above this one, added from lane 63 downwards
+__device__ __forceinline__ double wave_suffix_excl(double v, int lane) {
+  const double incl = wave_scan_incl(__shfl(v, 63 - lane, 64), lane);  // lane p: the lanes 63 - p .. 63
+  const double sfx = __shfl(incl, 63 - lane, 64);                        // this lane .. 63
+  const double above = __shfl_down(sfx, 1, 64);
+  return lane < 63 ? above : 0.0;
+}
+
+__global__ __launch_bounds__(256) void rsn_distortion_bwd_kernel(int n_rays, const int* n_dev, int S, const float* spacing_bins,
+                                                                 const float* euclid_bins, const float* sigma,
+                                                                 const float* g_loss_ray, float* g_sigma, int accumulate) {
+  const int R = dyn_count(n_rays, n_dev);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int ray = blockIdx.x * 4 + wid; ray < R; ray += gridDim.x * 4) {
+    const long long sbase = (long long)ray * S;
+    const float* sb = spacing_bins + (long long)ray * (S + 1);
+    const float* eb = euclid_bins + (long long)ray * (S + 1);
+    const float* sg = sigma + sbase;
+    const double g = (double)g_loss_ray[ray];
+    // walk 1: totals of w and w m
+    double tw = 0.0, twm = 0.0, carry_x = 0.0;
+    for (int base = 0; base < S; base += 64) {
+      const dist_sample64 c = dist_derive(sb, eb, sg, base + lane, base + lane < S, lane, carry_x);
+      tw += c.w;
+      twm += c.w * c.m;
+    }
+    tw = wave_sum_f64(tw);
+    twm = wave_sum_f64(twm);
+    // walk 2: every chunk's total of g_w w, chunk q in lane q; then, per lane, the total of the chunks behind its own
+    double chunk_total = 0.0, carry_w = 0.0, carry_wm = 0.0;
+    carry_x = 0.0;
+    for (int base = 0; base < S; base += 64) {
+      const dist_sample64 c = dist_derive(sb, eb, sg, base + lane, base + lane < S, lane, carry_x);
+      const double t = wave_sum_f64(dist_g_w(c, g, tw, twm, lane, carry_w, carry_wm) * c.w);
+      if (lane == (base >> 6)) chunk_total = t;
+    }
+    const double later = wave_suffix_excl(chunk_total, lane);
+    // walk 3: the gradient
+    carry_x = carry_w = carry_wm = 0.0;
+    for (int base = 0; base < S; base += 64) {
+      const int i = base + lane;
+      const bool in = i < S;
+      const dist_sample64 c = dist_derive(sb, eb, sg, i, in, lane, carry_x);
+      const double gw = dist_g_w(c, g, tw, twm, lane, carry_w, carry_wm);
+      const double suffix = wave_suffix_excl(gw * c.w, lane) + __shfl(later, base >> 6, 64);  // sum_{i>k} g_w[i] w_i
+      const float val = (float)(c.delta * (gw * c.t_next - suffix));
+      if (in) g_sigma[sbase + i] = accumulate ? g_sigma[sbase + i] + val : val;
+    }
+  }
+}
+
+extern "C" int rsn_distortion_backward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* spacing_bins,
+                                       const float* euclid_bins, const float* sigma, const float* g_loss_ray, float* g_sigma,
+                                       int32_t accumulate, void* stream) {
+  RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
+  RSN_REQUIRE(n_samples <= DIST_MAX_S, RSN_ERR_UNSUPPORTED, "n_samples=%d > %d", n_samples, DIST_MAX_S);
+  if (n_rays == 0) return RSN_OK;
+  RSN_REQUIRE(spacing_bins && euclid_bins && sigma && g_loss_ray && g_sigma, RSN_ERR_INVALID_ARGUMENT,
+              "spacing_bins/euclid_bins/sigma/g_loss_ray/g_sigma is NULL");
+  int blocks = (n_rays + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(rsn_distortion_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_rays, n_dev, n_samples,
+                     spacing_bins, euclid_bins, sigma, g_loss_ray, g_sigma, accumulate != 0 ? 1 : 0);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
 // column sums (bias gradients): each workgroup owns a chunk of rows, thread t owns columns t, t+256, ...
 __global__ __launch_bounds__(256) void rsn_colsum_kernel(long long n_rows, int n_cols, int ld, const float* x,
                                                          float* out, long long rows_per_block) {

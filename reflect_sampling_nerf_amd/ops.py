@@ -133,6 +133,24 @@ def composite(n_rays: int, n_dev: Optional[Tensor], n_samples: int, background: 
     return out
 
 
+def distortion_forward(n_rays: int, n_dev: Optional[Tensor], n_samples: int, spacing_bins: Tensor, weights: Tensor) -> Tensor:
+    """-> loss_ray [R]: the distortion loss of every ray's weights on its spacing bins, unscaled (rsn_distortion_forward).
+    Rows at and past *n_dev hold zeros."""
+    lib = _abi.load_library()
+    out = (torch.empty if n_dev is None else torch.zeros)(n_rays, device=weights.device, dtype=torch.float32)
+    check(lib.rsn_distortion_forward(n_rays, ptr(n_dev), n_samples, ptr(spacing_bins), ptr(weights), ptr(out), _stream()))
+    return out
+
+
+def distortion_backward(n_rays: int, n_dev: Optional[Tensor], n_samples: int, spacing_bins: Tensor, euclid_bins: Tensor,
+                        sigma: Tensor, g_loss_ray: Tensor, g_sigma: Tensor, accumulate: bool = True) -> None:
+    """g_sigma [R,S] += (accumulate) or = the gradient of sum_r g_loss_ray[r] L_ray w.r.t. sigma (rsn_distortion_backward, which
+    re-derives the level's weights from sigma and the euclidean bins in fp64)."""
+    lib = _abi.load_library()
+    check(lib.rsn_distortion_backward(n_rays, ptr(n_dev), n_samples, ptr(spacing_bins), ptr(euclid_bins), ptr(sigma),
+                                      ptr(g_loss_ray), ptr(g_sigma), 1 if accumulate else 0, _stream()))
+
+
 def reflect_setup(origins: Tensor, directions: Tensor, accumulation: Tensor, depth: Tensor, normals: Tensor,
                   roughness: Tensor, reflect_far: float) -> Dict[str, Tensor]:
     lib = _abi.load_library()

@@ -169,7 +169,8 @@ def apply_loss_warmup(model, step: int) -> None:
         c["orientation_loss_fine"] = 1e-1
 
 
-_MEAN_TERMS = ("loss_mid_coarse", "loss_mid_fine", "loss_reflect_mid_coarse", "loss_reflect_mid_fine")
+_MEAN_TERMS = ("loss_mid_coarse", "loss_mid_fine", "loss_reflect_mid_coarse", "loss_reflect_mid_fine",
+               "distortion_loss_coarse", "distortion_loss_fine")  # the opt-in distortion terms are means over the rays too
 
 
 def train_step(model, ray_bundle, batch, optimizer, reducer: Optional[FlatGradAllReduce], step: int,

@@ -141,7 +141,7 @@ class ReflectSamplingNeRFModel(Model):
         """Training mode: one autograd node (train_graph.GetOutputsTrain) over the HIP forward/backward kernels.
         `jitter` optionally injects the samplers' uniform draws and `bins` whole sampler outputs
         ({"fine_spacing", "fine_euclid", ...}); tests share them with the oracle / the reference's logged values."""
-        from .train_graph import DIFF_KEYS, FUSED_KEYS, GetOutputsTrain
+        from .train_graph import DIFF_KEYS, DIST_KEYS, FUSED_KEYS, GetOutputsTrain, distortion_levels
 
         R = ray_bundle.origins.shape[0]
         o = ops._f32c(ray_bundle.origins.reshape(R, 3))
@@ -158,6 +158,9 @@ class ReflectSamplingNeRFModel(Model):
         outputs.lazy = aux.lazy
         # not keys of the reference's dict: the normal losses of get_loss_dict, reduced per ray by the compositing kernel
         outputs.fused = dict(zip(FUSED_KEYS, outs[len(DIFF_KEYS):]))
+        # opt-in: the per-ray distortion loss of the levels whose coefficient is set (none by default: FUSED_KEYS only)
+        on = [k for k, lvl in zip(DIST_KEYS, distortion_levels(self)) if lvl]
+        outputs.fused.update(zip(on, outs[len(DIFF_KEYS) + len(FUSED_KEYS):]))
         return outputs
 
     @property
@@ -421,16 +424,22 @@ class ReflectSamplingNeRFModel(Model):
     # ------------------------------------------------------------------ loss (model.py:346-430; "next" row §8(f).1)
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> Dict[str, Tensor]:
         """model.py:346-430: four MSE terms against the (white-blended) image, two predicted-normal and two
-        orientation terms, scaled by config.loss_coefficients.  One fused HIP pass (train_ops.FusedLoss)."""
-        from .train_ops import fused_loss_dict, fused_ray_loss_dict
+        orientation terms, scaled by config.loss_coefficients.  One fused HIP pass (train_ops.FusedLoss).
+        Not in the reference, opt-in: distortion_loss_coarse / distortion_loss_fine (mip-NeRF 360 eq. 15) for the levels whose
+        coefficient is set and not 0, from the training graph's per-ray terms (train_ops.distortion_loss_dict)."""
+        from .train_ops import distortion_loss_dict, fused_loss_dict, fused_ray_loss_dict
 
         image = batch["image"].to(self.device)
         if image.shape[-1] == 4:  # RGBRenderer.blend_background with the white background colour
             image = image[..., :3] * image[..., 3:] + (1.0 - image[..., 3:])
         fused = getattr(outputs, "fused", None)
+        extra = distortion_loss_dict(fused, self.config.loss_coefficients)  # {} by default; raises when set without its fused term
         if fused is not None:  # outputs of this model's own training graph: the per-sample terms are already per-ray sums
-            return fused_ray_loss_dict(outputs, fused, image, self.config.loss_coefficients)
-        return fused_loss_dict(outputs, image, self.config.loss_coefficients)
+            losses = fused_ray_loss_dict(outputs, fused, image, self.config.loss_coefficients)
+        else:
+            losses = fused_loss_dict(outputs, image, self.config.loss_coefficients)
+        losses.update(extra)
+        return losses
 
     # ------------------------------------------------------------------ eval image (model.py:432-482; "next" row §8(f).4)
     def get_image_metrics_and_images(self, outputs: Dict[str, Tensor], batch: Dict[str, Tensor]):

@@ -445,11 +445,31 @@ DIFF_KEYS = ("mid_rgb_coarse", "mid_rgb_fine", "mid_reflect_coarse", "mid_reflec
 # differentiable per-ray reductions of the normal losses, handed to get_loss_dict beside the reference's keys
 # (LazyOutputs.fused): sum_s w |n - n_pred|^2 and sum_s w max(0, n.d)^2 of the coarse and the fine level
 FUSED_KEYS = ("pn_loss_ray_coarse", "pn_loss_ray_fine", "ori_loss_ray_coarse", "ori_loss_ray_fine")
+# Opt-in: the distortion loss of mip-NeRF 360 (eq. 15) per ray, of the coarse / the fine level's weights on the samplers' spacing bins
+# (rsn_distortion_forward).  A level whose coefficient (DIST_COEF_KEYS, in config.loss_coefficients) is absent or 0 is off: it runs no
+# launch and has no output; the outputs of the levels that are on follow FUSED_KEYS, in this order.  The reflect levels' weights are
+# detached (model.py:297,323): they never get the term.
+DIST_KEYS = ("dist_loss_ray_coarse", "dist_loss_ray_fine")
+DIST_COEF_KEYS = ("distortion_loss_coarse", "distortion_loss_fine")
+
+
+def distortion_levels(model):
+    """(coarse on, fine on): which primary levels the distortion loss regularises."""
+    coef = model.config.loss_coefficients
+    return tuple(float(coef.get(k, 0.0)) != 0.0 for k in DIST_COEF_KEYS)
+
+
+def _distortion_backward(level, sb, eb, g_loss_ray, g_sigma):
+    """Adds the distortion term's gradient to the g_sigma rsn_composite_backward wrote (all --mma modes consume that fp32 tensor)."""
+    n, S = g_sigma.shape
+    ops.timed("distortion_backward", {"points": n * S}, lambda: ops.distortion_backward(
+        n, None, S, sb, eb, level["sigma"], ops._f32c(g_loss_ray), g_sigma, accumulate=True))
 
 
 class GetOutputsTrain(torch.autograd.Function):
     """inputs: (model, ray tensors, jitter dict or None, bins dict or None, *field parameters) -> tuple of DIFF_KEYS
-    tensors.  The non-differentiable outputs are left on `model._train_aux` by forward.
+    tensors, then the FUSED_KEYS ones, then the DIST_KEYS ones of the levels that are on (distortion_levels: none by default).
+    The non-differentiable outputs are left on `model._train_aux` by forward.
     jitter: the samplers' uniform draws; bins: {"<level>_spacing", "<level>_euclid"} [n,S+1] replacing the sampler
     output of a level (the samplers' outputs are constants of the graph: PDFSampler detaches, model.py:182,317) --
     tests use both to put this pipeline and the reference / the oracle on identical sample positions."""
@@ -465,6 +485,7 @@ class GetOutputsTrain(torch.autograd.Function):
         jitter = jitter or {}
         bins = bins or {}
         fold = fold_enabled(model)  # exact fp32: the kernels with the bottleneck folded into mlp_mid (no bottleneck rows)
+        dist_c, dist_f = distortion_levels(model)
 
         def pad_rows(t, n):
             """[m, ...] -> [n, ...] (m <= n), zero rows behind: device-counted launches ignore them"""
@@ -507,11 +528,15 @@ class GetOutputsTrain(torch.autograd.Function):
                                                                            jit("coarse", R, Sc)))
         lc = fld.evaluate_frustums_train(o, d, pa, eb_c, want_normals=True, fold=fold)
         cc = ops.composite(R, None, Sc, 1, CLIP, lc["sigma"], eb_c, lc["color"], level=lc, ray_losses=True)
+        dl_c = ops.timed("distortion_forward", {"points": R * Sc}, lambda: ops.distortion_forward(
+            R, None, Sc, sb_c, cc["weights"])) if dist_c else None
         sb_f, eb_f = level_bins("fine", R, Sf, lambda: ops.sample_pdf(
             R, None, Sc, Sf, uni.spacing, uni.tan, model.sampler_pdf.histogram_padding, nears, fars, cc["weights"], sb_c,
             jit("fine", R, Sf)))
         lf = fld.evaluate_frustums_train(o, d, pa, eb_f, want_normals=True, fold=fold)
         cf = ops.composite(R, None, Sf, 1, CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True, ray_losses=True)
+        dl_f = ops.timed("distortion_forward", {"points": R * Sf}, lambda: ops.distortion_forward(
+            R, None, Sf, sb_f, cf["weights"])) if dist_f else None
         rs = ops.reflect_setup(o, d, cf["accumulation"], cf["depth"], cf["normals"], cf["roughness"], float(model.far))
         # C.-F. the reflect branch runs on the M <= R rays behind the mask.  Like the eval path (model.get_outputs) every
         # launch is sized for R rays and takes the count from device memory (rs["n_masked"]).  The host never reads M: the
@@ -565,6 +590,10 @@ class GetOutputsTrain(torch.autograd.Function):
         st = dict(R=R, Rb=Rb, fold=fold, eb_c=eb_c, eb_f=eb_f, lc=lc, lf=lf, cc=cc, cf=cf, rs=rs, rays=(o, d, pa),
                   rays2=(o2, d2, pa2), sq=sq, bg=bg, inf_saved=inf_saved, eb_rc=eb_rc, eb_rf=eb_rf, lrc=lrc, lrf=lrf,
                   crc=crc, crf=crf)
+        if dist_c:
+            st["sb_c"] = sb_c
+        if dist_f:
+            st["sb_f"] = sb_f
         if getattr(model, "_keep_train_state", False):  # test hook: the sample positions this pass evaluated
             if M is None:
                 M = int(nm.item())
@@ -583,12 +612,15 @@ class GetOutputsTrain(torch.autograd.Function):
         outs = (cc["rgb"], cf["rgb"], rs["reflect_coarse"], rs["reflect_fine"], lc["pred_normals"], lf["pred_normals"],
                 lc["n_dot_d"].unsqueeze(-1), lf["n_dot_d"].unsqueeze(-1), cf["roughness"].unsqueeze(-1),
                 cc["pn_loss_ray"], cf["pn_loss_ray"], cc["ori_loss_ray"], cf["ori_loss_ray"])
-        return outs
+        ctx.dist = (dist_c, dist_f)
+        return outs + tuple(t for t in (dl_c, dl_f) if t is not None)
 
     @staticmethod
     def backward(ctx, g_rgb_c, g_rgb_f, g_refl_c, g_refl_f, g_pn_c, g_pn_f, g_ndd_c, g_ndd_f, g_rough,
-                 g_pnr_c=None, g_pnr_f=None, g_orr_c=None, g_orr_f=None):
+                 g_pnr_c=None, g_pnr_f=None, g_orr_c=None, g_orr_f=None, *g_dist):
         st, model = ctx.st, ctx.model
+        g_dist = iter(g_dist)  # one per level that is on, coarse first (forward)
+        g_dl_c, g_dl_f = (next(g_dist) if on else None for on in ctx.dist)
         fld = model.field
         lib = _abi.load_library()
         R = st["R"]
@@ -653,6 +685,8 @@ class GetOutputsTrain(torch.autograd.Function):
                                                ops._stream()))
         cb = _composite_backward(R, Sf, 1, CLIP, 0, lf, st["eb_f"], cf["weights"], g_rgb_f, g_rough=g_rough_ray,
                                  rough_samples=lf["roughness"], g_acc=g_acc)
+        if g_dl_f is not None:
+            _distortion_backward(lf, st["sb_f"], st["eb_f"], g_dl_f, cb["g_sigma"])
         gin = {"sigma": cb["g_sigma"], "color": cb["g_color"], "roughness": cb["g_rough"],
                "pred_normals": ops._f32c(g_pn_f) if g_pn_f is not None else None,
                "n_dot_d": ops._f32c(g_ndd_f.reshape(R, Sf)) if g_ndd_f is not None else None,
@@ -663,6 +697,8 @@ class GetOutputsTrain(torch.autograd.Function):
         # coarse primary level
         lc, cc = st["lc"], st["cc"]
         cb = _composite_backward(R, Sc, 1, CLIP, 0, lc, st["eb_c"], cc["weights"], g_rgb_c)
+        if g_dl_c is not None:
+            _distortion_backward(lc, st["sb_c"], st["eb_c"], g_dl_c, cb["g_sigma"])
         gin = {"sigma": cb["g_sigma"], "color": cb["g_color"],
                "pred_normals": ops._f32c(g_pn_c) if g_pn_c is not None else None,
                "n_dot_d": ops._f32c(g_ndd_c.reshape(R, Sc)) if g_ndd_c is not None else None,

@@ -148,6 +148,27 @@ def fused_ray_loss_dict(outputs: Dict[str, Tensor], fused: Dict[str, Tensor], im
     return dict(zip(LOSS_TERMS, scaled.unbind(0)))
 
 
+# loss-coefficient key -> the training graph's per-ray output it scales (train_graph.DIST_COEF_KEYS / DIST_KEYS)
+DISTORTION_TERMS = (("distortion_loss_coarse", "dist_loss_ray_coarse"), ("distortion_loss_fine", "dist_loss_ray_fine"))
+
+
+def distortion_loss_dict(fused: Optional[Dict[str, Tensor]], coefficients: Dict[str, float]) -> Dict[str, Tensor]:
+    """The opt-in distortion terms of get_loss_dict: coef * mean over the rays of the level's per-ray loss (nerfstudio's
+    distortion_loss takes the same mean), for every level whose coefficient is present and not 0.  Device tensors: the mean is one
+    torch reduction over R floats, nothing is read back.  A coefficient that is set on outputs without the level's fused term
+    (outputs that did not come from this package's training graph) is an error: the term is never dropped silently."""
+    out = {}
+    for key, ray_key in DISTORTION_TERMS:
+        coef = float(coefficients.get(key, 0.0))
+        if coef == 0.0:
+            continue
+        if fused is None or ray_key not in fused:
+            raise _abi.RsnError(f"loss_coefficients[{key!r}] = {coef:g}, but the outputs carry no fused {ray_key!r}: the distortion loss "
+                                "exists only on the outputs of this model's own training graph (model.train(); get_outputs)")
+        out[key] = coef * fused[ray_key].mean()
+    return out
+
+
 def exponential_decay_lr(step: int, lr_init: float = 1e-3, lr_final: float = 1e-4, max_steps: int = 50000) -> float:
     """nerfstudio ExponentialDecayScheduler without warm-up (reference config.py:52): log-linear interpolation."""
     t = min(max(step / max_steps, 0.0), 1.0)

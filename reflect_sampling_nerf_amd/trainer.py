@@ -1,6 +1,6 @@
 """Standalone training and evaluation on Blender-format scenes, without nerfstudio.
 
-    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L]
+    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L] [--distortion-loss X [--distortion-loss-coarse Y]]
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
@@ -40,6 +40,14 @@ for every metric) are the means over the views at one scale, the plain keys the 
 be divisible by 2^(L-1), and `eval` needs the smallest scale to be at least 11 x 11 (the SSIM window).  The setting is recorded in the
 checkpoint when it is above 1 and comes back with --resume; the default, 1, is the single-scale run with the launches, bytes and
 checkpoint keys it always had.
+
+`train --distortion-loss X` adds the distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15; nerfstudio's distortion_loss) of
+the fine level's compositing weights to the objective, X times its mean over the batch's rays, and `--distortion-loss-coarse Y` the
+coarse level's: the term pulls a ray's weights together into one compact interval, on the samplers' normalised spacing bins
+(include/rsn.h: rsn_distortion_forward / _backward).  mip-NeRF 360 uses 0.01 and nerfacto 0.002; neither value has been measured on
+this method.  The reflect levels never get the term (their weights are detached).  Both are off by default, and the default run has
+the launches, bytes and checkpoint keys it always had; a coefficient that is set is recorded in the checkpoint and comes back with
+--resume.
 
 `export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
 the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
@@ -175,10 +183,16 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     tr.add_argument("--multiscale", type=int, default=dflt["multiscale"], metavar="L",
                     help="draw the training rays from L scales of every image, 1, 1/2, ... 1/2^(L-1), each with probability 1/L "
                          "(1 to 5; default 1: full resolution only); the image size must be divisible by 2^(L-1)")
+    tr.add_argument("--distortion-loss", type=float, default=None, metavar="X",
+                    help="add X times the distortion loss of mip-NeRF 360 (eq. 15) of the fine level's weights to the objective: it pulls "
+                         "each ray's weights into one compact interval.  mip-NeRF 360 uses 0.01 and nerfacto 0.002; neither value has "
+                         "been measured on this method (default: off)")
+    tr.add_argument("--distortion-loss-coarse", type=float, default=None, metavar="Y",
+                    help="the same term on the coarse level's weights, times Y (default: off)")
     tr.add_argument("--resume", default=None, metavar="PATH",
                     help="continue from this step-*.ckpt, or from the newest one in this run directory; --steps stays the total, and "
-                         "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite / --multiscale come from the "
-                         "checkpoint unless given")
+                         "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite / --multiscale / "
+                         "--distortion-loss / --distortion-loss-coarse come from the checkpoint unless given")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
     ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json")
     ev.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
@@ -495,12 +509,14 @@ def resolve_checkpoint(path: str) -> str:
 
 
 def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, max_grad_norm: Optional[float] = None,
-                   skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None) -> dict:
+                   skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
+                   distortion_loss_coarse: Optional[float] = None) -> dict:
     """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
     bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
     seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one.
     max_grad_norm / skip_nonfinite (the optimiser's guard) are recorded only when set: an unguarded run's entry has the keys it
-    always had.  Likewise multiscale (the number of pyramid levels the rays are drawn from): only when above 1."""
+    always had.  Likewise multiscale (the number of pyramid levels the rays are drawn from): only when above 1, and distortion_loss /
+    distortion_loss_coarse (the coefficients of the opt-in distortion term): only when set and not 0."""
     dev = torch.device(device)
     state = {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
              "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
@@ -511,6 +527,9 @@ def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, 
         state["skip_nonfinite"] = True
     if multiscale is not None and int(multiscale) > 1:
         state["multiscale"] = int(multiscale)
+    for key, coef in (("distortion_loss", distortion_loss), ("distortion_loss_coarse", distortion_loss_coarse)):
+        if coef is not None and float(coef) != 0.0:
+            state[key] = float(coef)
     return state
 
 
@@ -571,9 +590,9 @@ def load_checkpoint(path: str, model_config=None, device="cuda:0"):
 
 # ------------------------------------------------------------------------------------------------ train
 def _resolve_run_settings(given: dict, recorded: Optional[dict]):
-    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale: the caller's value if given, else the
-    checkpoint's, else the fresh-run default (deterministic: None = the model's own default; the two guard settings: None = off;
-    multiscale: 1, which a checkpoint does not record).
+    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale / distortion_loss / distortion_loss_coarse:
+    the caller's value if given, else the checkpoint's, else the fresh-run default (deterministic: None = the model's own default; the
+    two guard settings and the two distortion coefficients: None = off; multiscale: 1, which a checkpoint does not record).
     -> (settings, one line per given value that departs from the checkpoint's)."""
     out, notes = {}, []
     for k, v in given.items():
@@ -601,7 +620,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
           log_every: int = 100, seed: Optional[int] = None, device="cuda:0", model_config=None,
           log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None, resume: Optional[str] = None,
           on_step: Optional[Callable[[int, torch.Tensor], None]] = None, max_grad_norm: Optional[float] = None,
-          skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None) -> str:
+          skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
+          distortion_loss_coarse: Optional[float] = None) -> str:
     """Train on `scene` (a data.BlenderScene) up to iteration `steps` (the total, nerfstudio's max_num_iterations); returns the path
     of the last checkpoint.  Checkpoints at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer
     does the same).  The loss is read back only every log_every steps: the iterations in between never wait for the GPU.
@@ -618,6 +638,12 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     multiscale: the number of pyramid levels the rays are drawn from (RayDataManager's levels; None: the checkpoint's when resuming,
     else 1).  A batch stays a pure function of (seed, rank, step) and the pyramid one of the images, so the paragraph on the restored
     state below holds for a multi-scale run as it stands.
+
+    distortion_loss / distortion_loss_coarse: the coefficient of the distortion loss (mip-NeRF 360 eq. 15) of the fine / the coarse
+    level's weights (None: the checkpoint's when resuming, else off; 0 is off too).  A set coefficient goes into the model's
+    config.loss_coefficients as "distortion_loss_fine" / "distortion_loss_coarse" (train_graph.DIST_COEF_KEYS), which switches the
+    level's two launches on; mip-NeRF 360 uses 0.01, nerfacto 0.002, neither measured on this method.  The term reads no state beyond
+    the step's own weights and bins, so the paragraph on the restored state below holds with it as it stands.
 
     resume: a step-*.ckpt or a run directory (its latest).  A checkpoint of step k continues at k + 1 with the same checkpoint names
     and save_every rule; k >= steps - 1 is a ValueError.  Model (strict, as load_checkpoint) and FusedRAdam state come from the file.
@@ -641,7 +667,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     if steps < 1:
         raise ValueError(f"steps must be >= 1, got {steps}")
     given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic, "max_grad_norm": max_grad_norm,
-             "skip_nonfinite": skip_nonfinite, "multiscale": multiscale}
+             "skip_nonfinite": skip_nonfinite, "multiscale": multiscale, "distortion_loss": distortion_loss,
+             "distortion_loss_coarse": distortion_loss_coarse}
     first, model, ckpt, recorded = 0, None, None, None
     if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
         resume = resolve_checkpoint(resume)
@@ -656,6 +683,10 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     cfg, notes = _resolve_run_settings(given, recorded)
     rays, mma, seed, deterministic = cfg["rays"], cfg["mma"], cfg["seed"], cfg["deterministic"]
     max_grad_norm, skip_nonfinite, multiscale = cfg["max_grad_norm"], bool(cfg["skip_nonfinite"]), int(cfg["multiscale"])
+    distortion = {"distortion_loss_fine": cfg["distortion_loss"], "distortion_loss_coarse": cfg["distortion_loss_coarse"]}
+    for key, coef in distortion.items():
+        if coef is not None and not math.isfinite(float(coef)):
+            raise ValueError(f"{key} must be finite, got {coef!r}")
     if mma not in MMA_CHOICES:
         raise ValueError(f"mma must be one of {MMA_CHOICES}, got {mma!r}")
     pyramid_layout(scene.num_images, scene.height, scene.width, multiscale)  # a size the levels do not divide ends here, on the host
@@ -666,6 +697,9 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     model.field.set_mma_mode(mma)
     if deterministic is not None:
         model.set_deterministic(deterministic)
+    on = {key: float(coef) for key, coef in distortion.items() if coef is not None and float(coef) != 0.0}
+    if on:  # (off: the dictionary stays as it is, without the keys.)  A copy: a model_config the caller shares between runs stays as it was
+        model.config.loss_coefficients = dict(model.config.loss_coefficients, **on)
     dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed, levels=multiscale)
     params = model.get_param_groups()["fields"]
     name_of = {id(p): n for n, p in model.named_parameters()}
@@ -678,6 +712,9 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         settings += " skip_nonfinite True"
     if multiscale > 1:
         settings += f" multiscale {multiscale}"
+    for key, coef in distortion.items():
+        if coef is not None and float(coef) != 0.0:
+            settings += f" {key} {float(coef):g}"
     if resume is None:
         if log is not None:
             log(f"train: {settings}")
@@ -712,7 +749,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
             log(line)
         if (save_every and step > 0 and step % save_every == 0) or step == steps - 1:
             last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
-                                   make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite, multiscale))
+                                   make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite, multiscale,
+                                                  distortion["distortion_loss_fine"], distortion["distortion_loss_coarse"]))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -845,7 +883,8 @@ def main(argv=None) -> int:
                 ap.error(f"train: --multiscale {args.multiscale}: {e}")
         train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
               log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume,
-              max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None, multiscale=given.multiscale)
+              max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None, multiscale=given.multiscale,
+              distortion_loss=args.distortion_loss, distortion_loss_coarse=args.distortion_loss_coarse)
         return 0
     if args.command == "export-mesh":
         from . import mesh
