@@ -1083,6 +1083,57 @@ int rsn_pointcloud_select(int32_t n_views, const float* c2w, int32_t height, int
 int rsn_texture_points(int32_t n_vertices, const float* positions, int32_t n_triangles, const int32_t* triangles, int32_t texels,
                        int32_t squares_per_row, int32_t* face, float* point, float* footprint, void* stream);
 
+
+/* ---- geometry metrics: the composited predicted normal of an eval view against a ground-truth normal map, and the accumulation
+ * against the ground-truth alpha (additive to ABI 18: no existing call changes).  The numbers of the Ref-NeRF results table: the
+ * alpha-weighted mean angular error in degrees (multinerf's compute_normal_mae), here with its error map, on the device.
+ *
+ * P = n_pixels.  normals fp32 [P,3] is the predicted row p of every pixel; it is NOT required to be of unit length (the angle does
+ * not depend on the lengths, so nothing is normalised and the ground truth decodes exactly).  gt_normals uint8 [P,3] holds the
+ * bytes u_c of a normal map, encoding n_c * 0.5 + 0.5; gt_rgba uint8 [P,4], of which only the alpha byte a (index 3) is read;
+ * accumulation fp32 [P] or NULL; rotation fp32 [9], a row-major 3 x 3 matrix R on the device, or NULL; error_map fp32 [P] or NULL.
+ * Per pixel, every step one correctly rounded fp32 operation unless said otherwise, none contracted into a fused multiply-add:
+ *   1. v_c = 2*u_c - 255 in integers (an odd number in [-255, 255]), g_c = (float)v_c: exact.
+ *   2. valid = a > 0 and max_c |v_c| > 1.  The bytes 127 and 128 in all three channels mean "no normal" (how a background is
+ *      written: both decode to within half a step of zero); the test is on the integers, before any rotation.
+ *   3. with rotation: g = R g, g'_r = (R[3r]*g_0 + R[3r+1]*g_1) + R[3r+2]*g_2 for r = 0, 1, 2 (all three from the unrotated g).
+ *   4. c = p x g: c_0 = p_1*g_2 - p_2*g_1, c_1 = p_2*g_0 - p_0*g_2, c_2 = p_0*g_1 - p_1*g_0;
+ *      s = sqrtf((c_0*c_0 + c_1*c_1) + c_2*c_2);  d = (p_0*g_0 + p_1*g_1) + p_2*g_2.
+ *   5. theta = atan2f(s, d), in [0, pi]; but theta = (float)(pi/2) when s == 0 and d == 0, which is what a zero prediction gives
+ *      (multinerf normalises with an epsilon and gets arccos(0) there).  deg = theta * (float)(180/pi).
+ *      atan2 of the cross and the dot product is the angle multinerf takes as arccos of the normalised dot product; it is used
+ *      because it is well conditioned at 0 and 180 degrees, where fp32 arccos loses half its digits -- and a good model sits at 0.
+ *      A prediction so small or so large that the squares of step 4 leave the fp32 range is outside the recipe.
+ *   6. error_map[i] = valid ? deg : 0.
+ * Sums, in fp64, in an order fixed by (P, pixel index) alone (below):
+ *   S1 = sum over the valid pixels of (double)a * (double)deg        S2 = sum over the valid pixels of a
+ *   S3 = sum over ALL pixels of |(double)accumulation - (double)a / 255.0|   (fp64 steps)      n = the number of valid pixels
+ * out fp32 [4] on the device:
+ *   out[0] = (float)(S1 / S2)   the alpha-weighted mean angular error in degrees; NaN when S2 == 0 (no valid pixel)
+ *   out[1] = (float)(S2 / 255.0)   the weight behind it: the valid pixels' summed alpha
+ *   out[2] = (float)(S3 / P)   the mean absolute alpha error; 0 when accumulation is NULL
+ *   out[3] = (float)n   exact: P <= 2^24
+ * A non-finite predicted row of a valid pixel gives that pixel a non-finite deg and so a non-finite out[0]: it is not masked.  A
+ * non-finite accumulation makes out[2] non-finite.
+ *
+ * Launches: one lane per pixel in a grid-stride loop, G = min(ceil(P / 256), RSN_NORMAL_ERROR_MAX_GROUPS) workgroups of 256 lanes,
+ * so the first P at which a lane takes a second pixel is 256*RSN_NORMAL_ERROR_MAX_GROUPS + 1.  A lane adds its pixels in ascending
+ * order; the 64 lanes of a wave are added by a butterfly (offsets 32, 16, ... 1), the four waves of a workgroup in order, and the
+ * workgroup stores one record of four doubles (S1, S2, S3, n) at workspace[32 * group].  A second launch of one workgroup adds the
+ * G records the same way (lane i holds record i) and writes out.  No atomics: two runs give the same bits of out and error_map,
+ * and out does not depend on whether error_map is given.  workspace: device memory of at least rsn_normal_error_workspace_bytes
+ * bytes (32 G; 0 for a P outside the limits), 8-byte aligned, contents irrelevant.  No allocation, no synchronisation, no
+ * device-to-host read.
+ * RSN_ERR_INVALID_ARGUMENT before any launch, with the reason in rsn_last_error(): n_pixels <= 0 or n_pixels > 2^24
+ * (RSN_NORMAL_ERROR_MAX_PIXELS); a NULL normals, gt_normals, gt_rgba, workspace or out; a workspace that is not 8-byte aligned.
+ * RSN_ERR_WORKSPACE for a workspace_bytes below the size needed. */
+#define RSN_NORMAL_ERROR_MAX_GROUPS 256
+#define RSN_NORMAL_ERROR_MAX_PIXELS (1 << 24)
+size_t rsn_normal_error_workspace_bytes(int32_t n_pixels);
+int rsn_normal_error(int32_t n_pixels, const float* normals, const float* accumulation, const uint8_t* gt_normals,
+                     const uint8_t* gt_rgba, const float* rotation, float* error_map, void* workspace, size_t workspace_bytes,
+                     float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

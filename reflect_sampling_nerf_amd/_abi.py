@@ -17,6 +17,8 @@ RSN_SPACING_RECIPROCAL = 1
 RSN_MMA_F32, RSN_MMA_BF16X6, RSN_MMA_BF16X3, RSN_MMA_BF16 = 0, 1, 2, 3
 RSN_MMA_F32_FOLDED = 4  # exact fp32 training with field_output_bottleneck folded into mlp_mid (a descriptor value, not a Field mode)
 RSN_VIS_RGB, RSN_VIS_UNIT, RSN_VIS_GRAY, RSN_VIS_LUT = 0, 1, 2, 3
+RSN_NORMAL_ERROR_MAX_GROUPS = 256  # workgroups of 256 lanes: rsn_normal_error takes a second trip of its loop from 65,537 pixels on
+RSN_NORMAL_ERROR_MAX_PIXELS = 1 << 24
 
 _fp = C.c_void_p  # device float*
 
@@ -258,6 +260,8 @@ _SIGNATURES = {
                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                         _fp, C.c_void_p]),
     "rsn_texture_points": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _fp, _fp, C.c_void_p]),
+    "rsn_normal_error_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "rsn_normal_error": (C.c_int, [C.c_int32, _fp, _fp, C.c_void_p, C.c_void_p, _fp, _fp, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -15,7 +15,7 @@ import json
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -27,7 +27,8 @@ from .nerfstudio_compat import RayBundle
 @dataclass
 class BlenderScene:
     """One split of a posed image set: images uint8 [N,H,W,4] RGBA (alpha 255 for RGB sources), c2w float32 [N,3,4],
-    one pinhole camera (fx, fy, cx, cy) shared by all images."""
+    one pinhole camera (fx, fy, cx, cy) shared by all images.  normals: None, or the ground-truth normal maps uint8 [N,H,W,3], the
+    bytes of the scene's normal images, encoding n * 0.5 + 0.5 (eval's geometry metrics read them; training never does)."""
 
     images: np.ndarray
     c2w: np.ndarray
@@ -35,6 +36,7 @@ class BlenderScene:
     fy: float
     cx: float
     cy: float
+    normals: Optional[np.ndarray] = None
 
     @property
     def num_images(self) -> int:
@@ -49,9 +51,10 @@ class BlenderScene:
         return int(self.images.shape[2])
 
     @classmethod
-    def from_arrays(cls, images, c2w, focal: float, cx=None, cy=None) -> "BlenderScene":
+    def from_arrays(cls, images, c2w, focal: float, cx=None, cy=None, normals=None) -> "BlenderScene":
         """images [N,H,W,3|4] (uint8, or float in [0, 1] rounded to uint8), c2w [N,3,4] or [N,4,4]; fx = fy = focal,
-        principal point at the image centre unless given."""
+        principal point at the image centre unless given.  normals: None, or [N,H,W,3] normal maps -- uint8 taken as is, float unit
+        vectors encoded as rint((n * 0.5 + 0.5) * 255) clipped to 0..255."""
         im = np.asarray(images.cpu() if isinstance(images, torch.Tensor) else images)
         if im.ndim != 4 or im.shape[-1] not in (3, 4):
             raise ValueError(f"images must be [N,H,W,3|4], got {im.shape}")
@@ -63,14 +66,27 @@ class BlenderScene:
         if pose.ndim != 3 or pose.shape[0] != im.shape[0] or pose.shape[1:] not in ((3, 4), (4, 4)):
             raise ValueError(f"c2w must be [N,3,4] or [N,4,4] with N = {im.shape[0]}, got {pose.shape}")
         H, W = im.shape[1:3]
+        nm = None
+        if normals is not None:
+            nm = np.asarray(normals.cpu() if isinstance(normals, torch.Tensor) else normals)
+            if nm.shape != im.shape[:3] + (3,):
+                raise ValueError(f"normals must be [N,H,W,3] = {im.shape[:3] + (3,)}, got {nm.shape}")
+            if nm.dtype != np.uint8:
+                nm = np.clip(np.rint((nm.astype(np.float64) * 0.5 + 0.5) * 255.0), 0, 255).astype(np.uint8)
+            nm = np.ascontiguousarray(nm)
         return cls(images=np.ascontiguousarray(im), c2w=np.ascontiguousarray(pose[:, :3, :4]), fx=float(focal),
-                   fy=float(focal), cx=float(W / 2.0 if cx is None else cx), cy=float(H / 2.0 if cy is None else cy))
+                   fy=float(focal), cx=float(W / 2.0 if cx is None else cx), cy=float(H / 2.0 if cy is None else cy), normals=nm)
 
 
-def load_blender_split(root: str, split: str, scale_factor: float = 1.0) -> BlenderScene:
+def load_blender_split(root: str, split: str, scale_factor: float = 1.0, normals: bool = False,
+                       normals_suffix: str = "_normal") -> BlenderScene:
     """nerfstudio 0.3 BlenderDataParser: transforms_{split}.json; image = frame["file_path"] without a leading "./" plus
     ".png"; c2w = transform_matrix[:3] with the translation times scale_factor; fx = fy = 0.5 W / tan(0.5 camera_angle_x),
-    cx = W / 2, cy = H / 2."""
+    cx = W / 2, cy = H / 2.
+
+    normals=True also reads every frame's normal map, file_path + normals_suffix + ".png" (multinerf's naming of the Shiny Blender
+    scenes: r_0.png beside r_0_normal.png), into scene.normals: its first three channels, an alpha channel of that file ignored.
+    FileNotFoundError for a frame without one, ValueError for one of another size than the frame's image."""
     from PIL import Image
 
     meta_path = os.path.join(root, f"transforms_{split}.json")
@@ -81,7 +97,7 @@ def load_blender_split(root: str, split: str, scale_factor: float = 1.0) -> Blen
     frames = meta.get("frames") or []
     if not frames:
         raise ValueError(f"{meta_path} lists no frames")
-    images, poses = [], []
+    images, poses, normal_maps = [], [], []
     for fr in frames:
         rel = fr["file_path"]
         if rel.startswith("./"):
@@ -94,6 +110,16 @@ def load_blender_split(root: str, split: str, scale_factor: float = 1.0) -> Blen
         if images and im.shape != images[0].shape:
             raise ValueError(f"{path}: image size {im.shape[1]} x {im.shape[0]} differs from the split's first image "
                              f"({images[0].shape[1]} x {images[0].shape[0]}); all images of a split must be equal in size")
+        if normals:
+            npath = os.path.join(root, rel + normals_suffix + ".png")
+            if not os.path.isfile(npath):
+                raise FileNotFoundError(f"{npath}: normal map of frame {len(images)} of {meta_path} not found")
+            with Image.open(npath) as img:
+                nm = np.asarray(img.convert("RGB") if img.mode not in ("RGB", "RGBA") else img, dtype=np.uint8)[..., :3]
+            if nm.shape[:2] != im.shape[:2]:
+                raise ValueError(f"{npath}: normal map of {nm.shape[1]} x {nm.shape[0]} pixels beside an image of "
+                                 f"{im.shape[1]} x {im.shape[0]}; a frame's normal map must have its image's size")
+            normal_maps.append(nm)
         images.append(im)
         poses.append(np.asarray(fr["transform_matrix"], dtype=np.float32)[:3, :4])
     im = np.stack(images)
@@ -101,7 +127,8 @@ def load_blender_split(root: str, split: str, scale_factor: float = 1.0) -> Blen
     c2w[:, :, 3] *= np.float32(scale_factor)
     H, W = im.shape[1:3]
     focal = 0.5 * W / math.tan(0.5 * float(meta["camera_angle_x"]))
-    return BlenderScene(images=im, c2w=c2w, fx=focal, fy=focal, cx=W / 2.0, cy=H / 2.0)
+    return BlenderScene(images=im, c2w=c2w, fx=focal, fy=focal, cx=W / 2.0, cy=H / 2.0,
+                        normals=np.ascontiguousarray(np.stack(normal_maps)) if normals else None)
 
 
 MAX_LEVELS = 5  # include/rsn.h RSN_PYRAMID_MAX_LEVELS: a 16 x 16 box keeps the integer sums of the blend below 2^24
@@ -146,6 +173,9 @@ class RayDataManager:
         self.rank = int(rank) & 0xFFFFFFFF
         self.images = torch.from_numpy(np.ascontiguousarray(scene.images)).to(self.device)
         self.c2w = torch.from_numpy(np.ascontiguousarray(scene.c2w, dtype=np.float32)).to(self.device)
+        self.normals = None  # uint8 [N,H,W,3]: level 0 only, the pyramid builds no normal levels
+        if scene.normals is not None:
+            self.normals = torch.from_numpy(np.ascontiguousarray(scene.normals)).to(self.device)
         self._lib = _abi.load_library()
         self.pyramid = None  # fp32 [pixels of the levels >= 1, 3]
         if self.levels > 1:
@@ -216,3 +246,12 @@ class RayDataManager:
         h, w = self.level_sizes[level]
         first = self.level_offsets[level] + i * h * w
         return self.pyramid[first:first + h * w].view(h, w, 3)
+
+    def normal_image(self, i: int) -> torch.Tensor:
+        """Ground-truth normal map of camera i: uint8 [H,W,3] on the device, the bytes of the scene's normal image (n * 0.5 + 0.5);
+        a view of the one upload, not a copy.  Level 0 only.  ValueError when the scene has no normal maps."""
+        if self.normals is None:
+            raise ValueError("the scene has no normal maps (load_blender_split(..., normals=True) or from_arrays(..., normals=...))")
+        if not 0 <= i < self.scene.num_images:
+            raise IndexError(f"camera {i} of {self.scene.num_images}")
+        return self.normals[i]

@@ -1,11 +1,14 @@
 """Image metrics of the reference's evaluation (reflect_sampling_nerf_model.py:468-479), computed on the device.
 
-Both functions take [H,W,3] fp32 images (pred, target) and return a 0-d tensor on their device without reading anything
+`psnr` and `ssim` take [H,W,3] fp32 images (pred, target) and return a 0-d tensor on their device without reading anything
 back.  `ssim` is torchmetrics' structural_similarity_index_measure with the defaults the reference uses (model.py:131,470),
 fused into one HIP tile kernel plus a fixed-order reduction (rsn_ssim, include/rsn.h).  LPIPS needs pretrained network
-weights this package does not ship and is not provided.
+weights this package does not ship and is not provided.  `normal_error` is the geometry side of the Ref-NeRF family's tables: the
+alpha-weighted mean angular error of a view's composited predicted normals against a ground-truth normal map (rsn_normal_error).
 """
 from __future__ import annotations
+
+from typing import Dict, Optional
 
 import torch
 
@@ -45,3 +48,56 @@ def ssim(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     _abi.check(lib.rsn_ssim(H, W, _abi.ptr(p), _abi.ptr(t), _abi.ptr(data_range), _abi.ptr(ws), nbytes, _abi.ptr(out),
                             stream))
     return out
+
+
+def normal_error(normals: torch.Tensor, accumulation: Optional[torch.Tensor], gt_normals: torch.Tensor, gt_rgba: torch.Tensor,
+                 c2w: Optional[torch.Tensor] = None, error_map: bool = False) -> Dict[str, torch.Tensor]:
+    """A view's composited predicted normals against its ground-truth normal map (rsn_normal_error, include/rsn.h): the alpha-weighted
+    mean angular error in degrees of multinerf's compute_normal_mae, and the accumulation's mean absolute error against the alpha.
+
+    normals fp32 [H,W,3], of any length per pixel (the angle does not depend on it); accumulation fp32 [H,W,1] or [H,W], or None;
+    gt_normals uint8 [H,W,3], the bytes of the normal map (n * 0.5 + 0.5); gt_rgba uint8 [H,W,4], or float RGBA in [0, 1] as
+    RayDataManager.image returns it (its alpha goes back to its byte, rint(a * 255), on the device).  A pixel counts when its alpha is
+    above zero and its normal bytes are not all 127 or 128 (the background of a normal map).  c2w [3,4] or [4,4] on the device: the
+    maps are in that camera's frame (OpenGL axes, as the poses use them) and are rotated into the world by c2w[:3,:3] first.
+
+    -> 0-d tensors on the device: normal_mae (NaN when no pixel counts), normal_weight (the summed alpha / 255 of the pixels that
+    count), alpha_mae (0 without an accumulation), normal_pixels; with error_map=True also error_map fp32 [H,W], degrees, 0 where the
+    pixel does not count.  Two launches, no device-to-host read."""
+    if normals.dim() != 3 or normals.shape[-1] != 3 or normals.dtype != torch.float32:
+        raise ValueError(f"normals must be float32 [H,W,3], got {normals.dtype} {tuple(normals.shape)}")
+    H, W = int(normals.shape[0]), int(normals.shape[1])
+    dev = normals.device
+    if dev.type != "cuda":
+        raise ValueError(f"normal_error runs on the GPU (rsn_normal_error); got normals on {dev}")
+    if gt_normals.dtype != torch.uint8 or tuple(gt_normals.shape) != (H, W, 3):
+        raise ValueError(f"gt_normals must be uint8 [{H},{W},3], got {gt_normals.dtype} {tuple(gt_normals.shape)}")
+    if tuple(gt_rgba.shape) != (H, W, 4) or not (gt_rgba.dtype == torch.uint8 or gt_rgba.is_floating_point()):
+        raise ValueError(f"gt_rgba must be uint8 or float [{H},{W},4], got {gt_rgba.dtype} {tuple(gt_rgba.shape)}")
+    if accumulation is not None and (accumulation.dtype != torch.float32 or tuple(accumulation.shape) not in ((H, W), (H, W, 1))):
+        raise ValueError(f"accumulation must be float32 [{H},{W}] or [{H},{W},1], got {accumulation.dtype} {tuple(accumulation.shape)}")
+    if c2w is not None and (c2w.dim() != 2 or tuple(c2w.shape) not in ((3, 4), (4, 4))):
+        raise ValueError(f"c2w must be [3,4] or [4,4], got {tuple(c2w.shape)}")
+    for name, t in (("accumulation", accumulation), ("gt_normals", gt_normals), ("gt_rgba", gt_rgba), ("c2w", c2w)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"normals on {dev} and {name} on {t.device}")
+    if H * W < 1 or H * W > _abi.RSN_NORMAL_ERROR_MAX_PIXELS:
+        raise ValueError(f"{H} x {W} pixels: need 1 to 2^24")
+    lib = _abi.load_library()
+    if gt_rgba.dtype != torch.uint8:
+        alpha = torch.clamp(torch.round(gt_rgba[..., 3].float() * 255.0), 0.0, 255.0).to(torch.uint8)  # round: half to even, rint
+        gt_rgba = torch.zeros(H, W, 4, dtype=torch.uint8, device=dev)  # only the alpha byte is read
+        gt_rgba[..., 3] = alpha
+    n, g, a = normals.contiguous(), gt_normals.contiguous(), gt_rgba.contiguous()
+    acc = None if accumulation is None else accumulation.contiguous()
+    rot = None if c2w is None else c2w[:3, :3].to(torch.float32).contiguous()
+    emap = torch.empty(H, W, dtype=torch.float32, device=dev) if error_map else None
+    nbytes = int(lib.rsn_normal_error_workspace_bytes(H * W))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    _abi.check(lib.rsn_normal_error(H * W, _abi.ptr(n), _abi.ptr(acc), _abi.ptr(g), _abi.ptr(a), _abi.ptr(rot), _abi.ptr(emap),
+                                    _abi.ptr(ws), nbytes, _abi.ptr(out), torch.cuda.current_stream(dev).cuda_stream))
+    res = {"normal_mae": out[0], "normal_weight": out[1], "alpha_mae": out[2], "normal_pixels": out[3]}
+    if error_map:
+        res["error_map"] = emap
+    return res

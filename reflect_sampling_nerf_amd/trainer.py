@@ -1,7 +1,7 @@
 """Standalone training and evaluation on Blender-format scenes, without nerfstudio.
 
     python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L] [--distortion-loss X [--distortion-loss-coarse Y]]
-    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L]
+    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L] [--normals [--normals-suffix _normal] [--normals-space world|camera]]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
     python -m reflect_sampling_nerf_amd.trainer export-mesh ... --out mesh.obj --texture [--texels 8] [--min-footprint F]
@@ -48,6 +48,16 @@ coarse level's: the term pulls a ray's weights together into one compact interva
 this method.  The reflect levels never get the term (their weights are detached).  Both are off by default, and the default run has
 the launches, bytes and checkpoint keys it always had; a coefficient that is set is recorded in the checkpoint and comes back with
 --resume.
+
+`eval --normals` scores the geometry as the Ref-NeRF family's tables do: the scene's ground-truth normal maps (FILE_normal.png beside
+every FILE.png, multinerf's naming of the Shiny Blender scenes; --normals-suffix names another) are read with the split, and every
+view's composited predicted normal -- sum_s w_s n_s of the fine level, what the reflected rays start from -- is compared with them on
+the device (metrics.normal_error).  The JSON gains normal_mae, the mean over the views of the alpha-weighted mean angular error in
+degrees (multinerf's compute_normal_mae), and alpha_mae, the mean absolute difference between the fine accumulation and the ground-
+truth alpha, each with its _std, and normal_mae_views, the number of views that had a pixel to score.  The maps are taken as world-
+space normals, which is what Shiny Blender ships; --normals-space camera rotates them by each view's pose first.  With --multiscale
+only the full-resolution renders are scored this way.  The analytic (density-gradient) normals are not scored: the eval path does
+not form them.  Off by default, and the default eval has the launches, keys and bytes it always had.
 
 `export-mesh` takes the learnt geometry out of a checkpoint: the field's density on a regular grid, its iso-surface extracted on
 the device, and the diffuse colour, tint, roughness and predicted normal of the field at every surface vertex, as a binary PLY
@@ -105,6 +115,8 @@ EVAL_CHUNK = 1024  # reflect_sampling_nerf_config.py:41 eval_num_rays_per_chunk
 RUN_STATE_KEY = "rsn_run"  # the trainer's own fifth checkpoint key; nerfstudio's loader ignores it
 RUN_STATE_VERSION = 1
 RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0, "multiscale": 1}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
+DEFAULT_NORMALS_SUFFIX = "_normal"  # multinerf / Shiny Blender: r_0.png beside r_0_normal.png
+NORMALS_SPACES = ("world", "camera")
 LPIPS_NOTE = "fine_lpips not computed: LPIPS needs pretrained network weights that are not shipped with this package"
 
 
@@ -204,6 +216,14 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ev.add_argument("--multiscale", type=int, default=1, metavar="L",
                     help="score every view at L scales, 1, 1/2, ... 1/2^(L-1), against box-averaged ground truth (1 to 5; default 1); "
                          "the results gain KEY_x1, KEY_x2, ... per scale and the plain KEY becomes the mean of those")
+    ev.add_argument("--normals", action="store_true",
+                    help="also score the geometry against the scene's ground-truth normal maps: normal_mae, the alpha-weighted mean angular "
+                         "error of the composited predicted normals in degrees, and alpha_mae, the accumulation against the alpha")
+    ev.add_argument("--normals-suffix", default=None, metavar="S",
+                    help=f"with --normals: a frame's normal map is file_path + S + .png (default {DEFAULT_NORMALS_SUFFIX}, the Shiny Blender naming)")
+    ev.add_argument("--normals-space", choices=NORMALS_SPACES, default=None,
+                    help="with --normals: the frame the normal maps are written in (default world, what Shiny Blender uses; camera: "
+                         "OpenGL camera axes, rotated into the world by each view's pose)")
     _add_occupancy_flags(ev)
     ex = sub.add_parser("export-mesh", help="write the iso-surface of a checkpoint's density as a coloured triangle mesh (PLY)")
     ex.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
@@ -765,6 +785,40 @@ MULTISCALE_NOTE = ("every view is scored at every scale 1/s, s = 1, 2, 4, ..., a
                    "KEY_x<s> / KEY_x<s>_std are the mean and the unbiased standard deviation over the views at scale 1/s; the plain KEY "
                    "is the mean of the per-scale means and KEY_std the unbiased standard deviation of those means")
 SSIM_WINDOW = 11  # include/rsn.h rsn_ssim
+GEOMETRY_KEYS = ("normal_mae", "alpha_mae", "normal_weight")  # per_image, level 0
+GEOMETRY_NOTE = ("normal_mae is the alpha-weighted mean angle in degrees between the composited predicted normal of the fine level, "
+                 "sum_s w_s n_s (unnormalised: the angle does not depend on its length), and the ground-truth normal map, over the pixels "
+                 "with alpha above 0 and a normal other than the background's (bytes 127 / 128); alpha_mae is the mean of |accumulation_fine "
+                 "- alpha| over all pixels; both are scored on the full-resolution render only (with multiscale: level 0, no _x<s> variants, "
+                 "not folded into a per-scale mean), results hold their mean and unbiased standard deviation over the views, views without "
+                 "a pixel to score (normal_mae NaN) left out of normal_mae and counted out of normal_mae_views; the analytic (density-"
+                 "gradient) normals are not scored: eval mode does not form them")
+NORMAL_ERROR_DISPLAY_DEG = 45.0  # the error tile of NNNN_normals.png saturates here: a display range, not a measurement
+
+
+def check_normals_request(scene, normals_space: str) -> None:
+    """ValueError for an `evaluate(normals=True)` that cannot work; host checks only."""
+    if normals_space not in NORMALS_SPACES:
+        raise ValueError(f"normals_space = {normals_space!r}: choose from {', '.join(NORMALS_SPACES)}")
+    if scene.normals is None:
+        raise ValueError("normals=True needs a scene with ground-truth normal maps (scene.normals is None): load it with "
+                         "load_blender_split(..., normals=True) or build it with BlenderScene.from_arrays(..., normals=...)")
+
+
+def _save_normals_panel(path: str, outputs, gt_normals: torch.Tensor, gt_rgba: torch.Tensor, error_map: torch.Tensor) -> None:
+    """predicted normals | ground-truth normals (the file's own frame) | error map, turbo over 0 .. 45 degrees: three rsn_visualize tiles."""
+    from PIL import Image
+
+    from . import render
+    from ._abi import RSN_VIS_LUT, RSN_VIS_UNIT
+
+    H, W = int(error_map.shape[0]), int(error_map.shape[1])
+    panel = torch.empty(H, 3 * W, 3, dtype=torch.uint8, device=error_map.device)
+    render.visualize(render.ray_normals(outputs).contiguous(), RSN_VIS_UNIT, panel, 0, alpha=outputs["accumulation_fine"].contiguous())
+    gt = ((gt_normals.to(torch.float32) * 2.0 - 255.0) / 255.0).contiguous()
+    render.visualize(gt, RSN_VIS_UNIT, panel, W, alpha=(gt_rgba[..., 3].to(torch.float32) / 255.0).contiguous())
+    render.visualize(error_map.contiguous(), RSN_VIS_LUT, panel, 2 * W, lo=0.0, hi=NORMAL_ERROR_DISPLAY_DEG, lut=render.turbo_lut(error_map.device))
+    Image.fromarray(panel.cpu().numpy()).save(path)
 
 
 def eval_level_sizes(scene, multiscale: int):
@@ -780,7 +834,8 @@ def eval_level_sizes(scene, multiscale: int):
 
 
 def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Optional[str] = None, device="cuda:0",
-             model_config=None, occupancy: Optional[dict] = None, multiscale: int = 1) -> dict:
+             model_config=None, occupancy: Optional[dict] = None, multiscale: int = 1, normals: bool = False,
+             normals_space: str = "world") -> dict:
     """Score the checkpoint (a file, or the latest of a run directory) on every view of `scene` (a data.BlenderScene); -> ns-eval-
     shaped dict.  occupancy: None, or the settings of resolve_occupancy_args: the views are rendered with empty-space skipping and
     the dict gains an "occupancy" entry.
@@ -789,12 +844,20 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     per (view, level) with a "level" key, view after view; results gains k_x1, k_x2, k_x4, ... (+ _std) for every metric k, the mean
     over the views at that level; the plain k is the mean of the per-level means, and a "multiscale" entry says so.  The occupancy grid
     is built once, from the full-resolution cameras (whose frusta are those of every level), and culls the rays of every level.
-    ValueError, before the checkpoint is read, when the smallest level is below the 11 x 11 pixels SSIM needs."""
+    ValueError, before the checkpoint is read, when the smallest level is below the 11 x 11 pixels SSIM needs.
+
+    normals=True: the geometry metrics of metrics.normal_error against scene.normals (ValueError, before the checkpoint is read, when
+    the scene has none).  Every level-0 entry of per_image gains normal_mae, alpha_mae and normal_weight; results gains normal_mae,
+    normal_mae_std, alpha_mae, alpha_mae_std and normal_mae_views, and the dict a "geometry" entry (GEOMETRY_NOTE).  normals_space
+    "camera": the maps are in each view's camera frame.  With save_images, NNNN_normals.png: prediction | ground truth | error.
+    normals=False is the evaluation without any of it: the same launches, keys and bytes."""
     from . import metrics
     from .data import RayDataManager
 
     multiscale = int(multiscale)
     sizes = eval_level_sizes(scene, multiscale)
+    if normals:
+        check_normals_request(scene, normals_space)
     dev = torch.device(device)
     ckpt = resolve_checkpoint(ckpt)
     model, step = load_checkpoint(ckpt, model_config, dev)
@@ -819,6 +882,14 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         dt = time.time() - t0
         m["num_rays_per_sec"] = sizes[level][0] * sizes[level][1] / dt
         m["fps"] = 1.0 / dt
+        if normals and level == 0:  # after the clock: the rates above are those of the evaluation without it
+            composited = (outputs["weights_fine"] * outputs["pred_normals_fine"]).sum(dim=-2)
+            geo = metrics.normal_error(composited, outputs["accumulation_fine"], dm.normal_image(i), dm.images[i],
+                                       c2w=dm.c2w[i] if normals_space == "camera" else None, error_map=bool(save_images))
+            m.update({k: float(geo[k]) for k in GEOMETRY_KEYS})
+            if save_images:
+                _save_normals_panel(os.path.join(save_images, f"{i:04d}_normals.png"), outputs, dm.normal_image(i), dm.images[i],
+                                    geo["error_map"])
         per_image.append({"image": i, **({"level": level} if multiscale > 1 else {}), **m})
         if save_images:
             from PIL import Image
@@ -826,7 +897,7 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
             panel = (images["img"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
             name = f"{i:04d}_img.png" if level == 0 else f"{i:04d}_x{1 << level}_img.png"
             Image.fromarray(panel).save(os.path.join(save_images, name))
-    keys = [k for k in per_image[0] if k not in ("image", "level")] if per_image else []
+    keys = [k for k in per_image[0] if k not in ("image", "level") + GEOMETRY_KEYS] if per_image else []
 
     def mean_std(v):
         v = np.asarray(v, dtype=np.float64)
@@ -841,6 +912,12 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         results[k], results[k + "_std"] = mean_std([m for m, _ in per_level])
         for level, (m, sd) in enumerate(per_level):
             results[f"{k}_x{1 << level}"], results[f"{k}_x{1 << level}_std"] = m, sd
+    if normals:
+        scored = [p for p in per_image if "normal_mae" in p]
+        counted = [p["normal_mae"] for p in scored if not math.isnan(p["normal_mae"])]
+        results["normal_mae"], results["normal_mae_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
+        results["normal_mae_views"] = len(counted)
+        results["alpha_mae"], results["alpha_mae_std"] = mean_std([p["alpha_mae"] for p in scored]) if scored else (float("nan"), float("nan"))
     res = {"experiment_name": os.path.basename(os.path.dirname(os.path.abspath(ckpt))), "method_name": METHOD_NAME,
            "checkpoint": ckpt, "step": step, "results": results, "not_computed": {"fine_lpips": LPIPS_NOTE},
            "per_image": per_image}
@@ -848,6 +925,8 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         res["multiscale"] = {"levels": multiscale, "scales": [1 << level for level in range(multiscale)], "note": MULTISCALE_NOTE}
     if occupancy is not None:
         res["occupancy"] = model.occupancy.describe()
+    if normals:
+        res["geometry"] = {"normals_space": normals_space, "note": GEOMETRY_NOTE}
     return res
 
 
@@ -866,6 +945,10 @@ def main(argv=None) -> int:
     cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
         ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
+    if args.command == "eval" and not args.normals:
+        stray = [f for f, v in (("--normals-suffix", args.normals_suffix), ("--normals-space", args.normals_space)) if v is not None]
+        if stray:
+            ap.error(f"eval: {' '.join(stray)} need(s) --normals")
     if args.command in ("train", "eval") and not 1 <= args.multiscale <= 5:
         ap.error(f"{args.command}: --multiscale {args.multiscale}: need 1 to 5")
     if not torch.cuda.is_available():
@@ -935,13 +1018,18 @@ def main(argv=None) -> int:
         print(f"{res['checkpoint']} (step {res['step']}): {n} frames {res['width']} x {res['height']} of {' '.join(res['channels'])}; "
               f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
         return 0
-    scene = load_blender_split(args.data, args.split, args.scale_factor)
+    if args.normals:
+        scene = load_blender_split(args.data, args.split, args.scale_factor, normals=True,
+                                   normals_suffix=DEFAULT_NORMALS_SUFFIX if args.normals_suffix is None else args.normals_suffix)
+    else:
+        scene = load_blender_split(args.data, args.split, args.scale_factor)
     try:
         eval_level_sizes(scene, args.multiscale)
     except ValueError as e:
         ap.error(f"eval: {e}")
+    geometry = dict(normals=True, normals_space=args.normals_space or "world") if args.normals else {}
     res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images, occupancy=occupancy,
-                   multiscale=args.multiscale)
+                   multiscale=args.multiscale, **geometry)
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=2)
     r = res["results"]
@@ -950,6 +1038,8 @@ def main(argv=None) -> int:
                                         if f"{k}_x{1 << level}" in r and not math.isnan(r[f"{k}_x{1 << level}"])))
     print(" ".join(f"{k} {r[k]:.4f}" for k in ("psnr", "coarse_psnr", "fine_psnr", "fine_ssim") if k in r
                    and not math.isnan(r[k])) + f"  ({len(res['per_image'])} images) -> {args.out}")
+    if args.normals:
+        print(f"normal_mae {r['normal_mae']:.3f} deg over {r['normal_mae_views']} views, alpha_mae {r['alpha_mae']:.4f}")
     return 0
 
 
