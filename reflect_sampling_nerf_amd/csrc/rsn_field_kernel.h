@@ -16,17 +16,19 @@
 // SH part then accumulates into the same four blocks, and the K = W GEMM over the bottleneck row is gone with the row itself
 // (saved.bott is neither written nor read).  Heads, sigma and normals keep their bits: same K order, same bias start.
 // MMA: the rsn_mma_mode the kernel serves -- 0 exact fp32, 1 / 2 split-bf16, 3 plain-bf16 training, 4 = 0 with FOLD.
-// A loop GEMM of the analytic-normal sweep.  X9 (the exact-fp32 training instantiations): the nine-product loop on the bf16 MFMAs,
-// PACKED (FOLD) over the pre-split hT_* segment, else with the same pieces formed in registers from the fp32 wT_* segment (the
-// RSN_MMA_F32 buffer has no split copies): the same bits either way.  Otherwise the mode's own loop.
-template <bool X9, bool PACKED, int MODE, int NBO>
+// A loop GEMM of the analytic-normal sweep in the mode's own loop, and, for the exact-fp32 training instantiations, as the
+// nine-product loop on the 16x16x32 bf16 MFMAs: PACKED (FOLD) over the pre-split hT_* segment, else with the same pieces formed in
+// registers from the fp32 wT_* segment (the RSN_MMA_F32 buffer has no split copies): the same bits either way.
+template <int MODE, int NBO>
 __device__ __forceinline__ void sweep_gemm(f32x16 (&acc)[NBO], const float* __restrict__ w32, const float* __restrict__ w16,
                                            const float4* xl, int n_it, int lane) {
-  if constexpr (X9) {
-    if constexpr (PACKED) gemm_bf16<NBO, 3, true>(acc, w16, xl, n_it / 2, lane); else gemm_f32_x9<NBO>(acc, w32, xl, n_it / 2, lane);
-  } else {
-    gemm_mode<MODE, NBO, NBO, true>(acc, w32, w16, xl, n_it, lane);
-  }
+  gemm_mode<MODE, NBO, NBO, true>(acc, w32, w16, xl, n_it, lane);
+}
+template <bool PACKED, int N_IT, int NBO>
+__device__ __forceinline__ void sweep_gemm(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32, const float* __restrict__ w16,
+                                           const float4* xl, int lane) {
+  static_assert(N_IT % 4 == 0, "K = 8 N_IT is a multiple of 32 at every width (the units are padded to 32): no tail path");
+  if constexpr (PACKED) gemm_bf16_s16<NBO>(acc, w16, xl, N_IT / 4, lane); else gemm_f32_x9_s16<NBO>(acc, w32, xl, N_IT / 4, lane);
 }
 
 template <int NB, bool TRAIN, int MMA>
@@ -286,6 +288,8 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // has no encoded-input GEMM.
     // The GEMMs behind it (W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs) run on the bf16 MFMAs too, as all NINE products of
     // three bf16 pieces a side (sweep_gemm): no term of the fp32 product is dropped, only the order of the fp32 accumulation differs.
+    // They run on the 16x16x32 shape (rsn_mfma.h): a lane then reads and writes float4 of OTHER lanes' slots of the wave's X slab,
+    // which needs no barrier -- a wave's LDS instructions complete in order, and no other wave touches the slab.
     constexpr bool SEED_BITS = TRAIN && MODE == 0;
     if (TRAIN && a.saved.normals && a.saved.relu_bits) {
       const float* __restrict__ wd = pk + P.L.v_density;
@@ -317,20 +321,42 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
               __uint_as_float(__float_as_uint(w.w) & bit_mask(word, base + 3)));
         }
       }
-      f32x16 eacc[4];
-      zero_acc<4>(eacc);
+      if constexpr (SEED_BITS) {
+        // the mask words of the two old lanes whose float4 this lane writes (store_masked_bits16): point halves 0 and 1
+        auto bits16_at = [&](int l, int ph) -> const unsigned* {
+          const long long q = p0 + (ln & 15) + 16 * ph, qc = q < n_points ? q : n_points - 1;
+          return a.saved.relu_bits + ((((long long)l * (a.act_stride / W)) + qc) * 2 + ((ln >> 4) & 1)) * (NB / 2 > 2 ? NB / 2 : 2);
+        };
+        f32x4 eacc[4][2][2];
+        zero_acc16<4>(eacc);
 #pragma unroll 1
-      for (int l = P.num_layers - (peel ? 2 : 1); l >= 1; --l) {
-        if (l == P.skip_layer) sweep_gemm<SEED_BITS, FOLD, MODE, 4>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
-        const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));
-        __builtin_amdgcn_sched_barrier(0);
-        f32x16 acc[NB];
-        zero_acc<NB>(acc);
-        sweep_gemm<SEED_BITS, FOLD, MODE, NB>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln);
-        store_masked_bits<NB>(acc, X, mb, h);
+        for (int l = P.num_layers - (peel ? 2 : 1); l >= 1; --l) {
+          if (l == P.skip_layer) sweep_gemm<FOLD, NB * 4, 4>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, ln);
+          const ReluBits<NB> mb[2] = {load_relu_bits<NB>(bits16_at(l - 1, 0)), load_relu_bits<NB>(bits16_at(l - 1, 1))};
+          __builtin_amdgcn_sched_barrier(0);
+          f32x4 acc[NB][2][2];
+          zero_acc16<NB>(acc);
+          sweep_gemm<FOLD, NB * 4, NB>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, ln);
+          store_masked_bits16<NB>(acc, X, mb, ln);
+        }
+        sweep_gemm<FOLD, NB * 4, 4>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, ln);
+        store_act16<4>(eacc, X, ln);  // gradient w.r.t. the encoded inputs, slot order (its 0..12), where store_act puts it
+      } else {
+        f32x16 eacc[4];
+        zero_acc<4>(eacc);
+#pragma unroll 1
+        for (int l = P.num_layers - 1; l >= 1; --l) {
+          if (l == P.skip_layer) sweep_gemm<MODE, 4>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
+          const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));
+          __builtin_amdgcn_sched_barrier(0);
+          f32x16 acc[NB];
+          zero_acc<NB>(acc);
+          sweep_gemm<MODE, NB>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln);
+          store_masked_bits<NB>(acc, X, mb, h);
+        }
+        sweep_gemm<MODE, 4>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, NB * 4, ln);
+        store_act<4, 4, false>(eacc, X);  // gradient w.r.t. this lane's encoded inputs, slot order (its 0..12)
       }
-      sweep_gemm<SEED_BITS, FOLD, MODE, 4>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, NB * 4, ln);
-      store_act<4, 4, false>(eacc, X);  // gradient w.r.t. this lane's encoded inputs, slot order (its 0..12)
       float nrm[3];
 #pragma unroll 1
       for (int c = 0; c < 3; ++c) {

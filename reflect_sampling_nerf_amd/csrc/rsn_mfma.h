@@ -404,7 +404,9 @@ __device__ __forceinline__ void load_w16(bf16x8 (&w)[NH][3], const WBuf& wp, int
 
 // FULL (NSPLIT = 3 only): all NINE piece products -- w3x3, w3x2, w2x3 ahead of the six, so that the smallest terms meet the
 // accumulator first.  Every piece product is exact in fp32 and the pieces add up to the fp32 operands, so no term of the fp32
-// product is dropped: the result differs from the fp32 MFMA's only by the order of the fp32 accumulation.
+// product is dropped: the result differs from the fp32 MFMA's only by the order of the fp32 accumulation.  (The analytic-normal sweep
+// ran this form until it moved to the 16x16x32 shape, gemm_bf16_s16 below; tools/probes/sweep_x9_probe.hip still times the two
+// side by side.)
 template <int NBO, int NH, int NB0, int NSPLIT, bool FULL = false>
 __device__ __forceinline__ void mma16(f32x16 (&acc)[NBO], const bf16x8 (&w)[NH][3], const BSplit& b) {
   static_assert(!FULL || NSPLIT == 3, "the full product is over three pieces a side");
@@ -745,76 +747,195 @@ __device__ __forceinline__ void gemm_f32_bits(f32x16 (&acc)[NBO], const float* _
 }
 
 // ------------------------------------------------------------------------------------------------
-// Nine-product K loop without packed pieces (RSN_MMA_F32, whose packed buffer has no hT_* copies): gemm_bf16<NBO, 3, true> with the
-// weight pieces formed in registers from the fp32 fragments of a wT_* segment ([it][NBO][lane][4]; K-iterations 2kk, 2kk + 1 are
-// the eight values of K = 16 step kk).  split8<3> is split_elem's expression (rsn_pack.hip), and the nine products meet each
-// accumulator in mma16<.., true>'s order: bit for bit the result of the packed form.  K a multiple of 16.
+// The nine-product loops on v_mfma_f32_16x16x32_bf16 (exact-fp32 training, the analytic-normal sweep): the same MFMA cycles (36 of
+// 16 per block and K = 32 against 18 of 32) and the same arithmetic per accumulator (nine products, smallest terms first), on the
+// shape at which the chip holds the higher clock under load.  The wave's output tile stays 32 points x 32 NBO rows, as
+// NBO x 2 row halves x 2 point halves results of 16 x 16.  Lane L = (i = L & 15, g = L >> 4) owns K group g of a K = 32 step,
+// which is K group g & 1 of K = 16 step 2 s + (g >> 1): it reads the 16-byte granule of OLD lane (i + 16 rh) + 32 (g & 1) of the
+// very records the 32x32x16 loop reads (no other packing), and the two float4 of old lane (i + 16 ph) + 32 (g & 1) of the X slab,
+// so A and B meet on the same K set at every MFMA position and the K permutation of the packing carries over.
+// Accumulator register r of result (nb, rh, ph) is row 32 nb + 16 rh + 4 (L >> 4) + r of point i + 16 ph: in the X layout of
+// store_act one float4, K-iteration 4 nb + 2 rh + (L >> 5) of old lane (i + 16 ph) + 32 ((L >> 4) & 1).
+// K must be a multiple of 32 (the kernels pad their widths to 32): no tail path.
 // ------------------------------------------------------------------------------------------------
-// the nine products of one block and K step, in mma16<.., true>'s order
-__device__ __forceinline__ f32x16 x9_block(f32x16 c, const BSplit& w, const BSplit& b) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s3, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s2, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s3, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s1, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s2, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s3, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s1, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s2, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s1, c, 0, 0, 0);
-  return c;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <int NBO>
+__device__ __forceinline__ void zero_acc16(f32x4 (&acc)[NBO][2][2]) {
+#pragma unroll
+  for (int nb = 0; nb < NBO; ++nb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[nb][q >> 1][q & 1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 }
 
-// A software pipeline over the blocks: while the nine MFMAs of block b run (288 cycles), the VALU forms the pieces of block b + 1
-// (about 50 instructions, five or six behind each MFMA; the last block of a K step also splits the next step's activations).  A
-// fragment buffer is dead once its last block is split, and is reloaded for the next K step at the start of the block after that.
-// Written block by block (split, then nine MFMAs) hipcc issues the ~50 VALU instructions of a block in one run ahead of its MFMAs:
-// that loop took 0.98 of the fp32 form's time alone and made the unfolded training forward 7 % slower; this one 0.87-0.90
-// (tools/probes/sweep_x9_probe.hip), the forward 2 % faster.
+// the lane's place in the 16-shape: the old lane whose operand granules it reads for row half / point half 0 (the other half is
+// 16 old lanes on), and the half K = 32 step it owns
+struct Lane16 {
+  int ol;  // (L & 15) + 32 ((L >> 4) & 1)
+  int kh;  // L >> 5
+};
+__device__ __forceinline__ Lane16 lane16(int lane) {
+  Lane16 g;
+  g.ol = (lane & 15) + 2 * (lane & 16);
+  g.kh = lane >> 5;
+  return g;
+}
+
+// the nine products of NQ blocks against the two point halves, in mma16<.., true>'s order per accumulator; the four results of a
+// block take each product in turn (four independent accumulators between two MFMAs of one chain)
+__device__ __forceinline__ bf16x8 piece(const BSplit& b, int k) { return k == 0 ? b.s1 : (k == 1 ? b.s2 : b.s3); }  // k: a constant
+constexpr int x9_wp(int p) { constexpr int t[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0}; return t[p]; }  // product p: the weight's piece
+constexpr int x9_bp(int p) { constexpr int t[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0}; return t[p]; }  //            the activation's piece
+template <int NBO, int NQ>
+__device__ __forceinline__ void mma16s(f32x4 (&acc)[NBO][2][2], const bf16x8 (&w)[NQ][2][3], const BSplit (&b)[2], int nb0) {
+#pragma unroll
+  for (int t = 0; t < NQ; ++t)
+#pragma unroll
+    for (int p = 0; p < 9; ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        acc[nb0 + t][q >> 1][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[t][q >> 1][x9_wp(p)], piece(b[q & 1], x9_bp(p)),
+                                                                              acc[nb0 + t][q >> 1][q & 1], 0, 0, 0);
+}
+
+// the packed pieces of NQ blocks (both row halves) of K = 32 step s; wp.voff carries the lane's granule (gemm_bf16_s16)
+template <int NQ>
+__device__ __forceinline__ void load_w16s(bf16x8 (&w)[NQ][2][3], const WBuf& wp, int s, int nbo, int nb0) {
+#pragma unroll
+  for (int t = 0; t < NQ; ++t)
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+      for (int sp = 0; sp < 3; ++sp) {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wp.r, wp.voff + rh * 256u, (unsigned)(((2 * s * nbo + nb0 + t) * 3 + sp) * 1024), 0);
+        w[t][rh][sp] = __builtin_bit_cast(bf16x8, v);
+      }
+}
+
+// Packed pieces (hT_* segment, [k16][NBO][piece][lane][8 bf16]).  Fragment buffers of a quarter of the blocks (the 96 registers of
+// gemm_bf16's two half-step buffers); the next step's activations are split under the first two chunks' MFMAs, one point half each.
 template <int NBO>
-__device__ __forceinline__ void gemm_f32_x9(f32x16 (&acc)[NBO], const float* __restrict__ w32seg, const float4* xl, int n_k16,
-                                            int lane) {
-  static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
-  constexpr int NH = NBO / 2;
-  const WBuf wp = wbuf_make(w32seg, lane);
-  float4 fa[NH][2], fb[NH][2];
-  load_w32_pair<NBO, NH>(fa, wp, 0, 0);
-  load_w32_pair<NBO, NH>(fb, wp, 0, NH);
-  BSplit bc = split8<3>(xl[0], xl[64]);
-  const int k1 = n_k16 > 1 ? 1 : 0;
-  float4 xlo = xl[(2 * k1) * 64], xhi = xl[(2 * k1 + 1) * 64];  // fp32 activations of the NEXT K step
-  BSplit w = split8<3>(fa[0][0], fa[0][1]);
-  BSplit bn = bc;
+__device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ wseg, const float4* xl, int n_k32,
+                                              int lane) {
+  static_assert(NBO % 2 == 0, "an even number of fragment buffers' worth of blocks");
+  constexpr int NQ = NBO >= 4 ? NBO / 4 : 1, NC = NBO / NQ;  // blocks per fragment buffer, chunks per K step (even)
+  const Lane16 g = lane16(lane);
+  WBuf wp = wbuf_make(wseg, lane);
+  wp.voff = (unsigned)g.ol * 16u + (unsigned)g.kh * (NBO * 3072u);
+  const float4* xb = xl - lane + g.ol + g.kh * 128;  // LDS iterations 4 s + 2 kh, + 1; point half 1 is 16 float4 on
+  bf16x8 wa[NQ][2][3], wb[NQ][2][3];
+  load_w16s<NQ>(wa, wp, 0, NBO, 0);
+  BSplit bc[2] = {split8<3>(xb[0], xb[64]), split8<3>(xb[16], xb[80])};
+  const int s1 = n_k32 > 1 ? 1 : 0;
+  float4 x0lo = xb[4 * s1 * 64], x0hi = xb[(4 * s1 + 1) * 64], x1lo = xb[4 * s1 * 64 + 16], x1hi = xb[(4 * s1 + 1) * 64 + 16];
 #pragma unroll 1
-  for (int kk = 0; kk < n_k16; ++kk) {
-    const int kn = (kk + 1 < n_k16) ? kk + 1 : kk;  // clamped: one control path keeps the s_waitcnt counts exact
-    const int k2 = (kk + 2 < n_k16) ? kk + 2 : kn;
+  for (int s = 0; s < n_k32; ++s) {
+    const int sn = (s + 1 < n_k32) ? s + 1 : s;  // clamped: one control path keeps the s_waitcnt counts exact
+    const int s2 = (s + 2 < n_k32) ? s + 2 : sn;
+    BSplit bn[2];
 #pragma unroll
-    for (int b = 0; b < NBO; ++b) {
-      BSplit wn;
-      if (b + 1 < NH) wn = split8<3>(fa[b + 1][0], fa[b + 1][1]);
-      else if (b + 1 < NBO) wn = split8<3>(fb[b + 1 - NH][0], fb[b + 1 - NH][1]);
-      else wn = split8<3>(fa[0][0], fa[0][1]);  // block 0 of step kn: fa was reloaded at block NH - 1
-      if (b == NH - 1) load_w32_pair<NBO, NH>(fa, wp, kn, 0);
-      if (b == NBO - 1) {
-        load_w32_pair<NBO, NH>(fb, wp, kn, NH);
-        bn = split8<3>(xlo, xhi);
-        xlo = xl[(2 * k2) * 64];
-        xhi = xl[(2 * k2 + 1) * 64];
+    for (int c = 0; c < NC; ++c) {
+      if (c & 1) load_w16s<NQ>(wa, wp, c + 1 < NC ? s : sn, NBO, c + 1 < NC ? (c + 1) * NQ : 0);
+      else load_w16s<NQ>(wb, wp, s, NBO, (c + 1) * NQ);
+      __builtin_amdgcn_sched_barrier(0);
+      if (c == 0) bn[0] = split8<3>(x0lo, x0hi);
+      if (c == 1) bn[1] = split8<3>(x1lo, x1hi);
+      if (c == NC - 1) {
+        x0lo = xb[4 * s2 * 64]; x0hi = xb[(4 * s2 + 1) * 64];
+        x1lo = xb[4 * s2 * 64 + 16]; x1hi = xb[(4 * s2 + 1) * 64 + 16];
       }
-      acc[b] = x9_block(acc[b], w, bc);
-      const bool loads = b == NH - 1 || b == NBO - 1;
+      if (c & 1) mma16s<NBO, NQ>(acc, wb, bc, c * NQ); else mma16s<NBO, NQ>(acc, wa, bc, c * NQ);
 #pragma unroll
-      for (int g = 0; g < 9; ++g) {
+      for (int m = 0; m < NQ * 36; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
-        if (loads && g < 2 * NH) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
-        if (b == NBO - 1) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);  // the next block's pieces + the next step's activations
-        else __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);  // the next block's pieces
+        if (c < 2) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // the next step's pieces: an MFMA leaves 8 of its 16 cycles
       }
-      if (b == NBO - 1) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // the LDS reads of the activations
+      if (c == NC - 1) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // the LDS reads of the activations
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    bc[0] = bn[0];
+    bc[1] = bn[1];
+  }
+}
+
+// The same loop without packed pieces (RSN_MMA_F32): the weight pieces formed in registers by split8<3> from the fp32 fragments of
+// a wT_* segment ([it][NBO][lane][4]; the lane reads K-iterations 4 s + 2 kh, + 1 of old lane ol + 16 rh), the nine products in the
+// same order per accumulator: bit for bit the packed form.  A software pipeline over the 2 NBO row halves of a K step: the pieces
+// of row half u + 1 are formed under the eighteen MFMAs of row half u (the last two also split the next step's activations).  A
+// 16-cycle MFMA leaves the VALU 8 cycles where a 32-cycle one left 24, so about 50 VALU instructions per 18 MFMAs make this loop
+// VALU-bound: it takes 1.01-1.03 of the time of its 32x32x16 form (tools/probes/sweep_x9_probe.hip, forms (e) and (c)) and the
+// unfolded primary forward launch 3 % more (profiles/normals_shape16.json); it is on this shape for the bits it shares with the
+// packed loop.  A fragment buffer (a quarter of the blocks) is dead once its last row half is split and is reloaded, two
+// chunks ahead, under the MFMAs of that row half.
+template <int NQ>
+__device__ __forceinline__ void load_w32s(float4 (&f)[NQ][2][2], const WBuf& b, int s, int nbo, int nb0) {
+#pragma unroll
+  for (int t = 0; t < NQ; ++t)
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(b.r, b.voff + rh * 256u, (unsigned)(((4 * s + j) * nbo + nb0 + t) * 1024), 0);
+        f[t][rh][j] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+      }
+}
+
+template <int NBO>
+__device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32seg, const float4* xl,
+                                                int n_k32, int lane) {
+  static_assert(NBO % 2 == 0, "an even number of fragment buffers' worth of blocks");
+  constexpr int NQ = NBO >= 4 ? NBO / 4 : 1, NC = NBO / NQ, UQ = 2 * NQ, NU = 2 * NBO;  // row halves per chunk and per K step
+  const Lane16 g = lane16(lane);
+  WBuf wp = wbuf_make(w32seg, lane);
+  wp.voff = (unsigned)g.ol * 16u + (unsigned)g.kh * (NBO * 2048u);
+  const float4* xb = xl - lane + g.ol + g.kh * 128;
+  float4 fa[NQ][2][2], fb[NQ][2][2];
+  load_w32s<NQ>(fa, wp, 0, NBO, 0);
+  load_w32s<NQ>(fb, wp, 0, NBO, NQ);
+  BSplit bc[2] = {split8<3>(xb[0], xb[64]), split8<3>(xb[16], xb[80])};
+  const int s1 = n_k32 > 1 ? 1 : 0;
+  float4 x0lo = xb[4 * s1 * 64], x0hi = xb[(4 * s1 + 1) * 64], x1lo = xb[4 * s1 * 64 + 16], x1hi = xb[(4 * s1 + 1) * 64 + 16];
+  BSplit w = split8<3>(fa[0][0][0], fa[0][0][1]);
+  BSplit bn[2] = {bc[0], bc[1]};
+#pragma unroll 1
+  for (int s = 0; s < n_k32; ++s) {
+    const int sn = (s + 1 < n_k32) ? s + 1 : s;  // clamped: one control path keeps the s_waitcnt counts exact
+    const int s2 = (s + 2 < n_k32) ? s + 2 : sn;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int un = (u + 1) % NU, cn = (un / UQ) & 1, tn = (un / 2) % NQ;  // the next row half: its buffer and block in it
+      const BSplit wn = cn ? split8<3>(fb[tn][un & 1][0], fb[tn][un & 1][1]) : split8<3>(fa[tn][un & 1][0], fa[tn][un & 1][1]);
+      const bool reload = u % UQ == UQ - 1;
+      if (reload) {
+        const int c = u / UQ, c2 = (c + 2) % NC;
+        if (c & 1) load_w32s<NQ>(fb, wp, c + 2 < NC ? s : sn, NBO, c2 * NQ);
+        else load_w32s<NQ>(fa, wp, c + 2 < NC ? s : sn, NBO, c2 * NQ);
+      }
+      if (u == NU - 2) bn[0] = split8<3>(x0lo, x0hi);
+      if (u == NU - 1) {
+        bn[1] = split8<3>(x1lo, x1hi);
+        x0lo = xb[4 * s2 * 64]; x0hi = xb[(4 * s2 + 1) * 64];
+        x1lo = xb[4 * s2 * 64 + 16]; x1hi = xb[(4 * s2 + 1) * 64 + 16];
+      }
+#pragma unroll
+      for (int p = 0; p < 9; ++p)
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph)
+          acc[u >> 1][u & 1][ph] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(piece(w, x9_wp(p)), piece(bc[ph], x9_bp(p)),
+                                                                           acc[u >> 1][u & 1][ph], 0, 0, 0);
+#pragma unroll
+      for (int m = 0; m < 18; ++m) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+        if (reload && m < NQ * 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
+        if (u >= NU - 2) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // the next row half's pieces + the next step's activations
+        else __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // the next row half's pieces
+      }
+      if (u == NU - 1) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // the LDS reads of the activations
       __builtin_amdgcn_sched_barrier(0);
       w = wn;
     }
-    bc = bn;
+    bc[0] = bn[0];
+    bc[1] = bn[1];
   }
 }
 
@@ -844,6 +965,44 @@ __device__ __forceinline__ void store_masked_bits(const f32x16 (&acc)[NBO], floa
       v.w = __uint_as_float(__float_as_uint(acc[nb][4 * q + 3]) & bit_mask(word, base + 3));
       xl[(nb * 4 + q) * 64] = v;
       if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
+    }
+}
+
+// Epilogues of the 16-shape.  One result is one float4 of the X slab (see above); its mask nibble is bits 16 nb + 4 (2 rh + kh) ..
+// + 3 of the ReluBits of the old lane that owns that float4, so a lane holds the words of two old lanes (point halves 0 and 1).
+template <int NBO>
+__device__ __forceinline__ void store_masked_bits16(const f32x4 (&acc)[NBO][2][2], float4* xl, const ReluBits<NBO> (&m)[2], int lane) {
+  const Lane16 g = lane16(lane);
+  float4* xs = xl - lane + g.ol + g.kh * 64;
+#pragma unroll
+  for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+    for (int nb = 0; nb < NBO; ++nb) {
+      const int word = (int)(m[ph].w[nb / 2] >> (4 * g.kh));
+#pragma unroll
+      for (int rh = 0; rh < 2; ++rh) {
+        const int base = (nb & 1) * 16 + 8 * rh;
+        const f32x4& a = acc[nb][rh][ph];
+        float4 v;
+        v.x = __uint_as_float(__float_as_uint(a[0]) & bit_mask(word, base + 0));
+        v.y = __uint_as_float(__float_as_uint(a[1]) & bit_mask(word, base + 1));
+        v.z = __uint_as_float(__float_as_uint(a[2]) & bit_mask(word, base + 2));
+        v.w = __uint_as_float(__float_as_uint(a[3]) & bit_mask(word, base + 3));
+        xs[(nb * 4 + 2 * rh) * 64 + 16 * ph] = v;
+      }
+    }
+}
+
+template <int NBO>
+__device__ __forceinline__ void store_act16(const f32x4 (&acc)[NBO][2][2], float4* xl, int lane) {
+  const Lane16 g = lane16(lane);
+  float4* xs = xl - lane + g.ol + g.kh * 64;
+#pragma unroll
+  for (int nb = 0; nb < NBO; ++nb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4& a = acc[nb][q >> 1][q & 1];
+      xs[(nb * 4 + 2 * (q >> 1)) * 64 + 16 * (q & 1)] = make_float4(a[0], a[1], a[2], a[3]);
     }
 }
 

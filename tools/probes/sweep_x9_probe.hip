@@ -1,12 +1,17 @@
 // sweep_x9_probe.hip -- one W = 256 GEMM of the analytic-normal sweep (rsn_field_kernel.h, the loop over l behind the peeled seed
 // GEMM) in isolation: W_l^T (256 x 256) times the masked layer gradient of a 32-point tile, the B operand read from the wave's LDS
-// slab in the X layout.  Three forms:
-//   (a) fp32: gemm<8, 8, PF2> over a wT_x segment, 1,024 v_mfma_f32_32x32x2_f32 of 64 cycles (what the kernel runs);
+// slab in the X layout.  Five forms, (a) to (c) what the kernel ran in turn, (d) and (e) what it runs:
+//   (a) fp32: gemm<8, 8, PF2> over a wT_x segment, 1,024 v_mfma_f32_32x32x2_f32 of 64 cycles;
 //   (b) nine products, packed: gemm_bf16<8, 3, FULL> over an hT_x segment (three bf16 pieces per weight, split on the host by
 //       split_elem's expressions), 1,152 v_mfma_f32_32x32x16_bf16 of 32 cycles, 384 KiB of weights per wave and GEMM against 256;
-//   (c) nine products, the weight pieces formed in registers from the fp32 segment (gemm_f32_x9, the RSN_MMA_F32 kernel's form:
-//       the pieces of block b + 1 are formed under the nine MFMAs of block b);
+//   (c) nine products, the weight pieces formed in registers from the fp32 segment (gemm_f32_x9 below, the RSN_MMA_F32 kernel's
+//       form until the sweep took shape (e): the pieces of block b + 1 are formed under the nine MFMAs of block b);
+//   (d) nine products, packed, on v_mfma_f32_16x16x32_bf16: gemm_bf16_s16<8> over the same hT_x segment bytes (another per-lane
+//       offset), 4,608 MFMAs of 16 cycles into the same 32-point x 256-row tile per wave: the same MFMA cycles, another shape;
+//   (e) (d) with the weight pieces formed in registers from the fp32 segment (gemm_f32_x9_s16, the RSN_MMA_F32 kernel's form);
 // and, for scale, the six-product loop of the bf16x6 mode (gemm_bf16<8, 3>).
+// Before anything is timed, (b) and (d) run one tile each on integer operands whose every sum is exact in fp32 (17-bit weights
+// against 0 / +-1 activations, then the reverse) and their X slabs are compared with each other and with the host's integer sums.
 // The kernel's real grid: one workgroup of four waves per CU on every CU at once (clock and power effects show), each wave on its
 // own 32-point tile and LDS slab, the workgroup's LDS sized so that one workgroup fills the CU; every wave runs only this GEMM for
 // TILES tiles and the four waves start together behind a barrier.  Weights and activations are pseudo-random, not zeros: the
@@ -24,12 +29,84 @@
 void rsn_set_error(const char*, ...) {}
 #define CK(call) do { if ((call) != hipSuccess) { printf("%s failed\n", #call); exit(1); } } while (0)
 
+// The 32x32x16 form of the in-register loop, as the RSN_MMA_F32 kernel ran it before the sweep moved to the 16x16x32 shape; kept
+// here as form (c), what form (e) is measured against.  gemm_bf16<NBO, 3, true> with the weight pieces formed by split8<3> from the
+// fp32 fragments of a wT_* segment ([it][NBO][lane][4]; K-iterations 2kk, 2kk + 1 are the eight values of K = 16 step kk), the nine
+// products in mma16<.., true>'s order.  K a multiple of 16.
+// the nine products of one block and K step, in mma16<.., true>'s order
+__device__ __forceinline__ f32x16 x9_block(f32x16 c, const BSplit& w, const BSplit& b) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s3, b.s1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s2, b.s1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.s1, b.s1, c, 0, 0, 0);
+  return c;
+}
+
+// A software pipeline over the blocks: while the nine MFMAs of block b run (288 cycles), the VALU forms the pieces of block b + 1
+// (about 50 instructions, five or six behind each MFMA; the last block of a K step also splits the next step's activations).  A
+// fragment buffer is dead once its last block is split, and is reloaded for the next K step at the start of the block after that.
+// Written block by block (split, then nine MFMAs) hipcc issues the ~50 VALU instructions of a block in one run ahead of its MFMAs:
+// that loop took 0.98 of the fp32 form's time alone and made the unfolded training forward 7 % slower; this one 0.87-0.90
+// (tools/probes/sweep_x9_probe.hip), the forward 2 % faster.
+template <int NBO>
+__device__ __forceinline__ void gemm_f32_x9(f32x16 (&acc)[NBO], const float* __restrict__ w32seg, const float4* xl, int n_k16,
+                                            int lane) {
+  static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
+  constexpr int NH = NBO / 2;
+  const WBuf wp = wbuf_make(w32seg, lane);
+  float4 fa[NH][2], fb[NH][2];
+  load_w32_pair<NBO, NH>(fa, wp, 0, 0);
+  load_w32_pair<NBO, NH>(fb, wp, 0, NH);
+  BSplit bc = split8<3>(xl[0], xl[64]);
+  const int k1 = n_k16 > 1 ? 1 : 0;
+  float4 xlo = xl[(2 * k1) * 64], xhi = xl[(2 * k1 + 1) * 64];  // fp32 activations of the NEXT K step
+  BSplit w = split8<3>(fa[0][0], fa[0][1]);
+  BSplit bn = bc;
+#pragma unroll 1
+  for (int kk = 0; kk < n_k16; ++kk) {
+    const int kn = (kk + 1 < n_k16) ? kk + 1 : kk;  // clamped: one control path keeps the s_waitcnt counts exact
+    const int k2 = (kk + 2 < n_k16) ? kk + 2 : kn;
+#pragma unroll
+    for (int b = 0; b < NBO; ++b) {
+      BSplit wn;
+      if (b + 1 < NH) wn = split8<3>(fa[b + 1][0], fa[b + 1][1]);
+      else if (b + 1 < NBO) wn = split8<3>(fb[b + 1 - NH][0], fb[b + 1 - NH][1]);
+      else wn = split8<3>(fa[0][0], fa[0][1]);  // block 0 of step kn: fa was reloaded at block NH - 1
+      if (b == NH - 1) load_w32_pair<NBO, NH>(fa, wp, kn, 0);
+      if (b == NBO - 1) {
+        load_w32_pair<NBO, NH>(fb, wp, kn, NH);
+        bn = split8<3>(xlo, xhi);
+        xlo = xl[(2 * k2) * 64];
+        xhi = xl[(2 * k2 + 1) * 64];
+      }
+      acc[b] = x9_block(acc[b], w, bc);
+      const bool loads = b == NH - 1 || b == NBO - 1;
+#pragma unroll
+      for (int g = 0; g < 9; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+        if (loads && g < 2 * NH) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
+        if (b == NBO - 1) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);  // the next block's pieces + the next step's activations
+        else __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);  // the next block's pieces
+      }
+      if (b == NBO - 1) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // the LDS reads of the activations
+      __builtin_amdgcn_sched_barrier(0);
+      w = wn;
+    }
+    bc = bn;
+  }
+}
+
 #define TILES 64
 #define SEG_F32 (32 * 8 * 256)       // floats of the fp32 segment [it 32][nb 8][lane][4]
 #define SEG_B16 (16 * 8 * 3 * 256)   // floats of the three-piece segment [k16 16][nb 8][piece 3][lane][8 bf16]
 
 // FORM 0: (a) fp32; 1: (b) nine products, packed pieces; 2: (c) nine products, pieces formed in registers; 3: calibration, 1,024
-// fp32 MFMAs from registers; 4: six products (bf16x6).  OWN: every wave streams its own copy of the segment (no L1 sharing).
+// fp32 MFMAs from registers; 4: six products (bf16x6); 5: (d) nine products, packed pieces, 16x16x32; 6: (e) the same, pieces formed in registers.  OWN: every wave streams its own copy of the segment (no L1 sharing).
 template <int FORM, bool OWN>
 __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0,
                                           float* out) {
@@ -43,6 +120,16 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
   for (int t = 0; t < TILES; ++t) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
+    if constexpr (FORM == 5 || FORM == 6) {
+      f32x4 a16[8][2][2];
+      zero_acc16<8>(a16);
+      if (FORM == 5) gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
+      else gemm_f32_x9_s16<8>(a16, w32 + (OWN ? wid * SEG_F32 : 0), X, 8, ln);
+#pragma unroll
+      for (int nb = 0; nb < 8; ++nb) s += (a16[nb][0][0][0] + a16[nb][0][1][1]) + (a16[nb][1][0][2] + a16[nb][1][1][3]);
+      X[(t & 31) * 64].x = 0.5f + 1e-9f * s;
+      continue;
+    }
     f32x16 acc[8];
     zero_acc<8>(acc);
     if (FORM == 0) {
@@ -69,6 +156,31 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
     X[(t & 31) * 64].x = 0.5f + 1e-9f * s;
   }
   out[blockIdx.x * 256 + threadIdx.x] = s;
+}
+
+// one wave, one tile: the GEMM of form (b), (d) or (e), its result written to the X slab by the form's own epilogue and copied out
+template <int FORM>
+__global__ __launch_bounds__(64) void chk(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0, float* out) {
+  __shared__ float4 slab[32 * 64];
+  const int lane = threadIdx.x;
+  float4* X = slab + lane;
+  for (int it = 0; it < 32; ++it) X[it * 64] = *reinterpret_cast<const float4*>(x0 + ((size_t)it * 64 + lane) * 4);
+  __syncthreads();
+  if constexpr (FORM == 5 || FORM == 6) {
+    f32x4 a16[8][2][2];
+    zero_acc16<8>(a16);
+    if (FORM == 5) gemm_bf16_s16<8>(a16, w16, X, 8, lane); else gemm_f32_x9_s16<8>(a16, w32, X, 8, lane);
+    __syncthreads();
+    store_act16<8>(a16, X, lane);
+  } else {
+    f32x16 acc[8];
+    zero_acc<8>(acc);
+    gemm_bf16<8, 3, true>(acc, w16, X, 16, lane);
+    __syncthreads();
+    store_act<8, 8, false>(acc, X);
+  }
+  __syncthreads();
+  for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out + ((size_t)it * 64 + lane) * 4) = X[it * 64];
 }
 
 static int g_grid = 256;
@@ -111,6 +223,65 @@ static float bf16_f32(unsigned short b) {
   return v;
 }
 
+// one fp32 segment [it 32][nb 8][lane][4] as its three bf16 pieces [k16 16][nb 8][piece 3][lane][8] (split_elem, rsn_pack.hip)
+static void pack_pieces(const float* h, unsigned short* hb) {
+  for (int kk = 0; kk < 16; ++kk)
+    for (int nb = 0; nb < 8; ++nb)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int e = 0; e < 8; ++e) {
+          const float v = h[((size_t)((2 * kk + (e >> 2)) * 8 + nb) * 64 + lane) * 4 + (e & 3)];
+          const unsigned short b1 = bf16_rne(v);
+          const float r1 = v - bf16_f32(b1);
+          const unsigned short b2 = bf16_rne(r1);
+          const float r2 = r1 - bf16_f32(b2);
+          const unsigned short b3 = bf16_rne(r2);
+          const size_t base = (size_t)(kk * 8 + nb) * 3 * 512 + (size_t)lane * 8 + e;
+          hb[base] = b1; hb[base + 512] = b2; hb[base + 1024] = b3;
+        }
+}
+
+// Forms (b) and (d) on integer operands: `wide` weights of 17 bits (three non-zero pieces) against activations in {0, +-1}, three
+// in four zero, or the reverse.  Every partial sum stays under 2^24, so any order of accumulation gives the integer result.
+static bool check_forms(bool wide_w, float* w32, float* w16, float* x0, float* out) {
+  std::vector<float> hw(SEG_F32), hx(32 * 64 * 4);
+  auto big = [](size_t i) { return (float)((long long)((i * 2654435761u + 12345u) % 262143u) - 131071); };
+  auto small = [](size_t i) { const unsigned r = (unsigned)(i * 2246822519u) >> 13; return (r & 12u) ? 0.0f : ((r & 1u) ? 1.0f : -1.0f); };
+  for (size_t i = 0; i < hw.size(); ++i) hw[i] = wide_w ? big(i) : small(i);
+  for (size_t i = 0; i < hx.size(); ++i) hx[i] = wide_w ? small(i + 7) : big(i + 7);
+  std::vector<unsigned short> hb((size_t)SEG_B16 * 2);
+  pack_pieces(hw.data(), hb.data());
+  CK(hipMemcpy(w32, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
+  CK(hipMemcpy(w16, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+  CK(hipMemcpy(x0, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
+  std::vector<float> ob(hx.size()), od(hx.size()), oe(hx.size());
+  hipLaunchKernelGGL((chk<1>), dim3(1), dim3(64), 0, 0, w32, w16, x0, out);
+  CK(hipMemcpy(ob.data(), out, ob.size() * 4, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL((chk<5>), dim3(1), dim3(64), 0, 0, w32, w16, x0, out);
+  CK(hipMemcpy(od.data(), out, od.size() * 4, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL((chk<6>), dim3(1), dim3(64), 0, 0, w32, w16, x0, out);
+  CK(hipMemcpy(oe.data(), out, oe.size() * 4, hipMemcpyDeviceToHost));
+  size_t bad_b = 0, bad_d = 0, bad_e = 0, differ = 0;
+  for (int it = 0; it < 32; ++it)      // X[it][lane][c]: row 8 it + 4 (lane >> 5) + c of point lane & 31
+    for (int lane = 0; lane < 64; ++lane)
+      for (int c = 0; c < 4; ++c) {
+        const int row = 8 * it + 4 * (lane >> 5) + c, p = lane & 31;
+        long long ref = 0;
+        for (int ki = 0; ki < 32; ++ki)
+          for (int kh = 0; kh < 2; ++kh)
+            for (int kc = 0; kc < 4; ++kc)
+              ref += (long long)hw[((size_t)(ki * 8 + row / 32) * 64 + (row % 32) + 32 * kh) * 4 + kc] *
+                     (long long)hx[((size_t)ki * 64 + p + 32 * kh) * 4 + kc];
+        const size_t o = ((size_t)it * 64 + lane) * 4 + c;
+        bad_b += ob[o] != (float)ref;
+        bad_d += od[o] != (float)ref;
+        bad_e += oe[o] != (float)ref;
+        differ += ob[o] != od[o] || od[o] != oe[o];
+      }
+  printf("check, %s: (b) wrong %zu, (d) wrong %zu, (e) wrong %zu, not all equal %zu of %zu\n",
+         wide_w ? "17-bit weights x 0/+-1 activations" : "0/+-1 weights x 17-bit activations", bad_b, bad_d, bad_e, differ, ob.size());
+  return bad_b == 0 && bad_d == 0 && bad_e == 0 && differ == 0;
+}
+
 int main() {
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, 0));
@@ -120,25 +291,13 @@ int main() {
   CK(hipMalloc(&w16, 4ull * SEG_B16 * 4));
   CK(hipMalloc(&x0, 4ull * 32 * 64 * 4 * 4));
   CK(hipMalloc(&out, (size_t)g_grid * 256 * 4));
+  if (!check_forms(true, w32, w16, x0, out) || !check_forms(false, w32, w16, x0, out)) { printf("check FAILED\n"); return 1; }
   std::vector<float> h(4ull * SEG_F32);
   for (size_t i = 0; i < h.size(); ++i) h[i] = 1e-3f * (float)((i * 2654435761u) % 2001) - 1.0f;
   CK(hipMemcpy(w32, h.data(), h.size() * 4, hipMemcpyHostToDevice));
   // the three pieces of the same weights in hT_x's layout (split_elem, rsn_pack.hip)
   std::vector<unsigned short> hb(4ull * SEG_B16 * 2);
-  for (int c = 0; c < 4; ++c)
-    for (int kk = 0; kk < 16; ++kk)
-      for (int nb = 0; nb < 8; ++nb)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < 8; ++e) {
-            const float v = h[(size_t)c * SEG_F32 + ((size_t)((2 * kk + (e >> 2)) * 8 + nb) * 64 + lane) * 4 + (e & 3)];
-            const unsigned short b1 = bf16_rne(v);
-            const float r1 = v - bf16_f32(b1);
-            const unsigned short b2 = bf16_rne(r1);
-            const float r2 = r1 - bf16_f32(b2);
-            const unsigned short b3 = bf16_rne(r2);
-            const size_t base = (size_t)c * SEG_B16 * 2 + (size_t)(kk * 8 + nb) * 3 * 512 + (size_t)lane * 8 + e;
-            hb[base] = b1; hb[base + 512] = b2; hb[base + 1024] = b3;
-          }
+  for (int c = 0; c < 4; ++c) pack_pieces(h.data() + (size_t)c * SEG_F32, hb.data() + (size_t)c * SEG_B16 * 2);
   CK(hipMemcpy(w16, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
   // activations: a masked gradient row -- about half the entries zero, the rest of order one
   std::vector<float> hx(4ull * 32 * 64 * 4);
@@ -157,12 +316,25 @@ int main() {
   run<4, false>("    six products (gemm_bf16<8, 3>)", w32, w16, x0, out, cal, a0);
   const double a1 = run<0, false>("(a) again", w32, w16, x0, out, cal, a0);
   const double b1 = run<1, false>("(b) again", w32, w16, x0, out, cal, a0);
+  const double d0 = run<5, false>("(d) nine products, packed pieces, 16x16x32", w32, w16, x0, out, cal, a0);
+  const double b2 = run<1, false>("(b) again", w32, w16, x0, out, cal, a0);
+  const double d1 = run<5, false>("(d) again", w32, w16, x0, out, cal, a0);
+  run<6, false>("(e) nine products, pieces in registers, 16x16x32", w32, w16, x0, out, cal, a0);
+  run<2, false>("(c) again", w32, w16, x0, out, cal, a0);
+  run<6, false>("(e) again", w32, w16, x0, out, cal, a0);
   printf("-- every wave on its own copy of the segment (no L1 sharing between the waves)\n");
   const double a2 = run<0, true>("(a) fp32: gemm<8, 8, PF2>", w32, w16, x0, out, cal, 0.0);
   run<1, true>("(b) nine products, packed pieces (gemm_bf16 FULL)", w32, w16, x0, out, cal, a2);
   run<2, true>("(c) nine products, pieces in registers (gemm_f32_x9)", w32, w16, x0, out, cal, a2);
   run<4, true>("    six products (gemm_bf16<8, 3>)", w32, w16, x0, out, cal, a2);
+  run<5, true>("(d) nine products, packed pieces, 16x16x32", w32, w16, x0, out, cal, a2);
+  run<6, true>("(e) nine products, pieces in registers, 16x16x32", w32, w16, x0, out, cal, a2);
   const double ratio = (b0 + b1) / (a0 + a1);
   printf("go / no-go: (b) / (a) wall time = %.3f (go at <= 0.850): %s\n", ratio, ratio <= 0.85 ? "GO" : "NO-GO");
+  // the 16x16x32 shape: predicted step gain = (t_b - t_d) per tile x 7 GEMM equivalents x 16 tiles x 2 launches x 0.65 (the part of
+  // its prediction that the nine-product change realised, profiles/normals_x9.json)
+  const double gain_ms = ((b1 + b2) - (d0 + d1)) / 2.0 / TILES * 7.0 * 16.0 * 2.0 * 0.65;
+  printf("shape go / no-go: (d) / (b) wall time = %.3f, predicted step gain %.3f ms (go at >= 0.300): %s\n", (d0 + d1) / (b1 + b2), gain_ms,
+         gain_ms >= 0.3 ? "GO" : "NO-GO");
   return 0;
 }
