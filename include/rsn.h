@@ -641,7 +641,9 @@ int rsn_reflect_combine_backward(int32_t n_rays_max, const int32_t* n_masked, co
  * sum w max(0, n_dot_d)^2.  losses8 (device, overwritten) receives the UNSCALED terms; the gradient outputs
  * (w.r.t. rgb4, pred_normals2, n_dot_d2; all other inputs are constants of the loss) are scaled by coef8
  * (host array, the model's loss_coefficients incl. the 50-step warm-up of reflect_sampling_nerf_pipeline.py:79-91).
- * The *4 / *2 arguments are HOST arrays of device pointers (coarse, fine order). */
+ * The *4 / *2 arguments are HOST arrays of device pointers (coarse, fine order).
+ * losses8 is bit-reproducible: the blocks' partial sums go to a buffer the library owns (one per device) and are added in
+ * fp64 in a fixed order by a second launch, so two calls on different streams of one device must not overlap. */
 int rsn_loss_forward_backward(int32_t n_rays, int32_t s_coarse, int32_t s_fine, const float* image,
                               const float* const* rgb4, const float* const* weights2, const float* const* normals2,
                               const float* const* pred_normals2, const float* const* n_dot_d2, const float* coef8,

@@ -20,24 +20,30 @@ struct LossArgs {
   const float* pn[2];                       // pred_normals_* [R,S,3]
   const float* ndd[2];                      // n_dot_d_* [R,S]
   float coef[8];
-  float* losses;                            // [8], accumulated (zeroed by the launcher)
+  float* losses;                            // [8], written by rsn_loss_reduce_kernel
   float* g_rgb[4];                          // [R,3]
   float* g_pn[2];                           // [R,S,3]
   float* g_ndd[2];                          // [R,S]
 };
 
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+__device__ __forceinline__ double block_sum_256d(double v, double* sh) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) sh[wid] = v;
   __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
+// Per-block partial sums of the eight terms, owned by the library (one copy per device): the C ABI of rsn_loss_forward_backward
+// has no workspace argument.  Written by every block of rsn_loss_kernel, read by rsn_loss_reduce_kernel in the same stream; two
+// calls of rsn_loss_forward_backward on different streams of one device must not overlap.
+#define LOSS_MAX_BLOCKS 1024
+__device__ double rsn_loss_partials[LOSS_MAX_BLOCKS * 8];
+
 __global__ __launch_bounds__(256) void rsn_loss_kernel(const LossArgs a) {
-  __shared__ float sh[4];
+  __shared__ double shd[4];
   float part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -72,11 +78,24 @@ __global__ __launch_bounds__(256) void rsn_loss_kernel(const LossArgs a) {
       if (a.g_ndd[lv]) a.g_ndd[lv][e] = a.coef[6 + lv] * w * (2.0f * nd);
     }
   }
+  // this block's eight partial sums, in fp64 at a fixed position: rsn_loss_reduce_kernel adds the blocks' rows in a fixed order
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    float v = block_sum_256(part[k], sh);
-    if (k < 4) v *= inv;
-    if (threadIdx.x == 0) atomicAdd(&a.losses[k], v);
+    const double v = block_sum_256d((double)part[k], shd);
+    if (threadIdx.x == 0) rsn_loss_partials[blockIdx.x * 8 + k] = v;
+  }
+}
+
+// One workgroup after rsn_loss_kernel (the launch boundary is the hand-off): losses[k] = sum over the blocks' rows, each thread
+// over rows t, t + 256, ... in ascending order, then the fixed tree of block_sum_256d; one rounding to fp32.  Bit-reproducible.
+__global__ __launch_bounds__(256) void rsn_loss_reduce_kernel(int blocks, double inv, float* losses) {
+  __shared__ double shd[4];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += 256) s += rsn_loss_partials[b * 8 + k];
+    const double v = block_sum_256d(s, shd);
+    if (threadIdx.x == 0) losses[k] = (float)(k < 4 ? v * inv : v);
   }
 }
 
@@ -101,11 +120,12 @@ extern "C" int rsn_loss_forward_backward(int32_t n_rays, int32_t s_coarse, int32
   }
   for (int k = 0; k < 8; ++k) a.coef[k] = coef8[k];
   hipStream_t st = (hipStream_t)stream;
-  RSN_HIP(hipMemsetAsync(losses8, 0, 8 * sizeof(float), st));
   const long long work = (long long)n_rays * (s_coarse > s_fine ? s_coarse : s_fine);
   long long blocks = (work + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
+  if (blocks > LOSS_MAX_BLOCKS) blocks = LOSS_MAX_BLOCKS;
   hipLaunchKernelGGL(rsn_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  RSN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rsn_loss_reduce_kernel, dim3(1), dim3(256), 0, st, (int)blocks, 1.0 / (double)((long long)n_rays * 3), losses8);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

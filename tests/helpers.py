@@ -129,3 +129,26 @@ def _poisoned(bufs):
         it, pattern = _POISON[t.dtype]
         t.view(it).fill_(pattern)
     return bufs
+
+
+def _is_poison(t):
+    """bool [rows]: every element of the row still holds the fill pattern."""
+    it, pattern = _POISON[t.dtype]
+    return (t.view(it).reshape(t.shape[0], -1) == pattern).all(dim=1).cpu()
+
+
+def _has_poison(t):
+    it, pattern = _POISON[t.dtype]
+    return (t.view(it).reshape(t.shape[0], -1) == pattern).any(dim=1).cpu()
+
+
+def _check_count(label, bufs, live):
+    """Rows < live written (no element holds the fill pattern), rows >= live untouched (every element does)."""
+    for k, t in bufs.items():
+        assert not bool(_has_poison(t)[:live].any()), f"{label} {k}: a live row was not written"
+        behind = ~_is_poison(t)[live:]
+        assert not bool(behind.any()), f"{label} {k}: rows {(behind.nonzero().flatten() + live).tolist()[:8]} behind the count were written"
+
+
+def _count(n, dev):
+    return torch.tensor([n], dtype=torch.int32, device=dev)

@@ -45,6 +45,8 @@ def make_field(layers, width, dev, seed=0, bias_shift=0.0):
 @pytest.mark.parametrize("kind,tan,near,far", [("uniform", 1.0, 2.0, 6.0), ("reciprocal", 0.25, 0.0, 256.0)])
 @pytest.mark.parametrize("S", [1, 24, 128])
 def test_spaced_sampler(dev, kind, tan, near, far, S):
+    """The wrapper against the float32 oracle at one near / far for all rays.  The sharper checks -- fp64, per-ray near / far, device-side
+    counts, the stride loop -- live in tests/test_samplers_gpu.py."""
     R = 37
     nears, fars = torch.full((R, 1), near), torch.full((R, 1), far)
     g = torch.Generator().manual_seed(S)
@@ -61,6 +63,9 @@ def test_spaced_sampler(dev, kind, tan, near, far, S):
 
 @pytest.mark.parametrize("S_in,S_out", [(16, 16), (128, 128), (64, 33), (7, 130)])
 def test_pdf_sampler(dev, S_in, S_out):
+    """The wrapper against the float32 oracle under flat bounds.  The sharper checks -- fp64, bounds scaled by the inverse CDF's slope,
+    flat CDF runs, 1024 input bins, both spacing kinds with per-ray far -- live in tests/test_samplers_gpu.py; what the flat bounds
+    make of the same planted faults is in tests/test_samplers_cpu.py."""
     R = 29
     g = torch.Generator().manual_seed(S_in * 1000 + S_out)
     w = torch.rand(R, S_in, 1, generator=g) ** 4
@@ -1062,7 +1067,9 @@ def test_fused_loss_matches_torch_formulas(dev):
 
 def test_fused_radam_matches_torch_optim(dev):
     """rsn_radam_step against torch.optim.RAdam (lr 1e-3, eps 1e-15: reference config.py:50-53) over 12 steps, i.e.
-    across the rho_t > 5 switch (step 6), with a parameter that never receives a gradient."""
+    across the rho_t > 5 switch (step 6), with a parameter that never receives a gradient.  The sharper check -- one step at a time
+    against float64, every size and both branches -- lives in tests/test_radam_gpu.py; twelve steps at 2e-6 accept a rectification
+    factor that is off by 1e-3 (tests/test_radam_cpu.py)."""
     g = torch.Generator().manual_seed(3)
     shapes = [(17, 9), (33,), (256, 99), (1,)]
     ref_p = [torch.nn.Parameter(torch.randn(*s, generator=g)) for s in shapes] + [torch.nn.Parameter(torch.ones(5))]

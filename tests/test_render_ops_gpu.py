@@ -15,7 +15,7 @@ from reflect_sampling_nerf_amd import _abi, ops, train_graph
 from reflect_sampling_nerf_amd._abi import CompositeBwdIO, CompositeIO, ReflectIO, check, ptr
 from reflect_sampling_nerf_amd.train_ops import _ptr_array
 from tests import render_reference as rr
-from tests.helpers import _POISON, _poisoned, default_dtype, max_abs
+from tests.helpers import _check_count, _count, _is_poison, _poisoned, default_dtype, max_abs
 
 pytestmark = pytest.mark.gpu
 
@@ -88,34 +88,11 @@ def _check_chain(label, name, got, ref, n, keep=None, absolute=False):
     assert worst <= 1.0, f"{label} {name}: {worst * n:.2f} x 2^-24 relative > {n}"
 
 
-def _is_poison(t):
-    """bool [rows]: every element of the row still holds the fill pattern."""
-    it, pattern = _POISON[t.dtype]
-    return (t.view(it).reshape(t.shape[0], -1) == pattern).all(dim=1).cpu()
-
-
-def _has_poison(t):
-    it, pattern = _POISON[t.dtype]
-    return (t.view(it).reshape(t.shape[0], -1) == pattern).any(dim=1).cpu()
-
-
-def _check_count(label, bufs, live):
-    """Rows < live written (no element holds the fill pattern), rows >= live untouched (every element does)."""
-    for k, t in bufs.items():
-        assert not bool(_has_poison(t)[:live].any()), f"{label} {k}: a live row was not written"
-        behind = ~_is_poison(t)[live:]
-        assert not bool(behind.any()), f"{label} {k}: rows {(behind.nonzero().flatten() + live).tolist()[:8]} behind the count were written"
-
-
 def _exclusion(label, what, near, cap, R):
     n = int(near.sum())
     print(f"EXCLUDED {label}: {n} of {R} rays ({what}), cap {cap * R:.2f}")
     assert n <= cap * R, f"{label}: {n} rays excluded ({what}), cap {cap * R:.2f}"
     return ~near
-
-
-def _count(n, dev):
-    return torch.tensor([n], dtype=torch.int32, device=dev)
 
 
 # ------------------------------------------------------------------------------------------------------------- compositing
@@ -502,10 +479,14 @@ def test_loss_rays_forward_backward_match_fp64(dev, R):
     _check_chain(f"loss_rays_backward R{R}", "g_ori_ray2[0]", g_ori[0], torch.full((R,), c32[6] * rr.LOSS_UPSTREAM[6]), 1)
 
 
-@pytest.mark.parametrize("R,Sc,Sf", [(5, 3, 7), (300, 130, 33)])
+@pytest.mark.parametrize("R,Sc,Sf", [(5, 3, 7), (300, 130, 33), (2049, 128, 2)])
 def test_loss_scale_grads_on_fused_loss_buffers(dev, R, Sc, Sf):
     """rsn_loss_forward_backward's terms and gradients against fp64 at ragged shapes, then rsn_loss_scale_grads on the buffers it wrote:
-    one rounding per element."""
+    one rounding per element.  (2049, 128, 2): 262,272 work items against the grid's cap of 1024 blocks x 256 threads, so that the
+    stride loop of both kernels runs, with the three colour channels wider than the fine level.
+
+    losses8 is a fixed-order fp64 sum of the blocks' partial sums, rounded once (rsn_loss_reduce_kernel), so it holds the recorded
+    bound at 1024 blocks as at one, and a second call repeats it bit for bit."""
     lib = _abi.load_library()
     g = torch.Generator().manual_seed(R)
     rand = lambda *s: torch.rand(*s, generator=g)  # noqa: E731
@@ -522,7 +503,12 @@ def test_loss_scale_grads_on_fused_loss_buffers(dev, R, Sc, Sf):
     check(lib.rsn_loss_forward_backward(R, Sc, Sf, ptr(image.to(dev)), _ptr_array(d_rgb), _ptr_array(d_w), _ptr_array(d_nrm),
                                         _ptr_array(d_pn), _ptr_array(d_ndd), (C.c_float * 8)(*rr.LOSS_COEF), ptr(losses),
                                         _ptr_array(g_rgb), _ptr_array(g_pn), _ptr_array(g_ndd), ops._stream()))
+    losses_again = _poisoned({"l": torch.empty(8, device=dev)})["l"]
+    check(lib.rsn_loss_forward_backward(R, Sc, Sf, ptr(image.to(dev)), _ptr_array(d_rgb), _ptr_array(d_w), _ptr_array(d_nrm),
+                                        _ptr_array(d_pn), _ptr_array(d_ndd), (C.c_float * 8)(*rr.LOSS_COEF), ptr(losses_again),
+                                        _ptr_array(g_rgb), _ptr_array(g_pn), _ptr_array(g_ndd), ops._stream()))
     torch.cuda.synchronize()
+    assert torch.equal(losses.view(torch.int32), losses_again.view(torch.int32)), "losses8 must repeat bit for bit"
     label = f"loss_forward_backward R{R}"
     c = [float(np.float32(v)) for v in rr.LOSS_COEF]
     with default_dtype(torch.float64):
