@@ -1,6 +1,7 @@
 // Shared declarations of librsn_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -68,8 +69,9 @@ struct RsnPackedLayout {
   size_t h_enc0, h_enc_skip, h_bh, h_mid_sh, h_mid_x, h_rgb;
   size_t hT_x[RSN_MAX_TRUNK_LAYERS];  // split-bf16 copies of the transposed segments (training sweeps)
   size_t hT_enc0, hT_enc_skip, hT_bh, hT_mid_x, hT_rgb;
-  // RSN_MMA_F32_FOLDED writes hT_x[1 .. L-2], hT_enc_skip and hT_enc0 too (and nothing else of the h* / hT_* regions): the loop
-  // GEMMs of the analytic-normal sweep of its training forward read them with all nine piece products (gemm_bf16_s16).
+  // RSN_MMA_F32_FOLDED writes hT_x[1 .. L-2], hT_enc_skip and hT_enc0 too (and, of the other h* / hT_* regions, only hT_last
+  // below): the loop GEMMs of the analytic-normal sweep of its training forward read them with all nine piece products
+  // (gemm_bf16_s16), and so do the W x W GEMMs of its backward sweep (rsn_field_bwd.hip, stage 4).
   // RSN_MMA_F32 writes none: its training kernel forms the same pieces from the wT_* segments in registers (gemm_f32_x9_s16)
   // RSN_MMA_F32_FOLDED with num_layers >= 2 only (0 = absent): V = (x part of layer L-1)^T diag(w_density), one rounding per
   // element (rsn_seed_product), as three bf16 pieces in the layout and K order of hT_x[L-1] -- the first GEMM of the
@@ -91,6 +93,12 @@ struct RsnPackedLayout {
   // RSN_MMA_BF16X6 at width 256 (rsn_field_x6_train.hip): the same stream with every fragment as THREE 1 KiB pieces -- the lo, mid
   // and hi bf16 parts of the fp32 weights, in that order (small products first); q_pf = 3 and every group count above is x 3
   int q_pf;                           // 1 KiB pieces per fragment of q_stream: 1 (plain bf16) or 3 (split-bf16)
+  // RSN_MMA_F32_FOLDED with num_layers >= 2 only (0 = absent): the three bf16 pieces of wT_x[L-1] itself, whose place hT_seed has
+  // taken, for the first trunk GEMM of the folded backward sweep (gemm_bf16_s16).  They live in the hT_bh region, which the folded
+  // mode neither writes nor reads otherwise and which holds nb * 2 + 2 K = 16 steps against the nb * 2 of an hT_x segment: no offset
+  // or size moves.  32 bits in the four bytes that padded q_pf (static_assert below): the struct is passed to every field kernel,
+  // and this way no kernel's arguments move
+  unsigned hT_last;
   // RSN_MMA_F32_FOLDED only (0 = absent), appended behind everything above: the bottleneck folded into mlp_mid's x part.
   //   fold_wc / fold_bc  W_c = W_mid[:, 34:] W_b as a dense [mid_width, param_width] tensor and b_c [mid_width] (rsn_fold_kernel
   //                      writes them, the pack jobs of the three segments below read them like parameters)
@@ -99,6 +107,9 @@ struct RsnPackedLayout {
   size_t fold_wc, fold_bc, w_fold, b_fold, wT_fold;
   size_t total;                       // floats
 };
+static_assert(offsetof(RsnPackedLayout, fold_wc) == offsetof(RsnPackedLayout, hT_last) + 4 &&
+                  offsetof(RsnPackedLayout, hT_last) == offsetof(RsnPackedLayout, q_pf) + 4,
+              "hT_last fills the padding behind q_pf");
 #define RSN_RING_GROUP_FRAGS 16   // 1 KiB weight fragments per ring group
 #define RSN_RING_MAX_LAYERS 10   // trunk depth the ring kernels' LDS bias table is sized for
 // the TRAINING kernels on the LDS weight ring (rsn_field_bf16_train.hip: plain bf16; rsn_field_x6_train.hip: split-bf16) serve

@@ -125,19 +125,43 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
       store_masked_bits<NB, SBF>(acc, X, mb, h, rb_epi(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));
     }
     // ---------------- stage 4: trunk, layers L-1 .. 1 -----------------
+    // FOLD: the W x W GEMMs run on the bf16 MFMAs as all nine products of three bf16 pieces a side, on the 16x16x32 shape, from the
+    // packed pieces the analytic-normal sweep of the training forward reads (rsn_field_kernel.h; hT_last: those of layer L-1):
+    // exact fp32 products, another order of the fp32 accumulation.  Stages 1 to 3 left the slab in its standard layout, which is
+    // what that loop reads.  A lane reads and writes float4 of other lanes' slots there (in order within the wave: no barrier), so
+    // the saved rows leave for the rows of the two points it reads (rb16) and the mask words are those of the two it writes.
+    // The two encoded-input GEMMs stay on the fp32 loop (they read the same slab): on the nine-product loop d_input missed the rule
+    // of tests/test_layer_gemms_gpu.py in two cases.
     f32x16 eacc[4];
     zero_acc<4>(eacc);
+    auto rb16 = [&](float* base, long long elem, int row_elems) {
+      return rowbuf<false>(base, elem, rows, row_elems, ln & 15, (ln >> 4) & 1);
+    };
+    auto bits16_at = [&](int l, int ph) -> const unsigned* {  // the old lane (ln & 15) + 16 ph + 32 ((ln >> 4) & 1)
+      const long long q = p0 + (ln & 15) + 16 * ph, qc = q < n_points ? q : n_points - 1;
+      return a.saved.relu_bits + ((((long long)l * (a.act_stride / W)) + qc) * 2 + ((ln >> 4) & 1)) * (NB / 2 > 2 ? NB / 2 : 2);
+    };
 #pragma unroll 1
     for (int l = P.num_layers - 1; l >= 1; --l) {
       if (a.need_input_grad && l == P.skip_layer)
         gemm_mode<MODE, 4, 4, true>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, NB * 4, ln);
-      const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      f32x16 acc[NB];
-      zero_acc<NB>(acc);
-      gemm_mode<MODE, NB, NB, true>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln,
-                          rb_loop(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));  // reads (and keeps) dy[l]
-      store_masked_bits<NB, SBF>(acc, X, mb, h, rb_epi(a.gout.dy, (long long)(l - 1) * a.act_stride + p0 * W, W));
+      if constexpr (FOLD) {
+        const ReluBits<NB> mb[2] = {load_relu_bits<NB>(bits16_at(l - 1, 0)), load_relu_bits<NB>(bits16_at(l - 1, 1))};
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 acc[NB][2][2];
+        zero_acc16<NB>(acc);
+        gemm_bf16_s16<NB>(acc, pk + (l == P.num_layers - 1 ? (size_t)P.L.hT_last : P.L.hT_x[l]), X, NB, ln,
+                          rb16(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));  // reads (and keeps) dy[l]
+        store_masked_bits16<NB>(acc, X, mb, ln);
+      } else {
+        const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc[NB];
+        zero_acc<NB>(acc);
+        gemm_mode<MODE, NB, NB, true>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, NB * 4, ln,
+                            rb_loop(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));  // reads (and keeps) dy[l]
+        store_masked_bits<NB, SBF>(acc, X, mb, h, rb_epi(a.gout.dy, (long long)(l - 1) * a.act_stride + p0 * W, W));
+      }
     }
     if (LOOPST && !a.need_input_grad) {  // dy[0] has no GEMM behind it on this path: its rows leave here
       const RowBuf r0 = rb_loop(a.gout.dy, p0 * W, W);

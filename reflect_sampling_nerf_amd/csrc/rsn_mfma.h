@@ -812,11 +812,29 @@ __device__ __forceinline__ void load_w16s(bf16x8 (&w)[NQ][2][3], const WBuf& wp,
       }
 }
 
+// The saved rows of the 16-shape (gemm_run2's `save`, see there): the two float4 a lane reads of old lane ol + 16 ph, K-iterations
+// `it` and it + 1 of that point's row.  `b` is rowbuf(.., m = L & 15, h = (L >> 4) & 1): the row of point half 1 lies 16 rows on.
+// `it` differs between the lanes (kh), so what must not be stored (K-iterations past the row, `live` off) gets an offset outside the
+// descriptor's range, where the hardware drops it, instead of a branch: one control path.  Offsets in the vector offset only.
+__device__ __forceinline__ void sv_put16(const float*, int, int, bool, const float4, const float4) {}
+__device__ __forceinline__ void sv_put16(const RowBuf& b, int it, int ph, bool live, const float4 lo, const float4 hi) {
+  const unsigned at = b.voff + (unsigned)ph * 16u * b.lim + (unsigned)it * 32u;
+  const unsigned o0 = (live && (unsigned)it * 32u < b.lim) ? at : 0x80000000u;
+  const unsigned o1 = (live && (unsigned)it * 32u + 32u < b.lim) ? at + 32u : 0x80000000u;
+  const u32x4 v0 = {__float_as_uint(lo.x), __float_as_uint(lo.y), __float_as_uint(lo.z), __float_as_uint(lo.w)};
+  const u32x4 v1 = {__float_as_uint(hi.x), __float_as_uint(hi.y), __float_as_uint(hi.z), __float_as_uint(hi.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(v0, b.r, o0, 0, RSN_SAVED_ROW_AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(v1, b.r, o1, 0, RSN_SAVED_ROW_AUX);
+}
+
 // Packed pieces (hT_* segment, [k16][NBO][piece][lane][8 bf16]).  Fragment buffers of a quarter of the blocks (the 96 registers of
 // gemm_bf16's two half-step buffers); the next step's activations are split under the first two chunks' MFMAs, one point half each.
-template <int NBO>
+// `save` (optional, the backward sweep): every float4 of the slab this GEMM reads leaves once for its saved row -- step 0's ahead of
+// the loop, step s + 1's from the registers that are split under the chunks 0 and 1 of step s (two stores a chunk, behind that
+// chunk's fragment loads in the vmcnt order).
+template <int NBO, class SV = const float*>
 __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ wseg, const float4* xl, int n_k32,
-                                              int lane) {
+                                              int lane, SV save = nullptr) {
   static_assert(NBO % 2 == 0, "an even number of fragment buffers' worth of blocks");
   constexpr int NQ = NBO >= 4 ? NBO / 4 : 1, NC = NBO / NQ;  // blocks per fragment buffer, chunks per K step (even)
   const Lane16 g = lane16(lane);
@@ -825,7 +843,17 @@ __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const flo
   const float4* xb = xl - lane + g.ol + g.kh * 128;  // LDS iterations 4 s + 2 kh, + 1; point half 1 is 16 float4 on
   bf16x8 wa[NQ][2][3], wb[NQ][2][3];
   load_w16s<NQ>(wa, wp, 0, NBO, 0);
-  BSplit bc[2] = {split8<3>(xb[0], xb[64]), split8<3>(xb[16], xb[80])};
+  BSplit bc[2];
+  if (sv_on(save)) {  // step 0's four float4, kept for their rows
+    const float4 p0lo = xb[0], p0hi = xb[64], p1lo = xb[16], p1hi = xb[80];
+    bc[0] = split8<3>(p0lo, p0hi);
+    bc[1] = split8<3>(p1lo, p1hi);
+    sv_put16(save, 2 * g.kh, 0, true, p0lo, p0hi);
+    sv_put16(save, 2 * g.kh, 1, true, p1lo, p1hi);
+  } else {
+    bc[0] = split8<3>(xb[0], xb[64]);
+    bc[1] = split8<3>(xb[16], xb[80]);
+  }
   const int s1 = n_k32 > 1 ? 1 : 0;
   float4 x0lo = xb[4 * s1 * 64], x0hi = xb[(4 * s1 + 1) * 64], x1lo = xb[4 * s1 * 64 + 16], x1hi = xb[(4 * s1 + 1) * 64 + 16];
 #pragma unroll 1
@@ -840,6 +868,9 @@ __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const flo
       __builtin_amdgcn_sched_barrier(0);
       if (c == 0) bn[0] = split8<3>(x0lo, x0hi);
       if (c == 1) bn[1] = split8<3>(x1lo, x1hi);
+      // the registers hold step sn; in the last step that is this step again (the clamp), whose rows have left: not live
+      if (c == 0 && sv_on(save)) sv_put16(save, 4 * sn + 2 * g.kh, 0, s + 1 < n_k32, x0lo, x0hi);
+      if (c == 1 && sv_on(save)) sv_put16(save, 4 * sn + 2 * g.kh, 1, s + 1 < n_k32, x1lo, x1hi);
       if (c == NC - 1) {
         x0lo = xb[4 * s2 * 64]; x0hi = xb[(4 * s2 + 1) * 64];
         x1lo = xb[4 * s2 * 64 + 16]; x1hi = xb[(4 * s2 + 1) * 64 + 16];
@@ -849,6 +880,7 @@ __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const flo
       for (int m = 0; m < NQ * 36; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
         if (c < 2) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // the next step's pieces: an MFMA leaves 8 of its 16 cycles
+        if (c < 2 && sv_on(save) && (m == 8 || m == 20)) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // 1 row store
       }
       if (c == NC - 1) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // the LDS reads of the activations
       __builtin_amdgcn_sched_barrier(0);

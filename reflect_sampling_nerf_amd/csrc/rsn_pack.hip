@@ -147,6 +147,7 @@ int rsn_compute_layout(const rsn_field_desc* d, RsnPackedLayout* L) {
   off += (size_t)2 * L->nbm * 3 * blk;
   // the seed of the analytic-normal sweep in a slot RSN_MMA_F32_FOLDED leaves unused (see RsnPackedLayout)
   L->hT_seed = (d->mma_mode == RSN_MMA_F32_FOLDED && d->num_layers >= 2) ? L->hT_x[d->num_layers - 1] : 0;
+  L->hT_last = (d->mma_mode == RSN_MMA_F32_FOLDED && d->num_layers >= 2) ? (unsigned)L->hT_bh : 0u;  // pieces of wT_x[L-1] (see RsnPackedLayout)
   L->q_pf = 1;
   if ((d->mma_mode == RSN_MMA_BF16 || d->mma_mode == RSN_MMA_BF16X6) && d->width == 256) {
     // 16x32 fragments: enc 4 x 16, x 8 x 16, heads 8 x 2, bottleneck 8 x 16, mid SH 2 x 8, mid x 8 x 8, rgb 4 x 4; split-bf16:
@@ -640,6 +641,7 @@ int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed
     if (L.hT_seed != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_seed, L.v_density);
     if (d->mma_mode == RSN_MMA_F32_FOLDED) {
       for (int l = 1; l + 1 < n_layers; ++l) split(L.wT_x[l], NB * 4, NB, L.hT_x[l]);
+      if (L.hT_last != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_last);  // the backward sweep's first trunk GEMM
       if (skip >= 1) split(L.wT_enc_skip, NB * 4, 4, L.hT_enc_skip);
       split(L.wT_enc0, NB * 4, 4, L.hT_enc0);
     }

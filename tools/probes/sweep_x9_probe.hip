@@ -10,6 +10,10 @@
 //       offset), 4,608 MFMAs of 16 cycles into the same 32-point x 256-row tile per wave: the same MFMA cycles, another shape;
 //   (e) (d) with the weight pieces formed in registers from the fp32 segment (gemm_f32_x9_s16, the RSN_MMA_F32 kernel's form);
 // and, for scale, the six-product loop of the bf16x6 mode (gemm_bf16<8, 3>).
+// The backward sweep runs the same GEMMs and keeps, per GEMM, the 32 KiB of layer-gradient rows it reads in a row-major
+// [points, 256] buffer.  Three more forms for it: (a) with the stores in its K loop (gemm_run2's saver, what that sweep ran), (d)
+// with them in its K loop (gemm_bf16_s16's saver, checked first on the integer operands: result, rows and rows past the valid
+// ones), and (d) with the result rows stored from the epilogue; the go / no-go is the better placement against (a) with its stores.
 // Before anything is timed, (b) and (d) run one tile each on integer operands whose every sum is exact in fp32 (17-bit weights
 // against 0 / +-1 activations, then the reverse) and their X slabs are compared with each other and with the host's integer sums.
 // The kernel's real grid: one workgroup of four waves per CU on every CU at once (clock and power effects show), each wave on its
@@ -104,12 +108,35 @@ __device__ __forceinline__ void gemm_f32_x9(f32x16 (&acc)[NBO], const float* __r
 #define TILES 64
 #define SEG_F32 (32 * 8 * 256)       // floats of the fp32 segment [it 32][nb 8][lane][4]
 #define SEG_B16 (16 * 8 * 3 * 256)   // floats of the three-piece segment [k16 16][nb 8][piece 3][lane][8 bf16]
+#define ROW_SLOTS 16                 // saved-row tiles per wave, walked round: 1,024 waves x 16 x 32 KiB = 512 MiB, beyond every cache
+
+// The backward sweep's GEMMs keep the rows they read (forms 7 to 9): the epilogue variant of the 16-shape, every result float4 to
+// its row (the float4 store_masked_bits16 writes to the slab: K-iteration 4 nb + 2 rh + kh of old lane ol + 16 ph) -- a burst of 32
+// stores behind the K loop.  `b`: rowbuf(.., m = L & 15, h = (L >> 4) & 1).
+template <int NBO>
+__device__ __forceinline__ void store_rows16(const f32x4 (&acc)[NBO][2][2], const RowBuf& b, int lane) {
+  const unsigned at = b.voff + (unsigned)(lane >> 5) * 32u;
+#pragma unroll
+  for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+    for (int nb = 0; nb < NBO; ++nb)
+#pragma unroll
+      for (int rh = 0; rh < 2; ++rh) {
+        const f32x4& a = acc[nb][rh][ph];
+        const u32x4 o = {__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])};
+        __builtin_amdgcn_raw_buffer_store_b128(o, b.r, at + (unsigned)ph * 16u * b.lim + (unsigned)((nb * 4 + 2 * rh) * 32), 0,
+                                               RSN_SAVED_ROW_AUX);
+      }
+}
 
 // FORM 0: (a) fp32; 1: (b) nine products, packed pieces; 2: (c) nine products, pieces formed in registers; 3: calibration, 1,024
-// fp32 MFMAs from registers; 4: six products (bf16x6); 5: (d) nine products, packed pieces, 16x16x32; 6: (e) the same, pieces formed in registers.  OWN: every wave streams its own copy of the segment (no L1 sharing).
+// fp32 MFMAs from registers; 4: six products (bf16x6); 5: (d) nine products, packed pieces, 16x16x32; 6: (e) the same, pieces formed in registers;
+// 7: (d) keeping the rows it reads, stores in the K loop (gemm_bf16_s16's saver); 8: (a) keeping them, stores in the K loop (gemm_run2's
+// saver: what the backward sweep runs); 9: (d) with the result rows stored from the epilogue (store_rows16).
+// OWN: every wave streams its own copy of the segment (no L1 sharing).
 template <int FORM, bool OWN>
 __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0,
-                                          float* out) {
+                                          float* out, float* rowsbuf = nullptr) {
   extern __shared__ float4 smem[];  // 32 KiB slab per wave, padded so that one workgroup fills the CU
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float4* X = smem + wid * 32 * 64 + lane;
@@ -120,10 +147,17 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
   for (int t = 0; t < TILES; ++t) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
-    if constexpr (FORM == 5 || FORM == 6) {
+    // this tile's 32 rows of the row-major [points, 256] buffer (wave-uniform base)
+    const long long row0 = ((long long)(blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wid)) * ROW_SLOTS + (t % ROW_SLOTS)) * 32 * 256;
+    if constexpr (FORM == 5 || FORM == 6 || FORM == 7 || FORM == 9) {
       f32x4 a16[8][2][2];
       zero_acc16<8>(a16);
       if (FORM == 5) gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
+      else if (FORM == 7) gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 15, (ln >> 4) & 1));
+      else if (FORM == 9) {
+        gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
+        store_rows16<8>(a16, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 15, (ln >> 4) & 1), ln);
+      }
       else gemm_f32_x9_s16<8>(a16, w32 + (OWN ? wid * SEG_F32 : 0), X, 8, ln);
 #pragma unroll
       for (int nb = 0; nb < 8; ++nb) s += (a16[nb][0][0][0] + a16[nb][0][1][1]) + (a16[nb][1][0][2] + a16[nb][1][1][3]);
@@ -134,6 +168,8 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
     zero_acc<8>(acc);
     if (FORM == 0) {
       gemm<8, 8, true>(acc, w32 + (OWN ? wid * SEG_F32 : 0), X, 32, ln);
+    } else if (FORM == 8) {
+      gemm<8, 8, true>(acc, w32 + (OWN ? wid * SEG_F32 : 0), X, 32, ln, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 31, ln >> 5));
     } else if (FORM == 1) {
       gemm_bf16<8, 3, true>(acc, w16 + (OWN ? wid * SEG_B16 : 0), X, 16, ln);
     } else if (FORM == 2) {
@@ -183,7 +219,24 @@ __global__ __launch_bounds__(64) void chk(const float* __restrict__ w32, const f
   for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out + ((size_t)it * 64 + lane) * 4) = X[it * 64];
 }
 
+// one wave, one tile: form (d) keeping the rows it reads (gemm_bf16_s16's saver) with `valid` of the 32 rows inside the descriptor
+__global__ __launch_bounds__(64) void chk_rows(const float* __restrict__ w16, const float* __restrict__ x0, float* out, float* rows, int valid) {
+  __shared__ float4 slab[32 * 64];
+  const int lane = threadIdx.x;
+  float4* X = slab + lane;
+  for (int it = 0; it < 32; ++it) X[it * 64] = *reinterpret_cast<const float4*>(x0 + ((size_t)it * 64 + lane) * 4);
+  __syncthreads();
+  f32x4 a16[8][2][2];
+  zero_acc16<8>(a16);
+  gemm_bf16_s16<8>(a16, w16, X, 8, lane, rowbuf<false>(rows, 0, valid, 256, lane & 15, (lane >> 4) & 1));
+  __syncthreads();
+  store_act16<8>(a16, X, lane);
+  __syncthreads();
+  for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out + ((size_t)it * 64 + lane) * 4) = X[it * 64];
+}
+
 static int g_grid = 256;
+static float* g_rows = nullptr;  // [g_grid x 4 waves x ROW_SLOTS x 32 points, 256] saved rows of forms 7 to 9
 
 template <int FORM, bool OWN>
 static double run(const char* name, const float* w32, const float* w16, const float* x0, float* out, double cal_ms, double ref_ms) {
@@ -192,10 +245,10 @@ static double run(const char* name, const float* w32, const float* w16, const fl
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  hipLaunchKernelGGL((k<FORM, OWN>), dim3(g_grid), dim3(256), lds, 0, w32, w16, x0, out);
+  hipLaunchKernelGGL((k<FORM, OWN>), dim3(g_grid), dim3(256), lds, 0, w32, w16, x0, out, g_rows);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(e0, 0));
-  for (int r = 0; r < 5; ++r) hipLaunchKernelGGL((k<FORM, OWN>), dim3(g_grid), dim3(256), lds, 0, w32, w16, x0, out);
+  for (int r = 0; r < 5; ++r) hipLaunchKernelGGL((k<FORM, OWN>), dim3(g_grid), dim3(256), lds, 0, w32, w16, x0, out, g_rows);
   CK(hipEventRecord(e1, 0));
   CK(hipEventSynchronize(e1));
   float ms = 0.0f;
@@ -279,7 +332,30 @@ static bool check_forms(bool wide_w, float* w32, float* w16, float* x0, float* o
       }
   printf("check, %s: (b) wrong %zu, (d) wrong %zu, (e) wrong %zu, not all equal %zu of %zu\n",
          wide_w ? "17-bit weights x 0/+-1 activations" : "0/+-1 weights x 17-bit activations", bad_b, bad_d, bad_e, differ, ob.size());
-  return bad_b == 0 && bad_d == 0 && bad_e == 0 && differ == 0;
+  // (d) with the row saver: the same result, every float4 it read in its row of a [points, 256] buffer (row m, floats 8 it + 4 h
+  // .. of slab entry (it, old lane m + 32 h)), rows at or past `valid` and the guard rows behind the tile untouched
+  size_t bad_r = 0, bad_s = 0, stray = 0;
+  const int guard = 8;
+  std::vector<unsigned> hr((size_t)(32 + guard) * 256);
+  for (int valid : {32, 19, 1}) {
+    CK(hipMemset(g_rows, 0xCD, hr.size() * 4));
+    hipLaunchKernelGGL(chk_rows, dim3(1), dim3(64), 0, 0, w16, x0, out, g_rows, valid);
+    CK(hipMemcpy(oe.data(), out, oe.size() * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hr.data(), g_rows, hr.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t o = 0; o < od.size(); ++o) bad_r += oe[o] != od[o];
+    for (int m = 0; m < 32 + guard; ++m)
+      for (int f = 0; f < 256; ++f) {
+        const unsigned got = hr[(size_t)m * 256 + f];
+        if (m >= valid) { stray += got != 0xCDCDCDCDu; continue; }
+        const float want = hx[((size_t)(f / 8) * 64 + m + 32 * ((f / 4) & 1)) * 4 + (f & 3)];
+        unsigned wb;
+        memcpy(&wb, &want, 4);
+        bad_s += got != wb;
+      }
+  }
+  printf("check, %s: (d) with the row saver, 32 / 19 / 1 valid rows: result differs from (d) %zu, saved rows wrong %zu, stray stores %zu\n",
+         wide_w ? "17-bit weights x 0/+-1 activations" : "0/+-1 weights x 17-bit activations", bad_r, bad_s, stray);
+  return bad_b == 0 && bad_d == 0 && bad_e == 0 && differ == 0 && bad_r == 0 && bad_s == 0 && stray == 0;
 }
 
 int main() {
@@ -291,6 +367,7 @@ int main() {
   CK(hipMalloc(&w16, 4ull * SEG_B16 * 4));
   CK(hipMalloc(&x0, 4ull * 32 * 64 * 4 * 4));
   CK(hipMalloc(&out, (size_t)g_grid * 256 * 4));
+  CK(hipMalloc(&g_rows, (size_t)g_grid * 4 * ROW_SLOTS * 32 * 256 * 4));
   if (!check_forms(true, w32, w16, x0, out) || !check_forms(false, w32, w16, x0, out)) { printf("check FAILED\n"); return 1; }
   std::vector<float> h(4ull * SEG_F32);
   for (size_t i = 0; i < h.size(); ++i) h[i] = 1e-3f * (float)((i * 2654435761u) % 2001) - 1.0f;
@@ -322,6 +399,24 @@ int main() {
   run<6, false>("(e) nine products, pieces in registers, 16x16x32", w32, w16, x0, out, cal, a0);
   run<2, false>("(c) again", w32, w16, x0, out, cal, a0);
   run<6, false>("(e) again", w32, w16, x0, out, cal, a0);
+  // the backward sweep: every GEMM also keeps the 32 KiB of rows it reads (or, from the epilogue, writes) in a [points, 256] buffer
+  printf("-- the backward sweep's case: the GEMM keeps its rows (32 KiB per tile to a 512 MiB buffer), the four waves on the same segment\n");
+  const double f0 = run<8, false>("(a) fp32 + row stores in the K loop (gemm_run2 saver)", w32, w16, x0, out, cal, a0);
+  const double g0 = run<7, false>("(d) 16x16x32 + row stores in the K loop (saver)", w32, w16, x0, out, cal, a0);
+  const double h0 = run<9, false>("(d) 16x16x32 + row stores from the epilogue", w32, w16, x0, out, cal, a0);
+  const double f1 = run<8, false>("(a) + stores in the loop, again", w32, w16, x0, out, cal, a0);
+  const double g1 = run<7, false>("(d) + stores in the loop, again", w32, w16, x0, out, cal, a0);
+  const double h1 = run<9, false>("(d) + stores from the epilogue, again", w32, w16, x0, out, cal, a0);
+  {
+    const double best = (g0 + g1) < (h0 + h1) ? (g0 + g1) : (h0 + h1), r = best / (f0 + f1);
+    // predicted step gain, the forward's arithmetic: saving per tile and GEMM x 7 GEMMs x 16 tiles per wave and 524,288 points x 2.54
+    // such launches' worth of points per step (1.33 M) x the 0.65 in-kernel yield measured on the forward
+    const double gain = ((f0 + f1) - best) / 2.0 / TILES * 7.0 * 16.0 * 2.54 * 0.65;
+    printf("backward go / no-go: stores in the loop %.3f, from the epilogue %.3f of the fp32 loop with its stores; the better %.3f (go at <= 0.850): %s\n",
+           (g0 + g1) / (f0 + f1), (h0 + h1) / (f0 + f1), r, r <= 0.85 ? "GO" : "NO-GO");
+    printf("   predicted step gain: (%.2f - %.2f) us per tile x 7 GEMMs x 16 tiles x 2.54 launches x 0.65 = %.3f ms per step\n",
+           (f0 + f1) / 2.0 / TILES * 1000.0, best / 2.0 / TILES * 1000.0, gain);
+  }
   printf("-- every wave on its own copy of the segment (no L1 sharing between the waves)\n");
   const double a2 = run<0, true>("(a) fp32: gemm<8, 8, PF2>", w32, w16, x0, out, cal, 0.0);
   run<1, true>("(b) nine products, packed pieces (gemm_bf16 FULL)", w32, w16, x0, out, cal, a2);
