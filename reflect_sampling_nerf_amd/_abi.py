@@ -7,6 +7,8 @@ the stream as `torch.cuda.current_stream().cuda_stream`; the library never alloc
 import ctypes as C
 import os
 
+import torch
+
 from ._build import LIB_PATH
 
 RSN_ABI_VERSION = 18
@@ -308,3 +310,15 @@ def check(rc: int):
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def float3(v):
+    """Three numbers -> the float[3] an origin or a spacing is passed as."""
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def check_f32_cuda(who: str, **tensors) -> None:
+    """RsnError naming the first of `tensors` (None is skipped) that is not a contiguous fp32 tensor on a cuda (ROCm) device."""
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or t.device.type != "cuda" or not t.is_contiguous()):
+            raise RsnError(f"{who}: {name} must be a contiguous fp32 tensor on a cuda (ROCm) device")

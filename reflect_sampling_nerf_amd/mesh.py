@@ -16,9 +16,10 @@ nerfstudio's Blender scene box.  Pick the level per scene.
 
     ... export-mesh --method tsdf --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T] [--min-weight 1]
 
-The second route needs no level: fuse_depth renders the model's own median depth (depth_fine, where it starts its reflected rays:
-Model.get_surface_outputs) from the given cameras and fuses the maps into a truncated signed distance volume (rsn_tsdf_integrate
-of include/rsn.h) -> tsdf_volume -> the same extractor at level 0 -> drop_unobserved (without it a second shell appears inside
+The second route needs no level: fuse_depth takes the model's own median depth (depth_fine, where it starts its reflected rays:
+Model.get_surface_outputs) from the given cameras, a few views per launch, off the generator render.surface_maps -- the depth pass
+it shares with the point-cloud export -- and fuses the maps into a truncated signed distance volume (rsn_tsdf_integrate of
+include/rsn.h) -> tsdf_volume -> the same extractor at level 0 -> drop_unobserved (without it a second shell appears inside
 the object, where the observed band ends) -> vertex_attributes -> write_ply.  Its defaults, a truncation of 4 grid spacings and
 min_weight 1, are starting points from an experiment on analytic depth maps of a sphere; they have not been measured on a scene.
 
@@ -29,7 +30,6 @@ per-triangle atlas instead of per vertex (texture_atlas -> bake_textures).  Its 
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import time
 from typing import Dict, Optional, Sequence, Tuple, Union
@@ -38,31 +38,33 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _abi, ops
-from ._abi import check, ptr
+from . import _abi, ops, render
+from ._abi import check, float3, ptr
+from ._host import _np, replacing
+from .checkpoint import open_checkpoint
 
 DEFAULT_BOUNDS = (-1.5, -1.5, -1.5, 1.5, 1.5, 1.5)  # nerfstudio's Blender scene box
 DEFAULT_ISO = 10.0  # a starting point, not measured against any scene
 DEFAULT_CHUNK = 1 << 18
 
 
-def _resolution3(resolution: Union[int, Sequence[int]]) -> Tuple[int, int, int]:
-    r = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(x) for x in resolution)
-    if len(r) != 3 or min(r) < 2:
-        raise ValueError(f"resolution {resolution!r}: an int or (nx, ny, nz), every entry at least 2")
-    return r
+def _frame(bounds: Sequence[float], resolution: Union[int, Sequence[int]], vertices: bool):
+    """grid_frame (vertices: n >= 2 per axis, n - 1 intervals between the bounds) and pointcloud.cell_frame (n >= 1 cells, n intervals)."""
+    least = 2 if vertices else 1
+    n = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(x) for x in resolution)
+    if len(n) != 3 or min(n) < least:
+        raise ValueError(f"resolution {resolution!r}: an int or (nx, ny, nz), every entry at least {least}")
+    b = np.asarray(bounds, dtype=np.float64).reshape(6)
+    if not (np.all(np.isfinite(b)) and np.all(b[3:] > b[:3])):
+        raise ValueError(f"bounds {tuple(bounds)!r}: need x0 y0 z0 x1 y1 z1 with every upper bound above its lower one")
+    intervals = np.asarray(n, dtype=np.float64) - (1.0 if vertices else 0.0)
+    return n, b[:3].astype(np.float32), ((b[3:] - b[:3]) / intervals).astype(np.float32)
 
 
 def grid_frame(bounds: Sequence[float], resolution: Union[int, Sequence[int]]):
     """-> ((nx, ny, nz), origin [3], spacing [3]) as fp32 numpy: the grid whose first and last vertices sit on `bounds`
     = (x0, y0, z0, x1, y1, z1).  Vertex (i, j, k) is origin + spacing * (i, j, k) in fp32 -- the extractor's arithmetic."""
-    n = _resolution3(resolution)
-    b = np.asarray(bounds, dtype=np.float64).reshape(6)
-    if not (np.all(np.isfinite(b)) and np.all(b[3:] > b[:3])):
-        raise ValueError(f"bounds {tuple(bounds)!r}: need x0 y0 z0 x1 y1 z1 with every upper bound above its lower one")
-    origin = b[:3].astype(np.float32)
-    spacing = ((b[3:] - b[:3]) / (np.asarray(n, dtype=np.float64) - 1.0)).astype(np.float32)
-    return n, origin, spacing
+    return _frame(bounds, resolution, vertices=True)
 
 
 def _voxel_gaussians(field, mean: Tensor, spacing: Tensor):
@@ -112,9 +114,7 @@ def _extract(vol: Tensor, iso: float, origin, spacing, mark=None) -> Dict[str, T
     pos = torch.empty(n_vert, 3, device=dev, dtype=torch.float32)
     key = torch.empty(n_vert, device=dev, dtype=torch.int32)
     tri = torch.empty(n_tri, 3, device=dev, dtype=torch.int32)
-    o3 = (C.c_float * 3)(*[float(x) for x in origin])
-    s3 = (C.c_float * 3)(*[float(x) for x in spacing])
-    check(lib.rsn_mesh_emit(nx, ny, nz, ptr(vol), float(iso), o3, s3, ptr(ws), nbytes, n_vert, n_tri,
+    check(lib.rsn_mesh_emit(nx, ny, nz, ptr(vol), float(iso), float3(origin), float3(spacing), ptr(ws), nbytes, n_vert, n_tri,
                             ptr(pos) if n_vert else None, ptr(key) if n_vert else None, ptr(tri) if n_tri else None,
                             ops._stream()))
     if mark:
@@ -151,7 +151,7 @@ def vertex_attributes(field, positions: Tensor, spacing: Sequence[float], chunk:
 # ------------------------------------------------------------------------------------------------ TSDF fusion
 DEFAULT_TRUNC_SPACINGS = 4.0  # truncation in units of the largest spacing: a starting point from the sphere experiment, not measured on a scene
 DEFAULT_MIN_WEIGHT = 1.0      # likewise
-DEFAULT_RAY_CHUNK = 4096      # rays per chunk of the depth pass (render.DEFAULT_CHUNK)
+DEFAULT_RAY_CHUNK = render.DEFAULT_CHUNK  # rays per chunk of the depth pass
 EDGE_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))  # dir 0..6 of vert_key (include/rsn.h)
 
 
@@ -159,20 +159,16 @@ def integrate_depth(tsdf: Tensor, weight: Tensor, origin, spacing, c2w: Tensor, 
                     fy: float, cx: float, cy: float, trunc: float, near: float) -> None:
     """One rsn_tsdf_integrate launch: the views c2w [n,3,4] with depth maps depth [n, H*W] (fp32, on the volumes' device) into
     tsdf / weight (fp32 [nz, ny, nx], contiguous), in place."""
-    for name, t in (("tsdf", tsdf), ("weight", weight), ("c2w", c2w), ("depth", depth)):
-        if t.dtype != torch.float32 or t.device.type != "cuda" or not t.is_contiguous():
-            raise _abi.RsnError(f"integrate_depth: {name} must be a contiguous fp32 tensor on a cuda (ROCm) device")
+    _abi.check_f32_cuda("integrate_depth", tsdf=tsdf, weight=weight, c2w=c2w, depth=depth)
     if tsdf.dim() != 3 or weight.shape != tsdf.shape:
         raise _abi.RsnError("integrate_depth: tsdf and weight must be [nz, ny, nx] tensors of one shape")
     n = int(c2w.shape[0])
     if tuple(c2w.shape) != (n, 3, 4) or depth.numel() != n * int(height) * int(width):
         raise _abi.RsnError(f"integrate_depth: c2w {tuple(c2w.shape)} / depth {tuple(depth.shape)}: need [n,3,4] and [n, {height}*{width}]")
     nz, ny, nx = tsdf.shape
-    o3 = (C.c_float * 3)(*[float(x) for x in origin])
-    s3 = (C.c_float * 3)(*[float(x) for x in spacing])
-    check(_abi.load_library().rsn_tsdf_integrate(nx, ny, nz, o3, s3, n, ptr(c2w), int(height), int(width), float(fx), float(fy),
-                                                 float(cx), float(cy), ptr(depth), float(trunc), float(near), ptr(tsdf),
-                                                 ptr(weight), ops._stream()))
+    check(_abi.load_library().rsn_tsdf_integrate(nx, ny, nz, float3(origin), float3(spacing), n, ptr(c2w), int(height), int(width),
+                                                 float(fx), float(fy), float(cx), float(cy), ptr(depth), float(trunc), float(near),
+                                                 ptr(tsdf), ptr(weight), ops._stream()))
 
 
 def fuse_depth(model, poses, H: int, W: int, fx: float, fy: float, cx: float, cy: float, bounds: Sequence[float],
@@ -184,39 +180,16 @@ def fuse_depth(model, poses, H: int, W: int, fx: float, fy: float, cx: float, cy
     views_per_launch depth maps are held at a time and go into one rsn_tsdf_integrate launch (the result does not depend on it);
     chunk: rays per chunk of the depth pass.  No device-to-host read.
     events: a list that receives, per launch, three timing events: start, depth maps rendered, integrated."""
-    from .render import _upload, camera_rays
-
     (nx, ny, nz), origin, spacing = grid_frame(bounds, resolution)
-    H, W = int(H), int(W)
-    views_per_launch = max(1, int(views_per_launch))
     dev = model.device
-    c2w = np.ascontiguousarray(np.asarray(poses.cpu() if isinstance(poses, torch.Tensor) else poses, dtype=np.float32)[:, :3, :4])
     near = float(model.config.collider_params["near_plane"])
     tsdf = torch.zeros(nz, ny, nx, device=dev, dtype=torch.float32)
     weight = torch.zeros(nz, ny, nx, device=dev, dtype=torch.float32)
-    poses_dev = _upload(torch.from_numpy(c2w), dev) if len(c2w) else None
-    depth = torch.empty(min(views_per_launch, max(len(c2w), 1)), H * W, device=dev, dtype=torch.float32)
     with torch.no_grad():
-        for start in range(0, len(c2w), views_per_launch):
-            n = min(views_per_launch, len(c2w) - start)
-            _mark(events, new=True)
-            for i in range(n):
-                rays = camera_rays(poses_dev[start + i], H, W, fx, fy, cx, cy, dev)
-                depth[i] = model.get_surface_outputs_for_camera_ray_bundle(rays, chunk)["depth_fine"].reshape(H * W)
-            _mark(events)
-            integrate_depth(tsdf, weight, origin, spacing, poses_dev[start:start + n], depth[:n], H, W, fx, fy, cx, cy, trunc, near)
-            _mark(events)
+        for _, c2w, depth, _ in render.surface_maps(model, poses, H, W, fx, fy, cx, cy, views_per_launch, chunk, events=events):
+            integrate_depth(tsdf, weight, origin, spacing, c2w, depth, H, W, fx, fy, cx, cy, trunc, near)
+            ops.record_event(events and events[-1])
     return tsdf, weight
-
-
-def _mark(events: Optional[list], new: bool = False) -> None:
-    if events is None:
-        return
-    if new:
-        events.append([])
-    e = torch.cuda.Event(enable_timing=True)
-    e.record()
-    events[-1].append(e)
 
 
 def tsdf_volume(tsdf: Tensor, weight: Tensor, min_weight: float = DEFAULT_MIN_WEIGHT) -> Tensor:
@@ -255,17 +228,16 @@ PLY_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<
 PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
-def _np(x, dtype):
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    return np.ascontiguousarray(x, dtype=dtype)
-
-
 def write_ply(path: str, mesh: Dict) -> str:
     """`mesh`: positions [V,3], triangles [T,3], pred_normals [V,3], diff [V,3], roughness [V], tint [V,3] (tensors or arrays)
     -> binary_little_endian 1.0 PLY: per vertex float x y z nx ny nz, uchar red green blue (the diffuse colour,
     floor(clamp(c, 0, 1) * 255 + 0.5)), float roughness tint_r tint_g tint_b; faces as `list uchar int vertex_indices`."""
-    pos, tri = _np(mesh["positions"], np.float32).reshape(-1, 3), _np(mesh["triangles"], np.int32).reshape(-1, 3)
+    return _write_ply(path, mesh, "export-mesh", faces=True)
+
+
+def _write_ply(path: str, mesh: Dict, command: str, faces: bool) -> str:
+    """The PLY of write_ply (faces) and of pointcloud.write_ply_points (the vertex element alone); `command` ends the comment line."""
+    pos = _np(mesh["positions"], np.float32).reshape(-1, 3)
     V = pos.shape[0]
     vert = np.zeros(V, dtype=PLY_VERTEX_DTYPE)
     nrm = _np(mesh["pred_normals"], np.float32).reshape(V, 3)
@@ -278,19 +250,20 @@ def write_ply(path: str, mesh: Dict) -> str:
     vert["roughness"] = _np(mesh["roughness"], np.float32).reshape(V)
     for c, name in enumerate(("tint_r", "tint_g", "tint_b")):
         vert[name] = tint[:, c]
-    face = np.zeros(tri.shape[0], dtype=PLY_FACE_DTYPE)
-    face["n"], face["v"] = 3, tri
     kinds = {"<f4": "float", "u1": "uchar", "|u1": "uchar"}
-    header = ["ply", "format binary_little_endian 1.0", "comment reflect_sampling_nerf_amd export-mesh",
-              f"element vertex {V}"]
+    header = ["ply", "format binary_little_endian 1.0", f"comment reflect_sampling_nerf_amd {command}", f"element vertex {V}"]
     header += [f"property {kinds[PLY_VERTEX_DTYPE[n].str]} {n}" for n in PLY_VERTEX_DTYPE.names]
-    header += [f"element face {tri.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    face = np.zeros(0, dtype=PLY_FACE_DTYPE)
+    if faces:
+        tri = _np(mesh["triangles"], np.int32).reshape(-1, 3)
+        face = np.zeros(tri.shape[0], dtype=PLY_FACE_DTYPE)
+        face["n"], face["v"] = 3, tri
+        header += [f"element face {tri.shape[0]}", "property list uchar int vertex_indices"]
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path + ".tmp", "wb") as fh:
-        fh.write(("\n".join(header) + "\n").encode("ascii"))
+    with replacing(path) as tmp, open(tmp, "wb") as fh:
+        fh.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         fh.write(vert.tobytes())
         fh.write(face.tobytes())
-    os.replace(path + ".tmp", path)
     return path
 
 
@@ -299,20 +272,16 @@ class _Stages:
     """Per-stage device times from events recorded on the current stream: nothing waits until seconds() is read."""
 
     def __init__(self):
-        self.marks = [("start", self._event())]
-
-    @staticmethod
-    def _event():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
+        self.names, self.events = [], []
+        ops.record_event(self.events)  # the start of the first stage
 
     def __call__(self, name: str) -> None:
-        self.marks.append((name, self._event()))
+        self.names.append(name)
+        ops.record_event(self.events)
 
     def seconds(self) -> Dict[str, float]:
         torch.cuda.synchronize()
-        return {name: self.marks[i][1].elapsed_time(e) / 1000.0 for i, (name, e) in enumerate(self.marks[1:])}
+        return {name: a.elapsed_time(b) / 1000.0 for name, a, b in zip(self.names, self.events, self.events[1:])}
 
 
 def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256, bounds: Sequence[float] = DEFAULT_BOUNDS,
@@ -333,8 +302,6 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
     (texture.py) instead of a PLY; texels: the side of the square of texels a pair of triangles gets; min_footprint: the smallest
     footprint a texel is queried with (None: the largest spacing / 8) -- both defaults are starting points, not measured on a
     scene.  The stages atlas and bake join the seconds, texture_size, texels, live_texels, min_footprint and files the dict."""
-    from .trainer import load_checkpoint, resolve_checkpoint
-
     if texture:
         from . import texture as tex
 
@@ -346,10 +313,8 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
         raise ValueError(f"method {method!r}: density or tsdf")
     if method == "tsdf" and cameras is None:
         raise ValueError("method tsdf needs cameras")
-    ckpt = resolve_checkpoint(ckpt)
-    model, step = load_checkpoint(ckpt, model_config, device)
+    ckpt, model, step = open_checkpoint(ckpt, model_config, device, mma)
     field = model.field
-    field.set_mma_mode(mma)
     (nx, ny, nz), origin, spacing = grid_frame(bounds, resolution)
     extra = {}
     with torch.cuda.device(torch.device(device)):
@@ -362,8 +327,7 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
         else:
             trunc = float(DEFAULT_TRUNC_SPACINGS * float(spacing.max()) if trunc is None else trunc)
             events: list = []
-            tsdf, weight = fuse_depth(model, cameras["c2w"], cameras["height"], cameras["width"], cameras["fx"], cameras["fy"],
-                                      cameras["cx"], cameras["cy"], bounds, resolution, trunc, views_per_launch, ray_chunk, events)
+            tsdf, weight = fuse_depth(model, *render.camera_args(cameras), bounds, resolution, trunc, views_per_launch, ray_chunk, events)
             vol = tsdf_volume(tsdf, weight, min_weight)
             stages("fuse")
             mesh = _extract(vol, 0.0, origin, spacing, mark=stages)

@@ -65,8 +65,7 @@ class OccupancyGrid:
         self.origin = np.asarray(origin, dtype=np.float32).reshape(3).copy()
         self.spacing = np.asarray(spacing, dtype=np.float32).reshape(3).copy()
         self.threshold, self.dilate, self.outside_occupied = float(threshold), int(dilate), bool(outside_occupied)
-        self._origin3 = (C.c_float * 3)(*[float(x) for x in self.origin])
-        self._spacing3 = (C.c_float * 3)(*[float(x) for x in self.spacing])
+        self._origin3, self._spacing3 = _abi.float3(self.origin), _abi.float3(self.spacing)
         self.rays_seen = 0
         self.hits_dev = torch.zeros(1, device=bits.device, dtype=torch.int64)
         # per-sample skipping, one entry per level (LEVELS): the sample slots its launches covered -- rows behind a device-side

@@ -59,6 +59,22 @@ def timed(name: str, work: Optional[Dict], fn):
     return r
 
 
+def record_event(events: Optional[list]) -> None:
+    """Append a timing event recorded now on the current stream to `events`; None: nothing is recorded.  Nothing waits."""
+    if events is not None:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        events.append(e)
+
+
+def new_events(parent: Optional[list]) -> Optional[list]:
+    """A fresh list for the events of one launch or frame, appended to `parent`; None when `parent` is None."""
+    if parent is None:
+        return None
+    parent.append([])
+    return parent[-1]
+
+
 def _f32c(t: Tensor) -> Tensor:
     if t.dtype != torch.float32 or not t.is_contiguous():
         t = t.contiguous().float()

@@ -4,8 +4,9 @@
         [--max-views N] [--downscale K] [--resolution 512] [--min-accumulation 0.5] [--edge 0.05 | --no-edge] [--no-thin]
 
 A point is exactly where the model starts a reflected ray: origin + depth_fine * direction of a pixel.  No grid resampling, iso
-level or truncation distance comes between the model and the file.  The route: collect_points renders the model's median depth
-and accumulation from the given cameras (Model.get_surface_outputs: the depth-only pass), and rsn_pointcloud_mark /
+level or truncation distance comes between the model and the file.  The route: collect_points takes the model's median depth
+and accumulation from the given cameras (Model.get_surface_outputs: the depth-only pass) off the generator render.surface_maps,
+the depth pass it shares with the TSDF route of export-mesh, and rsn_pointcloud_mark /
 rsn_pointcloud_select of include/rsn.h turn the maps into one set of points -- a pixel is a candidate when its depth is finite
 and positive, its accumulation reaches `min_accumulation`, its depth differs from no neighbour's by more than `edge` times the
 smaller of the two (silhouette pixels go) and its point lies in `bounds`; with thinning, a grid of resolution^3 cells over the
@@ -22,16 +23,15 @@ measured on a scene.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import time
 from typing import Dict, Optional, Sequence, Tuple, Union
 
-import numpy as np
 import torch
 from torch import Tensor
 
-from . import _abi, mesh, ops
-from ._abi import check, ptr
+from . import _abi, mesh, ops, render
+from ._abi import check, float3, ptr
+from .checkpoint import open_checkpoint
 
 DEFAULT_RESOLUTION = 512       # cells per axis of the thinning grid: a starting point, not measured on a scene
 DEFAULT_MIN_ACCUMULATION = 0.5  # likewise
@@ -42,13 +42,7 @@ NO_OWNER = 0x7FFFFFFF          # what an owner array holds before the first mark
 def cell_frame(bounds: Sequence[float], resolution: Union[int, Sequence[int]]):
     """-> ((nx, ny, nz), origin [3], spacing [3]) as fp32 numpy: the grid of nx * ny * nz CELLS that tiles `bounds` =
     (x0, y0, z0, x1, y1, z1); cell (i, j, k) spans origin + spacing * (i..i+1, j..j+1, k..k+1)."""
-    n = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(x) for x in resolution)
-    if len(n) != 3 or min(n) < 1:
-        raise ValueError(f"resolution {resolution!r}: an int or (nx, ny, nz), every entry at least 1")
-    b = np.asarray(bounds, dtype=np.float64).reshape(6)
-    if not (np.all(np.isfinite(b)) and np.all(b[3:] > b[:3])):
-        raise ValueError(f"bounds {tuple(bounds)!r}: need x0 y0 z0 x1 y1 z1 with every upper bound above its lower one")
-    return n, b[:3].astype(np.float32), ((b[3:] - b[:3]) / np.asarray(n, dtype=np.float64)).astype(np.float32)
+    return mesh._frame(bounds, resolution, vertices=False)
 
 
 def new_owner(dims: Sequence[int], device) -> Tensor:
@@ -59,9 +53,7 @@ def new_owner(dims: Sequence[int], device) -> Tensor:
 
 def _views(who, c2w, depth, accumulation, height, width):
     n = int(c2w.shape[0])
-    for name, t in (("c2w", c2w), ("depth", depth), ("accumulation", accumulation)):
-        if t is not None and (t.dtype != torch.float32 or t.device.type != "cuda" or not t.is_contiguous()):
-            raise _abi.RsnError(f"{who}: {name} must be a contiguous fp32 tensor on a cuda (ROCm) device")
+    _abi.check_f32_cuda(who, c2w=c2w, depth=depth, accumulation=accumulation)
     if tuple(c2w.shape) != (n, 3, 4) or depth.numel() != n * int(height) * int(width) or (
             accumulation is not None and accumulation.numel() != depth.numel()):
         raise _abi.RsnError(f"{who}: c2w {tuple(c2w.shape)} / depth {tuple(depth.shape)}: need [n,3,4] and [n, {height}*{width}] "
@@ -74,7 +66,7 @@ def _grid_args(dims, origin, spacing, owner):
     if owner is not None and (owner.dtype != torch.int32 or owner.device.type != "cuda" or not owner.is_contiguous()
                               or tuple(owner.shape) != (nz, ny, nx)):
         raise _abi.RsnError(f"owner must be a contiguous int32 [{nz}, {ny}, {nx}] tensor on a cuda (ROCm) device")
-    return nx, ny, nz, (C.c_float * 3)(*[float(x) for x in origin]), (C.c_float * 3)(*[float(x) for x in spacing])
+    return nx, ny, nz, float3(origin), float3(spacing)
 
 
 def mark(owner: Optional[Tensor], dims, origin, spacing, c2w: Tensor, depth: Tensor, accumulation: Optional[Tensor], height: int,
@@ -130,20 +122,13 @@ def collect_points(model, poses, H: int, W: int, fx: float, fy: float, cx: float
     One device-to-host read per launch: the two counts of the selection (kept rows, which size the slice that is kept, and
     candidates) in one copy.  Nothing else is read back.
     events: a list that receives, per launch, four timing events: start, maps rendered, marked, selected."""
-    from .render import _upload, camera_rays
-
     dims, origin, spacing = cell_frame(bounds, resolution)
-    H, W = int(H), int(W)
-    views_per_launch = max(1, int(views_per_launch))
+    F, H, W = len(poses), int(H), int(W)
     dev = model.device
-    c2w = np.ascontiguousarray(np.asarray(poses.cpu() if isinstance(poses, torch.Tensor) else poses, dtype=np.float32)[:, :3, :4])
-    if (len(c2w) * H * W) > 2 ** 31 - 1:
-        raise ValueError(f"{len(c2w)} views of {W} x {H} pixels: the global pixel index needs views * H * W <= 2^31 - 1")
+    if F * H * W > 2 ** 31 - 1:
+        raise ValueError(f"{F} views of {W} x {H} pixels: the global pixel index needs views * H * W <= 2^31 - 1")
     owner = new_owner(dims, dev) if thin else None
-    poses_dev = _upload(torch.from_numpy(c2w), dev) if len(c2w) else None
-    per = min(views_per_launch, max(len(c2w), 1))
-    depth = torch.empty(per, H * W, device=dev, dtype=torch.float32)
-    acc = torch.empty(per, H * W, device=dev, dtype=torch.float32)
+    per = min(max(1, int(views_per_launch)), max(F, 1))  # the views of the largest launch: what the selection's buffers hold
     nbytes = int(_abi.load_library().rsn_pointcloud_workspace_bytes(per, H, W))
     if nbytes == 0:
         check(-1)
@@ -152,21 +137,12 @@ def collect_points(model, poses, H: int, W: int, fx: float, fy: float, cx: float
     candidates = 0
     index, points = [], []
     with torch.no_grad():
-        for start in range(0, len(c2w), views_per_launch):
-            n = min(views_per_launch, len(c2w) - start)
-            mesh._mark(events, new=True)
-            for i in range(n):
-                rays = camera_rays(poses_dev[start + i], H, W, fx, fy, cx, cy, dev)
-                surf = model.get_surface_outputs_for_camera_ray_bundle(rays, chunk)
-                depth[i] = surf["depth_fine"].reshape(H * W)
-                acc[i] = surf["accumulation_fine"].reshape(H * W)
-            mesh._mark(events)
-            views = (dims, origin, spacing, poses_dev[start:start + n], depth[:n], acc[:n], H, W, fx, fy, cx, cy, start,
-                     min_accumulation, edge)
+        for start, c2w, depth, acc in render.surface_maps(model, poses, H, W, fx, fy, cx, cy, views_per_launch, chunk, True, events):
+            views = (dims, origin, spacing, c2w, depth, acc, H, W, fx, fy, cx, cy, start, min_accumulation, edge)
             mark(owner, *views)
-            mesh._mark(events)
+            ops.record_event(events and events[-1])
             counts, pixel_index, positions = select(owner, *views, out=out)
-            mesh._mark(events)
+            ops.record_event(events and events[-1])
             kept, cand = (int(x) for x in counts.tolist())  # the one read of the launch
             candidates += cand
             index.append(pixel_index[:kept].clone())
@@ -181,29 +157,7 @@ def write_ply_points(path: str, cloud: Dict) -> str:
     binary_little_endian 1.0 PLY with one element, vertex, in the layout of mesh.write_ply (mesh.PLY_VERTEX_DTYPE): float x y z
     nx ny nz (the predicted normal), uchar red green blue (the field's diffuse colour, floor(clamp(c, 0, 1) * 255 + 0.5)), float
     roughness tint_r tint_g tint_b.  There is no face element.  Written to a temporary file that is then renamed."""
-    pos = mesh._np(cloud["positions"], np.float32).reshape(-1, 3)
-    P = pos.shape[0]
-    vert = np.zeros(P, dtype=mesh.PLY_VERTEX_DTYPE)
-    nrm = mesh._np(cloud["pred_normals"], np.float32).reshape(P, 3)
-    rgb = np.floor(np.clip(mesh._np(cloud["diff"], np.float32).reshape(P, 3), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
-    tint = mesh._np(cloud["tint"], np.float32).reshape(P, 3)
-    for c, (p, q) in enumerate((("x", "nx"), ("y", "ny"), ("z", "nz"))):
-        vert[p], vert[q] = pos[:, c], nrm[:, c]
-    for c, name in enumerate(("red", "green", "blue")):
-        vert[name] = rgb[:, c]
-    vert["roughness"] = mesh._np(cloud["roughness"], np.float32).reshape(P)
-    for c, name in enumerate(("tint_r", "tint_g", "tint_b")):
-        vert[name] = tint[:, c]
-    kinds = {"<f4": "float", "u1": "uchar", "|u1": "uchar"}
-    header = ["ply", "format binary_little_endian 1.0", "comment reflect_sampling_nerf_amd export-pointcloud", f"element vertex {P}"]
-    header += [f"property {kinds[mesh.PLY_VERTEX_DTYPE[n].str]} {n}" for n in mesh.PLY_VERTEX_DTYPE.names]
-    header += ["end_header"]
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path + ".tmp", "wb") as fh:
-        fh.write(("\n".join(header) + "\n").encode("ascii"))
-        fh.write(vert.tobytes())
-    os.replace(path + ".tmp", path)
-    return path
+    return mesh._write_ply(path, cloud, "export-pointcloud", faces=False)
 
 
 # ------------------------------------------------------------------------------------------------ checkpoint -> file
@@ -217,20 +171,16 @@ def export_pointcloud(ckpt: str, out: str, cameras: dict, resolution: Union[int,
     step, out, points, candidates (before thinning), views, image [W, H], resolution (cells per axis), bounds, spacing,
     min_accumulation, edge, thin, mma and seconds = {depth, mark, select, attributes} on the device, from events, and write on the
     host."""
-    from .trainer import load_checkpoint, resolve_checkpoint
-
     if min_accumulation != min_accumulation or not edge >= 0.0:
         raise ValueError(f"min_accumulation {min_accumulation} / edge {edge}: need a number and an edge >= 0 (inf: no edge test)")
-    ckpt = resolve_checkpoint(ckpt)
-    model, step = load_checkpoint(ckpt, model_config, device)
+    ckpt, model, step = open_checkpoint(ckpt, model_config, device, mma)
     field = model.field
-    field.set_mma_mode(mma)
     dims, _, spacing = cell_frame(bounds, resolution)
     with torch.cuda.device(torch.device(device)):
         field.packed_weights()  # the one-off weight packing is not part of the depth stage
         events: list = []
-        cloud = collect_points(model, cameras["c2w"], cameras["height"], cameras["width"], cameras["fx"], cameras["fy"], cameras["cx"],
-                               cameras["cy"], bounds, resolution, min_accumulation, edge, thin, views_per_launch, ray_chunk, events)
+        cloud = collect_points(model, *render.camera_args(cameras), bounds, resolution, min_accumulation, edge, thin, views_per_launch,
+                               ray_chunk, events)
         stages = mesh._Stages()
         cloud.update(mesh.vertex_attributes(field, cloud["positions"], spacing, chunk))
         stages("attributes")

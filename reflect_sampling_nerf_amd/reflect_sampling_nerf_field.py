@@ -270,18 +270,11 @@ class ReflectSamplingNeRFNerfField(Field):
         N = R * S
         dev = origins.device
         events = grid.sample_stage_events if isinstance(grid.sample_stage_events, list) else None
-        marks = []
-
-        def mark():
-            if events is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                marks.append(e)
-
-        mark()
+        marks = None if events is None else []
+        ops.record_event(marks)
         c = occupancy.mark_and_compact(grid, origins, directions, pixel_area, euclid_bins, n_dev)
         grid.count_samples(level_id, N, c["n_live"])
-        mark()
+        ops.record_event(marks)
         f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
         compact = {"sigma": f(N), "color": f(N, 3)}
         if full:
@@ -292,9 +285,9 @@ class ReflectSamplingNeRFNerfField(Field):
         ops.timed("field_forward_eval_live" if full else "field_forward_eval_color_live", {"points": N}, lambda: check(
             lib.rsn_field_forward_frustum(C.byref(desc), ptr(pk), N, ptr(c["n_live"]), 1, ptr(c["origins_c"]), ptr(c["directions_c"]),
                                           ptr(c["pixel_area_c"]), ptr(c["bins_c"]), C.byref(fo), ops._stream())))
-        mark()
+        ops.record_event(marks)
         level = occupancy.scatter_level(compact, c["n_live"], c["sample_index"], (R, S))
-        mark()
+        ops.record_event(marks)
         if events is not None:
             events.append((level_id, marks))
         level["live"] = c["live"]

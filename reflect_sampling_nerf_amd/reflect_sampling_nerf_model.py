@@ -314,20 +314,13 @@ class ReflectSamplingNeRFModel(Model):
         d = ops._f32c(ray_bundle.directions.reshape(R, 3))
         nears = ops._f32c(ray_bundle.nears.reshape(R))
         fars = ops._f32c(ray_bundle.fars.reshape(R))
-        self._mark(marks)
+        ops.record_event(marks)
         culled = occupancy.cull(self.occupancy, o, d, nears, fars)
         culled["fars"] = fars
-        self._mark(marks)
+        ops.record_event(marks)
         compact = ray_bundle[culled["ray_index"].long()]
-        self._mark(marks)
+        ops.record_event(marks)
         return compact, culled
-
-    @staticmethod
-    def _mark(marks: Optional[list]) -> None:
-        if marks is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append(e)
 
     @torch.no_grad()
     def _get_outputs_eval_culled(self, ray_bundle) -> Dict[str, Tensor]:
@@ -407,7 +400,7 @@ class ReflectSamplingNeRFModel(Model):
         if culled is not None:
             from . import occupancy
 
-            self._mark(marks)
+            ops.record_event(marks)
             joined: Dict[int, Tensor] = {}  # normals_* are the pred_normals_* tensors: joined and written back once
             compact = {}
             for k, v in lists.items():
@@ -416,7 +409,7 @@ class ReflectSamplingNeRFModel(Model):
                         joined[id(v[0])] = torch.cat(v)
                     compact[k] = joined[id(v[0])]
             full = occupancy.scatter_outputs(compact, culled, culled["fars"])
-            self._mark(marks)
+            ops.record_event(marks)
             return {k: v.view(*image_shape, *v.shape[1:]) for k, v in full.items()}
         return {k: torch.cat(v).view(*image_shape, *v[0].shape[1:]) for k, v in lists.items()
                 if len(v) == n_chunks and k != "depth_reflect_fine"}

@@ -22,8 +22,10 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, ops
 from ._abi import RSN_VIS_GRAY, RSN_VIS_LUT, RSN_VIS_RGB, RSN_VIS_UNIT
+from ._host import replacing
+from .checkpoint import open_checkpoint
 from .nerfstudio_compat import RayBundle
 
 # The turbo colour map (A. Mikhailov, Google, 2019; Apache-2.0), its published 256-entry table: what matplotlib ships as "turbo"
@@ -120,6 +122,7 @@ CHANNELS: Dict[str, Channel] = {
 }
 DEFAULT_CHANNELS = ("rgb", "diffuse", "tint", "roughness", "normals", "depth", "accumulation")
 MAX_ELEVATION_DEG = 89.9  # from here on the look direction is too close to world up for a stable `right`
+DEFAULT_CHUNK = 4096  # rays per eval chunk: the kernels are at their best from 4096 rays (INTEGRATION.md); the reference evaluates 1024
 
 _turbo_dev: Dict[torch.device, torch.Tensor] = {}
 
@@ -131,6 +134,11 @@ def _stream(dev) -> int:
 def _upload(host: torch.Tensor, dev) -> torch.Tensor:
     """Host tensor -> device through pinned memory, without waiting for the device."""
     return host.pin_memory().to(dev, non_blocking=True)
+
+
+def _poses(c2w) -> np.ndarray:
+    """One pose or a stack of them ([..,3,4] or [..,4,4]; tensor, array or nested lists) -> contiguous fp32 numpy [..,3,4]."""
+    return np.ascontiguousarray(np.asarray(c2w.cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)[..., :3, :4])
 
 
 def turbo_lut(device) -> torch.Tensor:
@@ -149,18 +157,49 @@ def camera_rays(c2w, height: int, width: int, fx: float, fy: float, cx: float, c
     """The [H,W] RayBundle (origins, directions [H,W,3], pixel_area [H,W,1]; row-major) of the pinhole camera with pose c2w
     ([3,4] or [4,4]; a tensor on `device` is used where it lies, anything else is uploaded).  One launch, no host read."""
     dev = torch.device(device)
-    if isinstance(c2w, torch.Tensor) and c2w.device.type == dev.type:
-        pose = c2w[:3, :4].to(torch.float32).contiguous()
-    else:
-        host = torch.from_numpy(np.ascontiguousarray(np.asarray(c2w.cpu() if isinstance(c2w, torch.Tensor) else c2w,
-                                                                dtype=np.float32)[:3, :4]))
-        pose = _upload(host, dev)
+    there = isinstance(c2w, torch.Tensor) and c2w.device.type == dev.type
+    pose = c2w[:3, :4].to(torch.float32).contiguous() if there else _upload(torch.from_numpy(_poses(c2w)), dev)
     H, W = int(height), int(width)
     flat = torch.empty(H * W * 7, device=dev, dtype=torch.float32)
     o, d, pa = flat[0:3 * H * W].view(H, W, 3), flat[3 * H * W:6 * H * W].view(H, W, 3), flat[6 * H * W:].view(H, W, 1)
     _abi.check(_abi.load_library().rsn_camera_rays_image(H, W, _abi.ptr(pose), fx, fy, cx, cy, _abi.ptr(o), _abi.ptr(d),
                                                          _abi.ptr(pa), _stream(dev)))
     return RayBundle(origins=o, directions=d, pixel_area=pa)
+
+
+def surface_maps(model, poses, H: int, W: int, fx: float, fy: float, cx: float, cy: float, views_per_launch: int = 8,
+                 chunk: int = DEFAULT_CHUNK, accumulation: bool = False, events: Optional[list] = None):
+    """The depth pass of mesh.fuse_depth and pointcloud.collect_points, a generator: the model's median depth (depth_fine of
+    Model.get_surface_outputs) and, with `accumulation`, its accumulation_fine from the cameras poses [F,3,4] (or [F,4,4]) with one
+    pinhole, views_per_launch views at a time, `chunk` rays per chunk.  Per launch it yields (start, poses_dev[start:start + n],
+    depth[:n], acc[:n] or None): the maps are fp32 [n, H*W] views of one buffer that the next launch overwrites, to be used on the
+    current stream before asking for the next.  F = 0 yields nothing.  No device-to-host read.
+    events: a list that receives, per launch, a fresh list of two timing events, start and maps rendered; the consumer appends its own."""
+    c2w = _poses(poses)
+    F, H, W = len(c2w), int(H), int(W)
+    views_per_launch = max(1, int(views_per_launch))
+    dev = model.device
+    poses_dev = _upload(torch.from_numpy(c2w), dev) if F else None
+    depth = torch.empty(min(views_per_launch, max(F, 1)), H * W, device=dev, dtype=torch.float32)
+    acc = torch.empty_like(depth) if accumulation else None
+    for start in range(0, F, views_per_launch):
+        n = min(views_per_launch, F - start)
+        ev = ops.new_events(events)
+        ops.record_event(ev)
+        with torch.no_grad():
+            for i in range(n):
+                rays = camera_rays(poses_dev[start + i], H, W, fx, fy, cx, cy, dev)
+                surf = model.get_surface_outputs_for_camera_ray_bundle(rays, chunk)
+                depth[i] = surf["depth_fine"].reshape(H * W)
+                if accumulation:
+                    acc[i] = surf["accumulation_fine"].reshape(H * W)
+        ops.record_event(ev)
+        yield start, poses_dev[start:start + n], depth[:n], acc[:n] if accumulation else None
+
+
+def camera_args(cameras: dict):
+    """The cameras dict of the trainer's resolve_*_args -> (c2w, height, width, fx, fy, cx, cy), the order the functions take them in."""
+    return tuple(cameras[k] for k in ("c2w", "height", "width", "fx", "fy", "cx", "cy"))
 
 
 def pinhole(width: int, height: int, fov_x: float) -> Tuple[float, float, float, float]:
@@ -253,7 +292,7 @@ def interpolate_path(c2w, steps: int) -> np.ndarray:
     """`steps` poses between every two consecutive ones of c2w [F,3,4]: the rotation by quaternion slerp along the shorter arc, the
     translation linear.  The given poses are passed through untouched; steps = 0 returns them all.  -> fp32
     [(F-1)(steps+1)+1,3,4]."""
-    src = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32)[:, :3, :4])
+    src = _poses(c2w)
     if steps < 0:
         raise ValueError(f"steps must be >= 0, got {steps}")
     if steps == 0 or len(src) < 2:
@@ -349,7 +388,7 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
     panel drawn, copy enqueued (tools/render_path_report.py)."""
     channels = check_channels(channels)
     dev = model.device
-    poses = np.ascontiguousarray(np.asarray(c2w.cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)[:, :3, :4])
+    poses = _poses(c2w)
     F, H, W, C = len(poses), int(height), int(width), len(channels)
     if depth_range is None:
         depth_range = (float(model.config.collider_params["near_plane"]), float(model.config.collider_params["far_plane"]))
@@ -371,28 +410,19 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
         else:
             on_frame(i, arr)
 
-    def mark(ev: Optional[list]) -> None:
-        if ev is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            ev.append(e)
-
     with torch.no_grad():
         for i in range(F):
-            ev = None
-            if stage_events is not None:
-                ev = []
-                stage_events.append(ev)
-            mark(ev)
+            ev = ops.new_events(stage_events)
+            ops.record_event(ev)
             rays = camera_rays(poses_dev[i], H, W, fx, fy, cx, cy, dev)
-            mark(ev)
+            ops.record_event(ev)
             outputs = model.get_outputs_for_camera_ray_bundle(rays)
-            mark(ev)
+            ops.record_event(ev)
             draw_channels(outputs, channels, (lo, hi), panel_dev, panel)
-            mark(ev)
+            ops.record_event(ev)
             host[i % 2].copy_(panel_dev, non_blocking=True)
             done[i % 2].record()
-            mark(ev)
+            ops.record_event(ev)
             del outputs, rays
             if i > 0:
                 deliver(i - 1)
@@ -402,9 +432,6 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
 
 
 # ------------------------------------------------------------------------------------------------ checkpoint -> frames
-DEFAULT_CHUNK = 4096  # rays per eval chunk: the kernels are at their best from 4096 rays (INTEGRATION.md); the reference evaluates 1024
-
-
 def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx: float, fy: float, cx: float, cy: float,
                       channels: Sequence[str] = DEFAULT_CHANNELS, depth_range: Optional[Tuple[float, float]] = None,
                       mma: str = "f32", chunk: int = DEFAULT_CHUNK, tiles: bool = False, device="cuda:0", model_config=None,
@@ -420,19 +447,14 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
     -> the dict written to frames.json plus {"seconds": wall time of the frames, "out": out_dir}."""
     from PIL import Image
 
-    from . import trainer
-
     channels = check_channels(channels)
     if chunk < 1:
         raise ValueError(f"chunk must be >= 1, got {chunk}")
-    dev = torch.device(device)
-    ckpt = trainer.resolve_checkpoint(ckpt)
-    model, step = trainer.load_checkpoint(ckpt, model_config, dev)
-    model.field.set_mma_mode(mma)
+    ckpt, model, step = open_checkpoint(ckpt, model_config, torch.device(device), mma)
     model.config.eval_num_rays_per_chunk = int(chunk)
     if depth_range is None:
         depth_range = (model.config.collider_params["near_plane"], model.config.collider_params["far_plane"])
-    poses = np.asarray(c2w, dtype=np.float32)[:, :3, :4]
+    poses = _poses(c2w)
     if occupancy is not None:
         from .occupancy import attach_occupancy
 
@@ -461,9 +483,7 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
             "frames": [{"files": f, "c2w": poses[i].astype(np.float64).tolist()} for i, f in enumerate(files)]}
     if occupancy is not None:
         meta["occupancy"] = model.occupancy.describe()
-    tmp = os.path.join(out_dir, "frames.json.tmp")
-    with open(tmp, "w") as fh:
+    with replacing(os.path.join(out_dir, "frames.json")) as tmp, open(tmp, "w") as fh:
         json.dump(meta, fh, indent=1)
         fh.write("\n")
-    os.replace(tmp, os.path.join(out_dir, "frames.json"))
     return {**meta, "seconds": seconds, "out": out_dir}

@@ -25,6 +25,8 @@ from torch import Tensor
 
 from . import _abi, ops
 from ._abi import RSN_VIS_GRAY, RSN_VIS_RGB, RSN_VIS_UNIT, check, ptr
+from ._host import _np, replacing
+from .render import visualize
 
 DEFAULT_TEXELS = 8            # texels per square side: a starting point, not measured on a scene
 MIN_FOOTPRINT_FRACTION = 8.0  # default min_footprint = largest spacing / 8: a starting point, not measured on a scene
@@ -105,8 +107,6 @@ def bake_textures(attributes: Callable[[Tensor, Tensor], Dict[str, Tensor]], atl
     (grey) and "normal" (object space, n * 0.5 + 0.5).  An unused texel holds 0.5 in the colour maps and roughness and (0, 0, 0) in
     the normal map: mid grey everywhere.  The bytes are rsn_visualize's (include/rsn.h): RSN_VIS_RGB, RSN_VIS_GRAY with lo 0 and hi
     1, RSN_VIS_UNIT, no alpha."""
-    from .render import visualize
-
     N = int(atlas["size"])
     live = atlas["live"]
     dev = atlas["point"].device
@@ -168,23 +168,11 @@ def field_attributes(field, spacing: Sequence[float], min_footprint: Optional[fl
 
 
 # ------------------------------------------------------------------------------------------------ OBJ
-def _np(x, dtype):
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    return np.ascontiguousarray(x, dtype=dtype)
-
-
 def _rows(fh, row_format: str, values: np.ndarray) -> None:
     """Write one text row per row of `values` [n, k]: the format of _ROWS_PER_FORMAT rows at a time is applied in one operation."""
     for start in range(0, values.shape[0], _ROWS_PER_FORMAT):
         part = values[start:start + _ROWS_PER_FORMAT]
         fh.write(((row_format * part.shape[0]) % tuple(part.reshape(-1).tolist())).encode("ascii"))
-
-
-def _replace(path: str, write) -> None:
-    with open(path + ".tmp", "wb") as fh:
-        write(fh)
-    os.replace(path + ".tmp", path)
 
 
 def obj_file_set(path: str) -> Dict[str, str]:
@@ -229,9 +217,10 @@ def write_obj(path: str, mesh: Dict, atlas_uv: np.ndarray, maps: Dict) -> Dict[s
         lines += [f"{key} {name}_{m}.png" for key, m in MTL_KEYS]
         fh.write(("\n".join(lines) + "\n").encode("ascii"))
 
-    _replace(files["obj"], obj)
-    _replace(files["mtl"], mtl)
-    for m in MAPS:
-        img = Image.fromarray(_np(maps[m], np.uint8))
-        _replace(files[m], lambda fh, img=img: img.save(fh, format="PNG"))
+    def png(m):
+        return lambda fh: Image.fromarray(_np(maps[m], np.uint8)).save(fh, format="PNG")
+
+    for k, write in (("obj", obj), ("mtl", mtl), *((m, png(m)) for m in MAPS)):
+        with replacing(files[k]) as tmp, open(tmp, "wb") as fh:
+            write(fh)
     return files

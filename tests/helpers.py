@@ -1,6 +1,7 @@
 """Shared helpers for the tests (fixture loading, tolerant comparisons)."""
 import contextlib
 import json
+import math
 import os
 
 import numpy as np
@@ -39,6 +40,35 @@ def model_spec_from_meta(meta):
 
 def max_abs(a, b):
     return float((a.double() - b.double()).abs().max()) if a.numel() else 0.0
+
+
+# ---------------------------------------------------------------------------------------------- the fog model of the export tests
+FOG_DEPTH = 3.5
+
+
+def fog_model(device):
+    """A 4 x 64 model (seed 3) in eval mode on `device` whose density head is a constant: a fog of sigma = ln 2 / 3.5, so every eval
+    ray (near plane 0) has its median depth about 3.5 from its camera and an accumulation of about 0.69, wherever it looks."""
+    import reflect_sampling_nerf_amd as pkg
+    from reflect_sampling_nerf_amd import trainer
+
+    cfg = pkg.ReflectSamplingNeRFModelConfig(base_mlp_num_layers=4, base_mlp_layer_width=64)
+    model = trainer.make_model(cfg, seed=3).to(device).eval()
+    sigma = math.log(2.0) / FOG_DEPTH
+    with torch.no_grad():
+        model.field.field_output_density.net.weight.zero_()
+        model.field.field_output_density.net.bias.fill_(math.log(math.expm1(sigma)) - model.field.density_bias)
+    return model
+
+
+def fog_checkpoint(run, device):
+    """The fog model saved as step 5 of the run directory `run` -> (the checkpoint's path, str(run))."""
+    import reflect_sampling_nerf_amd as pkg
+    from reflect_sampling_nerf_amd import trainer
+
+    model = fog_model(device)
+    opt = pkg.FusedRAdam(model.get_param_groups()["fields"], lr=1e-3, eps=1e-15)
+    return trainer.save_checkpoint(trainer.checkpoint_path(str(run), 5), model, opt, 5), str(run)
 
 
 # ---------------------------------------------------------------------------------------------- persistent-kernel coverage

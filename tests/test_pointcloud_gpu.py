@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import reflect_sampling_nerf_amd as pkg
 from reflect_sampling_nerf_amd import _abi, pointcloud, render, trainer
+from tests import helpers
 from tests import pointcloud_reference as ref
 from tests import tsdf_reference as tref
 
@@ -277,22 +277,14 @@ def test_empty_inputs():
 
 # ---------------------------------------------------------------------------------------------- 7. checkpoint -> PLY
 RES, BOUNDS, SIDE, FOV_DEG = 24, (-1.5, -1.5, -1.5, 1.5, 1.5, 1.5), 16, 40.0
-FOG_DEPTH = 3.5
+FOG_DEPTH = helpers.FOG_DEPTH
 
 
 @pytest.fixture(scope="module")
 def fog_checkpoint(tmp_path_factory):
     """A 4 x 64 field whose density head is a constant: a fog of sigma = ln 2 / 3.5, so every eval ray has its median depth about
     3.5 from its camera and an accumulation of about 0.69, wherever it looks (the construction of the TSDF export's fixture)."""
-    cfg = pkg.ReflectSamplingNeRFModelConfig(base_mlp_num_layers=4, base_mlp_layer_width=64)
-    model = trainer.make_model(cfg, seed=3).to(DEV).eval()
-    sigma = math.log(2.0) / FOG_DEPTH
-    with torch.no_grad():
-        model.field.field_output_density.net.weight.zero_()
-        model.field.field_output_density.net.bias.fill_(math.log(math.expm1(sigma)) - model.field.density_bias)
-    opt = pkg.FusedRAdam(model.get_param_groups()["fields"], lr=1e-3, eps=1e-15)
-    run = tmp_path_factory.mktemp("fog") / "run"
-    return trainer.save_checkpoint(trainer.checkpoint_path(str(run), 5), model, opt, 5), str(run)
+    return helpers.fog_checkpoint(tmp_path_factory.mktemp("fog") / "run", DEV)
 
 
 def orbit_cameras():

@@ -14,6 +14,7 @@ import reflect_sampling_nerf_amd as pkg
 from reflect_sampling_nerf_amd import _abi, mesh, ops, render, trainer
 from reflect_sampling_nerf_amd._abi import ptr
 from reflect_sampling_nerf_amd.nerfstudio_compat import RayBundle
+from tests import helpers
 from tests import tsdf_reference as ref
 from tests.mesh_reference import OFFSETS, parse_ply
 
@@ -279,7 +280,7 @@ def test_chunked_surface_image_is_the_full_image_and_reads_nothing_back(tiny_mod
 
 # ---------------------------------------------------------------------------------------------- checkpoint -> PLY
 RES, BOUNDS, SIDE, FOV_DEG = 12, (-1.5, -1.5, -1.5, 1.5, 1.5, 1.5), 16, 40.0
-FOG_DEPTH = 3.5
+FOG_DEPTH = helpers.FOG_DEPTH
 
 
 @pytest.fixture(scope="module")
@@ -287,15 +288,7 @@ def fog_checkpoint(tmp_path_factory):
     """A 4 x 64 field whose density head is a constant: a fog of sigma = ln 2 / 3.5, so every eval ray (near plane 0) has its
     median depth about 3.5 from its camera, wherever it looks.  From cameras 4 away from the origin the fused surface is then the
     part of the spheres of radius 3.5 around the cameras that lies in the box: zero crossings between observed vertices."""
-    cfg = pkg.ReflectSamplingNeRFModelConfig(base_mlp_num_layers=4, base_mlp_layer_width=64)
-    model = trainer.make_model(cfg, seed=3).to(DEV).eval()
-    sigma = math.log(2.0) / FOG_DEPTH
-    with torch.no_grad():
-        model.field.field_output_density.net.weight.zero_()
-        model.field.field_output_density.net.bias.fill_(math.log(math.expm1(sigma)) - model.field.density_bias)
-    opt = pkg.FusedRAdam(model.get_param_groups()["fields"], lr=1e-3, eps=1e-15)
-    run = tmp_path_factory.mktemp("fog") / "run"
-    return trainer.save_checkpoint(trainer.checkpoint_path(str(run), 5), model, opt, 5), str(run)
+    return helpers.fog_checkpoint(tmp_path_factory.mktemp("fog") / "run", DEV)
 
 
 def orbit_cameras():
