@@ -53,28 +53,22 @@ static int launch_field_jobs(const rsn_field_desc* d, const float* packed, Field
   if (train && rsn_ring_training(d))  // plain / split bf16 training at width 256: the LDS-ring kernels (256- / 128-point tiles)
     return mode == RSN_MMA_BF16X6 ? rsn_launch_field_x6_train(n_tiles, st, J) : rsn_launch_field_bf16_train(rsn_job_tiles(J, 256), st, J);
   if (mode == RSN_MMA_BF16X6 || (!train && mode == RSN_MMA_BF16X3)) {  // split-bf16 instantiations: rsn_field_split.hip
-    RSN_TRY(rsn_launch_field_split(d->width, train, mode == RSN_MMA_BF16X6 ? 1 : 2, grid, st, J));
+    RSN_TRY(rsn_launch_field_split(d->width, train, (rsn_mma_mode)mode, grid, st, J));
     RSN_HIP(hipGetLastError());
     return RSN_OK;
   }
-#define RSN_LAUNCH(NBV)                                                                                          \
-  do {                                                                                                           \
-    if (train && mode == RSN_MMA_BF16)  /* reduced-precision training: plain bf16 operands, fp32 accumulate */  \
-      hipLaunchKernelGGL((rsn_field_kernel<NBV, true, 3>), dim3((unsigned)grid), dim3(256), 0, st, J);            \
-    else if (train && mode == RSN_MMA_F32_FOLDED)  /* exact fp32, the bottleneck folded into mlp_mid */         \
-      hipLaunchKernelGGL((rsn_field_kernel<NBV, true, 4>), dim3((unsigned)grid), dim3(256), 0, st, J);      \
-    else if (train)  /* BF16X3 is an eval-only opt-in: training falls back to exact fp32 */                      \
-      hipLaunchKernelGGL((rsn_field_kernel<NBV, true, 0>), dim3((unsigned)grid), dim3(256), 0, st, J);            \
-    else                                                                                                         \
-      hipLaunchKernelGGL((rsn_field_kernel<NBV, false, 0>), dim3((unsigned)grid), dim3(256), 0, st, J);           \
-  } while (0)
-  switch (d->width) {
-    case 256: RSN_LAUNCH(8); break;
-    case 128: RSN_LAUNCH(4); break;
-    case 64: RSN_LAUNCH(2); break;
-    default: RSN_REQUIRE(false, RSN_ERR_UNSUPPORTED, "width=%d unsupported", d->width);
-  }
-#undef RSN_LAUNCH
+  RSN_TRY(rsn_for_width(d->width, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    const dim3 g((unsigned)grid), b(256);
+    if (train && mode == RSN_MMA_BF16)  // reduced-precision training: plain bf16 operands, fp32 accumulate
+      hipLaunchKernelGGL((rsn_field_kernel<NB, true, RSN_MMA_BF16>), g, b, 0, st, J);
+    else if (train && mode == RSN_MMA_F32_FOLDED)  // exact fp32, the bottleneck folded into mlp_mid
+      hipLaunchKernelGGL((rsn_field_kernel<NB, true, RSN_MMA_F32_FOLDED>), g, b, 0, st, J);
+    else if (train)  // BF16X3 is an eval-only opt-in: training falls back to exact fp32
+      hipLaunchKernelGGL((rsn_field_kernel<NB, true, RSN_MMA_F32>), g, b, 0, st, J);
+    else
+      hipLaunchKernelGGL((rsn_field_kernel<NB, false, RSN_MMA_F32>), g, b, 0, st, J);
+  }));
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

@@ -13,6 +13,7 @@
 // Weights: split 0 of the split-bf16 segments written by rsn_pack_weights ([k16][nb][3][lane][8 bf16]).
 // Slab: X[kk][lane] = 8 bf16 = the lane's features kk*16 + {4h..4h+3} and kk*16 + 8 + {4h..4h+3} (K-iterations 2kk, 2kk+1
 // of the fp32 kernel), so the packed K order is unchanged.
+#include "rsn_epilogues.h"  // init_acc
 #include "rsn_ring16.h"
 
 // acc -> slab: blocks 0..NBS-1; K=16 step nb*2 + qp holds accumulator registers 8qp..8qp+7 of block nb

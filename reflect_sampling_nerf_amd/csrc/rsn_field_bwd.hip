@@ -18,23 +18,22 @@
 //   reflect levels: the Gaussian covariance depends on pixel_area = pi * sqradius (a function of the NON-detached
 //   rendered roughness, model.py:225-227,272,286), so the gradient w.r.t. the encoded inputs' variance is carried
 //   back to pixel_area (need_input_grad).
-#include "rsn_mfma.h"
-
-#include "rsn_field_common.h"
+#include "rsn_epilogues.h"
 #include "rsn_field_bwd_common.h"
 
 // FOLD (RSN_MMA_F32_FOLDED, see rsn_field_kernel.h): stages 2 and 3 are ONE GEMM d emb = [W_c ; W_heads]^T [d a_mid ; dz_heads] over
 // K = 128 + 32; no bottleneck gradient row exists (gout.d_bott is neither written nor read).
-// MMA: the rsn_mma_mode the kernel serves -- 0 exact fp32, 1 split-bf16, 3 plain bf16, 4 = 0 with FOLD.
+// MMA: the rsn_mma_mode the kernel serves (MmaTraits, rsn_gemm_loops.h); MODE = the mode whose K loops it runs.
 template <int NB, int MMA>
 __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
-  constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;
-  constexpr int MODE = FOLD ? 0 : MMA;  // the arithmetic of the GEMM loops
+  using M = MmaTraits<MMA>;
+  constexpr bool FOLD = M::FOLD;
+  constexpr int MODE = M::LOOPS;
   constexpr int HIT = FOLD ? 16 : NB * 4;  // first K-iteration of the heads gradients in the slab (FOLD: behind d a_mid's 16)
   constexpr int XITS = (NB * 4 > 16) ? NB * 4 : 16;
   constexpr int WAVE_F4 = (XITS + RSN_AUX_ITS) * 64;
   constexpr int W = NB * 32;
-  constexpr bool SBF = MODE == 3;  // reduced-precision training: wide layer gradients (dy, d_bott, da_mid) stored as bf16
+  constexpr bool SBF = M::SAVE_BF16;  // reduced-precision training: wide layer gradients (dy, d_bott, da_mid) stored as bf16
   __shared__ float4 smem[4 * WAVE_F4];
 
   const int lane = threadIdx.x & 63;
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
     // produces it.  History: with the two-buffer K loop this arrangement ran the sweeps 12.1 -> 12.5 ms per step (vmcnt
     // counts stores in order with the loads, so a fragment wait also waited out the store in front of it); with the
     // fragments two iterations ahead (gemm_run2) it is 11.78 -> 11.55 ms.
-    constexpr bool LOOPST = MODE == 0;
+    constexpr bool LOOPST = M::LOOP_STORES;
     auto rb_epi = [&](float* base, long long elem, int row_elems) {
       return rowbuf<SBF>(LOOPST ? nullptr : base, elem, rows, row_elems, m, h);
     };
@@ -223,22 +222,16 @@ static int launch_bwd_jobs(const rsn_field_desc* d, const float* packed, BwdJob*
   const bool x6 = d->mma_mode == RSN_MMA_BF16X6;  // fp32-emulating split-bf16 sweeps (opt-in); else exact fp32
   if (rsn_ring_training(d))  // plain / split bf16 training at width 256: the LDS-ring kernels (256- / 128-point tiles)
     return x6 ? rsn_launch_field_x6_bwd(n_tiles, st, J) : rsn_launch_field_bf16_bwd(rsn_job_tiles(J, 256), st, J);
-#define RSN_LAUNCH_BWD(NBV)                                                                                  \
-  do {                                                                                                       \
-    if (x6) hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 1>), dim3((unsigned)grid), dim3(256), 0, st, J);    \
-    else if (d->mma_mode == RSN_MMA_BF16)  /* reduced-precision training sweeps (bf16 operands, fp32 accumulate) */ \
-      hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 3>), dim3((unsigned)grid), dim3(256), 0, st, J);              \
-    else if (d->mma_mode == RSN_MMA_F32_FOLDED)  /* exact fp32, the bottleneck folded into mlp_mid */           \
-      hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 4>), dim3((unsigned)grid), dim3(256), 0, st, J);        \
-    else hipLaunchKernelGGL((rsn_field_bwd_kernel<NBV, 0>), dim3((unsigned)grid), dim3(256), 0, st, J);       \
-  } while (0)
-  switch (d->width) {
-    case 256: RSN_LAUNCH_BWD(8); break;
-    case 128: RSN_LAUNCH_BWD(4); break;
-    case 64: RSN_LAUNCH_BWD(2); break;
-    default: RSN_REQUIRE(false, RSN_ERR_UNSUPPORTED, "width=%d unsupported", d->width);
-  }
-#undef RSN_LAUNCH_BWD
+  RSN_TRY(rsn_for_width(d->width, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    const dim3 g((unsigned)grid), b(256);
+    if (x6) hipLaunchKernelGGL((rsn_field_bwd_kernel<NB, RSN_MMA_BF16X6>), g, b, 0, st, J);
+    else if (d->mma_mode == RSN_MMA_BF16)  // reduced-precision training sweeps (bf16 operands, fp32 accumulate)
+      hipLaunchKernelGGL((rsn_field_bwd_kernel<NB, RSN_MMA_BF16>), g, b, 0, st, J);
+    else if (d->mma_mode == RSN_MMA_F32_FOLDED)  // exact fp32, the bottleneck folded into mlp_mid
+      hipLaunchKernelGGL((rsn_field_bwd_kernel<NB, RSN_MMA_F32_FOLDED>), g, b, 0, st, J);
+    else hipLaunchKernelGGL((rsn_field_bwd_kernel<NB, RSN_MMA_F32>), g, b, 0, st, J);
+  }));
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

@@ -2,9 +2,11 @@
 // reference's per-sample forward maths around the GEMMs (point -> contracted Gaussian, the head outputs, the colour combine),
 // stated once as row / point functions.  Users: rsn_field_kernel.h (exact fp32 / split-bf16 / per-wave training),
 // rsn_field_bf16.hip (plain-bf16 eval), rsn_field_bf16_train.hip and rsn_field_x6_train.hip (LDS-ring training).  The
-// backward counterpart is rsn_field_bwd_common.h.  What stays per family: the GEMM loops, the operand formats, the encode loops.
+// backward counterpart is rsn_field_bwd_common.h.  What stays per family: the GEMM loops, the operand formats, the encode loops
+// (the per-wave family's loops and epilogues: rsn_gemm_loops.h, rsn_epilogues.h).  The scalar maths below builds on is
+// rsn_device_math.h, the one header this one needs.
 #pragma once
-#include "rsn_mfma.h"
+#include "rsn_device_math.h"
 
 // What every evaluation of one launch shares (the network) ...
 struct FieldShared {
@@ -306,7 +308,20 @@ inline int rsn_fill_inf(JOB& a, const char* pfx, int n_rays, const int* n_dev, c
   return RSN_OK;
 }
 
+// The per-wave kernels (rsn_field_kernel, rsn_field_bwd_kernel) are built for three widths: `launch` gets NB = width / 32 row
+// blocks as a compile-time constant, std::integral_constant<int, NB>.
+template <class LAUNCH>
+inline int rsn_for_width(int width, LAUNCH&& launch) {
+  switch (width) {
+    case 256: launch(std::integral_constant<int, 8>()); break;
+    case 128: launch(std::integral_constant<int, 4>()); break;
+    case 64: launch(std::integral_constant<int, 2>()); break;
+    default: RSN_REQUIRE(false, RSN_ERR_UNSUPPORTED, "width=%d unsupported", width);
+  }
+  return RSN_OK;
+}
+
 // rsn_field_bf16.hip: the dedicated RSN_MMA_BF16 eval kernel (two workgroups per CU)
 int rsn_launch_field_bf16(int width, long long grid, hipStream_t st, const FieldArgs& a);
-// split-bf16 instantiations of rsn_field_kernel (rsn_field_split.hip); mode 1 = BF16X6, 2 = BF16X3 (eval only)
-int rsn_launch_field_split(int width, bool train, int mode, long long grid, hipStream_t st, const FieldJobs& J);
+// split-bf16 instantiations of rsn_field_kernel (rsn_field_split.hip): RSN_MMA_BF16X6, or RSN_MMA_BF16X3 (eval only)
+int rsn_launch_field_split(int width, bool train, rsn_mma_mode mode, long long grid, hipStream_t st, const FieldJobs& J);

@@ -1,12 +1,13 @@
 // rsn_field_kernel.h -- the field kernel template (see rsn_field.hip for the layout argument), shared by two translation
 // units that differ in ONE compiler flag (reflect_sampling_nerf_amd/_build.py, SOURCE_FLAGS):
-//   rsn_field.hip        exact fp32 (MODE 0) and plain-bf16 training (MODE 3): MFMA accumulators in architected VGPRs
-//                        (-amdgpu-mfma-vgpr-form: the epilogues touch every accumulator; no v_accvgpr copies, no scratch);
-//   rsn_field_split.hip  split-bf16 (MODE 1, 2): hipcc's default AGPR accumulators -- these kernels also hold the bf16
-//                        triples of the operands, and in VGPR form their training forward runs 14 % slower.
+//   rsn_field.hip        exact fp32 (RSN_MMA_F32, RSN_MMA_F32_FOLDED) and plain-bf16 training (RSN_MMA_BF16): MFMA accumulators in
+//                        architected VGPRs (-amdgpu-mfma-vgpr-form: the epilogues touch every accumulator; no v_accvgpr copies, no
+//                        scratch);
+//   rsn_field_split.hip  split-bf16 (RSN_MMA_BF16X6, RSN_MMA_BF16X3): hipcc's default AGPR accumulators -- these kernels also hold
+//                        the bf16 triples of the operands, and in VGPR form their training forward runs 14 % slower.
+// The K loops are rsn_gemm_loops.h (with MmaTraits: what a mode means), the epilogues rsn_epilogues.h.
 #pragma once
-#include "rsn_mfma.h"
-
+#include "rsn_epilogues.h"
 #include "rsn_field_common.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -15,7 +16,7 @@
 // N = W + 32 GEMM over the trunk output becomes N = 128 + 32 (the four mlp_mid blocks, started from b_c, and the heads block), the
 // SH part then accumulates into the same four blocks, and the K = W GEMM over the bottleneck row is gone with the row itself
 // (saved.bott is neither written nor read).  Heads, sigma and normals keep their bits: same K order, same bias start.
-// MMA: the rsn_mma_mode the kernel serves -- 0 exact fp32, 1 / 2 split-bf16, 3 plain-bf16 training, 4 = 0 with FOLD.
+// MMA: the rsn_mma_mode the kernel serves (MmaTraits, rsn_gemm_loops.h); MODE = the mode whose K loops it runs.
 // A loop GEMM of the analytic-normal sweep in the mode's own loop, and, for the exact-fp32 training instantiations, as the
 // nine-product loop on the 16x16x32 bf16 MFMAs: PACKED (FOLD) over the pre-split hT_* segment, else with the same pieces formed in
 // registers from the fp32 wT_* segment (the RSN_MMA_F32 buffer has no split copies): the same bits either way.
@@ -33,14 +34,15 @@ __device__ __forceinline__ void sweep_gemm(f32x4 (&acc)[NBO][2][2], const float*
 
 template <int NB, bool TRAIN, int MMA>
 __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
-  constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;
-  constexpr int MODE = FOLD ? 0 : MMA;  // the arithmetic of the GEMM loops
+  using M = MmaTraits<MMA>;
+  constexpr bool FOLD = M::FOLD;
+  constexpr int MODE = M::LOOPS;
   static_assert(!FOLD || TRAIN, "the folded bottleneck serves the exact-fp32 training kernels");
   constexpr int NBH = FOLD ? 5 : NB + 1;  // row blocks of the GEMM that carries the heads block (its last)
   constexpr int XITS = (NB * 4 > 16) ? NB * 4 : 16;  // >= 14 (encoding, K=16 steps) and >= 16 (mid hidden)
   constexpr int WAVE_F4 = (XITS + RSN_AUX_ITS) * 64;
   constexpr int W = NB * 32;
-  constexpr bool SBF = TRAIN && MODE == 3;  // reduced-precision training: activations / bottleneck / mid hidden saved as bf16
+  constexpr bool SBF = TRAIN && M::SAVE_BF16;  // reduced-precision training: activations / bottleneck / mid hidden saved as bf16
   __shared__ float4 smem[4 * WAVE_F4];
 
   const int lane = threadIdx.x & 63;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     const int rows = (int)(n_points - p0 < 32 ? n_points - p0 : 32);  // valid rows of this wave's tile (wave-uniform)
     // Saved rows (training).  Exact fp32: a row leaves from the K loop of the GEMM that READS it (one store per
     // K-iteration, gemm_run); the split / plain bf16 loops store from the epilogue that produces it.
-    constexpr bool LOOPST = TRAIN && MODE == 0;
+    constexpr bool LOOPST = TRAIN && M::LOOP_STORES;
     auto rb_epi = [&](float* base, long long elem, int row_elems) {
       return rowbuf<SBF>((TRAIN && !LOOPST) ? base : nullptr, elem, rows, row_elems, m, h);
     };
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
       float4 raw = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       if (h == 0) raw = make_float4(mc[0], mc[1], mc[2], 0.0f);
       X[12 * 64] = raw;
-      if (MODE != 0) X[13 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // K=16 steps read iteration 13 (zero weights)
+      if (!M::F32) X[13 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // K=16 steps read iteration 13 (zero weights)
     }
     // this lane's 52 encoded inputs, re-used by the skip layer.  Held as vector-typed SSA values (not an
     // indexable array) so that they stay in the unified VGPR/AGPR file instead of scratch memory.
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
             X[(8 + it) * 64] = make_float4(st2[4 * it], st2[4 * it + 1], st2[4 * it + 2], st2[4 * it + 3]);
           }
           X[12 * 64] = st3;
-          if (MODE != 0) X[13 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          if (!M::F32) X[13 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           gemm_mode_run<MODE, NB, NB, TRAIN>(acc, wpre, pk + P.L.w_enc_skip, pk + P.L.h_enc_skip, X, RSN_ENC_ITS, ln);
         }
       }
@@ -245,7 +247,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
           vals[s] = (u < 17) ? (h ? sh[17 + u] : sh[u]) : 0.0f;
         }
         AUX[it * 64] = make_float4(vals[0], vals[1], vals[2], vals[3]);
-        if (MODE != 0 && it == 0) AUX[5 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!M::F32 && it == 0) AUX[5 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (TRAIN && a.saved.sh && valid)
           *reinterpret_cast<float4*>(a.saved.sh + pc * RSN_K_SH_PAD + it * 8 + 4 * h) =
               make_float4(vals[0], vals[1], vals[2], vals[3]);
@@ -281,16 +283,16 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // saved activations; the encoded-input gradient accumulates in 4 extra blocks (slot order), and the chain
     // through sin(2 pi x f [+ pi/2]) * exp(-var f^2 / 2) is closed per lane (the covariance is a constant here,
     // exactly like the reference, which sets requires_grad on the mean after contraction).
-    // Exact fp32 (MMA 0 and 4): the first GEMM of the sweep, W_{L-1}^T (w_density masked by the bits of layer L-1), runs on the
-    // bf16 MFMAs straight from those bits against V = W_{L-1}^T diag(w_density) in three bf16 pieces: the peeled iteration
-    // l = L-1.  FOLD reads the pieces packed (hT_seed, gemm_bf16_bits); MMA 0, whose packed buffer has no such segment, forms them
-    // in registers (gemm_f32_bits): the same bits.  The skip layer is never the last one (rsn_compute_layout), so that iteration
-    // has no encoded-input GEMM.
+    // Exact fp32 (RSN_MMA_F32 and RSN_MMA_F32_FOLDED): the first GEMM of the sweep, W_{L-1}^T (w_density masked by the bits of
+    // layer L-1), runs on the bf16 MFMAs straight from those bits against V = W_{L-1}^T diag(w_density) in three bf16 pieces: the
+    // peeled iteration l = L-1.  FOLD reads the pieces packed (hT_seed, gemm_bf16_bits); RSN_MMA_F32, whose packed buffer has no
+    // such segment, forms them in registers (gemm_f32_bits): the same bits.  The skip layer is never the last one
+    // (rsn_compute_layout), so that iteration has no encoded-input GEMM.
     // The GEMMs behind it (W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs) run on the bf16 MFMAs too, as all NINE products of
     // three bf16 pieces a side (sweep_gemm): no term of the fp32 product is dropped, only the order of the fp32 accumulation differs.
-    // They run on the 16x16x32 shape (rsn_mfma.h): a lane then reads and writes float4 of OTHER lanes' slots of the wave's X slab,
-    // which needs no barrier -- a wave's LDS instructions complete in order, and no other wave touches the slab.
-    constexpr bool SEED_BITS = TRAIN && MODE == 0;
+    // They run on the 16x16x32 shape (rsn_gemm_loops.h): a lane then reads and writes float4 of OTHER lanes' slots of the wave's X
+    // slab, which needs no barrier -- a wave's LDS instructions complete in order, and no other wave touches the slab.
+    constexpr bool SEED_BITS = TRAIN && M::F32;
     if (TRAIN && a.saved.normals && a.saved.relu_bits) {
       const float* __restrict__ wd = pk + P.L.v_density;
       const bool peel = SEED_BITS && P.num_layers >= 2;  // workgroup-uniform

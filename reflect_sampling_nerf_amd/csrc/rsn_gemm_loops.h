@@ -1,122 +1,14 @@
-// rsn_mfma.h -- device helpers shared by the forward (rsn_field.hip) and backward (rsn_field_bwd.hip) field kernels:
-// the lane-local MFMA K loop over packed weight segments and the accumulator <-> LDS-slab epilogues.
+// rsn_gemm_loops.h -- the per-wave MFMA K loops of the forward (rsn_field_kernel.h) and backward (rsn_field_bwd.hip) field kernels
+// over packed weight segments, with what they load and store through (weight-fragment buffer loads, the saved-row buffer stores, the
+// bf16 splits) and what an rsn_mma_mode means to them (MmaTraits).  The accumulator <-> LDS-slab epilogues are rsn_epilogues.h.
 // See rsn_field.hip for the layout argument (why activations never cross lanes).
 #pragma once
-#include "rsn_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define RSN_MODE_FRUSTUM 0
-#define RSN_MODE_INF 1
-#define RSN_MODE_GAUSS 2
-#define RSN_MODE_EMB 3
-
-// ------------------------------------------------------------------------------------------------
-// small math, written to follow the torch op order of the reference (contraction off: -ffp-contract=off)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// sin / cos of an fp32 argument up to ~1e6 (the IPE reaches 2*pi*2*2^16 = 8.2e5), <= 1.7 ulp -- the quality of ocml's
-// sinf (1.57 ulp measured over the same range) at ~1/5 of its instruction count.  Instead of the branchy Payne-Hanek
-// path the argument is reduced by multiples of pi/2 with a three-constant Cody-Waite scheme on FUSED multiply-adds:
-// pi/2 = C1 + C2 + C3 with C1 = fl32(pi/2); q <= 2^20 is an integer and C1 a multiple of 2^-23, so a - q*C1 is a
-// multiple of 2^-23 below 1 in magnitude and the first fma is EXACT; the second rounds once (2^-25), the third term is
-// 1e-9.  Reduced argument within 3.1e-8 of the true one (measured over 4e6 arguments up to 8.3e5: max |r| 0.87 --
-// the fp32 product a*(2/pi) may pick the neighbouring quadrant, which costs nothing -- and 9.8e-8 / 1.65 ulp on the
-// result).  A degree-7/8 minimax pair is evaluated on the reduced argument.  quad = 0: sin, quad = 1: cos.
-// Round 1 reduced in fp64 (two v_fma_f64 + five conversions per evaluation): same accuracy, ~2x the issue cycles.
-__device__ __forceinline__ float sincos_big(float a, int quad) {
-  const float q = rintf(a * 0.63661977236758134308f);
-  float r = __builtin_fmaf(-q, 1.5707963705062866f, a);
-  r = __builtin_fmaf(-q, -4.371138828673793e-08f, r);
-  r = __builtin_fmaf(-q, -1.7151245100058819e-15f, r);
-  const int n = (int)q + quad;
-  const float s = r * r;
-  const float ps = r + r * s * (-1.6666654611e-1f + s * (8.3321608736e-3f + s * (-1.9515295891e-4f)));
-  const float pc =
-      1.0f + s * (-0.5f + s * (4.166664568298827e-2f + s * (-1.388731625493765e-3f + s * 2.443315711809948e-5f)));
-  const float v = (n & 1) ? pc : ps;
-  return (n & 2) ? -v : v;
-}
-__device__ __forceinline__ float sin_big(float a) { return sincos_big(a, 0); }
-__device__ __forceinline__ float cos_big(float a) { return sincos_big(a, 1); }
-
-// 34 real-SH polynomial terms, bands l = 1, 2, 4, 8 (reflect_sampling_nerf_components.py:65-127), then the
-// per-band roughness attenuation exp(-rho*{1,3,10,36}) (components.py:136-139).
-__device__ __forceinline__ void sh34_attenuated(float x, float y, float z, float rho, float sh[34]) {
-  const float x2 = x * x, y2 = y * y, z2 = z * z;
-  const float xy = x * y, xz = x * z, yz = y * z;
-  const float a = x2 - y2;
-  const float p = 3.0f * x2 - y2;
-  const float q = x2 - 3.0f * y2;
-  const float z4 = z2 * z2, x4 = x2 * x2, y4 = y2 * y2;
-  const float im5 = y4 - 10.0f * x2 * y2 + 5.0f * x4;
-  const float re5 = x4 - 10.0f * x2 * y2 + 5.0f * y4;
-  const float im7 = (x2 - 5.0f * y2) * 7.0f * x4 + (21.0f * x2 - y2) * y4;
-  const float re7 = (x2 - 21.0f * y2) * x4 + (5.0f * x2 - y2) * 7.0f * y4;
-  const float re4 = x2 * q - y2 * p;
-  const float t6 = 143.0f * z4 * z2 - 143.0f * z4 + 33.0f * z2 - 1.0f;
-  const float t7 = 715.0f * z4 * z2 - 1001.0f * z4 + 385.0f * z2 - 35.0f;
-  const float t5 = 39.0f * z4 - 26.0f * z2 + 3.0f;
-  const float t4 = 65.0f * z4 - 26.0f * z2 + 1.0f;
-  const float e1 = expf(-rho), e2 = expf(-rho * 3.0f), e4 = expf(-rho * 10.0f), e8 = expf(-rho * 36.0f);
-  sh[0] = 0.48860251190291992f * y * e1;
-  sh[1] = 0.48860251190291992f * z * e1;
-  sh[2] = 0.48860251190291992f * x * e1;
-  sh[3] = 1.09254843059207907f * xy * e2;
-  sh[4] = 1.09254843059207907f * yz * e2;
-  sh[5] = 0.31539156525252001f * (3.0f * z2 - 1.0f) * e2;
-  sh[6] = 1.09254843059207907f * xz * e2;
-  sh[7] = 0.54627421529603953f * a * e2;
-  sh[8] = 2.50334294179670453f * xy * a * e4;
-  sh[9] = 1.77013076977993053f * yz * p * e4;
-  sh[10] = 0.94617469575756001f * xy * (7.0f * z2 - 1.0f) * e4;
-  sh[11] = 0.66904654355728916f * yz * (7.0f * z2 - 3.0f) * e4;
-  sh[12] = 0.1057855469152043038f * (35.0f * z4 - 30.0f * z2 + 3.0f) * e4;
-  sh[13] = 0.66904654355728916f * xz * (7.0f * z2 - 3.0f) * e4;
-  sh[14] = 0.473087347878780009f * a * (7.0f * z2 - 1.0f) * e4;
-  sh[15] = 1.77013076977993053f * xz * q * e4;
-  sh[16] = 0.62583573544917613f * re4 * e4;
-  sh[17] = 5.83141328139863895f * xy * (x2 * x4 - 7.0f * x4 * y2 + 7.0f * x2 * y4 - y2 * y4) * e8;
-  sh[18] = 5.83141328139863895f * yz * im7 * e8;
-  sh[19] = 1.06466553211908514f * xy * (15.0f * z2 - 1.0f) * (3.0f * x4 - 10.0f * x2 * y2 + 3.0f * y4) * e8;
-  sh[20] = 3.44991062209810801f * yz * (5.0f * z2 - 1.0f) * im5 * e8;
-  sh[21] = 1.91366609903732278f * xy * t4 * a * e8;
-  sh[22] = 1.23526615529554407f * yz * t5 * p * e8;
-  sh[23] = 0.91230451686981894f * xy * t6 * e8;
-  sh[24] = 0.1090412458987799555f * yz * t7 * e8;
-  sh[25] = 0.0090867704915649962938f *
-           (6435.0f * z4 * z4 - 12012.0f * z4 * z2 + 6930.0f * z4 - 1260.0f * z2 + 35.0f) * e8;
-  sh[26] = 0.1090412458987799555f * xz * t7 * e8;
-  sh[27] = 0.456152258434909470f * t6 * a * e8;
-  sh[28] = 1.23526615529554407f * xz * t5 * q * e8;
-  sh[29] = 0.478416524759330697f * t4 * re4 * e8;
-  sh[30] = 3.44991062209810801f * xz * (5.0f * z2 - 1.0f) * re5 * e8;
-  sh[31] = 0.53233276605954257f * (15.0f * z2 - 1.0f) * (x2 * re5 - y2 * im5) * e8;
-  sh[32] = 5.83141328139863895f * xz * re7 * e8;
-  sh[33] = 0.72892666017482986f * (x2 * re7 - y2 * im7) * e8;
-}
-
-// ReLU as ONE instruction: v_max_i32 on the bits (as signed integers every negative float, and -0, is negative; positive floats
-// keep their order) -- from fmaxf / fmed3 hipcc emits v_max(x, x) first (it canonicalises a possible sNaN), two VALU per value in
-// every layer epilogue.  Deliberately NOT inline asm (rounds 1-3 had `asm("v_max_f32 %0, 0, %1")`): the compiler's hazard
-// recogniser does not see an asm operand, and a ReLU placed right behind the MFMA that writes its input reads the register
-// before the matrix pipe has written it (found in rsn_field_x6_train.hip, round 4).  -NaN -> 0, +NaN stays.
-__device__ __forceinline__ float relu_f(float x) {
-  const int xi = __float_as_int(x);
-  return __int_as_float(xi > 0 ? xi : 0);
-}
+#include "rsn_device_math.h"
 
 // Rows kept for the backward pass / the weight gradients.  fp32 rows in the exact and the split-bf16 modes; in the
 // reduced-precision training mode (RSN_MMA_BF16: the GEMMs round these values to bf16 anyway) the wide buffers
 // (activations, bottleneck, mid hidden; layer gradients) are stored AS bf16 -- half the step's HBM stream.  `save`
 // stays a float* in the signatures; SBF reinterprets it as a row of bf16 (element offsets, not bytes).
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-template <bool SBF>
-__device__ __forceinline__ float* row_ptr(float* base, long long elem) {
-  return SBF ? reinterpret_cast<float*>(reinterpret_cast<__bf16*>(base) + elem) : base + elem;
-}
 template <bool SBF>
 __device__ __forceinline__ void put4(float* save, int off, const float4 v) {
   if (SBF) {
@@ -134,8 +26,6 @@ __device__ __forceinline__ void put4(float* save, int off, const float4 v) {
 // cache policy of the saved-row buffer stores (aux bits: 0 = default, 2 = nt): the default policy measured best for the
 // per-wave-stream kernels in round 3 (the LDS-ring training kernels use nt, rsn_ringt.h)
 #define RSN_SAVED_ROW_AUX 0
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 struct RowBuf {
   __amdgpu_buffer_rsrc_t r;
   unsigned voff;
@@ -332,30 +222,6 @@ __device__ __forceinline__ void gemm_run(f32x16 (&acc)[NBO], float4 (&wa)[NBO], 
   }
 }
 
-template <int NBO, int NBT = NBO, bool PF2 = false, class SV = const float*>
-__device__ __forceinline__ void gemm(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const float4* xl, int n_it,
-                                     int lane, SV save = nullptr) {
-  float4 wa[NBO];
-  pre_w<NBO, NBT>(wa, wseg, lane);
-  if (PF2) gemm_run2<NBO, NBT>(acc, wa, wseg, xl, n_it, lane, save); else gemm_run<NBO, NBT>(acc, wa, wseg, xl, n_it, lane, save);
-}
-
-// acc[nb][4q+j] = bias[nb*32 + 8q + 4h + j]: the accumulators start from the bias (what torch's addmm does),
-// so the 4*NBO bias loads are issued back to back ahead of the K loop and the epilogue needs no memory reads.
-template <int NBO>
-__device__ __forceinline__ void init_acc(f32x16 (&acc)[NBO], const float* __restrict__ bias, int h) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 bv = *reinterpret_cast<const float4*>(bias + nb * 32 + 8 * q + 4 * h);
-      acc[nb][4 * q + 0] = bv.x;
-      acc[nb][4 * q + 1] = bv.y;
-      acc[nb][4 * q + 2] = bv.z;
-      acc[nb][4 * q + 3] = bv.w;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Split-bf16 K loop (RSN_MMA_BF16X6 / X3): the same GEMM on v_mfma_f32_32x32x16_bf16.
 // One K=16 step consumes the lane's two float4's of LDS iterations 2kk, 2kk+1 (same lane-local activations as
@@ -364,8 +230,6 @@ __device__ __forceinline__ void init_acc(f32x16 (&acc)[NBO], const float* __rest
 // w3x1 (dropped terms <= 2^-24 relative);  NSPLIT = 2: w1x1, w1x2, w2x1.
 // Weight fragments are double-buffered at half-step granularity (half of the output blocks) to fit the VGPR budget.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct BSplit {
   bf16x8 s1, s2, s3;
 };
@@ -471,139 +335,58 @@ __device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NBO], const float* __res
   }
 }
 
-// dispatch on the MMA mode: MODE 0 = fp32 MFMA over n_it K-iterations of 8, else split-bf16 over ceil(n_it/2) K=16 steps
-template <int MODE, int NBO, int NBT = NBO, bool PF2 = false, class SV = const float*>
-__device__ __forceinline__ void gemm_mode(f32x16 (&acc)[NBO], const float* __restrict__ w32, const float* __restrict__ w16,
-                                          const float4* xl, int n_it, int lane, SV save = nullptr) {
-  static_assert(MODE == 0 || NBT == NBO, "the split-bf16 loops own every output block of their segment");
-  if (MODE == 0) {
-    gemm<NBO, NBT, PF2>(acc, w32, xl, n_it, lane, save);
-  } else {
-    gemm_bf16<NBO, (MODE == 1 ? 3 : (MODE == 2 ? 2 : 1))>(acc, w16, xl, (n_it + 1) / 2, lane);
-  }
-}
+// ------------------------------------------------------------------------------------------------
+// What an rsn_mma_mode (include/rsn.h) means to the per-wave kernels rsn_field_kernel<NB, TRAIN, MMA> and
+// rsn_field_bwd_kernel<NB, MMA>, stated once.  (The template parameter stays an int: the kernels' names carry the number.)
+// ------------------------------------------------------------------------------------------------
+template <int MMA>
+struct MmaTraits {
+  static constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;  // training: the bottleneck folded into mlp_mid (rsn_field_kernel.h)
+  static constexpr int LOOPS = FOLD ? RSN_MMA_F32 : MMA;   // the arithmetic of the K loops: the folded kernels run the exact-fp32 ones
+  static constexpr bool F32 = LOOPS == RSN_MMA_F32;        // fp32 MFMA over K-iterations of 8; else (split) bf16 over K = 16 steps
+  static constexpr int NSPLIT = LOOPS == RSN_MMA_BF16X6 ? 3 : (LOOPS == RSN_MMA_BF16X3 ? 2 : 1);  // bf16 pieces per operand
+  static constexpr bool SAVE_BF16 = LOOPS == RSN_MMA_BF16;  // training: the wide saved rows are stored as bf16 (put4)
+  // training: a saved row leaves from the K loop of the GEMM that READS it (gemm_run's `save`); else from the epilogue that produces it
+  static constexpr bool LOOP_STORES = F32;
+};
 
-// the same with the first fp32 weight fragment fetched early by the caller (pre_mode ... gemm_mode_run); the
-// split-bf16 loops fetch their own first fragment (pre_mode is a no-op for them)
+// the first fp32 weight fragment of a GEMM, fetched early by the caller (pre_mode ... gemm_mode_run); the split-bf16 loops fetch
+// their own first fragment (pre_mode is a no-op for them)
 template <int MODE, int NBO, int NBT = NBO>
 __device__ __forceinline__ void pre_mode(float4 (&wa)[NBO], const float* __restrict__ w32, int lane) {
-  if (MODE == 0) pre_w<NBO, NBT>(wa, w32, lane);
+  if constexpr (MmaTraits<MODE>::F32) pre_w<NBO, NBT>(wa, w32, lane);
 }
 
+// The K loop of the mode: fp32 MFMA over n_it K-iterations of 8, started from the fragment in `wa`; else split-bf16 over
+// ceil(n_it / 2) K = 16 steps (those loops take no saver: their epilogues store).
 template <int MODE, int NBO, int NBT = NBO, bool PF2 = false, class SV = const float*>
 __device__ __forceinline__ void gemm_mode_run(f32x16 (&acc)[NBO], float4 (&wa)[NBO], const float* __restrict__ w32,
                                               const float* __restrict__ w16, const float4* xl, int n_it, int lane,
                                               SV save = nullptr) {
-  static_assert(MODE == 0 || NBT == NBO, "the split-bf16 loops own every output block of their segment");
-  if (MODE == 0) {  // (the split-bf16 loops take no saver: their epilogues store)
-    if (PF2) gemm_run2<NBO, NBT>(acc, wa, w32, xl, n_it, lane, save); else gemm_run<NBO, NBT>(acc, wa, w32, xl, n_it, lane, save);
+  using M = MmaTraits<MODE>;
+  static_assert(M::F32 || NBT == NBO, "the split-bf16 loops own every output block of their segment");
+  if constexpr (!M::F32) gemm_bf16<NBO, M::NSPLIT>(acc, w16, xl, (n_it + 1) / 2, lane);
+  else if constexpr (PF2) gemm_run2<NBO, NBT>(acc, wa, w32, xl, n_it, lane, save);
+  else gemm_run<NBO, NBT>(acc, wa, w32, xl, n_it, lane, save);
+}
+// The same, fetching the first fragment itself.  Only the fp32 loops have one: a fragment array that is never written moved the
+// register allocation of the split kernels (tools/code_object_identity.py), so those go straight to their loop.
+template <int MODE, int NBO, int NBT = NBO, bool PF2 = false, class SV = const float*>
+__device__ __forceinline__ void gemm_mode(f32x16 (&acc)[NBO], const float* __restrict__ w32, const float* __restrict__ w16,
+                                          const float4* xl, int n_it, int lane, SV save = nullptr) {
+  if constexpr (MmaTraits<MODE>::F32) {
+    float4 wa[NBO];
+    pre_w<NBO, NBT>(wa, w32, lane);
+    gemm_mode_run<MODE, NBO, NBT, PF2>(acc, wa, w32, w16, xl, n_it, lane, save);
   } else {
-    gemm_bf16<NBO, (MODE == 1 ? 3 : (MODE == 2 ? 2 : 1))>(acc, w16, xl, (n_it + 1) / 2, lane);
+    gemm_bf16<NBO, MmaTraits<MODE>::NSPLIT>(acc, w16, xl, (n_it + 1) / 2, lane);
   }
 }
-
-template <int NBO>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NBO]) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.0f;
-}
-
-// ReLU sign bits of one lane: bit nb*16 + r = (accumulator register r of block nb, the layer's pre-activation) > 0,
-// packed into NBO/2 words (rsn_field_saved.relu_bits).  The dX sweeps mask by these bits instead of re-reading the
-// saved fp32 activations (1 KiB per point and layer -> 32 B; 124 fewer live registers in the sweeps).
-__device__ __forceinline__ unsigned relu_bits16(const f32x16& a) {
-  // pre-activation x > 0  <=>  the bits of relu(x) (relu_f: one v_max_i32, shared with the ReLU epilogue beside this) are non-zero:
-  // v_min_u32(., 1), then v_lshl_or_b32.  The C forms (`t > 0`, clamp(t, 0, 1)) become v_cmp_lt_i32 (SGPR pair) + a hazard nop +
-  // v_cndmask + v_or3.  The asm takes the relu'd value, NOT the accumulator: an asm operand that is an MFMA result is invisible to
-  // the compiler's hazard recogniser (see relu_f); behind the compiler's own v_max_i32 it is an ordinary VALU result.
-  unsigned b = 0u;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const unsigned lo = __float_as_uint(relu_f(a[r]));
-    unsigned bit;
-    if (r == 0) {
-      asm("v_min_u32 %0, %1, 1" : "=v"(bit) : "v"(lo));
-      b = bit;
-    } else {
-      unsigned nb;
-      asm("v_min_u32 %0, %2, 1\n\tv_lshl_or_b32 %1, %0, %3, %4" : "=&v"(bit), "=v"(nb) : "v"(lo), "n"(r), "v"(b));
-      b = nb;
-    }
-  }
-  return b;
-}
-
-// the same for four relu'd values at bit positions 4 q .. 4 q + 3 (the ReLU epilogues below take the bits from the values they
-// have just formed: no second v_max per value)
-template <int Q>
-__device__ __forceinline__ unsigned relu_bits4q(unsigned b, const float4 v) {
-  const unsigned lo[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    unsigned bit, nb;
-    if (Q == 0 && t == 0) {
-      asm("v_min_u32 %0, %1, 1" : "=v"(bit) : "v"(lo[t]));
-      b = bit;
-    } else if (t == 0) {
-      asm("v_min_u32 %0, %2, 1\n\tv_lshl_or_b32 %1, %0, %3, %4" : "=&v"(bit), "=v"(nb) : "v"(lo[t]), "n"(4 * Q), "v"(b));
-      b = nb;
-    } else if (t == 1) {
-      asm("v_min_u32 %0, %2, 1\n\tv_lshl_or_b32 %1, %0, %3, %4" : "=&v"(bit), "=v"(nb) : "v"(lo[t]), "n"(4 * Q + 1), "v"(b));
-      b = nb;
-    } else if (t == 2) {
-      asm("v_min_u32 %0, %2, 1\n\tv_lshl_or_b32 %1, %0, %3, %4" : "=&v"(bit), "=v"(nb) : "v"(lo[t]), "n"(4 * Q + 2), "v"(b));
-      b = nb;
-    } else {
-      asm("v_min_u32 %0, %2, 1\n\tv_lshl_or_b32 %1, %0, %3, %4" : "=&v"(bit), "=v"(nb) : "v"(lo[t]), "n"(4 * Q + 3), "v"(b));
-      b = nb;
-    }
-  }
-  return b;
-}
-__device__ __forceinline__ unsigned relu_bits4(unsigned b, const float4 v, int q) {  // q: a constant after unrolling
-  return q == 0 ? relu_bits4q<0>(b, v) : (q == 1 ? relu_bits4q<1>(b, v) : (q == 2 ? relu_bits4q<2>(b, v) : relu_bits4q<3>(b, v)));
-}
-
-template <int NBO>
-__device__ __forceinline__ void store_relu_bits(const f32x16 (&acc)[NBO], unsigned* bits) {
-  if (NBO >= 8) {
-#pragma unroll
-    for (int w4 = 0; w4 < NBO / 8; ++w4) {
-      uint4 v;
-      v.x = relu_bits16(acc[w4 * 8 + 0]) | (relu_bits16(acc[w4 * 8 + 1]) << 16);
-      v.y = relu_bits16(acc[w4 * 8 + 2]) | (relu_bits16(acc[w4 * 8 + 3]) << 16);
-      v.z = relu_bits16(acc[w4 * 8 + 4]) | (relu_bits16(acc[w4 * 8 + 5]) << 16);
-      v.w = relu_bits16(acc[w4 * 8 + 6]) | (relu_bits16(acc[w4 * 8 + 7]) << 16);
-      *reinterpret_cast<uint4*>(bits + w4 * 4) = v;
-    }
-  } else {
-#pragma unroll
-    for (int w = 0; w < NBO / 2; ++w) bits[w] = relu_bits16(acc[2 * w]) | (relu_bits16(acc[2 * w + 1]) << 16);
-  }
-}
-
-// the lane's NBO/2 mask words of one layer (issued BEFORE the layer's GEMM, consumed by store_masked_bits after it)
-template <int NBO>
-struct ReluBits {
-  unsigned w[NBO / 2];
-};
-
-template <int NBO>
-__device__ __forceinline__ ReluBits<NBO> load_relu_bits(const unsigned* __restrict__ bits) {
-  ReluBits<NBO> m;
-  if (NBO >= 8) {
-#pragma unroll
-    for (int w4 = 0; w4 < NBO / 8; ++w4) {
-      const uint4 v = *reinterpret_cast<const uint4*>(bits + w4 * 4);
-      m.w[w4 * 4 + 0] = v.x; m.w[w4 * 4 + 1] = v.y; m.w[w4 * 4 + 2] = v.z; m.w[w4 * 4 + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int w = 0; w < NBO / 2; ++w) m.w[w] = bits[w];
-  }
-  return m;
+// the exact-fp32 loop by itself (tools/probes)
+template <int NBO, int NBT = NBO, bool PF2 = false, class SV = const float*>
+__device__ __forceinline__ void gemm(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const float4* xl, int n_it,
+                                     int lane, SV save = nullptr) {
+  gemm_mode<RSN_MMA_F32, NBO, NBT, PF2>(acc, wseg, nullptr, xl, n_it, lane, save);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -615,11 +398,12 @@ __device__ __forceinline__ ReluBits<NBO> load_relu_bits(const unsigned* __restri
 // B operand of K = 16 step kk: element e is K-iteration 2kk + (e >> 2), component e & 3 -- bit (kk & 3) * 8 + e of word kk / 4
 // (store_act: bit nb * 16 + 4 q + j of a lane is K-iteration 4 nb + q, component j).  The word is picked by selects over
 // static register indices (an indexed read would put the words in scratch).
+// BITS: the lane's NBO / 2 mask words of the layer, `w` (ReluBits<NBO>, rsn_epilogues.h).
 struct SeedWords {
   unsigned w0, w1, w2, w3;
 };
-template <int NBO>
-__device__ __forceinline__ SeedWords seed_words(const ReluBits<NBO>& m) {
+template <int NBO, class BITS>
+__device__ __forceinline__ SeedWords seed_words(const BITS& m) {
   static_assert(NBO == 2 || NBO == 4 || NBO == 8, "one, two or four mask words");
   SeedWords s = {m.w[0], 0u, 0u, 0u};
   if constexpr (NBO >= 4) s.w1 = m.w[1];
@@ -648,8 +432,8 @@ __device__ __forceinline__ void mma16_bits(f32x16 (&acc)[NBO], const bf16x8 (&w)
 
 // K = 32 NBO (the layer's output features), NBO row blocks; fragment buffers of half a K step like gemm_bf16 (a full step
 // ahead is 48 fragments = 192 registers beside the 128 accumulator registers: tools/probes/seed_bits_probe.hip measures both)
-template <int NBO>
-__device__ __forceinline__ void gemm_bf16_bits(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const ReluBits<NBO>& m, int lane) {
+template <int NBO, class BITS>
+__device__ __forceinline__ void gemm_bf16_bits(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const BITS& m, int lane) {
   static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
   constexpr int NH = NBO / 2, NK = 2 * NBO;
   const WBuf wp = wbuf_make(wseg, lane);
@@ -720,9 +504,9 @@ __device__ __forceinline__ void mma16_bits_f32(f32x16 (&acc)[NBO], const float4 
 }
 
 // w32seg: wT_x[L-1] ([it][NBO][lane][4]); wd: the packed density row (v_density)
-template <int NBO>
+template <int NBO, class BITS>
 __device__ __forceinline__ void gemm_f32_bits(f32x16 (&acc)[NBO], const float* __restrict__ w32seg, const float* __restrict__ wd,
-                                              const ReluBits<NBO>& m, int lane) {
+                                              const BITS& m, int lane) {
   static_assert(NBO % 2 == 0, "two fragment buffers of NBO / 2 blocks");
   constexpr int NH = NBO / 2, NK = 2 * NBO;
   const WBuf wp = wbuf_make(w32seg, lane);
@@ -758,16 +542,6 @@ __device__ __forceinline__ void gemm_f32_bits(f32x16 (&acc)[NBO], const float* _
 // store_act one float4, K-iteration 4 nb + 2 rh + (L >> 5) of old lane (i + 16 ph) + 32 ((L >> 4) & 1).
 // K must be a multiple of 32 (the kernels pad their widths to 32): no tail path.
 // ------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int NBO>
-__device__ __forceinline__ void zero_acc16(f32x4 (&acc)[NBO][2][2]) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[nb][q >> 1][q & 1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-}
-
 // the lane's place in the 16-shape: the old lane whose operand granules it reads for row half / point half 0 (the other half is
 // 16 old lanes on), and the half K = 32 step it owns
 struct Lane16 {
@@ -969,203 +743,5 @@ __device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const f
     bc[0] = bn[0];
     bc[1] = bn[1];
   }
-}
-
-// bit `pos` of `word` as 0 / 0xffffffff: one v_bfe_i32.  Written as (non-volatile) asm because hipcc rewrites
-// `x & sext(bit)` into v_and (test) + v_cmp_ne + v_cndmask: three VALU per value and a VCC hazard nop, where bfe + and is two.
-__device__ __forceinline__ unsigned bit_mask(int word, int pos) {
-  unsigned m;
-  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(word), "n"(pos));
-  return m;
-}
-
-// dX-sweep epilogue on mask bits: X[it][lane] = bit ? acc : 0 (v_bfe_i32 gives 0 / -1, one v_and applies it);
-// optionally also stored to row `save` (backward pass: the layer's pre-activation gradient for the weight gradients)
-template <int NBO, bool SBF = false, class SV = float*>
-__device__ __forceinline__ void store_masked_bits(const f32x16 (&acc)[NBO], float4* xl, const ReluBits<NBO>& m, int h,
-                                                  SV save = nullptr) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int word = m.w[nb / 2];
-      const int base = (nb & 1) * 16 + 4 * q;
-      float4 v;
-      v.x = __uint_as_float(__float_as_uint(acc[nb][4 * q + 0]) & bit_mask(word, base + 0));
-      v.y = __uint_as_float(__float_as_uint(acc[nb][4 * q + 1]) & bit_mask(word, base + 1));
-      v.z = __uint_as_float(__float_as_uint(acc[nb][4 * q + 2]) & bit_mask(word, base + 2));
-      v.w = __uint_as_float(__float_as_uint(acc[nb][4 * q + 3]) & bit_mask(word, base + 3));
-      xl[(nb * 4 + q) * 64] = v;
-      if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
-    }
-}
-
-// Epilogues of the 16-shape.  One result is one float4 of the X slab (see above); its mask nibble is bits 16 nb + 4 (2 rh + kh) ..
-// + 3 of the ReluBits of the old lane that owns that float4, so a lane holds the words of two old lanes (point halves 0 and 1).
-template <int NBO>
-__device__ __forceinline__ void store_masked_bits16(const f32x4 (&acc)[NBO][2][2], float4* xl, const ReluBits<NBO> (&m)[2], int lane) {
-  const Lane16 g = lane16(lane);
-  float4* xs = xl - lane + g.ol + g.kh * 64;
-#pragma unroll
-  for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-    for (int nb = 0; nb < NBO; ++nb) {
-      const int word = (int)(m[ph].w[nb / 2] >> (4 * g.kh));
-#pragma unroll
-      for (int rh = 0; rh < 2; ++rh) {
-        const int base = (nb & 1) * 16 + 8 * rh;
-        const f32x4& a = acc[nb][rh][ph];
-        float4 v;
-        v.x = __uint_as_float(__float_as_uint(a[0]) & bit_mask(word, base + 0));
-        v.y = __uint_as_float(__float_as_uint(a[1]) & bit_mask(word, base + 1));
-        v.z = __uint_as_float(__float_as_uint(a[2]) & bit_mask(word, base + 2));
-        v.w = __uint_as_float(__float_as_uint(a[3]) & bit_mask(word, base + 3));
-        xs[(nb * 4 + 2 * rh) * 64 + 16 * ph] = v;
-      }
-    }
-}
-
-template <int NBO>
-__device__ __forceinline__ void store_act16(const f32x4 (&acc)[NBO][2][2], float4* xl, int lane) {
-  const Lane16 g = lane16(lane);
-  float4* xs = xl - lane + g.ol + g.kh * 64;
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4& a = acc[nb][q >> 1][q & 1];
-      xs[(nb * 4 + 2 * (q >> 1)) * 64 + 16 * (q & 1)] = make_float4(a[0], a[1], a[2], a[3]);
-    }
-}
-
-// X[it = nb*4+q][lane] = act(acc[nb][4q..4q+3])   (bias already inside acc, see init_acc).
-// save (training): the same float4 also goes to row `save` of a row-major [N, 32*NBS] activation buffer
-// (this lane's point; the four q of one nb complete one 128-B line per row).
-template <int NBO, int NBS, bool RELU, bool SBF = false, class SV = float*>
-__device__ __forceinline__ void store_act(const f32x16 (&acc)[NBO], float4* xl, SV save = nullptr, int h = 0,
-                                          unsigned* bits = nullptr) {
-  unsigned bw[NBS / 2 > 0 ? NBS / 2 : 1];
-#pragma unroll
-  for (int nb = 0; nb < NBS; ++nb) {
-    unsigned b16 = 0u;  // the block's 16 mask bits, taken from the relu'd values as they are formed (dead code without `bits`)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float4 v = make_float4(acc[nb][4 * q + 0], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
-      if (RELU) {
-        v.x = relu_f(v.x);
-        v.y = relu_f(v.y);
-        v.z = relu_f(v.z);
-        v.w = relu_f(v.w);
-        b16 = relu_bits4(b16, v, q);
-      }
-      xl[(nb * 4 + q) * 64] = v;
-      if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
-    }
-    if (RELU) {
-      if (nb & 1) bw[nb / 2] |= b16 << 16; else bw[nb / 2] = b16;
-    }
-  }
-  if (RELU && bits) {
-    if (NBS >= 8) {
-#pragma unroll
-      for (int w4 = 0; w4 < NBS / 8; ++w4)
-        *reinterpret_cast<uint4*>(bits + w4 * 4) = make_uint4(bw[w4 * 4], bw[w4 * 4 + 1], bw[w4 * 4 + 2], bw[w4 * 4 + 3]);
-    } else {
-#pragma unroll
-      for (int w = 0; w < NBS / 2; ++w) bits[w] = bw[w];
-    }
-  }
-}
-
-// store_act of one layer fused with init_acc of the next (same NBO): block by block the accumulators are read out and
-// immediately re-loaded with the next layer's bias, so the bias round trip hides under the rest of the epilogue.
-template <int NBO, bool RELU, bool SBF = false, class SV = float*>
-__device__ __forceinline__ void store_act_init(f32x16 (&acc)[NBO], float4* xl, SV save, int h,
-                                               const float* __restrict__ bias, unsigned* bits = nullptr) {
-  unsigned bw[NBO / 2 > 0 ? NBO / 2 : 1];
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb) {
-    unsigned b16 = 0u;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float4 v = make_float4(acc[nb][4 * q + 0], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3]);
-      if (RELU) {
-        v.x = relu_f(v.x);
-        v.y = relu_f(v.y);
-        v.z = relu_f(v.z);
-        v.w = relu_f(v.w);
-        b16 = relu_bits4(b16, v, q);
-      }
-      xl[(nb * 4 + q) * 64] = v;
-      if (sv_on(save)) sv_put<SBF>(save, nb, q, h, v);
-      const float4 bv = *reinterpret_cast<const float4*>(bias + nb * 32 + 8 * q + 4 * h);
-      acc[nb][4 * q + 0] = bv.x;
-      acc[nb][4 * q + 1] = bv.y;
-      acc[nb][4 * q + 2] = bv.z;
-      acc[nb][4 * q + 3] = bv.w;
-    }
-    if (RELU) {
-      if (nb & 1) bw[nb / 2] |= b16 << 16; else bw[nb / 2] = b16;
-    }
-  }
-  if (RELU && bits) {
-    if (NBO >= 8) {
-#pragma unroll
-      for (int w4 = 0; w4 < NBO / 8; ++w4)
-        *reinterpret_cast<uint4*>(bits + w4 * 4) = make_uint4(bw[w4 * 4], bw[w4 * 4 + 1], bw[w4 * 4 + 2], bw[w4 * 4 + 3]);
-    } else {
-#pragma unroll
-      for (int w = 0; w < NBO / 2; ++w) bits[w] = bw[w];
-    }
-  }
-}
-
-// Prefetch of the ReLU-mask rows (saved post-ReLU activations) of a dX-sweep layer: issued BEFORE the layer's GEMM so
-// that the HBM round trip hides under its MFMAs (consuming them right after the load parked 30 % of the backward
-// kernel's wave cycles in s_waitcnt).
-template <int NBO>
-__device__ __forceinline__ void load_mask(float4 (&mk)[NBO * 4], const float* __restrict__ xin, int h) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) mk[nb * 4 + q] = *reinterpret_cast<const float4*>(xin + (nb * 4 + q) * 8 + 4 * h);
-}
-
-template <int NBO>
-__device__ __forceinline__ void store_masked_pre(const f32x16 (&acc)[NBO], float4* xl, const float4 (&mk)[NBO * 4], int h,
-                                                 float* save = nullptr) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 x = mk[nb * 4 + q];
-      float4 v;
-      v.x = x.x > 0.0f ? acc[nb][4 * q + 0] : 0.0f;
-      v.y = x.y > 0.0f ? acc[nb][4 * q + 1] : 0.0f;
-      v.z = x.z > 0.0f ? acc[nb][4 * q + 2] : 0.0f;
-      v.w = x.w > 0.0f ? acc[nb][4 * q + 3] : 0.0f;
-      xl[(nb * 4 + q) * 64] = v;
-      if (save) *reinterpret_cast<float4*>(save + (nb * 4 + q) * 8 + 4 * h) = v;
-    }
-}
-
-// dX-sweep epilogue: X[it][lane] = (x_in > 0) ? acc : 0 with x_in = the saved post-ReLU input of the layer
-// (row `xin` of a row-major activation buffer); optionally also stored to row `save` (backward pass).
-template <int NBO>
-__device__ __forceinline__ void store_masked(const f32x16 (&acc)[NBO], float4* xl, const float* __restrict__ xin, int h,
-                                             float* save = nullptr) {
-#pragma unroll
-  for (int nb = 0; nb < NBO; ++nb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 x = *reinterpret_cast<const float4*>(xin + (nb * 4 + q) * 8 + 4 * h);
-      float4 v;
-      v.x = x.x > 0.0f ? acc[nb][4 * q + 0] : 0.0f;
-      v.y = x.y > 0.0f ? acc[nb][4 * q + 1] : 0.0f;
-      v.z = x.z > 0.0f ? acc[nb][4 * q + 2] : 0.0f;
-      v.w = x.w > 0.0f ? acc[nb][4 * q + 3] : 0.0f;
-      xl[(nb * 4 + q) * 64] = v;
-      if (save) *reinterpret_cast<float4*>(save + (nb * 4 + q) * 8 + 4 * h) = v;
-    }
 }
 

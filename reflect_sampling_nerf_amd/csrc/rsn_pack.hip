@@ -636,7 +636,7 @@ int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed
   };
   if (d->mma_mode == RSN_MMA_F32 || d->mma_mode == RSN_MMA_F32_FOLDED) {
     // exact fp32: the forward and backward kernels read none of the copies below.  The folded mode splits what the analytic-normal
-    // sweep of its training forward reads (nine-product loop, rsn_mfma.h): the seed, then the transposed trunk and encoded-input
+    // sweep of its training forward reads (nine-product loop, rsn_gemm_loops.h): the seed, then the transposed trunk and encoded-input
     // segments behind it (RSN_MMA_F32 packs nothing more: its training kernel forms the same pieces in registers)
     if (L.hT_seed != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_seed, L.v_density);
     if (d->mma_mode == RSN_MMA_F32_FOLDED) {

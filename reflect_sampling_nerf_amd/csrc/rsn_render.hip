@@ -5,7 +5,7 @@
 // Reference semantics restated: nerfstudio SpacedSampler/PDFSampler/get_weights/renderers (SURVEY
 // §8(a) N5, N7-N11), reflect_sampling_nerf_components.py:14-36 (reciprocal spacing),
 // reflect_sampling_nerf_model.py:215-229,240-241,267-289,312-313,338-339.
-#include "rsn_mfma.h"  // shared device math (sin_big, sh34_attenuated); includes rsn_common.h
+#include "rsn_device_math.h"  // sin_big, sh34_attenuated; includes rsn_common.h
 
 // ---------------------------------------------------------------------------------------------------
 // helpers

@@ -10,7 +10,7 @@
 // permutation, so lane i takes the NKB CONSECUTIVE columns i*NKB .. i*NKB+NKB-1 (block kb = element kb) and
 // the two consecutive rows 2i, 2i+1: one row of X is two global_load_dwordx4 per lane (a half-wave reads
 // 1 KiB contiguous) and dY one dwordx2 -- 3 load instructions per 16 MFMAs instead of 10 (every vector-memory
-// instruction costs the matrix pipe a few cycles, see rsn_mfma.h).  The permutation is undone once, at the
+// instruction costs the matrix pipe a few cycles, see rsn_gemm_loops.h).  The permutation is undone once, at the
 // flush, through a wave-private 2 KiB LDS tile, so that the fp32 atomics keep the full-rate shape (two 128-B
 // row segments per wave instruction, MI355X_MICROARCH.md "Global float atomics").
 //
@@ -26,7 +26,7 @@
 // and the CU count alone, so the same call gives the same bits every time.
 //
 // MFMA-bound: 2 * N * n_out * k_in FLOP; HBM reads N * (n_out + k_in) * 4 B (each operand once per workgroup).
-#include "rsn_mfma.h"
+#include "rsn_device_math.h"
 
 // cache policy of the operand-row loads (buffer-instruction aux bits: 0 = default, 2 = nt)
 #define WG_LOAD_AUX 0

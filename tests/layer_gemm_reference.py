@@ -15,15 +15,15 @@ Families ("f32", "bf16x6", "bf16") and what each one's MFMA operands are:
   f32      the fp32 rows and the fp32 weights themselves (v_mfma_f32_32x32x2_f32).  fold=True: W_c = W_mid[:, 34:] W_b and
            b_c = b_mid + W_mid[:, 34:] b_b formed in fp64 and rounded ONCE to fp32, as rsn_fold_kernel (rsn_pack.hip) leaves them
            (README).
-  bf16x6   the same fp32 rows and weights, each split into three bf16 pieces (rsn_mfma.h: split8; rsn_pack.hip: the layout-2
+  bf16x6   the same fp32 rows and weights, each split into three bf16 pieces (rsn_gemm_loops.h: split8; rsn_pack.hip: the layout-2
            branch of the pack kernel and the split copy kernel; rsn_field_x6_train.hip: the pack2<false> chain), six of the nine piece
            products kept (mma16).  Every piece is a round-to-nearest-even conversion, `(__bf16)x` / v_cvt_pk_bf16_f32.
   bf16     ONE bf16 piece a side, fp32 accumulation from an fp32 bias.  Weights: `(__bf16)v` in the pack kernel of rsn_pack.hip
            (round to nearest even).  Rows: the wide rows (act, bott, hid, dy, d_bott, da_mid) are stored as bf16 and read back
            as stored -- rsn_ring16.h: pack2 (v_cvt_pk_bf16_f32 through __builtin_convertvector, nearest even) on the ring,
-           rsn_mfma.h: put4 / sv_put `(__bf16)v` per wave, and the per-wave GEMM rounds its fp32 LDS copy by split8<1>, the same
+           rsn_gemm_loops.h: put4 / sv_put `(__bf16)v` per wave, and the per-wave GEMM rounds its fp32 LDS copy by split8<1>, the same
            conversion.  Rows kept in fp32 are rounded where the operand is formed: enc / sh of the per-wave instantiation
-           (rsn_mfma.h: split8<1> in gemm_bf16), dz_heads / dz_rgb of both sweeps (rsn_field_bf16_train.hip: pack2<false> into
+           (rsn_gemm_loops.h: split8<1> in gemm_bf16), dz_heads / dz_rgb of both sweeps (rsn_field_bf16_train.hip: pack2<false> into
            XH / X0 of rsn_field_bf16_bwd_kernel; split8<1> per wave) -- nearest even everywhere.  The reference therefore
            applies ONE rounding, to_bf16 below, to every operand of this family (it is the identity on a row that is bf16 already).
 
@@ -52,7 +52,7 @@ import torch
 from tests import field_maths_reference as R
 
 U = 2.0 ** -23
-# bf16x6 (rsn_mfma.h: split8<3>, mma16): x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2), all to nearest even, 8 significant
+# bf16x6 (rsn_gemm_loops.h: split8<3>, mma16): x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2), all to nearest even, 8 significant
 # bits each.  For |x| in [2^e, 2^(e+1)): |x - x1| <= 2^(e-8) (half a bf16 ulp), so |x2| <= 2^-8 |x|; x - x1 is a multiple of the fp32
 # ulp 2^(e-23) and x2 keeps its leading 8 bits to within 2^(e-16), so |x3| <= 2^-16 |x|; what is left is a multiple of 2^(e-23) below
 # 2^(e-16), which fits the 8 bits of x3: the split has NO residual (barring underflow below 2^-126), x = x1 + x2 + x3.  The same

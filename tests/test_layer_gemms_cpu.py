@@ -225,7 +225,7 @@ def test_the_constants_are_the_derived_ones():
     e = (x.bfloat16().double() - x.double()).abs()
     assert bool((e <= G.half_ulp_bf16(x.double())).all()) and bool((e > 2.0 ** -9 * x.double()).any())
     assert 2 * 2.0 ** -24 <= G.C_X6 < 3 * 2.0 ** -24
-    # the split of rsn_mfma.h on random values: pieces to nearest even, the dropped part within C_X6 |w| |x|
+    # the split of rsn_gemm_loops.h on random values: pieces to nearest even, the dropped part within C_X6 |w| |x|
     g = torch.Generator().manual_seed(0)
     w, x = torch.randn(4096, generator=g), torch.randn(4096, generator=g) * 10.0 ** torch.randint(-6, 6, (4096,), generator=g)
 

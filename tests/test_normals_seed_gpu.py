@@ -1,5 +1,5 @@
 """The analytic normals of the exact-fp32 training forward (evaluate_frustums_train on one primary level), whose sweep starts on the
-bf16 MFMAs from the ReLU bits of the last trunk layer against the seed segment hT_seed (gemm_bf16_bits, rsn_mfma.h).
+bf16 MFMAs from the ReLU bits of the last trunk layer against the seed segment hT_seed (gemm_bf16_bits, rsn_gemm_loops.h).
 
 The reference is an fp64 restatement of the sweep on the kernel's own numbers -- its ReLU masks (saved activations > 0), its
 contracted means (the raw-coordinate slots of the saved encoded inputs) and the float32 IPE phases of tests/field_maths_reference.py

@@ -1,4 +1,4 @@
-"""The nine-product GEMMs of the analytic-normal sweep on the 16x16x32 bf16 MFMA shape (rsn_mfma.h: gemm_bf16_s16 over the packed
+"""The nine-product GEMMs of the analytic-normal sweep on the 16x16x32 bf16 MFMA shape (rsn_gemm_loops.h: gemm_bf16_s16 over the packed
 hT_* segments in the folded instantiation, gemm_f32_x9_s16 with the pieces formed in registers in the unfolded one).
 
 tests/test_normals_x9_gpu.py, test_normals_seed_gpu.py and test_fold_bottleneck_gpu.py judge the loop as they judged the 32x32x16

@@ -1,5 +1,5 @@
 """The analytic normals of the exact-fp32 training forward once every GEMM of the sweep runs on the bf16 MFMAs: behind the peeled
-seed GEMM, W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs take all nine products of three bf16 pieces a side (rsn_mfma.h:
+seed GEMM, W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs take all nine products of three bf16 pieces a side (rsn_gemm_loops.h:
 gemm_bf16<.., 3, true> over the packed hT_* segments in the folded instantiation, gemm_f32_x9 with the pieces formed in registers in
 the unfolded one).
 

@@ -2,7 +2,7 @@
 // "wave pairs" -- two waves share one 32-point tile and its LDS slab, each owning half of the output blocks, two
 // 4-wave workgroups per CU -- were built into rsn_field_bwd_kernel, passed the parity tests and ran 5.05 ms against
 // 4.97 ms for the one-wave-per-SIMD kernel; this probe isolates why.)
-// Part 1/2: the K loop alone (rsn_mfma.h: gemm<NBL, NBT>, weights streamed from an L2-resident packed segment, X from an
+// Part 1/2: the K loop alone (rsn_gemm_loops.h: gemm<NBL, NBT>, weights streamed from an L2-resident packed segment, X from an
 // LDS slab, no epilogue, no barriers): NBL output blocks per wave (8 = the product kernels, 4 = wave pairs), 1 or 2
 // workgroups per CU, the product's double-buffered loop against a block-major single-buffer loop (fewer bytes in
 // flight), with the loads removed one at a time.  Part 3: GEMM + the ReLU / LDS / activation-store epilogue per layer.
@@ -15,7 +15,8 @@
 #include <cstdlib>
 #include <vector>
 
-#include "rsn_mfma.h"
+#include "rsn_epilogues.h"
+#include "rsn_gemm_loops.h"
 void rsn_set_error(const char*, ...) {}
 
 // LDS-only barrier of a workgroup (weight prefetches and activation stores stay in flight across it)
@@ -26,7 +27,7 @@ __device__ __forceinline__ void pair_sync() {
 
 #define LAYERS 64  // GEMMs (256 x 256 over 32 points) per wave and launch
 
-// the K loop of rsn_mfma.h (gemm_run) with switches: VAR bit 0: no weight loads (registers), bit 1: no LDS reads,
+// the K loop of rsn_gemm_loops.h (gemm_run) with switches: VAR bit 0: no weight loads (registers), bit 1: no LDS reads,
 // bit 2: every weight load from the same 8 KiB (L1-resident), bit 3: no sched_group_barrier / sched_barrier pinning
 template <int NBO, int NBT, int VAR>
 __device__ __forceinline__ void gemm_var(f32x16 (&acc)[NBO], const float* __restrict__ wseg, const float4* xl, int n_it, int lane) {

@@ -15,7 +15,8 @@
 #include <cstdlib>
 #include <vector>
 
-#include "rsn_mfma.h"
+#include "rsn_epilogues.h"
+#include "rsn_gemm_loops.h"
 void rsn_set_error(const char*, ...) {}
 
 #define GEMMS 64          // 256 x 256 GEMMs per wave and launch

@@ -1,7 +1,7 @@
 // seed_bits_probe.hip -- the first GEMM of the analytic-normal sweep (rsn_field_kernel.h) in isolation: W_{L-1}^T times the
 // density row masked by the ReLU bits of layer L-1, 256 x 256 over a 32-point tile, once as the fp32 loop the kernel had (32
 // seed loads, masks and LDS writes, then gemm<8, 8, PF2> on v_mfma_f32_32x32x2_f32: 1,024 MFMAs of 64 cycles) and once as the
-// bits form (gemm_bf16_bits, rsn_mfma.h: the B operand built from the bits in registers, three pre-split bf16 pieces of
+// bits form (gemm_bf16_bits, rsn_gemm_loops.h: the B operand built from the bits in registers, three pre-split bf16 pieces of
 // V = W^T diag(w_density) per block and K = 16 step: 384 v_mfma_f32_32x32x16_bf16 of 32 cycles).  The bits form streams 384 KiB
 // per wave and tile against 256 KiB, in a fifth of the MFMA cycles: does the 64 B/clk/CU L1 fill eat the gain?
 // Four waves per workgroup, one workgroup per CU, every wave runs only this GEMM for TILES tiles; the four waves start together
@@ -16,7 +16,8 @@
 #include <cstdlib>
 #include <vector>
 
-#include "rsn_mfma.h"
+#include "rsn_epilogues.h"
+#include "rsn_gemm_loops.h"
 void rsn_set_error(const char*, ...) {}
 #define CK(call) do { if ((call) != hipSuccess) { printf("%s failed\n", #call); exit(1); } } while (0)
 

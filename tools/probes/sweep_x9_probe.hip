@@ -29,7 +29,8 @@
 #include <cstring>
 #include <vector>
 
-#include "rsn_mfma.h"
+#include "rsn_epilogues.h"
+#include "rsn_gemm_loops.h"
 void rsn_set_error(const char*, ...) {}
 #define CK(call) do { if ((call) != hipSuccess) { printf("%s failed\n", #call); exit(1); } } while (0)
 
