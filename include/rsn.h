@@ -1049,6 +1049,80 @@ int rsn_pointcloud_select(int32_t n_views, const float* c2w, int32_t height, int
                           float* positions, void* stream);
 
 
+/* ---- decimation: an indexed triangle mesh reduced by vertex clustering (additive to ABI 18: no existing call changes).  A regular
+ * grid of cluster cells covers a box; all vertices in a cell merge into one; triangles that collapse disappear.  The result is
+ * stated step by step so that a numpy restatement reproduces it by bits (tests/decimate_reference.py).
+ *
+ * Inputs: positions fp32 [n_vertices,3] and triangles int32 [n_triangles,3] on the device; origin3 / cell3 HOST arrays; cx, cy, cz
+ * CELLS per axis, each >= 1, cx*cy*cz <= 2^27: cell (i, j, k) spans origin + cell * (i..i+1, j..j+1, k..k+1) and has the flat id
+ * (k*cy + j)*cx + i -- the frame of the point-cloud calls (n cells, n intervals).
+ *
+ * Cell of a vertex, per axis a with n = the cell count of the axis, every step one correctly rounded fp32 operation:
+ *   1. u = (p_a - o_a) / c_a: one subtract, one divide.  A non-finite u (NaN or an infinity) becomes 0.
+ *   2. i = floor(u), clamped to [0, n - 1].  A vertex on an interior cell face belongs to the upper cell; a vertex on the box's upper
+ *      face, or outside the box, to the nearest boundary cell.
+ * Representative of a cell: the mean of EVERY input vertex that falls in it (whether a triangle names the vertex or not), in fixed
+ * point, so that it does not depend on the order of arrival:
+ *   3. f = u - (float)i in fp32;  q = rint(f * 2^20), ties to even, clamped to [0, 2^20].
+ *   4. per cell and axis S_a = the 64-bit integer sum of the q, and m = the int32 number of vertices of the cell.
+ *   5. in fp64, on the widened fp32 o_a and c_a:  r_a = o_a + c_a * ((double)i + ((double)S_a / (double)m) * 2^-20) -- one division,
+ *      an exact scaling, one add, one multiply, one add, none contracted -- rounded once to fp32.
+ * Integer atomic adds (the sums, the member counts and the four counts below) are the only atomics; there is no float atomic.
+ *
+ * Triangles.  Each corner maps to the cell of its vertex.  A triangle with an index outside [0, n_vertices) -- which is never
+ * dereferenced -- or with two corners in one cell is DEGENERATE and dropped.  The others are grouped by the UNORDERED set of their
+ * three cells.  Within a group a triangle is `+` when the cyclic order of its corners is that of the ascending cells, and `-`
+ * otherwise.  With net = n_plus - n_minus the survivors of a group are the first |net| triangles, by original index, of the majority
+ * orientation; net = 0 leaves none.  min(n_plus, n_minus) is the group's number of CANCELLED PAIRS, so that n_triangles = survivors
+ * + degenerate + 2 * cancelled pairs.  This is not "drop duplicates": clustering is a simplicial map and keeps a cycle a cycle only
+ * if opposite pairs cancel and multiplicity is kept; with it a closed input gives an output in which every directed edge (a, b)
+ * occurs exactly as often as (b, a).  Manifoldness and the genus are NOT promised.
+ *
+ * Output.  Vertices: the cells a surviving triangle names, in ascending cell id, at their representative.  Triangles: the survivors
+ * in ascending original index, each with its corners in its own order, renumbered to the new vertex ids.  Same bytes in the same
+ * order from run to run.
+ *
+ * The calls, in this order on one stream, with one workspace (rsn_decimate_workspace_bytes for the same n_vertices, n_triangles and
+ * cell counts, 8-byte aligned, contents irrelevant before the first call and kept by the caller between the calls) and one counts
+ * array, int32 [5] on the device: [0] vertices out, [1] triangles out, [2] degenerate triangles, [3] cancelled pairs, [4] occupied
+ * cells.
+ *   rsn_decimate_cluster  zeroes counts; finds the cell of every vertex and the RANK of every occupied cell among the occupied
+ *       cells in ascending id (counts[4] = their number); writes keys int64 [n_triangles]: for a triangle with ranks r0 < r1 < r2,
+ *       r0 * 2^42 + r1 * 2^21 + r2; for a degenerate one 2^63 - 1, and counts[2] = their number.
+ *   the caller sorts the keys STABLY in ascending order (signed 64-bit) and keeps the sorted keys and, as int64, the original index
+ *       of every sorted entry (what torch.sort(keys, stable=True) returns).  It is the one step left to the caller.
+ *   rsn_decimate_resolve  applies the group rule: counts[1] and counts[3].  Once per rsn_decimate_cluster call (it adds to the
+ *       counts).  One lane walks a group, so its time grows with the largest number of triangles that share three cells.
+ *       An entry of `order` outside [0, n_triangles) is skipped, never dereferenced.  Enough for a caller that only wants
+ *       the number of survivors.
+ *   rsn_decimate_count  numbers the surviving triangles and the cells they name: counts[0], and counts[1] again.  The caller reads
+ *       counts once, here, to size the outputs -- as with rsn_mesh_count / rsn_mesh_emit.
+ *   rsn_decimate_emit  sums the vertices of the named cells and writes out_positions fp32 [counts[0],3] and out_triangles int32
+ *       [counts[1],3], but only vertices < max_vertices and triangles < max_triangles: never a byte past either capacity; an output
+ *       with capacity 0 may be NULL, and with both capacities 0 nothing is launched.
+ * The ranks must fit 21 bits.  The number of occupied cells is known on the device only and the library never reads it back: when
+ * counts[4] exceeds 2^21 no triangle is grouped, counts[1..3] stay 0 and the caller must treat the call as refused
+ * (RSN_ERR_UNSUPPORTED is what the package raises); nothing is written out of bounds.  min(n_vertices, cx*cy*cz) <= 2^21 rules it out.
+ *
+ * All calls: RSN_ERR_INVALID_ARGUMENT before any launch, with the reason in rsn_last_error(): a cell count below 1; a negative
+ * n_vertices or n_triangles; with both counts positive a NULL workspace (or one not 8-byte aligned), positions, triangles, keys,
+ * sorted_keys, order or counts, or an output with a capacity above 0; a NULL origin3 or cell3; an origin that is not finite; a cell
+ * size that is not finite or not above 0; a negative capacity.  RSN_ERR_UNSUPPORTED for cx*cy*cz > 2^27 (the size call returns 0
+ * with a message for these); RSN_ERR_WORKSPACE for a workspace_bytes below the size.  n_vertices == 0 or n_triangles == 0 launches
+ * nothing: rsn_decimate_cluster then only zeroes counts.  No allocation, no synchronisation and no host read. */
+size_t rsn_decimate_workspace_bytes(int32_t n_vertices, int32_t n_triangles, int32_t cx, int32_t cy, int32_t cz);
+int rsn_decimate_cluster(int32_t n_vertices, const float* positions, int32_t n_triangles, const int32_t* triangles,
+                         const float* origin3, const float* cell3, int32_t cx, int32_t cy, int32_t cz, void* workspace,
+                         size_t workspace_bytes, int64_t* keys, int32_t* counts, void* stream);
+int rsn_decimate_resolve(int32_t n_vertices, int32_t n_triangles, int32_t cx, int32_t cy, int32_t cz, const int64_t* sorted_keys,
+                         const int64_t* order, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+int rsn_decimate_count(int32_t n_vertices, int32_t n_triangles, const int32_t* triangles, int32_t cx, int32_t cy, int32_t cz,
+                       void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+int rsn_decimate_emit(int32_t n_vertices, const float* positions, int32_t n_triangles, const int32_t* triangles, const float* origin3,
+                      const float* cell3, int32_t cx, int32_t cy, int32_t cz, void* workspace, size_t workspace_bytes,
+                      int32_t max_vertices, int32_t max_triangles, float* out_positions, int32_t* out_triangles, void* stream);
+
+
 /* ---- texture atlas: where on an indexed triangle mesh every texel of a per-triangle atlas samples the field (additive to ABI 18:
  * no existing call changes).  The field's material maps are then baked at those points, finer than the mesh's vertices.
  *

@@ -261,6 +261,15 @@ _SIGNATURES = {
                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                         _fp, C.c_void_p]),
+    "rsn_decimate_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rsn_decimate_cluster": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rsn_decimate_resolve": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rsn_decimate_count": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_void_p]),
+    "rsn_decimate_emit": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, _fp, C.c_void_p, C.c_void_p]),
     "rsn_texture_points": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _fp, _fp, C.c_void_p]),
     "rsn_normal_error_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "rsn_normal_error": (C.c_int, [C.c_int32, _fp, _fp, C.c_void_p, C.c_void_p, _fp, _fp, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),

@@ -27,6 +27,11 @@ min_weight 1, are starting points from an experiment on analytic depth maps of a
 
 With --texture either route ends in write_obj of texture.py instead of write_ply: the same four quantities, sampled per texel of a
 per-triangle atlas instead of per vertex (texture_atlas -> bake_textures).  Its defaults have not been measured on a scene either.
+
+    ... export-mesh ... [--decimate-cells N | --target-faces N]
+
+With either flag the extracted (and, on the tsdf route, filtered) mesh is reduced by vertex clustering before vertex_attributes
+(decimate.py): extract fine, reduce to a budget, let the texture carry the detail.  Without them nothing changes.
 """
 from __future__ import annotations
 
@@ -288,7 +293,8 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
                 iso: float = DEFAULT_ISO, mma: str = "f32", chunk: int = DEFAULT_CHUNK, device="cuda:0",
                 model_config=None, method: str = "density", cameras: Optional[dict] = None, trunc: Optional[float] = None,
                 min_weight: float = DEFAULT_MIN_WEIGHT, views_per_launch: int = 8, ray_chunk: int = DEFAULT_RAY_CHUNK,
-                texture: bool = False, texels: int = 8, min_footprint: Optional[float] = None) -> dict:
+                texture: bool = False, texels: int = 8, min_footprint: Optional[float] = None,
+                decimate_cells: Optional[int] = None, target_faces: Optional[int] = None) -> dict:
     """Checkpoint (a step-*.ckpt, or a run directory: its newest) -> PLY at `out` (texture=True: a textured OBJ, see below).  -> dict with the counts, the grid, the method
     and the seconds per stage.
     method "density": the iso-surface of the field's density at `iso`; stages: grid evaluation, count, emit, attributes on the
@@ -301,7 +307,22 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
     texture=True (either method): `out` must end in .obj and becomes a textured OBJ with its MTL and four PNG maps beside it
     (texture.py) instead of a PLY; texels: the side of the square of texels a pair of triangles gets; min_footprint: the smallest
     footprint a texel is queried with (None: the largest spacing / 8) -- both defaults are starting points, not measured on a
-    scene.  The stages atlas and bake join the seconds, texture_size, texels, live_texels, min_footprint and files the dict."""
+    scene.  The stages atlas and bake join the seconds, texture_size, texels, live_texels, min_footprint and files the dict.
+    decimate_cells=N or target_faces=N (one of them at most; either method, with or without texture): the extracted mesh -- on the
+    tsdf route after its filter, which needs vert_key -- is reduced by vertex clustering before anything else sees it (decimate.py):
+    with N cluster cells per axis over `bounds`, or with the cell count decimate_to finds for at most N triangles, looking from 2 up
+    to the grid's intervals per axis (finer clusters than the grid merge nothing).  The attributes of the merged vertices are then
+    queried with the CLUSTER CELL as `spacing` of vertex_attributes -- a merged vertex stands for a cell; a design rule that has not
+    been measured against a scene.  The texture bake is unchanged: it sees a mesh.  The dict gains vertices_extracted /
+    triangles_extracted (where the tsdf route has not set them), `decimate` (decimate.py's stats) and the stage decimate."""
+    decimating = decimate_cells is not None or target_faces is not None
+    if decimating:
+        from . import decimate as dec
+
+        if decimate_cells is not None and target_faces is not None:
+            raise ValueError("decimate_cells and target_faces exclude each other")
+        if (decimate_cells if target_faces is None else target_faces) < 1:
+            raise ValueError(f"decimate_cells {decimate_cells} / target_faces {target_faces}: need a value of at least 1")
     if texture:
         from . import texture as tex
 
@@ -336,7 +357,18 @@ def export_mesh(ckpt: str, out: str, resolution: Union[int, Sequence[int]] = 256
                      "image": [int(cameras["width"]), int(cameras["height"])]}
             mesh = drop_unobserved(mesh, weight, (nx, ny, nz), min_weight)
             stages("filter")
-        mesh.update(vertex_attributes(field, mesh["positions"], spacing, chunk))
+        attribute_spacing = spacing
+        if decimating:
+            extra.setdefault("vertices_extracted", int(mesh["positions"].shape[0]))
+            extra.setdefault("triangles_extracted", int(mesh["triangles"].shape[0]))
+            if target_faces is not None:
+                mesh, extra["decimate"] = dec.decimate_to(mesh, bounds, target_faces, max(2, max(nx, ny, nz) - 1))
+            else:
+                mesh = dec.decimate(mesh, bounds, decimate_cells)
+                extra["decimate"] = mesh.pop("stats")
+            attribute_spacing = np.asarray(extra["decimate"]["cell_size"], dtype=np.float32)
+            stages("decimate")
+        mesh.update(vertex_attributes(field, mesh["positions"], attribute_spacing, chunk))
         stages("attributes")
         if texture:
             attributes = tex.field_attributes(field, spacing, footprint_lo, chunk)

@@ -5,6 +5,7 @@
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
     python -m reflect_sampling_nerf_amd.trainer export-mesh ... --out mesh.obj --texture [--texels 8] [--min-footprint F]
+    python -m reflect_sampling_nerf_amd.trainer export-mesh ... [--decimate-cells N | --target-faces N]
     python -m reflect_sampling_nerf_amd.trainer export-pointcloud --ckpt FILE|DIR --out cloud.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--resolution 512] [--min-accumulation 0.5] [--edge 0.05 | --no-edge] [--no-thin]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
     (eval and render: [--skip-empty | --skip-empty-samples [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
@@ -72,6 +73,10 @@ colour, tint, roughness and the object-space predicted normal -- in which every 
 texels and the field is queried once per texel, with a footprint no smaller than --min-footprint.  The maps are the field's material
 decomposition, not a rendered colour.  The defaults, 8 texels and the largest grid spacing / 8, are starting points, not measured on
 a scene.
+With `--decimate-cells N` or `--target-faces N` either method reduces the extracted mesh by vertex clustering before it is coloured
+or textured (decimate.py): N cluster cells per axis over --bounds, or the cell count that leaves at most N triangles.  The merged
+vertices are queried with the cluster cell as footprint; that rule, the effect on appearance and the quality against an edge-collapse
+simplifier have not been measured.  Without the two flags nothing is reduced.
 
 `export-pointcloud` writes the surface the model renders as points (pointcloud.py): one point per pixel of the depth maps rendered
 from the cameras of --data's split or of --poses, origin + depth_fine * direction -- where the model starts its reflected rays --, for
@@ -263,6 +268,13 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ex.add_argument("--min-footprint", type=float, default=None, metavar="F",
                     help="texture: the smallest footprint, in world units, a texel is queried with (default the largest grid spacing "
                          "/ 8: a starting point, not measured on a scene)")
+    ex.add_argument("--decimate-cells", type=int, default=None, metavar="N",
+                    help="reduce the extracted mesh by vertex clustering with N cluster cells per axis over --bounds (decimate.py); "
+                         "the merged vertices' attributes are queried with the cluster cell as footprint (a design rule, not measured "
+                         "on a scene).  No default: without this flag and --target-faces nothing is reduced")
+    ex.add_argument("--target-faces", type=int, default=None, metavar="N",
+                    help="reduce the extracted mesh by vertex clustering to at most N triangles: the cell count is searched from 2 up "
+                         "to the grid's intervals per axis.  Excludes --decimate-cells")
     pc = sub.add_parser("export-pointcloud", help="write the surface a checkpoint's model renders as a coloured point cloud (PLY without faces)")
     pc.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
     pc.add_argument("--out", required=True, help="output file (binary little-endian PLY, vertex element only)")
@@ -409,6 +421,22 @@ def resolve_texture_args(ap: argparse.ArgumentParser, args) -> None:
             texture.footprint_bounds(spacing, args.min_footprint)
         except ValueError as e:
             ap.error(f"export-mesh: --min-footprint {args.min_footprint}: {e}")
+
+
+def resolve_decimate_args(ap: argparse.ArgumentParser, args) -> dict:
+    """The decimation flags of an `export-mesh` command line -> the keyword arguments export_mesh takes for them ({} without the
+    flags): --decimate-cells and --target-faces exclude each other and take values of at least 1; --target-faces searches up to the
+    grid's intervals per axis, so it needs a --resolution of at least 3.  Host work only; what cannot work is an argparse error."""
+    cells, faces = args.decimate_cells, args.target_faces
+    if cells is not None and faces is not None:
+        ap.error("export-mesh: --decimate-cells and --target-faces exclude each other")
+    if cells is not None and cells < 1:
+        ap.error(f"export-mesh: --decimate-cells {cells}: need a value of at least 1")
+    if faces is not None and faces < 1:
+        ap.error(f"export-mesh: --target-faces {faces}: need a value of at least 1")
+    if faces is not None and args.resolution < 3:
+        ap.error(f"export-mesh: --target-faces searches from 2 cells per axis up to the grid's intervals: --resolution {args.resolution} has fewer")
+    return {k: v for k, v in (("decimate_cells", cells), ("target_faces", faces)) if v is not None}
 
 
 def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
@@ -827,6 +855,7 @@ def main(argv=None) -> int:
     occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
     if args.command == "export-mesh":
         resolve_texture_args(ap, args)
+        decimate_args = resolve_decimate_args(ap, args)
     export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
     cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
@@ -862,6 +891,7 @@ def main(argv=None) -> int:
                       mma=args.mma, chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
         if args.texture:
             common.update(texture=True, texels=8 if args.texels is None else args.texels, min_footprint=args.min_footprint)
+        common.update(decimate_args)
         if args.method == "tsdf":
             res = mesh.export_mesh(args.ckpt, args.out, method="tsdf", cameras=export_cameras, trunc=args.trunc,
                                    min_weight=mesh.DEFAULT_MIN_WEIGHT if args.min_weight is None else args.min_weight,
@@ -874,6 +904,13 @@ def main(argv=None) -> int:
             what = f"at sigma = {res['iso']:g}"
             stages = ("grid", "count", "emit", "attributes", "write")
         sec = res["seconds"]
+        if decimate_args:
+            d = res["decimate"]
+            stages = stages[:stages.index("attributes")] + ("decimate",) + stages[stages.index("attributes"):]
+            what += (f", clustered from {d['triangles_in']} triangles with {' x '.join(str(n) for n in d['cells'])} cells "
+                     f"({d['degenerate']} collapsed, {d['cancelled_pairs']} opposite pairs cancelled"
+                     + (f", {len(d['probes'])} probes for at most {d['target_faces']}" + (": NOT reached" if d["over_budget"] else "")
+                        if "probes" in d else "") + ")")
         if args.texture:
             stages = stages[:-1] + ("atlas", "bake", "write")
             what += (f", textured with {res['texture_size']} x {res['texture_size']} texels ({res['live_texels']} live, "
