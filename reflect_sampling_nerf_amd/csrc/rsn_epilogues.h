@@ -163,6 +163,99 @@ __device__ __forceinline__ void store_act16(const f32x4 (&acc)[NBO][2][2], float
     }
 }
 
+// The training forward's trunk on the 16-shape (exact fp32, rsn_field_kernel.h).  Bias start: register r of result (nb, rh, ph) is
+// row 32 nb + 16 rh + 4 (L >> 4) + r, the same for both point halves.
+template <int NBO>
+__device__ __forceinline__ void init_acc16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ bias, int lane) {
+  const float* __restrict__ bl = bias + 4 * (lane >> 4);
+#pragma unroll
+  for (int nb = 0; nb < NBO; ++nb)
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh) {
+      const float4 bv = *reinterpret_cast<const float4*>(bl + nb * 32 + 16 * rh);
+      acc[nb][rh][0] = acc[nb][rh][1] = f32x4{bv.x, bv.y, bv.z, bv.w};
+    }
+}
+
+// ReLU epilogue of the 16-shape: store_act16 of the relu'd values, and the layer's mask words in ReluBits' layout.  The nibble of
+// result (nb, rh, ph) is bits 16 (nb & 1) + 4 (2 rh + kh) .. + 3 of word nb / 2 of old lane (L & 15) + 16 ph + 32 ((L >> 4) & 1):
+// lanes L and L ^ 32 hold the alternate nibbles (kh = 0 / 1) of the same words.  Each lane collects its nibbles per point half
+// (relu_bits4 at q = 2 rh, then shifted by 4 kh), hands the half it does not store to its partner (one 32-lane exchange per word)
+// and stores the words of point half kh: `bits` is that old lane's slot, (point (L & 15) + 16 kh, half (L >> 4) & 1), or nullptr.
+// REINIT: block by block the accumulators restart from the next layer's bias (init_acc16), like store_act_init.
+template <int NBO, bool REINIT>
+__device__ __forceinline__ void store_act16_relu_body(f32x4 (&acc)[NBO][2][2], float4* xl, int lane, const float* __restrict__ bias,
+                                                      unsigned* bits) {
+  static_assert(NBO % 2 == 0, "whole mask words");
+  const Lane16 g = lane16(lane);
+  float4* xs = xl - lane + g.ol + g.kh * 64;
+  const float* __restrict__ bl = bias + 4 * (lane >> 4);
+  unsigned bw[2][NBO / 2];
+#pragma unroll
+  for (int nb = 0; nb < NBO; ++nb) {
+    unsigned b16[2] = {0u, 0u};
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh) {
+#pragma unroll
+      for (int ph = 0; ph < 2; ++ph) {
+        const f32x4& a = acc[nb][rh][ph];
+        const float4 v = make_float4(relu_f(a[0]), relu_f(a[1]), relu_f(a[2]), relu_f(a[3]));
+        b16[ph] = relu_bits4(b16[ph], v, 2 * rh);
+        xs[(nb * 4 + 2 * rh) * 64 + 16 * ph] = v;
+      }
+      if constexpr (REINIT) {
+        const float4 bv = *reinterpret_cast<const float4*>(bl + nb * 32 + 16 * rh);
+        acc[nb][rh][0] = acc[nb][rh][1] = f32x4{bv.x, bv.y, bv.z, bv.w};
+      }
+    }
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph) {
+      if (nb & 1) bw[ph][nb / 2] |= b16[ph] << 16; else bw[ph][nb / 2] = b16[ph];
+    }
+  }
+  unsigned ow[NBO / 2];
+#pragma unroll
+  for (int w = 0; w < NBO / 2; ++w) {
+    const unsigned keep = (g.kh ? bw[1][w] : bw[0][w]) << (4 * g.kh);
+    const unsigned give = (g.kh ? bw[0][w] : bw[1][w]) << (4 * g.kh);
+    ow[w] = keep | (unsigned)__shfl_xor((int)give, 32, 64);
+  }
+  if (bits) {
+    if (NBO >= 8) {
+#pragma unroll
+      for (int w4 = 0; w4 < NBO / 8; ++w4)
+        *reinterpret_cast<uint4*>(bits + w4 * 4) = make_uint4(ow[w4 * 4], ow[w4 * 4 + 1], ow[w4 * 4 + 2], ow[w4 * 4 + 3]);
+    } else {
+#pragma unroll
+      for (int w = 0; w < NBO / 2; ++w) bits[w] = ow[w];
+    }
+  }
+}
+template <int NBO>
+__device__ __forceinline__ void store_act16_relu(f32x4 (&acc)[NBO][2][2], float4* xl, int lane, unsigned* bits) {
+  store_act16_relu_body<NBO, false>(acc, xl, lane, nullptr, bits);
+}
+template <int NBO>
+__device__ __forceinline__ void store_act16_relu_init(f32x4 (&acc)[NBO][2][2], float4* xl, int lane, const float* __restrict__ bias,
+                                                      unsigned* bits) {
+  store_act16_relu_body<NBO, true>(acc, xl, lane, bias, bits);
+}
+
+// the accumulators of the fp32 loop back from the slab: the inverse of store_act without activation (the lane's own float4)
+template <int NBO>
+__device__ __forceinline__ void load_acc(f32x16 (&acc)[NBO], const float4* xl) {
+#pragma unroll
+  for (int nb = 0; nb < NBO; ++nb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 v = xl[(nb * 4 + q) * 64];
+      acc[nb][4 * q + 0] = v.x;
+      acc[nb][4 * q + 1] = v.y;
+      acc[nb][4 * q + 2] = v.z;
+      acc[nb][4 * q + 3] = v.w;
+    }
+}
+
 // X[it = nb*4+q][lane] = act(acc[nb][4q..4q+3])   (bias already inside acc, see init_acc).
 // save (training): the same float4 also goes to row `save` of a row-major [N, 32*NBS] activation buffer
 // (this lane's point; the four q of one nb complete one 128-B line per row).

@@ -2,7 +2,7 @@
 // units that differ in ONE compiler flag (reflect_sampling_nerf_amd/_build.py, SOURCE_FLAGS):
 //   rsn_field.hip        exact fp32 (RSN_MMA_F32, RSN_MMA_F32_FOLDED) and plain-bf16 training (RSN_MMA_BF16): MFMA accumulators in
 //                        architected VGPRs (-amdgpu-mfma-vgpr-form: the epilogues touch every accumulator; no v_accvgpr copies, no
-//                        scratch);
+//                        scratch -- but for the two NB = 8 exact-fp32 training kernels, which hold both trunk paths: DESIGN 4.3);
 //   rsn_field_split.hip  split-bf16 (RSN_MMA_BF16X6, RSN_MMA_BF16X3): hipcc's default AGPR accumulators -- these kernels also hold
 //                        the bf16 triples of the operands, and in VGPR form their training forward runs 14 % slower.
 // The K loops are rsn_gemm_loops.h (with MmaTraits: what a mode means), the epilogues rsn_epilogues.h.
@@ -25,11 +25,14 @@ __device__ __forceinline__ void sweep_gemm(f32x16 (&acc)[NBO], const float* __re
                                            const float4* xl, int n_it, int lane) {
   gemm_mode<MODE, NBO, NBO, true>(acc, w32, w16, xl, n_it, lane);
 }
-template <bool PACKED, int N_IT, int NBO>
+// The W x W GEMMs of the training forward's trunk (layers l >= 1, the x part) go the same way, over h_x[l] / w_x[l], with `save`:
+// the rows of act[l-1] leave from the K loop that reads them.
+template <bool PACKED, int N_IT, int NBO, class SV = const float*>
 __device__ __forceinline__ void sweep_gemm(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32, const float* __restrict__ w16,
-                                           const float4* xl, int lane) {
+                                           const float4* xl, int lane, SV save = nullptr) {
   static_assert(N_IT % 4 == 0, "K = 8 N_IT is a multiple of 32 at every width (the units are padded to 32): no tail path");
-  if constexpr (PACKED) gemm_bf16_s16<NBO>(acc, w16, xl, N_IT / 4, lane); else gemm_f32_x9_s16<NBO>(acc, w32, xl, N_IT / 4, lane);
+  if constexpr (PACKED) gemm_bf16_s16<NBO>(acc, w16, xl, N_IT / 4, lane, save);
+  else gemm_f32_x9_s16<NBO>(acc, w32, xl, N_IT / 4, lane, save);
 }
 
 template <int NB, bool TRAIN, int MMA>
@@ -158,7 +161,73 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     }
 
     // ---------------- trunk -----------------
-    {
+    // Exact-fp32 training (RSN_MMA_F32 and RSN_MMA_F32_FOLDED): the W x W GEMM of every layer l >= 1 (its x part) runs as nine bf16
+    // products on the 16x16x32 shape (sweep_gemm: FOLD over the packed pieces h_x[l], else the same pieces formed in registers from
+    // w_x[l] -- the same bits), its accumulators started from the bias in that shape's layout (init_acc16) and left through
+    // store_act16_relu, which writes the slab and the mask words exactly where store_act does.  Layer 0 and the encoded-input part
+    // of the skip layer stay on the fp32 loop (K = 104 is no multiple of 32).  The skip layer's x part moves too: its accumulators
+    // change layout once through the wave's own slab (store_act16, load_acc) before the encoded-input GEMM adds to them.
+    // The jobs of a training step take this path (conical frustums, get_inf_color).  The explicit-Gaussian job of the granular
+    // Field API keeps the fp32 loop (workgroup-uniform branch): get_density(.., requires_density_grad) hands out the bits of the
+    // plain forward, which runs the eval kernel (tests/test_gpu_parity.py holds the two equal).
+    bool s16 = false;
+    if constexpr (TRAIN && M::F32) s16 = a.mode == RSN_MODE_FRUSTUM || a.mode == RSN_MODE_INF;
+    if (s16) {
+     if constexpr (TRAIN && M::F32) {
+      // the mask words this lane stores from the 16-shape: point (L & 15) + 16 (L >> 5), half (L >> 4) & 1 (store_act16_relu)
+      auto bits16_st = [&](int l) -> unsigned* {
+        const long long q = p0 + (ln & 15) + 16 * (ln >> 5);
+        if (!a.saved.relu_bits || q >= n_points) return nullptr;
+        return a.saved.relu_bits + ((((long long)l * (a.act_stride / W)) + q) * 2 + ((ln >> 4) & 1)) * (NB / 2 > 2 ? NB / 2 : 2);
+      };
+      auto rb_loop16 = [&](float* base, long long elem, int row_elems) {
+        return rowbuf<false>(base, elem, rows, row_elems, ln & 15, (ln >> 4) & 1);
+      };
+      {
+        f32x16 acc[NB];
+        float4 wpre[NB];
+        pre_mode<MODE, NB>(wpre, pk + P.L.w_enc0, ln);
+        init_acc<NB>(acc, pk + P.L.b[0], h);
+        gemm_mode_run<MODE, NB, NB, TRAIN>(acc, wpre, pk + P.L.w_enc0, pk + P.L.h_enc0, X, RSN_ENC_ITS, ln);
+        if (P.num_layers == 1) pre_mode<MODE, NBH>(wbh, w_bh, ln);
+        store_act<NB, NB, true, false>(acc, X, rb_epi(a.saved.act, p0 * W, W), h, (a.saved.relu_bits && valid) ? bits_at(0) : nullptr);
+      }
+      if (P.num_layers > 1) {
+        f32x4 a16[NB][2][2];
+        init_acc16<NB>(a16, pk + P.L.b[1], ln);
+#pragma unroll 1
+        for (int l = 1; l < P.num_layers; ++l) {
+          sweep_gemm<FOLD, NB * 4, NB>(a16, pk + P.L.w_x[l], pk + P.L.h_x[l], X, ln,
+                                       rb_loop16(a.saved.act, (l - 1) * a.act_stride + p0 * W, W));
+          const bool last = l + 1 == P.num_layers;
+          if (l == P.skip_layer) {
+            f32x16 acc[NB];
+            float4 wpre[NB];
+            pre_mode<MODE, NB>(wpre, pk + P.L.w_enc_skip, ln);
+            store_act16<NB>(a16, X, ln);
+            load_acc<NB>(acc, X);
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+              X[it * 64] = make_float4(st0[4 * it], st0[4 * it + 1], st0[4 * it + 2], st0[4 * it + 3]);
+              X[(4 + it) * 64] = make_float4(st1[4 * it], st1[4 * it + 1], st1[4 * it + 2], st1[4 * it + 3]);
+              X[(8 + it) * 64] = make_float4(st2[4 * it], st2[4 * it + 1], st2[4 * it + 2], st2[4 * it + 3]);
+            }
+            X[12 * 64] = st3;
+            gemm_mode_run<MODE, NB, NB, TRAIN>(acc, wpre, pk + P.L.w_enc_skip, pk + P.L.h_enc_skip, X, RSN_ENC_ITS, ln);
+            if (last) pre_mode<MODE, NBH>(wbh, w_bh, ln);
+            store_act<NB, NB, true, false>(acc, X, rb_epi(a.saved.act, p0 * W, W), h,
+                                           (a.saved.relu_bits && valid) ? bits_at(l) : nullptr);
+            if (!last) init_acc16<NB>(a16, pk + P.L.b[l + 1], ln);
+          } else if (!last) {
+            store_act16_relu_init<NB>(a16, X, ln, pk + P.L.b[l + 1], bits16_st(l));
+          } else {
+            pre_mode<MODE, NBH>(wbh, w_bh, ln);
+            store_act16_relu<NB>(a16, X, ln, bits16_st(l));
+          }
+        }
+      }
+     }
+    } else {
       f32x16 acc[NB];
       float4 wpre[NB];  // first weight fragment of the next GEMM, fetched ahead of the epilogue in front of it
       pre_mode<MODE, NB>(wpre, pk + P.L.w_enc0, ln);

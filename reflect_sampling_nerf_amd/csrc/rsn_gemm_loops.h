@@ -341,7 +341,9 @@ __device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NBO], const float* __res
 // ------------------------------------------------------------------------------------------------
 template <int MMA>
 struct MmaTraits {
-  static constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;  // training: the bottleneck folded into mlp_mid (rsn_field_kernel.h)
+  // training: the bottleneck folded into mlp_mid (rsn_field_kernel.h).  The folded kernels also read the packed bf16 pieces of their
+  // buffer: h_x[l] (the forward trunk's W x W GEMMs), hT_seed / hT_x / hT_enc* (the normal sweep), hT_last / hT_x (the backward sweep)
+  static constexpr bool FOLD = MMA == RSN_MMA_F32_FOLDED;
   static constexpr int LOOPS = FOLD ? RSN_MMA_F32 : MMA;   // the arithmetic of the K loops: the folded kernels run the exact-fp32 ones
   static constexpr bool F32 = LOOPS == RSN_MMA_F32;        // fp32 MFMA over K-iterations of 8; else (split) bf16 over K = 16 steps
   static constexpr int NSPLIT = LOOPS == RSN_MMA_BF16X6 ? 3 : (LOOPS == RSN_MMA_BF16X3 ? 2 : 1);  // bf16 pieces per operand
@@ -603,7 +605,7 @@ __device__ __forceinline__ void sv_put16(const RowBuf& b, int it, int ph, bool l
 
 // Packed pieces (hT_* segment, [k16][NBO][piece][lane][8 bf16]).  Fragment buffers of a quarter of the blocks (the 96 registers of
 // gemm_bf16's two half-step buffers); the next step's activations are split under the first two chunks' MFMAs, one point half each.
-// `save` (optional, the backward sweep): every float4 of the slab this GEMM reads leaves once for its saved row -- step 0's ahead of
+// `save` (optional: the backward sweep, the training forward's trunk): every float4 of the slab this GEMM reads leaves once for its saved row -- step 0's ahead of
 // the loop, step s + 1's from the registers that are split under the chunks 0 and 1 of step s (two stores a chunk, behind that
 // chunk's fragment loads in the vmcnt order).
 template <int NBO, class SV = const float*>
@@ -686,9 +688,11 @@ __device__ __forceinline__ void load_w32s(float4 (&f)[NQ][2][2], const WBuf& b, 
       }
 }
 
-template <int NBO>
+// `save` (optional): as in gemm_bf16_s16 -- step 0's float4 ahead of the loop, step s + 1's from the registers that the last two row
+// halves of step s split.
+template <int NBO, class SV = const float*>
 __device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32seg, const float4* xl,
-                                                int n_k32, int lane) {
+                                                int n_k32, int lane, SV save = nullptr) {
   static_assert(NBO % 2 == 0, "an even number of fragment buffers' worth of blocks");
   constexpr int NQ = NBO >= 4 ? NBO / 4 : 1, NC = NBO / NQ, UQ = 2 * NQ, NU = 2 * NBO;  // row halves per chunk and per K step
   const Lane16 g = lane16(lane);
@@ -698,7 +702,17 @@ __device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const f
   float4 fa[NQ][2][2], fb[NQ][2][2];
   load_w32s<NQ>(fa, wp, 0, NBO, 0);
   load_w32s<NQ>(fb, wp, 0, NBO, NQ);
-  BSplit bc[2] = {split8<3>(xb[0], xb[64]), split8<3>(xb[16], xb[80])};
+  BSplit bc[2];
+  if (sv_on(save)) {  // step 0's four float4, kept for their rows
+    const float4 p0lo = xb[0], p0hi = xb[64], p1lo = xb[16], p1hi = xb[80];
+    bc[0] = split8<3>(p0lo, p0hi);
+    bc[1] = split8<3>(p1lo, p1hi);
+    sv_put16(save, 2 * g.kh, 0, true, p0lo, p0hi);
+    sv_put16(save, 2 * g.kh, 1, true, p1lo, p1hi);
+  } else {
+    bc[0] = split8<3>(xb[0], xb[64]);
+    bc[1] = split8<3>(xb[16], xb[80]);
+  }
   const int s1 = n_k32 > 1 ? 1 : 0;
   float4 x0lo = xb[4 * s1 * 64], x0hi = xb[(4 * s1 + 1) * 64], x1lo = xb[4 * s1 * 64 + 16], x1hi = xb[(4 * s1 + 1) * 64 + 16];
   BSplit w = split8<3>(fa[0][0][0], fa[0][0][1]);
@@ -718,6 +732,9 @@ __device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const f
         else load_w32s<NQ>(fa, wp, c + 2 < NC ? s : sn, NBO, c2 * NQ);
       }
       if (u == NU - 2) bn[0] = split8<3>(x0lo, x0hi);
+      // the registers hold step sn; in the last step that is this step again (the clamp), whose rows have left: not live
+      if (u == NU - 2 && sv_on(save)) sv_put16(save, 4 * sn + 2 * g.kh, 0, s + 1 < n_k32, x0lo, x0hi);
+      if (u == NU - 1 && sv_on(save)) sv_put16(save, 4 * sn + 2 * g.kh, 1, s + 1 < n_k32, x1lo, x1hi);
       if (u == NU - 1) {
         bn[1] = split8<3>(x1lo, x1hi);
         x0lo = xb[4 * s2 * 64]; x0hi = xb[(4 * s2 + 1) * 64];
@@ -735,6 +752,7 @@ __device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const f
         if (reload && m < NQ * 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
         if (u >= NU - 2) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // the next row half's pieces + the next step's activations
         else __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // the next row half's pieces
+        if (u >= NU - 2 && sv_on(save) && (m == 5 || m == 12)) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // 1 row store
       }
       if (u == NU - 1) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // the LDS reads of the activations
       __builtin_amdgcn_sched_barrier(0);

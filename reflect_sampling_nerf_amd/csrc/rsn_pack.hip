@@ -637,13 +637,15 @@ int build_jobs(const rsn_field_desc* d, const rsn_field_params* p, float* packed
   if (d->mma_mode == RSN_MMA_F32 || d->mma_mode == RSN_MMA_F32_FOLDED) {
     // exact fp32: the forward and backward kernels read none of the copies below.  The folded mode splits what the analytic-normal
     // sweep of its training forward reads (nine-product loop, rsn_gemm_loops.h): the seed, then the transposed trunk and encoded-input
-    // segments behind it (RSN_MMA_F32 packs nothing more: its training kernel forms the same pieces in registers)
+    // segments behind it, and the forward trunk segments h_x[l], which the W x W GEMMs of its training forward read the same way
+    // (RSN_MMA_F32 packs nothing more: its training kernel forms the same pieces in registers)
     if (L.hT_seed != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_seed, L.v_density);
     if (d->mma_mode == RSN_MMA_F32_FOLDED) {
       for (int l = 1; l + 1 < n_layers; ++l) split(L.wT_x[l], NB * 4, NB, L.hT_x[l]);
       if (L.hT_last != 0) split(L.wT_x[n_layers - 1], NB * 4, NB, L.hT_last);  // the backward sweep's first trunk GEMM
       if (skip >= 1) split(L.wT_enc_skip, NB * 4, 4, L.hT_enc_skip);
       split(L.wT_enc0, NB * 4, 4, L.hT_enc0);
+      for (int l = 1; l < n_layers; ++l) split(L.w_x[l], NB * 4, NB, L.h_x[l]);  // the training forward's trunk GEMMs
     }
     return RSN_OK;
   }

@@ -14,6 +14,9 @@
 // [points, 256] buffer.  Three more forms for it: (a) with the stores in its K loop (gemm_run2's saver, what that sweep ran), (d)
 // with them in its K loop (gemm_bf16_s16's saver, checked first on the integer operands: result, rows and rows past the valid
 // ones), and (d) with the result rows stored from the epilogue; the go / no-go is the better placement against (a) with its stores.
+// The training forward's trunk runs W_l (256 x 256) the same way behind a bias start and in front of a ReLU epilogue: three more forms
+// (kf / fwd_tile below: the fp32 loop with store_act_init, the packed and the in-register 16-shape with store_act16_relu_init),
+// checked first on integer operands (slab, mask words, restarted accumulators, kept rows, stray stores), then timed tile feeding tile.
 // Before anything is timed, (b) and (d) run one tile each on integer operands whose every sum is exact in fp32 (17-bit weights
 // against 0 / +-1 activations, then the reverse) and their X slabs are compared with each other and with the host's integer sums.
 // The kernel's real grid: one workgroup of four waves per CU on every CU at once (clock and power effects show), each wave on its
@@ -195,6 +198,76 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
   out[blockIdx.x * 256 + threadIdx.x] = s;
 }
 
+// The training forward's trunk runs the same W x W GEMM per layer with the ReLU epilogue behind it: the accumulators start from the
+// layer's bias, the GEMM keeps the rows it reads (act[l-1], 32 KiB per tile, stores in its K loop), and the epilogue writes the
+// relu'd result to the slab -- the next GEMM's operand -- with the layer's mask words (1 KiB per tile) and restarts the
+// accumulators from the next bias.  Three forms, every tile feeding the next as the layers do (weights scaled so that the
+// activations stay of order one):
+//   FORM 0: the fp32 loop as the kernel ran it (gemm_run2 with its saver, first fragment fetched ahead of store_act_init);
+//   FORM 1: gemm_bf16_s16 with its saver + store_act16_relu_init (the RSN_MMA_F32_FOLDED kernel's form);
+//   FORM 2: gemm_f32_x9_s16 with its saver + store_act16_relu_init (the RSN_MMA_F32 kernel's form).
+template <int FORM>
+__device__ __forceinline__ void fwd_tile(f32x16 (&acc)[8], f32x4 (&a16)[8][2][2], float4 (&wa)[8], const float* __restrict__ w32,
+                                         const float* __restrict__ w16, float4* X, const float* __restrict__ bias, float* rows,
+                                         long long row0, int valid, unsigned* bits32, int ln) {
+  if constexpr (FORM == 0) {
+    gemm_run2<8, 8>(acc, wa, w32, X, 32, ln, rowbuf<false>(rows, row0, valid, 256, ln & 31, ln >> 5));
+    pre_w<8>(wa, w32, ln);
+    const int m = ln & 31, h = ln >> 5;
+    store_act_init<8, true, false>(acc, X, (float*)nullptr, h, bias, m < valid ? bits32 + (m * 2 + h) * 4 : nullptr);
+  } else {
+    const RowBuf rb = rowbuf<false>(rows, row0, valid, 256, ln & 15, (ln >> 4) & 1);
+    if constexpr (FORM == 1) gemm_bf16_s16<8>(a16, w16, X, 8, ln, rb); else gemm_f32_x9_s16<8>(a16, w32, X, 8, ln, rb);
+    const int m = (ln & 15) + 16 * (ln >> 5), h = (ln >> 4) & 1;
+    store_act16_relu_init<8>(a16, X, ln, bias, m < valid ? bits32 + (m * 2 + h) * 4 : nullptr);
+  }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(256) void kf(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0,
+                                           const float* __restrict__ bias, float* out, float* rowsbuf, unsigned* bitsbuf) {
+  extern __shared__ float4 smem[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float4* X = smem + wid * 32 * 64 + lane;
+#pragma unroll 4
+  for (int it = 0; it < 32; ++it) X[it * 64] = *reinterpret_cast<const float4*>(x0 + ((size_t)(wid * 32 + it) * 64 + lane) * 4);
+  f32x16 acc[8];
+  f32x4 a16[8][2][2];
+  float4 wa[8];
+  if constexpr (FORM == 0) { init_acc<8>(acc, bias, lane >> 5); pre_w<8>(wa, w32, lane); } else init_acc16<8>(a16, bias, lane);
+  __syncthreads();
+  for (int t = 0; t < TILES; ++t) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const long long slot = (long long)(blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wid)) * ROW_SLOTS + (t % ROW_SLOTS);
+    fwd_tile<FORM>(acc, a16, wa, w32, w16, X, bias, rowsbuf, slot * 32 * 256, 32, bitsbuf + slot * 32 * 8, ln);
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = X[0].x + X[17 * 64].y;
+}
+
+// one wave, one tile of a forward form on integer operands: the slab behind the epilogue, the mask words, the rows the GEMM kept
+// (`valid` of 32 inside the descriptor) and, through a second plain epilogue, the accumulators as the epilogue restarted them
+template <int FORM>
+__global__ __launch_bounds__(64) void chkf(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0,
+                                            const float* __restrict__ bias, float* out, float* out2, float* rows, unsigned* bits, int valid) {
+  __shared__ float4 slab[32 * 64];
+  const int lane = threadIdx.x;
+  float4* X = slab + lane;
+  for (int it = 0; it < 32; ++it) X[it * 64] = *reinterpret_cast<const float4*>(x0 + ((size_t)it * 64 + lane) * 4);
+  __syncthreads();
+  f32x16 acc[8];
+  f32x4 a16[8][2][2];
+  float4 wa[8];
+  if constexpr (FORM == 0) { init_acc<8>(acc, bias, lane >> 5); pre_w<8>(wa, w32, lane); } else init_acc16<8>(a16, bias, lane);
+  fwd_tile<FORM>(acc, a16, wa, w32, w16, X, bias + 256, rows, 0, valid, bits, lane);
+  __syncthreads();
+  for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out + ((size_t)it * 64 + lane) * 4) = X[it * 64];
+  __syncthreads();
+  if constexpr (FORM == 0) store_act<8, 8, false>(acc, X); else store_act16<8>(a16, X, lane);
+  __syncthreads();
+  for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out2 + ((size_t)it * 64 + lane) * 4) = X[it * 64];
+}
+
 // one wave, one tile: the GEMM of form (b), (d) or (e), its result written to the X slab by the form's own epilogue and copied out
 template <int FORM>
 __global__ __launch_bounds__(64) void chk(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0, float* out) {
@@ -359,6 +432,105 @@ static bool check_forms(bool wide_w, float* w32, float* w16, float* x0, float* o
   return bad_b == 0 && bad_d == 0 && bad_e == 0 && differ == 0 && bad_r == 0 && bad_s == 0 && stray == 0;
 }
 
+static float* g_bias = nullptr;     // two biases of 256 (the layer's, the next layer's)
+static unsigned* g_bits = nullptr;  // mask words, 256 per tile, laid out like the saved rows
+
+// The three forward forms on the integer operands of check_forms(true) with integer biases: the relu'd slab, the mask words in
+// ReluBits' layout ([point][half][4 words]: unit 32 nb + 8 q + 4 h + j is bit 16 (nb & 1) + 4 q + j of word nb / 2), the restarted
+// accumulators, the kept rows, and nothing written for rows at or past `valid`.
+static bool check_fwd(float* w32, float* w16, float* x0, float* out) {
+  std::vector<float> hw(SEG_F32), hx(32 * 64 * 4), hbias(512);
+  auto big = [](size_t i) { return (float)((long long)((i * 2654435761u + 12345u) % 262143u) - 131071); };
+  auto small = [](size_t i) { const unsigned r = (unsigned)(i * 2246822519u) >> 13; return (r & 12u) ? 0.0f : ((r & 1u) ? 1.0f : -1.0f); };
+  for (size_t i = 0; i < hw.size(); ++i) hw[i] = big(i);
+  for (size_t i = 0; i < hx.size(); ++i) hx[i] = small(i + 7);
+  for (int r = 0; r < 256; ++r) { hbias[r] = (float)((r * 37) % 201 - 100); hbias[256 + r] = (float)((r * 11) % 61 - 30); }
+  std::vector<unsigned short> hb((size_t)SEG_B16 * 2);
+  pack_pieces(hw.data(), hb.data());
+  CK(hipMemcpy(w32, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
+  CK(hipMemcpy(w16, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+  CK(hipMemcpy(x0, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
+  CK(hipMemcpy(g_bias, hbias.data(), hbias.size() * 4, hipMemcpyHostToDevice));
+  std::vector<long long> ref(256 * 32);
+  for (int row = 0; row < 256; ++row)
+    for (int p = 0; p < 32; ++p) {
+      long long s = (long long)hbias[row];
+      for (int ki = 0; ki < 32; ++ki)
+        for (int kh = 0; kh < 2; ++kh)
+          for (int kc = 0; kc < 4; ++kc)
+            s += (long long)hw[((size_t)(ki * 8 + row / 32) * 64 + (row % 32) + 32 * kh) * 4 + kc] * (long long)hx[((size_t)ki * 64 + p + 32 * kh) * 4 + kc];
+      ref[row * 32 + p] = s;
+    }
+  const int guard = 8;
+  std::vector<float> o1(hx.size()), o2(hx.size());
+  std::vector<unsigned> hr((size_t)(32 + guard) * 256), hm((size_t)(32 + guard) * 8);
+  bool ok = true;
+  for (int form = 0; form < 3; ++form) {
+    size_t bad_x = 0, bad_a = 0, bad_s = 0, bad_m = 0, stray = 0;
+    for (int valid : {32, 19, 1}) {
+      CK(hipMemset(g_rows, 0xCD, hr.size() * 4));
+      CK(hipMemset(g_bits, 0xCD, hm.size() * 4));
+      if (form == 0) hipLaunchKernelGGL((chkf<0>), dim3(1), dim3(64), 0, 0, w32, w16, x0, g_bias, out, out + 8192, g_rows, g_bits, valid);
+      else if (form == 1) hipLaunchKernelGGL((chkf<1>), dim3(1), dim3(64), 0, 0, w32, w16, x0, g_bias, out, out + 8192, g_rows, g_bits, valid);
+      else hipLaunchKernelGGL((chkf<2>), dim3(1), dim3(64), 0, 0, w32, w16, x0, g_bias, out, out + 8192, g_rows, g_bits, valid);
+      CK(hipMemcpy(o1.data(), out, o1.size() * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(o2.data(), out + 8192, o2.size() * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(hr.data(), g_rows, hr.size() * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(hm.data(), g_bits, hm.size() * 4, hipMemcpyDeviceToHost));
+      for (int it = 0; it < 32; ++it)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int c = 0; c < 4; ++c) {
+            const int row = 8 * it + 4 * (lane >> 5) + c, p = lane & 31;
+            const long long z = ref[row * 32 + p];
+            const size_t o = ((size_t)it * 64 + lane) * 4 + c;
+            bad_x += o1[o] != (float)(z > 0 ? z : 0);
+            bad_a += o2[o] != hbias[256 + row];
+            if (p < valid) {
+              const int nb = row / 32, q = (row % 32) / 8, h = (row % 8) / 4, j = row % 4;
+              bad_m += ((hm[(size_t)(p * 2 + h) * 4 + nb / 2] >> (16 * (nb & 1) + 4 * q + j)) & 1u) != (unsigned)(z > 0);
+            }
+          }
+      for (int m = 0; m < 32 + guard; ++m) {
+        for (int w = 0; w < 8; ++w) stray += m >= valid && hm[(size_t)m * 8 + w] != 0xCDCDCDCDu;
+        for (int f = 0; f < 256; ++f) {
+          const unsigned got = hr[(size_t)m * 256 + f];
+          if (m >= valid) { stray += got != 0xCDCDCDCDu; continue; }
+          const float want = hx[((size_t)(f / 8) * 64 + m + 32 * ((f / 4) & 1)) * 4 + (f & 3)];
+          unsigned wb;
+          memcpy(&wb, &want, 4);
+          bad_s += got != wb;
+        }
+      }
+    }
+    printf("check, forward form %d (0 fp32 loop, 1 packed 16-shape, 2 in-register 16-shape), 32 / 19 / 1 valid rows: slab wrong %zu, "
+           "restarted accumulators wrong %zu, mask bits wrong %zu, kept rows wrong %zu, stray stores %zu\n", form, bad_x, bad_a, bad_m, bad_s, stray);
+    ok = ok && bad_x == 0 && bad_a == 0 && bad_m == 0 && bad_s == 0 && stray == 0;
+  }
+  return ok;
+}
+
+template <int FORM>
+static double run_fwd(const char* name, const float* w32, const float* w16, const float* x0, float* out, double cal_ms, double ref_ms) {
+  const size_t lds = 150 * 1024;
+  CK(hipFuncSetAttribute((const void*)kf<FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0));
+  CK(hipEventCreate(&e1));
+  hipLaunchKernelGGL((kf<FORM>), dim3(g_grid), dim3(256), lds, 0, w32, w16, x0, g_bias, out, g_rows, g_bits);
+  CK(hipDeviceSynchronize());
+  CK(hipEventRecord(e0, 0));
+  for (int r = 0; r < 5; ++r) hipLaunchKernelGGL((kf<FORM>), dim3(g_grid), dim3(256), lds, 0, w32, w16, x0, g_bias, out, g_rows, g_bits);
+  CK(hipEventRecord(e1, 0));
+  CK(hipEventSynchronize(e1));
+  float ms = 0.0f;
+  CK(hipEventElapsedTime(&ms, e0, e1));
+  ms /= 5;
+  if (hipGetLastError() != hipSuccess) { printf("%s: launch failed\n", name); exit(1); }
+  if (ref_ms <= 0.0) printf("%-52s %8.3f ms  %7.2f us per tile  %8.0f cycles per tile\n", name, ms, ms * 1000.0 / TILES, ms / cal_ms * 65536.0);
+  else printf("%-52s %8.3f ms  %7.2f us per tile  %8.0f cycles per tile  %.3f of the fp32 form\n", name, ms, ms * 1000.0 / TILES, ms / cal_ms * 65536.0, ms / ref_ms);
+  return ms;
+}
+
 int main() {
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, 0));
@@ -369,7 +541,10 @@ int main() {
   CK(hipMalloc(&x0, 4ull * 32 * 64 * 4 * 4));
   CK(hipMalloc(&out, (size_t)g_grid * 256 * 4));
   CK(hipMalloc(&g_rows, (size_t)g_grid * 4 * ROW_SLOTS * 32 * 256 * 4));
+  CK(hipMalloc(&g_bias, 512 * 4));
+  CK(hipMalloc(&g_bits, (size_t)g_grid * 4 * ROW_SLOTS * 256 * 4 + 4096));
   if (!check_forms(true, w32, w16, x0, out) || !check_forms(false, w32, w16, x0, out)) { printf("check FAILED\n"); return 1; }
+  if (!check_fwd(w32, w16, x0, out)) { printf("check FAILED\n"); return 1; }
   std::vector<float> h(4ull * SEG_F32);
   for (size_t i = 0; i < h.size(); ++i) h[i] = 1e-3f * (float)((i * 2654435761u) % 2001) - 1.0f;
   CK(hipMemcpy(w32, h.data(), h.size() * 4, hipMemcpyHostToDevice));
@@ -417,6 +592,33 @@ int main() {
            (g0 + g1) / (f0 + f1), (h0 + h1) / (f0 + f1), r, r <= 0.85 ? "GO" : "NO-GO");
     printf("   predicted step gain: (%.2f - %.2f) us per tile x 7 GEMMs x 16 tiles x 2.54 launches x 0.65 = %.3f ms per step\n",
            (f0 + f1) / 2.0 / TILES * 1000.0, best / 2.0 / TILES * 1000.0, gain);
+  }
+  {
+    // the training forward's trunk: weights scaled to 0.153 of the above (standard deviation sqrt(2 / 256): a ReLU layer then keeps
+    // the scale of its input), small biases of both signs; every tile's relu'd result is the next tile's operand
+    printf("-- the forward trunk's case: bias start, the GEMM keeps its rows, ReLU + mask words + bias restart behind it, tile feeds tile\n");
+    std::vector<float> hf(SEG_F32), hbias(512);
+    for (size_t i = 0; i < hf.size(); ++i) hf[i] = 0.153f * h[i];
+    for (int r = 0; r < 512; ++r) hbias[r] = 0.02f * (float)((r * 5) % 7 - 2);
+    std::vector<unsigned short> hfb((size_t)SEG_B16 * 2);
+    pack_pieces(hf.data(), hfb.data());
+    float *w32f, *w16f;
+    CK(hipMalloc(&w32f, (size_t)SEG_F32 * 4));
+    CK(hipMalloc(&w16f, (size_t)SEG_B16 * 4));
+    CK(hipMemcpy(w32f, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(w16f, hfb.data(), hfb.size() * 2, hipMemcpyHostToDevice));
+    CK(hipMemcpy(g_bias, hbias.data(), hbias.size() * 4, hipMemcpyHostToDevice));
+    const double p0 = run_fwd<0>("fp32 loop + saver, store_act_init", w32f, w16f, x0, out, cal, 0.0);
+    const double q0 = run_fwd<1>("packed 16-shape + saver, store_act16_relu_init", w32f, w16f, x0, out, cal, p0);
+    const double r0 = run_fwd<2>("in-register 16-shape + saver, store_act16_relu_init", w32f, w16f, x0, out, cal, p0);
+    const double p1 = run_fwd<0>("fp32 loop, again", w32f, w16f, x0, out, cal, p0);
+    const double q1 = run_fwd<1>("packed 16-shape, again", w32f, w16f, x0, out, cal, p0);
+    const double r1 = run_fwd<2>("in-register 16-shape, again", w32f, w16f, x0, out, cal, p0);
+    const double ratio = (q0 + q1) / (p0 + p1);
+    printf("forward go / no-go: packed %.3f, in-register %.3f of the fp32 form (go at packed <= 0.850): %s\n", ratio, (r0 + r1) / (p0 + p1),
+           ratio <= 0.85 ? "GO" : "NO-GO");
+    printf("   predicted step gain: (%.2f - %.2f) us per tile x 7 GEMMs x 16 tiles x 2.54 launches x 0.65 = %.3f ms per step\n",
+           (p0 + p1) / 2.0 / TILES * 1000.0, (q0 + q1) / 2.0 / TILES * 1000.0, ((p0 + p1) - (q0 + q1)) / 2.0 / TILES * 7.0 * 16.0 * 2.54 * 0.65);
   }
   printf("-- every wave on its own copy of the segment (no L1 sharing between the waves)\n");
   const double a2 = run<0, true>("(a) fp32: gemm<8, 8, PF2>", w32, w16, x0, out, cal, 0.0);
