@@ -795,6 +795,47 @@ int rsn_sample_pyramid_rays(int32_t n_images, int32_t height, int32_t width, int
                             float* directions, float* pixel_area, float* rgb, int32_t* indices, int32_t* level, void* stream);
 
 
+/* ---- captures (additive to ABI 18: no existing call changes): image sets whose every image has its own camera, with lens
+ * distortion -- what a nerfstudio-format transforms.json of real photographs describes.
+ *
+ * Camera table: cameras is fp32 [N, 9] on the device; row i = (fx, fy, cx, cy, k1, k2, k3, p1, p2) of image i.
+ *
+ * Model: COLMAP's / OpenCV's (COLMAP writes the coefficients of a transforms.json).  Image coordinates: x right, y DOWN.  For
+ * the undistorted normalised point (X, Y):
+ *   r2  = X^2 + Y^2
+ *   rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+ *   Xd  = X rad + 2 p1 X Y + p2 (r2 + 2 X^2)
+ *   Yd  = Y rad + p1 (r2 + 2 Y^2) + 2 p2 X Y
+ *   u   = fx Xd + cx,   v = fy Yd + cy                                                                   (pixel coordinates)
+ * (nerfstudio 0.3 undistorts the coordinates after its y flip, which amounts to -p1; this library does not: DESIGN.md 4.23.)
+ *
+ * Ray of pixel (y, x): (Xd, Yd) = ((x+.5-cx)/fx, (y+.5-cy)/fy); (X, Y) solves the model by Newton on the 2 x 2 system, started at
+ * (Xd, Yd): exactly 10 iterations, no early exit, an iteration whose |det J| <= 1e-12 leaves the point where it is; the solve runs
+ * in fp64.  Camera-space direction v = (X, -Y, -1); directions = normalize(c2w[:, :3] v); origins = c2w[:, 3].  pixel_area =
+ * |d - d_x1| * |d - d_y1| as in the standalone data path; the x+1 / y+1 neighbours are undistorted by their own solves, their
+ * camera-space offsets from v are differences of the solved points formed in fp64 and rounded to fp32 once, and the differences of
+ * the unit vectors keep the cancellation-free rearrangement.  Nothing on the device checks that the solve converged: the caller
+ * makes sure the model is invertible over the image (data.load_nerfstudio_split does) and that fx, fy != 0.
+ *
+ * A row whose five coefficients are all exactly zero runs the pinhole function of the standalone data path unchanged: its rays
+ * have the bits rsn_camera_rays_image / rsn_sample_camera_rays give for the same (pose, intrinsics, y, x).
+ *
+ * Level l of a pyramid: the row's fx, fy, cx, cy over 2^l (exact); the coefficients act on normalised coordinates and stay. */
+
+/* rsn_sample_pyramid_rays with a camera table in place of the four intrinsics: the same Philox recipe for level, image and pixel,
+ * the same rgb and outputs, one launch, no atomics; image i's rays go through row i.  levels == 1 with pyramid NULL is the
+ * single-scale batch: level may then be NULL too (where given it is written: zeros). */
+int rsn_sample_capture_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images,
+                            const float* pyramid, size_t pyramid_pixels, const float* c2w, const float* cameras, int32_t n_rays,
+                            uint32_t seed, uint32_t rank, uint32_t step, float* origins, float* directions, float* pixel_area,
+                            float* rgb, int32_t* indices, int32_t* level, void* stream);
+
+/* rsn_camera_rays_image for ONE camera row (camera: device fp32 [9], read on the device): the sampler's device function, so equal
+ * (i, y, x) give equal bits. */
+int rsn_capture_rays_image(int32_t height, int32_t width, const float* c2w, const float* camera, float* origins,
+                           float* directions, float* pixel_area, void* stream);
+
+
 /* ---- mesh export: the iso-surface of a scalar volume as an indexed triangle mesh (additive to ABI 18: no existing call
  * changes).  Marching tetrahedra on the Kuhn (Freudenthal) split of every grid cell: no case table, consistent across
  * shared cell faces by construction (a surface away from the grid boundary is closed), and every surface vertex lies on

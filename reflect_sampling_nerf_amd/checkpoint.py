@@ -49,13 +49,16 @@ def resolve_checkpoint(path: str) -> str:
 
 def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, max_grad_norm: Optional[float] = None,
                    skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
-                   distortion_loss_coarse: Optional[float] = None) -> dict:
+                   distortion_loss_coarse: Optional[float] = None, rays_and_data: Optional[dict] = None) -> dict:
     """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
     bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
     seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one.
     max_grad_norm / skip_nonfinite (the optimiser's guard) are recorded only when set: an unguarded run's entry has the keys it
     always had.  Likewise multiscale (the number of pyramid levels the rays are drawn from): only when above 1, and distortion_loss /
-    distortion_loss_coarse (the coefficients of the opt-in distortion term): only when set and not 0."""
+    distortion_loss_coarse (the coefficients of the opt-in distortion term): only when set and not 0.  rays_and_data: the entries
+    of RAY_KEYS ("near", "far": the collider planes; "primary_spacing", "primary_tan": the coarse sampler of the primary rays) and
+    "data" (how a capture was read: format, orientation, center, auto_scale, scale_factor, train_split_fraction, eval_mode, and the
+    transform [3][4] and scale that were applied) that are not None are recorded; a Blender-format run with its defaults has none."""
     dev = torch.device(device)
     state = {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
              "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
@@ -69,7 +72,55 @@ def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, 
     for key, coef in (("distortion_loss", distortion_loss), ("distortion_loss_coarse", distortion_loss_coarse)):
         if coef is not None and float(coef) != 0.0:
             state[key] = float(coef)
+    for key, v in (rays_and_data or {}).items():
+        if key not in RAY_KEYS + ("data",):
+            raise KeyError(f"rays_and_data: unknown entry {key!r}")
+        if v is not None:
+            state[key] = v
     return state
+
+
+RAY_KEYS = ("near", "far", "primary_spacing", "primary_tan")
+PRIMARY_SPACINGS = ("uniform", "reciprocal")
+
+
+def read_run_state(path: str) -> Optional[dict]:
+    """The `rsn_run` entry of a step-*.ckpt (or of the newest one of a run directory); None for a checkpoint without one."""
+    return torch.load(resolve_checkpoint(path), map_location="cpu", weights_only=False).get(RUN_STATE_KEY)
+
+
+def config_with_planes(config, near: Optional[float] = None, far: Optional[float] = None):
+    """`config` itself when both are None, else a copy whose collider_params hold the given planes (the other one as it was)."""
+    if near is None and far is None:
+        return config
+    import copy
+
+    planes = dict(config.collider_params)
+    if near is not None:
+        planes["near_plane"] = float(near)
+    if far is not None:
+        planes["far_plane"] = float(far)
+    if not planes["far_plane"] > planes["near_plane"] >= 0.0:
+        raise ValueError(f"near {planes['near_plane']} far {planes['far_plane']}: need 0 <= near < far")
+    config = copy.copy(config)
+    config.collider_params = planes
+    return config
+
+
+def set_primary_sampler(model, spacing: Optional[str] = None, tan: Optional[float] = None) -> None:
+    """The coarse sampler of the primary rays: None or "uniform" leaves model.sampler_uniform as the model built it; "reciprocal"
+    replaces it by ReciprocalSampler(tan) with the same sample count (spacing s(t) = t / (1/tan + t): fine near the camera, coarse
+    far away, for a far plane an unbounded scene needs).  The samplers, the training graph and the eval path read the spacing and tan
+    from that object's spec."""
+    if spacing not in (None,) + PRIMARY_SPACINGS:
+        raise ValueError(f"primary_spacing = {spacing!r}: choose from {', '.join(PRIMARY_SPACINGS)}")
+    if spacing == "reciprocal":
+        from .reflect_sampling_nerf_components import ReciprocalSampler
+
+        tan = 1.0 if tan is None else float(tan)
+        if not tan > 0.0:
+            raise ValueError(f"primary_tan = {tan}: need a value above 0")
+        model.sampler_uniform = ReciprocalSampler(tan=tan, num_samples=model.config.num_coarse_samples)
 
 
 def save_checkpoint(path: str, model, optimizer, step: int, run_state: Optional[dict] = None) -> str:
@@ -111,11 +162,18 @@ class _Pipeline(torch.nn.Module):
         self._model = model
 
 
-def _load_pipeline(path: str, model_config=None):
-    """-> (model on the CPU with the checkpoint's `pipeline` loaded under strict key checking, the checkpoint dict)."""
-    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+def _load_pipeline(path: str, model_config=None, rays: Optional[dict] = None, ckpt: Optional[dict] = None):
+    """-> (model on the CPU with the checkpoint's `pipeline` loaded under strict key checking, the checkpoint dict).  The collider
+    planes and the primary rays' coarse sampler that the run recorded (RAY_KEYS of `rsn_run`) are set on the model: every tool that
+    opens the checkpoint casts its rays the way the run did.  A checkpoint without them gets the config's.  rays: entries of
+    RAY_KEYS that take the place of the recorded ones (None entries do not).  ckpt: the file's content when the caller has read it."""
+    if ckpt is None:
+        ckpt = torch.load(path, map_location="cpu", weights_only=False)
     state = ckpt["pipeline"]
-    model = make_model(config_for_checkpoint(state, model_config))
+    run = dict(ckpt.get(RUN_STATE_KEY) or {})
+    run.update({k: v for k, v in (rays or {}).items() if v is not None})
+    model = make_model(config_with_planes(config_for_checkpoint(state, model_config), run.get("near"), run.get("far")))
+    set_primary_sampler(model, run.get("primary_spacing"), run.get("primary_tan"))
     _Pipeline(model).load_state_dict(state, strict=True)
     return model, ckpt
 

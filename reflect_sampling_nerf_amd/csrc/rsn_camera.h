@@ -1,5 +1,6 @@
-// The camera ray of a pixel (include/rsn.h, "standalone data path"): one device function for every kernel that needs it, so that
-// equal (pose, intrinsics, y, x) give bit-identical rays in rsn_sample_camera_rays, rsn_camera_rays_image and the point-cloud calls.
+// The camera ray of a pixel (include/rsn.h, "standalone data path" and "captures"): one device function for every kernel that needs
+// it, so that equal (pose, camera, y, x) give bit-identical rays in rsn_sample_camera_rays, rsn_camera_rays_image, the pyramid and
+// capture samplers and the point-cloud calls.
 #pragma once
 #include "rsn_common.h"
 
@@ -7,25 +8,39 @@ struct Intrinsics {
   float fx, fy, cx, cy;
 };
 
-// nerfstudio 0.3 Cameras._generate_rays_from_coords, perspective: the pixel centre's camera-space direction
-// v = ((x+.5-cx)/fx, -(y+.5-cy)/fy, -1), rotated by c2w[:, :3] and normalised; origin = c2w[:, 3].  pixel_area =
-// |d - d_x1| |d - d_y1| with d_x1 / d_y1 the normalised directions of the x+1 / y+1 neighbours.  Those differences are
-// formed without cancellation: with w = R v, g = R e (e = the neighbour's camera-space offset, (1/fx, 0, 0) or
-// (0, -1/fy, 0)), a = |w|, b = |w + g|:  w/a - (w+g)/b = w (b - a)/(a b) - g/b,  b - a = (2 w.g + g.g) / (a + b).
-__device__ __forceinline__ void camera_ray(const float* __restrict__ c2w, Intrinsics k, int y, int x, float* o, float* d,
-                                           float* area) {
+// One row of a capture's camera table (include/rsn.h, "captures"): the pinhole part and the OpenCV / COLMAP coefficients.
+struct Camera {
+  Intrinsics k;
+  float k1, k2, k3, p1, p2;
+};
+
+__device__ __forceinline__ Camera load_camera(const float* __restrict__ row) {
+  return Camera{Intrinsics{row[0], row[1], row[2], row[3]}, row[4], row[5], row[6], row[7], row[8]};
+}
+
+// The ray whose camera-space direction is v = (vx, vy, -1), rotated by c2w[:, :3] and normalised; origin = c2w[:, 3].  pixel_area =
+// |d - d_x1| |d - d_y1| with d_x1 / d_y1 the normalised directions of the x+1 / y+1 neighbours, whose camera-space directions are
+// v + (exx, exy, 0) and v + (eyx, eyy, 0).  Those differences are formed without cancellation: with w = R v, g = R e (e = the
+// neighbour's camera-space offset), a = |w|, b = |w + g|:  w/a - (w+g)/b = w (b - a)/(a b) - g/b,  b - a = (2 w.g + g.g) / (a + b).
+// AXIS: the offsets are (exx, 0) and (0, eyy) (a pinhole camera); exy and eyx are not read, and the arithmetic is the pinhole
+// function's as it always was.
+template <bool AXIS>
+__device__ __forceinline__ void camera_ray_at(const float* __restrict__ c2w, float vx, float vy, float exx, float exy, float eyx,
+                                              float eyy, float* o, float* d, float* area) {
   float R[12];
 #pragma unroll
   for (int j = 0; j < 12; ++j) R[j] = c2w[j];
-  const float vx = ((float)x + 0.5f - k.cx) / k.fx;
-  const float vy = -(((float)y + 0.5f - k.cy) / k.fy);
   float w[3], gx[3], gy[3];
-  const float ex = 1.0f / k.fx, ey = -(1.0f / k.fy);
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     w[i] = vx * R[4 * i + 0] + vy * R[4 * i + 1] + (-1.0f) * R[4 * i + 2];
-    gx[i] = ex * R[4 * i + 0];
-    gy[i] = ey * R[4 * i + 1];
+    if (AXIS) {
+      gx[i] = exx * R[4 * i + 0];
+      gy[i] = eyy * R[4 * i + 1];
+    } else {
+      gx[i] = exx * R[4 * i + 0] + exy * R[4 * i + 1];
+      gy[i] = eyx * R[4 * i + 0] + eyy * R[4 * i + 1];
+    }
   }
   const float a2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   const float a = sqrtf(a2);
@@ -48,4 +63,61 @@ __device__ __forceinline__ void camera_ray(const float* __restrict__ c2w, Intrin
     o[i] = R[4 * i + 3];
   }
   *area = nb[0] * nb[1];
+}
+
+// nerfstudio 0.3 Cameras._generate_rays_from_coords, perspective: the pixel centre's camera-space direction
+// v = ((x+.5-cx)/fx, -(y+.5-cy)/fy, -1); the neighbours' camera-space offsets are (1/fx, 0, 0) and (0, -1/fy, 0).
+__device__ __forceinline__ void camera_ray(const float* __restrict__ c2w, Intrinsics k, int y, int x, float* o, float* d,
+                                           float* area) {
+  const float vx = ((float)x + 0.5f - k.cx) / k.fx;
+  const float vy = -(((float)y + 0.5f - k.cy) / k.fy);
+  const float ex = 1.0f / k.fx, ey = -(1.0f / k.fy);
+  camera_ray_at<true>(c2w, vx, vy, ex, 0.0f, 0.0f, ey, o, d, area);
+}
+
+// The undistorted normalised point (X, Y) whose image under the OpenCV model (include/rsn.h, "captures") is (xd, yd): Newton on the
+// 2 x 2 system from (xd, yd), exactly 10 iterations, none of them skipped early; an iteration whose |det J| <= 1e-12 leaves the
+// point where it is.  fp64: the neighbours' offsets below are differences of two such points.  Nothing here checks convergence (the
+// loader does, on the host, before a run starts).
+__device__ __forceinline__ void undistort_point(const Camera& c, double xd, double yd, double* X, double* Y) {
+  const double k1 = c.k1, k2 = c.k2, k3 = c.k3, p1 = c.p1, p2 = c.p2;
+  double x = xd, y = yd;
+#pragma unroll 1
+  for (int it = 0; it < 10; ++it) {
+    const double r2 = x * x + y * y;
+    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double drad = k1 + r2 * (2.0 * k2 + r2 * (3.0 * k3));  // d rad / d r2
+    const double rx = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x) - xd;
+    const double ry = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y - yd;
+    const double j11 = rad + 2.0 * x * x * drad + 2.0 * p1 * y + 6.0 * p2 * x;
+    const double j12 = 2.0 * x * y * drad + 2.0 * p1 * x + 2.0 * p2 * y;  // = j21
+    const double j22 = rad + 2.0 * y * y * drad + 6.0 * p1 * y + 2.0 * p2 * x;
+    const double det = j11 * j22 - j12 * j12;
+    if (fabs(det) > 1e-12) {
+      x -= (j22 * rx - j12 * ry) / det;
+      y -= (j11 * ry - j12 * rx) / det;
+    }
+  }
+  *X = x;
+  *Y = y;
+}
+
+// The ray of pixel (y, x) of a camera-table row.  All five coefficients exactly zero: camera_ray, unchanged.  Otherwise the pixel
+// centre and its x+1 / y+1 neighbours are undistorted by their own solves; the centre's camera-space direction is (X, -Y, -1) and
+// the neighbours' offsets are differences of the solved points, formed in fp64 and rounded to fp32 once.
+__device__ __forceinline__ void capture_ray(const float* __restrict__ c2w, const Camera& c, int y, int x, float* o, float* d,
+                                            float* area) {
+  if (c.k1 == 0.0f && c.k2 == 0.0f && c.k3 == 0.0f && c.p1 == 0.0f && c.p2 == 0.0f) {
+    camera_ray(c2w, c.k, y, x, o, d, area);
+    return;
+  }
+  const double fx = c.k.fx, fy = c.k.fy, cx = c.k.cx, cy = c.k.cy;
+  const double xd0 = ((double)x + 0.5 - cx) / fx, yd0 = ((double)y + 0.5 - cy) / fy;
+  const double xd1 = ((double)x + 1.5 - cx) / fx, yd1 = ((double)y + 1.5 - cy) / fy;
+  double X0, Y0, Xx, Yx, Xy, Yy;
+  undistort_point(c, xd0, yd0, &X0, &Y0);
+  undistort_point(c, xd1, yd0, &Xx, &Yx);
+  undistort_point(c, xd0, yd1, &Xy, &Yy);
+  camera_ray_at<false>(c2w, (float)X0, (float)(-Y0), (float)(Xx - X0), (float)(-(Yx - Y0)), (float)(Xy - X0), (float)(-(Yy - Y0)),
+                       o, d, area);
 }

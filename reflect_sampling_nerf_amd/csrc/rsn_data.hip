@@ -1,6 +1,7 @@
 // The standalone data path (reference reflect_sampling_nerf_datamanager.py:49-58 next_train, model.py:468-479 metrics):
 //   rsn_sample_camera_rays  Philox pixel sampler + pixel gather + camera ray generator, one thread per ray
 //   rsn_camera_rays_image   the same ray arithmetic for every pixel of one camera (rendering views)
+//   rsn_capture_rays_image  every pixel of one camera of a capture: a camera-table row with lens distortion (rsn_camera.h capture_ray)
 //   rsn_ssim                torchmetrics' structural_similarity_index_measure of two [H, W, 3] images, on the device
 // Recipes (Philox keying, ray arithmetic, SSIM definition): include/rsn.h.
 #include "rsn_camera.h"
@@ -58,6 +59,22 @@ __global__ __launch_bounds__(256) void rsn_camera_rays_image_kernel(int height, 
   const int y = p / width, x = p - y * width;
   float o[3], d[3], area;
   camera_ray(c2w, k, y, x, o, d, &area);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    origins[3 * p + j] = o[j];
+    directions[3 * p + j] = d[j];
+  }
+  pixel_area[p] = area;
+}
+
+// the camera row is read on the device: no host read, and a caller may pass a row of a table it scaled there
+__global__ __launch_bounds__(256) void rsn_capture_rays_image_kernel(int height, int width, const float* c2w, const float* camera,
+                                                                     float* origins, float* directions, float* pixel_area) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= height * width) return;
+  const int y = p / width, x = p - y * width;
+  float o[3], d[3], area;
+  capture_ray(c2w, load_camera(camera), y, x, o, d, &area);
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     origins[3 * p + j] = o[j];
@@ -204,6 +221,18 @@ extern "C" int rsn_camera_rays_image(int32_t height, int32_t width, const float*
   const int n = height * width;
   hipLaunchKernelGGL(rsn_camera_rays_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      height, width, c2w, Intrinsics{fx, fy, cx, cy}, origins, directions, pixel_area);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+extern "C" int rsn_capture_rays_image(int32_t height, int32_t width, const float* c2w, const float* camera, float* origins,
+                                      float* directions, float* pixel_area, void* stream) {
+  RSN_REQUIRE(height >= 1 && width >= 1 && (int64_t)height * width <= 0x7fffffff, RSN_ERR_INVALID_ARGUMENT,
+              "height=%d width=%d", height, width);
+  RSN_REQUIRE(c2w && camera && origins && directions && pixel_area, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
+  const int n = height * width;
+  hipLaunchKernelGGL(rsn_capture_rays_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     height, width, c2w, camera, origins, directions, pixel_area);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

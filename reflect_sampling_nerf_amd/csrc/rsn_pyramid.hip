@@ -1,6 +1,7 @@
 // Multi-scale data path (include/rsn.h, "image pyramids"):
 //   rsn_build_pyramid        levels 1 .. L-1 of every image as white-blended fp32 box averages of level 0, one lane per output pixel
 //   rsn_sample_pyramid_rays  Philox level + pixel sampler, pixel gather and camera ray generator, one lane per ray
+//   rsn_sample_capture_rays  the same sampler with a camera table: per-image intrinsics and lens distortion (rsn_camera.h capture_ray)
 // Level 0 is the uint8 RGBA image set itself and is never copied.  Recipes: include/rsn.h.
 #include "rsn_camera.h"
 #include "rsn_common.h"
@@ -78,7 +79,8 @@ struct PyramidSampleArgs {
   const uint8_t* images;  // [N, H, W, 4]
   const float* pyramid;   // [off[L], 3]; not read when levels == 1
   const float* c2w;       // [N, 3, 4]
-  Intrinsics k;
+  Intrinsics k;           // the one camera of all images (CAPTURE: not read)
+  const float* cameras;   // CAPTURE: the camera table [N, 9] (else not read)
   uint32_t seed, rank, step;
   float* origins;
   float* directions;
@@ -89,6 +91,9 @@ struct PyramidSampleArgs {
   LevelTable t;
 };
 
+// CAPTURE: image i's camera is row i of a.cameras, and the ray comes from capture_ray, which is camera_ray for a row without
+// distortion.  Everything else -- the Philox draw, the gather, the blend, the outputs -- is one text for both.
+template <bool CAPTURE>
 __global__ __launch_bounds__(256) void rsn_sample_pyramid_rays_kernel(PyramidSampleArgs a) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.n_rays) return;
@@ -101,9 +106,15 @@ __global__ __launch_bounds__(256) void rsn_sample_pyramid_rays_kernel(PyramidSam
   const uint32_t rem = flat - (uint32_t)i * hw;
   const int y = (int)(rem / wl), x = (int)(rem - (uint32_t)y * wl);
   const float inv = 1.0f / (float)(1 << l);  // a power of two: the level's intrinsics are exact
-  const Intrinsics k{a.k.fx * inv, a.k.fy * inv, a.k.cx * inv, a.k.cy * inv};
   float o[3], d[3], area;
-  camera_ray(a.c2w + (size_t)i * 12, k, y, x, o, d, &area);
+  if (CAPTURE) {  // the coefficients act on normalised coordinates: a level changes the four intrinsics only
+    Camera c = load_camera(a.cameras + (size_t)i * 9);
+    c.k = Intrinsics{c.k.fx * inv, c.k.fy * inv, c.k.cx * inv, c.k.cy * inv};
+    capture_ray(a.c2w + (size_t)i * 12, c, y, x, o, d, &area);
+  } else {
+    const Intrinsics k{a.k.fx * inv, a.k.fy * inv, a.k.cx * inv, a.k.cy * inv};
+    camera_ray(a.c2w + (size_t)i * 12, k, y, x, o, d, &area);
+  }
   float c[3];
   if (l == 0) {  // today's blend (rsn_sample_camera_rays)
     const uchar4 px = reinterpret_cast<const uchar4*>(a.images)[(size_t)flat];
@@ -130,7 +141,7 @@ __global__ __launch_bounds__(256) void rsn_sample_pyramid_rays_kernel(PyramidSam
   a.indices[3 * r + 0] = i;
   a.indices[3 * r + 1] = y;
   a.indices[3 * r + 2] = x;
-  a.level[r] = l;
+  if (a.level) a.level[r] = l;  // NULL only from the capture sampler at levels == 1, where every level is 0
 }
 
 // the checks both calls share; the message names what was given
@@ -144,6 +155,33 @@ int check_pyramid_shape(int32_t n_images, int32_t height, int32_t width, int32_t
               "height=%d width=%d: levels=%d needs both divisible by 2^(levels-1) = %d", height, width, levels, s);
   RSN_REQUIRE((uint64_t)n_images * (uint64_t)height * (uint64_t)width < (1ull << 32), RSN_ERR_INVALID_ARGUMENT,
               "n_images*height*width = %llu pixels: at most 2^32 - 1", (unsigned long long)n_images * height * width);
+  return RSN_OK;
+}
+
+// both samplers: the checks, the level table, one launch.  capture: the camera table `cameras`, else the shared pinhole k
+int sample_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images, const float* pyramid,
+                size_t pyramid_pixels, const float* c2w, bool capture, Intrinsics k, const float* cameras, int32_t n_rays,
+                uint32_t seed, uint32_t rank, uint32_t step, float* origins, float* directions, float* pixel_area, float* rgb, int32_t* indices,
+                int32_t* level, void* stream) {
+  RSN_TRY(check_pyramid_shape(n_images, height, width, levels));
+  RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
+  RSN_REQUIRE(capture || (k.fx != 0.0f && k.fy != 0.0f), RSN_ERR_INVALID_ARGUMENT, "fx=%g fy=%g", (double)k.fx, (double)k.fy);
+  if (n_rays == 0) return RSN_OK;
+  RSN_REQUIRE(images && c2w && origins && directions && pixel_area && rgb && indices && (level || (capture && levels == 1)) &&
+                  (pyramid || levels == 1) && (cameras || !capture),
+              RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
+  RSN_REQUIRE(((uintptr_t)images & 3) == 0, RSN_ERR_INVALID_ARGUMENT, "images must be 4-byte aligned");
+  const LevelTable t = level_table(n_images, height, width, levels);
+  RSN_REQUIRE(pyramid_pixels >= t.off[levels], RSN_ERR_INVALID_ARGUMENT, "pyramid of %zu pixels, %u needed", pyramid_pixels,
+              t.off[levels]);
+  PyramidSampleArgs a{n_images, height, width, levels, n_rays, images, pyramid, c2w, k, cameras,
+                      seed, rank, step, origins, directions, pixel_area, rgb, indices, level, t};
+  const dim3 grid((unsigned)((n_rays + 255) / 256));
+  if (capture)
+    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  RSN_HIP(hipGetLastError());
   return RSN_OK;
 }
 
@@ -169,20 +207,15 @@ extern "C" int rsn_sample_pyramid_rays(int32_t n_images, int32_t height, int32_t
                                        int32_t n_rays, uint32_t seed, uint32_t rank, uint32_t step, float* origins,
                                        float* directions, float* pixel_area, float* rgb, int32_t* indices, int32_t* level,
                                        void* stream) {
-  RSN_TRY(check_pyramid_shape(n_images, height, width, levels));
-  RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
-  RSN_REQUIRE(fx != 0.0f && fy != 0.0f, RSN_ERR_INVALID_ARGUMENT, "fx=%g fy=%g", (double)fx, (double)fy);
-  if (n_rays == 0) return RSN_OK;
-  RSN_REQUIRE(images && c2w && origins && directions && pixel_area && rgb && indices && level && (pyramid || levels == 1),
-              RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
-  RSN_REQUIRE(((uintptr_t)images & 3) == 0, RSN_ERR_INVALID_ARGUMENT, "images must be 4-byte aligned");
-  const LevelTable t = level_table(n_images, height, width, levels);
-  RSN_REQUIRE(pyramid_pixels >= t.off[levels], RSN_ERR_INVALID_ARGUMENT, "pyramid of %zu pixels, %u needed", pyramid_pixels,
-              t.off[levels]);
-  PyramidSampleArgs a{n_images, height, width, levels, n_rays, images, pyramid, c2w, Intrinsics{fx, fy, cx, cy},
-                      seed, rank, step, origins, directions, pixel_area, rgb, indices, level, t};
-  hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     a);
-  RSN_HIP(hipGetLastError());
-  return RSN_OK;
+  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, false, Intrinsics{fx, fy, cx, cy}, nullptr,
+                     n_rays, seed, rank, step, origins, directions, pixel_area, rgb, indices, level, stream);
+}
+
+extern "C" int rsn_sample_capture_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images,
+                                       const float* pyramid, size_t pyramid_pixels, const float* c2w, const float* cameras,
+                                       int32_t n_rays, uint32_t seed, uint32_t rank, uint32_t step, float* origins,
+                                       float* directions, float* pixel_area, float* rgb, int32_t* indices, int32_t* level,
+                                       void* stream) {
+  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, true, Intrinsics{}, cameras, n_rays,
+                     seed, rank, step, origins, directions, pixel_area, rgb, indices, level, stream);
 }

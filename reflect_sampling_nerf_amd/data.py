@@ -1,4 +1,5 @@
-"""Posed image sets without nerfstudio: a Blender-format parser and a device-resident ray data manager.
+"""Posed image sets without nerfstudio: a Blender-format parser, a nerfstudio-format (capture) parser and a device-resident ray
+data manager.
 
 `load_blender_split` follows nerfstudio 0.3's BlenderDataParser (the reference trains with it: reflect_sampling_nerf_config.py:36-41);
 `RayDataManager.next_train` is the reference datamanager's next_train (reflect_sampling_nerf_datamanager.py:49-58: pixel sampler ->
@@ -8,6 +9,12 @@ no device-to-host read.  The exact sampling and ray recipes are in include/rsn.h
 `RayDataManager(..., levels=L)` with L > 1 is mip-NeRF's multi-scale protocol: rsn_build_pyramid forms every image at 1/2 .. 1/2^(L-1)
 of its size once, next_train draws each ray's level with probability 1/L (rsn_sample_pyramid_rays, still one launch), and
 camera_ray_bundle / image take a level.
+
+`load_nerfstudio_split` reads a nerfstudio-format capture (one transforms.json, as ns-process-data writes it): per-frame intrinsics,
+OpenCV radial and tangential distortion, JPEG or PNG images, nerfstudio's pose normalisation and train / eval split.  Its scene
+carries a camera table (`cameras` [N,9]); with one, RayDataManager uploads the table once and draws its batches with
+rsn_sample_capture_rays and its views with rsn_capture_rays_image (include/rsn.h, "captures"): distorted rays are made on the
+device, one launch, no host read.  Without a table every call is the one it always was.
 """
 from __future__ import annotations
 
@@ -15,7 +22,7 @@ import json
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,7 +35,12 @@ from .nerfstudio_compat import RayBundle
 class BlenderScene:
     """One split of a posed image set: images uint8 [N,H,W,4] RGBA (alpha 255 for RGB sources), c2w float32 [N,3,4],
     one pinhole camera (fx, fy, cx, cy) shared by all images.  normals: None, or the ground-truth normal maps uint8 [N,H,W,3], the
-    bytes of the scene's normal images, encoding n * 0.5 + 0.5 (eval's geometry metrics read them; training never does)."""
+    bytes of the scene's normal images, encoding n * 0.5 + 0.5 (eval's geometry metrics read them; training never does).
+
+    cameras: None (the shared pinhole above, and nothing else changes), or the camera table of a capture, float32 [N,9] with row i =
+    (fx, fy, cx, cy, k1, k2, k3, p1, p2) of image i (include/rsn.h, "captures"); fx .. cy then repeat row 0's pinhole part, for the
+    callers that want one representative camera (an orbit's field of view, the occupancy box).  dataparser_transform [3,4] float64 and
+    dataparser_scale: what load_nerfstudio_split applied to the file's poses (None for other sources); file_paths: the frames' names."""
 
     images: np.ndarray
     c2w: np.ndarray
@@ -37,6 +49,10 @@ class BlenderScene:
     cx: float
     cy: float
     normals: Optional[np.ndarray] = None
+    cameras: Optional[np.ndarray] = None
+    dataparser_transform: Optional[np.ndarray] = None
+    dataparser_scale: Optional[float] = None
+    file_paths: Optional[List[str]] = None
 
     @property
     def num_images(self) -> int:
@@ -131,6 +147,253 @@ def load_blender_split(root: str, split: str, scale_factor: float = 1.0, normals
                         normals=np.ascontiguousarray(np.stack(normal_maps)) if normals else None)
 
 
+# ------------------------------------------------------------------------------------------------ captures (nerfstudio format)
+CAMERA_COLUMNS = ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")  # a row of the camera table (include/rsn.h, "captures")
+CAPTURE_CAMERA_MODELS = (None, "OPENCV", "PINHOLE")
+ORIENTATIONS = ("up", "none")
+CENTERS = ("poses", "none")
+EVAL_MODES = ("fraction", "all")
+DATA_FORMATS = ("auto", "blender", "nerfstudio")
+UNDISTORT_ITERATIONS = 10  # the kernel's count (rsn_camera.h)
+UNDISTORT_MAX_RESIDUAL = 1e-9  # of the load-time check, in normalised image units
+
+
+def distort_points(row, X, Y):
+    """The OpenCV / COLMAP model of include/rsn.h ("captures") in float64: undistorted normalised (X, Y) -> distorted (Xd, Yd).
+    row: the nine numbers of a camera-table row (only k1 .. p2 are read).  Image coordinates: x right, y down."""
+    k1, k2, k3, p1, p2 = (float(v) for v in row[4:9])
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    r2 = X * X + Y * Y
+    rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    return X * rad + 2.0 * p1 * X * Y + p2 * (r2 + 2.0 * X * X), Y * rad + p1 * (r2 + 2.0 * Y * Y) + 2.0 * p2 * X * Y
+
+
+def undistort_points(row, Xd, Yd, iterations: int = UNDISTORT_ITERATIONS):
+    """The kernel's solve in float64: Newton on the 2 x 2 system from (Xd, Yd), `iterations` steps, none skipped early; a step whose
+    |det J| <= 1e-12 leaves the point where it is.  -> (X, Y)."""
+    k1, k2, k3, p1, p2 = (float(v) for v in row[4:9])
+    Xd, Yd = np.asarray(Xd, dtype=np.float64), np.asarray(Yd, dtype=np.float64)
+    x, y = Xd.copy(), Yd.copy()
+    for _ in range(iterations):
+        r2 = x * x + y * y
+        rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+        drad = k1 + r2 * (2.0 * k2 + r2 * (3.0 * k3))
+        rx = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x) - Xd
+        ry = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y - Yd
+        j11 = rad + 2.0 * x * x * drad + 2.0 * p1 * y + 6.0 * p2 * x
+        j12 = 2.0 * x * y * drad + 2.0 * p1 * x + 2.0 * p2 * y
+        j22 = rad + 2.0 * y * y * drad + 6.0 * p1 * y + 2.0 * p2 * x
+        det = j11 * j22 - j12 * j12
+        ok = np.abs(det) > 1e-12
+        safe = np.where(ok, det, 1.0)
+        x = np.where(ok, x - (j22 * rx - j12 * ry) / safe, x)
+        y = np.where(ok, y - (j11 * ry - j12 * rx) / safe, y)
+    return x, y
+
+
+def undistort_residual(row, height: int, width: int) -> float:
+    """The largest |distort(solve(p)) - p| of the kernel's solve at the four corners and four edge midpoints of the outermost pixel
+    centres -- where the radius, and with it the distortion, is largest.  inf when the solve left the finite numbers."""
+    fx, fy, cx, cy = (float(v) for v in row[:4])
+    xs = np.array([0.5, 0.5 * width, width - 0.5], dtype=np.float64)
+    ys = np.array([0.5, 0.5 * height, height - 0.5], dtype=np.float64)
+    px, py = (a.ravel() for a in np.meshgrid(xs, ys))
+    keep = ~((px == xs[1]) & (py == ys[1]))  # not the centre
+    Xd, Yd = (px[keep] - cx) / fx, (py[keep] - cy) / fy
+    with np.errstate(all="ignore"):
+        X, Y = undistort_points(row, Xd, Yd)
+        bx, by = distort_points(row, X, Y)
+        res = np.maximum(np.abs(bx - Xd), np.abs(by - Yd))
+    return float(res.max()) if np.all(np.isfinite(res)) else math.inf
+
+
+def rotation_onto_z(up) -> np.ndarray:
+    """The rotation [3,3] that takes the unit vector `up` onto +z, by Rodrigues' formula about up x z: I + K + K^2 / (1 + c) with
+    c = up . z.  up = -z (no axis is singled out): the turn of pi about x."""
+    a = np.asarray(up, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    c = float(a[2])
+    if c < -1.0 + 1e-8:
+        return np.diag([1.0, -1.0, -1.0])
+    v = np.cross(a, np.array([0.0, 0.0, 1.0]))
+    K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return np.eye(3) + K + K @ K / (1.0 + c)
+
+
+def auto_orient_and_center_poses(c2w, orientation: str = "up", center: str = "poses") -> Tuple[np.ndarray, np.ndarray]:
+    """nerfstudio's auto_orient_and_center_poses for the two methods a capture uses, in float64: c2w [N,3,4] -> (transform @ c2w,
+    transform [3,4]).  center "poses": the mean camera position goes to the origin; orientation "up": the normalised mean of the
+    cameras' up axes, c2w[:, :3, 1], goes to +z.  transform = [R | -R t]."""
+    if orientation not in ORIENTATIONS:
+        raise ValueError(f"orientation = {orientation!r}: choose from {', '.join(ORIENTATIONS)}")
+    if center not in CENTERS:
+        raise ValueError(f"center = {center!r}: choose from {', '.join(CENTERS)}")
+    P = np.asarray(c2w, dtype=np.float64)[:, :3, :4]
+    t = P[:, :, 3].mean(axis=0) if center == "poses" else np.zeros(3)
+    R = np.eye(3)
+    if orientation == "up":
+        up = P[:, :, 1].mean(axis=0)
+        n = np.linalg.norm(up)
+        if not n > 0.0:
+            raise ValueError("orientation 'up': the cameras' up axes average to zero; use orientation 'none'")
+        R = rotation_onto_z(up / n)
+    transform = np.concatenate([R, -(R @ t)[:, None]], axis=1)
+    out = np.einsum("ij,njk->nik", R, P)
+    out[:, :, 3] += transform[:, 3]
+    return out, transform
+
+
+def capture_split_indices(n: int, split: str, train_split_fraction: float = 0.9, eval_mode: str = "fraction") -> np.ndarray:
+    """nerfstudio's fraction split of n frames (sorted by name): num_train = ceil(n * fraction), i_train = linspace(0, n - 1,
+    num_train) truncated to integers, the eval set its complement; "train" gets i_train, "val" and "test" the complement.
+    eval_mode "all": every split gets every frame."""
+    if eval_mode not in EVAL_MODES:
+        raise ValueError(f"eval_mode = {eval_mode!r}: choose from {', '.join(EVAL_MODES)}")
+    if split not in ("train", "val", "test"):
+        raise ValueError(f"split = {split!r}: choose from train, val, test")
+    every = np.arange(n)
+    if eval_mode == "all":
+        return every
+    if not 0.0 < train_split_fraction <= 1.0:
+        raise ValueError(f"train_split_fraction = {train_split_fraction}: need 0 < F <= 1")
+    i_train = np.linspace(0, n - 1, int(math.ceil(n * train_split_fraction)), dtype=int)
+    return i_train if split == "train" else np.setdiff1d(every, i_train)
+
+
+def detect_data_format(root: str, data_format: str = "auto") -> str:
+    """"nerfstudio" for a directory with transforms.json, "blender" for one with transforms_train.json or any other
+    transforms_{split}.json (the former wins when both exist); data_format other than "auto" is returned as it is."""
+    if data_format not in DATA_FORMATS:
+        raise ValueError(f"data_format = {data_format!r}: choose from {', '.join(DATA_FORMATS)}")
+    if data_format != "auto":
+        return data_format
+    if os.path.isfile(os.path.join(root, "transforms.json")):
+        return "nerfstudio"
+    if os.path.isdir(root) and any(n.startswith("transforms_") and n.endswith(".json") for n in os.listdir(root)):
+        return "blender"
+    raise FileNotFoundError(f"{root}: neither transforms.json (a nerfstudio-format capture) nor transforms_train.json (a Blender-format scene)")
+
+
+def write_dataparser_transforms(path: str, transform, scale: float) -> None:
+    """nerfstudio's dataparser_transforms.json: {"transform": [3][4], "scale": s}."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump({"transform": np.asarray(transform, dtype=np.float64).tolist(), "scale": float(scale)}, fh, indent=4)
+        fh.write("\n")
+
+
+def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orientation: str = "up", center: str = "poses",
+                          auto_scale: bool = True, train_split_fraction: float = 0.9, eval_mode: str = "fraction",
+                          applied: Optional[Tuple[Sequence, float]] = None, pixels: bool = True) -> BlenderScene:
+    """One split of a nerfstudio-format capture, root/transforms.json, as nerfstudio's NerfstudioDataParser reads it; -> a scene
+    with a camera table.  All arithmetic on the host in float64, rounded once to float32.
+
+    Cameras: fl_x, fl_y, cx, cy, w, h, k1, k2, k3, p1, p2 globally or per frame (the frame's value wins), missing coefficients 0;
+    camera_model absent, OPENCV or PINHOLE.  Frames are ordered by file_path (plain string sort); file_path is relative to the JSON
+    and carries its extension; PNG and JPEG through Pillow, RGB images get alpha 255.
+    Poses: auto_orient_and_center_poses over ALL frames (before the split), then the translations times scale_factor / max |t| --
+    the largest absolute translation component, nerfstudio's rule -- when auto_scale is on, else times scale_factor.
+    applied = (transform [3,4], scale): apply exactly these instead (a checkpoint's: the frame a model was trained in).
+    Split: capture_split_indices.
+    pixels=False: the images are not decoded, only their headers read (every check below still runs); scene.images is then a
+    read-only zero-stride array of the right shape -- for a caller that wants the cameras alone (render).
+
+    ValueError, naming the frame: another camera_model (OPENCV_FISHEYE, ...), a non-zero k4, a mask_path, images of differing
+    sizes, a w / h that disagrees with the file, and a coefficient set whose solve does not converge over the image (residual above
+    1e-9 at the corners and edge midpoints: the model is not invertible there; the kernels do not check).  FileNotFoundError for a
+    missing image.  downscale_factor / images_K directories, masks, fisheye and equirectangular cameras are not supported."""
+    from PIL import Image
+
+    meta_path = os.path.join(root, "transforms.json")
+    if not os.path.isfile(meta_path):
+        raise FileNotFoundError(f"{meta_path}: no such file (a nerfstudio-format capture has one transforms.json)")
+    with open(meta_path) as fh:
+        meta = json.load(fh)
+    frames = sorted(meta.get("frames") or [], key=lambda fr: fr["file_path"])
+    if not frames:
+        raise ValueError(f"{meta_path} lists no frames")
+
+    def value(fr, key, default=None):
+        v = fr.get(key, meta.get(key, default))
+        if v is None:
+            raise ValueError(f"{meta_path}: frame {fr['file_path']} has no {key}, and the file has no global one")
+        return v
+
+    rows, poses = [], []
+    for fr in frames:
+        name = fr["file_path"]
+        model = fr.get("camera_model", meta.get("camera_model"))
+        if model not in CAPTURE_CAMERA_MODELS:
+            raise ValueError(f"{meta_path}: frame {name}: camera_model {model!r} is not supported (OPENCV, PINHOLE or absent)")
+        if float(fr.get("k4", meta.get("k4", 0.0)) or 0.0) != 0.0:
+            raise ValueError(f"{meta_path}: frame {name}: k4 = {fr.get('k4', meta.get('k4'))} is not zero; the model here has k1, k2, k3, p1, p2")
+        if "mask_path" in fr:
+            raise ValueError(f"{meta_path}: frame {name} has a mask_path; masks are not supported")
+        rows.append([float(value(fr, "fl_x")), float(value(fr, "fl_y")), float(value(fr, "cx")), float(value(fr, "cy"))]
+                    + [float(value(fr, k, 0.0)) for k in CAMERA_COLUMNS[4:]])
+        if rows[-1][0] == 0.0 or rows[-1][1] == 0.0:
+            raise ValueError(f"{meta_path}: frame {name}: fl_x = {rows[-1][0]}, fl_y = {rows[-1][1]}: a focal length is zero")
+        poses.append(np.asarray(fr["transform_matrix"], dtype=np.float64)[:3, :4])
+    rows64, poses = np.asarray(rows, dtype=np.float64), np.stack(poses)
+    if applied is None:
+        poses, transform = auto_orient_and_center_poses(poses, orientation, center)
+        scale = float(scale_factor)
+        if auto_scale:
+            scale /= float(np.abs(poses[:, :, 3]).max())
+    else:
+        transform, scale = np.asarray(applied[0], dtype=np.float64)[:3, :4], float(applied[1])
+        poses = np.einsum("ij,njk->nik", transform[:, :3], poses)
+        poses[:, :, 3] += transform[:, 3]
+    poses[:, :, 3] *= scale
+
+    keep = capture_split_indices(len(frames), split, train_split_fraction, eval_mode)
+    if len(keep) == 0:
+        raise ValueError(f"{meta_path}: the {split} split of {len(frames)} frames at train_split_fraction {train_split_fraction} is empty")
+    images, size = [], None
+    checked = {}
+    for i in keep:
+        fr, name = frames[i], frames[i]["file_path"]
+        path = os.path.join(root, name)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path}: image of frame {name} of {meta_path} not found")
+        with Image.open(path) as img:
+            if pixels:
+                im = np.asarray(img.convert("RGBA") if img.mode != "RGBA" else img, dtype=np.uint8)
+            else:
+                im = np.broadcast_to(np.zeros(1, np.uint8), (img.size[1], img.size[0], 4))
+        if size is None:
+            size = im.shape[:2]
+        if im.shape[:2] != size:
+            raise ValueError(f"{meta_path}: frame {name} is {im.shape[1]} x {im.shape[0]} pixels, the split's first image "
+                             f"{size[1]} x {size[0]}; images of differing sizes are not supported")
+        w, h = fr.get("w", meta.get("w")), fr.get("h", meta.get("h"))
+        if (w is not None and int(w) != im.shape[1]) or (h is not None and int(h) != im.shape[0]):
+            raise ValueError(f"{meta_path}: frame {name}: w x h = {w} x {h}, but the file holds {im.shape[1]} x {im.shape[0]} pixels")
+        key = rows64[i].tobytes()
+        if key not in checked and np.any(rows64[i, 4:] != 0.0):
+            checked[key] = undistort_residual(rows64[i], im.shape[0], im.shape[1])
+            if not checked[key] <= UNDISTORT_MAX_RESIDUAL:
+                raise ValueError(f"{meta_path}: frame {name}: the distortion model (k1, k2, k3, p1, p2) = {tuple(rows64[i, 4:])} is not "
+                                 f"invertible over the {im.shape[1]} x {im.shape[0]} image: {UNDISTORT_ITERATIONS} Newton steps leave a "
+                                 f"residual of {checked[key]:.3g} at its border (at most {UNDISTORT_MAX_RESIDUAL:g})")
+        images.append(im)
+    cams = np.ascontiguousarray(rows64[keep].astype(np.float32))
+    stack = np.ascontiguousarray(np.stack(images)) if pixels else np.broadcast_to(np.zeros(1, np.uint8), (len(images),) + images[0].shape)
+    return BlenderScene(images=stack, c2w=np.ascontiguousarray(poses[keep].astype(np.float32)),
+                        fx=float(cams[0, 0]), fy=float(cams[0, 1]), cx=float(cams[0, 2]), cy=float(cams[0, 3]), cameras=cams,
+                        dataparser_transform=transform, dataparser_scale=scale, file_paths=[frames[i]["file_path"] for i in keep])
+
+
+def shared_pinhole(scene: BlenderScene, what: str) -> Tuple[float, float, float, float]:
+    """(fx, fy, cx, cy) for a caller that projects through ONE pinhole camera (the TSDF and point-cloud exports): the scene's own,
+    or a camera table's when all its rows are equal and free of distortion.  ValueError naming `what` otherwise."""
+    cams = scene.cameras
+    if cams is not None and (np.any(cams[:, 4:] != 0.0) or np.any(cams != cams[0])):
+        raise ValueError(f"{what} projects through one shared pinhole camera: it accepts a capture only when all its cameras are equal "
+                         "and free of lens distortion, and this one's are not")
+    return scene.fx, scene.fy, scene.cx, scene.cy
+
+
 MAX_LEVELS = 5  # include/rsn.h RSN_PYRAMID_MAX_LEVELS: a 16 x 16 box keeps the integer sums of the blend below 2^24
 
 
@@ -161,7 +424,11 @@ class RayDataManager:
 
     levels > 1: the images also exist at 1/2 .. 1/2^(levels-1) of their size (self.pyramid, built once on the device); a ray's level
     is drawn first, with probability 1 / levels, then its pixel within the level, from the same Philox words.  levels = 1 is the
-    single-scale path: the same launches and bytes as without the argument."""
+    single-scale path: the same launches and bytes as without the argument.
+
+    A scene with a camera table (scene.cameras, a capture): the table is uploaded once, per level with the four intrinsics over 2^l,
+    and next_train / camera_ray_bundle go through rsn_sample_capture_rays / rsn_capture_rays_image at every level count.  Without a
+    table they make the calls they always made."""
 
     def __init__(self, scene: BlenderScene, device, num_rays_per_batch: int = 1024, seed: int = 0, rank: int = 0, levels: int = 1):
         self.levels = int(levels)
@@ -176,6 +443,14 @@ class RayDataManager:
         self.normals = None  # uint8 [N,H,W,3]: level 0 only, the pyramid builds no normal levels
         if scene.normals is not None:
             self.normals = torch.from_numpy(np.ascontiguousarray(scene.normals)).to(self.device)
+        self.cameras = None  # fp32 [levels, N, 9]: level l's table has fx, fy, cx, cy over 2^l (exact), the coefficients as they are
+        if scene.cameras is not None:
+            cams = np.ascontiguousarray(scene.cameras, dtype=np.float32)
+            if cams.shape != (scene.num_images, len(CAMERA_COLUMNS)):
+                raise ValueError(f"cameras must be [{scene.num_images},{len(CAMERA_COLUMNS)}], got {cams.shape}")
+            scale = np.ones((self.levels, 1, len(CAMERA_COLUMNS)), np.float32)
+            scale[:, 0, :4] = (0.5 ** np.arange(self.levels, dtype=np.float32))[:, None]
+            self.cameras = torch.from_numpy(cams[None] * scale).to(self.device)
         self._lib = _abi.load_library()
         self.pyramid = None  # fp32 [pixels of the levels >= 1, 3]
         if self.levels > 1:
@@ -196,6 +471,17 @@ class RayDataManager:
         idx = torch.empty(R, 4 if multi else 3, device=self.device, dtype=torch.int32)  # multi: the levels ride behind the indices
         o, d, pa, rgb = (flat[0:3 * R].view(R, 3), flat[3 * R:6 * R].view(R, 3), flat[6 * R:7 * R].view(R, 1),
                          flat[7 * R:10 * R].view(R, 3))
+        if self.cameras is not None:
+            lvl = None  # single-scale: the sampler takes no level pointer, and the batch is shaped as it always was
+            if multi:
+                both = idx.view(-1)
+                idx, lvl = both[:3 * R].view(R, 3), both[3 * R:]
+            _abi.check(self._lib.rsn_sample_capture_rays(
+                s.num_images, s.height, s.width, self.levels, _abi.ptr(self.images), _abi.ptr(self.pyramid),
+                self.pyramid.shape[0] if multi else 0, _abi.ptr(self.c2w), _abi.ptr(self.cameras), R, self.seed, self.rank,
+                int(step) & 0xFFFFFFFF, _abi.ptr(o), _abi.ptr(d), _abi.ptr(pa), _abi.ptr(rgb), _abi.ptr(idx), _abi.ptr(lvl), self._stream()))
+            rb = RayBundle(origins=o, directions=d, pixel_area=pa, camera_indices=idx[:, 0:1])
+            return rb, ({"image": rgb, "indices": idx, "levels": lvl} if multi else {"image": rgb, "indices": idx})
         if not multi:
             _abi.check(self._lib.rsn_sample_camera_rays(
                 s.num_images, s.height, s.width, _abi.ptr(self.images), _abi.ptr(self.c2w), s.fx, s.fy, s.cx, s.cy, R,
@@ -231,7 +517,7 @@ class RayDataManager:
         from .render import camera_rays
 
         (h, w), (fx, fy, cx, cy) = self.level_sizes[self._level(level)], self.level_intrinsics(level)
-        rb = camera_rays(self.c2w[i], h, w, fx, fy, cx, cy, self.device)
+        rb = camera_rays(self.c2w[i], h, w, fx, fy, cx, cy, self.device, camera=None if self.cameras is None else self.cameras[level, i])
         rb.camera_indices = torch.full((h, w, 1), i, device=self.device, dtype=torch.int32)
         return rb
 

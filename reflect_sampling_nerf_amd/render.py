@@ -153,15 +153,28 @@ def turbo_lut(device) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ rays
-def camera_rays(c2w, height: int, width: int, fx: float, fy: float, cx: float, cy: float, device) -> RayBundle:
+def camera_rays(c2w, height: int, width: int, fx: float, fy: float, cx: float, cy: float, device, camera=None) -> RayBundle:
     """The [H,W] RayBundle (origins, directions [H,W,3], pixel_area [H,W,1]; row-major) of the pinhole camera with pose c2w
-    ([3,4] or [4,4]; a tensor on `device` is used where it lies, anything else is uploaded).  One launch, no host read."""
+    ([3,4] or [4,4]; a tensor on `device` is used where it lies, anything else is uploaded).  One launch, no host read.
+    camera: None, or a camera row (fx, fy, cx, cy, k1, k2, k3, p1, p2) of a capture (include/rsn.h, "captures") -- nine numbers, or a
+    fp32 tensor [9] on `device`, used where it lies; the view then goes through rsn_capture_rays_image and fx .. cy are not read."""
     dev = torch.device(device)
     there = isinstance(c2w, torch.Tensor) and c2w.device.type == dev.type
     pose = c2w[:3, :4].to(torch.float32).contiguous() if there else _upload(torch.from_numpy(_poses(c2w)), dev)
     H, W = int(height), int(width)
     flat = torch.empty(H * W * 7, device=dev, dtype=torch.float32)
     o, d, pa = flat[0:3 * H * W].view(H, W, 3), flat[3 * H * W:6 * H * W].view(H, W, 3), flat[6 * H * W:].view(H, W, 1)
+    if camera is not None:
+        if isinstance(camera, torch.Tensor) and camera.device.type == dev.type:
+            row = camera.to(torch.float32).contiguous()
+        else:
+            row = _upload(torch.from_numpy(np.ascontiguousarray(np.asarray(camera.cpu() if isinstance(camera, torch.Tensor) else camera,
+                                                                         dtype=np.float32))), dev)
+        if tuple(row.shape) != (9,):
+            raise ValueError(f"camera must hold the 9 numbers fx fy cx cy k1 k2 k3 p1 p2, got shape {tuple(row.shape)}")
+        _abi.check(_abi.load_library().rsn_capture_rays_image(H, W, _abi.ptr(pose), _abi.ptr(row), _abi.ptr(o), _abi.ptr(d),
+                                                              _abi.ptr(pa), _stream(dev)))
+        return RayBundle(origins=o, directions=d, pixel_area=pa)
     _abi.check(_abi.load_library().rsn_camera_rays_image(H, W, _abi.ptr(pose), fx, fy, cx, cy, _abi.ptr(o), _abi.ptr(d),
                                                          _abi.ptr(pa), _stream(dev)))
     return RayBundle(origins=o, directions=d, pixel_area=pa)
@@ -374,11 +387,12 @@ def check_channels(channels: Sequence[str]) -> Tuple[str, ...]:
 def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: float, cy: float,
                 channels: Sequence[str] = DEFAULT_CHANNELS, depth_range: Optional[Tuple[float, float]] = None,
                 on_frame: Optional[Callable[[int, np.ndarray], None]] = None, panel: bool = True,
-                stage_events: Optional[list] = None) -> List[np.ndarray]:
+                stage_events: Optional[list] = None, camera_table=None) -> List[np.ndarray]:
     """Render the poses c2w [F,3,4] with `model` (eval mode, on its device) and hand every frame to on_frame(i, array) in order.
     array is uint8 [H, C*W, 3] (panel: the channels' tiles left to right) or [C,H,W,3] (panel=False); it is a view of one of two
     pinned host buffers, valid until on_frame returns.  Without on_frame the frames are copied and returned as a list (with
-    on_frame the list is empty).  depth_range: None = the model's collider planes.
+    on_frame the list is empty).  depth_range: None = the model's collider planes.  camera_table: None, or one camera row per pose
+    [F,9] (a capture's frames through their own cameras, lens distortion included); fx .. cy are then not read.
 
     Per frame i: rays, model.get_outputs_for_camera_ray_bundle, one rsn_visualize per channel, a non_blocking copy into host
     buffer i % 2 and an event.  Only after frame i is enqueued does the host wait for the event of frame i-1 and call its on_frame,
@@ -397,6 +411,12 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
         raise ValueError(f"depth_range {depth_range}: need finite near < far")
     shape = (H, C * W, 3) if panel else (C, H, W, 3)
     poses_dev = _upload(torch.from_numpy(poses), dev)
+    table_dev = None
+    if camera_table is not None:
+        table = np.ascontiguousarray(camera_table, dtype=np.float32)
+        if table.shape != (F, 9):
+            raise ValueError(f"camera_table must be [{F},9], one row per pose, got {table.shape}")
+        table_dev = _upload(torch.from_numpy(table), dev)
     panel_dev = torch.empty(shape, device=dev, dtype=torch.uint8)
     host = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(min(2, F))]
     done = [torch.cuda.Event() for _ in host]
@@ -414,7 +434,7 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
         for i in range(F):
             ev = ops.new_events(stage_events)
             ops.record_event(ev)
-            rays = camera_rays(poses_dev[i], H, W, fx, fy, cx, cy, dev)
+            rays = camera_rays(poses_dev[i], H, W, fx, fy, cx, cy, dev, camera=None if table_dev is None else table_dev[i])
             ops.record_event(ev)
             outputs = model.get_outputs_for_camera_ray_bundle(rays)
             ops.record_event(ev)
@@ -435,7 +455,7 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
 def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx: float, fy: float, cx: float, cy: float,
                       channels: Sequence[str] = DEFAULT_CHANNELS, depth_range: Optional[Tuple[float, float]] = None,
                       mma: str = "f32", chunk: int = DEFAULT_CHUNK, tiles: bool = False, device="cuda:0", model_config=None,
-                      occupancy: Optional[dict] = None) -> dict:
+                      occupancy: Optional[dict] = None, camera_table=None) -> dict:
     """Render the poses c2w [F,3,4] from a checkpoint (a step-*.ckpt, or the newest of a run directory) into out_dir: the tiled
     panel of every frame as out_dir/panel/0000.png ..., or with `tiles` one image per channel as out_dir/<channel>/0000.png ...,
     and out_dir/frames.json (checkpoint, step, size, intrinsics, channels in tile order, depth range, mma, chunk, and per frame
@@ -444,6 +464,8 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
     rendered with empty-space skipping and frames.json gains an "occupancy" entry (settings, box, occupied share of cells, culled
     share of rays; the latter read from the device once, after the last frame).  With "samples": True in it the field is also
     evaluated only on the samples in occupied cells, and the entry holds "samples": per level the sample slots seen and the live ones.
+    camera_table: None, or [F,9], one camera row per pose (render_path); frames.json then holds every frame's row as "camera", and
+    the occupancy box is laid out from the pinhole fx .. cy given here.
     -> the dict written to frames.json plus {"seconds": wall time of the frames, "out": out_dir}."""
     from PIL import Image
 
@@ -475,12 +497,15 @@ def render_checkpoint(ckpt: str, out_dir: str, c2w, height: int, width: int, fx:
             files.append({"panel": f"panel/{name}"})
 
     t0 = time.time()
-    render_path(model, poses, height, width, fx, fy, cx, cy, channels, depth_range, write, panel=not tiles)
+    render_path(model, poses, height, width, fx, fy, cx, cy, channels, depth_range, write, panel=not tiles, camera_table=camera_table)
     seconds = time.time() - t0
     meta = {"checkpoint": ckpt, "step": step, "width": int(width), "height": int(height), "fx": float(fx), "fy": float(fy),
             "cx": float(cx), "cy": float(cy), "channels": list(channels), "tiles": bool(tiles),
             "depth_range": [float(depth_range[0]), float(depth_range[1])], "mma": mma, "chunk": int(chunk),
             "frames": [{"files": f, "c2w": poses[i].astype(np.float64).tolist()} for i, f in enumerate(files)]}
+    if camera_table is not None:
+        for fr, row in zip(meta["frames"], np.asarray(camera_table, dtype=np.float64)):
+            fr["camera"] = row.tolist()
     if occupancy is not None:
         meta["occupancy"] = model.occupancy.describe()
     with replacing(os.path.join(out_dir, "frames.json")) as tmp, open(tmp, "w") as fh:

@@ -1,4 +1,4 @@
-"""Standalone training and evaluation on Blender-format scenes, without nerfstudio.
+"""Standalone training and evaluation on Blender-format scenes and nerfstudio-format captures, without nerfstudio.
 
     python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L] [--distortion-loss X [--distortion-loss-coarse Y]]
     python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L] [--normals [--normals-suffix _normal] [--normals-space world|camera]]
@@ -8,6 +8,7 @@
     python -m reflect_sampling_nerf_amd.trainer export-mesh ... [--decimate-cells N | --target-faces N]
     python -m reflect_sampling_nerf_amd.trainer export-pointcloud --ckpt FILE|DIR --out cloud.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--resolution 512] [--min-accumulation 0.5] [--edge 0.05 | --no-edge] [--no-thin]
     python -m reflect_sampling_nerf_amd.trainer render --ckpt FILE|DIR --out DIR [--data DIR | --poses FILE.json | --width W --height H --fov-x DEG --radius R]
+    (train, eval, render, on a nerfstudio-format capture: [--data-format auto|blender|nerfstudio] [--orientation up|none] [--center poses|none] [--no-auto-scale] [--train-split-fraction F] [--eval-mode fraction|all]; train: [--near N --far F] [--primary-spacing uniform|reciprocal [--primary-tan T]])
     (eval and render: [--skip-empty | --skip-empty-samples [--occupancy-resolution N] [--occupancy-sigma S] [--occupancy-dilate D] [--occupancy-bounds X0 Y0 Z0 X1 Y1 Z1]])
 
 `train` is the reference's `ns-train reflect-sampling-nerf --data DIR` loop on this package's own pieces: the reference
@@ -31,6 +32,23 @@ and `--skip-nonfinite` leaves parameters and moments untouched on a step whose g
 GradScaler does for `ns-train` under mixed precision); both are off by default and decided on the device (FusedRAdam).  A guarded
 run's log lines carry the gradient norm, the clip factor and the number of skipped steps, and the first line after a skip names the
 parameters whose gradients were not finite.  Both settings are recorded in the checkpoint and come back with --resume.
+
+`--data DIR` with a transforms.json in it is a nerfstudio-format capture (ns-process-data's output; transforms_train.json: a Blender-
+format scene; --data-format overrides): per-frame or global fl_x fl_y cx cy w h and OpenCV coefficients k1 k2 k3 p1 p2, JPEG or PNG
+frames named with their extension, sorted by name (data.load_nerfstudio_split).  The poses are normalised as nerfstudio does --
+--orientation up rotates the cameras' mean up axis onto +z, --center poses moves their mean position to the origin, and the
+translations are scaled so that the largest component is --scale-factor (--no-auto-scale: times --scale-factor alone) -- over all
+frames, and then split: ceil(N F) evenly spaced frames train, the others are held out for `eval` (--eval-mode all: every frame does
+both).  Distorted rays are made on the device (include/rsn.h, "captures").  `train` records how it read the capture, and the transform
+and scale it applied, in the checkpoint and in OUT/dataparser_transforms.json (nerfstudio's file); --resume, `eval` and `render --data`
+take them from there unless told otherwise (`--center-poses` is their name for train's --center), so a checkpoint is evaluated and
+rendered in the frame it was trained in.  `render --data` on a capture renders the file's frames through their own cameras; an orbit
+(--path orbit) goes through the first camera's pinhole part.  A capture's primary rays default to --near 0.05 --far 256
+--primary-spacing reciprocal --primary-tan 1 (s(t) = t / (1/T + t); far 256 is the far of the model's own reflected rays): starting
+points that have NOT been measured on a scene.  The four flags work on a Blender-format scene too, whose defaults stay 2, 6 and
+uniform with nothing recorded; what is recorded, every tool that opens the checkpoint applies.  Masks, images of differing sizes,
+fisheye cameras and a non-zero k4 are errors that name the frame; the TSDF and point-cloud exports take a capture only when all its
+cameras are equal and undistorted.
 
 `train --multiscale L` and `eval --multiscale L` are mip-NeRF's multi-scale protocol (Barron et al. 2021) for L = 2 .. 5: every view
 also exists at 1/2 .. 1/2^(L-1) of its size, as box averages of the white-blended pixels built once on the device (data.py).  Training
@@ -113,9 +131,9 @@ from typing import Callable, Optional
 import numpy as np
 import torch
 
-from .checkpoint import (RUN_STATE_KEY, RUN_STATE_VERSION, _load_pipeline, _Pipeline, checkpoint_path,  # noqa: F401 (re-exported)
-                         config_for_checkpoint, latest_checkpoint, load_checkpoint, make_model, make_run_state, open_checkpoint,
-                         resolve_checkpoint, save_checkpoint)
+from .checkpoint import (PRIMARY_SPACINGS, RAY_KEYS, RUN_STATE_KEY, RUN_STATE_VERSION, _load_pipeline, _Pipeline,  # noqa: F401 (re-exported)
+                         checkpoint_path, config_for_checkpoint, config_with_planes, latest_checkpoint, load_checkpoint, make_model,
+                         make_run_state, open_checkpoint, read_run_state, resolve_checkpoint, save_checkpoint, set_primary_sampler)
 
 METHOD_NAME = "reflect-sampling-nerf"
 MMA_CHOICES = ("f32", "bf16x6", "bf16")
@@ -123,6 +141,21 @@ EVAL_CHUNK = 1024  # reflect_sampling_nerf_config.py:41 eval_num_rays_per_chunk
 RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0, "multiscale": 1}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
 DEFAULT_NORMALS_SUFFIX = "_normal"  # multinerf / Shiny Blender: r_0.png beside r_0_normal.png
 NORMALS_SPACES = ("world", "camera")
+# A capture (a nerfstudio-format transforms.json): how it is read when nothing says otherwise (nerfstudio's NerfstudioDataParserConfig) ...
+CAPTURE_DATA_DEFAULTS = {"orientation": "up", "center": "poses", "auto_scale": True, "scale_factor": 1.0, "train_split_fraction": 0.9,
+                         "eval_mode": "fraction"}
+# ... and how its primary rays are cast: far 256 is the far of the model's own reflected rays, reciprocal spacing puts the samples
+# where an unbounded scene needs them.  Starting points that have NOT been measured on a scene.  Blender-format scenes keep the
+# model's own 2 .. 6 with uniform spacing.
+CAPTURE_RAY_DEFAULTS = {"near": 0.05, "far": 256.0, "primary_spacing": "reciprocal", "primary_tan": 1.0}
+
+
+class _NotGiven(float):
+    """The default of --scale-factor: 1.0 to everything that computes with it, and recognisable as "the user typed nothing", so that a
+    capture's scale_factor can come from the checkpoint's record."""
+
+
+SCALE_NOT_GIVEN = _NotGiven(1.0)
 LPIPS_NOTE = "fine_lpips not computed: LPIPS needs pretrained network weights that are not shipped with this package"
 
 
@@ -175,14 +208,33 @@ def resolve_occupancy_args(ap: argparse.ArgumentParser, args) -> Optional[dict]:
     return settings
 
 
+def _add_data_flags(p: argparse.ArgumentParser, train: bool) -> None:
+    """--data-format and how a capture is read.  Every default is None: "not given", so that a checkpoint's own record decides."""
+    from .data import CENTERS, DATA_FORMATS, EVAL_MODES, ORIENTATIONS
+
+    whose = "" if train else "; default: the checkpoint's"
+    p.add_argument("--data-format", choices=DATA_FORMATS, default="auto",
+                   help="auto: a directory with transforms.json is a nerfstudio-format capture, one with transforms_train.json a Blender-format scene")
+    p.add_argument("--orientation", choices=ORIENTATIONS, default=None,
+                   help=f"capture: rotate the poses so that the cameras' mean up axis becomes +z (default up{whose})")
+    p.add_argument("--center" if train else "--center-poses", dest="center_poses", choices=CENTERS, default=None,  # render has an orbit --center
+                   help=f"capture: move the mean camera position to the origin (default poses{whose})")
+    p.add_argument("--no-auto-scale", action="store_true", default=None,
+                   help="capture: do not scale the poses so that the largest translation component is --scale-factor")
+    p.add_argument("--train-split-fraction", type=float, default=None, metavar="F",
+                   help=f"capture: the share of the frames, evenly spaced, that is trained on; the others are held out (default 0.9{whose})")
+    p.add_argument("--eval-mode", choices=EVAL_MODES, default=None,
+                   help=f"capture: fraction, or all: train and evaluate on every frame (default fraction{whose})")
+
+
 def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     """run_defaults=False: --rays / --mma / --seed parse to None when absent, so that `main` can tell "not given" (a resumed run then
     takes the checkpoint's value) from a value typed by the user."""
     dflt = RUN_DEFAULTS if run_defaults else dict.fromkeys(RUN_DEFAULTS)
     ap = argparse.ArgumentParser(prog="python -m reflect_sampling_nerf_amd.trainer", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="command", required=True)
-    tr = sub.add_parser("train", help="train on the train split of a Blender-format scene")
-    tr.add_argument("--data", required=True, help="scene directory with transforms_train.json")
+    tr = sub.add_parser("train", help="train on the train split of a Blender-format scene or of a nerfstudio-format capture")
+    tr.add_argument("--data", required=True, help="scene directory with transforms_train.json (Blender format) or transforms.json (a capture)")
     tr.add_argument("--out", required=True, help="directory for step-*.ckpt")
     tr.add_argument("--steps", type=int, default=100000, help="training iterations (reference max_num_iterations)")
     tr.add_argument("--rays", type=int, default=dflt["rays"], help="rays per batch (default 1024)")
@@ -193,7 +245,9 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     tr.add_argument("--seed", type=int, default=dflt["seed"], help="model initialisation and ray sampling seed (default 0)")
     tr.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible run: weight gradients reduced in a fixed order (slower flush, one 68 MB workspace)")
-    tr.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    tr.add_argument("--scale-factor", type=float, default=SCALE_NOT_GIVEN,
+                    help="BlenderDataParser scale_factor (default 1); a capture: the dataparser's scale_factor, what the largest translation "
+                         "component becomes under auto-scaling (default 1)")
     tr.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global gradient norm to X before every optimiser step (default: no clipping)")
     tr.add_argument("--skip-nonfinite", action="store_true",
@@ -207,18 +261,31 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                          "been measured on this method (default: off)")
     tr.add_argument("--distortion-loss-coarse", type=float, default=None, metavar="Y",
                     help="the same term on the coarse level's weights, times Y (default: off)")
+    _add_data_flags(tr, train=True)
+    tr.add_argument("--near", type=float, default=None, metavar="N",
+                    help="near plane of the primary rays (default: 2 for a Blender-format scene, 0.05 for a capture -- a starting point, not measured on a scene)")
+    tr.add_argument("--far", type=float, default=None, metavar="F",
+                    help="far plane of the primary rays (default: 6 for a Blender-format scene, 256 for a capture -- the far of the model's "
+                         "own reflected rays; a starting point, not measured on a scene)")
+    tr.add_argument("--primary-spacing", choices=PRIMARY_SPACINGS, default=None,
+                    help="spacing of the primary rays' coarse samples: uniform in distance, or reciprocal, s(t) = t / (1/T + t) (default: uniform for "
+                         "a Blender-format scene, reciprocal for a capture -- a starting point, not measured on a scene)")
+    tr.add_argument("--primary-tan", type=float, default=None, metavar="T", help="T of the reciprocal spacing (default 1: a starting point, not measured)")
     tr.add_argument("--resume", default=None, metavar="PATH",
                     help="continue from this step-*.ckpt, or from the newest one in this run directory; --steps stays the total, and "
                          "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite / --multiscale / "
-                         "--distortion-loss / --distortion-loss-coarse come from the checkpoint unless given")
+                         "--distortion-loss / --distortion-loss-coarse, the ray flags (--near / --far / --primary-spacing / --primary-tan) "
+                         "and a capture's data flags come from the checkpoint unless given")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
-    ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json")
+    ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json (Blender format) or transforms.json (a capture)")
     ev.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
     ev.add_argument("--split", default="test")
     ev.add_argument("--max-images", type=int, default=None, help="score only the first N views")
     ev.add_argument("--out", default="metrics.json", help="output JSON")
     ev.add_argument("--save-images", default=None, help="directory for rendered ground truth | coarse | fine panels")
-    ev.add_argument("--scale-factor", type=float, default=1.0, help="BlenderDataParser scale_factor")
+    ev.add_argument("--scale-factor", type=float, default=SCALE_NOT_GIVEN,
+                    help="BlenderDataParser scale_factor (default 1); a capture: the dataparser's scale_factor (default: the checkpoint's)")
+    _add_data_flags(ev, train=False)
     ev.add_argument("--multiscale", type=int, default=1, metavar="L",
                     help="score every view at L scales, 1, 1/2, ... 1/2^(L-1), against box-averaged ground truth (1 to 5; default 1); "
                          "the results gain KEY_x1, KEY_x2, ... per scale and the plain KEY becomes the mean of those")
@@ -248,7 +315,9 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ex.add_argument("--split", default="train", help="tsdf: the split of --data (default train)")
     ex.add_argument("--poses", default=None, metavar="FILE.json",
                     help="tsdf: transforms-format file with frames[].transform_matrix, camera_angle_x and w / h")
-    ex.add_argument("--scale-factor", type=float, default=1.0, help="tsdf: scale of the translations read from --data / --poses")
+    ex.add_argument("--scale-factor", type=float, default=SCALE_NOT_GIVEN,
+                    help="tsdf: scale of the translations read from --data / --poses (default 1; a capture: the checkpoint's)")
+    _add_data_flags(ex, train=False)
     ex.add_argument("--max-views", type=int, default=None, metavar="N", help="tsdf: use N evenly spaced views of the file (default: all)")
     ex.add_argument("--downscale", type=int, default=1, metavar="K",
                     help="tsdf: render every depth map at 1/K of the cameras' size, intrinsics scaled alike (default 1)")
@@ -282,7 +351,9 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     pc.add_argument("--split", default="train", help="the split of --data (default train)")
     pc.add_argument("--poses", default=None, metavar="FILE.json",
                     help="transforms-format file with frames[].transform_matrix, camera_angle_x and w / h")
-    pc.add_argument("--scale-factor", type=float, default=1.0, help="scale of the translations read from --data / --poses")
+    pc.add_argument("--scale-factor", type=float, default=SCALE_NOT_GIVEN,
+                    help="scale of the translations read from --data / --poses (default 1; a capture: the checkpoint's)")
+    _add_data_flags(pc, train=False)
     pc.add_argument("--max-views", type=int, default=None, metavar="N", help="use N evenly spaced views of the file (default: all)")
     pc.add_argument("--downscale", type=int, default=1, metavar="K",
                     help="render every depth map at 1/K of the cameras' size, intrinsics scaled alike (default 1)")
@@ -307,7 +378,8 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     rn.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
     rn.add_argument("--out", required=True, help="output directory: panel/0000.png ... (or <channel>/0000.png ... with --tiles), frames.json")
     rn.add_argument("--path", choices=("orbit", "poses"), default=None,
-                    help="orbit around --center, or the poses of --poses / of --data's split (default: poses when --poses is given, else orbit)")
+                    help="orbit around --center, or the poses of --poses / of --data's split (default: poses when --poses is given or --data "
+                         "is a nerfstudio-format capture, whose frames are rendered through their own cameras; else orbit)")
     rn.add_argument("--frames", type=int, default=120, help="frames of an orbit (default 120)")
     rn.add_argument("--center", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"), help="orbit centre (default 0 0 0)")
     rn.add_argument("--radius", type=float, default=None,
@@ -318,7 +390,9 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     rn.add_argument("--poses", default=None, metavar="FILE.json", help="transforms-format file: frames[].transform_matrix, camera_angle_x, w / h")
     rn.add_argument("--data", default=None, metavar="DIR", help="scene directory: poses, field of view and image size of transforms_{split}.json")
     rn.add_argument("--split", default="test")
-    rn.add_argument("--scale-factor", type=float, default=1.0, help="scale of the translations read from --poses / --data")
+    rn.add_argument("--scale-factor", type=float, default=SCALE_NOT_GIVEN,
+                    help="scale of the translations read from --poses / --data (default 1; a capture: the checkpoint's)")
+    _add_data_flags(rn, train=False)
     rn.add_argument("--interpolate", type=int, default=0, metavar="K", help="poses inserted between consecutive ones of a poses path (default 0)")
     rn.add_argument("--width", type=int, default=None)
     rn.add_argument("--height", type=int, default=None)
@@ -334,6 +408,55 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     return ap
 
 
+def _scale_factor(args) -> float:
+    return float(args.scale_factor)
+
+
+CAPTURE_POSE_KEYS = ("orientation", "center", "auto_scale", "scale_factor")
+
+
+def capture_load_args(args, recorded: Optional[dict] = None):
+    """How a command line reads a capture -> (the keyword arguments of data.load_nerfstudio_split, the settings to record).  Each of
+    CAPTURE_DATA_DEFAULTS' keys: the flag if given, else the record of the checkpoint's run (`recorded`: its rsn_run entry or None),
+    else the default.  When the run recorded the transform and scale it applied and no flag that bears on the poses is given, exactly
+    those are applied again: the checkpoint is trained on, evaluated and rendered in the frame it was trained in."""
+    rec = (recorded or {}).get("data") or {}
+    given = {"orientation": args.orientation, "center": args.center_poses, "auto_scale": False if args.no_auto_scale else None,
+             "scale_factor": None if isinstance(args.scale_factor, _NotGiven) else float(args.scale_factor), "train_split_fraction": args.train_split_fraction, "eval_mode": args.eval_mode}
+    settings = {k: given[k] if given[k] is not None else rec.get(k, dflt) for k, dflt in CAPTURE_DATA_DEFAULTS.items()}
+    kwargs = dict(settings)
+    if rec.get("transform") is not None and all(given[k] is None for k in CAPTURE_POSE_KEYS):
+        kwargs["applied"] = (rec["transform"], rec["scale"])
+    return kwargs, settings
+
+
+def capture_flags_given(args):
+    """The capture-only flags a command line carries (for the error that says a Blender-format scene has no use for them)."""
+    names = (("--orientation", "orientation"), ("--center", "center_poses"), ("--no-auto-scale", "no_auto_scale"),
+             ("--train-split-fraction", "train_split_fraction"), ("--eval-mode", "eval_mode"))
+    return [flag for flag, attr in names if getattr(args, attr, None) is not None]
+
+
+def load_scene(ap: argparse.ArgumentParser, args, split: str, recorded: Optional[dict] = None, pixels: bool = True, **blender):
+    """The scene --data names -> (scene, the data settings to record: None for a Blender-format scene).  The format is detected
+    (data.detect_data_format) unless --data-format says it.  blender: further arguments of load_blender_split (normals)."""
+    from .data import detect_data_format, load_blender_split, load_nerfstudio_split
+
+    try:
+        fmt = detect_data_format(args.data, args.data_format)
+    except FileNotFoundError as e:
+        ap.error(f"{args.command}: {e}")
+    if fmt == "blender":
+        stray = capture_flags_given(args)
+        if stray:
+            ap.error(f"{args.command}: {' '.join(stray)} bear(s) on a nerfstudio-format capture; {args.data} is a Blender-format scene")
+        return load_blender_split(args.data, split, _scale_factor(args), **blender), None
+    if blender.get("normals"):
+        ap.error(f"{args.command}: --normals needs a Blender-format scene with normal maps; {args.data} is a nerfstudio-format capture")
+    kwargs, settings = capture_load_args(args, recorded)
+    return load_nerfstudio_split(args.data, split, pixels=pixels, **kwargs), {"format": "nerfstudio", **settings}
+
+
 def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
     """The cameras of a `render` command line: {"c2w" [F,3,4], "width", "height", "fx", "fy", "cx", "cy"}.  Host work only (JSON and
     one image header).  What the command line leaves open and no file settles is an argparse error that names the option."""
@@ -342,10 +465,22 @@ def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
     if args.poses is not None and args.data is not None:
         ap.error("render: give --poses or --data, not both")
     src = None
-    if args.poses is not None:
-        src = render.load_poses(args.poses, args.scale_factor)
+    capture = None
+    if args.data is not None:
+        from .data import detect_data_format
+
+        try:
+            if detect_data_format(args.data, args.data_format) == "nerfstudio":
+                capture = _capture_cameras(ap, args)
+        except FileNotFoundError as e:
+            ap.error(f"render: {e}")
+    if capture is not None:  # the cameras of the file's frames, in the frame the checkpoint was trained in
+        src = {"c2w": capture.c2w, "width": capture.width, "height": capture.height,
+               "camera_angle_x": 2.0 * math.atan(0.5 * capture.width / capture.fx), "file_paths": capture.file_paths}
+    elif args.poses is not None:
+        src = render.load_poses(args.poses, _scale_factor(args))
     elif args.data is not None:
-        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), args.scale_factor)
+        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), _scale_factor(args))
         if src["width"] is None or src["height"] is None:  # Blender-format files carry no size: the first image's header has it
             rel = src["file_paths"][0]
             path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
@@ -363,7 +498,7 @@ def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
             ap.error(f"render: {name} is required{where}: without --data / --poses all of --width --height --fov-x are")
     if width < 1 or height < 1 or not 0.0 < fov < math.pi:
         ap.error(f"render: --width {width} --height {height} --fov-x {math.degrees(fov):g}: need a positive size and 0 < fov < 180")
-    path = args.path or ("poses" if args.poses is not None else "orbit")
+    path = args.path or ("poses" if args.poses is not None or capture is not None else "orbit")
     if path == "poses":
         if src is None:
             ap.error("render: --path poses needs --poses or --data")
@@ -390,7 +525,25 @@ def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
     if args.chunk < 1:
         ap.error("render: --chunk must be >= 1")
     fx, fy, cx, cy = render.pinhole(width, height, fov)
-    return {"c2w": c2w, "width": int(width), "height": int(height), "fx": fx, "fy": fy, "cx": cx, "cy": cy}
+    cameras = {"c2w": c2w, "width": int(width), "height": int(height), "fx": fx, "fy": fy, "cx": cx, "cy": cy}
+    if capture is not None and path == "poses":  # the file's frames through their own cameras; an orbit: the first one's pinhole part
+        if args.interpolate or args.width is not None or args.height is not None or args.fov_x is not None:
+            ap.error("render: a capture's frames are rendered through their own cameras: --interpolate / --width / --height / --fov-x "
+                     "do not apply (an orbit, --path orbit, takes them)")
+        cameras.update(fx=capture.fx, fy=capture.fy, cx=capture.cx, cy=capture.cy, camera_table=capture.cameras)
+    elif capture is not None and args.width is None and args.height is None and args.fov_x is None:
+        cameras.update(fx=capture.fx, fy=capture.fy, cx=capture.cx, cy=capture.cy)  # an orbit: the first camera's pinhole part, no distortion
+    return cameras
+
+
+def _capture_cameras(ap: argparse.ArgumentParser, args):
+    """The cameras of --data's split of a capture, read as the checkpoint's run read it (headers only, no pixels)."""
+    try:
+        recorded = read_run_state(args.ckpt)
+    except (FileNotFoundError, NotADirectoryError) as e:
+        ap.error(f"{args.command}: --ckpt {args.ckpt}: {e}")
+    scene, _ = load_scene(ap, args, args.split, recorded, pixels=False)
+    return scene
 
 
 TSDF_ONLY_FLAGS = ("data", "poses", "max_views", "trunc", "min_weight", "ray_chunk")
@@ -470,10 +623,30 @@ def export_cameras_from_args(ap: argparse.ArgumentParser, args, command: str, ne
 
     if (args.poses is None) == (args.data is None):
         ap.error(f"{command}: {needs} cameras: give --data DIR or --poses FILE.json (one of them)")
+    capture = None
+    if args.data is not None:
+        from .data import detect_data_format, shared_pinhole
+
+        try:
+            if detect_data_format(args.data, args.data_format) == "nerfstudio":
+                capture = _capture_cameras(ap, args)
+                shared_pinhole(capture, command)  # one pinhole for all views is what the export kernels project through
+        except (FileNotFoundError, ValueError) as e:
+            ap.error(f"{command}: {e}")
+    if capture is not None:
+        if args.downscale < 1 or (args.max_views is not None and args.max_views < 1):
+            ap.error(f"{command}: --downscale and --max-views must be >= 1")
+        c2w = capture.c2w
+        if args.max_views is not None and args.max_views < len(c2w):
+            c2w = c2w[(np.arange(args.max_views, dtype=np.int64) * len(c2w)) // args.max_views]
+        width, height = max(1, capture.width // args.downscale), max(1, capture.height // args.downscale)
+        sx, sy = width / capture.width, height / capture.height
+        return {"c2w": np.ascontiguousarray(c2w), "width": int(width), "height": int(height), "fx": capture.fx * sx, "fy": capture.fy * sy,
+                "cx": capture.cx * sx, "cy": capture.cy * sy}
     if args.poses is not None:
-        src = render.load_poses(args.poses, args.scale_factor)
+        src = render.load_poses(args.poses, _scale_factor(args))
     else:
-        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), args.scale_factor)
+        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), _scale_factor(args))
         if src["width"] is None or src["height"] is None:  # Blender-format files carry no size: the first image's header has it
             rel = src["file_paths"][0] or ""
             path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
@@ -525,7 +698,8 @@ def resolve_pointcloud_args(ap: argparse.ArgumentParser, args) -> dict:
 
 # ------------------------------------------------------------------------------------------------ train
 def _resolve_run_settings(given: dict, recorded: Optional[dict]):
-    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale / distortion_loss / distortion_loss_coarse:
+    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale / distortion_loss / distortion_loss_coarse /
+    near / far / primary_spacing / primary_tan:
     the caller's value if given, else the checkpoint's, else the fresh-run default (deterministic: None = the model's own default; the
     two guard settings and the two distortion coefficients: None = off; multiscale: 1, which a checkpoint does not record).
     -> (settings, one line per given value that departs from the checkpoint's)."""
@@ -556,7 +730,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
           log: Optional[Callable[[str], None]] = print, deterministic: Optional[bool] = None, resume: Optional[str] = None,
           on_step: Optional[Callable[[int, torch.Tensor], None]] = None, max_grad_norm: Optional[float] = None,
           skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
-          distortion_loss_coarse: Optional[float] = None) -> str:
+          distortion_loss_coarse: Optional[float] = None, near: Optional[float] = None, far: Optional[float] = None,
+          primary_spacing: Optional[str] = None, primary_tan: Optional[float] = None, data_settings: Optional[dict] = None) -> str:
     """Train on `scene` (a data.BlenderScene) up to iteration `steps` (the total, nerfstudio's max_num_iterations); returns the path
     of the last checkpoint.  Checkpoints at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer
     does the same).  The loss is read back only every log_every steps: the iterations in between never wait for the GPU.
@@ -579,6 +754,14 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     config.loss_coefficients as "distortion_loss_fine" / "distortion_loss_coarse" (train_graph.DIST_COEF_KEYS), which switches the
     level's two launches on; mip-NeRF 360 uses 0.01, nerfacto 0.002, neither measured on this method.  The term reads no state beyond
     the step's own weights and bins, so the paragraph on the restored state below holds with it as it stands.
+
+    near / far: the collider planes of the primary rays; primary_spacing / primary_tan: their coarse sampler, "uniform" or "reciprocal"
+    with s(t) = t / (1/tan + t) (checkpoint.set_primary_sampler).  None: the checkpoint's when resuming; else, for a scene with a
+    camera table (a capture), CAPTURE_RAY_DEFAULTS -- 0.05, 256, reciprocal, 1: starting points, not measured on a scene -- and for
+    every other scene the model config's own (2, 6, uniform), with nothing recorded.  What is set is recorded in the checkpoint, and
+    every tool that opens it casts its rays the same way.  data_settings: how the scene was read (load_scene); recorded as "data"
+    together with the transform and scale the scene carries, which also go to out_dir/dataparser_transforms.json (nerfstudio's file).
+    None of this is state a step leaves behind: the paragraph on the restored state below holds as it stands.
 
     resume: a step-*.ckpt or a run directory (its latest).  A checkpoint of step k continues at k + 1 with the same checkpoint names
     and save_every rule; k >= steps - 1 is a ValueError.  Model (strict, as load_checkpoint) and FusedRAdam state come from the file.
@@ -603,11 +786,12 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         raise ValueError(f"steps must be >= 1, got {steps}")
     given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic, "max_grad_norm": max_grad_norm,
              "skip_nonfinite": skip_nonfinite, "multiscale": multiscale, "distortion_loss": distortion_loss,
-             "distortion_loss_coarse": distortion_loss_coarse}
+             "distortion_loss_coarse": distortion_loss_coarse, "near": near, "far": far, "primary_spacing": primary_spacing,
+             "primary_tan": primary_tan}
     first, model, ckpt, recorded = 0, None, None, None
     if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
         resume = resolve_checkpoint(resume)
-        model, ckpt = _load_pipeline(resume, model_config)
+        ckpt = torch.load(resume, map_location="cpu", weights_only=False)
         first = int(ckpt["step"]) + 1
         if first >= steps:
             raise ValueError(f"{resume} is at step {first - 1} and steps is {steps}: the run ends with step {steps - 1}, nothing is "
@@ -616,6 +800,15 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         if recorded is not None and recorded.get("version") != RUN_STATE_VERSION:
             raise ValueError(f"{resume}: {RUN_STATE_KEY} version {recorded.get('version')!r}, this trainer reads {RUN_STATE_VERSION}")
     cfg, notes = _resolve_run_settings(given, recorded)
+    rays_cast = {k: cfg[k] for k in RAY_KEYS}
+    if getattr(scene, "cameras", None) is not None:  # a capture: its own starting points where nothing else says
+        rays_cast = {k: CAPTURE_RAY_DEFAULTS[k] if v is None else v for k, v in rays_cast.items()}
+    if rays_cast["primary_spacing"] != "reciprocal":
+        if given["primary_tan"] is not None:
+            raise ValueError(f"primary_tan = {primary_tan} needs primary_spacing = 'reciprocal'")
+        rays_cast["primary_tan"] = None
+    if resume is not None:
+        model, _ = _load_pipeline(resume, model_config, rays=rays_cast, ckpt=ckpt)
     rays, mma, seed, deterministic = cfg["rays"], cfg["mma"], cfg["seed"], cfg["deterministic"]
     max_grad_norm, skip_nonfinite, multiscale = cfg["max_grad_norm"], bool(cfg["skip_nonfinite"]), int(cfg["multiscale"])
     distortion = {"distortion_loss_fine": cfg["distortion_loss"], "distortion_loss_coarse": cfg["distortion_loss_coarse"]}
@@ -627,7 +820,12 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     pyramid_layout(scene.num_images, scene.height, scene.width, multiscale)  # a size the levels do not divide ends here, on the host
     dev = torch.device(device)
     if model is None:
-        model = make_model(model_config, seed)
+        from .reflect_sampling_nerf_model import ReflectSamplingNeRFModelConfig
+
+        planes = config_with_planes(model_config if model_config is not None else ReflectSamplingNeRFModelConfig(), rays_cast["near"],
+                                    rays_cast["far"])
+        model = make_model(planes, seed)
+        set_primary_sampler(model, rays_cast["primary_spacing"], rays_cast["primary_tan"])
     model = model.to(dev).train()
     model.field.set_mma_mode(mma)
     if deterministic is not None:
@@ -650,6 +848,17 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     for key, coef in distortion.items():
         if coef is not None and float(coef) != 0.0:
             settings += f" {key} {float(coef):g}"
+    for k in RAY_KEYS:
+        if rays_cast[k] is not None:
+            settings += f" {k} {rays_cast[k]}"
+    data_record = None
+    if data_settings is not None:
+        data_record = dict(data_settings)
+        if getattr(scene, "dataparser_transform", None) is not None:
+            from .data import write_dataparser_transforms
+
+            data_record.update(transform=np.asarray(scene.dataparser_transform, dtype=np.float64).tolist(), scale=float(scene.dataparser_scale))
+            write_dataparser_transforms(os.path.join(out_dir, "dataparser_transforms.json"), scene.dataparser_transform, scene.dataparser_scale)
     if resume is None:
         if log is not None:
             log(f"train: {settings}")
@@ -685,7 +894,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         if (save_every and step > 0 and step % save_every == 0) or step == steps - 1:
             last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
                                    make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite, multiscale,
-                                                  distortion["distortion_loss_fine"], distortion["distortion_loss_coarse"]))
+                                                  distortion["distortion_loss_fine"], distortion["distortion_loss_coarse"],
+                                                  rays_and_data={**rays_cast, "data": data_record}))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -753,7 +963,8 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
              normals_space: str = "world") -> dict:
     """Score the checkpoint (a file, or the latest of a run directory) on every view of `scene` (a data.BlenderScene); -> ns-eval-
     shaped dict.  occupancy: None, or the settings of resolve_occupancy_args: the views are rendered with empty-space skipping and
-    the dict gains an "occupancy" entry.
+    the dict gains an "occupancy" entry.  A scene with a camera table (a capture) is rendered through its own cameras; the occupancy
+    box alone is laid out from the first camera's pinhole part.
 
     multiscale = L > 1: every view is rendered and scored at the L levels of RayDataManager's pyramid.  per_image then holds one entry
     per (view, level) with a "level" key, view after view; results gains k_x1, k_x2, k_x4, ... (+ _std) for every metric k, the mean
@@ -846,8 +1057,6 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
 
 # ------------------------------------------------------------------------------------------------ CLI
 def main(argv=None) -> int:
-    from .data import load_blender_split
-
     ap = build_parser()
     args = ap.parse_args(argv)
     given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
@@ -858,6 +1067,8 @@ def main(argv=None) -> int:
         decimate_args = resolve_decimate_args(ap, args)
     export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
     cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
+    if args.command == "train" and args.primary_tan is not None and not args.primary_tan > 0.0:
+        ap.error(f"train: --primary-tan {args.primary_tan}: need a value above 0")
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
         ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
     if args.command == "eval" and not args.normals:
@@ -870,8 +1081,10 @@ def main(argv=None) -> int:
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
     if args.command == "train":
-        scene = load_blender_split(args.data, "train", args.scale_factor)
-        print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}")
+        scene, data_settings = load_scene(ap, args, "train", read_run_state(args.resume) if args.resume is not None else None)
+        print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}"
+              + ("" if scene.cameras is None else f" (image 0; a capture with {len(np.unique(scene.cameras, axis=0))} distinct camera(s), "
+                                                  f"{int(np.any(scene.cameras[:, 4:] != 0.0, axis=1).sum())} image(s) with lens distortion)"))
         if args.multiscale > 1:  # a resumed run's own level count is checked by train()
             from .data import pyramid_layout
 
@@ -882,7 +1095,8 @@ def main(argv=None) -> int:
         train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
               log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume,
               max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None, multiscale=given.multiscale,
-              distortion_loss=args.distortion_loss, distortion_loss_coarse=args.distortion_loss_coarse)
+              distortion_loss=args.distortion_loss, distortion_loss_coarse=args.distortion_loss_coarse, near=args.near, far=args.far,
+              primary_spacing=args.primary_spacing, primary_tan=args.primary_tan, data_settings=data_settings)
         return 0
     if args.command == "export-mesh":
         from . import mesh
@@ -933,18 +1147,23 @@ def main(argv=None) -> int:
     if args.command == "render":
         from . import render
 
-        res = render.render_checkpoint(args.ckpt, args.out, *render.camera_args(cameras), channels=args.channels,
+        res = render.render_checkpoint(args.ckpt, args.out, *render.camera_args(cameras), camera_table=cameras.get("camera_table"),
+                                       channels=args.channels,
                                        depth_range=None if args.depth_range is None else tuple(args.depth_range), mma=args.mma,
                                        chunk=args.chunk, tiles=args.tiles, occupancy=occupancy)
         n, sec = len(res["frames"]), res["seconds"]
         print(f"{res['checkpoint']} (step {res['step']}): {n} frames {res['width']} x {res['height']} of {' '.join(res['channels'])}; "
               f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
         return 0
+    try:
+        recorded = read_run_state(args.ckpt)
+    except (FileNotFoundError, NotADirectoryError) as e:
+        ap.error(f"eval: --ckpt {args.ckpt}: {e}")
     if args.normals:
-        scene = load_blender_split(args.data, args.split, args.scale_factor, normals=True,
-                                   normals_suffix=DEFAULT_NORMALS_SUFFIX if args.normals_suffix is None else args.normals_suffix)
+        scene, _ = load_scene(ap, args, args.split, recorded, normals=True,
+                              normals_suffix=DEFAULT_NORMALS_SUFFIX if args.normals_suffix is None else args.normals_suffix)
     else:
-        scene = load_blender_split(args.data, args.split, args.scale_factor)
+        scene, _ = load_scene(ap, args, args.split, recorded)
     try:
         eval_level_sizes(scene, args.multiscale)
     except ValueError as e:
