@@ -66,7 +66,12 @@ typedef struct rsn_field_desc {
 } rsn_field_desc;
 
 /* How the field kernel multiplies fp32 operands on the matrix cores:
- *   RSN_MMA_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (157 TFLOP/s peak);
+ *   RSN_MMA_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (157 TFLOP/s peak); in the training forward (this mode and
+ *                   RSN_MMA_F32_FOLDED) the W x W GEMMs of the trunk run as nine exact bf16 piece products and the loop GEMMs of
+ *                   the analytic-normal sweep as the six largest of them (each dropped term <= 2^-25 relative); the backward
+ *                   sweep of this mode is on the fp32 MFMA loop, that of RSN_MMA_F32_FOLDED runs its W x W GEMMs as the nine
+ *                   products; the training graph reduces the weight gradients of such a field with RSN_MMA_BF16X6 (a call that
+ *                   names RSN_MMA_F32 runs the fp32 reduction);
  *   RSN_MMA_BF16X6  fp32 emulation: both operands split exactly into 3 bf16 (8+8+8 mantissa bits), the 6 leading
  *                   cross products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (dropped terms <= 2^-24
  *                   relative): fp32-equivalent results at 6/16 of the fp32-MFMA cost;
@@ -158,8 +163,8 @@ int rsn_train_saved_layout(const rsn_field_desc* desc, int32_t* enc_cols, int32_
  * training forward forms the same pieces in registers, and its buffer is byte for byte what it was.  All sizes are unchanged.
  * RSN_MMA_F32_FOLDED also fills the split-bf16 copies of the OTHER segments the analytic-normal sweep reads -- the transposed x
  * parts of trunk layers 1 .. L-2 and the transposed encoded-input parts of layer 0 and of the skip layer -- in their own regions,
- * as the split-bf16 modes write them: the folded training forward runs those GEMMs on all nine products of the three pieces of the
- * weights and of the activations.  The remaining split-bf16 regions of the two exact-fp32 modes stay unwritten. */
+ * as the split-bf16 modes write them: the folded training forward runs those GEMMs on six of the nine products of the three pieces of
+ * the weights and of the activations, the three smallest left out.  The remaining split-bf16 regions of the two exact-fp32 modes stay unwritten. */
 size_t rsn_packed_weights_bytes(const rsn_field_desc* desc);
 int rsn_pack_weights(const rsn_field_desc* desc, const rsn_field_params* params, float* packed,
                      size_t packed_bytes, void* stream);

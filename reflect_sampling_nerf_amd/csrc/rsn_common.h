@@ -70,10 +70,10 @@ struct RsnPackedLayout {
   size_t hT_x[RSN_MAX_TRUNK_LAYERS];  // split-bf16 copies of the transposed segments (training sweeps)
   size_t hT_enc0, hT_enc_skip, hT_bh, hT_mid_x, hT_rgb;
   // RSN_MMA_F32_FOLDED writes hT_x[1 .. L-2], hT_enc_skip and hT_enc0 too (and, of the other h* / hT_* regions, only hT_last
-  // below and h_x[1 .. L-1]): the loop GEMMs of the analytic-normal sweep of its training forward read them with all nine piece
-  // products (gemm_bf16_s16), and so do the W x W GEMMs of its backward sweep (rsn_field_bwd.hip, stage 4); the W x W GEMMs of its
-  // training forward's trunk read h_x[l] the same way.
-  // RSN_MMA_F32 writes none: its training kernel forms the same pieces from the w_x / wT_* segments in registers (gemm_f32_x9_s16)
+  // below and h_x[1 .. L-1]): the loop GEMMs of the analytic-normal sweep of its training forward read them with six of the nine
+  // piece products (gemm_bf16_s16<.., 6>); the W x W GEMMs of its backward sweep (rsn_field_bwd.hip, stage 4) read them with all
+  // nine (gemm_bf16_s16<.., 9>), as the W x W GEMMs of its training forward's trunk read h_x[l].
+  // RSN_MMA_F32 writes none: its training kernel forms the same pieces from the w_x / wT_* segments in registers (gemm_f32_s16)
   // RSN_MMA_F32_FOLDED with num_layers >= 2 only (0 = absent): V = (x part of layer L-1)^T diag(w_density), one rounding per
   // element (rsn_seed_product), as three bf16 pieces in the layout and K order of hT_x[L-1] -- the first GEMM of the
   // analytic-normal sweep reads it against the ReLU bits of layer L-1 (gemm_bf16_bits).  It takes the PLACE of hT_x[L-1]: the

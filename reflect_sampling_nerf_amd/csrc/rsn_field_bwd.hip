@@ -129,6 +129,7 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
     // exact fp32 products, another order of the fp32 accumulation.  Stages 1 to 3 left the slab in its standard layout, which is
     // what that loop reads.  A lane reads and writes float4 of other lanes' slots there (in order within the wave: no barrier), so
     // the saved rows leave for the rows of the two points it reads (rb16) and the mask words are those of the two it writes.
+    // (Nine here, where the analytic-normal sweep takes six: with six, d_input missed its rule -- DESIGN 4.3.)
     // The two encoded-input GEMMs stay on the fp32 loop (they read the same slab): on the nine-product loop d_input missed the rule
     // of tests/test_layer_gemms_gpu.py in two cases.
     f32x16 eacc[4];
@@ -149,8 +150,8 @@ __global__ __launch_bounds__(256) void rsn_field_bwd_kernel(const BwdJobs J) {
         __builtin_amdgcn_sched_barrier(0);
         f32x4 acc[NB][2][2];
         zero_acc16<NB>(acc);
-        gemm_bf16_s16<NB>(acc, pk + (l == P.num_layers - 1 ? (size_t)P.L.hT_last : P.L.hT_x[l]), X, NB, ln,
-                          rb16(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));  // reads (and keeps) dy[l]
+        gemm_bf16_s16<NB, 9>(acc, pk + (l == P.num_layers - 1 ? (size_t)P.L.hT_last : P.L.hT_x[l]), X, NB, ln,
+                             rb16(a.gout.dy, (long long)l * a.act_stride + p0 * W, W));  // reads (and keeps) dy[l]
         store_masked_bits16<NB>(acc, X, mb, ln);
       } else {
         const ReluBits<NB> mb = load_relu_bits<NB>(bits_at(l - 1));

@@ -18,7 +18,7 @@
 // (saved.bott is neither written nor read).  Heads, sigma and normals keep their bits: same K order, same bias start.
 // MMA: the rsn_mma_mode the kernel serves (MmaTraits, rsn_gemm_loops.h); MODE = the mode whose K loops it runs.
 // A loop GEMM of the analytic-normal sweep in the mode's own loop, and, for the exact-fp32 training instantiations, as the
-// nine-product loop on the 16x16x32 bf16 MFMAs: PACKED (FOLD) over the pre-split hT_* segment, else with the same pieces formed in
+// piece-product loop on the 16x16x32 bf16 MFMAs: PACKED (FOLD) over the pre-split hT_* segment, else with the same pieces formed in
 // registers from the fp32 wT_* segment (the RSN_MMA_F32 buffer has no split copies): the same bits either way.
 template <int MODE, int NBO>
 __device__ __forceinline__ void sweep_gemm(f32x16 (&acc)[NBO], const float* __restrict__ w32, const float* __restrict__ w16,
@@ -27,12 +27,13 @@ __device__ __forceinline__ void sweep_gemm(f32x16 (&acc)[NBO], const float* __re
 }
 // The W x W GEMMs of the training forward's trunk (layers l >= 1, the x part) go the same way, over h_x[l] / w_x[l], with `save`:
 // the rows of act[l-1] leave from the K loop that reads them.
-template <bool PACKED, int N_IT, int NBO, class SV = const float*>
+// NP: the piece products per accumulator and K step (rsn_gemm_loops.h): 9 in the trunk, 6 in the analytic-normal sweep.
+template <bool PACKED, int N_IT, int NBO, int NP, class SV = const float*>
 __device__ __forceinline__ void sweep_gemm(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32, const float* __restrict__ w16,
                                            const float4* xl, int lane, SV save = nullptr) {
   static_assert(N_IT % 4 == 0, "K = 8 N_IT is a multiple of 32 at every width (the units are padded to 32): no tail path");
-  if constexpr (PACKED) gemm_bf16_s16<NBO>(acc, w16, xl, N_IT / 4, lane, save);
-  else gemm_f32_x9_s16<NBO>(acc, w32, xl, N_IT / 4, lane, save);
+  if constexpr (PACKED) gemm_bf16_s16<NBO, NP>(acc, w16, xl, N_IT / 4, lane, save);
+  else gemm_f32_s16<NBO, NP>(acc, w32, xl, N_IT / 4, lane, save);
 }
 
 template <int NB, bool TRAIN, int MMA>
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         init_acc16<NB>(a16, pk + P.L.b[1], ln);
 #pragma unroll 1
         for (int l = 1; l < P.num_layers; ++l) {
-          sweep_gemm<FOLD, NB * 4, NB>(a16, pk + P.L.w_x[l], pk + P.L.h_x[l], X, ln,
+          sweep_gemm<FOLD, NB * 4, NB, 9>(a16, pk + P.L.w_x[l], pk + P.L.h_x[l], X, ln,
                                        rb_loop16(a.saved.act, (l - 1) * a.act_stride + p0 * W, W));
           const bool last = l + 1 == P.num_layers;
           if (l == P.skip_layer) {
@@ -357,11 +358,13 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
     // peeled iteration l = L-1.  FOLD reads the pieces packed (hT_seed, gemm_bf16_bits); RSN_MMA_F32, whose packed buffer has no
     // such segment, forms them in registers (gemm_f32_bits): the same bits.  The skip layer is never the last one
     // (rsn_compute_layout), so that iteration has no encoded-input GEMM.
-    // The GEMMs behind it (W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs) run on the bf16 MFMAs too, as all NINE products of
-    // three bf16 pieces a side (sweep_gemm): no term of the fp32 product is dropped, only the order of the fp32 accumulation differs.
+    // The GEMMs behind it (W_l^T for l = L-2 .. 1 and the two encoded-input GEMMs) run on the bf16 MFMAs too, as SIX products of
+    // three bf16 pieces a side (sweep_gemm, SWEEP_NP): the three smallest of the nine, at most 2^-25 of the product each, are left
+    // out -- below the rounding of the fp32 accumulation they would join, and no sign is decided from these sums (rsn_gemm_loops.h).
     // They run on the 16x16x32 shape (rsn_gemm_loops.h): a lane then reads and writes float4 of OTHER lanes' slots of the wave's X
     // slab, which needs no barrier -- a wave's LDS instructions complete in order, and no other wave touches the slab.
     constexpr bool SEED_BITS = TRAIN && M::F32;
+    [[maybe_unused]] constexpr int SWEEP_NP = 6;  // piece products per accumulator and K step of the sweep's loop GEMMs, folded and unfolded alike
     if (TRAIN && a.saved.normals && a.saved.relu_bits) {
       const float* __restrict__ wd = pk + P.L.v_density;
       const bool peel = SEED_BITS && P.num_layers >= 2;  // workgroup-uniform
@@ -402,15 +405,15 @@ __global__ __launch_bounds__(256) void rsn_field_kernel(const FieldJobs J) {
         zero_acc16<4>(eacc);
 #pragma unroll 1
         for (int l = P.num_layers - (peel ? 2 : 1); l >= 1; --l) {
-          if (l == P.skip_layer) sweep_gemm<FOLD, NB * 4, 4>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, ln);
+          if (l == P.skip_layer) sweep_gemm<FOLD, NB * 4, 4, SWEEP_NP>(eacc, pk + P.L.wT_enc_skip, pk + P.L.hT_enc_skip, X, ln);
           const ReluBits<NB> mb[2] = {load_relu_bits<NB>(bits16_at(l - 1, 0)), load_relu_bits<NB>(bits16_at(l - 1, 1))};
           __builtin_amdgcn_sched_barrier(0);
           f32x4 acc[NB][2][2];
           zero_acc16<NB>(acc);
-          sweep_gemm<FOLD, NB * 4, NB>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, ln);
+          sweep_gemm<FOLD, NB * 4, NB, SWEEP_NP>(acc, pk + P.L.wT_x[l], pk + P.L.hT_x[l], X, ln);
           store_masked_bits16<NB>(acc, X, mb, ln);
         }
-        sweep_gemm<FOLD, NB * 4, 4>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, ln);
+        sweep_gemm<FOLD, NB * 4, 4, SWEEP_NP>(eacc, pk + P.L.wT_enc0, pk + P.L.hT_enc0, X, ln);
         store_act16<4>(eacc, X, ln);  // gradient w.r.t. the encoded inputs, slot order (its 0..12), where store_act puts it
       } else {
         f32x16 eacc[4];

@@ -533,10 +533,18 @@ __device__ __forceinline__ void gemm_f32_bits(f32x16 (&acc)[NBO], const float* _
 }
 
 // ------------------------------------------------------------------------------------------------
-// The nine-product loops on v_mfma_f32_16x16x32_bf16 (exact-fp32 training, the analytic-normal sweep): the same MFMA cycles (36 of
-// 16 per block and K = 32 against 18 of 32) and the same arithmetic per accumulator (nine products, smallest terms first), on the
-// shape at which the chip holds the higher clock under load.  The wave's output tile stays 32 points x 32 NBO rows, as
-// NBO x 2 row halves x 2 point halves results of 16 x 16.  Lane L = (i = L & 15, g = L >> 4) owns K group g of a K = 32 step,
+// The piece-product loops on v_mfma_f32_16x16x32_bf16 (exact-fp32 training: the forward trunk, the analytic-normal sweep, the folded
+// backward sweep): the MFMA cycles of mma16 (4 NP of 16 per block and K = 32 against 2 NP of 32) and its arithmetic per accumulator
+// (smallest terms first), on the shape at which the chip holds the higher clock under load.
+// NP, the products per accumulator and K step, is the caller's choice, stated at every call:
+//   9  every product of three pieces a side: no term of the fp32 product is dropped (the forward trunk, whose values and ReLU bits
+//      everything else reads; the backward sweep's dX, rsn_field_bwd.hip);
+//   6  without the three smallest, w_lo b_lo, w_lo b_mid, w_mid b_lo.  Nearest-rounding pieces are bounded by |mid| <= 2^-8 |x| and
+//      |lo| <= 2^-17 |x|, so each of the two larger dropped terms is at most 2^-25 |w b| and the three sum to at most
+//      (2 * 2^-25 + 2^-34) |w b|, with both operands at their worst: the rounding of ONE fp32 product, in a sum that is rounded to
+//      fp32 at every MFMA (the analytic-normal sweep, from whose sums no sign decision is taken).  The six are products 3 .. 8 of
+//      the nine, in the same order.
+// The wave's output tile stays 32 points x 32 NBO rows, as NBO x 2 row halves x 2 point halves results of 16 x 16.  Lane L = (i = L & 15, g = L >> 4) owns K group g of a K = 32 step,
 // which is K group g & 1 of K = 16 step 2 s + (g >> 1): it reads the 16-byte granule of OLD lane (i + 16 rh) + 32 (g & 1) of the
 // very records the 32x32x16 loop reads (no other packing), and the two float4 of old lane (i + 16 ph) + 32 (g & 1) of the X slab,
 // so A and B meet on the same K set at every MFMA position and the K permutation of the packing carries over.
@@ -557,20 +565,21 @@ __device__ __forceinline__ Lane16 lane16(int lane) {
   return g;
 }
 
-// the nine products of NQ blocks against the two point halves, in mma16<.., true>'s order per accumulator; the four results of a
-// block take each product in turn (four independent accumulators between two MFMAs of one chain)
+// the last NP of the nine products of NQ blocks against the two point halves, in mma16<.., true>'s order per accumulator; the four
+// results of a block take each product in turn (four independent accumulators between two MFMAs of one chain)
 __device__ __forceinline__ bf16x8 piece(const BSplit& b, int k) { return k == 0 ? b.s1 : (k == 1 ? b.s2 : b.s3); }  // k: a constant
-constexpr int x9_wp(int p) { constexpr int t[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0}; return t[p]; }  // product p: the weight's piece
-constexpr int x9_bp(int p) { constexpr int t[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0}; return t[p]; }  //            the activation's piece
-template <int NBO, int NQ>
+constexpr int prod_wp(int p) { constexpr int t[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0}; return t[p]; }  // product p: the weight's piece
+constexpr int prod_bp(int p) { constexpr int t[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0}; return t[p]; }  //            the activation's piece
+template <int NBO, int NQ, int NP>
 __device__ __forceinline__ void mma16s(f32x4 (&acc)[NBO][2][2], const bf16x8 (&w)[NQ][2][3], const BSplit (&b)[2], int nb0) {
+  static_assert(NP == 9 || NP == 6, "all nine piece products, or the six without w_lo b_lo, w_lo b_mid, w_mid b_lo");
 #pragma unroll
   for (int t = 0; t < NQ; ++t)
 #pragma unroll
-    for (int p = 0; p < 9; ++p)
+    for (int p = 9 - NP; p < 9; ++p)
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        acc[nb0 + t][q >> 1][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[t][q >> 1][x9_wp(p)], piece(b[q & 1], x9_bp(p)),
+        acc[nb0 + t][q >> 1][q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[t][q >> 1][prod_wp(p)], piece(b[q & 1], prod_bp(p)),
                                                                               acc[nb0 + t][q >> 1][q & 1], 0, 0, 0);
 }
 
@@ -608,7 +617,7 @@ __device__ __forceinline__ void sv_put16(const RowBuf& b, int it, int ph, bool l
 // `save` (optional: the backward sweep, the training forward's trunk): every float4 of the slab this GEMM reads leaves once for its saved row -- step 0's ahead of
 // the loop, step s + 1's from the registers that are split under the chunks 0 and 1 of step s (two stores a chunk, behind that
 // chunk's fragment loads in the vmcnt order).
-template <int NBO, class SV = const float*>
+template <int NBO, int NP, class SV = const float*>
 __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ wseg, const float4* xl, int n_k32,
                                               int lane, SV save = nullptr) {
   static_assert(NBO % 2 == 0, "an even number of fragment buffers' worth of blocks");
@@ -651,9 +660,9 @@ __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const flo
         x0lo = xb[4 * s2 * 64]; x0hi = xb[(4 * s2 + 1) * 64];
         x1lo = xb[4 * s2 * 64 + 16]; x1hi = xb[(4 * s2 + 1) * 64 + 16];
       }
-      if (c & 1) mma16s<NBO, NQ>(acc, wb, bc, c * NQ); else mma16s<NBO, NQ>(acc, wa, bc, c * NQ);
+      if (c & 1) mma16s<NBO, NQ, NP>(acc, wb, bc, c * NQ); else mma16s<NBO, NQ, NP>(acc, wa, bc, c * NQ);
 #pragma unroll
-      for (int m = 0; m < NQ * 36; ++m) {
+      for (int m = 0; m < NQ * 4 * NP; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
         if (c < 2) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // the next step's pieces: an MFMA leaves 8 of its 16 cycles
         if (c < 2 && sv_on(save) && (m == 8 || m == 20)) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // 1 row store
@@ -667,11 +676,11 @@ __device__ __forceinline__ void gemm_bf16_s16(f32x4 (&acc)[NBO][2][2], const flo
 }
 
 // The same loop without packed pieces (RSN_MMA_F32): the weight pieces formed in registers by split8<3> from the fp32 fragments of
-// a wT_* segment ([it][NBO][lane][4]; the lane reads K-iterations 4 s + 2 kh, + 1 of old lane ol + 16 rh), the nine products in the
-// same order per accumulator: bit for bit the packed form.  A software pipeline over the 2 NBO row halves of a K step: the pieces
-// of row half u + 1 are formed under the eighteen MFMAs of row half u (the last two also split the next step's activations).  A
-// 16-cycle MFMA leaves the VALU 8 cycles where a 32-cycle one left 24, so about 50 VALU instructions per 18 MFMAs make this loop
-// VALU-bound: it takes 1.01-1.03 of the time of its 32x32x16 form (tools/probes/sweep_x9_probe.hip, forms (e) and (c)) and the
+// a wT_* segment ([it][NBO][lane][4]; the lane reads K-iterations 4 s + 2 kh, + 1 of old lane ol + 16 rh), the same NP products in
+// the same order per accumulator: bit for bit the packed form.  A software pipeline over the 2 NBO row halves of a K step: the pieces
+// of row half u + 1 are formed under the 2 NP MFMAs of row half u (the last two also split the next step's activations).  A
+// 16-cycle MFMA leaves the VALU 8 cycles where a 32-cycle one left 24, so about 50 VALU instructions per 18 MFMAs (12 at NP = 6,
+// which therefore gains nothing here) make this loop VALU-bound: it takes 1.01-1.03 of the time of its 32x32x16 form (tools/probes/sweep_x9_probe.hip, forms (e) and (c)) and the
 // unfolded primary forward launch 3 % more (profiles/normals_shape16.json); it is on this shape for the bits it shares with the
 // packed loop.  A fragment buffer (a quarter of the blocks) is dead once its last row half is split and is reloaded, two
 // chunks ahead, under the MFMAs of that row half.
@@ -690,11 +699,18 @@ __device__ __forceinline__ void load_w32s(float4 (&f)[NQ][2][2], const WBuf& b, 
 
 // `save` (optional): as in gemm_bf16_s16 -- step 0's float4 ahead of the loop, step s + 1's from the registers that the last two row
 // halves of step s split.
-template <int NBO, class SV = const float*>
-__device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32seg, const float4* xl,
+template <int NBO, int NP, class SV = const float*>
+__device__ __forceinline__ void gemm_f32_s16(f32x4 (&acc)[NBO][2][2], const float* __restrict__ w32seg, const float4* xl,
                                                 int n_k32, int lane, SV save = nullptr) {
   static_assert(NBO % 2 == 0, "an even number of fragment buffers' worth of blocks");
+  static_assert(NP == 9 || NP == 6, "all nine piece products, or the six without w_lo b_lo, w_lo b_mid, w_mid b_lo");
   constexpr int NQ = NBO >= 4 ? NBO / 4 : 1, NC = NBO / NQ, UQ = 2 * NQ, NU = 2 * NBO;  // row halves per chunk and per K step
+  // per MFMA of a row half: the VALU instructions scheduled behind it, and the two MFMAs that a row store follows.  At nine
+  // products the requests place 3 x 18 = 54 / 6 x 18 = 108 VALU instructions a row half, all of the split's.  At six they place
+  // 2 x 12 = 24 / 4 x 12 = 48, fewer than half; the rest go where hipcc puts them.  Larger groups at six (4 / 8 and up) crash hipcc
+  // (ROCm 7.2, clang 22: a segmentation fault in its AGPR-copy-MFMA rewrite pass on rsn_field_kernel<8, true, 0>).  The loop is
+  // VALU-bound either way.
+  constexpr int VA = NP == 9 ? 3 : 2, VB = NP == 9 ? 6 : 4, ST0 = NP == 9 ? 5 : 3, ST1 = NP == 9 ? 12 : 8;
   const Lane16 g = lane16(lane);
   WBuf wp = wbuf_make(w32seg, lane);
   wp.voff = (unsigned)g.ol * 16u + (unsigned)g.kh * (NBO * 2048u);
@@ -741,18 +757,18 @@ __device__ __forceinline__ void gemm_f32_x9_s16(f32x4 (&acc)[NBO][2][2], const f
         x1lo = xb[4 * s2 * 64 + 16]; x1hi = xb[(4 * s2 + 1) * 64 + 16];
       }
 #pragma unroll
-      for (int p = 0; p < 9; ++p)
+      for (int p = 9 - NP; p < 9; ++p)
 #pragma unroll
         for (int ph = 0; ph < 2; ++ph)
-          acc[u >> 1][u & 1][ph] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(piece(w, x9_wp(p)), piece(bc[ph], x9_bp(p)),
+          acc[u >> 1][u & 1][ph] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(piece(w, prod_wp(p)), piece(bc[ph], prod_bp(p)),
                                                                            acc[u >> 1][u & 1][ph], 0, 0, 0);
 #pragma unroll
-      for (int m = 0; m < 18; ++m) {
+      for (int m = 0; m < 2 * NP; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
         if (reload && m < NQ * 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
-        if (u >= NU - 2) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // the next row half's pieces + the next step's activations
-        else __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // the next row half's pieces
-        if (u >= NU - 2 && sv_on(save) && (m == 5 || m == 12)) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // 1 row store
+        if (u >= NU - 2) __builtin_amdgcn_sched_group_barrier(0x002, VB, 0);  // the next row half's pieces + the next step's activations
+        else __builtin_amdgcn_sched_group_barrier(0x002, VA, 0);  // the next row half's pieces
+        if (u >= NU - 2 && sv_on(save) && (m == ST0 || m == ST1)) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // 1 row store
       }
       if (u == NU - 1) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // the LDS reads of the activations
       __builtin_amdgcn_sched_barrier(0);

@@ -7,7 +7,8 @@ forward  = samplers (stratified jitter) -> fused field kernels in training mode 
 backward = the same pipeline reversed through librsn_hip.so: reflect combine / composite backward (suffix scan),
            rsn_field_backward_* (transposed-weight MFMA sweep producing every layer's pre-activation gradient),
            then rsn_weight_grad: dW = dY^T X and db for every linear layer (output-stationary MFMA reduction over
-           all samples), accumulated straight into nn.Linear-layout gradient tensors.
+           all samples), accumulated straight into nn.Linear-layout gradient tensors.  A field in the exact-fp32 mode takes the
+           split-bf16 reduction (RSN_MMA_BF16X6: six piece products, fp32 accumulation, the fp32 kernel's bound against fp64).
 
 Which outputs carry gradient, and the detach points, follow the reference exactly: mid_rgb_*, mid_reflect_*
 (through colour and -- for the primary levels -- through the weights), pred_normals_*, n_dot_d_*, roughness;
@@ -263,8 +264,11 @@ def _weight_grads(field, levels, acc: _GradAcc, ordered: bool = False, fold: boo
     fold: the levels come from the folded kernels (no bottleneck rows).  The bottleneck leaves the W x W launch; d a_mid is reduced
     against the trunk output into a zeroed scratch C (and its column sums s), and rsn_unfold_bottleneck_grads adds the gradients of
     field_output_bottleneck and of mlp_mid's x part that follow from C and s (linear in both: one call per _weight_grads call)."""
-    # passed to every call below; bf16x6: split operands (fp32-equivalent); bf16: rounded operands (reduced precision)
-    how = {"mode": int(field.mma_mode), "ordered": bool(ordered)}
+    # passed to every call below; bf16x6: split operands (fp32-equivalent); bf16: rounded operands (reduced precision).  The
+    # exact-fp32 field, folded or not, reduces on the split-bf16 kernel too (six piece products with fp32 accumulation, held to
+    # the fp32 kernel's bound against fp64): the fp32 MFMA reduction stays what a call that names RSN_MMA_F32 runs.
+    mode = int(field.mma_mode)
+    how = {"mode": _abi.RSN_MMA_BF16X6 if mode == _abi.RSN_MMA_F32 else mode, "ordered": bool(ordered)}
     # W: the PARAMETER width (n_out / k_in of the reductions); the operand rows are [N, field.width] (leading dimension = the
     # kernels' padded width, taken from the tensors' strides)
     L, W = field.mlp_base.num_layers, field.param_width

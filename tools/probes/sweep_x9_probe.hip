@@ -8,8 +8,12 @@
 //       form until the sweep took shape (e): the pieces of block b + 1 are formed under the nine MFMAs of block b);
 //   (d) nine products, packed, on v_mfma_f32_16x16x32_bf16: gemm_bf16_s16<8> over the same hT_x segment bytes (another per-lane
 //       offset), 4,608 MFMAs of 16 cycles into the same 32-point x 256-row tile per wave: the same MFMA cycles, another shape;
-//   (e) (d) with the weight pieces formed in registers from the fp32 segment (gemm_f32_x9_s16, the RSN_MMA_F32 kernel's form);
+//   (e) (d) with the weight pieces formed in registers from the fp32 segment (gemm_f32_s16, the RSN_MMA_F32 kernel's form);
 // and, for scale, the six-product loop of the bf16x6 mode (gemm_bf16<8, 3>).
+// The derivative GEMMs (the analytic-normal sweep, the backward sweep's dX) run (d) and (e) with SIX of the nine products, the three
+// smallest left out (gemm_bf16_s16<8, 6>, gemm_f32_s16<8, 6>): forms (d6), (e6) and (d6) with the row stores in its K loop, checked on
+// the integer operands like the others (every dropped product has a zero factor there) and timed against (d) and (d) with its stores:
+// go per site at <= 0.85 of the nine-product form's time.
 // The backward sweep runs the same GEMMs and keeps, per GEMM, the 32 KiB of layer-gradient rows it reads in a row-major
 // [points, 256] buffer.  Three more forms for it: (a) with the stores in its K loop (gemm_run2's saver, what that sweep ran), (d)
 // with them in its K loop (gemm_bf16_s16's saver, checked first on the integer operands: result, rows and rows past the valid
@@ -17,7 +21,7 @@
 // The training forward's trunk runs W_l (256 x 256) the same way behind a bias start and in front of a ReLU epilogue: three more forms
 // (kf / fwd_tile below: the fp32 loop with store_act_init, the packed and the in-register 16-shape with store_act16_relu_init),
 // checked first on integer operands (slab, mask words, restarted accumulators, kept rows, stray stores), then timed tile feeding tile.
-// Before anything is timed, (b) and (d) run one tile each on integer operands whose every sum is exact in fp32 (17-bit weights
+// Before anything is timed, (b) and (d) run one tile each on integer operands whose every sum is exact in fp32 (19-bit weights
 // against 0 / +-1 activations, then the reverse) and their X slabs are compared with each other and with the host's integer sums.
 // The kernel's real grid: one workgroup of four waves per CU on every CU at once (clock and power effects show), each wave on its
 // own 32-point tile and LDS slab, the workgroup's LDS sized so that one workgroup fills the CU; every wave runs only this GEMM for
@@ -136,7 +140,9 @@ __device__ __forceinline__ void store_rows16(const f32x4 (&acc)[NBO][2][2], cons
 // FORM 0: (a) fp32; 1: (b) nine products, packed pieces; 2: (c) nine products, pieces formed in registers; 3: calibration, 1,024
 // fp32 MFMAs from registers; 4: six products (bf16x6); 5: (d) nine products, packed pieces, 16x16x32; 6: (e) the same, pieces formed in registers;
 // 7: (d) keeping the rows it reads, stores in the K loop (gemm_bf16_s16's saver); 8: (a) keeping them, stores in the K loop (gemm_run2's
-// saver: what the backward sweep runs); 9: (d) with the result rows stored from the epilogue (store_rows16).
+// saver: what the backward sweep ran); 9: (d) with the result rows stored from the epilogue (store_rows16);
+// 10: (d) with six products (the analytic-normal sweep's form); 11: 10 keeping the rows it reads, stores in the K loop (the backward
+// sweep's form); 12: (e) with six products.
 // OWN: every wave streams its own copy of the segment (no L1 sharing).
 template <int FORM, bool OWN>
 __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0,
@@ -153,16 +159,19 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
     asm volatile("" : "+v"(ln));
     // this tile's 32 rows of the row-major [points, 256] buffer (wave-uniform base)
     const long long row0 = ((long long)(blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wid)) * ROW_SLOTS + (t % ROW_SLOTS)) * 32 * 256;
-    if constexpr (FORM == 5 || FORM == 6 || FORM == 7 || FORM == 9) {
+    if constexpr (FORM == 5 || FORM == 6 || FORM == 7 || FORM == 9 || FORM == 10 || FORM == 11 || FORM == 12) {
       f32x4 a16[8][2][2];
       zero_acc16<8>(a16);
-      if (FORM == 5) gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
-      else if (FORM == 7) gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 15, (ln >> 4) & 1));
+      if (FORM == 5) gemm_bf16_s16<8, 9>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
+      else if (FORM == 7) gemm_bf16_s16<8, 9>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 15, (ln >> 4) & 1));
       else if (FORM == 9) {
-        gemm_bf16_s16<8>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
+        gemm_bf16_s16<8, 9>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
         store_rows16<8>(a16, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 15, (ln >> 4) & 1), ln);
       }
-      else gemm_f32_x9_s16<8>(a16, w32 + (OWN ? wid * SEG_F32 : 0), X, 8, ln);
+      else if (FORM == 10) gemm_bf16_s16<8, 6>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln);
+      else if (FORM == 11) gemm_bf16_s16<8, 6>(a16, w16 + (OWN ? wid * SEG_B16 : 0), X, 8, ln, rowbuf<false>(rowsbuf, row0, 32, 256, ln & 15, (ln >> 4) & 1));
+      else if (FORM == 12) gemm_f32_s16<8, 6>(a16, w32 + (OWN ? wid * SEG_F32 : 0), X, 8, ln);
+      else gemm_f32_s16<8, 9>(a16, w32 + (OWN ? wid * SEG_F32 : 0), X, 8, ln);
 #pragma unroll
       for (int nb = 0; nb < 8; ++nb) s += (a16[nb][0][0][0] + a16[nb][0][1][1]) + (a16[nb][1][0][2] + a16[nb][1][1][3]);
       X[(t & 31) * 64].x = 0.5f + 1e-9f * s;
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(256) void k(const float* __restrict__ w32, const fl
 // activations stay of order one):
 //   FORM 0: the fp32 loop as the kernel ran it (gemm_run2 with its saver, first fragment fetched ahead of store_act_init);
 //   FORM 1: gemm_bf16_s16 with its saver + store_act16_relu_init (the RSN_MMA_F32_FOLDED kernel's form);
-//   FORM 2: gemm_f32_x9_s16 with its saver + store_act16_relu_init (the RSN_MMA_F32 kernel's form).
+//   FORM 2: gemm_f32_s16 with its saver + store_act16_relu_init (the RSN_MMA_F32 kernel's form).
 template <int FORM>
 __device__ __forceinline__ void fwd_tile(f32x16 (&acc)[8], f32x4 (&a16)[8][2][2], float4 (&wa)[8], const float* __restrict__ w32,
                                          const float* __restrict__ w16, float4* X, const float* __restrict__ bias, float* rows,
@@ -217,7 +226,7 @@ __device__ __forceinline__ void fwd_tile(f32x16 (&acc)[8], f32x4 (&a16)[8][2][2]
     store_act_init<8, true, false>(acc, X, (float*)nullptr, h, bias, m < valid ? bits32 + (m * 2 + h) * 4 : nullptr);
   } else {
     const RowBuf rb = rowbuf<false>(rows, row0, valid, 256, ln & 15, (ln >> 4) & 1);
-    if constexpr (FORM == 1) gemm_bf16_s16<8>(a16, w16, X, 8, ln, rb); else gemm_f32_x9_s16<8>(a16, w32, X, 8, ln, rb);
+    if constexpr (FORM == 1) gemm_bf16_s16<8, 9>(a16, w16, X, 8, ln, rb); else gemm_f32_s16<8, 9>(a16, w32, X, 8, ln, rb);
     const int m = (ln & 15) + 16 * (ln >> 5), h = (ln >> 4) & 1;
     store_act16_relu_init<8>(a16, X, ln, bias, m < valid ? bits32 + (m * 2 + h) * 4 : nullptr);
   }
@@ -268,7 +277,7 @@ __global__ __launch_bounds__(64) void chkf(const float* __restrict__ w32, const 
   for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out2 + ((size_t)it * 64 + lane) * 4) = X[it * 64];
 }
 
-// one wave, one tile: the GEMM of form (b), (d) or (e), its result written to the X slab by the form's own epilogue and copied out
+// one wave, one tile: the GEMM of form (b), (d), (e), (d6) = 10 or (e6) = 12, its result written to the X slab by the form's own epilogue and copied out
 template <int FORM>
 __global__ __launch_bounds__(64) void chk(const float* __restrict__ w32, const float* __restrict__ w16, const float* __restrict__ x0, float* out) {
   __shared__ float4 slab[32 * 64];
@@ -276,10 +285,13 @@ __global__ __launch_bounds__(64) void chk(const float* __restrict__ w32, const f
   float4* X = slab + lane;
   for (int it = 0; it < 32; ++it) X[it * 64] = *reinterpret_cast<const float4*>(x0 + ((size_t)it * 64 + lane) * 4);
   __syncthreads();
-  if constexpr (FORM == 5 || FORM == 6) {
+  if constexpr (FORM == 5 || FORM == 6 || FORM == 10 || FORM == 12) {
     f32x4 a16[8][2][2];
     zero_acc16<8>(a16);
-    if (FORM == 5) gemm_bf16_s16<8>(a16, w16, X, 8, lane); else gemm_f32_x9_s16<8>(a16, w32, X, 8, lane);
+    if (FORM == 5) gemm_bf16_s16<8, 9>(a16, w16, X, 8, lane);
+    else if (FORM == 10) gemm_bf16_s16<8, 6>(a16, w16, X, 8, lane);
+    else if (FORM == 12) gemm_f32_s16<8, 6>(a16, w32, X, 8, lane);
+    else gemm_f32_s16<8, 9>(a16, w32, X, 8, lane);
     __syncthreads();
     store_act16<8>(a16, X, lane);
   } else {
@@ -293,7 +305,9 @@ __global__ __launch_bounds__(64) void chk(const float* __restrict__ w32, const f
   for (int it = 0; it < 32; ++it) *reinterpret_cast<float4*>(out + ((size_t)it * 64 + lane) * 4) = X[it * 64];
 }
 
-// one wave, one tile: form (d) keeping the rows it reads (gemm_bf16_s16's saver) with `valid` of the 32 rows inside the descriptor
+// one wave, one tile: form (d) (NP = 9) or (d6) (NP = 6) keeping the rows it reads (gemm_bf16_s16's saver) with `valid` of the 32
+// rows inside the descriptor
+template <int NP>
 __global__ __launch_bounds__(64) void chk_rows(const float* __restrict__ w16, const float* __restrict__ x0, float* out, float* rows, int valid) {
   __shared__ float4 slab[32 * 64];
   const int lane = threadIdx.x;
@@ -302,7 +316,7 @@ __global__ __launch_bounds__(64) void chk_rows(const float* __restrict__ w16, co
   __syncthreads();
   f32x4 a16[8][2][2];
   zero_acc16<8>(a16);
-  gemm_bf16_s16<8>(a16, w16, X, 8, lane, rowbuf<false>(rows, 0, valid, 256, lane & 15, (lane >> 4) & 1));
+  gemm_bf16_s16<8, NP>(a16, w16, X, 8, lane, rowbuf<false>(rows, 0, valid, 256, lane & 15, (lane >> 4) & 1));
   __syncthreads();
   store_act16<8>(a16, X, lane);
   __syncthreads();
@@ -367,12 +381,16 @@ static void pack_pieces(const float* h, unsigned short* hb) {
         }
 }
 
-// Forms (b) and (d) on integer operands: `wide` weights of 17 bits (three non-zero pieces) against activations in {0, +-1}, three
-// in four zero, or the reverse.  Every partial sum stays under 2^24, so any order of accumulation gives the integer result.
+// Forms (b), (d), (e) and their six-product forms on integer operands: `wide` weights of up to 19 bits against activations in
+// {0, +-1}, fifteen in sixteen zero, or the reverse.  (With nearest-rounding pieces an integer below 2^17 has no lo piece; from 2^18
+// on hi, mid and lo are all there, so every kept product of the six-product forms -- w_lo b_hi, w_mid b_hi, w_hi b_lo, w_hi b_mid
+// among them -- carries part of the sums.  w_mid b_mid needs both operands wide: tests/test_six_products_gpu.py has random operands
+// for that.)  The sum of the magnitudes of every dot product stays under 2^24 / 1.01^2 (checked below), so any order of accumulation
+// of any pieces gives the integer result.
 static bool check_forms(bool wide_w, float* w32, float* w16, float* x0, float* out) {
   std::vector<float> hw(SEG_F32), hx(32 * 64 * 4);
-  auto big = [](size_t i) { return (float)((long long)((i * 2654435761u + 12345u) % 262143u) - 131071); };
-  auto small = [](size_t i) { const unsigned r = (unsigned)(i * 2246822519u) >> 13; return (r & 12u) ? 0.0f : ((r & 1u) ? 1.0f : -1.0f); };
+  auto big = [](size_t i) { return (float)((long long)((i * 2654435761u + 12345u) % 1048575u) - 524287); };
+  auto small = [](size_t i) { const unsigned r = (unsigned)(i * 2246822519u) >> 13; return (r & 60u) ? 0.0f : ((r & 1u) ? 1.0f : -1.0f); };
   for (size_t i = 0; i < hw.size(); ++i) hw[i] = wide_w ? big(i) : small(i);
   for (size_t i = 0; i < hx.size(); ++i) hx[i] = wide_w ? small(i + 7) : big(i + 7);
   std::vector<unsigned short> hb((size_t)SEG_B16 * 2);
@@ -387,33 +405,51 @@ static bool check_forms(bool wide_w, float* w32, float* w16, float* x0, float* o
   CK(hipMemcpy(od.data(), out, od.size() * 4, hipMemcpyDeviceToHost));
   hipLaunchKernelGGL((chk<6>), dim3(1), dim3(64), 0, 0, w32, w16, x0, out);
   CK(hipMemcpy(oe.data(), out, oe.size() * 4, hipMemcpyDeviceToHost));
-  size_t bad_b = 0, bad_d = 0, bad_e = 0, differ = 0;
+  std::vector<float> od6(hx.size()), oe6(hx.size());
+  hipLaunchKernelGGL((chk<10>), dim3(1), dim3(64), 0, 0, w32, w16, x0, out);
+  CK(hipMemcpy(od6.data(), out, od6.size() * 4, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL((chk<12>), dim3(1), dim3(64), 0, 0, w32, w16, x0, out);
+  CK(hipMemcpy(oe6.data(), out, oe6.size() * 4, hipMemcpyDeviceToHost));
+  size_t bad_b = 0, bad_d = 0, bad_e = 0, differ = 0, bad_d6 = 0, bad_e6 = 0;
+  double worst_abs = 0.0;  // largest sum of |w| |x| over a dot product
   for (int it = 0; it < 32; ++it)      // X[it][lane][c]: row 8 it + 4 (lane >> 5) + c of point lane & 31
     for (int lane = 0; lane < 64; ++lane)
       for (int c = 0; c < 4; ++c) {
         const int row = 8 * it + 4 * (lane >> 5) + c, p = lane & 31;
-        long long ref = 0;
+        long long ref = 0, mag = 0;
         for (int ki = 0; ki < 32; ++ki)
           for (int kh = 0; kh < 2; ++kh)
-            for (int kc = 0; kc < 4; ++kc)
-              ref += (long long)hw[((size_t)(ki * 8 + row / 32) * 64 + (row % 32) + 32 * kh) * 4 + kc] *
-                     (long long)hx[((size_t)ki * 64 + p + 32 * kh) * 4 + kc];
+            for (int kc = 0; kc < 4; ++kc) {
+              const long long t = (long long)hw[((size_t)(ki * 8 + row / 32) * 64 + (row % 32) + 32 * kh) * 4 + kc] *
+                                  (long long)hx[((size_t)ki * 64 + p + 32 * kh) * 4 + kc];
+              ref += t;
+              mag += t < 0 ? -t : t;
+            }
+        if ((double)mag > worst_abs) worst_abs = (double)mag;
         const size_t o = ((size_t)it * 64 + lane) * 4 + c;
         bad_b += ob[o] != (float)ref;
         bad_d += od[o] != (float)ref;
         bad_e += oe[o] != (float)ref;
+        bad_d6 += od6[o] != (float)ref;
+        bad_e6 += oe6[o] != (float)ref;
         differ += ob[o] != od[o] || od[o] != oe[o];
       }
   printf("check, %s: (b) wrong %zu, (d) wrong %zu, (e) wrong %zu, not all equal %zu of %zu\n",
-         wide_w ? "17-bit weights x 0/+-1 activations" : "0/+-1 weights x 17-bit activations", bad_b, bad_d, bad_e, differ, ob.size());
+         wide_w ? "19-bit weights x 0/+-1 activations" : "0/+-1 weights x 19-bit activations", bad_b, bad_d, bad_e, differ, ob.size());
+  printf("check, %s: six products: (d6) wrong %zu, (e6) wrong %zu of %zu; largest sum of magnitudes %.0f (%.3f of 2^24)\n",
+         wide_w ? "19-bit weights x 0/+-1 activations" : "0/+-1 weights x 19-bit activations", bad_d6, bad_e6, ob.size(), worst_abs,
+         worst_abs / 16777216.0);
+  if (worst_abs * 1.0201 >= 16777216.0) { printf("the integer case is not exact in every order\n"); return false; }
   // (d) with the row saver: the same result, every float4 it read in its row of a [points, 256] buffer (row m, floats 8 it + 4 h
   // .. of slab entry (it, old lane m + 32 h)), rows at or past `valid` and the guard rows behind the tile untouched
   size_t bad_r = 0, bad_s = 0, stray = 0;
   const int guard = 8;
   std::vector<unsigned> hr((size_t)(32 + guard) * 256);
-  for (int valid : {32, 19, 1}) {
+  for (int pass = 0; pass < 6; ++pass) {  // (d), then (d6): the same result, rows and silence past the valid rows
+    const int valid = pass % 3 == 0 ? 32 : (pass % 3 == 1 ? 19 : 1);
     CK(hipMemset(g_rows, 0xCD, hr.size() * 4));
-    hipLaunchKernelGGL(chk_rows, dim3(1), dim3(64), 0, 0, w16, x0, out, g_rows, valid);
+    if (pass < 3) hipLaunchKernelGGL(chk_rows<9>, dim3(1), dim3(64), 0, 0, w16, x0, out, g_rows, valid);
+    else hipLaunchKernelGGL(chk_rows<6>, dim3(1), dim3(64), 0, 0, w16, x0, out, g_rows, valid);
     CK(hipMemcpy(oe.data(), out, oe.size() * 4, hipMemcpyDeviceToHost));
     CK(hipMemcpy(hr.data(), g_rows, hr.size() * 4, hipMemcpyDeviceToHost));
     for (size_t o = 0; o < od.size(); ++o) bad_r += oe[o] != od[o];
@@ -427,9 +463,9 @@ static bool check_forms(bool wide_w, float* w32, float* w16, float* x0, float* o
         bad_s += got != wb;
       }
   }
-  printf("check, %s: (d) with the row saver, 32 / 19 / 1 valid rows: result differs from (d) %zu, saved rows wrong %zu, stray stores %zu\n",
-         wide_w ? "17-bit weights x 0/+-1 activations" : "0/+-1 weights x 17-bit activations", bad_r, bad_s, stray);
-  return bad_b == 0 && bad_d == 0 && bad_e == 0 && differ == 0 && bad_r == 0 && bad_s == 0 && stray == 0;
+  printf("check, %s: (d) and (d6) with the row saver, 32 / 19 / 1 valid rows: result differs from (d) %zu, saved rows wrong %zu, stray stores %zu\n",
+         wide_w ? "19-bit weights x 0/+-1 activations" : "0/+-1 weights x 19-bit activations", bad_r, bad_s, stray);
+  return bad_b == 0 && bad_d == 0 && bad_e == 0 && differ == 0 && bad_d6 == 0 && bad_e6 == 0 && bad_r == 0 && bad_s == 0 && stray == 0;
 }
 
 static float* g_bias = nullptr;     // two biases of 256 (the layer's, the next layer's)
@@ -575,6 +611,14 @@ int main() {
   run<6, false>("(e) nine products, pieces in registers, 16x16x32", w32, w16, x0, out, cal, a0);
   run<2, false>("(c) again", w32, w16, x0, out, cal, a0);
   run<6, false>("(e) again", w32, w16, x0, out, cal, a0);
+  // six of the nine products (the analytic-normal sweep's GEMMs): against (d), same run
+  const double d2 = run<5, false>("(d) again", w32, w16, x0, out, cal, a0);
+  const double s0 = run<10, false>("(d6) six products, packed pieces, 16x16x32", w32, w16, x0, out, cal, a0);
+  const double d3 = run<5, false>("(d) again", w32, w16, x0, out, cal, a0);
+  const double s1 = run<10, false>("(d6) again", w32, w16, x0, out, cal, a0);
+  run<12, false>("(e6) six products, pieces in registers, 16x16x32", w32, w16, x0, out, cal, a0);
+  printf("six-product go / no-go, normal sweep: (d6) / (d) wall time = %.3f (go at <= 0.850): %s\n", (s0 + s1) / (d2 + d3),
+         (s0 + s1) / (d2 + d3) <= 0.85 ? "GO" : "NO-GO");
   // the backward sweep: every GEMM also keeps the 32 KiB of rows it reads (or, from the epilogue, writes) in a [points, 256] buffer
   printf("-- the backward sweep's case: the GEMM keeps its rows (32 KiB per tile to a 512 MiB buffer), the four waves on the same segment\n");
   const double f0 = run<8, false>("(a) fp32 + row stores in the K loop (gemm_run2 saver)", w32, w16, x0, out, cal, a0);
@@ -583,6 +627,15 @@ int main() {
   const double f1 = run<8, false>("(a) + stores in the loop, again", w32, w16, x0, out, cal, a0);
   const double g1 = run<7, false>("(d) + stores in the loop, again", w32, w16, x0, out, cal, a0);
   const double h1 = run<9, false>("(d) + stores from the epilogue, again", w32, w16, x0, out, cal, a0);
+  {
+    // six of the nine products with the row stores in the K loop (the backward sweep's stage 4): against (d) with its stores
+    const double g2 = run<7, false>("(d) + stores in the loop, again", w32, w16, x0, out, cal, a0);
+    const double t0 = run<11, false>("(d6) six products + row stores in the K loop", w32, w16, x0, out, cal, a0);
+    const double g3 = run<7, false>("(d) + stores in the loop, again", w32, w16, x0, out, cal, a0);
+    const double t1 = run<11, false>("(d6) + stores in the loop, again", w32, w16, x0, out, cal, a0);
+    printf("six-product go / no-go, backward sweep: (d6) / (d), both with their stores, wall time = %.3f (go at <= 0.850): %s\n",
+           (t0 + t1) / (g2 + g3), (t0 + t1) / (g2 + g3) <= 0.85 ? "GO" : "NO-GO");
+  }
   {
     const double best = (g0 + g1) < (h0 + h1) ? (g0 + g1) : (h0 + h1), r = best / (f0 + f1);
     // predicted step gain, the forward's arithmetic: saving per tile and GEMM x 7 GEMMs x 16 tiles per wave and 524,288 points x 2.54
