@@ -51,9 +51,9 @@ typedef enum rsn_spacing { RSN_SPACING_UNIFORM = 0, RSN_SPACING_RECIPROCAL = 1 }
  * model builds for it (reflect_sampling_nerf_model.py:98-100: 2**linspace(0,16,16), computed by the
  * caller so that it is bit-identical to the host framework's table). */
 typedef struct rsn_field_desc {
-  int32_t num_layers;   /* trunk nn.Linear count (base_mlp_num_layers), 2..RSN_MAX_TRUNK_LAYERS */
+  int32_t num_layers;   /* trunk nn.Linear count (base_mlp_num_layers), 1..RSN_MAX_TRUNK_LAYERS */
   int32_t width;        /* base_mlp_layer_width: 64, 128 or 256 */
-  int32_t skip_layer;   /* layer whose input is cat([encoding, x]) (4 when num_layers >= 6), or -1 */
+  int32_t skip_layer;   /* layer whose input is cat([encoding, x]): 1..num_layers-2 (4 when num_layers >= 6), or -1 */
   int32_t mid_width;    /* head_mlp_layer_width: 128 */
   float density_bias;   /* 0.5 */
   float freqs[RSN_NUM_FREQS];

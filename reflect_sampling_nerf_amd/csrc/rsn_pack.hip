@@ -330,7 +330,9 @@ __global__ void rsn_pack_kernel(const PackJob job) { pack_elem(job, blockIdx.x *
 
 // Every segment in ONE launch (rsn_pack_weights_table): the job descriptors live in device memory, uploaded once per
 // (parameter pointers, shape); workgroup b serves job j with block_start[j] <= b < block_start[j + 1].
-#define PACK_MAX_JOBS 96
+// build_jobs adds 5 L + 4 s + 21 jobs at most (L trunk layers, s = 1 with a live skip; the ring stream of a bf16 mode at width 256
+// included, which rsn_compute_layout lays out at every depth): 105 at RSN_MAX_TRUNK_LAYERS; a table of 96 refused 15 layers with a skip and 16 layers
+#define PACK_MAX_JOBS (5 * RSN_MAX_TRUNK_LAYERS + 4 + 21 + 7)
 struct PackTable {
   int n_jobs, n_blocks;
   int block_start[PACK_MAX_JOBS + 1];

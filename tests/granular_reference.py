@@ -42,21 +42,24 @@ SMALL_FIELDS = [(8, 64), (4, 128), (8, 256), (8, 200)]
 _fields = {}
 
 
-def make_field(layers, width):
+def make_field(layers, width, skips=None):
     """The package's Field on the host with its seeded random init (density bias shifted by +1 as in the suite's other field
-    tests) -> (module, parameters by state_dict name, cpu_ref.FieldSpec).  Cached: the GPU file moves a deep copy to the device."""
+    tests) -> (module, parameters by state_dict name, cpu_ref.FieldSpec).  Cached: the GPU file moves a deep copy to the device.
+    skips: skip_connections other than the Field's default (tests/test_depth_skip_gpu.py); the seed then follows from the shape."""
     import reflect_sampling_nerf_amd as pkg
 
-    key = (layers, width)
+    key = (layers, width) if skips is None else (layers, width, tuple(skips))
     if key not in _fields:
         rng = torch.get_rng_state()
-        torch.manual_seed(FIELD_SEEDS[key])
-        f = pkg.ReflectSamplingNeRFNerfField(base_mlp_num_layers=layers, base_mlp_layer_width=width)
+        torch.manual_seed(FIELD_SEEDS[key] if skips is None else 200 + 32 * layers + width + sum(skips))
+        kw = {} if skips is None else {"skip_connections": tuple(skips)}
+        f = pkg.ReflectSamplingNeRFNerfField(base_mlp_num_layers=layers, base_mlp_layer_width=width, **kw)
         torch.set_rng_state(rng)
         with torch.no_grad():
             f.field_output_density.net.bias += 1.0
         P = {k: v.detach().clone() for k, v in f.state_dict().items()}
-        _fields[key] = (f.eval(), P, cpu_ref.FieldSpec(num_layers=layers, width=width))
+        fs = cpu_ref.FieldSpec(num_layers=layers, width=width) if skips is None else cpu_ref.FieldSpec(num_layers=layers, width=width, skip=tuple(skips))
+        _fields[key] = (f.eval(), P, fs)
     return _fields[key]
 
 

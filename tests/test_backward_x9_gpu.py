@@ -124,12 +124,12 @@ INT_CASES = [(w, n, layer) for w in (64, 256) for n, (L, _) in INT_NETS.items() 
 M_INF = 49  # a full wave tile and one that ends one row into its second point half
 
 
-def _integer_net(width, layers, skips):
-    """_integer_field (trunk x parts -2 .. 2 on eight rows a column, the raw-coordinate columns of the encoded parts, the density
+def _integer_net(width, layers, skips, base=_integer_field):
+    """base (_integer_field: trunk x parts -2 .. 2 on eight rows a column, the raw-coordinate columns of the encoded parts, the density
     row) plus what the backward sweep crosses in front of the trunk and behind it: sparse -2 .. 2 on the sin / cos columns of the
     encoded parts (one row in sixteen), a bottleneck of two +-1 a row, one +-1 bottleneck unit per mlp_mid unit (so W_c = W_mid,x W_b
     is exact, two +-1 a row), integer biases there (b_c exact), and an RGB head of -1 / 0 / 1."""
-    f = _integer_field(width, layers, skips)
+    f = base(width, layers, skips)
     i, j = torch.arange(width)[:, None], torch.arange(width)[None, :]
     with torch.no_grad():
         for l in range(layers):

@@ -11,6 +11,7 @@ import reflect_sampling_nerf_amd as pkg
 from oracle import cpu_ref
 from reflect_sampling_nerf_amd import ops
 from reflect_sampling_nerf_amd._abi import RSN_SPACING_RECIPROCAL, RSN_SPACING_UNIFORM
+from tests import depth_skip_cases
 from tests.helpers import load_golden, max_abs
 
 pytestmark = pytest.mark.gpu
@@ -903,9 +904,7 @@ def test_chunked_eval_image_issues_no_device_to_host_read(dev):
     assert torch.equal(img["mask"].reshape(n), single["mask"])
 
 
-@pytest.mark.parametrize("mode", ["f32", "bf16x6", "bf16"])
-@pytest.mark.parametrize("layers,width", [(8, 256), (4, 128), (6, 64)])
-def test_single_launch_packing_equals_per_segment_packing(dev, layers, width, mode):
+def _packing_paths_agree(dev, fld, mode):
     """rsn_pack_weights_table (every segment in one launch, job table in device memory) against rsn_pack_weights (one
     launch per segment): bit-identical packed buffers, also when the table is re-used for changed parameter values."""
     import ctypes as C
@@ -913,7 +912,6 @@ def test_single_launch_packing_equals_per_segment_packing(dev, layers, width, mo
     from reflect_sampling_nerf_amd._abi import check, load_library, ptr
 
     lib = load_library()
-    fld, _, _ = make_field(layers, width, dev, seed=5)
     fld.set_mma_mode(mode)
     fld.packed_weights()  # allocates the buffer; regions no launch writes (split-bf16 copies in f32 mode) get zeros
     fld._packed.zero_()
@@ -934,6 +932,24 @@ def test_single_launch_packing_equals_per_segment_packing(dev, layers, width, mo
     check(lib.rsn_pack_weights(C.byref(desc), C.byref(ps), ptr(slow), nbytes, ops._stream()))
     torch.cuda.synchronize()
     assert torch.equal(fast2.view(torch.int32), slow.view(torch.int32)) and not torch.equal(fast2, fast)
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16x6", "bf16"])
+@pytest.mark.parametrize("layers,width", [(8, 256), (4, 128), (6, 64)])
+def test_single_launch_packing_equals_per_segment_packing(dev, layers, width, mode):
+    fld, _, _ = make_field(layers, width, dev, seed=5)
+    _packing_paths_agree(dev, fld, mode)
+
+
+@pytest.mark.parametrize("mode,width,net", depth_skip_cases.PACK_CASES, ids=[f"{m}-w{w}-{n}" for m, w, n in depth_skip_cases.PACK_CASES])
+def test_single_launch_packing_equals_per_segment_packing_at_depth_and_skip_extremes(dev, mode, width, net):
+    """The same at the nets of tests/depth_skip_cases.py that move the segment and job counts: skip = 1 = L-2, the ring's deepest
+    net, the first one past it (whose ring stream is laid out and packed all the same) and the maximum depth, where the job
+    table is at its fullest (5 L + 4 s + 21 jobs with the ring stream, rsn_pack.hip)."""
+    layers, skips = depth_skip_cases.NETS[net]
+    torch.manual_seed(5)
+    fld = pkg.ReflectSamplingNeRFNerfField(base_mlp_num_layers=layers, base_mlp_layer_width=width, skip_connections=skips)
+    _packing_paths_agree(dev, fld.to(dev).eval(), mode)
 
 
 # (trunk layers, base_mlp_layer_width, skip_connections): the smallest shapes that reach every segment kind, the zero-padded

@@ -139,10 +139,11 @@ def _first(d, n):
     return {k: v[:n] for k, v in d.items()}
 
 
-def _geometry(label, mode, width, kind, N, cus, loop):
-    """(tile, grid) of the launch that serves (mode, kernel width, kind); loop: asserted with helpers.multitile_geometry."""
+def _geometry(label, mode, width, kind, N, cus, loop, layers=8):
+    """(tile, grid) of the launch that serves (mode, kernel width, kind); loop: asserted with helpers.multitile_geometry.
+    layers: the ring serves trunks of up to 10 layers (RSN_RING_MAX_LAYERS, rsn_launch_field_bf16)."""
     if mode == "bf16":
-        tile, units = (256, cus) if (kind == "gauss" and width == 256) else (128, 2 * cus)  # the ring / rsn_field_bf16_kernel<NB>
+        tile, units = (256, cus) if (kind == "gauss" and width == 256 and layers <= 10) else (128, 2 * cus)  # the ring / rsn_field_bf16_kernel<NB>
     else:
         tile, units = 128, cus
     if loop:

@@ -49,6 +49,7 @@ def _cases():
 
 CASES = _cases()
 RING = {("bf16x6", 256), ("bf16", 256), ("bf16", 200)}  # (family, width) the LDS-ring kernels serve: asserted in _kernel
+RING_MAX_LAYERS = 10  # ... up to this trunk depth (RSN_RING_MAX_LAYERS, rsn_common.h: the ring kernels' LDS bias table); deeper nets run per wave
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +98,7 @@ def _poisoned_allocators(f):
 def _kernel(f, family, width):
     """The kernel family that serves this Field, asserted from the layout the library reports."""
     lay = f.train_layout()
-    ring = (family, width) in RING
+    ring = (family, width) in RING and f.mlp_base.num_layers <= RING_MAX_LAYERS
     assert (lay["enc_cols"] == 128) == ring and (lay["sh_cols"] == 64) == ring, (family, width, lay["enc_cols"], lay["sh_cols"])
     assert lay["narrow_dtype"] == (torch.bfloat16 if (ring and family == "bf16") else f32)
     assert f.wide_dtype() == (torch.bfloat16 if family == "bf16" else f32)
@@ -158,11 +159,13 @@ def _check(*results):
         assert r["d_input"].ok, "\n" + r["d_input"].report()
 
 
-def run_case(dev, family, fold, width, net, points, n_live_rays=None):
-    """One launch pair on a frustum level -> the result of _judge (nothing asserted about the rows yet: _check).  n_live_rays: a device-side count below the buffers."""
-    layers, skips = NETS[net]
+def run_case(dev, family, fold, width, net, points, n_live_rays=None, nets=NETS, make_field=None, keep=False):
+    """One launch pair on a frustum level -> the result of _judge (nothing asserted about the rows yet: _check).  n_live_rays: a device-side count below the buffers.
+    nets: where `net` names (layers, skips); make_field(width, layers, skips): the Field instead of S._field's seed 23; keep: the result also
+    carries the level, the saved rows and the Field's layout on the host ("level", "saved", "lay": tests/test_depth_skip_gpu.py)."""
+    layers, skips = nets[net]
     Rn, Sn = points
-    f = S._field(width, layers=layers, skips=skips, seed=23)
+    f = S._field(width, layers=layers, skips=skips, seed=23) if make_field is None else make_field(width, layers, skips)
     inp = S._rays(Rn, Sn, seed=width + layers + Rn)
     f.to(dev).train()
     f.set_mma_mode(family)
@@ -177,7 +180,11 @@ def run_case(dev, family, fold, width, net, points, n_live_rays=None):
     label = f"{family}{' folded' if fold else ''} w{width} {net} {Rn * Sn} points" + ("" if n_live_rays is None else f" ({n_live_rays * Sn} live)")
     rows = _rows(Rn * Sn, lv, lv["saved"], go, fold)
     geometry = {"o": inp["o"], "d": inp["d"], "pa": inp["pa"], "eb": inp["eb"]}
-    return _judge(label, f, lay, ring, rows, layers, skips, family, fold, geometry, None if n_live_rays is None else n_live_rays * Sn)
+    res = _judge(label, f, lay, ring, rows, layers, skips, family, fold, geometry, None if n_live_rays is None else n_live_rays * Sn)
+    if keep:
+        host = lambda d: {k: v.detach().cpu() for k, v in d.items() if torch.is_tensor(v)}  # noqa: E731
+        res.update({"level": host(lv), "saved": host(lv["saved"]), "lay": lay, "ring": ring, "field": f, "inputs": inp})
+    return res
 
 
 @pytest.mark.parametrize("family,fold,width,net,points", CASES,
