@@ -841,6 +841,65 @@ int rsn_capture_rays_image(int32_t height, int32_t width, const float* c2w, cons
                            float* directions, float* pixel_area, void* stream);
 
 
+/* ---- captures: masks and fisheye lenses (additive to ABI 18: no existing call changes, and the calls above keep their bits).
+ *
+ * Camera table with 12 columns: row i = (fx, fy, cx, cy, k1, k2, k3, p1, p2, k4, model, 0).  model == 0: a perspective row, the
+ * arithmetic of the 9-column table above on its first nine columns (k4 is not read).  model != 0 (the loader writes 1): OpenCV's
+ * equidistant fisheye model, as COLMAP's OPENCV_FISHEYE writes it (p1, p2 are not read).  A call that takes camera_stride accepts
+ * 9 (every row perspective) or 12.
+ *
+ * Fisheye ray of pixel (y, x), every step up to the rounding of the direction in fp64:
+ *   (xd, yd) = ((x+.5-cx)/fx, (y+.5-cy)/fy);   theta_d = sqrt(xd^2 + yd^2)
+ *   theta solves  theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) = theta_d  by Newton from theta = theta_d:
+ *     t2 = theta^2;  f  = theta (1 + t2 (k1 + t2 (k2 + t2 (k3 + t2 k4)))) - theta_d
+ *                    f' = 1 + t2 (3 k1 + t2 (5 k2 + t2 (7 k3 + t2 9 k4)));   theta -= f / f'
+ *     exactly 10 steps, none skipped early; a step with |f'| <= 1e-12 leaves theta where it is; then theta = min(max(theta, 0), pi)
+ *   v = (xd s, -(yd s), -cos theta) with s = sin(theta) / theta_d;  at theta_d == 0:  v = (0, 0, -1)        (fp64 sin, cos, sqrt)
+ * v is the camera-space UNIT direction; it is rounded to fp32 once.  The x+1 and y+1 neighbours get their own solves; their
+ * camera-space offsets e = v_neighbour - v are formed in fp64 and rounded to fp32 once.  From there on fp32, as every other ray:
+ * w = R v and g = R e with all three components (v.z > 0 beyond 90 degrees from the axis), directions = w / |w|, origins =
+ * c2w[:, 3], pixel_area by the cancellation-free rearrangement of the standalone data path.  Nothing on the device checks that the
+ * solve converged: the caller makes sure the model is invertible over the image (data.load_nerfstudio_split does).
+ * Level l of a pyramid: the row's fx, fy, cx, cy over 2^l (exact); k1 .. k4 act on angles and stay.
+ *
+ * Live-pixel lists: masks is uint8 [N, H, W], non-zero = the pixel may be trained on.  Pixel (i, y, x) of level l has the flat
+ * index i (H >> l)(W >> l) + y (W >> l) + x -- the numbering the samplers draw in -- and is live when ALL 2^l x 2^l level-0
+ * pixels under it are, so that the pyramid's box colour of a live pixel never mixes a masked one in.  The list of a level holds
+ * its live indices in ascending order; the lists are concatenated in level order, counts[l] is the length of level l's. */
+#define RSN_LIVE_TILE 256          /* level pixels per workgroup of the compaction */
+#define RSN_LIVE_SCAN_CHUNK 65536  /* level pixels per trip of the scan's loop: RSN_LIVE_TILE tiles; a carry crosses each boundary */
+
+/* Bytes of workspace rsn_build_live_pixels needs (4 per tile of RSN_LIVE_TILE pixels of every level), or 0 with a message for a
+ * shape rsn_build_pyramid would refuse. */
+size_t rsn_live_pixels_workspace_bytes(int32_t n_images, int32_t height, int32_t width, int32_t levels);
+
+/* counts (device uint32 [levels]) receives the lengths of the lists.  live == NULL (or live_capacity == 0): that is all.  Else
+ * the lists are written to live (device uint32), but only entries < live_capacity: never a byte past it.  Stable compaction, no
+ * atomics: per-tile counts, one workgroup per level scans them, every tile writes behind its own offset; two runs give the same
+ * bytes, equal to numpy.flatnonzero of the level's liveness.  workspace: 4-byte aligned, device.  No host read, no allocation. */
+int rsn_build_live_pixels(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* masks, uint32_t* live,
+                          size_t live_capacity, uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* rsn_sample_capture_rays with two changes.  (a) With live != NULL the flat pixel of ray r at level l is
+ *   live[live_offsets[l] + (uint32)(((uint64)u * count_l) >> 32)],   count_l = live_offsets[l+1] - live_offsets[l]
+ * in place of (uint32)(((uint64)u * (N H_l W_l)) >> 32); live_offsets is device uint32 [levels + 1], the running sum of the counts
+ * above.  live == NULL: every pixel, and live_offsets is not read.  A level with count_l == 0 is the caller's error; the kernel
+ * then takes the level's pixel 0 and reads nothing outside the lists, and a list entry beyond the level's last pixel is clamped to
+ * it.  (b) The camera row is read at camera_stride, and a fisheye row takes the fisheye ray.  The level draw (v), the gather, the
+ * blend, the outputs and the Philox counter layout are unchanged: with live == NULL (or all pixels live) and perspective rows the
+ * output bytes are rsn_sample_capture_rays'. */
+int rsn_sample_capture_rays_live(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images,
+                                 const float* pyramid, size_t pyramid_pixels, const float* c2w, const float* cameras,
+                                 int32_t camera_stride, const uint32_t* live, const uint32_t* live_offsets, int32_t n_rays,
+                                 uint32_t seed, uint32_t rank, uint32_t step, float* origins, float* directions, float* pixel_area,
+                                 float* rgb, int32_t* indices, int32_t* level, void* stream);
+
+/* rsn_capture_rays_image for a row of camera_stride (9 or 12) columns: the sampler's device function, so equal (pose, row, y, x)
+ * give equal bits; a perspective row gives rsn_capture_rays_image's. */
+int rsn_capture_rays_image2(int32_t height, int32_t width, const float* c2w, const float* camera, int32_t camera_stride,
+                            float* origins, float* directions, float* pixel_area, void* stream);
+
+
 /* ---- mesh export: the iso-surface of a scalar volume as an indexed triangle mesh (additive to ABI 18: no existing call
  * changes).  Marching tetrahedra on the Kuhn (Freudenthal) split of every grid cell: no case table, consistent across
  * shared cell faces by construction (a surface away from the grid boundary is closed), and every surface vertex lies on

@@ -234,6 +234,13 @@ _SIGNATURES = {
                                           C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, _fp, _fp, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "rsn_capture_rays_image": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_void_p]),
+    "rsn_live_pixels_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rsn_build_live_pixels": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rsn_sample_capture_rays_live": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, _fp, C.c_size_t, _fp, _fp,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, _fp,
+                                               _fp, _fp, _fp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rsn_capture_rays_image2": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_void_p]),
     "rsn_ssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rsn_ssim": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
     "rsn_mesh_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -24,24 +24,10 @@ __device__ __forceinline__ Camera load_camera(const float* __restrict__ row) {
 // neighbour's camera-space offset), a = |w|, b = |w + g|:  w/a - (w+g)/b = w (b - a)/(a b) - g/b,  b - a = (2 w.g + g.g) / (a + b).
 // AXIS: the offsets are (exx, 0) and (0, eyy) (a pinhole camera); exy and eyx are not read, and the arithmetic is the pinhole
 // function's as it always was.
-template <bool AXIS>
-__device__ __forceinline__ void camera_ray_at(const float* __restrict__ c2w, float vx, float vy, float exx, float exy, float eyx,
-                                              float eyy, float* o, float* d, float* area) {
-  float R[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) R[j] = c2w[j];
-  float w[3], gx[3], gy[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    w[i] = vx * R[4 * i + 0] + vy * R[4 * i + 1] + (-1.0f) * R[4 * i + 2];
-    if (AXIS) {
-      gx[i] = exx * R[4 * i + 0];
-      gy[i] = eyy * R[4 * i + 1];
-    } else {
-      gx[i] = exx * R[4 * i + 0] + exy * R[4 * i + 1];
-      gy[i] = eyx * R[4 * i + 0] + eyy * R[4 * i + 1];
-    }
-  }
+// The tail every ray shares: w = R v and the neighbours' rotated offsets gx, gy -> direction, origin and pixel_area by the
+// rearrangement above.
+__device__ __forceinline__ void ray_from_rotated(const float* R, const float* w, const float* gx, const float* gy, float* o, float* d,
+                                                 float* area) {
   const float a2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   const float a = sqrtf(a2);
   float nb[2];
@@ -63,6 +49,44 @@ __device__ __forceinline__ void camera_ray_at(const float* __restrict__ c2w, flo
     o[i] = R[4 * i + 3];
   }
   *area = nb[0] * nb[1];
+}
+
+template <bool AXIS>
+__device__ __forceinline__ void camera_ray_at(const float* __restrict__ c2w, float vx, float vy, float exx, float exy, float eyx,
+                                              float eyy, float* o, float* d, float* area) {
+  float R[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) R[j] = c2w[j];
+  float w[3], gx[3], gy[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    w[i] = vx * R[4 * i + 0] + vy * R[4 * i + 1] + (-1.0f) * R[4 * i + 2];
+    if (AXIS) {
+      gx[i] = exx * R[4 * i + 0];
+      gy[i] = eyy * R[4 * i + 1];
+    } else {
+      gx[i] = exx * R[4 * i + 0] + exy * R[4 * i + 1];
+      gy[i] = eyx * R[4 * i + 0] + eyy * R[4 * i + 1];
+    }
+  }
+  ray_from_rotated(R, w, gx, gy, o, d, area);
+}
+
+// camera_ray_at for a camera-space direction v and neighbour offsets ex, ey with three components each: a fisheye pixel beyond
+// 90 degrees from the axis has v.z > 0, and its neighbours differ from it in z too.
+__device__ __forceinline__ void camera_ray_at3(const float* __restrict__ c2w, const float* v, const float* ex, const float* ey, float* o,
+                                               float* d, float* area) {
+  float R[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) R[j] = c2w[j];
+  float w[3], gx[3], gy[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    w[i] = v[0] * R[4 * i + 0] + v[1] * R[4 * i + 1] + v[2] * R[4 * i + 2];
+    gx[i] = ex[0] * R[4 * i + 0] + ex[1] * R[4 * i + 1] + ex[2] * R[4 * i + 2];
+    gy[i] = ey[0] * R[4 * i + 0] + ey[1] * R[4 * i + 1] + ey[2] * R[4 * i + 2];
+  }
+  ray_from_rotated(R, w, gx, gy, o, d, area);
 }
 
 // nerfstudio 0.3 Cameras._generate_rays_from_coords, perspective: the pixel centre's camera-space direction
@@ -120,4 +144,74 @@ __device__ __forceinline__ void capture_ray(const float* __restrict__ c2w, const
   undistort_point(c, xd0, yd1, &Xy, &Yy);
   camera_ray_at<false>(c2w, (float)X0, (float)(-Y0), (float)(Xx - X0), (float)(-(Yx - Y0)), (float)(Xy - X0), (float)(-(Yy - Y0)),
                        o, d, area);
+}
+
+// One row of a 9- or 12-column camera table (include/rsn.h, "captures: masks and fisheye lenses"): 12 columns add k4 and the model
+// (0: the perspective arithmetic above, else OpenCV's equidistant fisheye); a 9-column row is a perspective one.
+struct LensCamera {
+  Camera c;
+  float k4;
+  bool fisheye;
+};
+
+__device__ __forceinline__ LensCamera load_lens_camera(const float* __restrict__ row, int stride) {
+  LensCamera lc{load_camera(row), 0.0f, false};
+  if (stride == 12) {
+    lc.k4 = row[9];
+    lc.fisheye = row[10] != 0.0f;
+  }
+  return lc;
+}
+
+// The camera-space unit direction of the distorted normalised point (xd, yd) of a fisheye row, all of it in fp64: theta solves
+// theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) = theta_d = |(xd, yd)| by Newton from theta_d, exactly 10 steps, none
+// skipped early, a step whose |derivative| <= 1e-12 leaves theta where it is; theta is clipped to [0, pi].
+__device__ __forceinline__ void fisheye_direction(const LensCamera& lc, double xd, double yd, double* v) {
+  const double k1 = lc.c.k1, k2 = lc.c.k2, k3 = lc.c.k3, k4 = lc.k4;
+  const double td = sqrt(xd * xd + yd * yd);
+  double th = td;
+#pragma unroll 1
+  for (int it = 0; it < 10; ++it) {
+    const double t2 = th * th;
+    const double f = th * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4)))) - td;
+    const double df = 1.0 + t2 * (3.0 * k1 + t2 * (5.0 * k2 + t2 * (7.0 * k3 + t2 * (9.0 * k4))));
+    if (fabs(df) > 1e-12) th -= f / df;
+  }
+  th = fmin(fmax(th, 0.0), 3.141592653589793);
+  if (td == 0.0) {
+    v[0] = 0.0, v[1] = 0.0, v[2] = -1.0;
+    return;
+  }
+  const double s = sin(th) / td;
+  v[0] = xd * s, v[1] = -(yd * s), v[2] = -cos(th);
+}
+
+// The ray of pixel (y, x) of a fisheye row: the centre and its x+1 / y+1 neighbours get their own solves; the neighbours' offsets
+// are differences of the solved directions, formed in fp64 and rounded to fp32 once.
+__device__ __forceinline__ void fisheye_ray(const float* __restrict__ c2w, const LensCamera& lc, int y, int x, float* o, float* d,
+                                            float* area) {
+  const double fx = lc.c.k.fx, fy = lc.c.k.fy, cx = lc.c.k.cx, cy = lc.c.k.cy;
+  const double xd0 = ((double)x + 0.5 - cx) / fx, yd0 = ((double)y + 0.5 - cy) / fy;
+  const double xd1 = ((double)x + 1.5 - cx) / fx, yd1 = ((double)y + 1.5 - cy) / fy;
+  double v0[3], vx[3], vy[3];
+  fisheye_direction(lc, xd0, yd0, v0);
+  fisheye_direction(lc, xd1, yd0, vx);
+  fisheye_direction(lc, xd0, yd1, vy);
+  float v[3], ex[3], ey[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    v[j] = (float)v0[j];
+    ex[j] = (float)(vx[j] - v0[j]);
+    ey[j] = (float)(vy[j] - v0[j]);
+  }
+  camera_ray_at3(c2w, v, ex, ey, o, d, area);
+}
+
+// The ray of pixel (y, x) of a row of either table: a perspective row runs capture_ray unchanged.
+__device__ __forceinline__ void lens_ray(const float* __restrict__ c2w, const LensCamera& lc, int y, int x, float* o, float* d,
+                                         float* area) {
+  if (lc.fisheye)
+    fisheye_ray(c2w, lc, y, x, o, d, area);
+  else
+    capture_ray(c2w, lc.c, y, x, o, d, area);
 }

@@ -2,6 +2,7 @@
 //   rsn_sample_camera_rays  Philox pixel sampler + pixel gather + camera ray generator, one thread per ray
 //   rsn_camera_rays_image   the same ray arithmetic for every pixel of one camera (rendering views)
 //   rsn_capture_rays_image  every pixel of one camera of a capture: a camera-table row with lens distortion (rsn_camera.h capture_ray)
+//   rsn_capture_rays_image2 the same for a row of 9 or 12 columns: a fisheye row takes the equidistant model (rsn_camera.h lens_ray)
 //   rsn_ssim                torchmetrics' structural_similarity_index_measure of two [H, W, 3] images, on the device
 // Recipes (Philox keying, ray arithmetic, SSIM definition): include/rsn.h.
 #include "rsn_camera.h"
@@ -75,6 +76,23 @@ __global__ __launch_bounds__(256) void rsn_capture_rays_image_kernel(int height,
   const int y = p / width, x = p - y * width;
   float o[3], d[3], area;
   capture_ray(c2w, load_camera(camera), y, x, o, d, &area);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    origins[3 * p + j] = o[j];
+    directions[3 * p + j] = d[j];
+  }
+  pixel_area[p] = area;
+}
+
+// a row of a 9- or 12-column table: a fisheye row takes fisheye_ray, any other capture_ray unchanged (rsn_camera.h lens_ray)
+__global__ __launch_bounds__(256) void rsn_capture_rays_image2_kernel(int height, int width, const float* c2w, const float* camera,
+                                                                      int camera_stride, float* origins, float* directions,
+                                                                      float* pixel_area) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= height * width) return;
+  const int y = p / width, x = p - y * width;
+  float o[3], d[3], area;
+  lens_ray(c2w, load_lens_camera(camera, camera_stride), y, x, o, d, &area);
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     origins[3 * p + j] = o[j];
@@ -233,6 +251,19 @@ extern "C" int rsn_capture_rays_image(int32_t height, int32_t width, const float
   const int n = height * width;
   hipLaunchKernelGGL(rsn_capture_rays_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      height, width, c2w, camera, origins, directions, pixel_area);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+extern "C" int rsn_capture_rays_image2(int32_t height, int32_t width, const float* c2w, const float* camera, int32_t camera_stride,
+                                       float* origins, float* directions, float* pixel_area, void* stream) {
+  RSN_REQUIRE(height >= 1 && width >= 1 && (int64_t)height * width <= 0x7fffffff, RSN_ERR_INVALID_ARGUMENT,
+              "height=%d width=%d", height, width);
+  RSN_REQUIRE(camera_stride == 9 || camera_stride == 12, RSN_ERR_INVALID_ARGUMENT, "camera_stride=%d: 9 or 12", camera_stride);
+  RSN_REQUIRE(c2w && camera && origins && directions && pixel_area, RSN_ERR_INVALID_ARGUMENT, "a pointer is NULL");
+  const int n = height * width;
+  hipLaunchKernelGGL(rsn_capture_rays_image2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     height, width, c2w, camera, camera_stride, origins, directions, pixel_area);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

@@ -2,6 +2,7 @@
 //   rsn_build_pyramid        levels 1 .. L-1 of every image as white-blended fp32 box averages of level 0, one lane per output pixel
 //   rsn_sample_pyramid_rays  Philox level + pixel sampler, pixel gather and camera ray generator, one lane per ray
 //   rsn_sample_capture_rays  the same sampler with a camera table: per-image intrinsics and lens distortion (rsn_camera.h capture_ray)
+//   rsn_sample_capture_rays_live  the same again with a 9- or 12-column table (fisheye rows) and the pixel drawn from live-pixel lists
 // Level 0 is the uint8 RGBA image set itself and is never copied.  Recipes: include/rsn.h.
 #include "rsn_camera.h"
 #include "rsn_common.h"
@@ -80,7 +81,10 @@ struct PyramidSampleArgs {
   const float* pyramid;   // [off[L], 3]; not read when levels == 1
   const float* c2w;       // [N, 3, 4]
   Intrinsics k;           // the one camera of all images (CAPTURE: not read)
-  const float* cameras;   // CAPTURE: the camera table [N, 9] (else not read)
+  const float* cameras;   // CAPTURE: the camera table [N, 9] (else not read); LIVE: [N, camera_stride]
+  int32_t camera_stride;  // LIVE: 9 or 12
+  const uint32_t* live;   // LIVE: the levels' live-pixel lists, or NULL: every pixel
+  const uint32_t* live_offsets;  // LIVE: [levels + 1], level l's list is live[live_offsets[l] .. live_offsets[l+1]) (not read without live)
   uint32_t seed, rank, step;
   float* origins;
   float* directions;
@@ -92,8 +96,11 @@ struct PyramidSampleArgs {
 };
 
 // CAPTURE: image i's camera is row i of a.cameras, and the ray comes from capture_ray, which is camera_ray for a row without
-// distortion.  Everything else -- the Philox draw, the gather, the blend, the outputs -- is one text for both.
-template <bool CAPTURE>
+// distortion.  LIVE: the flat pixel is drawn from the level's live-pixel list, the row has a.camera_stride columns and a fisheye row
+// takes fisheye_ray (rsn_camera.h lens_ray).  Everything else -- the Philox draw, the gather, the blend, the outputs -- is one text.
+enum SampleMode { PINHOLE = 0, CAPTURE = 1, LIVE = 2 };
+
+template <SampleMode MODE>
 __global__ __launch_bounds__(256) void rsn_sample_pyramid_rays_kernel(PyramidSampleArgs a) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.n_rays) return;
@@ -101,13 +108,23 @@ __global__ __launch_bounds__(256) void rsn_sample_pyramid_rays_kernel(PyramidSam
   const int l = (int)(((uint64_t)rnd.y * (uint32_t)a.levels) >> 32);
   const uint32_t wl = (uint32_t)(a.width >> l), hw = (uint32_t)(a.height >> l) * wl;
   const uint32_t total = hw * (uint32_t)a.n_images;  // < 2^32 (checked by the host for level 0, the largest)
-  const uint32_t flat = (uint32_t)(((uint64_t)rnd.x * total) >> 32);
+  uint32_t flat = (uint32_t)(((uint64_t)rnd.x * total) >> 32);
+  if (MODE == LIVE && a.live) {
+    const uint32_t first = a.live_offsets[l], count = a.live_offsets[l + 1] - first;
+    // a level without a live pixel is the caller's error (the data manager refuses it): pixel 0 then, and never a read outside
+    // `live`; the clamp keeps a list that is not one of this image set from indexing outside the images
+    flat = count ? min(a.live[first + (uint32_t)(((uint64_t)rnd.x * count) >> 32)], total - 1u) : 0u;
+  }
   const int i = (int)(flat / hw);
   const uint32_t rem = flat - (uint32_t)i * hw;
   const int y = (int)(rem / wl), x = (int)(rem - (uint32_t)y * wl);
   const float inv = 1.0f / (float)(1 << l);  // a power of two: the level's intrinsics are exact
   float o[3], d[3], area;
-  if (CAPTURE) {  // the coefficients act on normalised coordinates: a level changes the four intrinsics only
+  if (MODE == LIVE) {
+    LensCamera lc = load_lens_camera(a.cameras + (size_t)i * (size_t)a.camera_stride, a.camera_stride);
+    lc.c.k = Intrinsics{lc.c.k.fx * inv, lc.c.k.fy * inv, lc.c.k.cx * inv, lc.c.k.cy * inv};
+    lens_ray(a.c2w + (size_t)i * 12, lc, y, x, o, d, &area);
+  } else if (MODE == CAPTURE) {  // the coefficients act on normalised coordinates: a level changes the four intrinsics only
     Camera c = load_camera(a.cameras + (size_t)i * 9);
     c.k = Intrinsics{c.k.fx * inv, c.k.fy * inv, c.k.cx * inv, c.k.cy * inv};
     capture_ray(a.c2w + (size_t)i * 12, c, y, x, o, d, &area);
@@ -158,13 +175,20 @@ int check_pyramid_shape(int32_t n_images, int32_t height, int32_t width, int32_t
   return RSN_OK;
 }
 
-// both samplers: the checks, the level table, one launch.  capture: the camera table `cameras`, else the shared pinhole k
+// all samplers: the checks, the level table, one launch.  CAPTURE and LIVE: the camera table `cameras`, else the shared pinhole k;
+// LIVE: the table's stride and the live-pixel lists
 int sample_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images, const float* pyramid,
-                size_t pyramid_pixels, const float* c2w, bool capture, Intrinsics k, const float* cameras, int32_t n_rays,
+                size_t pyramid_pixels, const float* c2w, SampleMode mode, Intrinsics k, const float* cameras, int32_t camera_stride,
+                const uint32_t* live, const uint32_t* live_offsets, int32_t n_rays,
                 uint32_t seed, uint32_t rank, uint32_t step, float* origins, float* directions, float* pixel_area, float* rgb, int32_t* indices,
                 int32_t* level, void* stream) {
   RSN_TRY(check_pyramid_shape(n_images, height, width, levels));
   RSN_REQUIRE(n_rays >= 0, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d", n_rays);
+  const bool capture = mode != PINHOLE;
+  RSN_REQUIRE(mode != LIVE || camera_stride == 9 || camera_stride == 12, RSN_ERR_INVALID_ARGUMENT, "camera_stride=%d: 9 or 12",
+              camera_stride);
+  RSN_REQUIRE(!live || (live_offsets && (((uintptr_t)live | (uintptr_t)live_offsets) & 3u) == 0), RSN_ERR_INVALID_ARGUMENT,
+              "live needs live_offsets, both 4-byte aligned");
   RSN_REQUIRE(capture || (k.fx != 0.0f && k.fy != 0.0f), RSN_ERR_INVALID_ARGUMENT, "fx=%g fy=%g", (double)k.fx, (double)k.fy);
   if (n_rays == 0) return RSN_OK;
   RSN_REQUIRE(images && c2w && origins && directions && pixel_area && rgb && indices && (level || (capture && levels == 1)) &&
@@ -174,13 +198,15 @@ int sample_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels,
   const LevelTable t = level_table(n_images, height, width, levels);
   RSN_REQUIRE(pyramid_pixels >= t.off[levels], RSN_ERR_INVALID_ARGUMENT, "pyramid of %zu pixels, %u needed", pyramid_pixels,
               t.off[levels]);
-  PyramidSampleArgs a{n_images, height, width, levels, n_rays, images, pyramid, c2w, k, cameras,
+  PyramidSampleArgs a{n_images, height, width, levels, n_rays, images, pyramid, c2w, k, cameras, camera_stride, live, live_offsets,
                       seed, rank, step, origins, directions, pixel_area, rgb, indices, level, t};
   const dim3 grid((unsigned)((n_rays + 255) / 256));
-  if (capture)
-    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  if (mode == LIVE)
+    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<LIVE>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else if (mode == CAPTURE)
+    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<CAPTURE>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rsn_sample_pyramid_rays_kernel<PINHOLE>, grid, dim3(256), 0, (hipStream_t)stream, a);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }
@@ -207,8 +233,8 @@ extern "C" int rsn_sample_pyramid_rays(int32_t n_images, int32_t height, int32_t
                                        int32_t n_rays, uint32_t seed, uint32_t rank, uint32_t step, float* origins,
                                        float* directions, float* pixel_area, float* rgb, int32_t* indices, int32_t* level,
                                        void* stream) {
-  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, false, Intrinsics{fx, fy, cx, cy}, nullptr,
-                     n_rays, seed, rank, step, origins, directions, pixel_area, rgb, indices, level, stream);
+  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, PINHOLE, Intrinsics{fx, fy, cx, cy}, nullptr,
+                     0, nullptr, nullptr, n_rays, seed, rank, step, origins, directions, pixel_area, rgb, indices, level, stream);
 }
 
 extern "C" int rsn_sample_capture_rays(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images,
@@ -216,6 +242,16 @@ extern "C" int rsn_sample_capture_rays(int32_t n_images, int32_t height, int32_t
                                        int32_t n_rays, uint32_t seed, uint32_t rank, uint32_t step, float* origins,
                                        float* directions, float* pixel_area, float* rgb, int32_t* indices, int32_t* level,
                                        void* stream) {
-  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, true, Intrinsics{}, cameras, n_rays,
+  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, CAPTURE, Intrinsics{}, cameras, 9, nullptr,
+                     nullptr, n_rays,
                      seed, rank, step, origins, directions, pixel_area, rgb, indices, level, stream);
+}
+
+extern "C" int rsn_sample_capture_rays_live(int32_t n_images, int32_t height, int32_t width, int32_t levels, const uint8_t* images,
+                                            const float* pyramid, size_t pyramid_pixels, const float* c2w, const float* cameras,
+                                            int32_t camera_stride, const uint32_t* live, const uint32_t* live_offsets, int32_t n_rays,
+                                            uint32_t seed, uint32_t rank, uint32_t step, float* origins, float* directions,
+                                            float* pixel_area, float* rgb, int32_t* indices, int32_t* level, void* stream) {
+  return sample_rays(n_images, height, width, levels, images, pyramid, pyramid_pixels, c2w, LIVE, Intrinsics{}, cameras, camera_stride,
+                     live, live_offsets, n_rays, seed, rank, step, origins, directions, pixel_area, rgb, indices, level, stream);
 }

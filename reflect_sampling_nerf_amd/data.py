@@ -15,6 +15,11 @@ OpenCV radial and tangential distortion, JPEG or PNG images, nerfstudio's pose n
 carries a camera table (`cameras` [N,9]); with one, RayDataManager uploads the table once and draws its batches with
 rsn_sample_capture_rays and its views with rsn_capture_rays_image (include/rsn.h, "captures"): distorted rays are made on the
 device, one launch, no host read.  Without a table every call is the one it always was.
+
+Opt-in arguments of `load_nerfstudio_split` read what a real ns-process-data directory also holds: masks (scene.masks; the data
+manager then builds per-level live-pixel lists on the device, rsn_build_live_pixels, and draws only from them), OPENCV_FISHEYE
+cameras (a 12-column table whose fisheye rows go through the equidistant model on the device) and the images_K directories of a
+downscale factor.  A scene with neither masks nor a 12-column table makes the calls it made before.
 """
 from __future__ import annotations
 
@@ -40,7 +45,10 @@ class BlenderScene:
     cameras: None (the shared pinhole above, and nothing else changes), or the camera table of a capture, float32 [N,9] with row i =
     (fx, fy, cx, cy, k1, k2, k3, p1, p2) of image i (include/rsn.h, "captures"); fx .. cy then repeat row 0's pinhole part, for the
     callers that want one representative camera (an orbit's field of view, the occupancy box).  dataparser_transform [3,4] float64 and
-    dataparser_scale: what load_nerfstudio_split applied to the file's poses (None for other sources); file_paths: the frames' names."""
+    dataparser_scale: what load_nerfstudio_split applied to the file's poses (None for other sources); file_paths: the frames' names.
+
+    A table of 12 columns (LENS_CAMERA_COLUMNS) holds fisheye rows: k4, the model (0 perspective, 1 OpenCV fisheye) and a zero follow
+    the nine.  masks: None, or uint8 [N,H,W] of 0 / 1: 1 = the pixel is live, it may be drawn into a training batch."""
 
     images: np.ndarray
     c2w: np.ndarray
@@ -53,6 +61,7 @@ class BlenderScene:
     dataparser_transform: Optional[np.ndarray] = None
     dataparser_scale: Optional[float] = None
     file_paths: Optional[List[str]] = None
+    masks: Optional[np.ndarray] = None
 
     @property
     def num_images(self) -> int:
@@ -67,10 +76,10 @@ class BlenderScene:
         return int(self.images.shape[2])
 
     @classmethod
-    def from_arrays(cls, images, c2w, focal: float, cx=None, cy=None, normals=None) -> "BlenderScene":
+    def from_arrays(cls, images, c2w, focal: float, cx=None, cy=None, normals=None, masks=None) -> "BlenderScene":
         """images [N,H,W,3|4] (uint8, or float in [0, 1] rounded to uint8), c2w [N,3,4] or [N,4,4]; fx = fy = focal,
         principal point at the image centre unless given.  normals: None, or [N,H,W,3] normal maps -- uint8 taken as is, float unit
-        vectors encoded as rint((n * 0.5 + 0.5) * 255) clipped to 0..255."""
+        vectors encoded as rint((n * 0.5 + 0.5) * 255) clipped to 0..255.  masks: None, or [N,H,W], non-zero = live (stored as 0 / 1)."""
         im = np.asarray(images.cpu() if isinstance(images, torch.Tensor) else images)
         if im.ndim != 4 or im.shape[-1] not in (3, 4):
             raise ValueError(f"images must be [N,H,W,3|4], got {im.shape}")
@@ -90,8 +99,15 @@ class BlenderScene:
             if nm.dtype != np.uint8:
                 nm = np.clip(np.rint((nm.astype(np.float64) * 0.5 + 0.5) * 255.0), 0, 255).astype(np.uint8)
             nm = np.ascontiguousarray(nm)
+        mk = None
+        if masks is not None:
+            mk = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+            if mk.shape != im.shape[:3]:
+                raise ValueError(f"masks must be [N,H,W] = {im.shape[:3]}, got {mk.shape}")
+            mk = np.ascontiguousarray((mk != 0).astype(np.uint8))
         return cls(images=np.ascontiguousarray(im), c2w=np.ascontiguousarray(pose[:, :3, :4]), fx=float(focal),
-                   fy=float(focal), cx=float(W / 2.0 if cx is None else cx), cy=float(H / 2.0 if cy is None else cy), normals=nm)
+                   fy=float(focal), cx=float(W / 2.0 if cx is None else cx), cy=float(H / 2.0 if cy is None else cy), normals=nm,
+                   masks=mk)
 
 
 def load_blender_split(root: str, split: str, scale_factor: float = 1.0, normals: bool = False,
@@ -149,7 +165,9 @@ def load_blender_split(root: str, split: str, scale_factor: float = 1.0, normals
 
 # ------------------------------------------------------------------------------------------------ captures (nerfstudio format)
 CAMERA_COLUMNS = ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2")  # a row of the camera table (include/rsn.h, "captures")
+LENS_CAMERA_COLUMNS = CAMERA_COLUMNS + ("k4", "model", "pad")  # a row of a table with fisheye rows; model: 0 perspective, 1 fisheye
 CAPTURE_CAMERA_MODELS = (None, "OPENCV", "PINHOLE")
+FISHEYE_CAMERA_MODEL = "OPENCV_FISHEYE"
 ORIENTATIONS = ("up", "none")
 CENTERS = ("poses", "none")
 EVAL_MODES = ("fraction", "all")
@@ -205,6 +223,50 @@ def undistort_residual(row, height: int, width: int) -> float:
         bx, by = distort_points(row, X, Y)
         res = np.maximum(np.abs(bx - Xd), np.abs(by - Yd))
     return float(res.max()) if np.all(np.isfinite(res)) else math.inf
+
+
+def fisheye_forward(row, theta):
+    """OpenCV's equidistant fisheye model of include/rsn.h ("captures: masks and fisheye lenses") in float64: the angle theta from the
+    optical axis -> theta_d, the distorted radius in normalised image units.  row: a 12-column row (k1, k2, k3 and k4 are read)."""
+    k1, k2, k3, k4 = float(row[4]), float(row[5]), float(row[6]), float(row[9])
+    t = np.asarray(theta, dtype=np.float64)
+    t2 = t * t
+    return t * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+
+
+def fisheye_solve(row, theta_d, iterations: int = UNDISTORT_ITERATIONS):
+    """The kernel's solve in float64, before its clip to [0, pi]: Newton from theta = theta_d, `iterations` steps, none skipped early;
+    a step whose |derivative| <= 1e-12 leaves theta where it is."""
+    k1, k2, k3, k4 = float(row[4]), float(row[5]), float(row[6]), float(row[9])
+    td = np.asarray(theta_d, dtype=np.float64)
+    th = td.copy()
+    for _ in range(iterations):
+        t2 = th * th
+        f = th * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4)))) - td
+        df = 1.0 + t2 * (3.0 * k1 + t2 * (5.0 * k2 + t2 * (7.0 * k3 + t2 * (9.0 * k4))))
+        ok = np.abs(df) > 1e-12
+        th = np.where(ok, th - f / np.where(ok, df, 1.0), th)
+    return th
+
+
+def fisheye_residual(row, height: int, width: int) -> float:
+    """undistort_residual for a fisheye row: the largest |forward(solve(theta_d)) - theta_d| at the four corners and four edge
+    midpoints of the outermost pixel centres.  inf when a solve left the finite numbers or [0, pi], or when theta_d is not strictly
+    increasing in theta up to the largest solved angle (256 steps): the image then folds inside its border, and a pixel has two rays."""
+    fx, fy, cx, cy = (float(v) for v in row[:4])
+    xs = np.array([0.5, 0.5 * width, width - 0.5], dtype=np.float64)
+    ys = np.array([0.5, 0.5 * height, height - 0.5], dtype=np.float64)
+    px, py = (a.ravel() for a in np.meshgrid(xs, ys))
+    keep = ~((px == xs[1]) & (py == ys[1]))  # not the centre
+    td = np.hypot((px[keep] - cx) / fx, (py[keep] - cy) / fy)
+    with np.errstate(all="ignore"):
+        th = fisheye_solve(row, td)
+        res = np.abs(fisheye_forward(row, th) - td)
+        if not (np.all(np.isfinite(res)) and np.all(np.isfinite(th)) and np.all(th >= 0.0) and np.all(th <= math.pi)):
+            return math.inf
+        if np.any(np.diff(fisheye_forward(row, np.linspace(0.0, float(th.max()), 257))) <= 0.0):
+            return math.inf
+    return float(res.max())
 
 
 def rotation_onto_z(up) -> np.ndarray:
@@ -284,7 +346,8 @@ def write_dataparser_transforms(path: str, transform, scale: float) -> None:
 
 def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orientation: str = "up", center: str = "poses",
                           auto_scale: bool = True, train_split_fraction: float = 0.9, eval_mode: str = "fraction",
-                          applied: Optional[Tuple[Sequence, float]] = None, pixels: bool = True) -> BlenderScene:
+                          applied: Optional[Tuple[Sequence, float]] = None, pixels: bool = True, masks: bool = False,
+                          fisheye: bool = False, downscale_factor: int = 1) -> BlenderScene:
     """One split of a nerfstudio-format capture, root/transforms.json, as nerfstudio's NerfstudioDataParser reads it; -> a scene
     with a camera table.  All arithmetic on the host in float64, rounded once to float32.
 
@@ -301,7 +364,19 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
     ValueError, naming the frame: another camera_model (OPENCV_FISHEYE, ...), a non-zero k4, a mask_path, images of differing
     sizes, a w / h that disagrees with the file, and a coefficient set whose solve does not converge over the image (residual above
     1e-9 at the corners and edge midpoints: the model is not invertible there; the kernels do not check).  FileNotFoundError for a
-    missing image.  downscale_factor / images_K directories, masks, fisheye and equirectangular cameras are not supported."""
+    missing image.  Masks, fisheye cameras and a non-zero k4 are refused in the same way unless the arguments below ask for them;
+    images of differing sizes and equirectangular cameras always are.
+
+    masks=True: a frame's mask_path (relative to the JSON, read through Pillow) says which of its pixels are live: those whose first
+    channel is non-zero, nerfstudio's rule for its single-channel masks; a frame without one is all live.  scene.masks is uint8
+    [N,H,W] of 0 / 1, or None when no kept frame has a mask (and with pixels=False).  ValueError naming the frame for a mask of
+    another size than its image, FileNotFoundError naming the file for a missing one.
+    fisheye=True: camera_model OPENCV_FISHEYE (k1 .. k4; p1 and p2 must be 0) is accepted, and k4 with it (a perspective row must
+    keep k4 = 0).  When a kept frame is a fisheye one the table has 12 columns, LENS_CAMERA_COLUMNS; else the 9 it always had.  The
+    invertibility check of a fisheye row is fisheye_residual, against the same 1e-9.
+    downscale_factor=K > 1, nerfstudio's rule: images/frame.png is read from images_K/frame.png (the parent directory's name gets
+    _K; a mask_path likewise), fl_x, fl_y, cx, cy are divided by K, and a declared w, h must be the file's size times K up to the
+    truncation of w // K, h // K.  FileNotFoundError naming the directory when it is missing: nothing is resampled here."""
     from PIL import Image
 
     meta_path = os.path.join(root, "transforms.json")
@@ -319,22 +394,49 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
             raise ValueError(f"{meta_path}: frame {fr['file_path']} has no {key}, and the file has no global one")
         return v
 
-    rows, poses = [], []
+    K = int(downscale_factor)
+    if K < 1 or K != downscale_factor:
+        raise ValueError(f"downscale_factor = {downscale_factor}: need an integer >= 1")
+
+    def on_disk(rel):  # nerfstudio: images/frame.png -> images_K/frame.png
+        if K == 1:
+            return os.path.join(root, rel)
+        parent, base = os.path.split(rel)
+        if not parent:
+            raise ValueError(f"{meta_path}: {rel} lies in no directory whose name could get _{K} (downscale_factor = {K})")
+        scaled = os.path.join(root, parent + f"_{K}")
+        if not os.path.isdir(scaled):
+            raise FileNotFoundError(f"{scaled}: no such directory; downscale_factor = {K} reads the {parent}_{K} that ns-process-data "
+                                    "writes beside it, and nothing is resampled here")
+        return os.path.join(scaled, base)
+
+    rows, poses, fish, k4s = [], [], [], []
     for fr in frames:
         name = fr["file_path"]
         model = fr.get("camera_model", meta.get("camera_model"))
-        if model not in CAPTURE_CAMERA_MODELS:
+        fish.append(bool(fisheye) and model == FISHEYE_CAMERA_MODEL)
+        if model not in CAPTURE_CAMERA_MODELS and not fish[-1]:
             raise ValueError(f"{meta_path}: frame {name}: camera_model {model!r} is not supported (OPENCV, PINHOLE or absent)")
-        if float(fr.get("k4", meta.get("k4", 0.0)) or 0.0) != 0.0:
+        k4s.append(float(fr.get("k4", meta.get("k4", 0.0)) or 0.0))
+        if k4s[-1] != 0.0 and not fisheye:
             raise ValueError(f"{meta_path}: frame {name}: k4 = {fr.get('k4', meta.get('k4'))} is not zero; the model here has k1, k2, k3, p1, p2")
-        if "mask_path" in fr:
+        if k4s[-1] != 0.0 and not fish[-1]:
+            raise ValueError(f"{meta_path}: frame {name}: k4 = {k4s[-1]} is not zero, and its camera_model {model!r} is a perspective "
+                             "one; only OPENCV_FISHEYE has a k4")
+        if "mask_path" in fr and not masks:
             raise ValueError(f"{meta_path}: frame {name} has a mask_path; masks are not supported")
         rows.append([float(value(fr, "fl_x")), float(value(fr, "fl_y")), float(value(fr, "cx")), float(value(fr, "cy"))]
                     + [float(value(fr, k, 0.0)) for k in CAMERA_COLUMNS[4:]])
         if rows[-1][0] == 0.0 or rows[-1][1] == 0.0:
             raise ValueError(f"{meta_path}: frame {name}: fl_x = {rows[-1][0]}, fl_y = {rows[-1][1]}: a focal length is zero")
+        if fish[-1] and (rows[-1][7] != 0.0 or rows[-1][8] != 0.0):
+            raise ValueError(f"{meta_path}: frame {name}: p1 = {rows[-1][7]}, p2 = {rows[-1][8]}: an OPENCV_FISHEYE camera has k1 .. k4 "
+                             "and no tangential terms")
         poses.append(np.asarray(fr["transform_matrix"], dtype=np.float64)[:3, :4])
     rows64, poses = np.asarray(rows, dtype=np.float64), np.stack(poses)
+    if K > 1:
+        rows64[:, :4] /= float(K)
+    lens64 = np.concatenate([rows64, np.asarray(k4s)[:, None], np.asarray(fish, dtype=np.float64)[:, None], np.zeros((len(rows), 1))], axis=1)
     if applied is None:
         poses, transform = auto_orient_and_center_poses(poses, orientation, center)
         scale = float(scale_factor)
@@ -350,10 +452,11 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
     if len(keep) == 0:
         raise ValueError(f"{meta_path}: the {split} split of {len(frames)} frames at train_split_fraction {train_split_fraction} is empty")
     images, size = [], None
+    live = {}  # position among the kept frames -> uint8 [H,W]
     checked = {}
     for i in keep:
         fr, name = frames[i], frames[i]["file_path"]
-        path = os.path.join(root, name)
+        path = on_disk(name)
         if not os.path.isfile(path):
             raise FileNotFoundError(f"{path}: image of frame {name} of {meta_path} not found")
         with Image.open(path) as img:
@@ -367,28 +470,54 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
             raise ValueError(f"{meta_path}: frame {name} is {im.shape[1]} x {im.shape[0]} pixels, the split's first image "
                              f"{size[1]} x {size[0]}; images of differing sizes are not supported")
         w, h = fr.get("w", meta.get("w")), fr.get("h", meta.get("h"))
-        if (w is not None and int(w) != im.shape[1]) or (h is not None and int(h) != im.shape[0]):
-            raise ValueError(f"{meta_path}: frame {name}: w x h = {w} x {h}, but the file holds {im.shape[1]} x {im.shape[0]} pixels")
-        key = rows64[i].tobytes()
-        if key not in checked and np.any(rows64[i, 4:] != 0.0):
+        if (w is not None and int(w) // K != im.shape[1]) or (h is not None and int(h) // K != im.shape[0]):
+            raise ValueError(f"{meta_path}: frame {name}: w x h = {w} x {h}, but the file holds {im.shape[1]} x {im.shape[0]} pixels"
+                             + ("" if K == 1 else f" (downscale_factor = {K}: {int(w) // K} x {int(h) // K} expected)"))
+        if masks and "mask_path" in fr:
+            mpath = on_disk(fr["mask_path"])
+            if not os.path.isfile(mpath):
+                raise FileNotFoundError(f"{mpath}: mask of frame {name} of {meta_path} not found")
+            with Image.open(mpath) as img:
+                if (img.size[1], img.size[0]) != tuple(im.shape[:2]):
+                    raise ValueError(f"{meta_path}: frame {name}: its mask {fr['mask_path']} is {img.size[0]} x {img.size[1]} pixels, "
+                                     f"the image {im.shape[1]} x {im.shape[0]}; a frame's mask must have its image's size")
+                if pixels:
+                    mk = np.asarray(img)
+                    live[len(images)] = ((mk if mk.ndim == 2 else mk[..., 0]) != 0).astype(np.uint8)
+        key = lens64[i].tobytes()
+        if fish[i]:
+            if key not in checked:
+                checked[key] = fisheye_residual(lens64[i], im.shape[0], im.shape[1])
+                if not checked[key] <= UNDISTORT_MAX_RESIDUAL:
+                    raise ValueError(f"{meta_path}: frame {name}: the fisheye model (k1, k2, k3, k4) = {tuple(lens64[i, [4, 5, 6, 9]])} is "
+                                     f"not invertible over the {im.shape[1]} x {im.shape[0]} image: {UNDISTORT_ITERATIONS} Newton steps leave "
+                                     f"a residual of {checked[key]:.3g} at its border (at most {UNDISTORT_MAX_RESIDUAL:g}; inf: theta "
+                                     "beyond pi, or an image that folds inside its border)")
+        elif key not in checked and np.any(rows64[i, 4:] != 0.0):
             checked[key] = undistort_residual(rows64[i], im.shape[0], im.shape[1])
             if not checked[key] <= UNDISTORT_MAX_RESIDUAL:
                 raise ValueError(f"{meta_path}: frame {name}: the distortion model (k1, k2, k3, p1, p2) = {tuple(rows64[i, 4:])} is not "
                                  f"invertible over the {im.shape[1]} x {im.shape[0]} image: {UNDISTORT_ITERATIONS} Newton steps leave a "
                                  f"residual of {checked[key]:.3g} at its border (at most {UNDISTORT_MAX_RESIDUAL:g})")
         images.append(im)
-    cams = np.ascontiguousarray(rows64[keep].astype(np.float32))
+    cams = np.ascontiguousarray((lens64 if np.any(np.asarray(fish)[keep]) else rows64)[keep].astype(np.float32))
+    mask_stack = None
+    if live:
+        mask_stack = np.ones((len(images),) + tuple(size), np.uint8)
+        for at, mk in live.items():
+            mask_stack[at] = mk
     stack = np.ascontiguousarray(np.stack(images)) if pixels else np.broadcast_to(np.zeros(1, np.uint8), (len(images),) + images[0].shape)
     return BlenderScene(images=stack, c2w=np.ascontiguousarray(poses[keep].astype(np.float32)),
                         fx=float(cams[0, 0]), fy=float(cams[0, 1]), cx=float(cams[0, 2]), cy=float(cams[0, 3]), cameras=cams,
-                        dataparser_transform=transform, dataparser_scale=scale, file_paths=[frames[i]["file_path"] for i in keep])
+                        dataparser_transform=transform, dataparser_scale=scale, file_paths=[frames[i]["file_path"] for i in keep],
+                        masks=mask_stack)
 
 
 def shared_pinhole(scene: BlenderScene, what: str) -> Tuple[float, float, float, float]:
     """(fx, fy, cx, cy) for a caller that projects through ONE pinhole camera (the TSDF and point-cloud exports): the scene's own,
     or a camera table's when all its rows are equal and free of distortion.  ValueError naming `what` otherwise."""
     cams = scene.cameras
-    if cams is not None and (np.any(cams[:, 4:] != 0.0) or np.any(cams != cams[0])):
+    if cams is not None and (np.any(cams[:, 4:] != 0.0) or np.any(cams != cams[0])):  # a fisheye row has model = 1 in column 10
         raise ValueError(f"{what} projects through one shared pinhole camera: it accepts a capture only when all its cameras are equal "
                          "and free of lens distortion, and this one's are not")
     return scene.fx, scene.fy, scene.cx, scene.cy
@@ -428,9 +557,16 @@ class RayDataManager:
 
     A scene with a camera table (scene.cameras, a capture): the table is uploaded once, per level with the four intrinsics over 2^l,
     and next_train / camera_ray_bundle go through rsn_sample_capture_rays / rsn_capture_rays_image at every level count.  Without a
-    table they make the calls they always made."""
+    table they make the calls they always made.
 
-    def __init__(self, scene: BlenderScene, device, num_rays_per_batch: int = 1024, seed: int = 0, rank: int = 0, levels: int = 1):
+    A scene with masks: the per-level lists of live pixels (include/rsn.h, "captures: masks and fisheye lenses") are built on the
+    device at construction -- counted, the counts read once, allocated exactly, filled -- and next_train draws only from them;
+    ValueError for a level without a live pixel; live_lists=False uploads the masks and builds no lists (eval draws no batches, and
+    next_train then draws from every pixel).  With masks or a 12-column table next_train goes through
+    rsn_sample_capture_rays_live and the views through rsn_capture_rays_image2; still one launch and no host read per call."""
+
+    def __init__(self, scene: BlenderScene, device, num_rays_per_batch: int = 1024, seed: int = 0, rank: int = 0, levels: int = 1,
+                 live_lists: bool = True):
         self.levels = int(levels)
         self.level_sizes, self.level_offsets = pyramid_layout(scene.num_images, scene.height, scene.width, self.levels)  # raises first
         self.scene = scene
@@ -446,9 +582,10 @@ class RayDataManager:
         self.cameras = None  # fp32 [levels, N, 9]: level l's table has fx, fy, cx, cy over 2^l (exact), the coefficients as they are
         if scene.cameras is not None:
             cams = np.ascontiguousarray(scene.cameras, dtype=np.float32)
-            if cams.shape != (scene.num_images, len(CAMERA_COLUMNS)):
-                raise ValueError(f"cameras must be [{scene.num_images},{len(CAMERA_COLUMNS)}], got {cams.shape}")
-            scale = np.ones((self.levels, 1, len(CAMERA_COLUMNS)), np.float32)
+            if cams.shape not in ((scene.num_images, len(CAMERA_COLUMNS)), (scene.num_images, len(LENS_CAMERA_COLUMNS))):
+                raise ValueError(f"cameras must be [{scene.num_images},{len(CAMERA_COLUMNS)}] (or {len(LENS_CAMERA_COLUMNS)} columns, with "
+                                 f"fisheye rows), got {cams.shape}")
+            scale = np.ones((self.levels, 1, cams.shape[1]), np.float32)
             scale[:, 0, :4] = (0.5 ** np.arange(self.levels, dtype=np.float32))[:, None]
             self.cameras = torch.from_numpy(cams[None] * scale).to(self.device)
         self._lib = _abi.load_library()
@@ -457,6 +594,39 @@ class RayDataManager:
             self.pyramid = torch.empty(self.level_offsets[-1], 3, device=self.device, dtype=torch.float32)
             _abi.check(self._lib.rsn_build_pyramid(scene.num_images, scene.height, scene.width, self.levels, _abi.ptr(self.images),
                                                    _abi.ptr(self.pyramid), self.pyramid.shape[0], self._stream()))
+        self.masks = None  # uint8 [N,H,W] of 0 / 1
+        self.live = self.live_offsets = self.live_counts = None  # the lists (uint32 bits in int32 tensors), [levels+1] offsets; host counts
+        if scene.masks is not None and live_lists:
+            self._build_live_pixels(scene)
+        elif scene.masks is not None:  # a caller that draws no batches (eval): the masks alone, for mask_image
+            self.masks = torch.from_numpy(np.ascontiguousarray(scene.masks, dtype=np.uint8)).to(self.device)
+
+    def _build_live_pixels(self, scene: BlenderScene) -> None:
+        mk = np.ascontiguousarray(scene.masks, dtype=np.uint8)
+        if mk.shape != (scene.num_images, scene.height, scene.width):
+            raise ValueError(f"masks must be [{scene.num_images},{scene.height},{scene.width}], got {mk.shape}")
+        if self.cameras is None:  # the masked sampler reads a table: the shared pinhole as N equal rows without distortion (the same bits)
+            row = np.float32([scene.fx, scene.fy, scene.cx, scene.cy, 0, 0, 0, 0, 0])
+            scale = np.ones((self.levels, 1, len(CAMERA_COLUMNS)), np.float32)
+            scale[:, 0, :4] = (0.5 ** np.arange(self.levels, dtype=np.float32))[:, None]
+            self.cameras = torch.from_numpy(np.tile(row, (scene.num_images, 1))[None] * scale).to(self.device)
+        self.masks = torch.from_numpy(mk).to(self.device)
+        shape = (scene.num_images, scene.height, scene.width, self.levels)
+        ws = torch.empty(max(1, self._lib.rsn_live_pixels_workspace_bytes(*shape) // 4), device=self.device, dtype=torch.int32)
+        counts = torch.zeros(self.levels, device=self.device, dtype=torch.int32)
+        _abi.check(self._lib.rsn_build_live_pixels(*shape, _abi.ptr(self.masks), None, 0, _abi.ptr(counts), _abi.ptr(ws),
+                                                   ws.numel() * 4, self._stream()))
+        host = counts.cpu().numpy().view(np.uint32).astype(np.int64)  # the one host read, at construction
+        for l, c in enumerate(host):
+            if c == 0:
+                raise ValueError(f"the masks leave no live pixel at level {l} of {self.levels} (a level-l pixel is live when all "
+                                 f"{1 << l} x {1 << l} pixels under it are): nothing could be drawn there")
+        self.live_counts = tuple(int(c) for c in host)
+        self.live = torch.empty(int(host.sum()), device=self.device, dtype=torch.int32)
+        _abi.check(self._lib.rsn_build_live_pixels(*shape, _abi.ptr(self.masks), _abi.ptr(self.live), self.live.numel(), _abi.ptr(counts),
+                                                   _abi.ptr(ws), ws.numel() * 4, self._stream()))
+        offsets = np.concatenate([[0], np.cumsum(host)]).astype(np.uint32).view(np.int32)
+        self.live_offsets = torch.from_numpy(offsets).to(self.device)
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -476,6 +646,14 @@ class RayDataManager:
             if multi:
                 both = idx.view(-1)
                 idx, lvl = both[:3 * R].view(R, 3), both[3 * R:]
+            if self.live is not None or self.cameras.shape[-1] != len(CAMERA_COLUMNS):
+                _abi.check(self._lib.rsn_sample_capture_rays_live(
+                    s.num_images, s.height, s.width, self.levels, _abi.ptr(self.images), _abi.ptr(self.pyramid),
+                    self.pyramid.shape[0] if multi else 0, _abi.ptr(self.c2w), _abi.ptr(self.cameras), self.cameras.shape[-1],
+                    _abi.ptr(self.live), _abi.ptr(self.live_offsets), R, self.seed, self.rank, int(step) & 0xFFFFFFFF, _abi.ptr(o),
+                    _abi.ptr(d), _abi.ptr(pa), _abi.ptr(rgb), _abi.ptr(idx), _abi.ptr(lvl), self._stream()))
+                rb = RayBundle(origins=o, directions=d, pixel_area=pa, camera_indices=idx[:, 0:1])
+                return rb, ({"image": rgb, "indices": idx, "levels": lvl} if multi else {"image": rgb, "indices": idx})
             _abi.check(self._lib.rsn_sample_capture_rays(
                 s.num_images, s.height, s.width, self.levels, _abi.ptr(self.images), _abi.ptr(self.pyramid),
                 self.pyramid.shape[0] if multi else 0, _abi.ptr(self.c2w), _abi.ptr(self.cameras), R, self.seed, self.rank,
@@ -532,6 +710,15 @@ class RayDataManager:
         h, w = self.level_sizes[level]
         first = self.level_offsets[level] + i * h * w
         return self.pyramid[first:first + h * w].view(h, w, 3)
+
+    def mask_image(self, i: int) -> torch.Tensor:
+        """The mask of camera i: uint8 [H,W] of 0 / 1 on the device (1 = live), a view of the one upload.  Level 0 only.  ValueError
+        when the scene has no masks."""
+        if self.masks is None:
+            raise ValueError("the scene has no masks (load_nerfstudio_split(..., masks=True) or from_arrays(..., masks=...))")
+        if not 0 <= i < self.scene.num_images:
+            raise IndexError(f"camera {i} of {self.scene.num_images}")
+        return self.masks[i]
 
     def normal_image(self, i: int) -> torch.Tensor:
         """Ground-truth normal map of camera i: uint8 [H,W,3] on the device, the bytes of the scene's normal image (n * 0.5 + 0.5);

@@ -157,7 +157,8 @@ def camera_rays(c2w, height: int, width: int, fx: float, fy: float, cx: float, c
     """The [H,W] RayBundle (origins, directions [H,W,3], pixel_area [H,W,1]; row-major) of the pinhole camera with pose c2w
     ([3,4] or [4,4]; a tensor on `device` is used where it lies, anything else is uploaded).  One launch, no host read.
     camera: None, or a camera row (fx, fy, cx, cy, k1, k2, k3, p1, p2) of a capture (include/rsn.h, "captures") -- nine numbers, or a
-    fp32 tensor [9] on `device`, used where it lies; the view then goes through rsn_capture_rays_image and fx .. cy are not read."""
+    fp32 tensor [9] on `device`, used where it lies; the view then goes through rsn_capture_rays_image and fx .. cy are not read.
+    A row of 12 numbers (fx fy cx cy k1 k2 k3 p1 p2 k4 model 0: a capture with fisheye cameras) goes through rsn_capture_rays_image2."""
     dev = torch.device(device)
     there = isinstance(c2w, torch.Tensor) and c2w.device.type == dev.type
     pose = c2w[:3, :4].to(torch.float32).contiguous() if there else _upload(torch.from_numpy(_poses(c2w)), dev)
@@ -170,8 +171,12 @@ def camera_rays(c2w, height: int, width: int, fx: float, fy: float, cx: float, c
         else:
             row = _upload(torch.from_numpy(np.ascontiguousarray(np.asarray(camera.cpu() if isinstance(camera, torch.Tensor) else camera,
                                                                          dtype=np.float32))), dev)
+        if tuple(row.shape) == (12,):
+            _abi.check(_abi.load_library().rsn_capture_rays_image2(H, W, _abi.ptr(pose), _abi.ptr(row), 12, _abi.ptr(o), _abi.ptr(d),
+                                                                   _abi.ptr(pa), _stream(dev)))
+            return RayBundle(origins=o, directions=d, pixel_area=pa)
         if tuple(row.shape) != (9,):
-            raise ValueError(f"camera must hold the 9 numbers fx fy cx cy k1 k2 k3 p1 p2, got shape {tuple(row.shape)}")
+            raise ValueError(f"camera must hold the 9 numbers fx fy cx cy k1 k2 k3 p1 p2 (or 12, with k4 model 0 behind them), got shape {tuple(row.shape)}")
         _abi.check(_abi.load_library().rsn_capture_rays_image(H, W, _abi.ptr(pose), _abi.ptr(row), _abi.ptr(o), _abi.ptr(d),
                                                               _abi.ptr(pa), _stream(dev)))
         return RayBundle(origins=o, directions=d, pixel_area=pa)
@@ -414,8 +419,8 @@ def render_path(model, c2w, height: int, width: int, fx: float, fy: float, cx: f
     table_dev = None
     if camera_table is not None:
         table = np.ascontiguousarray(camera_table, dtype=np.float32)
-        if table.shape != (F, 9):
-            raise ValueError(f"camera_table must be [{F},9], one row per pose, got {table.shape}")
+        if table.shape not in ((F, 9), (F, 12)):
+            raise ValueError(f"camera_table must be [{F},9] (or [{F},12] with fisheye rows), one row per pose, got {table.shape}")
         table_dev = _upload(torch.from_numpy(table), dev)
     panel_dev = torch.empty(shape, device=dev, dtype=torch.uint8)
     host = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(min(2, F))]

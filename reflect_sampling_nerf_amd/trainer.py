@@ -46,9 +46,12 @@ rendered in the frame it was trained in.  `render --data` on a capture renders t
 (--path orbit) goes through the first camera's pinhole part.  A capture's primary rays default to --near 0.05 --far 256
 --primary-spacing reciprocal --primary-tan 1 (s(t) = t / (1/T + t); far 256 is the far of the model's own reflected rays): starting
 points that have NOT been measured on a scene.  The four flags work on a Blender-format scene too, whose defaults stay 2, 6 and
-uniform with nothing recorded; what is recorded, every tool that opens the checkpoint applies.  Masks, images of differing sizes,
-fisheye cameras and a non-zero k4 are errors that name the frame; the TSDF and point-cloud exports take a capture only when all its
-cameras are equal and undistorted.
+uniform with nothing recorded; what is recorded, every tool that opens the checkpoint applies.  A frame's mask_path is read (first
+channel non-zero = live): a masked pixel is never drawn into a training batch, and `eval` adds psnr_masked, the PSNR over the live
+pixels, to the whole-image scores.  OPENCV_FISHEYE cameras (k1 .. k4) cast their rays through the equidistant model on the device.
+--downscale-factor K reads images_K/ and masks_K/ beside images/ with the intrinsics over K (recorded when K != 1; nothing is
+resampled).  Images of differing sizes and equirectangular cameras are errors that name the frame; the TSDF and point-cloud exports
+take a capture only when all its cameras are equal and undistorted.
 
 `train --multiscale L` and `eval --multiscale L` are mip-NeRF's multi-scale protocol (Barron et al. 2021) for L = 2 .. 5: every view
 also exists at 1/2 .. 1/2^(L-1) of its size, as box averages of the white-blended pixels built once on the device (data.py).  Training
@@ -225,6 +228,19 @@ def _add_data_flags(p: argparse.ArgumentParser, train: bool) -> None:
                    help=f"capture: the share of the frames, evenly spaced, that is trained on; the others are held out (default 0.9{whose})")
     p.add_argument("--eval-mode", choices=EVAL_MODES, default=None,
                    help=f"capture: fraction, or all: train and evaluate on every frame (default fraction{whose})")
+    p.add_argument("--downscale-factor", type=_downscale_factor, default=None, metavar="K",
+                   help="capture: read images_K/ (and masks_K/) beside images/, as ns-process-data writes them, with the intrinsics "
+                        f"over K; nothing is resampled (default 1{whose})")
+
+
+def _downscale_factor(text: str) -> int:
+    try:
+        k = int(text)
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: an integer >= 1")
+    return k
 
 
 def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
@@ -425,6 +441,11 @@ def capture_load_args(args, recorded: Optional[dict] = None):
              "scale_factor": None if isinstance(args.scale_factor, _NotGiven) else float(args.scale_factor), "train_split_fraction": args.train_split_fraction, "eval_mode": args.eval_mode}
     settings = {k: given[k] if given[k] is not None else rec.get(k, dflt) for k, dflt in CAPTURE_DATA_DEFAULTS.items()}
     kwargs = dict(settings)
+    # the downscale factor is passed on and recorded only when it is not 1: a capture without one keeps the record it always had
+    asked = getattr(args, "downscale_factor", None)
+    downscale = int(asked if asked is not None else rec.get("downscale_factor", 1))
+    if downscale != 1:
+        settings["downscale_factor"] = kwargs["downscale_factor"] = downscale
     if rec.get("transform") is not None and all(given[k] is None for k in CAPTURE_POSE_KEYS):
         kwargs["applied"] = (rec["transform"], rec["scale"])
     return kwargs, settings
@@ -433,7 +454,7 @@ def capture_load_args(args, recorded: Optional[dict] = None):
 def capture_flags_given(args):
     """The capture-only flags a command line carries (for the error that says a Blender-format scene has no use for them)."""
     names = (("--orientation", "orientation"), ("--center", "center_poses"), ("--no-auto-scale", "no_auto_scale"),
-             ("--train-split-fraction", "train_split_fraction"), ("--eval-mode", "eval_mode"))
+             ("--train-split-fraction", "train_split_fraction"), ("--eval-mode", "eval_mode"), ("--downscale-factor", "downscale_factor"))
     return [flag for flag, attr in names if getattr(args, attr, None) is not None]
 
 
@@ -454,7 +475,12 @@ def load_scene(ap: argparse.ArgumentParser, args, split: str, recorded: Optional
     if blender.get("normals"):
         ap.error(f"{args.command}: --normals needs a Blender-format scene with normal maps; {args.data} is a nerfstudio-format capture")
     kwargs, settings = capture_load_args(args, recorded)
-    return load_nerfstudio_split(args.data, split, pixels=pixels, **kwargs), {"format": "nerfstudio", **settings}
+    try:  # masks and fisheye cameras are read where the file has them
+        return load_nerfstudio_split(args.data, split, pixels=pixels, masks=True, fisheye=True, **kwargs), {"format": "nerfstudio", **settings}
+    except FileNotFoundError as e:
+        if "downscale_factor" not in kwargs:
+            raise
+        ap.error(f"{args.command}: --downscale-factor {kwargs['downscale_factor']}: {e}")
 
 
 def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
@@ -976,7 +1002,12 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     the scene has none).  Every level-0 entry of per_image gains normal_mae, alpha_mae and normal_weight; results gains normal_mae,
     normal_mae_std, alpha_mae, alpha_mae_std and normal_mae_views, and the dict a "geometry" entry (GEOMETRY_NOTE).  normals_space
     "camera": the maps are in each view's camera frame.  With save_images, NNNN_normals.png: prediction | ground truth | error.
-    normals=False is the evaluation without any of it: the same launches, keys and bytes."""
+    normals=False is the evaluation without any of it: the same launches, keys and bytes.
+
+    A scene with masks (a capture's): psnr / ssim stay those of the whole image, as nerfstudio reports them; every level-0 entry of
+    per_image gains psnr_masked, the fine PSNR over the live pixels alone (nan for a view without one), and results psnr_masked and
+    psnr_masked_std over the views that have one.  It is formed on the device from the tensors of the view and read once, after the
+    last view.  Without masks nothing is added."""
     from . import metrics
     from .data import RayDataManager
 
@@ -987,7 +1018,8 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     dev = torch.device(device)
     ckpt, model, step = open_checkpoint(ckpt, model_config, dev)
     model.config.eval_num_rays_per_chunk = EVAL_CHUNK
-    dm = RayDataManager(scene, dev, levels=multiscale)
+    dm = RayDataManager(scene, dev, levels=multiscale, live_lists=False)
+    masked = []  # (entry of per_image, device scalar)
     n = scene.num_images if max_images is None else min(int(max_images), scene.num_images)
     if occupancy is not None:
         from .occupancy import attach_occupancy
@@ -1016,13 +1048,20 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
                 _save_normals_panel(os.path.join(save_images, f"{i:04d}_normals.png"), outputs, dm.normal_image(i), dm.images[i],
                                     geo["error_map"])
         per_image.append({"image": i, **({"level": level} if multiscale > 1 else {}), **m})
+        if dm.masks is not None and level == 0:
+            live = dm.mask_image(i).to(torch.float32).unsqueeze(-1)
+            err = ((torch.clip(outputs["mid_reflect_fine"], 0.0, 1.0) - _white(gt)) ** 2 * live).sum() / (3.0 * live.sum())  # 0 / 0 = nan
+            masked.append((per_image[-1], 10.0 * torch.log10(1.0 / err.clamp(min=1e-12))))
         if save_images:
             from PIL import Image
 
             panel = (images["img"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
             name = f"{i:04d}_img.png" if level == 0 else f"{i:04d}_x{1 << level}_img.png"
             Image.fromarray(panel).save(os.path.join(save_images, name))
-    keys = [k for k in per_image[0] if k not in ("image", "level") + GEOMETRY_KEYS] if per_image else []
+    if masked:
+        for (entry, _), v in zip(masked, torch.stack([v for _, v in masked]).cpu().tolist()):  # the one read of the masked scores
+            entry["psnr_masked"] = float(v)
+    keys = [k for k in per_image[0] if k not in ("image", "level", "psnr_masked") + GEOMETRY_KEYS] if per_image else []
 
     def mean_std(v):
         v = np.asarray(v, dtype=np.float64)
@@ -1037,6 +1076,9 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         results[k], results[k + "_std"] = mean_std([m for m, _ in per_level])
         for level, (m, sd) in enumerate(per_level):
             results[f"{k}_x{1 << level}"], results[f"{k}_x{1 << level}_std"] = m, sd
+    if masked:
+        counted = [p["psnr_masked"] for p, _ in masked if not math.isnan(p["psnr_masked"])]
+        results["psnr_masked"], results["psnr_masked_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
     if normals:
         scored = [p for p in per_image if "normal_mae" in p]
         counted = [p["normal_mae"] for p in scored if not math.isnan(p["normal_mae"])]
