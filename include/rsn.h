@@ -1315,6 +1315,69 @@ int rsn_normal_error(int32_t n_pixels, const float* normals, const float* accumu
                      const uint8_t* gt_rgba, const float* rotation, float* error_map, void* workspace, size_t workspace_bytes,
                      float* out, void* stream);
 
+
+/* ---- depth supervision (additive to ABI 18: no existing call changes): a capture's depth maps as a training target (the DS-NeRF
+ * term) and as an eval metric.  A target is a distance along the NORMALISED ray, in scene units; 0 means "no target".
+ *
+ * rsn_gather_ray_depth: t [R] of the rays a sampler drew.  One lane per ray, one launch, no atomics, no host read.
+ *   indices int32 [R,3] = (image, y, x) as the samplers write them; level int32 [R] or NULL (rsn_sample_pyramid_rays' output);
+ *   depths fp32 [N,H,W], 0 = no measurement; cameras: the level-0 camera table fp32 [N, camera_stride] (9 or 12 columns,
+ *   "captures") or NULL, in which case the four shared intrinsics fx .. cy are read instead (they are not read otherwise).
+ *   t[r] = 0 when the stored depth is 0, when level[r] > 0 (the pyramid builds no depth levels: multi-scale training supervises
+ *   only its level-0 rays -- a design rule, not a limit of the kernel), or when an index lies outside [N,H,W].
+ *   euclidean != 0: the files hold distances along the ray, t[r] = the stored value.
+ *   euclidean == 0 (the default of the loader: Polycam and Record3D write z-depths): t[r] = (float)((double)z * |v|), with
+ *   v = (X, -Y, -1) the un-normalised camera-space direction of the pixel centre in fp64: (X, Y) = ((x+.5-cx)/fx, (y+.5-cy)/fy) for
+ *   a row whose five coefficients are zero, and the Newton solve of "captures" (10 iterations, fp64) from that point otherwise.
+ *   A fisheye row has a unit v and no z-plane beyond 90 degrees: the caller states whether the table holds one (has_fisheye; the
+ *   table is on the device and is not read by the host), and has_fisheye != 0 with euclidean == 0 is RSN_ERR_INVALID_ARGUMENT
+ *   before any launch.  (A fisheye row met by the kernel with euclidean == 0 gives 0.)
+ *   RSN_ERR_INVALID_ARGUMENT before any launch also for: n_images, height or width < 1, n_rays < 0, a camera_stride other than 9 or
+ *   12 with a table, has_fisheye with a 9-column table or none, fx or fy == 0 without a table, and, with n_rays > 0, a NULL
+ *   indices, depths or t.  n_rays == 0 launches nothing. */
+int rsn_gather_ray_depth(int32_t n_rays, const int32_t* indices, const int32_t* level, const float* depths, int32_t n_images,
+                         int32_t height, int32_t width, const float* cameras, int32_t camera_stride, float fx, float fy, float cx,
+                         float cy, int32_t has_fisheye, int32_t euclidean, float* t, void* stream);
+
+/* The DS-NeRF depth term (Deng et al. 2022; nerfstudio's ds_nerf_depth_loss) of one primary level.  Per ray, with the target
+ * D = target[r], the euclidean bins e_0 <= ... <= e_S (euclid_bins [R,S+1]), midpoints m_k = (e_k + e_{k+1}) / 2, lengths
+ * l_k = e_{k+1} - e_k, the compositing weights w_k and s = depth_sigma, a standard deviation in scene units:
+ *   L_ray        = [D > 0] sum_k -log(w_k + EPS) exp(-(m_k - D)^2 / (2 s^2)) l_k                      EPS = 1e-7
+ *   dL_ray/dw_k  = -[D > 0] exp(-(m_k - D)^2 / (2 s^2)) l_k / (w_k + EPS)
+ * This formula is the definition.  (nerfstudio's version is remembered to divide by 2 sigma, which would make its
+ * depth_sigma = 0.01 an s of 0.1 here; that was not checked against its source.)
+ * Both calls take sigma [R,S] and euclid_bins, the inputs of the level's rsn_composite call, not its fp32 weights: they form
+ * w_k = -expm1(-x_k) exp(-X_k), x_k = l_k sigma_k, X_k = sum_{j<k} x_j in fp64, as rsn_distortion_backward does.  rsn_composite's
+ * weights are good to 2^-24 of the transmittance and EPS is 2^-23: log(w + EPS) and 1 / (w + EPS) of a thin sample -- a target in
+ * what is still empty space, the state the term acts on most -- would be off by tens of percent.  The interior is fp64 and the
+ * result is rounded to fp32 once.
+ * One wave per ray, 64-sample chunks with a carried scan, no atomics, a fixed order of addition: the same inputs give the same bits.
+ * n_dev (or NULL): device-side ray count, min(n_rays, *n_dev) rows are processed and the rows behind are not touched.
+ *
+ * rsn_depth_loss_forward: loss_ray [R] = L_ray, unscaled; exactly 0 for a ray without a target.
+ * rsn_depth_loss_backward: g_w[k] = g_loss_ray[r] dL_ray/dw_k is recomputed (nothing [R,S]-sized is kept from the forward) and
+ *   carried to sigma by rsn_composite_backward's rule, g_sigma[k] = l_k (g_w[k] T_{k+1} - sum_{i>k} g_w[i] w_i), the suffix sum
+ *   added up from the far end of the ray.  accumulate != 0: the value, rounded to fp32, is ADDED to g_sigma [R,S] (a ray without a
+ *   target is left as it is); 0: it overwrites (zeros for such a ray).
+ *
+ * Before any launch: RSN_ERR_INVALID_ARGUMENT for n_rays < 0, n_samples < 1, a depth_sigma that is not a positive finite number
+ * or, with n_rays > 0, a NULL pointer other than n_dev; RSN_ERR_UNSUPPORTED for n_samples > 4096.  n_rays == 0 launches nothing. */
+int rsn_depth_loss_forward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* euclid_bins, const float* sigma,
+                           const float* target, float depth_sigma, float* loss_ray, void* stream);
+int rsn_depth_loss_backward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* euclid_bins, const float* sigma,
+                            const float* target, float depth_sigma, const float* g_loss_ray, float* g_sigma, int32_t accumulate,
+                            void* stream);
+
+/* rsn_depth_error: one eval view's rendered depth against its target distances (rsn_gather_ray_depth over the whole view).
+ * depth, target fp32 [P]; mask uint8 [P] or NULL (a capture's mask: 0 = the pixel is not scored).  Over the pixels with
+ * target > 0 and a live mask byte, in fp64 and in rsn_normal_error's fixed order (same launch shape, same workspace: at least
+ * rsn_normal_error_workspace_bytes(n_pixels) bytes, 8-byte aligned), no atomics, no host read:
+ *   out[0] = (float)sum |depth - target|    out[1] = (float)sum (depth - target)^2    out[2] = (float)count   (exact: P <= 2^24)
+ * RSN_ERR_INVALID_ARGUMENT before any launch: n_pixels outside [1, 2^24], a NULL depth, target, workspace or out, a misaligned
+ * workspace; RSN_ERR_WORKSPACE for a workspace_bytes below the size needed. */
+int rsn_depth_error(int32_t n_pixels, const float* depth, const float* target, const uint8_t* mask, void* workspace,
+                    size_t workspace_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,6 +284,11 @@ _SIGNATURES = {
     "rsn_texture_points": (C.c_int, [C.c_int32, _fp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _fp, _fp, C.c_void_p]),
     "rsn_normal_error_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "rsn_normal_error": (C.c_int, [C.c_int32, _fp, _fp, C.c_void_p, C.c_void_p, _fp, _fp, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
+    "rsn_gather_ray_depth": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32,
+                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _fp, C.c_void_p]),
+    "rsn_depth_loss_forward": (C.c_int, [C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, C.c_float, _fp, C.c_void_p]),
+    "rsn_depth_loss_backward": (C.c_int, [C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, C.c_float, _fp, _fp, C.c_int32, C.c_void_p]),
+    "rsn_depth_error": (C.c_int, [C.c_int32, _fp, _fp, C.c_void_p, C.c_void_p, C.c_size_t, _fp, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

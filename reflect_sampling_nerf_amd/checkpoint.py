@@ -49,7 +49,8 @@ def resolve_checkpoint(path: str) -> str:
 
 def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, max_grad_norm: Optional[float] = None,
                    skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
-                   distortion_loss_coarse: Optional[float] = None, rays_and_data: Optional[dict] = None) -> dict:
+                   distortion_loss_coarse: Optional[float] = None, rays_and_data: Optional[dict] = None,
+                   depth: Optional[dict] = None) -> dict:
     """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
     bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
     seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one.
@@ -58,7 +59,10 @@ def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, 
     distortion_loss_coarse (the coefficients of the opt-in distortion term): only when set and not 0.  rays_and_data: the entries
     of RAY_KEYS ("near", "far": the collider planes; "primary_spacing", "primary_tan": the coarse sampler of the primary rays) and
     "data" (how a capture was read: format, orientation, center, auto_scale, scale_factor, train_split_fraction, eval_mode, and the
-    transform [3][4] and scale that were applied) that are not None are recorded; a Blender-format run with its defaults has none."""
+    transform [3][4] and scale that were applied) that are not None are recorded; a Blender-format run with its defaults has none.
+    depth: the settings of the opt-in depth term, DEPTH_RUN_KEYS: "depth_loss" / "depth_loss_coarse" (the coefficients) are recorded
+    when set and not 0, and only with one of them "depth_sigma" (when set) and "depth_euclidean" (when true); a run without the term
+    records none of them."""
     dev = torch.device(device)
     state = {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
              "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
@@ -72,6 +76,16 @@ def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, 
     for key, coef in (("distortion_loss", distortion_loss), ("distortion_loss_coarse", distortion_loss_coarse)):
         if coef is not None and float(coef) != 0.0:
             state[key] = float(coef)
+    depth = depth or {}
+    if set(depth) - set(DEPTH_RUN_KEYS):
+        raise KeyError(f"depth: unknown entries {sorted(set(depth) - set(DEPTH_RUN_KEYS))}")
+    coefs = {k: float(depth[k]) for k in ("depth_loss", "depth_loss_coarse") if depth.get(k) is not None and float(depth[k]) != 0.0}
+    if coefs:
+        state.update(coefs)
+        if depth.get("depth_sigma") is not None:
+            state["depth_sigma"] = float(depth["depth_sigma"])
+        if depth.get("depth_euclidean"):
+            state["depth_euclidean"] = True
     for key, v in (rays_and_data or {}).items():
         if key not in RAY_KEYS + ("data",):
             raise KeyError(f"rays_and_data: unknown entry {key!r}")
@@ -81,6 +95,7 @@ def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, 
 
 
 RAY_KEYS = ("near", "far", "primary_spacing", "primary_tan")
+DEPTH_RUN_KEYS = ("depth_loss", "depth_loss_coarse", "depth_sigma", "depth_euclidean")
 PRIMARY_SPACINGS = ("uniform", "reciprocal")
 
 

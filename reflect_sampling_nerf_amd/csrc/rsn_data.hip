@@ -3,6 +3,7 @@
 //   rsn_camera_rays_image   the same ray arithmetic for every pixel of one camera (rendering views)
 //   rsn_capture_rays_image  every pixel of one camera of a capture: a camera-table row with lens distortion (rsn_camera.h capture_ray)
 //   rsn_capture_rays_image2 the same for a row of 9 or 12 columns: a fisheye row takes the equidistant model (rsn_camera.h lens_ray)
+//   rsn_gather_ray_depth    the target distance along the ray of every sampled pixel, from a capture's depth maps (depth supervision)
 //   rsn_ssim                torchmetrics' structural_similarity_index_measure of two [H, W, 3] images, on the device
 // Recipes (Philox keying, ray arithmetic, SSIM definition): include/rsn.h.
 #include "rsn_camera.h"
@@ -99,6 +100,47 @@ __global__ __launch_bounds__(256) void rsn_capture_rays_image2_kernel(int height
     directions[3 * p + j] = d[j];
   }
   pixel_area[p] = area;
+}
+
+// ------------------------------------------------------------------------------------------------ depth targets
+// The target distance along the normalised ray of every sampled pixel (include/rsn.h, "depth supervision"): one lane per ray, a
+// 4-byte gather from the depth images and, for a z-depth, the length of the pixel centre's un-normalised camera-space direction
+// v = (X, -Y, -1) in fp64 ((X, Y) from undistort_point for a distorted row).  A ray of a pyramid level above 0, a stored 0, an index
+// outside the images and a fisheye row whose depth is not euclidean (no z-plane: the host refuses it) give 0, "no target".
+struct GatherDepthArgs {
+  int32_t n_rays, n_images, height, width;
+  const int32_t* indices;  // [R, 3] = (image, y, x)
+  const int32_t* level;    // [R] or NULL
+  const float* depths;     // [N, H, W]
+  const float* cameras;    // [N, stride] or NULL: the shared intrinsics k
+  int32_t stride;
+  Intrinsics k;
+  int32_t euclidean;
+  float* t;
+};
+
+__global__ __launch_bounds__(256) void rsn_gather_ray_depth_kernel(GatherDepthArgs a) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.n_rays) return;
+  const int i = a.indices[3 * (size_t)r], y = a.indices[3 * (size_t)r + 1], x = a.indices[3 * (size_t)r + 2];
+  float out = 0.0f;
+  const bool level0 = !a.level || a.level[r] == 0;
+  if (level0 && i >= 0 && i < a.n_images && y >= 0 && y < a.height && x >= 0 && x < a.width) {
+    const float z = a.depths[((size_t)i * a.height + y) * a.width + x];
+    if (a.euclidean) {
+      out = z;
+    } else if (z != 0.0f) {
+      LensCamera lc{Camera{a.k, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, false};
+      if (a.cameras) lc = load_lens_camera(a.cameras + (size_t)i * a.stride, a.stride);
+      if (!lc.fisheye) {
+        const Camera& c = lc.c;
+        double X = ((double)x + 0.5 - (double)c.k.cx) / (double)c.k.fx, Y = ((double)y + 0.5 - (double)c.k.cy) / (double)c.k.fy;
+        if (!(c.k1 == 0.0f && c.k2 == 0.0f && c.k3 == 0.0f && c.p1 == 0.0f && c.p2 == 0.0f)) undistort_point(c, X, Y, &X, &Y);
+        out = (float)((double)z * sqrt(X * X + Y * Y + 1.0));
+      }
+    }
+  }
+  a.t[r] = out;
 }
 
 // ------------------------------------------------------------------------------------------------ SSIM
@@ -264,6 +306,33 @@ extern "C" int rsn_capture_rays_image2(int32_t height, int32_t width, const floa
   const int n = height * width;
   hipLaunchKernelGGL(rsn_capture_rays_image2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      height, width, c2w, camera, camera_stride, origins, directions, pixel_area);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+extern "C" int rsn_gather_ray_depth(int32_t n_rays, const int32_t* indices, const int32_t* level, const float* depths,
+                                    int32_t n_images, int32_t height, int32_t width, const float* cameras, int32_t camera_stride,
+                                    float fx, float fy, float cx, float cy, int32_t has_fisheye, int32_t euclidean, float* t,
+                                    void* stream) {
+  RSN_REQUIRE(n_images >= 1 && height >= 1 && width >= 1 && n_rays >= 0, RSN_ERR_INVALID_ARGUMENT,
+              "gather_ray_depth: n_images=%d height=%d width=%d n_rays=%d", n_images, height, width, n_rays);
+  if (cameras) {
+    RSN_REQUIRE(camera_stride == 9 || camera_stride == 12, RSN_ERR_INVALID_ARGUMENT, "gather_ray_depth: camera_stride=%d: 9 or 12",
+                camera_stride);
+    RSN_REQUIRE(!(has_fisheye && camera_stride != 12), RSN_ERR_INVALID_ARGUMENT,
+                "gather_ray_depth: has_fisheye with a %d-column table (a fisheye row has 12 columns)", camera_stride);
+  } else {
+    RSN_REQUIRE(fx != 0.0f && fy != 0.0f, RSN_ERR_INVALID_ARGUMENT, "gather_ray_depth: fx=%g fy=%g", (double)fx, (double)fy);
+    RSN_REQUIRE(!has_fisheye, RSN_ERR_INVALID_ARGUMENT, "gather_ray_depth: has_fisheye without a camera table");
+  }
+  RSN_REQUIRE(!(has_fisheye && !euclidean), RSN_ERR_INVALID_ARGUMENT,
+              "gather_ray_depth: a fisheye row has no z-plane beyond 90 degrees: its depth files must hold distances along the ray "
+              "(euclidean != 0)");
+  if (n_rays == 0) return RSN_OK;
+  RSN_REQUIRE(indices && depths && t, RSN_ERR_INVALID_ARGUMENT, "gather_ray_depth: indices, depths or t is NULL");
+  const GatherDepthArgs a{n_rays, n_images, height, width, indices, level, depths, cameras, camera_stride,
+                          Intrinsics{fx, fy, cx, cy}, euclidean != 0 ? 1 : 0, t};
+  hipLaunchKernelGGL(rsn_gather_ray_depth_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

@@ -2,6 +2,8 @@
 //
 //   rsn_normal_error   per-pixel angle between the composited predicted normal and the decoded ground truth, its alpha-weighted
 //                      mean, the alpha error of the accumulation and the count of scored pixels, all on the device
+//   rsn_depth_error    a view's rendered depth against its target distances: sum |d - D|, sum (d - D)^2 and the count over the pixels
+//                      with a target (and a live mask byte), by the same launch shape and the same fixed-order sums
 //
 // One lane per pixel in a grid-stride loop of at most RSN_NORMAL_ERROR_MAX_GROUPS workgroups of 256 lanes.  A lane reads its 12
 // bytes of prediction, 3 bytes of ground-truth normal, the alpha byte (whose pixel's other three bytes travel with it) and, when
@@ -118,6 +120,44 @@ __global__ __launch_bounds__(RSN_NE_BLOCK) void rsn_normal_error_reduce_kernel(c
   }
 }
 
+// rsn_depth_error: the first pass.  Record: (sum |d - D|, sum (d - D)^2, 0, count) over the pixels with D > 0 (and a live mask byte).
+__global__ __launch_bounds__(RSN_NE_BLOCK) void rsn_depth_error_kernel(int n_pixels, const float* depth, const float* target,
+                                                                       const uint8_t* mask, double* partial) {
+  __shared__ double red[RSN_NE_BLOCK / 64][4];
+  double sum[4] = {0.0, 0.0, 0.0, 0.0};
+  const int stride = (int)gridDim.x * RSN_NE_BLOCK;
+  for (int i = (int)blockIdx.x * RSN_NE_BLOCK + (int)threadIdx.x; i < n_pixels; i += stride) {
+    const float D = target[i];
+    if (D > 0.0f && (!mask || mask[i] != 0)) {
+      const double e = (double)depth[i] - (double)D;
+      sum[0] += fabs(e);
+      sum[1] += e * e;
+      sum[3] += 1.0;
+    }
+  }
+  group_sum(sum, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) partial[4 * (size_t)blockIdx.x + k] = sum[k];
+  }
+}
+
+__global__ __launch_bounds__(RSN_NE_BLOCK) void rsn_depth_error_reduce_kernel(const double* partial, int n_partial, float* out) {
+  __shared__ double red[RSN_NE_BLOCK / 64][4];
+  const int tid = threadIdx.x;
+  double sum[4] = {0.0, 0.0, 0.0, 0.0};
+  if (tid < n_partial) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum[k] = partial[4 * (size_t)tid + k];
+  }
+  group_sum(sum, red);
+  if (tid == 0) {
+    out[0] = (float)sum[0];
+    out[1] = (float)sum[1];
+    out[2] = (float)sum[3];
+  }
+}
+
 inline int normal_error_groups(int32_t n_pixels) {
   const int want = (n_pixels + RSN_NE_BLOCK - 1) / RSN_NE_BLOCK;
   return want < RSN_NORMAL_ERROR_MAX_GROUPS ? want : RSN_NORMAL_ERROR_MAX_GROUPS;
@@ -145,6 +185,23 @@ extern "C" int rsn_normal_error(int32_t n_pixels, const float* normals, const fl
   hipLaunchKernelGGL(rsn_normal_error_kernel, dim3((unsigned)groups), dim3(RSN_NE_BLOCK), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(rsn_normal_error_reduce_kernel, dim3(1), dim3(RSN_NE_BLOCK), 0, (hipStream_t)stream,
                      (const double*)workspace, groups, (int)n_pixels, accumulation ? 1 : 0, out);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+extern "C" int rsn_depth_error(int32_t n_pixels, const float* depth, const float* target, const uint8_t* mask, void* workspace,
+                               size_t workspace_bytes, float* out, void* stream) {
+  RSN_REQUIRE(n_pixels >= 1 && n_pixels <= RSN_NORMAL_ERROR_MAX_PIXELS, RSN_ERR_INVALID_ARGUMENT,
+              "depth_error: n_pixels=%d: need 1 <= n_pixels <= 2^24 (the pixel count is returned as a float)", n_pixels);
+  RSN_REQUIRE(depth && target && workspace && out, RSN_ERR_INVALID_ARGUMENT, "depth_error: depth, target, workspace or out is NULL");
+  const size_t need = rsn_normal_error_workspace_bytes(n_pixels);
+  RSN_REQUIRE(workspace_bytes >= need, RSN_ERR_WORKSPACE, "depth_error: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  RSN_REQUIRE(((uintptr_t)workspace & 7) == 0, RSN_ERR_INVALID_ARGUMENT, "depth_error: workspace must be 8-byte aligned");
+  const int groups = normal_error_groups(n_pixels);
+  hipLaunchKernelGGL(rsn_depth_error_kernel, dim3((unsigned)groups), dim3(RSN_NE_BLOCK), 0, (hipStream_t)stream, (int)n_pixels, depth,
+                     target, mask, (double*)workspace);
+  hipLaunchKernelGGL(rsn_depth_error_reduce_kernel, dim3(1), dim3(RSN_NE_BLOCK), 0, (hipStream_t)stream, (const double*)workspace,
+                     groups, out);
   RSN_HIP(hipGetLastError());
   return RSN_OK;
 }

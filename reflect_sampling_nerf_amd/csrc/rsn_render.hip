@@ -618,6 +618,139 @@ extern "C" int rsn_distortion_backward(int32_t n_rays, const int32_t* n_dev, int
   return RSN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// depth loss (DS-NeRF, Deng et al. 2022) of one primary level against a target distance D along the ray (include/rsn.h):
+//   L = [D > 0] sum_k -log(w_k + EPS) exp(-(m_k - D)^2 / (2 s^2)) l_k,   dL/dw_k = -[D > 0] exp(-(m_k - D)^2 / (2 s^2)) l_k / (w_k + EPS)
+// on the euclidean bins (midpoints m_k, lengths l_k).  EPS = 1e-7 is 2^-23 and rsn_composite's fp32 weights are good to 2^-24 of the
+// transmittance: both kernels re-derive w_k = -expm1(-x_k) exp(-X_k) in fp64 from sigma and the bins, as rsn_distortion_bwd_kernel
+// does.  fp64 inside, one rounding to fp32 at the end.  One wave per ray, 64-sample chunks with a carried scan of the optical depth.
+// ---------------------------------------------------------------------------------------------------
+#define DEPTH_LOSS_EPS 1e-7
+
+struct depth_sample64 {
+  double w, gauss_l, delta, t_next;  // weight, exp(-(m - D)^2 / (2 s^2)) l, euclidean length l, T_{k+1}
+};
+
+__device__ __forceinline__ depth_sample64 depth_derive(const float* eb, const float* sigma, double D, double inv_2s2, int i, bool in,
+                                                       int lane, double& carry_x) {
+  depth_sample64 c = {0.0, 0.0, 0.0, 0.0};
+  double x = 0.0;
+  if (in) {
+    const double a = (double)eb[i], b = (double)eb[i + 1];
+    const double u = 0.5 * (a + b) - D;
+    c.delta = b - a;
+    c.gauss_l = exp(-(u * u) * inv_2s2) * c.delta;
+    x = c.delta * (double)sigma[i];
+  }
+  const double incl = wave_scan_incl(x, lane);
+  const double prev = __shfl_up(incl, 1, 64);
+  const double excl = (lane > 0 ? prev : 0.0) + carry_x;  // X_k
+  const double xin = incl + carry_x;                       // X_{k+1}
+  carry_x = __shfl(xin, 63, 64);
+  c.w = in ? -expm1(-x) * exp(-excl) : 0.0;
+  c.t_next = exp(-xin);
+  return c;
+}
+
+__global__ __launch_bounds__(256) void rsn_depth_loss_fwd_kernel(int n_rays, const int* n_dev, int S, const float* euclid_bins,
+                                                                 const float* sigma, const float* target, double inv_2s2,
+                                                                 float* loss_ray) {
+  const int R = dyn_count(n_rays, n_dev);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int ray = blockIdx.x * 4 + wid; ray < R; ray += gridDim.x * 4) {
+    const float* eb = euclid_bins + (long long)ray * (S + 1);
+    const float* sg = sigma + (long long)ray * S;
+    const double D = (double)target[ray];
+    double part = 0.0;
+    if (D > 0.0) {  // the same for the whole wave
+      double carry_x = 0.0;
+      for (int base = 0; base < S; base += 64) {
+        const int i = base + lane;
+        const depth_sample64 c = depth_derive(eb, sg, D, inv_2s2, i, i < S, lane, carry_x);
+        part += -log(c.w + DEPTH_LOSS_EPS) * c.gauss_l;  // lanes past the end: gauss_l = 0
+      }
+      part = wave_sum_f64(part);
+    }
+    if (lane == 0) loss_ray[ray] = (float)part;
+  }
+}
+
+__global__ __launch_bounds__(256) void rsn_depth_loss_bwd_kernel(int n_rays, const int* n_dev, int S, const float* euclid_bins,
+                                                                 const float* sigma, const float* target, double inv_2s2,
+                                                                 const float* g_loss_ray, float* g_sigma, int accumulate) {
+  const int R = dyn_count(n_rays, n_dev);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int ray = blockIdx.x * 4 + wid; ray < R; ray += gridDim.x * 4) {
+    const long long sbase = (long long)ray * S;
+    const float* eb = euclid_bins + (long long)ray * (S + 1);
+    const float* sg = sigma + sbase;
+    const double D = (double)target[ray];
+    if (!(D > 0.0)) {  // no target (the same for the whole wave): the term adds nothing
+      if (!accumulate)
+        for (int i = lane; i < S; i += 64) g_sigma[sbase + i] = 0.0f;
+      continue;
+    }
+    const double g = (double)g_loss_ray[ray];
+    // walk 1: every chunk's total of g_w w, chunk q in lane q; then, per lane, the total of the chunks behind its own
+    double chunk_total = 0.0, carry_x = 0.0;
+    for (int base = 0; base < S; base += 64) {
+      const depth_sample64 c = depth_derive(eb, sg, D, inv_2s2, base + lane, base + lane < S, lane, carry_x);
+      const double t = wave_sum_f64(-g * c.gauss_l / (c.w + DEPTH_LOSS_EPS) * c.w);
+      if (lane == (base >> 6)) chunk_total = t;
+    }
+    const double later = wave_suffix_excl(chunk_total, lane);
+    // walk 2: the gradient
+    carry_x = 0.0;
+    for (int base = 0; base < S; base += 64) {
+      const int i = base + lane;
+      const bool in = i < S;
+      const depth_sample64 c = depth_derive(eb, sg, D, inv_2s2, i, in, lane, carry_x);
+      const double gw = -g * c.gauss_l / (c.w + DEPTH_LOSS_EPS);
+      const double suffix = wave_suffix_excl(gw * c.w, lane) + __shfl(later, base >> 6, 64);  // sum_{i>k} g_w[i] w_i
+      const float val = (float)(c.delta * (gw * c.t_next - suffix));
+      if (in) g_sigma[sbase + i] = accumulate ? g_sigma[sbase + i] + val : val;
+    }
+  }
+}
+
+static int depth_loss_args(int32_t n_rays, int32_t n_samples, float s) {
+  RSN_REQUIRE(n_rays >= 0 && n_samples >= 1, RSN_ERR_INVALID_ARGUMENT, "n_rays=%d n_samples=%d", n_rays, n_samples);
+  RSN_REQUIRE(n_samples <= DIST_MAX_S, RSN_ERR_UNSUPPORTED, "n_samples=%d > %d", n_samples, DIST_MAX_S);
+  RSN_REQUIRE(s > 0.0f && s < __builtin_huge_valf(), RSN_ERR_INVALID_ARGUMENT, "depth_sigma=%g is not a positive finite number", (double)s);
+  return RSN_OK;
+}
+
+extern "C" int rsn_depth_loss_forward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* euclid_bins,
+                                      const float* sigma, const float* target, float depth_sigma, float* loss_ray, void* stream) {
+  const int rc = depth_loss_args(n_rays, n_samples, depth_sigma);
+  if (rc != RSN_OK) return rc;
+  if (n_rays == 0) return RSN_OK;
+  RSN_REQUIRE(euclid_bins && sigma && target && loss_ray, RSN_ERR_INVALID_ARGUMENT, "euclid_bins/sigma/target/loss_ray is NULL");
+  int blocks = (n_rays + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(rsn_depth_loss_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_rays, n_dev, n_samples,
+                     euclid_bins, sigma, target, 0.5 / ((double)depth_sigma * (double)depth_sigma), loss_ray);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
+extern "C" int rsn_depth_loss_backward(int32_t n_rays, const int32_t* n_dev, int32_t n_samples, const float* euclid_bins,
+                                       const float* sigma, const float* target, float depth_sigma, const float* g_loss_ray,
+                                       float* g_sigma, int32_t accumulate, void* stream) {
+  const int rc = depth_loss_args(n_rays, n_samples, depth_sigma);
+  if (rc != RSN_OK) return rc;
+  if (n_rays == 0) return RSN_OK;
+  RSN_REQUIRE(euclid_bins && sigma && target && g_loss_ray && g_sigma, RSN_ERR_INVALID_ARGUMENT,
+              "euclid_bins/sigma/target/g_loss_ray/g_sigma is NULL");
+  int blocks = (n_rays + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(rsn_depth_loss_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n_rays, n_dev, n_samples,
+                     euclid_bins, sigma, target, 0.5 / ((double)depth_sigma * (double)depth_sigma), g_loss_ray, g_sigma,
+                     accumulate != 0 ? 1 : 0);
+  RSN_HIP(hipGetLastError());
+  return RSN_OK;
+}
+
 // column sums (bias gradients): each workgroup owns a chunk of rows, thread t owns columns t, t+256, ...
 __global__ __launch_bounds__(256) void rsn_colsum_kernel(long long n_rows, int n_cols, int ld, const float* x,
                                                          float* out, long long rows_per_block) {

@@ -48,7 +48,9 @@ class BlenderScene:
     dataparser_scale: what load_nerfstudio_split applied to the file's poses (None for other sources); file_paths: the frames' names.
 
     A table of 12 columns (LENS_CAMERA_COLUMNS) holds fisheye rows: k4, the model (0 perspective, 1 OpenCV fisheye) and a zero follow
-    the nine.  masks: None, or uint8 [N,H,W] of 0 / 1: 1 = the pixel is live, it may be drawn into a training batch."""
+    the nine.  masks: None, or uint8 [N,H,W] of 0 / 1: 1 = the pixel is live, it may be drawn into a training batch.
+    depths: None, or float32 [N,H,W] depth maps in scene units (the poses' units), 0 = no measurement: z-depths along the camera
+    axis unless the caller says otherwise (RayDataManager(depth_euclidean=True): distances along the ray)."""
 
     images: np.ndarray
     c2w: np.ndarray
@@ -62,6 +64,7 @@ class BlenderScene:
     dataparser_scale: Optional[float] = None
     file_paths: Optional[List[str]] = None
     masks: Optional[np.ndarray] = None
+    depths: Optional[np.ndarray] = None
 
     @property
     def num_images(self) -> int:
@@ -76,10 +79,12 @@ class BlenderScene:
         return int(self.images.shape[2])
 
     @classmethod
-    def from_arrays(cls, images, c2w, focal: float, cx=None, cy=None, normals=None, masks=None) -> "BlenderScene":
+    def from_arrays(cls, images, c2w, focal: float, cx=None, cy=None, normals=None, masks=None, depths=None) -> "BlenderScene":
         """images [N,H,W,3|4] (uint8, or float in [0, 1] rounded to uint8), c2w [N,3,4] or [N,4,4]; fx = fy = focal,
         principal point at the image centre unless given.  normals: None, or [N,H,W,3] normal maps -- uint8 taken as is, float unit
-        vectors encoded as rint((n * 0.5 + 0.5) * 255) clipped to 0..255.  masks: None, or [N,H,W], non-zero = live (stored as 0 / 1)."""
+        vectors encoded as rint((n * 0.5 + 0.5) * 255) clipped to 0..255.  masks: None, or [N,H,W], non-zero = live (stored as 0 / 1).
+        depths: None, or [N,H,W] depth maps in scene units, 0 = no measurement (stored as float32); ValueError for a negative or
+        non-finite value."""
         im = np.asarray(images.cpu() if isinstance(images, torch.Tensor) else images)
         if im.ndim != 4 or im.shape[-1] not in (3, 4):
             raise ValueError(f"images must be [N,H,W,3|4], got {im.shape}")
@@ -105,9 +110,17 @@ class BlenderScene:
             if mk.shape != im.shape[:3]:
                 raise ValueError(f"masks must be [N,H,W] = {im.shape[:3]}, got {mk.shape}")
             mk = np.ascontiguousarray((mk != 0).astype(np.uint8))
+        dp = None
+        if depths is not None:
+            dp = np.asarray(depths.cpu() if isinstance(depths, torch.Tensor) else depths)
+            if dp.shape != im.shape[:3]:
+                raise ValueError(f"depths must be [N,H,W] = {im.shape[:3]}, got {dp.shape}")
+            if not np.all(np.isfinite(dp)) or np.any(dp < 0):
+                raise ValueError("depths must be finite and >= 0 (0 = no measurement)")
+            dp = np.ascontiguousarray(dp.astype(np.float32))
         return cls(images=np.ascontiguousarray(im), c2w=np.ascontiguousarray(pose[:, :3, :4]), fx=float(focal),
                    fy=float(focal), cx=float(W / 2.0 if cx is None else cx), cy=float(H / 2.0 if cy is None else cy), normals=nm,
-                   masks=mk)
+                   masks=mk, depths=dp)
 
 
 def load_blender_split(root: str, split: str, scale_factor: float = 1.0, normals: bool = False,
@@ -347,7 +360,8 @@ def write_dataparser_transforms(path: str, transform, scale: float) -> None:
 def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orientation: str = "up", center: str = "poses",
                           auto_scale: bool = True, train_split_fraction: float = 0.9, eval_mode: str = "fraction",
                           applied: Optional[Tuple[Sequence, float]] = None, pixels: bool = True, masks: bool = False,
-                          fisheye: bool = False, downscale_factor: int = 1) -> BlenderScene:
+                          fisheye: bool = False, downscale_factor: int = 1, depths: bool = False,
+                          depth_unit_scale: float = 1e-3) -> BlenderScene:
     """One split of a nerfstudio-format capture, root/transforms.json, as nerfstudio's NerfstudioDataParser reads it; -> a scene
     with a camera table.  All arithmetic on the host in float64, rounded once to float32.
 
@@ -376,7 +390,16 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
     invertibility check of a fisheye row is fisheye_residual, against the same 1e-9.
     downscale_factor=K > 1, nerfstudio's rule: images/frame.png is read from images_K/frame.png (the parent directory's name gets
     _K; a mask_path likewise), fl_x, fl_y, cx, cy are divided by K, and a declared w, h must be the file's size times K up to the
-    truncation of w // K, h // K.  FileNotFoundError naming the directory when it is missing: nothing is resampled here."""
+    truncation of w // K, h // K.  FileNotFoundError naming the directory when it is missing: nothing is resampled here.
+    depths=True: a frame's depth_file_path (what ns-process-data polycam --use-depth and record3d write; relative to the JSON) is read
+    as a 16-bit PNG (Pillow mode I;16 or I) or a .npy float array, and scene.depths is float32 [N,H,W] =
+    raw * depth_unit_scale * s, s being the factor the translations were multiplied by above (scale_factor, over max |t| when
+    auto_scale is on; applied's scale): the product is formed in float64 and rounded once; 0 = no measurement.
+    depth_unit_scale = 1e-3 is nerfstudio's (millimetres).  scene.depths is None when no kept frame has the key (and with
+    pixels=False, which still checks the files' presence).  ValueError naming the frame: a kept frame without the key when another
+    has it, a file of another size than its image, of another kind than the two above, or with a negative or non-finite value;
+    FileNotFoundError naming the frame for a missing file.  With downscale_factor = K the file comes from depths_K/ (the same
+    folder rule); nothing is resampled.  depths=False (the default): the key is ignored."""
     from PIL import Image
 
     meta_path = os.path.join(root, "transforms.json")
@@ -454,6 +477,12 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
     images, size = [], None
     live = {}  # position among the kept frames -> uint8 [H,W]
     checked = {}
+    depth_maps = []
+    with_depth = [i for i in keep if "depth_file_path" in frames[i]] if depths else []
+    if with_depth and len(with_depth) != len(keep):
+        lacking = next(frames[i]["file_path"] for i in keep if "depth_file_path" not in frames[i])
+        raise ValueError(f"{meta_path}: frame {lacking} has no depth_file_path, and frame {frames[with_depth[0]]['file_path']} of the same "
+                         "split has one; depth supervision needs a depth file for every frame of the split or for none")
     for i in keep:
         fr, name = frames[i], frames[i]["file_path"]
         path = on_disk(name)
@@ -484,6 +513,34 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
                 if pixels:
                     mk = np.asarray(img)
                     live[len(images)] = ((mk if mk.ndim == 2 else mk[..., 0]) != 0).astype(np.uint8)
+        if with_depth:
+            dpath = on_disk(fr["depth_file_path"])
+            if not os.path.isfile(dpath):
+                raise FileNotFoundError(f"{dpath}: depth file of frame {name} of {meta_path} not found")
+            if dpath.lower().endswith(".npy"):
+                raw = np.load(dpath, mmap_mode=None if pixels else "r", allow_pickle=False)
+                if raw.ndim == 3 and raw.shape[-1] == 1:
+                    raw = raw[..., 0]
+                if not np.issubdtype(raw.dtype, np.floating) or raw.ndim != 2:
+                    raise ValueError(f"{meta_path}: frame {name}: its depth file {fr['depth_file_path']} holds a {raw.dtype} array of "
+                                     f"shape {raw.shape}; a .npy depth file is a float [H,W] array")
+                dsize = raw.shape
+            else:
+                with Image.open(dpath) as img:
+                    if img.mode not in ("I;16", "I"):
+                        raise ValueError(f"{meta_path}: frame {name}: its depth file {fr['depth_file_path']} has Pillow mode {img.mode}; "
+                                         "a depth image is a 16-bit PNG (mode I;16 or I)")
+                    dsize = (img.size[1], img.size[0])
+                    raw = np.asarray(img) if pixels else None
+            if tuple(dsize) != tuple(im.shape[:2]):
+                raise ValueError(f"{meta_path}: frame {name}: its depth file {fr['depth_file_path']} is {dsize[1]} x {dsize[0]} pixels, "
+                                 f"the image {im.shape[1]} x {im.shape[0]}; a frame's depth map must have its image's size")
+            if pixels:
+                raw64 = np.asarray(raw, dtype=np.float64)
+                if not np.all(np.isfinite(raw64)) or np.any(raw64 < 0):
+                    raise ValueError(f"{meta_path}: frame {name}: its depth file {fr['depth_file_path']} holds a negative or non-finite "
+                                     "value (0 = no measurement)")
+                depth_maps.append((raw64 * float(depth_unit_scale) * scale).astype(np.float32))
         key = lens64[i].tobytes()
         if fish[i]:
             if key not in checked:
@@ -510,7 +567,7 @@ def load_nerfstudio_split(root: str, split: str, scale_factor: float = 1.0, orie
     return BlenderScene(images=stack, c2w=np.ascontiguousarray(poses[keep].astype(np.float32)),
                         fx=float(cams[0, 0]), fy=float(cams[0, 1]), cx=float(cams[0, 2]), cy=float(cams[0, 3]), cameras=cams,
                         dataparser_transform=transform, dataparser_scale=scale, file_paths=[frames[i]["file_path"] for i in keep],
-                        masks=mask_stack)
+                        masks=mask_stack, depths=np.ascontiguousarray(np.stack(depth_maps)) if depth_maps else None)
 
 
 def shared_pinhole(scene: BlenderScene, what: str) -> Tuple[float, float, float, float]:
@@ -563,10 +620,17 @@ class RayDataManager:
     device at construction -- counted, the counts read once, allocated exactly, filled -- and next_train draws only from them;
     ValueError for a level without a live pixel; live_lists=False uploads the masks and builds no lists (eval draws no batches, and
     next_train then draws from every pixel).  With masks or a 12-column table next_train goes through
-    rsn_sample_capture_rays_live and the views through rsn_capture_rays_image2; still one launch and no host read per call."""
+    rsn_sample_capture_rays_live and the views through rsn_capture_rays_image2; still one launch and no host read per call.
+
+    A scene with depth maps (scene.depths): they are uploaded once, depth_image(i) serves them, and next_train adds the batch's
+    target distances along the normalised rays, "depth" float32 [R] with 0 = no target, to the batch and, as [R,1], to the bundle's
+    metadata (where the training graph's opt-in depth term reads them): one more launch (rsn_gather_ray_depth), no host read, no
+    atomics.  depth_euclidean: the maps hold distances along the ray, not z-depths; a table with a fisheye row needs it (ValueError
+    at construction otherwise: such a camera has no z-plane beyond 90 degrees).  The pyramid builds no depth levels: with levels > 1
+    only the level-0 rays of a batch get a target -- a design rule.  A scene without depths makes the calls it made before."""
 
     def __init__(self, scene: BlenderScene, device, num_rays_per_batch: int = 1024, seed: int = 0, rank: int = 0, levels: int = 1,
-                 live_lists: bool = True):
+                 live_lists: bool = True, depth_euclidean: bool = False):
         self.levels = int(levels)
         self.level_sizes, self.level_offsets = pyramid_layout(scene.num_images, scene.height, scene.width, self.levels)  # raises first
         self.scene = scene
@@ -600,6 +664,18 @@ class RayDataManager:
             self._build_live_pixels(scene)
         elif scene.masks is not None:  # a caller that draws no batches (eval): the masks alone, for mask_image
             self.masks = torch.from_numpy(np.ascontiguousarray(scene.masks, dtype=np.uint8)).to(self.device)
+        self.depths = None  # fp32 [N,H,W]: level 0 only, the pyramid builds no depth levels
+        self.depth_euclidean = bool(depth_euclidean)
+        self.has_fisheye = bool(scene.cameras is not None and scene.cameras.shape[1] == len(LENS_CAMERA_COLUMNS)
+                                and np.any(scene.cameras[:, 10] != 0.0))
+        if scene.depths is not None:
+            dp = np.ascontiguousarray(scene.depths, dtype=np.float32)
+            if dp.shape != (scene.num_images, scene.height, scene.width):
+                raise ValueError(f"depths must be [{scene.num_images},{scene.height},{scene.width}], got {dp.shape}")
+            if self.has_fisheye and not self.depth_euclidean:
+                raise ValueError("the camera table holds a fisheye row and the depth maps are z-depths: a fisheye camera has no z-plane "
+                                 "beyond 90 degrees; its depth maps must hold distances along the ray (depth_euclidean=True)")
+            self.depths = torch.from_numpy(dp).to(self.device)
 
     def _build_live_pixels(self, scene: BlenderScene) -> None:
         mk = np.ascontiguousarray(scene.masks, dtype=np.uint8)
@@ -631,7 +707,47 @@ class RayDataManager:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def ray_depth(self, indices: torch.Tensor, levels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> float32 [R]: the target distance along the normalised ray of the pixels indices int32 [R,3] = (image, y, x), 0 = no
+        target (a stored 0, or a ray of a level above 0); rsn_gather_ray_depth, one launch.  ValueError without depth maps."""
+        if self.depths is None:
+            raise ValueError("the scene has no depth maps (load_nerfstudio_split(..., depths=True) or from_arrays(..., depths=...))")
+        from . import ops
+
+        s = self.scene
+        return ops.gather_ray_depth(indices, levels, self.depths, None if self.cameras is None else self.cameras[0],
+                                    (s.fx, s.fy, s.cx, s.cy), self.has_fisheye, self.depth_euclidean)
+
+    def view_ray_depth(self, i: int) -> torch.Tensor:
+        """-> float32 [H,W]: ray_depth of every pixel of camera i, what eval's depth metrics compare depth_fine with."""
+        s = self.scene
+        if not 0 <= i < s.num_images:
+            raise IndexError(f"camera {i} of {s.num_images}")
+        y, x = torch.meshgrid(torch.arange(s.height, device=self.device, dtype=torch.int32),
+                              torch.arange(s.width, device=self.device, dtype=torch.int32), indexing="ij")
+        idx = torch.stack([torch.full_like(y, i), y, x], dim=-1).reshape(-1, 3).contiguous()
+        return self.ray_depth(idx).view(s.height, s.width)
+
+    def depth_image(self, i: int) -> torch.Tensor:
+        """The depth map of camera i as stored: float32 [H,W] on the device, scene units, 0 = no measurement; a view of the one
+        upload.  Level 0 only.  ValueError when the scene has no depth maps."""
+        if self.depths is None:
+            raise ValueError("the scene has no depth maps (load_nerfstudio_split(..., depths=True) or from_arrays(..., depths=...))")
+        if not 0 <= i < self.scene.num_images:
+            raise IndexError(f"camera {i} of {self.scene.num_images}")
+        return self.depths[i]
+
     def next_train(self, step: int) -> Tuple[RayBundle, Dict[str, torch.Tensor]]:
+        """_draw(step); a scene with depth maps adds batch["depth"] float32 [R], the rays' target distances (ray_depth), and the same
+        values as ray_bundle.metadata["depth"] [R,1]."""
+        rb, batch = self._draw(step)
+        if self.depths is not None:
+            t = self.ray_depth(batch["indices"], batch.get("levels"))
+            batch["depth"] = t
+            rb.metadata = {"depth": t.view(-1, 1)}
+        return rb, batch
+
+    def _draw(self, step: int) -> Tuple[RayBundle, Dict[str, torch.Tensor]]:
         """-> (RayBundle [R] with nears / fars None (the model's collider fills them), {"image": [R,3] white-blended
         rgb, "indices": int32 [R,3] = (image, y, x)}).  One kernel launch.  With levels > 1 the batch also holds "levels": int32
         [R], and (y, x) are pixel coordinates of the ray's own level."""

@@ -101,3 +101,39 @@ def normal_error(normals: torch.Tensor, accumulation: Optional[torch.Tensor], gt
     if error_map:
         res["error_map"] = emap
     return res
+
+
+def depth_error(depth: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """A view's rendered depth against its target distances along the rays (rsn_depth_error, include/rsn.h).
+
+    depth fp32 [H,W] or [H,W,1] (outputs["depth_fine"]); target fp32 [H,W] or [H*W], what ops.gather_ray_depth gives for every pixel
+    of the view, 0 = no measurement; mask uint8 or bool [H,W] or None, a capture's mask of the view: 0 = the pixel is not scored.
+
+    -> 0-d tensors on the device: depth_mae and depth_rmse over the scored pixels (NaN when there is none), depth_pixels, their
+    number, and depth_valid, their share of the view; depth_sums fp32 [3], the kernel's (sum |e|, sum e^2, count).  Two launches, no
+    device-to-host read."""
+    if depth.dtype != torch.float32 or depth.dim() not in (2, 3) or (depth.dim() == 3 and depth.shape[-1] != 1):
+        raise ValueError(f"depth must be float32 [H,W] or [H,W,1], got {depth.dtype} {tuple(depth.shape)}")
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    dev = depth.device
+    if dev.type != "cuda":
+        raise ValueError(f"depth_error runs on the GPU (rsn_depth_error); got depth on {dev}")
+    if target.dtype != torch.float32 or target.numel() != H * W:
+        raise ValueError(f"target must be float32 with {H} x {W} entries, got {target.dtype} {tuple(target.shape)}")
+    if mask is not None and (mask.dtype not in (torch.uint8, torch.bool) or mask.numel() != H * W):
+        raise ValueError(f"mask must be uint8 or bool with {H} x {W} entries, got {mask.dtype} {tuple(mask.shape)}")
+    for name, t in (("target", target), ("mask", mask)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"depth on {dev} and {name} on {t.device}")
+    if H * W < 1 or H * W > _abi.RSN_NORMAL_ERROR_MAX_PIXELS:
+        raise ValueError(f"{H} x {W} pixels: need 1 to 2^24")
+    lib = _abi.load_library()
+    d, t = depth.contiguous(), target.contiguous()
+    m = None if mask is None else mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
+    nbytes = int(lib.rsn_normal_error_workspace_bytes(H * W))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    _abi.check(lib.rsn_depth_error(H * W, _abi.ptr(d), _abi.ptr(t), _abi.ptr(m), _abi.ptr(ws), nbytes, _abi.ptr(out),
+                                   torch.cuda.current_stream(dev).cuda_stream))
+    return {"depth_mae": out[0] / out[2], "depth_rmse": torch.sqrt(out[1] / out[2]), "depth_pixels": out[2],
+            "depth_valid": out[2] / float(H * W), "depth_sums": out}

@@ -61,7 +61,11 @@ except ImportError:
             for name in ("origins", "directions", "pixel_area", "camera_indices", "nears", "fars", "times"):
                 v = getattr(self, name)
                 kw[name] = fn(v) if isinstance(v, Tensor) else v
-            return RayBundle(metadata=self.metadata, **kw)
+            # per-ray entries travel with the rays, as nerfstudio's TensorDataclass maps its dict fields ("depth": the target distance)
+            meta = self.metadata
+            if meta is not None:
+                meta = {k: (fn(v) if isinstance(v, Tensor) else v) for k, v in meta.items()}
+            return RayBundle(metadata=meta, **kw)
 
         def __getitem__(self, idx):
             return self._map(lambda t: t[idx])

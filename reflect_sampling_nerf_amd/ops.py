@@ -167,6 +167,48 @@ def distortion_backward(n_rays: int, n_dev: Optional[Tensor], n_samples: int, sp
                                       ptr(g_loss_ray), ptr(g_sigma), 1 if accumulate else 0, _stream()))
 
 
+def depth_loss_forward(n_rays: int, n_dev: Optional[Tensor], n_samples: int, euclid_bins: Tensor, sigma: Tensor, target: Tensor,
+                       depth_sigma: float) -> Tensor:
+    """-> loss_ray [R]: the DS-NeRF depth term of every ray against its target distance, unscaled (rsn_depth_loss_forward, which
+    derives the level's weights from sigma and the euclidean bins in fp64).  Rows at and past *n_dev hold zeros."""
+    lib = _abi.load_library()
+    out = (torch.empty if n_dev is None else torch.zeros)(n_rays, device=sigma.device, dtype=torch.float32)
+    check(lib.rsn_depth_loss_forward(n_rays, ptr(n_dev), n_samples, ptr(euclid_bins), ptr(sigma), ptr(target), float(depth_sigma),
+                                     ptr(out), _stream()))
+    return out
+
+
+def depth_loss_backward(n_rays: int, n_dev: Optional[Tensor], n_samples: int, euclid_bins: Tensor, sigma: Tensor, target: Tensor,
+                        depth_sigma: float, g_loss_ray: Tensor, g_sigma: Tensor, accumulate: bool = True) -> None:
+    """g_sigma [R,S] += (accumulate) or = the gradient of sum_r g_loss_ray[r] L_ray w.r.t. sigma (rsn_depth_loss_backward)."""
+    lib = _abi.load_library()
+    check(lib.rsn_depth_loss_backward(n_rays, ptr(n_dev), n_samples, ptr(euclid_bins), ptr(sigma), ptr(target), float(depth_sigma),
+                                      ptr(g_loss_ray), ptr(g_sigma), 1 if accumulate else 0, _stream()))
+
+
+def gather_ray_depth(indices: Tensor, level: Optional[Tensor], depths: Tensor, cameras: Optional[Tensor],
+                     intrinsics: Optional[tuple], has_fisheye: bool, euclidean: bool) -> Tensor:
+    """-> t [R]: the target distance along the normalised ray of every sampled pixel, 0 = no target (rsn_gather_ray_depth).
+    indices int32 [R,3], level int32 [R] or None, depths fp32 [N,H,W] on the device; cameras: the level-0 table [N,9|12] or None,
+    in which case intrinsics = (fx, fy, cx, cy) is read."""
+    lib = _abi.load_library()
+    if indices.dtype != torch.int32 or not indices.is_contiguous() or indices.dim() != 2 or indices.shape[1] != 3:
+        raise _abi.RsnError("gather_ray_depth: indices must be a contiguous int32 [R,3] tensor")
+    if level is not None and (level.dtype != torch.int32 or not level.is_contiguous() or level.numel() != indices.shape[0]):
+        raise _abi.RsnError("gather_ray_depth: level must be a contiguous int32 [R] tensor")
+    if depths.dim() != 3:
+        raise _abi.RsnError("gather_ray_depth: depths must be [N,H,W]")
+    _abi.check_f32_cuda("gather_ray_depth", depths=depths, cameras=cameras)
+    N, H, W = depths.shape
+    R = indices.shape[0]
+    stride = 0 if cameras is None else int(cameras.shape[1])
+    fx, fy, cx, cy = (0.0, 0.0, 0.0, 0.0) if cameras is not None else [float(v) for v in intrinsics]
+    t = torch.empty(R, device=depths.device, dtype=torch.float32)
+    check(lib.rsn_gather_ray_depth(R, ptr(indices), ptr(level), ptr(depths), N, H, W, ptr(cameras), stride, fx, fy, cx, cy,
+                                   1 if has_fisheye else 0, 1 if euclidean else 0, ptr(t), _stream()))
+    return t
+
+
 def reflect_setup(origins: Tensor, directions: Tensor, accumulation: Tensor, depth: Tensor, normals: Tensor,
                   roughness: Tensor, reflect_far: float) -> Dict[str, Tensor]:
     lib = _abi.load_library()

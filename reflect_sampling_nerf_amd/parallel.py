@@ -170,7 +170,8 @@ def apply_loss_warmup(model, step: int) -> None:
 
 
 _MEAN_TERMS = ("loss_mid_coarse", "loss_mid_fine", "loss_reflect_mid_coarse", "loss_reflect_mid_fine",
-               "distortion_loss_coarse", "distortion_loss_fine")  # the opt-in distortion terms are means over the rays too
+               "distortion_loss_coarse", "distortion_loss_fine",  # the opt-in distortion terms are means over the rays too
+               "depth_loss_coarse", "depth_loss_fine")  # and so are the opt-in depth terms
 
 
 def train_step(model, ray_bundle, batch, optimizer, reducer: Optional[FlatGradAllReduce], step: int,

@@ -91,6 +91,9 @@ class ReflectSamplingNeRFModel(Model):
                                               include_original=False)
         self.far = 2**8
         self.near = 1.0 / 16
+        # Standard deviation, in scene units, of the opt-in depth term (loss_coefficients["depth_loss_fine" / "depth_loss_coarse"],
+        # include/rsn.h: rsn_depth_loss_forward).  A starting point: no scene has been measured.
+        self.depth_sigma = 0.1
         self.background_color = torch.tensor([1.0, 1.0, 1.0])  # colors.WHITE
         self.rgb_loss = nn.MSELoss()
         # Checkpoints of the reference: its Model also owns torchmetrics modules (model.py:131-133: psnr, ssim,
@@ -141,7 +144,7 @@ class ReflectSamplingNeRFModel(Model):
         """Training mode: one autograd node (train_graph.GetOutputsTrain) over the HIP forward/backward kernels.
         `jitter` optionally injects the samplers' uniform draws and `bins` whole sampler outputs
         ({"fine_spacing", "fine_euclid", ...}); tests share them with the oracle / the reference's logged values."""
-        from .train_graph import DIFF_KEYS, DIST_KEYS, FUSED_KEYS, GetOutputsTrain, distortion_levels
+        from .train_graph import DEPTH_KEYS, DIFF_KEYS, DIST_KEYS, FUSED_KEYS, GetOutputsTrain, depth_levels, distortion_levels
 
         R = ray_bundle.origins.shape[0]
         o = ops._f32c(ray_bundle.origins.reshape(R, 3))
@@ -149,7 +152,14 @@ class ReflectSamplingNeRFModel(Model):
         pa = ops._f32c(ray_bundle.pixel_area.reshape(R))
         nears = ops._f32c(ray_bundle.nears.reshape(R))
         fars = ops._f32c(ray_bundle.fars.reshape(R))
-        outs = GetOutputsTrain.apply(self, o, d, pa, nears, fars, jitter, bins, *self.field.parameters())
+        # the opt-in depth term's target distances: a constant of the graph, read only when a depth coefficient is set
+        meta = getattr(ray_bundle, "metadata", None)
+        target = meta.get("depth") if isinstance(meta, dict) else None
+        self._depth_target = None if target is None else ops._f32c(target.reshape(-1))
+        try:
+            outs = GetOutputsTrain.apply(self, o, d, pa, nears, fars, jitter, bins, *self.field.parameters())
+        finally:
+            self._depth_target = None
         aux = self._train_aux
         self._train_aux = None
         outputs = type(aux)(zip(DIFF_KEYS, outs))  # LazyOutputs: depth_reflect_fine ([M, 1]) on first access
@@ -160,6 +170,7 @@ class ReflectSamplingNeRFModel(Model):
         outputs.fused = dict(zip(FUSED_KEYS, outs[len(DIFF_KEYS):]))
         # opt-in: the per-ray distortion loss of the levels whose coefficient is set (none by default: FUSED_KEYS only)
         on = [k for k, lvl in zip(DIST_KEYS, distortion_levels(self)) if lvl]
+        on += [k for k, lvl in zip(DEPTH_KEYS, depth_levels(self)) if lvl]  # and the opt-in depth term's, behind them
         outputs.fused.update(zip(on, outs[len(DIFF_KEYS) + len(FUSED_KEYS):]))
         return outputs
 
@@ -420,13 +431,14 @@ class ReflectSamplingNeRFModel(Model):
         orientation terms, scaled by config.loss_coefficients.  One fused HIP pass (train_ops.FusedLoss).
         Not in the reference, opt-in: distortion_loss_coarse / distortion_loss_fine (mip-NeRF 360 eq. 15) for the levels whose
         coefficient is set and not 0, from the training graph's per-ray terms (train_ops.distortion_loss_dict)."""
-        from .train_ops import distortion_loss_dict, fused_loss_dict, fused_ray_loss_dict
+        from .train_ops import depth_loss_dict, distortion_loss_dict, fused_loss_dict, fused_ray_loss_dict
 
         image = batch["image"].to(self.device)
         if image.shape[-1] == 4:  # RGBRenderer.blend_background with the white background colour
             image = image[..., :3] * image[..., 3:] + (1.0 - image[..., 3:])
         fused = getattr(outputs, "fused", None)
         extra = distortion_loss_dict(fused, self.config.loss_coefficients)  # {} by default; raises when set without its fused term
+        extra.update(depth_loss_dict(fused, self.config.loss_coefficients))  # likewise: the opt-in depth term (DESIGN.md 4.25)
         if fused is not None:  # outputs of this model's own training graph: the per-sample terms are already per-ray sums
             losses = fused_ray_loss_dict(outputs, fused, image, self.config.loss_coefficients)
         else:

@@ -470,9 +470,41 @@ def _distortion_backward(level, sb, eb, g_loss_ray, g_sigma):
         n, None, S, sb, eb, level["sigma"], ops._f32c(g_loss_ray), g_sigma, accumulate=True))
 
 
+# Opt-in: the DS-NeRF depth term per ray, of the coarse / the fine level against the rays' target distances (rsn_depth_loss_forward).
+# A level whose coefficient (DEPTH_COEF_KEYS) is absent or 0 is off, as above; the outputs of the levels that are on follow the
+# DIST_KEYS ones.  The target [R] is a constant of the graph: model._depth_target, which _get_outputs_train takes from
+# ray_bundle.metadata["depth"].  model.depth_sigma is the term's standard deviation in scene units.  Reflect levels never get it.
+DEPTH_KEYS = ("depth_loss_ray_coarse", "depth_loss_ray_fine")
+DEPTH_COEF_KEYS = ("depth_loss_coarse", "depth_loss_fine")
+
+
+def depth_levels(model):
+    """(coarse on, fine on): which primary levels the depth term supervises."""
+    coef = model.config.loss_coefficients
+    return tuple(float(coef.get(k, 0.0)) != 0.0 for k in DEPTH_COEF_KEYS)
+
+
+def _depth_forward(model, R, S, eb, level, target):
+    if target is None:
+        raise _abi.RsnError("a depth loss coefficient is set, but the rays carry no target: ray_bundle.metadata['depth'] ([R] or [R,1], "
+                            "distance along the ray, 0 = none) is missing")
+    if target.numel() != R:
+        raise _abi.RsnError(f"ray_bundle.metadata['depth'] has {target.numel()} entries for {R} rays")
+    return ops.timed("depth_loss_forward", {"points": R * S}, lambda: ops.depth_loss_forward(
+        R, None, S, eb, level["sigma"], target, float(model.depth_sigma)))
+
+
+def _depth_backward(model, level, eb, target, g_loss_ray, g_sigma):
+    """Adds the depth term's gradient to the g_sigma rsn_composite_backward wrote, like _distortion_backward."""
+    n, S = g_sigma.shape
+    ops.timed("depth_loss_backward", {"points": n * S}, lambda: ops.depth_loss_backward(
+        n, None, S, eb, level["sigma"], target, float(model.depth_sigma), ops._f32c(g_loss_ray), g_sigma, accumulate=True))
+
+
 class GetOutputsTrain(torch.autograd.Function):
     """inputs: (model, ray tensors, jitter dict or None, bins dict or None, *field parameters) -> tuple of DIFF_KEYS
-    tensors, then the FUSED_KEYS ones, then the DIST_KEYS ones of the levels that are on (distortion_levels: none by default).
+    tensors, then the FUSED_KEYS ones, then the DIST_KEYS ones of the levels that are on (distortion_levels: none by default),
+    then the DEPTH_KEYS ones of the levels that are on (depth_levels: none by default).
     The non-differentiable outputs are left on `model._train_aux` by forward.
     jitter: the samplers' uniform draws; bins: {"<level>_spacing", "<level>_euclid"} [n,S+1] replacing the sampler
     output of a level (the samplers' outputs are constants of the graph: PDFSampler detaches, model.py:182,317) --
@@ -490,6 +522,8 @@ class GetOutputsTrain(torch.autograd.Function):
         bins = bins or {}
         fold = fold_enabled(model)  # exact fp32: the kernels with the bottleneck folded into mlp_mid (no bottleneck rows)
         dist_c, dist_f = distortion_levels(model)
+        depth_c, depth_f = depth_levels(model)
+        target = getattr(model, "_depth_target", None) if (depth_c or depth_f) else None
 
         def pad_rows(t, n):
             """[m, ...] -> [n, ...] (m <= n), zero rows behind: device-counted launches ignore them"""
@@ -534,6 +568,7 @@ class GetOutputsTrain(torch.autograd.Function):
         cc = ops.composite(R, None, Sc, 1, CLIP, lc["sigma"], eb_c, lc["color"], level=lc, ray_losses=True)
         dl_c = ops.timed("distortion_forward", {"points": R * Sc}, lambda: ops.distortion_forward(
             R, None, Sc, sb_c, cc["weights"])) if dist_c else None
+        zl_c = _depth_forward(model, R, Sc, eb_c, lc, target) if depth_c else None
         sb_f, eb_f = level_bins("fine", R, Sf, lambda: ops.sample_pdf(
             R, None, Sc, Sf, uni.spacing, uni.tan, model.sampler_pdf.histogram_padding, nears, fars, cc["weights"], sb_c,
             jit("fine", R, Sf)))
@@ -541,6 +576,7 @@ class GetOutputsTrain(torch.autograd.Function):
         cf = ops.composite(R, None, Sf, 1, CLIP, lf["sigma"], eb_f, lf["color"], level=lf, surface=True, ray_losses=True)
         dl_f = ops.timed("distortion_forward", {"points": R * Sf}, lambda: ops.distortion_forward(
             R, None, Sf, sb_f, cf["weights"])) if dist_f else None
+        zl_f = _depth_forward(model, R, Sf, eb_f, lf, target) if depth_f else None
         rs = ops.reflect_setup(o, d, cf["accumulation"], cf["depth"], cf["normals"], cf["roughness"], float(model.far))
         # C.-F. the reflect branch runs on the M <= R rays behind the mask.  Like the eval path (model.get_outputs) every
         # launch is sized for R rays and takes the count from device memory (rs["n_masked"]).  The host never reads M: the
@@ -598,6 +634,8 @@ class GetOutputsTrain(torch.autograd.Function):
             st["sb_c"] = sb_c
         if dist_f:
             st["sb_f"] = sb_f
+        if depth_c or depth_f:
+            st["depth_target"] = target
         if getattr(model, "_keep_train_state", False):  # test hook: the sample positions this pass evaluated
             if M is None:
                 M = int(nm.item())
@@ -616,15 +654,15 @@ class GetOutputsTrain(torch.autograd.Function):
         outs = (cc["rgb"], cf["rgb"], rs["reflect_coarse"], rs["reflect_fine"], lc["pred_normals"], lf["pred_normals"],
                 lc["n_dot_d"].unsqueeze(-1), lf["n_dot_d"].unsqueeze(-1), cf["roughness"].unsqueeze(-1),
                 cc["pn_loss_ray"], cf["pn_loss_ray"], cc["ori_loss_ray"], cf["ori_loss_ray"])
-        ctx.dist = (dist_c, dist_f)
-        return outs + tuple(t for t in (dl_c, dl_f) if t is not None)
+        ctx.dist = (dist_c, dist_f, depth_c, depth_f)
+        return outs + tuple(t for t in (dl_c, dl_f, zl_c, zl_f) if t is not None)
 
     @staticmethod
     def backward(ctx, g_rgb_c, g_rgb_f, g_refl_c, g_refl_f, g_pn_c, g_pn_f, g_ndd_c, g_ndd_f, g_rough,
                  g_pnr_c=None, g_pnr_f=None, g_orr_c=None, g_orr_f=None, *g_dist):
         st, model = ctx.st, ctx.model
-        g_dist = iter(g_dist)  # one per level that is on, coarse first (forward)
-        g_dl_c, g_dl_f = (next(g_dist) if on else None for on in ctx.dist)
+        g_dist = iter(g_dist)  # one per term and level that is on: distortion coarse, fine, then depth coarse, fine (forward)
+        g_dl_c, g_dl_f, g_zl_c, g_zl_f = (next(g_dist) if on else None for on in ctx.dist)
         fld = model.field
         lib = _abi.load_library()
         R = st["R"]
@@ -691,6 +729,8 @@ class GetOutputsTrain(torch.autograd.Function):
                                  rough_samples=lf["roughness"], g_acc=g_acc)
         if g_dl_f is not None:
             _distortion_backward(lf, st["sb_f"], st["eb_f"], g_dl_f, cb["g_sigma"])
+        if g_zl_f is not None:
+            _depth_backward(model, lf, st["eb_f"], st["depth_target"], g_zl_f, cb["g_sigma"])
         gin = {"sigma": cb["g_sigma"], "color": cb["g_color"], "roughness": cb["g_rough"],
                "pred_normals": ops._f32c(g_pn_f) if g_pn_f is not None else None,
                "n_dot_d": ops._f32c(g_ndd_f.reshape(R, Sf)) if g_ndd_f is not None else None,
@@ -703,6 +743,8 @@ class GetOutputsTrain(torch.autograd.Function):
         cb = _composite_backward(R, Sc, 1, CLIP, 0, lc, st["eb_c"], cc["weights"], g_rgb_c)
         if g_dl_c is not None:
             _distortion_backward(lc, st["sb_c"], st["eb_c"], g_dl_c, cb["g_sigma"])
+        if g_zl_c is not None:
+            _depth_backward(model, lc, st["eb_c"], st["depth_target"], g_zl_c, cb["g_sigma"])
         gin = {"sigma": cb["g_sigma"], "color": cb["g_color"],
                "pred_normals": ops._f32c(g_pn_c) if g_pn_c is not None else None,
                "n_dot_d": ops._f32c(g_ndd_c.reshape(R, Sc)) if g_ndd_c is not None else None,

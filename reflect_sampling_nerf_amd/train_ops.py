@@ -169,6 +169,28 @@ def distortion_loss_dict(fused: Optional[Dict[str, Tensor]], coefficients: Dict[
     return out
 
 
+# likewise for the opt-in depth term (train_graph.DEPTH_COEF_KEYS / DEPTH_KEYS)
+DEPTH_TERMS = (("depth_loss_coarse", "depth_loss_ray_coarse"), ("depth_loss_fine", "depth_loss_ray_fine"))
+
+
+def depth_loss_dict(fused: Optional[Dict[str, Tensor]], coefficients: Dict[str, float]) -> Dict[str, Tensor]:
+    """The opt-in DS-NeRF depth terms of get_loss_dict: coef * mean over ALL the rays of the level's per-ray loss (a ray without a
+    target contributes 0 to the sum and counts in the mean, as in nerfstudio's depth loss), for every level whose coefficient is
+    present and not 0.  Device tensors, nothing is read back.  A coefficient that is set on outputs without the level's fused term
+    is an error: the term is never dropped silently."""
+    out = {}
+    for key, ray_key in DEPTH_TERMS:
+        coef = float(coefficients.get(key, 0.0))
+        if coef == 0.0:
+            continue
+        if fused is None or ray_key not in fused:
+            raise _abi.RsnError(f"loss_coefficients[{key!r}] = {coef:g}, but the outputs carry no fused {ray_key!r}: the depth loss "
+                                "exists only on the outputs of this model's own training graph (model.train(); get_outputs) for rays "
+                                "that carry a target (ray_bundle.metadata['depth'])")
+        out[key] = coef * fused[ray_key].mean()
+    return out
+
+
 def exponential_decay_lr(step: int, lr_init: float = 1e-3, lr_final: float = 1e-4, max_steps: int = 50000) -> float:
     """nerfstudio ExponentialDecayScheduler without warm-up (reference config.py:52): log-linear interpolation."""
     t = min(max(step / max_steps, 0.0), 1.0)

@@ -1,7 +1,7 @@
 """Standalone training and evaluation on Blender-format scenes and nerfstudio-format captures, without nerfstudio.
 
-    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L] [--distortion-loss X [--distortion-loss-coarse Y]]
-    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L] [--normals [--normals-suffix _normal] [--normals-space world|camera]]
+    python -m reflect_sampling_nerf_amd.trainer train --data DIR --out DIR [--steps N] [--rays 1024] [--mma f32|bf16x6|bf16] [--resume FILE|DIR] [--max-grad-norm X] [--skip-nonfinite] [--multiscale L] [--distortion-loss X [--distortion-loss-coarse Y]] [--depth-loss X [--depth-loss-coarse Y] [--depth-sigma S] [--depth-unit-scale U] [--depth-euclidean]]
+    python -m reflect_sampling_nerf_amd.trainer eval --data DIR --ckpt FILE|DIR [--split test] [--out metrics.json] [--multiscale L] [--normals [--normals-suffix _normal] [--normals-space world|camera]] [--depth [--depth-unit-scale U] [--depth-euclidean]]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --ckpt FILE|DIR --out mesh.ply [--resolution N] [--iso S]
     python -m reflect_sampling_nerf_amd.trainer export-mesh --method tsdf --ckpt FILE|DIR --out mesh.ply --data DIR | --poses FILE.json [--max-views N] [--downscale K] [--trunc T]
     python -m reflect_sampling_nerf_amd.trainer export-mesh ... --out mesh.obj --texture [--texels 8] [--min-footprint F]
@@ -70,6 +70,17 @@ coarse level's: the term pulls a ray's weights together into one compact interva
 this method.  The reflect levels never get the term (their weights are detached).  Both are off by default, and the default run has
 the launches, bytes and checkpoint keys it always had; a coefficient that is set is recorded in the checkpoint and comes back with
 --resume.
+
+`train --depth-loss X` supervises a capture with depth maps -- frames with a depth_file_path, as `ns-process-data polycam --use-depth`
+and `record3d` write them: 16-bit PNGs or .npy arrays, --depth-unit-scale U (0.001, millimetres) times the pose scale -- with the
+DS-NeRF depth term (Deng et al. 2022; include/rsn.h: rsn_depth_loss_forward / _backward) of the fine level, X times its mean over the
+batch's rays; `--depth-loss-coarse Y` adds the coarse level's.  --depth-sigma S is the term's standard deviation around the measured
+depth in scene units (0.1); --depth-euclidean says that the files hold distances along the ray, not z-depths (fisheye cameras need
+that).  X, Y and S are starting points: no scene has been measured.  With --multiscale only the full-resolution rays are supervised
+(the pyramid builds no depth levels: a design rule).  The depth files are read only when a depth flag asks for them; what is set is
+recorded in the checkpoint and comes back with --resume, and the default run has the launches, bytes and checkpoint keys it always
+had.  `eval --depth` scores every view's depth_fine against the same maps on the device (metrics.depth_error): the JSON gains
+depth_mae and depth_rmse in scene units with their _std, depth_valid, the share of supervised pixels, and the per-image values.
 
 `eval --normals` scores the geometry as the Ref-NeRF family's tables do: the scene's ground-truth normal maps (FILE_normal.png beside
 every FILE.png, multinerf's naming of the Shiny Blender scenes; --normals-suffix names another) are read with the split, and every
@@ -277,6 +288,19 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
                          "been measured on this method (default: off)")
     tr.add_argument("--distortion-loss-coarse", type=float, default=None, metavar="Y",
                     help="the same term on the coarse level's weights, times Y (default: off)")
+    tr.add_argument("--depth-loss", type=float, default=None, metavar="X",
+                    help="a capture with depth maps (depth_file_path, as ns-process-data polycam --use-depth / record3d write them): add X "
+                         "times the DS-NeRF depth term of the fine level to the objective; it pulls each supervised ray's weight to its "
+                         "measured depth.  A starting point, not measured on a scene (default: off)")
+    tr.add_argument("--depth-loss-coarse", type=float, default=None, metavar="Y",
+                    help="the same term on the coarse level, times Y (default: off)")
+    tr.add_argument("--depth-sigma", type=float, default=None, metavar="S",
+                    help="standard deviation of the depth term around the measured depth, in scene units (default 0.1: a starting point, "
+                         "not measured on a scene)")
+    tr.add_argument("--depth-unit-scale", type=float, default=None, metavar="U",
+                    help="what one unit of a depth file is in the units of the poses (default 0.001: millimetres, nerfstudio's)")
+    tr.add_argument("--depth-euclidean", action="store_true", default=None,
+                    help="the depth files hold distances along the ray, not z-depths (needed for fisheye cameras)")
     _add_data_flags(tr, train=True)
     tr.add_argument("--near", type=float, default=None, metavar="N",
                     help="near plane of the primary rays (default: 2 for a Blender-format scene, 0.05 for a capture -- a starting point, not measured on a scene)")
@@ -290,7 +314,8 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     tr.add_argument("--resume", default=None, metavar="PATH",
                     help="continue from this step-*.ckpt, or from the newest one in this run directory; --steps stays the total, and "
                          "--rays / --mma / --seed / --deterministic / --max-grad-norm / --skip-nonfinite / --multiscale / "
-                         "--distortion-loss / --distortion-loss-coarse, the ray flags (--near / --far / --primary-spacing / --primary-tan) "
+                         "--distortion-loss / --distortion-loss-coarse / --depth-loss / --depth-loss-coarse / --depth-sigma / "
+                         "--depth-euclidean, the ray flags (--near / --far / --primary-spacing / --primary-tan) "
                          "and a capture's data flags come from the checkpoint unless given")
     ev = sub.add_parser("eval", help="score a checkpoint on held-out views")
     ev.add_argument("--data", required=True, help="scene directory with transforms_{split}.json (Blender format) or transforms.json (a capture)")
@@ -313,6 +338,13 @@ def build_parser(run_defaults: bool = True) -> argparse.ArgumentParser:
     ev.add_argument("--normals-space", choices=NORMALS_SPACES, default=None,
                     help="with --normals: the frame the normal maps are written in (default world, what Shiny Blender uses; camera: "
                          "OpenGL camera axes, rotated into the world by each view's pose)")
+    ev.add_argument("--depth", action="store_true",
+                    help="a capture with depth maps: also score depth_fine against them: depth_mae, depth_rmse (scene units) and "
+                         "depth_valid, the share of supervised pixels")
+    ev.add_argument("--depth-unit-scale", type=float, default=None, metavar="U",
+                    help="with --depth: what one unit of a depth file is in the units of the poses (default: the checkpoint's, else 0.001)")
+    ev.add_argument("--depth-euclidean", action="store_true", default=None,
+                    help="with --depth: the depth files hold distances along the ray, not z-depths (default: the checkpoint's)")
     _add_occupancy_flags(ev)
     ex = sub.add_parser("export-mesh", help="write the iso-surface of a checkpoint's density as a coloured triangle mesh (PLY)")
     ex.add_argument("--ckpt", required=True, help="step-*.ckpt written by `train` (or by ns-train), or a run directory (its newest)")
@@ -431,7 +463,7 @@ def _scale_factor(args) -> float:
 CAPTURE_POSE_KEYS = ("orientation", "center", "auto_scale", "scale_factor")
 
 
-def capture_load_args(args, recorded: Optional[dict] = None):
+def capture_load_args(args, recorded: Optional[dict] = None, depths: bool = False):
     """How a command line reads a capture -> (the keyword arguments of data.load_nerfstudio_split, the settings to record).  Each of
     CAPTURE_DATA_DEFAULTS' keys: the flag if given, else the record of the checkpoint's run (`recorded`: its rsn_run entry or None),
     else the default.  When the run recorded the transform and scale it applied and no flag that bears on the poses is given, exactly
@@ -446,6 +478,10 @@ def capture_load_args(args, recorded: Optional[dict] = None):
     downscale = int(asked if asked is not None else rec.get("downscale_factor", 1))
     if downscale != 1:
         settings["downscale_factor"] = kwargs["downscale_factor"] = downscale
+    if depths:  # the depth files are read, and their unit recorded, only when a depth flag (or the resumed run's record) asks
+        asked = getattr(args, "depth_unit_scale", None)
+        settings["depth_unit_scale"] = kwargs["depth_unit_scale"] = float(asked if asked is not None else rec.get("depth_unit_scale", 1e-3))
+        kwargs["depths"] = True
     if rec.get("transform") is not None and all(given[k] is None for k in CAPTURE_POSE_KEYS):
         kwargs["applied"] = (rec["transform"], rec["scale"])
     return kwargs, settings
@@ -458,7 +494,8 @@ def capture_flags_given(args):
     return [flag for flag, attr in names if getattr(args, attr, None) is not None]
 
 
-def load_scene(ap: argparse.ArgumentParser, args, split: str, recorded: Optional[dict] = None, pixels: bool = True, **blender):
+def load_scene(ap: argparse.ArgumentParser, args, split: str, recorded: Optional[dict] = None, pixels: bool = True, depths: bool = False,
+               **blender):
     """The scene --data names -> (scene, the data settings to record: None for a Blender-format scene).  The format is detected
     (data.detect_data_format) unless --data-format says it.  blender: further arguments of load_blender_split (normals)."""
     from .data import detect_data_format, load_blender_split, load_nerfstudio_split
@@ -471,10 +508,13 @@ def load_scene(ap: argparse.ArgumentParser, args, split: str, recorded: Optional
         stray = capture_flags_given(args)
         if stray:
             ap.error(f"{args.command}: {' '.join(stray)} bear(s) on a nerfstudio-format capture; {args.data} is a Blender-format scene")
+        if depths:
+            ap.error(f"{args.command}: the depth flags need a nerfstudio-format capture with depth_file_path entries; {args.data} is a "
+                     "Blender-format scene")
         return load_blender_split(args.data, split, _scale_factor(args), **blender), None
     if blender.get("normals"):
         ap.error(f"{args.command}: --normals needs a Blender-format scene with normal maps; {args.data} is a nerfstudio-format capture")
-    kwargs, settings = capture_load_args(args, recorded)
+    kwargs, settings = capture_load_args(args, recorded, depths)
     try:  # masks and fisheye cameras are read where the file has them
         return load_nerfstudio_split(args.data, split, pixels=pixels, masks=True, fisheye=True, **kwargs), {"format": "nerfstudio", **settings}
     except FileNotFoundError as e:
@@ -725,7 +765,7 @@ def resolve_pointcloud_args(ap: argparse.ArgumentParser, args) -> dict:
 # ------------------------------------------------------------------------------------------------ train
 def _resolve_run_settings(given: dict, recorded: Optional[dict]):
     """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale / distortion_loss / distortion_loss_coarse /
-    near / far / primary_spacing / primary_tan:
+    near / far / primary_spacing / primary_tan / depth_loss / depth_loss_coarse / depth_sigma / depth_euclidean:
     the caller's value if given, else the checkpoint's, else the fresh-run default (deterministic: None = the model's own default; the
     two guard settings and the two distortion coefficients: None = off; multiscale: 1, which a checkpoint does not record).
     -> (settings, one line per given value that departs from the checkpoint's)."""
@@ -757,7 +797,9 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
           on_step: Optional[Callable[[int, torch.Tensor], None]] = None, max_grad_norm: Optional[float] = None,
           skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
           distortion_loss_coarse: Optional[float] = None, near: Optional[float] = None, far: Optional[float] = None,
-          primary_spacing: Optional[str] = None, primary_tan: Optional[float] = None, data_settings: Optional[dict] = None) -> str:
+          primary_spacing: Optional[str] = None, primary_tan: Optional[float] = None, data_settings: Optional[dict] = None,
+          depth_loss: Optional[float] = None, depth_loss_coarse: Optional[float] = None, depth_sigma: Optional[float] = None,
+          depth_euclidean: Optional[bool] = None) -> str:
     """Train on `scene` (a data.BlenderScene) up to iteration `steps` (the total, nerfstudio's max_num_iterations); returns the path
     of the last checkpoint.  Checkpoints at every step > 0 divisible by save_every and after the last step (nerfstudio's trainer
     does the same).  The loss is read back only every log_every steps: the iterations in between never wait for the GPU.
@@ -780,6 +822,14 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     config.loss_coefficients as "distortion_loss_fine" / "distortion_loss_coarse" (train_graph.DIST_COEF_KEYS), which switches the
     level's two launches on; mip-NeRF 360 uses 0.01, nerfacto 0.002, neither measured on this method.  The term reads no state beyond
     the step's own weights and bins, so the paragraph on the restored state below holds with it as it stands.
+
+    depth_loss / depth_loss_coarse: the coefficient of the DS-NeRF depth term (include/rsn.h: rsn_depth_loss_forward) of the fine / the
+    coarse level against the scene's depth maps (None: the checkpoint's when resuming, else off; 0 is off too); depth_sigma: its
+    standard deviation in scene units (None: the checkpoint's, else the model's 0.1); depth_euclidean: the maps hold distances along
+    the ray, not z-depths.  A set coefficient goes into config.loss_coefficients as "depth_loss_fine" / "depth_loss_coarse"
+    (train_graph.DEPTH_COEF_KEYS) and needs scene.depths (ValueError otherwise); with both off the scene's depth maps are not
+    uploaded and the step makes the launches it made before.  No scene has been measured: the values are starting points.  The
+    targets are a pure function of the batch's pixels, so the paragraph on the restored state below holds with the term as it stands.
 
     near / far: the collider planes of the primary rays; primary_spacing / primary_tan: their coarse sampler, "uniform" or "reciprocal"
     with s(t) = t / (1/tan + t) (checkpoint.set_primary_sampler).  None: the checkpoint's when resuming; else, for a scene with a
@@ -813,7 +863,8 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic, "max_grad_norm": max_grad_norm,
              "skip_nonfinite": skip_nonfinite, "multiscale": multiscale, "distortion_loss": distortion_loss,
              "distortion_loss_coarse": distortion_loss_coarse, "near": near, "far": far, "primary_spacing": primary_spacing,
-             "primary_tan": primary_tan}
+             "primary_tan": primary_tan, "depth_loss": depth_loss, "depth_loss_coarse": depth_loss_coarse, "depth_sigma": depth_sigma,
+             "depth_euclidean": depth_euclidean}
     first, model, ckpt, recorded = 0, None, None, None
     if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
         resume = resolve_checkpoint(resume)
@@ -841,6 +892,16 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     for key, coef in distortion.items():
         if coef is not None and not math.isfinite(float(coef)):
             raise ValueError(f"{key} must be finite, got {coef!r}")
+    depth = {"depth_loss_fine": cfg["depth_loss"], "depth_loss_coarse": cfg["depth_loss_coarse"]}
+    for key, coef in depth.items():
+        if coef is not None and not math.isfinite(float(coef)):
+            raise ValueError(f"{key} must be finite, got {coef!r}")
+    depth_on = {key: float(coef) for key, coef in depth.items() if coef is not None and float(coef) != 0.0}
+    if cfg["depth_sigma"] is not None and not (math.isfinite(float(cfg["depth_sigma"])) and float(cfg["depth_sigma"]) > 0.0):
+        raise ValueError(f"depth_sigma must be a positive finite number, got {cfg['depth_sigma']!r}")
+    if depth_on and getattr(scene, "depths", None) is None:
+        raise ValueError(f"{' / '.join(depth_on)} set, but the scene has no depth maps (scene.depths is None): load it with "
+                         "load_nerfstudio_split(..., depths=True) or build it with BlenderScene.from_arrays(..., depths=...)")
     if mma not in MMA_CHOICES:
         raise ValueError(f"mma must be one of {MMA_CHOICES}, got {mma!r}")
     pyramid_layout(scene.num_images, scene.height, scene.width, multiscale)  # a size the levels do not divide ends here, on the host
@@ -859,7 +920,15 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     on = {key: float(coef) for key, coef in distortion.items() if coef is not None and float(coef) != 0.0}
     if on:  # (off: the dictionary stays as it is, without the keys.)  A copy: a model_config the caller shares between runs stays as it was
         model.config.loss_coefficients = dict(model.config.loss_coefficients, **on)
-    dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed, levels=multiscale)
+    if depth_on:
+        model.config.loss_coefficients = dict(model.config.loss_coefficients, **depth_on)
+        if cfg["depth_sigma"] is not None:
+            model.depth_sigma = float(cfg["depth_sigma"])
+    elif getattr(scene, "depths", None) is not None:  # the term is off: no upload, no gather launch, the batches as they always were
+        import dataclasses
+
+        scene = dataclasses.replace(scene, depths=None)
+    dm = RayDataManager(scene, dev, num_rays_per_batch=rays, seed=seed, levels=multiscale, depth_euclidean=bool(cfg["depth_euclidean"]))
     params = model.get_param_groups()["fields"]
     name_of = {id(p): n for n, p in model.named_parameters()}
     optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000,  # config.py:50-53
@@ -874,6 +943,10 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     for key, coef in distortion.items():
         if coef is not None and float(coef) != 0.0:
             settings += f" {key} {float(coef):g}"
+    for key, coef in depth_on.items():
+        settings += f" {key} {coef:g}"
+    if depth_on:
+        settings += f" depth_sigma {float(model.depth_sigma):g}" + (" depth_euclidean True" if cfg["depth_euclidean"] else "")
     for k in RAY_KEYS:
         if rays_cast[k] is not None:
             settings += f" {k} {rays_cast[k]}"
@@ -921,7 +994,9 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
             last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
                                    make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite, multiscale,
                                                   distortion["distortion_loss_fine"], distortion["distortion_loss_coarse"],
-                                                  rays_and_data={**rays_cast, "data": data_record}))
+                                                  rays_and_data={**rays_cast, "data": data_record},
+                                                  depth={"depth_loss": depth["depth_loss_fine"], "depth_loss_coarse": depth["depth_loss_coarse"],
+                                                         "depth_sigma": cfg["depth_sigma"], "depth_euclidean": cfg["depth_euclidean"]}))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -944,6 +1019,13 @@ GEOMETRY_NOTE = ("normal_mae is the alpha-weighted mean angle in degrees between
                  "not folded into a per-scale mean), results hold their mean and unbiased standard deviation over the views, views without "
                  "a pixel to score (normal_mae NaN) left out of normal_mae and counted out of normal_mae_views; the analytic (density-"
                  "gradient) normals are not scored: eval mode does not form them")
+DEPTH_KEYS = ("depth_mae", "depth_rmse", "depth_valid")  # per_image, level 0
+DEPTH_NOTE = ("depth_mae / depth_rmse are the mean absolute and the root mean square difference, in scene units, between depth_fine (the "
+              "fine level's expected distance along the ray) and the distance along the ray that the view's depth map gives the pixel "
+              "(a z-depth times the length of the pixel's un-normalised camera-space direction, unless the maps are euclidean), over the "
+              "pixels with a measurement (depth > 0) and, where the split has masks, a live mask byte; depth_valid is their share of the "
+              "view; scored on the full-resolution render only; results hold the mean and the unbiased standard deviation over the views "
+              "with a scored pixel")
 NORMAL_ERROR_DISPLAY_DEG = 45.0  # the error tile of NNNN_normals.png saturates here: a display range, not a measurement
 
 
@@ -986,7 +1068,7 @@ def eval_level_sizes(scene, multiscale: int):
 
 def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Optional[str] = None, device="cuda:0",
              model_config=None, occupancy: Optional[dict] = None, multiscale: int = 1, normals: bool = False,
-             normals_space: str = "world") -> dict:
+             normals_space: str = "world", depth: bool = False, depth_euclidean: bool = False) -> dict:
     """Score the checkpoint (a file, or the latest of a run directory) on every view of `scene` (a data.BlenderScene); -> ns-eval-
     shaped dict.  occupancy: None, or the settings of resolve_occupancy_args: the views are rendered with empty-space skipping and
     the dict gains an "occupancy" entry.  A scene with a camera table (a capture) is rendered through its own cameras; the occupancy
@@ -1007,7 +1089,17 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     A scene with masks (a capture's): psnr / ssim stay those of the whole image, as nerfstudio reports them; every level-0 entry of
     per_image gains psnr_masked, the fine PSNR over the live pixels alone (nan for a view without one), and results psnr_masked and
     psnr_masked_std over the views that have one.  It is formed on the device from the tensors of the view and read once, after the
-    last view.  Without masks nothing is added."""
+    last view.  Without masks nothing is added.
+
+    depth=True: the depth metrics of metrics.depth_error (rsn_depth_error) against scene.depths (ValueError, before the checkpoint is
+    read, when the scene has none): every view's depth_fine against the distance along the ray its depth map gives every pixel
+    (RayDataManager.view_ray_depth; depth_euclidean: the maps hold such distances already, not z-depths), over the pixels with a
+    measurement and, where the split has masks, a live mask byte.  Every level-0 entry of per_image gains depth_mae, depth_rmse (scene
+    units) and depth_valid, the share of the view's pixels that were scored; results gains depth_mae, depth_rmse (+ _std, over the views
+    with a scored pixel) and depth_valid (the mean share), and the dict a "depth" entry (DEPTH_NOTE).  The figures are formed on the
+    device and read once, after the last view.  depth=False is the evaluation without any of it: the same launches, keys and bytes."""
+    import dataclasses
+
     from . import metrics
     from .data import RayDataManager
 
@@ -1015,11 +1107,17 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     sizes = eval_level_sizes(scene, multiscale)
     if normals:
         check_normals_request(scene, normals_space)
+    if depth and getattr(scene, "depths", None) is None:
+        raise ValueError("depth=True needs a scene with depth maps (scene.depths is None): load it with "
+                         "load_nerfstudio_split(..., depths=True) or build it with BlenderScene.from_arrays(..., depths=...)")
+    if not depth and getattr(scene, "depths", None) is not None:
+        scene = dataclasses.replace(scene, depths=None)  # nothing is uploaded
     dev = torch.device(device)
     ckpt, model, step = open_checkpoint(ckpt, model_config, dev)
     model.config.eval_num_rays_per_chunk = EVAL_CHUNK
-    dm = RayDataManager(scene, dev, levels=multiscale, live_lists=False)
+    dm = RayDataManager(scene, dev, levels=multiscale, live_lists=False, depth_euclidean=depth_euclidean)
     masked = []  # (entry of per_image, device scalar)
+    depth_scores = []  # (entry of per_image, device [3]: mae, rmse, valid share)
     n = scene.num_images if max_images is None else min(int(max_images), scene.num_images)
     if occupancy is not None:
         from .occupancy import attach_occupancy
@@ -1048,6 +1146,9 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
                 _save_normals_panel(os.path.join(save_images, f"{i:04d}_normals.png"), outputs, dm.normal_image(i), dm.images[i],
                                     geo["error_map"])
         per_image.append({"image": i, **({"level": level} if multiscale > 1 else {}), **m})
+        if depth and level == 0:
+            de = metrics.depth_error(outputs["depth_fine"], dm.view_ray_depth(i), dm.mask_image(i) if dm.masks is not None else None)
+            depth_scores.append((per_image[-1], torch.stack([de[k] for k in DEPTH_KEYS])))
         if dm.masks is not None and level == 0:
             live = dm.mask_image(i).to(torch.float32).unsqueeze(-1)
             err = ((torch.clip(outputs["mid_reflect_fine"], 0.0, 1.0) - _white(gt)) ** 2 * live).sum() / (3.0 * live.sum())  # 0 / 0 = nan
@@ -1061,7 +1162,10 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     if masked:
         for (entry, _), v in zip(masked, torch.stack([v for _, v in masked]).cpu().tolist()):  # the one read of the masked scores
             entry["psnr_masked"] = float(v)
-    keys = [k for k in per_image[0] if k not in ("image", "level", "psnr_masked") + GEOMETRY_KEYS] if per_image else []
+    if depth_scores:
+        for (entry, _), v in zip(depth_scores, torch.stack([v for _, v in depth_scores]).cpu().tolist()):  # the one read of the depth scores
+            entry.update({k: float(x) for k, x in zip(DEPTH_KEYS, v)})
+    keys = [k for k in per_image[0] if k not in ("image", "level", "psnr_masked") + GEOMETRY_KEYS + DEPTH_KEYS] if per_image else []
 
     def mean_std(v):
         v = np.asarray(v, dtype=np.float64)
@@ -1085,6 +1189,12 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         results["normal_mae"], results["normal_mae_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
         results["normal_mae_views"] = len(counted)
         results["alpha_mae"], results["alpha_mae_std"] = mean_std([p["alpha_mae"] for p in scored]) if scored else (float("nan"), float("nan"))
+    if depth:
+        scored = [p for p, _ in depth_scores]
+        for k in ("depth_mae", "depth_rmse"):
+            counted = [p[k] for p in scored if not math.isnan(p[k])]
+            results[k], results[k + "_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
+        results["depth_valid"] = float(np.mean([p["depth_valid"] for p in scored])) if scored else float("nan")
     res = {"experiment_name": os.path.basename(os.path.dirname(os.path.abspath(ckpt))), "method_name": METHOD_NAME,
            "checkpoint": ckpt, "step": step, "results": results, "not_computed": {"fine_lpips": LPIPS_NOTE},
            "per_image": per_image}
@@ -1094,6 +1204,8 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         res["occupancy"] = model.occupancy.describe()
     if normals:
         res["geometry"] = {"normals_space": normals_space, "note": GEOMETRY_NOTE}
+    if depth:
+        res["depth"] = {"euclidean": bool(depth_euclidean), "note": DEPTH_NOTE}
     return res
 
 
@@ -1113,6 +1225,12 @@ def main(argv=None) -> int:
         ap.error(f"train: --primary-tan {args.primary_tan}: need a value above 0")
     if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
         ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
+    if args.command == "eval" and not args.depth:
+        stray = [f for f, v in (("--depth-unit-scale", args.depth_unit_scale), ("--depth-euclidean", args.depth_euclidean)) if v is not None]
+        if stray:
+            ap.error(f"eval: {' '.join(stray)} need(s) --depth")
+    if args.command == "eval" and args.normals and args.depth:
+        ap.error("eval: --normals scores a Blender-format scene and --depth a nerfstudio-format capture; give one of them")
     if args.command == "eval" and not args.normals:
         stray = [f for f, v in (("--normals-suffix", args.normals_suffix), ("--normals-space", args.normals_space)) if v is not None]
         if stray:
@@ -1123,7 +1241,18 @@ def main(argv=None) -> int:
         print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
         return 2
     if args.command == "train":
-        scene, data_settings = load_scene(ap, args, "train", read_run_state(args.resume) if args.resume is not None else None)
+        resumed = read_run_state(args.resume) if args.resume is not None else None
+        depth_flags = [f for f, v in (("--depth-loss", args.depth_loss), ("--depth-loss-coarse", args.depth_loss_coarse)) if v]
+        stray = [f for f, v in (("--depth-sigma", args.depth_sigma), ("--depth-unit-scale", args.depth_unit_scale),
+                                ("--depth-euclidean", args.depth_euclidean)) if v is not None]
+        want_depth = bool(depth_flags) or any((resumed or {}).get(k) for k in ("depth_loss", "depth_loss_coarse"))
+        if stray and not want_depth:
+            ap.error(f"train: {' '.join(stray)} need(s) --depth-loss or --depth-loss-coarse")
+        if args.depth_sigma is not None and not args.depth_sigma > 0.0:
+            ap.error(f"train: --depth-sigma {args.depth_sigma}: need a value above 0")
+        scene, data_settings = load_scene(ap, args, "train", resumed, depths=want_depth)
+        if want_depth and scene.depths is None:
+            ap.error(f"train: {' '.join(depth_flags) or 'the resumed run'} needs depth maps, and no frame of {args.data} has a depth_file_path")
         print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}"
               + ("" if scene.cameras is None else f" (image 0; a capture with {len(np.unique(scene.cameras, axis=0))} distinct camera(s), "
                                                   f"{int(np.any(scene.cameras[:, 4:] != 0.0, axis=1).sum())} image(s) with lens distortion)"))
@@ -1138,7 +1267,9 @@ def main(argv=None) -> int:
               log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume,
               max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None, multiscale=given.multiscale,
               distortion_loss=args.distortion_loss, distortion_loss_coarse=args.distortion_loss_coarse, near=args.near, far=args.far,
-              primary_spacing=args.primary_spacing, primary_tan=args.primary_tan, data_settings=data_settings)
+              primary_spacing=args.primary_spacing, primary_tan=args.primary_tan, data_settings=data_settings,
+              depth_loss=args.depth_loss, depth_loss_coarse=args.depth_loss_coarse, depth_sigma=args.depth_sigma,
+              depth_euclidean=args.depth_euclidean)
         return 0
     if args.command == "export-mesh":
         from . import mesh
@@ -1205,12 +1336,17 @@ def main(argv=None) -> int:
         scene, _ = load_scene(ap, args, args.split, recorded, normals=True,
                               normals_suffix=DEFAULT_NORMALS_SUFFIX if args.normals_suffix is None else args.normals_suffix)
     else:
-        scene, _ = load_scene(ap, args, args.split, recorded)
+        scene, _ = load_scene(ap, args, args.split, recorded, depths=args.depth)
+    if args.depth and scene.depths is None:
+        ap.error(f"eval: --depth needs depth maps, and no frame of the {args.split} split of {args.data} has a depth_file_path")
     try:
         eval_level_sizes(scene, args.multiscale)
     except ValueError as e:
         ap.error(f"eval: {e}")
     geometry = dict(normals=True, normals_space=args.normals_space or "world") if args.normals else {}
+    if args.depth:
+        euclid = args.depth_euclidean if args.depth_euclidean is not None else bool((recorded or {}).get("depth_euclidean"))
+        geometry.update(depth=True, depth_euclidean=bool(euclid))
     res = evaluate(scene, args.ckpt, max_images=args.max_images, save_images=args.save_images, occupancy=occupancy,
                    multiscale=args.multiscale, **geometry)
     with open(args.out, "w") as fh:
@@ -1223,6 +1359,8 @@ def main(argv=None) -> int:
                    and not math.isnan(r[k])) + f"  ({len(res['per_image'])} images) -> {args.out}")
     if args.normals:
         print(f"normal_mae {r['normal_mae']:.3f} deg over {r['normal_mae_views']} views, alpha_mae {r['alpha_mae']:.4f}")
+    if args.depth:
+        print(f"depth_mae {r['depth_mae']:.5f} depth_rmse {r['depth_rmse']:.5f} over {100.0 * r['depth_valid']:.1f} % of the pixels")
     return 0
 
 
