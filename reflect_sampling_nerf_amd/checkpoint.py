@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import os
 import re
-from typing import Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import torch
 
@@ -47,56 +47,97 @@ def resolve_checkpoint(path: str) -> str:
     return latest_checkpoint(path) if os.path.isdir(path) else path
 
 
-def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, max_grad_norm: Optional[float] = None,
-                   skip_nonfinite: Optional[bool] = None, multiscale: Optional[int] = None, distortion_loss: Optional[float] = None,
-                   distortion_loss_coarse: Optional[float] = None, rays_and_data: Optional[dict] = None,
-                   depth: Optional[dict] = None) -> dict:
+def _when_set(v):
+    return None if v is None else float(v)
+
+
+def _when_true(v):
+    return True if v else None
+
+
+def _above_one(v):
+    return int(v) if v is not None and int(v) > 1 else None
+
+
+def _coefficient(v):
+    return float(v) if v is not None and float(v) != 0.0 else None
+
+
+def _as_it_is(v):
+    return v
+
+
+class RunSetting(NamedTuple):
+    default: object  # what a fresh run gets when it is not told (None: off, or the model's own)
+    record: Callable  # the value -> what `rsn_run` holds for it; None: the key is left out
+    term: Optional[str] = None  # the part of the run it belongs to; a loss term's further settings are recorded only with a coefficient
+
+
+PRIMARY_RAYS = "primary rays"
+# The settings of a run, each stated once: `train` takes them by these names, --resume restores them, make_run_state records them
+# (in this order) and the line that starts a run prints them.  rays / mma / seed: reflect_sampling_nerf_config.py:36-41.
+# An unguarded, single-scale run without the opt-in loss terms on a Blender-format scene records the first four alone: the keys
+# its checkpoints always had.
+RUN_SETTINGS = {
+    "rays": RunSetting(1024, int),
+    "mma": RunSetting("f32", str),
+    "seed": RunSetting(0, int),
+    "deterministic": RunSetting(None, bool),
+    "max_grad_norm": RunSetting(None, _when_set),  # the optimiser's guard
+    "skip_nonfinite": RunSetting(None, _when_true),
+    "multiscale": RunSetting(1, _above_one),  # the number of pyramid levels the rays are drawn from
+    "distortion_loss": RunSetting(None, _coefficient, "distortion"),  # the opt-in distortion term, fine / coarse level
+    "distortion_loss_coarse": RunSetting(None, _coefficient, "distortion"),
+    "depth_loss": RunSetting(None, _coefficient, "depth"),  # the opt-in depth term
+    "depth_loss_coarse": RunSetting(None, _coefficient, "depth"),
+    "depth_sigma": RunSetting(None, _when_set, "depth"),
+    "depth_euclidean": RunSetting(None, _when_true, "depth"),
+    "near": RunSetting(None, _as_it_is, PRIMARY_RAYS),  # the collider planes
+    "far": RunSetting(None, _as_it_is, PRIMARY_RAYS),
+    "primary_spacing": RunSetting(None, _as_it_is, PRIMARY_RAYS),  # the coarse sampler of the primary rays
+    "primary_tan": RunSetting(None, _as_it_is, PRIMARY_RAYS),
+}
+COEFFICIENTS = tuple(k for k, s in RUN_SETTINGS.items() if s.record is _coefficient)
+RAY_KEYS = tuple(k for k, s in RUN_SETTINGS.items() if s.term == PRIMARY_RAYS)
+LOSS_TERMS = {RUN_SETTINGS[k].term for k in COEFFICIENTS}
+PRIMARY_SPACINGS = ("uniform", "reciprocal")
+
+
+def recorded_settings(settings: dict) -> dict:
+    """The entries of RUN_SETTINGS that `rsn_run` holds for a run with these settings, in the table's order: each by its own rule,
+    and a loss term's further settings only beside one of its coefficients.  Of the optional ones an absent name counts as None;
+    KeyError for a name the table does not have."""
+    unknown = sorted(set(settings) - set(RUN_SETTINGS))
+    if unknown:
+        raise KeyError(f"unknown run settings {unknown}")
+    out, terms_on = {}, set()
+    for name, s in RUN_SETTINGS.items():
+        v = s.record(settings.get(name))
+        if v is None:
+            continue
+        if name in COEFFICIENTS:
+            terms_on.add(s.term)
+        if s.term not in LOSS_TERMS or s.term in terms_on:
+            out[name] = v
+    return out
+
+
+def make_run_state(seed: int, rays: int, mma: str, deterministic: bool, device, data: Optional[dict] = None, **settings) -> dict:
     """What a checkpoint needs beyond model, optimiser and step for `train(resume=...)` to continue with the uninterrupted run's
     bits: the run's settings and the two torch generators as they stand now (i.e. after the checkpoint's step; the CUDA generator's
     seed and offset live on the host, reading them waits for nothing).  cuda_rng_state is None for a device without one.
-    max_grad_norm / skip_nonfinite (the optimiser's guard) are recorded only when set: an unguarded run's entry has the keys it
-    always had.  Likewise multiscale (the number of pyramid levels the rays are drawn from): only when above 1, and distortion_loss /
-    distortion_loss_coarse (the coefficients of the opt-in distortion term): only when set and not 0.  rays_and_data: the entries
-    of RAY_KEYS ("near", "far": the collider planes; "primary_spacing", "primary_tan": the coarse sampler of the primary rays) and
-    "data" (how a capture was read: format, orientation, center, auto_scale, scale_factor, train_split_fraction, eval_mode, and the
-    transform [3][4] and scale that were applied) that are not None are recorded; a Blender-format run with its defaults has none.
-    depth: the settings of the opt-in depth term, DEPTH_RUN_KEYS: "depth_loss" / "depth_loss_coarse" (the coefficients) are recorded
-    when set and not 0, and only with one of them "depth_sigma" (when set) and "depth_euclidean" (when true); a run without the term
-    records none of them."""
+    settings: the further entries of RUN_SETTINGS, each by its own name and recorded by its own rule there (recorded_settings): a
+    run that sets none of them has the keys it always had.  max_grad_norm when set and skip_nonfinite when true; multiscale above
+    1; a coefficient -- distortion_loss / distortion_loss_coarse, depth_loss / depth_loss_coarse -- when set and not 0, and only
+    with a depth coefficient depth_sigma (when set) and depth_euclidean (when true); near / far / primary_spacing / primary_tan
+    when not None.  data: how a capture was read (format, orientation, center, auto_scale, scale_factor, train_split_fraction,
+    eval_mode, and the transform [3][4] and scale that were applied), recorded when not None; a Blender-format run has none."""
     dev = torch.device(device)
-    state = {"version": RUN_STATE_VERSION, "seed": int(seed), "rays": int(rays), "mma": str(mma), "deterministic": bool(deterministic),
-             "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
-             "cpu_rng_state": torch.get_rng_state()}
-    if max_grad_norm is not None:
-        state["max_grad_norm"] = float(max_grad_norm)
-    if skip_nonfinite:
-        state["skip_nonfinite"] = True
-    if multiscale is not None and int(multiscale) > 1:
-        state["multiscale"] = int(multiscale)
-    for key, coef in (("distortion_loss", distortion_loss), ("distortion_loss_coarse", distortion_loss_coarse)):
-        if coef is not None and float(coef) != 0.0:
-            state[key] = float(coef)
-    depth = depth or {}
-    if set(depth) - set(DEPTH_RUN_KEYS):
-        raise KeyError(f"depth: unknown entries {sorted(set(depth) - set(DEPTH_RUN_KEYS))}")
-    coefs = {k: float(depth[k]) for k in ("depth_loss", "depth_loss_coarse") if depth.get(k) is not None and float(depth[k]) != 0.0}
-    if coefs:
-        state.update(coefs)
-        if depth.get("depth_sigma") is not None:
-            state["depth_sigma"] = float(depth["depth_sigma"])
-        if depth.get("depth_euclidean"):
-            state["depth_euclidean"] = True
-    for key, v in (rays_and_data or {}).items():
-        if key not in RAY_KEYS + ("data",):
-            raise KeyError(f"rays_and_data: unknown entry {key!r}")
-        if v is not None:
-            state[key] = v
+    state = {"version": RUN_STATE_VERSION, "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+             "cpu_rng_state": torch.get_rng_state(), **recorded_settings(dict(settings, seed=seed, rays=rays, mma=mma, deterministic=deterministic))}
+    if data is not None:
+        state["data"] = data
     return state
-
-
-RAY_KEYS = ("near", "far", "primary_spacing", "primary_tan")
-DEPTH_RUN_KEYS = ("depth_loss", "depth_loss_coarse", "depth_sigma", "depth_euclidean")
-PRIMARY_SPACINGS = ("uniform", "reciprocal")
 
 
 def read_run_state(path: str) -> Optional[dict]:

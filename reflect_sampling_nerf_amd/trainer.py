@@ -145,14 +145,15 @@ from typing import Callable, Optional
 import numpy as np
 import torch
 
-from .checkpoint import (PRIMARY_SPACINGS, RAY_KEYS, RUN_STATE_KEY, RUN_STATE_VERSION, _load_pipeline, _Pipeline,  # noqa: F401 (re-exported)
-                         checkpoint_path, config_for_checkpoint, config_with_planes, latest_checkpoint, load_checkpoint, make_model,
-                         make_run_state, open_checkpoint, read_run_state, resolve_checkpoint, save_checkpoint, set_primary_sampler)
+from .checkpoint import (COEFFICIENTS, PRIMARY_SPACINGS, RAY_KEYS, RUN_SETTINGS, RUN_STATE_KEY, RUN_STATE_VERSION,  # noqa: F401 (re-exported)
+                         _load_pipeline, _Pipeline, checkpoint_path, config_for_checkpoint, config_with_planes, latest_checkpoint,
+                         load_checkpoint, make_model, make_run_state, open_checkpoint, read_run_state, recorded_settings,
+                         resolve_checkpoint, save_checkpoint, set_primary_sampler)
 
 METHOD_NAME = "reflect-sampling-nerf"
 MMA_CHOICES = ("f32", "bf16x6", "bf16")
 EVAL_CHUNK = 1024  # reflect_sampling_nerf_config.py:41 eval_num_rays_per_chunk
-RUN_DEFAULTS = {"rays": 1024, "mma": "f32", "seed": 0, "multiscale": 1}  # reflect_sampling_nerf_config.py:36-41; what a fresh run gets when not told
+RUN_DEFAULTS = {k: s.default for k, s in RUN_SETTINGS.items() if s.default is not None}  # what a fresh run gets when not told (the others: None)
 DEFAULT_NORMALS_SUFFIX = "_normal"  # multinerf / Shiny Blender: r_0.png beside r_0_normal.png
 NORMALS_SPACES = ("world", "camera")
 # A capture (a nerfstudio-format transforms.json): how it is read when nothing says otherwise (nerfstudio's NerfstudioDataParserConfig) ...
@@ -174,6 +175,19 @@ LPIPS_NOTE = "fine_lpips not computed: LPIPS needs pretrained network weights th
 
 
 OCCUPANCY_SUBFLAGS = ("occupancy_resolution", "occupancy_sigma", "occupancy_dilate", "occupancy_bounds")
+
+
+def _flags_need(ap: argparse.ArgumentParser, args, names, needed: str, more=()) -> None:
+    """The error for flags that have no meaning without `needed`: those of `names` (attributes of args; --like-this on the command
+    line) that were given, and `more` (flag texts the caller found given by a test of its own)."""
+    stray = ["--" + n.replace("_", "-") for n in names if getattr(args, n, None) is not None] + list(more)
+    if stray:
+        ap.error(f"{args.command}: {' '.join(stray)} need(s) {needed}")
+
+
+def _check_box(ap: argparse.ArgumentParser, args, flag: str, b) -> None:
+    if b is not None and not (all(math.isfinite(x) for x in b) and all(b[3 + a] > b[a] for a in range(3))):
+        ap.error(f"{args.command}: {flag} needs X0 Y0 Z0 X1 Y1 Z1 with every upper bound above its lower one")
 
 
 def _add_occupancy_flags(p: argparse.ArgumentParser) -> None:
@@ -202,9 +216,7 @@ def resolve_occupancy_args(ap: argparse.ArgumentParser, args) -> Optional[dict]:
 
     samples = bool(getattr(args, "skip_empty_samples", False))
     if not (getattr(args, "skip_empty", False) or samples):
-        given = ["--" + f.replace("_", "-") for f in OCCUPANCY_SUBFLAGS if getattr(args, f, None) is not None]
-        if given:
-            ap.error(f"{args.command}: {' '.join(given)} need(s) --skip-empty")
+        _flags_need(ap, args, OCCUPANCY_SUBFLAGS, "--skip-empty")
         return None
     res = DEFAULT_RESOLUTION if args.occupancy_resolution is None else args.occupancy_resolution
     sigma = DEFAULT_SIGMA if args.occupancy_sigma is None else args.occupancy_sigma
@@ -213,8 +225,7 @@ def resolve_occupancy_args(ap: argparse.ArgumentParser, args) -> Optional[dict]:
     if not math.isfinite(sigma):
         ap.error(f"{args.command}: --occupancy-sigma {sigma}: need a finite value")
     b = args.occupancy_bounds
-    if b is not None and not (all(math.isfinite(x) for x in b) and all(b[3 + a] > b[a] for a in range(3))):
-        ap.error(f"{args.command}: --occupancy-bounds needs X0 Y0 Z0 X1 Y1 Z1 with every upper bound above its lower one")
+    _check_box(ap, args, "--occupancy-bounds", b)
     settings = {"resolution": int(res), "sigma": float(sigma), "dilate": DEFAULT_DILATE if args.occupancy_dilate is None else args.occupancy_dilate,
                 "bounds": None if b is None else tuple(float(x) for x in b)}
     if samples:
@@ -530,31 +541,10 @@ def resolve_render_args(ap: argparse.ArgumentParser, args) -> dict:
 
     if args.poses is not None and args.data is not None:
         ap.error("render: give --poses or --data, not both")
-    src = None
-    capture = None
-    if args.data is not None:
-        from .data import detect_data_format
-
-        try:
-            if detect_data_format(args.data, args.data_format) == "nerfstudio":
-                capture = _capture_cameras(ap, args)
-        except FileNotFoundError as e:
-            ap.error(f"render: {e}")
+    capture, src = _camera_source(ap, args)
     if capture is not None:  # the cameras of the file's frames, in the frame the checkpoint was trained in
         src = {"c2w": capture.c2w, "width": capture.width, "height": capture.height,
                "camera_angle_x": 2.0 * math.atan(0.5 * capture.width / capture.fx), "file_paths": capture.file_paths}
-    elif args.poses is not None:
-        src = render.load_poses(args.poses, _scale_factor(args))
-    elif args.data is not None:
-        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), _scale_factor(args))
-        if src["width"] is None or src["height"] is None:  # Blender-format files carry no size: the first image's header has it
-            rel = src["file_paths"][0]
-            path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
-            if os.path.isfile(path):
-                from PIL import Image
-
-                with Image.open(path) as img:
-                    src["width"], src["height"] = (int(v) for v in img.size)
     width = args.width if args.width is not None else (src or {}).get("width")
     height = args.height if args.height is not None else (src or {}).get("height")
     fov = math.radians(args.fov_x) if args.fov_x is not None else (src or {}).get("camera_angle_x")
@@ -612,6 +602,35 @@ def _capture_cameras(ap: argparse.ArgumentParser, args):
     return scene
 
 
+def _camera_source(ap: argparse.ArgumentParser, args, capture_errors=(FileNotFoundError,)):
+    """Where --data [--split] [--data-format] / --poses / --scale-factor take a command's cameras from (the caller has seen to it
+    that at most one of --data and --poses is given) -> (the capture's scene or None, what render.load_poses reads of the file or
+    None): one of the two, or neither without both flags.  A Blender-format file carries no size: width and height are then the
+    first image's, where there is one.  Host work only (JSON and image headers).  capture_errors: what reading a capture may raise
+    that becomes an argparse error of the command."""
+    from . import render
+
+    if args.data is None:
+        return None, None if args.poses is None else render.load_poses(args.poses, _scale_factor(args))
+    from .data import detect_data_format
+
+    try:
+        if detect_data_format(args.data, args.data_format) == "nerfstudio":
+            return _capture_cameras(ap, args), None
+    except capture_errors as e:
+        ap.error(f"{args.command}: {e}")
+    src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), _scale_factor(args))
+    if src["width"] is None or src["height"] is None:
+        rel = src["file_paths"][0] or ""
+        path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
+        if os.path.isfile(path):
+            from PIL import Image
+
+            with Image.open(path) as img:
+                src["width"], src["height"] = (int(v) for v in img.size)
+    return None, src
+
+
 TSDF_ONLY_FLAGS = ("data", "poses", "max_views", "trunc", "min_weight", "ray_chunk")
 TEXTURE_ONLY_FLAGS = ("texels", "min_footprint")
 
@@ -623,9 +642,7 @@ def resolve_texture_args(ap: argparse.ArgumentParser, args) -> None:
     from . import mesh, texture
 
     if not args.texture:
-        given = ["--" + f.replace("_", "-") for f in TEXTURE_ONLY_FLAGS if getattr(args, f, None) is not None]
-        if given:
-            ap.error(f"export-mesh: {' '.join(given)} need(s) --texture")
+        _flags_need(ap, args, TEXTURE_ONLY_FLAGS, "--texture")
         return
     if not args.out.lower().endswith(".obj"):
         ap.error(f"export-mesh: --texture writes an OBJ with its MTL and PNG maps: --out {args.out} must end in .obj")
@@ -663,11 +680,7 @@ def resolve_export_cameras(ap: argparse.ArgumentParser, args) -> Optional[dict]:
     [F,3,4], "width", "height", "fx", "fy", "cx", "cy"} after --max-views and --downscale.  Host work only (JSON and one image
     header).  What the command line leaves open and no file settles is an argparse error that names the option."""
     if args.method != "tsdf":
-        given = ["--" + f.replace("_", "-") for f in TSDF_ONLY_FLAGS if getattr(args, f, None) is not None]
-        if args.downscale != 1:
-            given.append("--downscale")
-        if given:
-            ap.error(f"export-mesh: {' '.join(given)} need(s) --method tsdf")
+        _flags_need(ap, args, TSDF_ONLY_FLAGS, "--method tsdf", more=["--downscale"] if args.downscale != 1 else [])
         return None
     if args.iso is not None:
         ap.error("export-mesh: --iso is the density route's level; --method tsdf has none")
@@ -689,51 +702,31 @@ def export_cameras_from_args(ap: argparse.ArgumentParser, args, command: str, ne
 
     if (args.poses is None) == (args.data is None):
         ap.error(f"{command}: {needs} cameras: give --data DIR or --poses FILE.json (one of them)")
-    capture = None
-    if args.data is not None:
-        from .data import detect_data_format, shared_pinhole
+    capture, src = _camera_source(ap, args, capture_errors=(FileNotFoundError, ValueError))
+    if capture is not None:
+        from .data import shared_pinhole
 
         try:
-            if detect_data_format(args.data, args.data_format) == "nerfstudio":
-                capture = _capture_cameras(ap, args)
-                shared_pinhole(capture, command)  # one pinhole for all views is what the export kernels project through
-        except (FileNotFoundError, ValueError) as e:
+            pinhole = shared_pinhole(capture, command)  # one pinhole for all views is what the export kernels project through
+        except ValueError as e:
             ap.error(f"{command}: {e}")
-    if capture is not None:
-        if args.downscale < 1 or (args.max_views is not None and args.max_views < 1):
-            ap.error(f"{command}: --downscale and --max-views must be >= 1")
-        c2w = capture.c2w
-        if args.max_views is not None and args.max_views < len(c2w):
-            c2w = c2w[(np.arange(args.max_views, dtype=np.int64) * len(c2w)) // args.max_views]
-        width, height = max(1, capture.width // args.downscale), max(1, capture.height // args.downscale)
-        sx, sy = width / capture.width, height / capture.height
-        return {"c2w": np.ascontiguousarray(c2w), "width": int(width), "height": int(height), "fx": capture.fx * sx, "fy": capture.fy * sy,
-                "cx": capture.cx * sx, "cy": capture.cy * sy}
-    if args.poses is not None:
-        src = render.load_poses(args.poses, _scale_factor(args))
-    else:
-        src = render.load_poses(os.path.join(args.data, f"transforms_{args.split}.json"), _scale_factor(args))
-        if src["width"] is None or src["height"] is None:  # Blender-format files carry no size: the first image's header has it
-            rel = src["file_paths"][0] or ""
-            path = os.path.join(args.data, (rel[2:] if rel.startswith("./") else rel) + ".png")
-            if os.path.isfile(path):
-                from PIL import Image
-
-                with Image.open(path) as img:
-                    src["width"], src["height"] = (int(v) for v in img.size)
+        return _views_at_scale(ap, args, capture.c2w, capture.width, capture.height, *pinhole)
     for name in ("width", "height", "camera_angle_x"):
         if src[name] is None:
             ap.error(f"{command}: the cameras' {name} is unknown: the file needs camera_angle_x and w / h (or, with --data, a first image)")
+    return _views_at_scale(ap, args, src["c2w"], src["width"], src["height"], *render.pinhole(src["width"], src["height"], src["camera_angle_x"]))
+
+
+def _views_at_scale(ap: argparse.ArgumentParser, args, c2w, width, height, fx, fy, cx, cy) -> dict:
+    """--max-views N evenly spaced ones of the views, the first one among them, at 1/--downscale of their size with the intrinsics
+    scaled alike."""
     if args.downscale < 1 or (args.max_views is not None and args.max_views < 1):
-        ap.error(f"{command}: --downscale and --max-views must be >= 1")
-    c2w = src["c2w"]
-    if args.max_views is not None and args.max_views < len(c2w):  # N evenly spaced views, the first one among them
+        ap.error(f"{args.command}: --downscale and --max-views must be >= 1")
+    if args.max_views is not None and args.max_views < len(c2w):
         c2w = c2w[(np.arange(args.max_views, dtype=np.int64) * len(c2w)) // args.max_views]
-    fx, fy, cx, cy = render.pinhole(src["width"], src["height"], src["camera_angle_x"])
-    width, height = max(1, src["width"] // args.downscale), max(1, src["height"] // args.downscale)
-    sx, sy = width / src["width"], height / src["height"]
-    return {"c2w": np.ascontiguousarray(c2w), "width": int(width), "height": int(height), "fx": fx * sx, "fy": fy * sy,
-            "cx": cx * sx, "cy": cy * sy}
+    w, h = max(1, width // args.downscale), max(1, height // args.downscale)
+    sx, sy = w / width, h / height
+    return {"c2w": np.ascontiguousarray(c2w), "width": int(w), "height": int(h), "fx": fx * sx, "fy": fy * sy, "cx": cx * sx, "cy": cy * sy}
 
 
 def resolve_pointcloud_args(ap: argparse.ArgumentParser, args) -> dict:
@@ -749,8 +742,7 @@ def resolve_pointcloud_args(ap: argparse.ArgumentParser, args) -> dict:
     if math.isnan(args.min_accumulation):
         ap.error(f"export-pointcloud: --min-accumulation {args.min_accumulation}: need a number")
     b = args.bounds
-    if b is not None and not (all(math.isfinite(x) for x in b) and all(b[3 + a] > b[a] for a in range(3))):
-        ap.error("export-pointcloud: --bounds needs X0 Y0 Z0 X1 Y1 Z1 with every upper bound above its lower one")
+    _check_box(ap, args, "--bounds", b)
     if args.ray_chunk is not None and args.ray_chunk < 1:
         ap.error("export-pointcloud: --ray-chunk must be >= 1")
     if args.chunk is not None and args.chunk < 1:
@@ -764,20 +756,31 @@ def resolve_pointcloud_args(ap: argparse.ArgumentParser, args) -> dict:
 
 # ------------------------------------------------------------------------------------------------ train
 def _resolve_run_settings(given: dict, recorded: Optional[dict]):
-    """Each of rays / mma / seed / deterministic / max_grad_norm / skip_nonfinite / multiscale / distortion_loss / distortion_loss_coarse /
-    near / far / primary_spacing / primary_tan / depth_loss / depth_loss_coarse / depth_sigma / depth_euclidean:
-    the caller's value if given, else the checkpoint's, else the fresh-run default (deterministic: None = the model's own default; the
-    two guard settings and the two distortion coefficients: None = off; multiscale: 1, which a checkpoint does not record).
+    """Each entry of `given` (names of checkpoint.RUN_SETTINGS, any subset): the caller's value if given, else the checkpoint's, else the
+    table's fresh-run default (deterministic: None = the model's own default; the two guard settings and the coefficients of the opt-in
+    loss terms: None = off; multiscale: 1, which a checkpoint does not record).
     -> (settings, one line per given value that departs from the checkpoint's)."""
     out, notes = {}, []
     for k, v in given.items():
         rec = None if recorded is None else recorded.get(k)
         if v is None:
-            v = rec if rec is not None else RUN_DEFAULTS.get(k)
+            v = rec if rec is not None else RUN_SETTINGS[k].default
         elif rec is not None and v != rec:
             notes.append(f"train: {k} {v!r} given, the checkpoint's run had {rec!r}: using {v!r}; the continuation is not bit-exact")
         out[k] = v
     return out, notes
+
+
+def _loss_key(name: str) -> str:
+    """A coefficient's name in the model's config.loss_coefficients: the fine level's says so there."""
+    return name + "_fine" if name in COEFFICIENTS and not name.endswith("_coarse") else name
+
+
+def _settings_text(settings: dict) -> str:
+    """The settings of a run as the line that starts it shows them: the ones its checkpoints record (recorded_settings), a float that
+    is a setting of the optimiser or of a loss term in %g, everything else as it prints."""
+    return "".join(f" {_loss_key(k)} {v:g}" if isinstance(v, float) and k not in RAY_KEYS else f" {_loss_key(k)} {v}"
+                   for k, v in recorded_settings(settings).items())
 
 
 def _guard_log(stats: dict, skips_logged: int) -> str:
@@ -854,17 +857,14 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     (test_deterministic_gpu).  One value does travel between steps, only under the opt-in reflect_capacity = "auto": the reflected
     count that sizes the next step's reflect buffers.  It is not saved.  A resumed run starts with full-size buffers, which is
     the exact computation; it can differ from the uninterrupted run only on a step which that run truncated (and warned about)."""
+    given = {k: v for k, v in locals().items() if k in RUN_SETTINGS}  # the arguments that are run settings, in the signature's order
+    assert len(given) == len(RUN_SETTINGS)  # the signature spells out the table's names
     from .data import RayDataManager, pyramid_layout
     from .parallel import train_step
     from .train_ops import FusedRAdam
 
     if steps < 1:
         raise ValueError(f"steps must be >= 1, got {steps}")
-    given = {"rays": rays, "mma": mma, "seed": seed, "deterministic": deterministic, "max_grad_norm": max_grad_norm,
-             "skip_nonfinite": skip_nonfinite, "multiscale": multiscale, "distortion_loss": distortion_loss,
-             "distortion_loss_coarse": distortion_loss_coarse, "near": near, "far": far, "primary_spacing": primary_spacing,
-             "primary_tan": primary_tan, "depth_loss": depth_loss, "depth_loss_coarse": depth_loss_coarse, "depth_sigma": depth_sigma,
-             "depth_euclidean": depth_euclidean}
     first, model, ckpt, recorded = 0, None, None, None
     if resume is not None:  # host work only up to the ValueError: a run with nothing left to do never touches the device
         resume = resolve_checkpoint(resume)
@@ -886,17 +886,13 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         rays_cast["primary_tan"] = None
     if resume is not None:
         model, _ = _load_pipeline(resume, model_config, rays=rays_cast, ckpt=ckpt)
-    rays, mma, seed, deterministic = cfg["rays"], cfg["mma"], cfg["seed"], cfg["deterministic"]
-    max_grad_norm, skip_nonfinite, multiscale = cfg["max_grad_norm"], bool(cfg["skip_nonfinite"]), int(cfg["multiscale"])
-    distortion = {"distortion_loss_fine": cfg["distortion_loss"], "distortion_loss_coarse": cfg["distortion_loss_coarse"]}
-    for key, coef in distortion.items():
-        if coef is not None and not math.isfinite(float(coef)):
-            raise ValueError(f"{key} must be finite, got {coef!r}")
-    depth = {"depth_loss_fine": cfg["depth_loss"], "depth_loss_coarse": cfg["depth_loss_coarse"]}
-    for key, coef in depth.items():
-        if coef is not None and not math.isfinite(float(coef)):
-            raise ValueError(f"{key} must be finite, got {coef!r}")
-    depth_on = {key: float(coef) for key, coef in depth.items() if coef is not None and float(coef) != 0.0}
+    rays, mma, seed, multiscale = cfg["rays"], cfg["mma"], cfg["seed"], int(cfg["multiscale"])
+    for k in COEFFICIENTS:
+        if cfg[k] is not None and not math.isfinite(float(cfg[k])):
+            raise ValueError(f"{_loss_key(k)} must be finite, got {cfg[k]!r}")
+    # the coefficients that switch a term on, under their names in the model's config.loss_coefficients (train_graph.DIST_COEF_KEYS, DEPTH_COEF_KEYS)
+    terms_on = {_loss_key(k): float(cfg[k]) for k in COEFFICIENTS if cfg[k] is not None and float(cfg[k]) != 0.0}
+    depth_on = [_loss_key(k) for k in COEFFICIENTS if _loss_key(k) in terms_on and RUN_SETTINGS[k].term == "depth"]
     if cfg["depth_sigma"] is not None and not (math.isfinite(float(cfg["depth_sigma"])) and float(cfg["depth_sigma"]) > 0.0):
         raise ValueError(f"depth_sigma must be a positive finite number, got {cfg['depth_sigma']!r}")
     if depth_on and getattr(scene, "depths", None) is None:
@@ -915,13 +911,11 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
         set_primary_sampler(model, rays_cast["primary_spacing"], rays_cast["primary_tan"])
     model = model.to(dev).train()
     model.field.set_mma_mode(mma)
-    if deterministic is not None:
-        model.set_deterministic(deterministic)
-    on = {key: float(coef) for key, coef in distortion.items() if coef is not None and float(coef) != 0.0}
-    if on:  # (off: the dictionary stays as it is, without the keys.)  A copy: a model_config the caller shares between runs stays as it was
-        model.config.loss_coefficients = dict(model.config.loss_coefficients, **on)
+    if cfg["deterministic"] is not None:
+        model.set_deterministic(cfg["deterministic"])
+    if terms_on:  # (off: the dictionary stays as it is, without the keys.)  A copy: a model_config the caller shares between runs stays as it was
+        model.config.loss_coefficients = dict(model.config.loss_coefficients, **terms_on)
     if depth_on:
-        model.config.loss_coefficients = dict(model.config.loss_coefficients, **depth_on)
         if cfg["depth_sigma"] is not None:
             model.depth_sigma = float(cfg["depth_sigma"])
     elif getattr(scene, "depths", None) is not None:  # the term is off: no upload, no gather launch, the batches as they always were
@@ -932,24 +926,9 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
     params = model.get_param_groups()["fields"]
     name_of = {id(p): n for n, p in model.named_parameters()}
     optimizer = FusedRAdam(params, lr=1e-3, eps=1e-15, lr_final=1e-4, max_steps=50000,  # config.py:50-53
-                           max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, names=[name_of[id(p)] for p in params])
-    settings = f"steps {steps} rays {rays} mma {mma} seed {seed} deterministic {model.deterministic}"
-    if max_grad_norm is not None:
-        settings += f" max_grad_norm {max_grad_norm:g}"
-    if skip_nonfinite:
-        settings += " skip_nonfinite True"
-    if multiscale > 1:
-        settings += f" multiscale {multiscale}"
-    for key, coef in distortion.items():
-        if coef is not None and float(coef) != 0.0:
-            settings += f" {key} {float(coef):g}"
-    for key, coef in depth_on.items():
-        settings += f" {key} {coef:g}"
-    if depth_on:
-        settings += f" depth_sigma {float(model.depth_sigma):g}" + (" depth_euclidean True" if cfg["depth_euclidean"] else "")
-    for k in RAY_KEYS:
-        if rays_cast[k] is not None:
-            settings += f" {k} {rays_cast[k]}"
+                           max_grad_norm=cfg["max_grad_norm"], skip_nonfinite=bool(cfg["skip_nonfinite"]), names=[name_of[id(p)] for p in params])
+    run_settings = {**cfg, **rays_cast, "deterministic": model.deterministic}  # what the run goes by: what its checkpoints record
+    settings = f"steps {steps}" + _settings_text(dict(run_settings, depth_sigma=model.depth_sigma))
     data_record = None
     if data_settings is not None:
         data_record = dict(data_settings)
@@ -992,11 +971,7 @@ def train(scene, out_dir: str, steps: int = 100000, rays: Optional[int] = None, 
             log(line)
         if (save_every and step > 0 and step % save_every == 0) or step == steps - 1:
             last = save_checkpoint(checkpoint_path(out_dir, step), model, optimizer, step,
-                                   make_run_state(seed, rays, mma, model.deterministic, dev, max_grad_norm, skip_nonfinite, multiscale,
-                                                  distortion["distortion_loss_fine"], distortion["distortion_loss_coarse"],
-                                                  rays_and_data={**rays_cast, "data": data_record},
-                                                  depth={"depth_loss": depth["depth_loss_fine"], "depth_loss_coarse": depth["depth_loss_coarse"],
-                                                         "depth_sigma": cfg["depth_sigma"], "depth_euclidean": cfg["depth_euclidean"]}))
+                                   make_run_state(device=dev, data=data_record, **run_settings))
             if log is not None:
                 log(f"saved {last}")
     return last
@@ -1116,8 +1091,7 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
     ckpt, model, step = open_checkpoint(ckpt, model_config, dev)
     model.config.eval_num_rays_per_chunk = EVAL_CHUNK
     dm = RayDataManager(scene, dev, levels=multiscale, live_lists=False, depth_euclidean=depth_euclidean)
-    masked = []  # (entry of per_image, device scalar)
-    depth_scores = []  # (entry of per_image, device [3]: mae, rmse, valid share)
+    masked, depth_scores = [], []  # (entry of per_image, device [K]) pairs: the live pixels' PSNR (K = 1) and DEPTH_KEYS' three figures
     n = scene.num_images if max_images is None else min(int(max_images), scene.num_images)
     if occupancy is not None:
         from .occupancy import attach_occupancy
@@ -1152,23 +1126,23 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
         if dm.masks is not None and level == 0:
             live = dm.mask_image(i).to(torch.float32).unsqueeze(-1)
             err = ((torch.clip(outputs["mid_reflect_fine"], 0.0, 1.0) - _white(gt)) ** 2 * live).sum() / (3.0 * live.sum())  # 0 / 0 = nan
-            masked.append((per_image[-1], 10.0 * torch.log10(1.0 / err.clamp(min=1e-12))))
+            masked.append((per_image[-1], (10.0 * torch.log10(1.0 / err.clamp(min=1e-12))).reshape(1)))
         if save_images:
             from PIL import Image
 
             panel = (images["img"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
             name = f"{i:04d}_img.png" if level == 0 else f"{i:04d}_x{1 << level}_img.png"
             Image.fromarray(panel).save(os.path.join(save_images, name))
-    if masked:
-        for (entry, _), v in zip(masked, torch.stack([v for _, v in masked]).cpu().tolist()):  # the one read of the masked scores
-            entry["psnr_masked"] = float(v)
-    if depth_scores:
-        for (entry, _), v in zip(depth_scores, torch.stack([v for _, v in depth_scores]).cpu().tolist()):  # the one read of the depth scores
-            entry.update({k: float(x) for k, x in zip(DEPTH_KEYS, v)})
+    for scores, names in ((masked, ("psnr_masked",)), (depth_scores, DEPTH_KEYS)):
+        if scores:
+            for (entry, _), v in zip(scores, torch.stack([v for _, v in scores]).cpu().tolist()):  # the one read of these scores
+                entry.update({k: float(x) for k, x in zip(names, v)})
     keys = [k for k in per_image[0] if k not in ("image", "level", "psnr_masked") + GEOMETRY_KEYS + DEPTH_KEYS] if per_image else []
 
     def mean_std(v):
         v = np.asarray(v, dtype=np.float64)
+        if not len(v):  # no view had a value to count
+            return float("nan"), float("nan")
         return float(v.mean()), float(v.std(ddof=1)) if len(v) > 1 else 0.0  # torch.std_mean (ns-eval): unbiased
 
     results = {}
@@ -1182,18 +1156,18 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
             results[f"{k}_x{1 << level}"], results[f"{k}_x{1 << level}_std"] = m, sd
     if masked:
         counted = [p["psnr_masked"] for p, _ in masked if not math.isnan(p["psnr_masked"])]
-        results["psnr_masked"], results["psnr_masked_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
+        results["psnr_masked"], results["psnr_masked_std"] = mean_std(counted)
     if normals:
         scored = [p for p in per_image if "normal_mae" in p]
         counted = [p["normal_mae"] for p in scored if not math.isnan(p["normal_mae"])]
-        results["normal_mae"], results["normal_mae_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
+        results["normal_mae"], results["normal_mae_std"] = mean_std(counted)
         results["normal_mae_views"] = len(counted)
-        results["alpha_mae"], results["alpha_mae_std"] = mean_std([p["alpha_mae"] for p in scored]) if scored else (float("nan"), float("nan"))
+        results["alpha_mae"], results["alpha_mae_std"] = mean_std([p["alpha_mae"] for p in scored])
     if depth:
         scored = [p for p, _ in depth_scores]
         for k in ("depth_mae", "depth_rmse"):
             counted = [p[k] for p in scored if not math.isnan(p[k])]
-            results[k], results[k + "_std"] = mean_std(counted) if counted else (float("nan"), float("nan"))
+            results[k], results[k + "_std"] = mean_std(counted)
         results["depth_valid"] = float(np.mean([p["depth_valid"] for p in scored])) if scored else float("nan")
     res = {"experiment_name": os.path.basename(os.path.dirname(os.path.abspath(ckpt))), "method_name": METHOD_NAME,
            "checkpoint": ckpt, "step": step, "results": results, "not_computed": {"fine_lpips": LPIPS_NOTE},
@@ -1210,124 +1184,135 @@ def evaluate(scene, ckpt: str, max_images: Optional[int] = None, save_images: Op
 
 
 # ------------------------------------------------------------------------------------------------ CLI
-def main(argv=None) -> int:
-    ap = build_parser()
-    args = ap.parse_args(argv)
-    given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
-    cameras = resolve_render_args(ap, args) if args.command == "render" else None  # a command line that cannot work ends here
-    occupancy = resolve_occupancy_args(ap, args) if args.command in ("render", "eval") else None
-    if args.command == "export-mesh":
-        resolve_texture_args(ap, args)
-        decimate_args = resolve_decimate_args(ap, args)
-    export_cameras = resolve_export_cameras(ap, args) if args.command == "export-mesh" else None
-    cloud_args = resolve_pointcloud_args(ap, args) if args.command == "export-pointcloud" else None
-    if args.command == "train" and args.primary_tan is not None and not args.primary_tan > 0.0:
-        ap.error(f"train: --primary-tan {args.primary_tan}: need a value above 0")
-    if args.command == "train" and args.max_grad_norm is not None and not args.max_grad_norm > 0.0:
-        ap.error(f"train: --max-grad-norm {args.max_grad_norm}: need a value above 0")
-    if args.command == "eval" and not args.depth:
-        stray = [f for f, v in (("--depth-unit-scale", args.depth_unit_scale), ("--depth-euclidean", args.depth_euclidean)) if v is not None]
-        if stray:
-            ap.error(f"eval: {' '.join(stray)} need(s) --depth")
-    if args.command == "eval" and args.normals and args.depth:
-        ap.error("eval: --normals scores a Blender-format scene and --depth a nerfstudio-format capture; give one of them")
-    if args.command == "eval" and not args.normals:
-        stray = [f for f, v in (("--normals-suffix", args.normals_suffix), ("--normals-space", args.normals_space)) if v is not None]
-        if stray:
-            ap.error(f"eval: {' '.join(stray)} need(s) --normals")
-    if args.command in ("train", "eval") and not 1 <= args.multiscale <= 5:
+# Per command: `_check_*` holds what the command line alone (and host-side file headers) can rule out, and returns what it resolved
+# on the way; `_run_*` is the command itself, on a machine with a GPU.
+def _check_train(ap: argparse.ArgumentParser, args):
+    for flag, v in (("--primary-tan", args.primary_tan), ("--max-grad-norm", args.max_grad_norm)):
+        if v is not None and not v > 0.0:
+            ap.error(f"train: {flag} {v}: need a value above 0")
+    _check_multiscale(ap, args)
+
+
+def _check_multiscale(ap: argparse.ArgumentParser, args) -> None:
+    if not 1 <= args.multiscale <= 5:
         ap.error(f"{args.command}: --multiscale {args.multiscale}: need 1 to 5")
-    if not torch.cuda.is_available():
-        print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
-        return 2
-    if args.command == "train":
-        resumed = read_run_state(args.resume) if args.resume is not None else None
-        depth_flags = [f for f, v in (("--depth-loss", args.depth_loss), ("--depth-loss-coarse", args.depth_loss_coarse)) if v]
-        stray = [f for f, v in (("--depth-sigma", args.depth_sigma), ("--depth-unit-scale", args.depth_unit_scale),
-                                ("--depth-euclidean", args.depth_euclidean)) if v is not None]
-        want_depth = bool(depth_flags) or any((resumed or {}).get(k) for k in ("depth_loss", "depth_loss_coarse"))
-        if stray and not want_depth:
-            ap.error(f"train: {' '.join(stray)} need(s) --depth-loss or --depth-loss-coarse")
-        if args.depth_sigma is not None and not args.depth_sigma > 0.0:
-            ap.error(f"train: --depth-sigma {args.depth_sigma}: need a value above 0")
-        scene, data_settings = load_scene(ap, args, "train", resumed, depths=want_depth)
-        if want_depth and scene.depths is None:
-            ap.error(f"train: {' '.join(depth_flags) or 'the resumed run'} needs depth maps, and no frame of {args.data} has a depth_file_path")
-        print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}"
-              + ("" if scene.cameras is None else f" (image 0; a capture with {len(np.unique(scene.cameras, axis=0))} distinct camera(s), "
-                                                  f"{int(np.any(scene.cameras[:, 4:] != 0.0, axis=1).sum())} image(s) with lens distortion)"))
-        if args.multiscale > 1:  # a resumed run's own level count is checked by train()
-            from .data import pyramid_layout
 
-            try:
-                pyramid_layout(scene.num_images, scene.height, scene.width, args.multiscale)
-            except ValueError as e:
-                ap.error(f"train: --multiscale {args.multiscale}: {e}")
-        train(scene, args.out, steps=args.steps, rays=given.rays, mma=given.mma, save_every=args.save_every,
-              log_every=args.log_every, seed=given.seed, deterministic=True if args.deterministic else None, resume=args.resume,
-              max_grad_norm=args.max_grad_norm, skip_nonfinite=True if args.skip_nonfinite else None, multiscale=given.multiscale,
-              distortion_loss=args.distortion_loss, distortion_loss_coarse=args.distortion_loss_coarse, near=args.near, far=args.far,
-              primary_spacing=args.primary_spacing, primary_tan=args.primary_tan, data_settings=data_settings,
-              depth_loss=args.depth_loss, depth_loss_coarse=args.depth_loss_coarse, depth_sigma=args.depth_sigma,
-              depth_euclidean=args.depth_euclidean)
-        return 0
-    if args.command == "export-mesh":
-        from . import mesh
 
-        common = dict(resolution=args.resolution, bounds=mesh.DEFAULT_BOUNDS if args.bounds is None else tuple(args.bounds),
-                      mma=args.mma, chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
-        if args.texture:
-            common.update(texture=True, texels=8 if args.texels is None else args.texels, min_footprint=args.min_footprint)
-        common.update(decimate_args)
-        if args.method == "tsdf":
-            res = mesh.export_mesh(args.ckpt, args.out, method="tsdf", cameras=export_cameras, trunc=args.trunc,
-                                   min_weight=mesh.DEFAULT_MIN_WEIGHT if args.min_weight is None else args.min_weight,
-                                   ray_chunk=mesh.DEFAULT_RAY_CHUNK if args.ray_chunk is None else args.ray_chunk, **common)
-            what = (f"of {res['views']} depth maps {res['image'][0]} x {res['image'][1]} fused at truncation {res['trunc']:g} "
-                    f"({res['triangles_extracted']} triangles before the filter)")
-            stages = ("depth", "integrate", "count", "emit", "filter", "attributes", "write")
-        else:
-            res = mesh.export_mesh(args.ckpt, args.out, iso=mesh.DEFAULT_ISO if args.iso is None else args.iso, **common)
-            what = f"at sigma = {res['iso']:g}"
-            stages = ("grid", "count", "emit", "attributes", "write")
-        sec = res["seconds"]
-        if decimate_args:
-            d = res["decimate"]
-            stages = stages[:stages.index("attributes")] + ("decimate",) + stages[stages.index("attributes"):]
-            what += (f", clustered from {d['triangles_in']} triangles with {' x '.join(str(n) for n in d['cells'])} cells "
-                     f"({d['degenerate']} collapsed, {d['cancelled_pairs']} opposite pairs cancelled"
-                     + (f", {len(d['probes'])} probes for at most {d['target_faces']}" + (": NOT reached" if d["over_budget"] else "")
-                        if "probes" in d else "") + ")")
-        if args.texture:
-            stages = stages[:-1] + ("atlas", "bake", "write")
-            what += (f", textured with {res['texture_size']} x {res['texture_size']} texels ({res['live_texels']} live, "
-                     f"{res['texels']} per square side, footprint >= {res['min_footprint']:g})")
-        print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles {what} "
-              f"on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
-              " ".join(f"{k} {sec[k]:.3f} s" for k in stages) + f" -> {res['out']}")
-        return 0
-    if args.command == "export-pointcloud":
-        from . import pointcloud
+def _run_train(ap: argparse.ArgumentParser, args, given, _) -> None:
+    resumed = read_run_state(args.resume) if args.resume is not None else None
+    depth_coefficients = [k for k in COEFFICIENTS if RUN_SETTINGS[k].term == "depth"]
+    depth_flags = ["--" + k.replace("_", "-") for k in depth_coefficients if getattr(args, k)]
+    want_depth = bool(depth_flags) or any((resumed or {}).get(k) for k in depth_coefficients)
+    if not want_depth:
+        _flags_need(ap, args, ("depth_sigma", "depth_unit_scale", "depth_euclidean"), "--depth-loss or --depth-loss-coarse")
+    if args.depth_sigma is not None and not args.depth_sigma > 0.0:
+        ap.error(f"train: --depth-sigma {args.depth_sigma}: need a value above 0")
+    scene, data_settings = load_scene(ap, args, "train", resumed, depths=want_depth)
+    if want_depth and scene.depths is None:
+        ap.error(f"train: {' '.join(depth_flags) or 'the resumed run'} needs depth maps, and no frame of {args.data} has a depth_file_path")
+    print(f"{args.data}: {scene.num_images} train images {scene.width} x {scene.height}, focal {scene.fx:.3f}"
+          + ("" if scene.cameras is None else f" (image 0; a capture with {len(np.unique(scene.cameras, axis=0))} distinct camera(s), "
+                                              f"{int(np.any(scene.cameras[:, 4:] != 0.0, axis=1).sum())} image(s) with lens distortion)"))
+    if args.multiscale > 1:  # a resumed run's own level count is checked by train()
+        from .data import pyramid_layout
 
-        res = pointcloud.export_pointcloud(args.ckpt, args.out, cloud_args.pop("cameras"), mma=args.mma, **cloud_args)
-        sec = res["seconds"]
-        print(f"{res['checkpoint']} (step {res['step']}): a grid of {' x '.join(str(n) for n in res['resolution'])} cells, "
-              f"accumulation >= {res['min_accumulation']:g}, edge {res['edge']:g}, {'one point per cell' if res['thin'] else 'every candidate'}; " +
-              " ".join(f"{k} {sec[k]:.3f} s" for k in ("depth", "mark", "select", "attributes", "write")))
-        print(f"{res['points']} points from {res['views']} depth maps {res['image'][0]} x {res['image'][1]} "
-              f"({res['candidates']} candidates) -> {res['out']}")
-        return 0
-    if args.command == "render":
-        from . import render
+        try:
+            pyramid_layout(scene.num_images, scene.height, scene.width, args.multiscale)
+        except ValueError as e:
+            ap.error(f"train: --multiscale {args.multiscale}: {e}")
+    # every run setting as the user typed it, None where nothing was typed (`given`: the parse without the run defaults; a switch
+    # that is off was not typed): a resumed run's checkpoint decides those
+    typed = {k: None if getattr(given, k) is False else getattr(given, k) for k in RUN_SETTINGS}
+    train(scene, args.out, steps=args.steps, save_every=args.save_every, log_every=args.log_every, resume=args.resume,
+          data_settings=data_settings, **typed)
 
-        res = render.render_checkpoint(args.ckpt, args.out, *render.camera_args(cameras), camera_table=cameras.get("camera_table"),
-                                       channels=args.channels,
-                                       depth_range=None if args.depth_range is None else tuple(args.depth_range), mma=args.mma,
-                                       chunk=args.chunk, tiles=args.tiles, occupancy=occupancy)
-        n, sec = len(res["frames"]), res["seconds"]
-        print(f"{res['checkpoint']} (step {res['step']}): {n} frames {res['width']} x {res['height']} of {' '.join(res['channels'])}; "
-              f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
-        return 0
+
+def _check_export_mesh(ap: argparse.ArgumentParser, args):
+    resolve_texture_args(ap, args)
+    decimate_args = resolve_decimate_args(ap, args)
+    return decimate_args, resolve_export_cameras(ap, args)
+
+
+def _run_export_mesh(ap: argparse.ArgumentParser, args, given, resolved) -> None:
+    from . import mesh
+
+    decimate_args, export_cameras = resolved
+    common = dict(resolution=args.resolution, bounds=mesh.DEFAULT_BOUNDS if args.bounds is None else tuple(args.bounds),
+                  mma=args.mma, chunk=mesh.DEFAULT_CHUNK if args.chunk is None else args.chunk)
+    if args.texture:
+        common.update(texture=True, texels=8 if args.texels is None else args.texels, min_footprint=args.min_footprint)
+    common.update(decimate_args)
+    if args.method == "tsdf":
+        res = mesh.export_mesh(args.ckpt, args.out, method="tsdf", cameras=export_cameras, trunc=args.trunc,
+                               min_weight=mesh.DEFAULT_MIN_WEIGHT if args.min_weight is None else args.min_weight,
+                               ray_chunk=mesh.DEFAULT_RAY_CHUNK if args.ray_chunk is None else args.ray_chunk, **common)
+        what = (f"of {res['views']} depth maps {res['image'][0]} x {res['image'][1]} fused at truncation {res['trunc']:g} "
+                f"({res['triangles_extracted']} triangles before the filter)")
+        stages = ("depth", "integrate", "count", "emit", "filter", "attributes", "write")
+    else:
+        res = mesh.export_mesh(args.ckpt, args.out, iso=mesh.DEFAULT_ISO if args.iso is None else args.iso, **common)
+        what = f"at sigma = {res['iso']:g}"
+        stages = ("grid", "count", "emit", "attributes", "write")
+    sec = res["seconds"]
+    if decimate_args:
+        d = res["decimate"]
+        stages = stages[:stages.index("attributes")] + ("decimate",) + stages[stages.index("attributes"):]
+        what += (f", clustered from {d['triangles_in']} triangles with {' x '.join(str(n) for n in d['cells'])} cells "
+                 f"({d['degenerate']} collapsed, {d['cancelled_pairs']} opposite pairs cancelled"
+                 + (f", {len(d['probes'])} probes for at most {d['target_faces']}" + (": NOT reached" if d["over_budget"] else "")
+                    if "probes" in d else "") + ")")
+    if args.texture:
+        stages = stages[:-1] + ("atlas", "bake", "write")
+        what += (f", textured with {res['texture_size']} x {res['texture_size']} texels ({res['live_texels']} live, "
+                 f"{res['texels']} per square side, footprint >= {res['min_footprint']:g})")
+    print(f"{res['checkpoint']} (step {res['step']}): {res['vertices']} vertices, {res['triangles']} triangles {what} "
+          f"on a {' x '.join(str(n) for n in res['resolution'])} grid; " +
+          " ".join(f"{k} {sec[k]:.3f} s" for k in stages) + f" -> {res['out']}")
+
+
+def _run_export_pointcloud(ap: argparse.ArgumentParser, args, given, cloud_args) -> None:
+    from . import pointcloud
+
+    res = pointcloud.export_pointcloud(args.ckpt, args.out, cloud_args.pop("cameras"), mma=args.mma, **cloud_args)
+    sec = res["seconds"]
+    print(f"{res['checkpoint']} (step {res['step']}): a grid of {' x '.join(str(n) for n in res['resolution'])} cells, "
+          f"accumulation >= {res['min_accumulation']:g}, edge {res['edge']:g}, {'one point per cell' if res['thin'] else 'every candidate'}; " +
+          " ".join(f"{k} {sec[k]:.3f} s" for k in ("depth", "mark", "select", "attributes", "write")))
+    print(f"{res['points']} points from {res['views']} depth maps {res['image'][0]} x {res['image'][1]} "
+          f"({res['candidates']} candidates) -> {res['out']}")
+
+
+def _check_render(ap: argparse.ArgumentParser, args):
+    cameras = resolve_render_args(ap, args)
+    return cameras, resolve_occupancy_args(ap, args)
+
+
+def _run_render(ap: argparse.ArgumentParser, args, given, resolved) -> None:
+    from . import render
+
+    cameras, occupancy = resolved
+    res = render.render_checkpoint(args.ckpt, args.out, *render.camera_args(cameras), camera_table=cameras.get("camera_table"),
+                                   channels=args.channels,
+                                   depth_range=None if args.depth_range is None else tuple(args.depth_range), mma=args.mma,
+                                   chunk=args.chunk, tiles=args.tiles, occupancy=occupancy)
+    n, sec = len(res["frames"]), res["seconds"]
+    print(f"{res['checkpoint']} (step {res['step']}): {n} frames {res['width']} x {res['height']} of {' '.join(res['channels'])}; "
+          f"{sec / max(n, 1):.3f} s per frame, {n * res['width'] * res['height'] / max(sec, 1e-9):.0f} rays/s -> {res['out']}")
+
+
+def _check_eval(ap: argparse.ArgumentParser, args):
+    occupancy = resolve_occupancy_args(ap, args)
+    if not args.depth:
+        _flags_need(ap, args, ("depth_unit_scale", "depth_euclidean"), "--depth")
+    if args.normals and args.depth:
+        ap.error("eval: --normals scores a Blender-format scene and --depth a nerfstudio-format capture; give one of them")
+    if not args.normals:
+        _flags_need(ap, args, ("normals_suffix", "normals_space"), "--normals")
+    _check_multiscale(ap, args)
+    return occupancy
+
+
+def _run_eval(ap: argparse.ArgumentParser, args, given, occupancy) -> None:
     try:
         recorded = read_run_state(args.ckpt)
     except (FileNotFoundError, NotADirectoryError) as e:
@@ -1361,6 +1346,22 @@ def main(argv=None) -> int:
         print(f"normal_mae {r['normal_mae']:.3f} deg over {r['normal_mae_views']} views, alpha_mae {r['alpha_mae']:.4f}")
     if args.depth:
         print(f"depth_mae {r['depth_mae']:.5f} depth_rmse {r['depth_rmse']:.5f} over {100.0 * r['depth_valid']:.1f} % of the pixels")
+
+
+COMMANDS = {"train": (_check_train, _run_train), "eval": (_check_eval, _run_eval), "export-mesh": (_check_export_mesh, _run_export_mesh),
+            "export-pointcloud": (resolve_pointcloud_args, _run_export_pointcloud), "render": (_check_render, _run_render)}
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    given = build_parser(run_defaults=False).parse_args(argv)  # None where the user typed nothing: a resumed run's checkpoint decides
+    check, run = COMMANDS[args.command]
+    resolved = check(ap, args)  # a command line that cannot work ends here
+    if not torch.cuda.is_available():
+        print("reflect_sampling_nerf_amd.trainer needs a GPU (the HIP kernels have no CPU path)", file=sys.stderr)
+        return 2
+    run(ap, args, given, resolved)
     return 0
 
 

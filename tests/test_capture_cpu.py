@@ -281,10 +281,10 @@ def test_run_state_round_trip_of_the_new_keys_and_none_for_a_blender_run(tmp_pat
     opt = pkg.FusedRAdam(model.get_param_groups()["fields"], lr=1e-3, eps=1e-15)
     plain = checkpoint.make_run_state(0, 1024, "f32", False, "cpu")
     assert not set(NEW_KEYS) & set(plain)
-    assert checkpoint.make_run_state(0, 1024, "f32", False, "cpu", rays_and_data=dict.fromkeys(NEW_KEYS)) .keys() == plain.keys()
+    assert checkpoint.make_run_state(0, 1024, "f32", False, "cpu", **dict.fromkeys(NEW_KEYS)) .keys() == plain.keys()
     record = {"format": "nerfstudio", **trainer.CAPTURE_DATA_DEFAULTS, "transform": np.eye(4)[:3].tolist(), "scale": 0.25}
     rays = {"near": 0.5, "far": 1.5, "primary_spacing": "reciprocal", "primary_tan": 2.0}
-    state = checkpoint.make_run_state(0, 1024, "f32", False, "cpu", rays_and_data={**rays, "data": record})
+    state = checkpoint.make_run_state(0, 1024, "f32", False, "cpu", **{**rays, "data": record})
     path = trainer.save_checkpoint(trainer.checkpoint_path(str(tmp_path / "run"), 7), model, opt, 7, state)
     back = checkpoint.read_run_state(str(tmp_path / "run"))
     assert {k: back[k] for k in rays} == rays and back["data"] == record
@@ -331,7 +331,7 @@ def test_render_and_export_cameras_of_a_capture_come_from_the_file_and_the_check
     opt = pkg.FusedRAdam(model.get_param_groups()["fields"], lr=1e-3, eps=1e-15)
     run = str(tmp_path / "run")
     trainer.save_checkpoint(trainer.checkpoint_path(run, 3), model, opt, 3,
-                            checkpoint.make_run_state(0, 1024, "f32", False, "cpu", rays_and_data={"data": record}))
+                            checkpoint.make_run_state(0, 1024, "f32", False, "cpu", **{"data": record}))
     ap = trainer.build_parser()
     cams = trainer.resolve_render_args(ap, ap.parse_args(["render", "--ckpt", run, "--out", "o", "--data", root]))
     # the file's frames (every one: the run's eval_mode) in the run's frame, through their own cameras

@@ -428,16 +428,16 @@ def test_parser_flags_and_defaults(capsys):
 def test_run_state_records_the_settings_only_when_set():
     plain = trainer.make_run_state(0, 1024, "f32", False, "cpu")
     none = dict(depth_loss=None, depth_loss_coarse=None, depth_sigma=None, depth_euclidean=None)
-    assert set(trainer.make_run_state(0, 1024, "f32", False, "cpu", depth=none)) == set(plain)
-    assert set(trainer.make_run_state(0, 1024, "f32", False, "cpu", depth=dict(none, depth_loss=0.0, depth_sigma=0.2))) == set(plain)
-    fine = trainer.make_run_state(0, 1024, "f32", False, "cpu", depth=dict(none, depth_loss=0.01))
+    assert set(trainer.make_run_state(0, 1024, "f32", False, "cpu", **none)) == set(plain)
+    assert set(trainer.make_run_state(0, 1024, "f32", False, "cpu", **dict(none, depth_loss=0.0, depth_sigma=0.2))) == set(plain)
+    fine = trainer.make_run_state(0, 1024, "f32", False, "cpu", **dict(none, depth_loss=0.01))
     assert set(fine) - set(plain) == {"depth_loss"} and fine["depth_loss"] == 0.01 and fine["version"] == 1
-    full = trainer.make_run_state(0, 1024, "f32", False, "cpu", depth=dict(depth_loss=0.01, depth_loss_coarse=0.002, depth_sigma=0.05,
+    full = trainer.make_run_state(0, 1024, "f32", False, "cpu", **dict(depth_loss=0.01, depth_loss_coarse=0.002, depth_sigma=0.05,
                                                                          depth_euclidean=True))
     assert set(full) - set(plain) == {"depth_loss", "depth_loss_coarse", "depth_sigma", "depth_euclidean"}
     assert (full["depth_loss_coarse"], full["depth_sigma"], full["depth_euclidean"]) == (0.002, 0.05, True)
     with pytest.raises(KeyError):
-        trainer.make_run_state(0, 1024, "f32", False, "cpu", depth={"depth": 1})
+        trainer.make_run_state(0, 1024, "f32", False, "cpu", **{"depth": 1})
     cfg, notes = trainer._resolve_run_settings(none, {"depth_loss": 0.01, "depth_sigma": 0.05})
     assert cfg == dict(none, depth_loss=0.01, depth_sigma=0.05) and notes == []   # recorded, not given: restored
 

@@ -266,8 +266,8 @@ def test_parser_refuses_a_zero_downscale_factor_and_the_checkpoint_round_trips_t
     import torch
 
     state = checkpoint.make_run_state(0, 64, "f32", False, torch.device("cpu"),
-                                      rays_and_data={"data": {"format": "nerfstudio", **trainer.CAPTURE_DATA_DEFAULTS, "downscale_factor": 2,
-                                                              "transform": np.eye(4)[:3].tolist(), "scale": 0.5}})
+                                      **{"data": {"format": "nerfstudio", **trainer.CAPTURE_DATA_DEFAULTS, "downscale_factor": 2,
+                                                  "transform": np.eye(4)[:3].tolist(), "scale": 0.5}})
     path = str(tmp_path / "step-000000000.ckpt")
     torch.save({checkpoint.RUN_STATE_KEY: state, "step": 0}, path)
     rec = checkpoint.read_run_state(path)

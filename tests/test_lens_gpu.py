@@ -382,7 +382,7 @@ def run_end_to_end(root, rows, masks, out_dir, steps=None):
     init = trainer.make_model(checkpoint.config_with_planes(_cfg(), 0.5, 1.5), seed=0)
     opt0 = pkg.FusedRAdam(init.get_param_groups()["fields"], lr=1e-3, eps=1e-15)
     ck0 = trainer.save_checkpoint(trainer.checkpoint_path(os.path.join(out_dir, "init"), 0), init, opt0, 0,
-                                  checkpoint.make_run_state(0, 1024, "f32", False, DEV, rays_and_data={"near": 0.5, "far": 1.5}))
+                                  checkpoint.make_run_state(0, 1024, "f32", False, DEV, **{"near": 0.5, "far": 1.5}))
     before = trainer.evaluate(held_out, ck0, device=DEV, model_config=_cfg())
     after = trainer.evaluate(held_out, run, device=DEV, model_config=_cfg())
     assert after["checkpoint"] == ck and len(after["per_image"]) == 2
